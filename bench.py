@@ -8,7 +8,10 @@ Workload at N=1: BASELINE.json configs[1] = cfg-B (5,000 nodes / 50,000 directed
 steps, fp32).  Each rank owns one graph (graphs shard by sequence; weak scaling); `value` is
 sum_ranks(E) * K / max_rank(time).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--mode fwd|train] [--config B] [--agg sum]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--mode fwd|train] [--config B] [--agg sum] [--full] [--dump-outputs DIR]
+A plain run sets up, warms up, times the K steps and prints the line; --full adds everything else the line can carry (per-kernel
+rooflines from dispatch-attached events, steady-state graph prep, CPU baseline, forward rate, the other fp32 mode, the all-reduce alone,
+the other BASELINE.json configurations).  --dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy.
 N>1: either the driver's launcher form  python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...  (ranks read
 RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* from the env), or plain  python bench.py --gpus N ...  -- with no WORLD_SIZE in the env the
 parent starts the N ranks itself as fresh child processes (spawn_ranks) before it touches the GPU, and rank 0 prints the ONE line.
@@ -54,7 +57,34 @@ def parse():
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-extras", action="store_true",
                     help="skip the short labelled measurements of the other BASELINE.json configurations appended to the default line")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need (rooflines, steady-state graph prep, CPU baseline, forward rate, "
+                         "the other fp32 mode, the all-reduce alone, other configurations); the --no-* options switch parts of it off")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed (logits; in training also the loss, the gradients and "
+                         "the updated parameters) as DIR/<name>.npy, float32, at most 64 MB in all")
     return ap.parse_args()
+
+
+DUMP_LIMIT_BYTES = 64 * 1000 * 1000 - 64 * 1024   # (room for the .npy headers)
+
+
+def dump_outputs(dirname, arrays):
+    """arrays: name -> tensor.  Written as float32 (float64 stays float64); if they exceed DUMP_LIMIT_BYTES together, each is cut to
+    its share of the limit by a fixed, seeded sample of its flattened elements (sorted indices, seed 0: the same for every run)."""
+    os.makedirs(dirname, exist_ok=True)
+    host = {}
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
+        host[name] = np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)
+    total = sum(a.nbytes for a in host.values())
+    for name, a in host.items():
+        if total > DUMP_LIMIT_BYTES:
+            keep = int(DUMP_LIMIT_BYTES * (a.nbytes / total)) // a.itemsize
+            if a.size > keep:
+                idx = np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))
+                a = a.reshape(-1)[idx]
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 def usable_cores():
@@ -406,16 +436,18 @@ def main():
     _prepared(ei, N, holder)
     torch.cuda.synchronize()
     prep_ms = (time.perf_counter() - t0) * 1e3
-    # what a loop that sees a NEW graph every step pays per step (the first call above includes allocations and
-    # rocPRIM's one-time set-up): steady-state prep of the same edge list, not cached
-    for _ in range(2):
-        capi.PreparedGraph(ei, N)
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(10):
-        capi.PreparedGraph(ei, N)
-    torch.cuda.synchronize()
-    prep_steady_ms = (time.perf_counter() - t0) * 1e3 / 10
+    prep_steady_ms = None
+    if args.full:
+        # what a loop that sees a NEW graph every step pays per step (the first call above includes allocations and
+        # rocPRIM's one-time set-up): steady-state prep of the same edge list, not cached
+        for _ in range(2):
+            capi.PreparedGraph(ei, N)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(10):
+            capi.PreparedGraph(ei, N)
+        torch.cuda.synchronize()
+        prep_steady_ms = (time.perf_counter() - t0) * 1e3 / 10
 
     if mode == "fwd":
         model.eval()
@@ -433,7 +465,7 @@ def main():
     lib = capi.load()
     for _ in range(args.warmup):
         step()
-    profiled = rank == 0 and not args.no_roofline
+    profiled = rank == 0 and args.full and not args.no_roofline
     if profiled:
         # HIP events attached to every 7th launch of each profiled kernel kind (7: coprime with the 12 chain launches and the 3
         # differently-sized weight-gradient launches of a step, so every position of a step is sampled); large graphs (cfg-E: ~10
@@ -445,11 +477,19 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        last = step()
     torch.cuda.synchronize()
     barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        # what the caller of the timed step receives from its last call: the logits and, in training, the loss (total then per
+        # step), the gradients and the parameters after the optimizer step (the flat buffers, in hot_path_parameters() order)
+        outs = {"logits": last}
+        if mode == "train":
+            outs.update(loss=stepper.last_loss, grads=stepper.bucket.flat[:stepper.bucket.n],
+                        params=stepper.bucket.flat_params[:stepper.bucket.n])
+        dump_outputs(args.dump_outputs, outs)
     prof = None
     counts = capi.path_counters(reset=True)
     if profiled:
@@ -503,15 +543,17 @@ def main():
                                   "graphs sharded 1 per GPU (dp%d)" % world if args.backend == "nccl" or world == 1 else
                                   "dp%d over gloo, %d ranks per GPU (functional run of the N > 1 path, not a scaling number)"
                                   % (world, (world + torch.cuda.device_count() - 1) // torch.cuda.device_count())},
-        "graph_prep_ms": prep_ms, "graph_prep_steady_ms": prep_steady_ms,
+        "graph_prep_ms": prep_ms,
         "edge_steps_per_ms": value * c["L"],
     }
+    if prep_steady_ms is not None:
+        out["graph_prep_steady_ms"] = prep_steady_ms
 
     if prof is not None:
         keep = []
         chain = int(lib.mpnhip_edge_chain_active(model.c_model(keep, n_edges=E)))   # 1: fp32 / split chain kernels, 2: bf16-operand chain
         out.update(rooflines(prof, c, args, N, E, chain, mode))
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(params, W, g, mode == "train")
     def forward_rate():
         # forward-only rate beside the training rate (the north-star target is quoted on forward)
@@ -528,9 +570,9 @@ def main():
         model.train(mode == "train")
         return E / ((time.perf_counter() - t0) * 1e3 / 20)
 
-    if mode == "train" and not args.no_forward_rate:
+    if args.full and mode == "train" and not args.no_forward_rate:
         out["forward_edges_per_ms"] = forward_rate()
-    if world == 1 and args.precision in ("fp32", "fp32_split", "fp32_wgsplit") and not args.no_split_line:
+    if args.full and world == 1 and args.precision in ("fp32", "fp32_split", "fp32_wgsplit") and not args.no_split_line:
         other = "fp32_split" if args.precision == "fp32" else "fp32"
         try:
             # the same step in the OTHER fp32 mode, reported beside the headline: fp32 MFMAs
@@ -555,7 +597,7 @@ def main():
         except Exception as exc:   # the headline line above must survive a failure of the extra measurement
             model.gemm_precision = args.precision
             out["fp32_split" if other == "fp32_split" else "fp32_mfma"] = {"error": "%s: %s" % (type(exc).__name__, exc)}
-    if (world > 1 or force_pg) and mode == "train":
+    if args.full and (world > 1 or force_pg) and mode == "train":
         # SURVEY.md section 8e "Reporting": the gradient all-reduce alone -- S bytes of the flat fp32 bucket, all-reduce(sum) as
         # one collective, HIP events around 20 calls -- and the bus bandwidth 2 (n - 1) / n x S / t it corresponds to (ring
         # all-reduce over xGMI: 7 links x ~153 GB/s per GPU; at these sizes, 1.2 - 19 MB, the collective is latency-bound)
@@ -588,7 +630,7 @@ def main():
         except Exception as exc:
             out["allreduce_ms"] = None
             out["allreduce_error"] = "%s: %s" % (type(exc).__name__, exc)
-    if rank == 0 and world == 1 and not args.no_extras and args.config == "B" and not args.graph_file and args.mode == "auto":
+    if args.full and rank == 0 and world == 1 and not args.no_extras and args.config == "B" and not args.graph_file and args.mode == "auto":
         # the other BASELINE.json configurations, short and clearly labelled (never part of `value`)
         try:
             del x, ei, ea

@@ -86,6 +86,34 @@ def test_bench_runs_from_a_graph_file(tmp_path):
     assert d["config"]["mode"] == "train" and d["value"] > 0 and "graph file" in d["data"], d
 
 
+def test_plain_bench_run_times_the_steps_and_dumps_the_same_outputs_twice(tmp_path):
+    """`bench.py --steps K --warmup W --dump-outputs DIR` without --full: the line carries the headline only, K timed steps, and the
+    last step's logits / loss / gradients / parameters as float32 .npy files; two runs with the same arguments agree."""
+    lines, dumps = [], []
+    for run in ("a", "b"):
+        out_dir = tmp_path / run
+        r = subprocess.run([sys.executable, "bench.py", "--config", "D", "--steps", "3", "--warmup", "1", "--dump-outputs", str(out_dir)],
+                           cwd=REPO, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+        lines.append(json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1]))
+        dumps.append({f[:-4]: np.load(str(out_dir / f)) for f in sorted(os.listdir(str(out_dir)))})
+    d = lines[0]
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["higher_is_better"] is True, d
+    assert abs(d["value"] - d["config"]["edges"] / d["ms_per_step"]) <= 1e-6 * d["value"], d
+    for k in ("metric", "unit", "dtype"):
+        assert d[k], (k, d)
+    for k in ("cpu_baseline", "other_configs", "roofline", "graph_prep_steady_ms", "allreduce_ms"):
+        assert k not in d, (k, d)
+    assert not d["summary"], d["summary"]
+    a, b = dumps
+    assert sorted(a) == ["grads", "logits", "loss", "params"], sorted(a)
+    assert a["logits"].shape == (d["config"]["mp_steps"], d["config"]["edges"]), a["logits"].shape
+    assert all(v.dtype == np.float32 for v in a.values()) and sum(v.nbytes for v in a.values()) <= 64e6
+    assert all(np.isfinite(v).all() for v in a.values())
+    for k in a:
+        assert a[k].shape == b[k].shape and err(a[k], b[k]) < 1e-4, k
+
+
 # ------------------------------------------------------------------------------------------------ (b) container types
 def _sample(seed, n_frames, dets, top_k, with_maps=False):
     g = synth.make_knn_graph(seed=seed, frames=n_frames, dets=dets, top_k=top_k, node_in_dim=64)

@@ -65,9 +65,9 @@ def test_one_rank_rccl_group_runs_the_data_parallel_step(L, d):
 
 
 def test_bench_one_rank_rccl_group_reports_the_allreduce():
-    """bench.py --gpus 1 --backend nccl --force-collectives: a 1-rank RCCL group, the step's collectives issued, allreduce_ms printed."""
+    """bench.py --gpus 1 --backend nccl --force-collectives --full: a 1-rank RCCL group, the step's collectives issued, allreduce_ms printed."""
     r = run_ranks(["bench.py", "--gpus", "1", "--backend", "nccl", "--force-collectives", "--config", "D", "--steps", "5", "--warmup", "3",
-                   "--no-cpu-baseline", "--no-split-line", "--no-extras"], nproc=1)
+                   "--full", "--no-cpu-baseline", "--no-split-line", "--no-extras"], nproc=1)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert d["n_gpus"] == 1 and d["value"] > 0 and d["allreduce_ms"] > 0 and d["allreduce_bytes"] > 0, d
@@ -77,7 +77,7 @@ def test_bench_one_rank_rccl_group_reports_the_allreduce():
 @pytest.mark.parametrize("cfg", ["A", "D"])
 def test_bench_two_ranks_on_one_gpu(cfg):
     """bench.py's N > 1 branch; cfg-D is the configuration BASELINE.json names for the 8-GPU run (one KITTIMOTS-like graph per rank)."""
-    r = run_ranks(["bench.py", "--gpus", "2", "--backend", "gloo", "--config", cfg, "--steps", "3", "--warmup", "2", "--no-cpu-baseline",
+    r = run_ranks(["bench.py", "--gpus", "2", "--backend", "gloo", "--config", cfg, "--steps", "3", "--warmup", "2", "--full", "--no-cpu-baseline",
                    "--no-split-line"])
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
@@ -91,7 +91,7 @@ def test_bench_eight_ranks_on_one_gpu_reports_the_sum_of_the_ranks_edges():
     """the exact layout of BASELINE.json configs[3] -- eight ranks, one KITTIMOTS-like graph each (cfg-D: every
     rank builds its OWN kNN graph, seed 1 + rank, so the edge counts differ) -- on the one leased GPU over gloo (functional only).
     `value` must be the sum of the ranks' edge counts over the step time, not rank 0's count times eight."""
-    r = run_ranks(["bench.py", "--gpus", "8", "--backend", "gloo", "--config", "D", "--steps", "3", "--warmup", "2", "--no-cpu-baseline",
+    r = run_ranks(["bench.py", "--gpus", "8", "--backend", "gloo", "--config", "D", "--steps", "3", "--warmup", "2", "--full", "--no-cpu-baseline",
                    "--no-split-line", "--no-extras"], nproc=8, timeout=900)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -107,7 +107,7 @@ def test_bench_gpus_flag_starts_the_ranks_itself():
     """`python bench.py --gpus 2 ...` with NO launcher and no WORLD_SIZE in the env -- the parent starts the two
     ranks as child processes (bench.spawn_ranks) and rank 0 prints the one line with n_gpus = 2."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
-    r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--backend", "gloo", "--config", "D", "--steps", "3", "--warmup", "2"],
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--backend", "gloo", "--config", "D", "--steps", "3", "--warmup", "2", "--full"],
                        cwd=REPO, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

@@ -187,3 +187,24 @@ def test_bench_gpus_flag_refuses_more_rccl_ranks_than_devices():
     r = subprocess.run([sys.executable, "bench.py", "--gpus", str(n), "--config", "D", "--steps", "2", "--warmup", "1"],
                        cwd=REPO, env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode != 0 and "one GPU per rank" in (r.stderr + r.stdout), r.stdout[-1000:] + r.stderr[-1000:]
+
+
+def test_bench_dump_outputs_writes_float32_and_samples_a_fixed_subset_over_the_limit(tmp_path, monkeypatch):
+    """bench.dump_outputs: float32 .npy files (float64 kept); above the size limit every array is cut to its share of it by the
+    same seeded sample in every run."""
+    import bench
+    arrays = {"logits": torch.arange(1000, dtype=torch.float32).view(10, 100), "loss": torch.tensor([1.5, 2.5], dtype=torch.float64),
+              "grads": np.arange(50, dtype=np.int64)}
+    bench.dump_outputs(str(tmp_path / "all"), arrays)
+    got = {k: np.load(str(tmp_path / "all" / (k + ".npy"))) for k in arrays}
+    assert got["logits"].dtype == np.float32 and got["logits"].shape == (10, 100) and (got["logits"].ravel() == np.arange(1000)).all()
+    assert got["loss"].dtype == np.float64 and got["loss"].tolist() == [1.5, 2.5]
+    assert got["grads"].dtype == np.float32 and (got["grads"] == np.arange(50)).all()
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 2000)
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), arrays)
+    a = {k: np.load(str(tmp_path / "a" / (k + ".npy"))) for k in arrays}
+    b = {k: np.load(str(tmp_path / "b" / (k + ".npy"))) for k in arrays}
+    assert sum(v.nbytes for v in a.values()) <= 2000
+    assert a["logits"].size < 1000 and (np.diff(a["logits"]) > 0).all()   # a sorted subset of the flattened values
+    assert all((a[k] == b[k]).all() for k in arrays)
