@@ -219,12 +219,11 @@ static int side_stream_ready(SideStream** out) {
     SideStream& ss = g_side_dev[dev];
     if (!ss.stream) {
         // lowest priority: the caller's stream carries the critical path (the step loop); when both have workgroups pending, the
-        // dispatcher should place the loop's first (MPNHIP_SIDE_PRIORITY=0: default priority, for measurements)
+        // dispatcher should place the loop's first
         int least = 0, greatest = 0;
         (void)hipDeviceGetStreamPriorityRange(&least, &greatest);
-        static const bool low = [] { const char* e = getenv("MPNHIP_SIDE_PRIORITY"); return !(e && e[0] == '0'); }();
-        MPN_HIP(hipStreamCreateWithPriority(&ss.stream, hipStreamNonBlocking, low ? least : 0));
-        MPN_HIP(hipStreamCreateWithPriority(&ss.stream2, hipStreamNonBlocking, low ? least : 0));
+        MPN_HIP(hipStreamCreateWithPriority(&ss.stream, hipStreamNonBlocking, least));
+        MPN_HIP(hipStreamCreateWithPriority(&ss.stream2, hipStreamNonBlocking, least));
         MPN_HIP(hipEventCreateWithFlags(&ss.ready, hipEventDisableTiming));
         MPN_HIP(hipEventCreateWithFlags(&ss.done, hipEventDisableTiming));
         MPN_HIP(hipEventCreateWithFlags(&ss.done2, hipEventDisableTiming));
@@ -615,7 +614,7 @@ static int act_grad(int ngroups, const float* A, int64_t lda, const int* a_idx, 
             if (!kp || !kp->valid) MPN_TRY(transpose_padded(W[q], ldw, 0, K, N, wt, K, N, s));
             // the kept blocks also as bf16 rows (rounded once per backward instead of in every block of every step's product)
             // (N % 4: launch_gemm's bf16-row path needs whole 16-byte result vectors; otherwise the fp32 image on the register-staged path)
-            const bool img16 = kp && kp->wt16 && K % 8 == 0 && N % 4 == 0 && ((size_t)K * N) % 4 == 0 && !getenv("MPNHIP_NO_GEMM_BF16_ROWS");
+            const bool img16 = kp && kp->wt16 && K % 8 == 0 && N % 4 == 0 && ((size_t)K * N) % 4 == 0;
             if (img16 && !kp->valid) MPN_TRY(to_bf16_rows(wt, kp->wt16, (int64_t)K * N, s));
             if (kp) kp->valid = true;   // (one stream: the later steps' products are ordered behind this transposition)
             g.B = img16 ? reinterpret_cast<const float*>(kp->wt16) : wt;
@@ -770,7 +769,7 @@ extern "C" size_t mpnhip_backward_workspace_bytes(const mpnhip_model* model, int
     return plan_backward(*model, d, n_nodes, n_edges, nullptr, nullptr);
 }
 
-static bool backward_forks(const mpnhip_model& m) { return m.num_enc_steps >= 4 && !getenv("MPNHIP_NO_SIDE_STREAM"); }
+static bool backward_forks(const mpnhip_model& m) { return m.num_enc_steps >= 4; }
 
 extern "C" int mpnhip_backward_uses_side_stream(const mpnhip_model* model) { return model && backward_forks(*model) ? 1 : 0; }
 
@@ -820,8 +819,7 @@ extern "C" int mpnhip_backward_flags(const mpnhip_model* model, const void* grap
         bool old;
         explicit WgradScope(bool v) : old(g_wgrad_split) { g_wgrad_split = v; }
         ~WgradScope() { g_wgrad_split = old; }
-    } wgrad_scope((m.precision == MPNHIP_PREC_FP32_SPLIT || m.precision == MPNHIP_PREC_FP32_WGSPLIT || m.precision == MPNHIP_PREC_BF16) &&
-                  !getenv("MPNHIP_NO_WGRAD_PANEL"));
+    } wgrad_scope((m.precision == MPNHIP_PREC_FP32_SPLIT || m.precision == MPNHIP_PREC_FP32_WGSPLIT || m.precision == MPNHIP_PREC_BF16));
     struct Bf16Scope {
         bool old; float* olds; size_t oldn;
         Bf16Scope(bool v) : old(g_bwd_bf16), olds(g_wt_scratch), oldn(g_wt_scratch_floats) { g_bwd_bf16 = v; }
@@ -845,7 +843,6 @@ extern "C" int mpnhip_backward_flags(const mpnhip_model* model, const void* grap
         KeepScope(const BwdPlan& q) { for (int i = 0; i < 2; ++i) g_wt_keep[i] = {q.wt_keep_floats[i] ? q.wt_keep[i] : nullptr, q.wt_keep_floats[i], false, q.wt_keep_floats[i] ? q.wt_keep16[i] : nullptr}; }
         ~KeepScope() { for (int i = 0; i < 2; ++i) g_wt_keep[i] = {nullptr, 0, false, nullptr}; }
     } keep_scope(p);
-    if (getenv("MPNHIP_NO_WT_KEEP")) for (int i = 0; i < 2; ++i) g_wt_keep[i].wt = nullptr;
     GraphView g;
     graph_layout(n_nodes, n_edges, &g, const_cast<void*>(graph_buf));
     const int he = d.he, hn = d.hn, dn = d.dn, de = d.de, kx = d.kx, ke = d.ke, pw = d.pw, L = d.L;
@@ -894,7 +891,7 @@ extern "C" int mpnhip_backward_flags(const mpnhip_model* model, const void* grap
         MPN_TRY(pack_chain_bf16_bwd(m.edge.weight[0], m.edge.in_dim, 2 * kx + de, m.edge.weight[1], m.classifier.weight[0], f0, m.flow_out.in_dim, kx, f1,
                                     he, de, hn, dn, m.classifier.out_dims[0], p.cb16_img, s));
     }
-    const bool use_chain = chain_shapes_ok(m, d) && E > 0 && L > 0 && !getenv("MPNHIP_NO_CHAIN_BWD");
+    const bool use_chain = chain_shapes_ok(m, d) && E > 0 && L > 0;
     const bool bwd_split = use_chain && chain_split(m);
     if (use_chain) {
         const int HE = pad32(he), DE = pad32(de), HN = pad32(hn), DN = pad32(dn);
@@ -961,13 +958,13 @@ extern "C" int mpnhip_backward_flags(const mpnhip_model* model, const void* grap
 
     // The re-attached x0 does not change from step to step: its share of dX (and of the packed projection weight's gradient)
     // comes from the SUM of the steps' dP, once, after the loop
-    const bool hoist_x = d.nf == 2 && L > 1 && N > 0 && pw % 4 == 0 && dn % 4 == 0 && !getenv("MPNHIP_NO_DX0_HOIST");
+    const bool hoist_x = d.nf == 2 && L > 1 && N > 0 && pw % 4 == 0 && dn % 4 == 0;
     // The same for the re-attached e0 on the edge side (fused chain, whole 64-column passes: 32 < de <= 64): the gradient w.r.t. e0
     // through the edge MLP's first layer and the e0 columns of that layer's weight gradient are ONE product each with
     // S = sum_s dZ1_s after the loop -- 2 E he de MACs less in every step's backward chain and in every step's weight gradient
     // (2 x 2.05 of ~31 GFLOP per step at cfg-B), for one pass over the kept dZ1 blocks.
     // (the bf16 backward chain kernel never contracts the e0 columns: always hoisted there, also at L = 1)
-    const bool hoist_e0 = use_b16 || (use_chain && d.ef == 2 && L > 1 && pad32(de) == 64 && he % 4 == 0 && de % 4 == 0 && !getenv("MPNHIP_NO_DE0_HOIST"));
+    const bool hoist_e0 = use_b16 || (use_chain && d.ef == 2 && L > 1 && pad32(de) == 64 && he % 4 == 0 && de % 4 == 0);
     // bf16-operand training: the per-node projections' weight gradient over bf16 ROWS -- dP_s rounded once by the scatter-add kernel that
     // produces it, x_{s-1} from the forward's bf16 mirror -- on the LDS-DMA kernel in 256 x 256 output tiles (wgrad_rows16.hip)
     // (f.xb_hist is filled under the forward's own run-time test: plan.h node_rows16_runtime, the one definition both sides use)
@@ -1132,26 +1129,10 @@ extern "C" int mpnhip_backward_flags(const mpnhip_model* model, const void* grap
     // smallest: it starts only when the loop is over and what it has not finished when the encoder's backward ends is
     // exposed.  Default for L = 12: 5 + 4 + 3; in general three groups with sizes ~ (5 : 4 : 3), two below six steps or when
     // the products are small.
-    int gsize[8] = {0};
+    int gsize[3] = {0};
     int ngroups = 1;
     if (want_fork) {
-        static const char* spec = getenv("MPNHIP_WGRAD_SPLIT");  // tuning override, e.g. "4,4,4"
-        int parsed = 0, total = 0;
-        if (spec) {
-            const char* q = spec;
-            while (*q && parsed < 8) {
-                gsize[parsed] = atoi(q);
-                total += gsize[parsed] > 0 ? gsize[parsed] : 0;
-                ++parsed;
-                while (*q && *q != ',') ++q;
-                if (*q == ',') ++q;
-            }
-        }
-        bool ok = parsed >= 2 && total == (int)L;
-        for (int i = 0; i < parsed; ++i) ok = ok && gsize[i] > 0;
-        if (ok) {
-            ngroups = parsed;
-        } else if (L >= 6 && (double)E * dn * dn >= 3e8 && !g_wgrad_split) {
+        if (L >= 6 && (double)E * dn * dn >= 3e8 && !g_wgrad_split) {
             // (enough work per group to pay for a third round of ~30 launches: cfg-B 8e8; the reference's 32-d widths, 8e7 at
             // cfg-C, do better with two groups -- measured 2.59 -> 2.48 ms.  The row-panel products of MPNHIP_PREC_FP32_SPLIT are
             // two launches per group whatever its size, and a larger group needs fewer slabs per row: two groups there,
@@ -1381,7 +1362,7 @@ extern "C" int mpnhip_backward_flags(const mpnhip_model* model, const void* grap
     // message-passing modules' gradients (a trainer puts their all-reduce behind it while the encoder's backward still runs).
     WpBatch tailb;
     WpBatchGuard tail_guard;
-    const bool defer_tail = g_wgrad_split && L > 0 && forked && !getenv("MPNHIP_NO_TAIL_DEFER");
+    const bool defer_tail = g_wgrad_split && L > 0 && forked;
     const bool defer_encoder = defer_tail && !(flags & MPNHIP_BWD_DEFER_SIDE_JOIN) && m.enc_node.n_layers <= 3 && m.enc_edge.n_layers <= 3;
     if (defer_tail) wp_batch_begin(&tailb, p.slab_tail, p.slab_tail_floats, true);
     // flush_tail runs what was recorded and closes the batch (its "+=" go to gradient columns disjoint from the groups': it may run
@@ -1393,10 +1374,8 @@ extern "C" int mpnhip_backward_flags(const mpnhip_model* model, const void* grap
     // the launches' blocks dispatched longest first it no longer pays.  A trainer's path (MPNHIP_BWD_DEFER_SIDE_JOIN: the hoisted
     // shares' products run early, the message-passing gradients' collective follows on the first side stream) keeps the second stream
     // on large graphs -- the first side stream is ordered behind it, so the unpacking and the collective that follow there see both.
-    // MPNHIP_TAIL_STREAM2=1 / MPNHIP_NO_TAIL_STREAM2=1 force either, MPNHIP_NO_TAIL_INLINE=1 keeps the batch off the caller's stream.
-    const bool tail_beside = !getenv("MPNHIP_NO_TAIL_STREAM2") &&
-                             (getenv("MPNHIP_TAIL_STREAM2") || ((flags & MPNHIP_BWD_DEFER_SIDE_JOIN) && (double)E * dn >= 1e6));
-    const bool tail_inline = defer_encoder && !tail_beside && !getenv("MPNHIP_NO_TAIL_INLINE");
+    const bool tail_beside = (flags & MPNHIP_BWD_DEFER_SIDE_JOIN) && (double)E * dn >= 1e6;
+    const bool tail_inline = defer_encoder && !tail_beside;
     Rows16Later later16;
     later16.pool = p.enc16;
     later16.pool_elems = p.enc16_elems;
@@ -1441,7 +1420,7 @@ extern "C" int mpnhip_backward_flags(const mpnhip_model* model, const void* grap
         // bf16-operand training: both consumers of S round it to bf16 as they stage it, so S itself is kept as bf16 rows (rounded once,
         // the same values) and its partner e0 is the forward's bf16 mirror: half the bytes written and read twice, the GEMM reads
         // bf16 rows, the weight-gradient product runs on the bf16-row kernels
-        const bool s16 = use_b16 && f.eb_hist && he % 8 == 0 && de % 8 == 0 && !getenv("MPNHIP_NO_S16");
+        const bool s16 = use_b16 && f.eb_hist && he % 8 == 0 && de % 8 == 0;
         if (s16) hipLaunchKernelGGL(k_sum_blocks_bf16<true>, dim3((unsigned)((n4 / 2 + 255) / 256)), dim3(256), 0, s, reinterpret_cast<const unsigned short*>(p.dZed[0]),
                                     E * he, (int)L, n4 / 2, p.dZ1sum);
         else if (use_b16) hipLaunchKernelGGL(k_sum_blocks_bf16<false>, dim3((unsigned)((n4 / 2 + 255) / 256)), dim3(256), 0, s, reinterpret_cast<const unsigned short*>(p.dZed[0]),

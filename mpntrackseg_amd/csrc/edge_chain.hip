@@ -776,11 +776,7 @@ __global__ __launch_bounds__(256, chain_waves(T1)) void edge_chain_bwd_kernel(Ed
     // dZ rows leave through a per-wave LDS slab as whole 128-byte lines (row_stage.h; tools/micro/store_pattern.hip: the 16-byte
     // pieces of 32 different rows a wave instruction writes straight from the accumulator layout run at 1.65 TB/s, 8 whole lines
     // per instruction at 5.4).  The 128-d template only: 18 KB more LDS per block would cost the narrower ones their third wave.
-#ifdef MPNHIP_CHAIN_DIRECT_ROWS
-    constexpr bool SLAB = false;     // (A-B build: make EXTRA=-DMPNHIP_CHAIN_DIRECT_ROWS)
-#else
     constexpr bool SLAB = T1 >= 10;
-#endif
     __shared__ __attribute__((aligned(16))) char rowslab[SLAB ? 4 * ROW_SLAB_BYTES : 16];   // (touched by inline assembly only)
     RowStage rs;
     rs.init(rowslab + (SLAB ? wave * ROW_SLAB_BYTES : 0), lane, tile0 + wave * 32, end);
@@ -1130,7 +1126,7 @@ __global__ __launch_bounds__(256) void k_pack_split_multi(SplitBatch b) {
 static thread_local SplitBatch* g_split_batch = nullptr;
 void split_batch_begin(SplitBatch* b) {
     b->n = 0;
-    g_split_batch = getenv("MPNHIP_NO_PACK_BATCH") ? nullptr : b;
+    g_split_batch = b;
 }
 void split_batch_abort() { g_split_batch = nullptr; }
 int split_batch_flush(hipStream_t s) {
@@ -1301,7 +1297,7 @@ __global__ __launch_bounds__(256, 2) void k_edge_encoder_mfma(const float* __res
 int launch_edge_encoder_mfma(const float* x, const int* idx, int64_t rows, int in_dim, const float* const w[3], const float* const b[3],
                              const int dims[3], float* h1_out, float* h2_out, float* y, hipStream_t s) {
     if (rows <= 0 || in_dim < 1 || in_dim > 16 || dims[0] > 96 || dims[1] > 96 || dims[2] > 64 || dims[0] % 4 || dims[1] % 4 || dims[2] % 4 ||
-        dims[0] < 4 || dims[1] < 4 || dims[2] < 4 || getenv("MPNHIP_NO_ENCODER_MFMA"))
+        dims[0] < 4 || dims[1] < 4 || dims[2] < 4)
         return 0;
     auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
     if (!al16(y) || (h1_out && !al16(h1_out)) || (h2_out && !al16(h2_out))) return 0;
@@ -1340,7 +1336,6 @@ int launch_edge_chain(const EdgeChainArgs& a_in, hipStream_t s) {
         return MPNHIP_ERR_UNSUPPORTED;
     }
     const unsigned blocks = (unsigned)((a.E + 127) / 128 + 3);
-    if (getenv("MPNHIP_CHAIN_ABLATE_COL")) a.scol = a.srow;   // timing ablation: the col-side gathers read the (sorted) row's table row; results wrong
     count_path(a.split ? PC_CHAIN_FWD_SPLIT : PC_CHAIN_FWD);
 #ifdef MPNHIP_CHAIN_TS
     a.ts = g_stamp_fwd.prepare(blocks, s);

@@ -31,10 +31,6 @@
 #include "edge_chain.h"
 #include "edge_chain_bf16_common.h"
 
-#ifndef MPNHIP_ROWSTORE_AB
-#define MPNHIP_ROWSTORE_AB 1   // 0: compile the A-B switches of the row stores out
-#endif
-
 namespace mpnhip {
 
 // Debug build (make EXTRA=-DMPNHIP_CHAIN_TS): lane 0 of every wave stamps s_memtime at the phase boundaries and after every hidden
@@ -123,9 +119,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void edge_chain_bf16_kern
     // (the edge's end points first: the C-in gathers that depend on them then go out under the input rows' loads)
     const int row = A.srow[edge], col = A.scol[edge];
     const unsigned pro = (unsigned)row * (unsigned)A.pw;
-    // (timing ablation, MPNHIP_CHAIN_BF16_DEBUG_SKIP bit 16: the col-side gathers take the ROW's table row -- sorted edges, a few
-    // distinct lines per wave instruction instead of 32; results wrong)
-    const unsigned pco = (unsigned)((A.debug_skip & 16) ? row : col) * (unsigned)A.pw + (unsigned)he;
+    const unsigned pco = (unsigned)col * (unsigned)A.pw + (unsigned)he;
     const unsigned pfo = pco + (unsigned)(he + (grp == 1 ? hn : 0));
     // GD: lane l of DMA instruction q fetches chunk (l & 7) ^ swizzle of edge 8 q + (l >> 3)'s row; the patch image is [edge][8 chunks],
     // chunk positions XOR-ed with (edge >> 1) & 7 (through the SOURCE address: the DMA destination is lane-linear), which makes the
@@ -137,7 +131,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void edge_chain_bf16_kern
         for (int q = 0; q < 4; ++q) {
             const int eq_raw = tile0 + wave * 32 + 8 * q + (lane >> 3);
             const int eq = eq_raw < end ? eq_raw : end - 1;
-            const int cq = (A.debug_skip & 16) ? A.srow[eq] : A.scol[eq];
+            const int cq = A.scol[eq];
             const int rq = 8 * q + (lane >> 3);
             gco[q] = (unsigned)cq * (unsigned)A.pw + (unsigned)he + (unsigned)(((lane & 7) ^ ((rq >> 1) & 7)) * 4);
         }
@@ -176,19 +170,17 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void edge_chain_bf16_kern
     unsigned* const mask_wt = SAVE ? A.save_mask + ((size_t)(blockIdx.x * NW + wave) * NWORDS) * 64 + lane : nullptr;
     auto mask_put = [&](int wbase, int t, int T, unsigned bits) {
         mw = (t & 1) ? (mw | (bits << 8)) : bits;
-        if (((t & 1) || t + 1 == T) && !(A.debug_skip & 2)) mask_wt[(size_t)(wbase + (t >> 1)) * 64] = mw;
+        if ((t & 1) || t + 1 == T) mask_wt[(size_t)(wbase + (t >> 1)) * 64] = mw;
     };
     RowStage rs;
     rs.init(rowslab + wave * ROW_SLAB_BYTES, lane, tile0 + wave * 32, end);
     // a finished bf16 tile t of T to its rows [E, width]: tiles go out in pairs, 128 bytes per row = whole lines (RowStage); a lone
     // last tile straight from the registers (32 contiguous bytes per lane: tile_rows16).  NT: non-temporal -- rows that are read
-    // again only in the backward pass, a whole forward later (984 -> 935 us per launch at cfg-E; MPNHIP_CHAIN_BF16_DEBUG_SKIP=4: plain)
+    // again only in the backward pass, a whole forward later (984 -> 935 us per launch at cfg-E)
     auto save_tile = [&](unsigned short* base, int width, int t, int T, const bf16x8& h0, const bf16x8& h1, bool nt_ok) {
-        if (A.debug_skip & 1) return;
         uint4 lo, hi;
         tile_rows16(h0, h1, lo, hi);
-        const bool nt = nt_ok && !(A.debug_skip & 4);
-        if ((!(t & 1) && t + 1 == T) || (MPNHIP_ROWSTORE_AB && (A.debug_skip & 8))) {   // (8: A-B, every tile straight from the registers)
+        if (!(t & 1) && t + 1 == T) {
             const int f = 32 * t + 16 * lh;
             unsigned short* q = base + (size_t)edge * width + f;
             if (edge_ok && (EXACT || f < width)) *reinterpret_cast<uint4*>(q) = lo;
@@ -197,7 +189,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void edge_chain_bf16_kern
         }
         rs.put16(t & 1, lo, hi);
         if (t & 1) {
-            if (nt) rs.flush<true>(reinterpret_cast<char*>(base), (size_t)width * 2, 64 * (t - 1), (width - 32 * (t - 1)) * 2);
+            if (nt_ok) rs.flush<true>(reinterpret_cast<char*>(base), (size_t)width * 2, 64 * (t - 1), (width - 32 * (t - 1)) * 2);
             else rs.flush<false>(reinterpret_cast<char*>(base), (size_t)width * 2, 64 * (t - 1), (width - 32 * (t - 1)) * 2);
         }
     };
@@ -658,12 +650,11 @@ int launch_edge_chain_bf16(const EdgeChainBf16Args& a_in, hipStream_t s) {
     if (a_in.E <= 0) return MPNHIP_OK;
     EdgeChainBf16Args a = a_in;
     if (const char* e = getenv("MPNHIP_CHAIN_BF16_PLAIN_BARRIERS")) a.plain_barriers = e[0] == '1' ? 1 : 0;
-    if (const char* e = getenv("MPNHIP_CHAIN_BF16_DEBUG_SKIP")) a.debug_skip = atoi(e);
     if ((int64_t)a.E * bmax(bmax(a.he, a.dn), a.de) >= ((int64_t)1 << 32) || (int64_t)a.N * a.pw >= ((int64_t)1 << 32)) {
         set_error("edge_chain_bf16: graph too large for 32-bit row offsets");
         return MPNHIP_ERR_UNSUPPORTED;
     }
-    // 256-d: 4-wave blocks, two per CU (cfg-E: 643 -> 581 us per launch; A-B switch MPNHIP_CHAIN_BF16_NW=8 for one 8-wave block)
+    // 256-d: 4-wave blocks, two per CU (cfg-E: 643 -> 581 us per launch against one 8-wave block)
     const int variant = chain_bf16_variant(a.he, a.de, a.hn, a.dn, a.hc);
     int epb, nwv;
     chain_bf16_geometry(a.he, a.de, a.hn, a.dn, a.hc, &epb, &nwv);
@@ -682,22 +673,17 @@ int launch_edge_chain_bf16(const EdgeChainBf16Args& a_in, hipStream_t s) {
         if (ts_cap) { (void)hipMemsetAsync(ts_buf, 0, need, s); a.ts = ts_buf; }
     }
 #endif
-    static const int dep_env = [] { const char* e = getenv("MPNHIP_CHAIN16_DEPTH"); return e ? atoi(e) : 0; }();   // A-B: LDS operand reads in flight
     const bool save = a.save_mask != nullptr;
     if (save && !(a.save_h1 && a.save_hc && a.save_hf && a.save_eb)) { set_error("edge_chain_bf16: incomplete save buffers"); return MPNHIP_ERR_ARG; }
     if (save) a.e16_out = a.save_eb;
     if (!a.e_new && !a.e16_out) { set_error("edge_chain_bf16: no output for the edge features"); return MPNHIP_ERR_ARG; }
-#define MPN_CB16(SV, ...) do { if (SV) MPN_LAUNCH_PROFILED((edge_chain_bf16_kernel<__VA_ARGS__, true>), dim3(blocks), dim3(four ? 256 : 512), s, a); \
-                              else MPN_LAUNCH_PROFILED((edge_chain_bf16_kernel<__VA_ARGS__, false>), dim3(blocks), dim3(four ? 256 : 512), s, a); } while (0)
+#define MPN_CB16(SV, ...) do { if (SV) MPN_LAUNCH_PROFILED((edge_chain_bf16_kernel<__VA_ARGS__, true>), dim3(blocks), dim3(512), s, a); \
+                              else MPN_LAUNCH_PROFILED((edge_chain_bf16_kernel<__VA_ARGS__, false>), dim3(blocks), dim3(512), s, a); } while (0)
     switch (variant) {
         case 256:
             // (widths that are multiples of 32 only: the masked form of this variant does not fit the register budget)
-            if (four && !save && dep_env == 8) MPN_LAUNCH_PROFILED((edge_chain_bf16_kernel<20, 4, 14, 8, 2, 2, true, 4, 1, false, 8>), dim3(blocks), dim3(256), s, a);
-            else if (four && !save && dep_env == 6) MPN_LAUNCH_PROFILED((edge_chain_bf16_kernel<20, 4, 14, 8, 2, 2, true, 4, 1, false, 6>), dim3(blocks), dim3(256), s, a);
-            else if (four && !save && !getenv("MPNHIP_CHAIN_BF16_NO_GDMA"))
-                MPN_LAUNCH_PROFILED((edge_chain_bf16_kernel<20, 4, 14, 8, 2, 2, true, 4, 1, false, DEPTH, true>), dim3(blocks), dim3(256), s, a);
-            else if (four) MPN_CB16(save, 20, 4, 14, 8, 2, 2, true, 4, 1);
-            else MPN_CB16(save, 20, 4, 14, 8, 2, 2, true, 8, 2);
+            if (save) MPN_LAUNCH_PROFILED((edge_chain_bf16_kernel<20, 4, 14, 8, 2, 2, true, 4, 1, true>), dim3(blocks), dim3(256), s, a);
+            else MPN_LAUNCH_PROFILED((edge_chain_bf16_kernel<20, 4, 14, 8, 2, 2, true, 4, 1, false, DEPTH, true>), dim3(blocks), dim3(256), s, a);
             break;
         case 128:
             if (exact) MPN_CB16(save, 10, 2, 7, 4, 1, 2, true, 8, 2);
@@ -733,8 +719,7 @@ int launch_edge_chain_bf16(const EdgeChainBf16Args& a_in, hipStream_t s) {
 }
 
 void chain_bf16_geometry(int he, int de, int hn, int dn, int hc, int* epb, int* nw) {
-    static const int nw_env = [] { const char* e = getenv("MPNHIP_CHAIN_BF16_NW"); return e ? atoi(e) : 0; }();
-    const bool four = chain_bf16_variant(he, de, hn, dn, hc) == 256 && nw_env != 8;
+    const bool four = chain_bf16_variant(he, de, hn, dn, hc) == 256;
     *epb = four ? 128 : 256;
     *nw = four ? 4 : 8;
 }

@@ -20,10 +20,6 @@
 #include "edge_chain.h"
 #include "edge_chain_bf16_common.h"
 
-#ifndef MPNHIP_ROWSTORE_AB
-#define MPNHIP_ROWSTORE_AB 1   // 0: compile the A-B switches of the row stores out
-#endif
-
 namespace mpnhip {
 
 // T1 = he / 32 ... as in edge_chain_bf16_kernel; NW waves per block, CT hidden tiles per weight chunk -- the SAME NW as the
@@ -76,12 +72,11 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void edge_chain_bf16_bwd_
     rs.init(rowslab + wave * ROW_SLAB_BYTES, lane, tile0 + wave * 32, end);
     // a finished dZ tile t of T to its bf16 rows [E, width]: in pairs, 128 bytes per row = whole lines (RowStage); a lone last tile
     // straight from the registers.  Plain stores: the scatter-adds and the weight-gradient products read these rows right away
-    // (non-temporal: 611 -> 756 us per launch at cfg-E; MPNHIP_CHAIN_BF16_DEBUG_SKIP=4 selects them, A-B)
+    // (non-temporal: 611 -> 756 us per launch at cfg-E)
     auto save_tile = [&](unsigned short* base, int width, int t, int T, const bf16x8& h0, const bf16x8& h1) {
-        if (A.debug_skip & 1) return;
         uint4 lo, hi;
         tile_rows16(h0, h1, lo, hi);
-        if ((!(t & 1) && t + 1 == T) || (MPNHIP_ROWSTORE_AB && (A.debug_skip & 8))) {   // (8: A-B, every tile straight from the registers)
+        if (!(t & 1) && t + 1 == T) {
             const int f = 32 * t + 16 * lh;
             unsigned short* q = base + (size_t)edge * width + f;
             if (edge_ok && (EXACT || f < width)) *reinterpret_cast<uint4*>(q) = lo;
@@ -89,10 +84,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void edge_chain_bf16_bwd_
             return;
         }
         rs.put16(t & 1, lo, hi);
-        if (t & 1) {
-            if (A.debug_skip & 4) rs.flush<true>(reinterpret_cast<char*>(base), (size_t)width * 2, 64 * (t - 1), (width - 32 * (t - 1)) * 2);
-            else rs.flush<false>(reinterpret_cast<char*>(base), (size_t)width * 2, 64 * (t - 1), (width - 32 * (t - 1)) * 2);
-        }
+        if (t & 1) rs.flush<false>(reinterpret_cast<char*>(base), (size_t)width * 2, 64 * (t - 1), (width - 32 * (t - 1)) * 2);
     };
     const float dl = A.dlog[A.perm[edge]];
 
@@ -280,12 +272,6 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void edge_chain_bf16_bwd_
     }
 #pragma unroll
     for (int o = 0; o < T2; ++o) {   // (fp32 tiles: 128 bytes per row, whole lines through the slab)
-        if (MPNHIP_ROWSTORE_AB && (A.debug_skip & 16)) {
-            const unsigned eo = (unsigned)edge * (unsigned)de;
-#pragma unroll
-            for (int g = 0; g < 4; ++g) strow<EXACT>(dst, eo, 32 * o + 8 * g + 4 * lh, de, get4(dp[o], g), edge_ok);
-            continue;
-        }
         rs.put32(dp[o]);
         rs.flush<false>(reinterpret_cast<char*>(dst), (size_t)de * 4, 128 * o, (de - 32 * o) * 4);
     }
@@ -325,7 +311,6 @@ int launch_edge_chain_bf16_bwd(const EdgeChainBf16BwdArgs& a_in, hipStream_t s) 
     if (a_in.E <= 0) return MPNHIP_OK;
     EdgeChainBf16BwdArgs a = a_in;
     if (const char* e = getenv("MPNHIP_CHAIN_BF16_PLAIN_BARRIERS")) a.plain_barriers = e[0] == '1' ? 1 : 0;
-    if (const char* e = getenv("MPNHIP_CHAIN_BF16_DEBUG_SKIP")) a.debug_skip = atoi(e);
     const int wmax = a.he > a.dn ? a.he : a.dn;
     if ((int64_t)a.E * wmax >= ((int64_t)1 << 32) || (int64_t)a.N * 2 * a.dn >= ((int64_t)1 << 32)) {
         set_error("edge_chain_bf16_bwd: graph too large for 32-bit row offsets");
@@ -343,8 +328,7 @@ int launch_edge_chain_bf16_bwd(const EdgeChainBf16BwdArgs& a_in, hipStream_t s) 
     count_path(PC_CHAIN_BWD_BF16);
 #define MPN_CBB(...) MPN_LAUNCH_PROFILED((edge_chain_bf16_bwd_kernel<__VA_ARGS__>), dim3(blocks), dim3(64 * nw), s, a)
     if (t1 == 20 && t2 == 4 && tf == 14 && td == 8 && tc == 2 && exact) {
-        if (nw == 4) MPN_CBB(20, 4, 14, 8, 2, true, 4, 1);
-        else MPN_CBB(20, 4, 14, 8, 2, true, 8, 2);
+        MPN_CBB(20, 4, 14, 8, 2, true, 4, 1);
     } else if (t1 == 10 && t2 == 2 && tf == 7 && td == 4 && tc == 1) {
         if (exact) MPN_CBB(10, 2, 7, 4, 1, true, 8, 2);
         else MPN_CBB(10, 2, 7, 4, 1, false, 8, 2);

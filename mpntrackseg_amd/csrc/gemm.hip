@@ -509,7 +509,7 @@ static int launch_cfg(const GemmArgs& a, int bl, hipStream_t s) {
     // measured on MI355X (tools/gemm_bench.py --check): 5000 x 1088 x 256 38.9 -> 31.6 us, 5000 x 512 x 2048 141 -> 122 us,
     // 50000 x 320 x 128 65.6 -> 48.5 us; narrow outputs (N = 128) and short K lose to the fp32 MFMA kernel's smaller LDS image
     if (prec == 2 && !(a.K >= 128 && a.N >= 256)) prec = 0;
-    if (const char* e = getenv("MPNHIP_GEMM_PREC")) prec = atoi(e);  // tuning override (tools/gemm_bench.py)
+    if (const char* e = getenv("MPNHIP_GEMM_PREC")) prec = atoi(e);  // operand-form override (tools/diag/split_accuracy.py)
     count_path(bl == B_KCONTIG && prec == 2 ? PC_GEMM_SPLIT : (bl == B_KCONTIG && prec == 1 ? PC_GEMM_BF16 : PC_GEMM_FP32));
     if (bl == B_KCONTIG && prec == 2)
         MPN_LAUNCH_PROFILED((gemm_kernel<WM, WN, TN, B_KCONTIG, 2>), grid, dim3(NTHREADS), s, a);
@@ -560,7 +560,7 @@ int launch_gemm(const GemmArgs& a_in, int al, int bl, hipStream_t s) {
         const GemmGroup& G0 = a.g[0];
         if (a.ngroups == 1 && a.K >= 1 && a.K <= 8 && a.ksplit == a.K && bl == B_KCONTIG && !G0.A2 && !G0.G1 && !G0.G2 && !G0.mask &&
             !G0.c_idx && !a.accumulate && a.N % 4 == 0 && a.N >= 4 && a.N <= 4 * NTHREADS && G0.ldc % 4 == 0 &&
-            (((uintptr_t)G0.C) & 15) == 0 && a.m_upper >= 4096 && !getenv("MPNHIP_NO_SMALLK")) {
+            (((uintptr_t)G0.C) & 15) == 0 && a.m_upper >= 4096) {
             const int rpp = NTHREADS / (a.N / 4);
             // (a thread's 4 x K weights are 28 scalar loads: at least eight row passes per block to pay for them)
             int64_t nb = ((a.m_upper + rpp - 1) / rpp + 7) / 8;
@@ -612,10 +612,6 @@ int launch_gemm(const GemmArgs& a_in, int al, int bl, hipStream_t s) {
             const int64_t rb = (M + 127) / 128;
             while (best > 1 && rb * ((nt + best - 1) / best) < 256) best = (best + 1) / 2;
         }
-        if (const char* e = getenv("MPNHIP_TN")) {  // tuning override
-            int v = atoi(e);
-            if (v >= 1 && v <= 8) best = v;
-        }
         switch (best) {
             case 8: return launch_cfg<4, 1, 8>(a, bl, s);
             case 7: return launch_cfg<4, 1, 7>(a, bl, s);
@@ -628,17 +624,6 @@ int launch_gemm(const GemmArgs& a_in, int al, int bl, hipStream_t s) {
         }
     }
     // few rows (node-level products): spread the columns over the waves so that the grid fills the chip
-    if (const char* e = getenv("MPNHIP_SMALL_CFG")) {  // tuning override: 412 = <4,1,2>, 141 = <1,4,1>, ...
-        switch (atoi(e)) {
-            case 411: return launch_cfg<4, 1, 1>(a, bl, s);
-            case 412: return launch_cfg<4, 1, 2>(a, bl, s);
-            case 414: return launch_cfg<4, 1, 4>(a, bl, s);
-            case 141: return launch_cfg<1, 4, 1>(a, bl, s);
-            case 142: return launch_cfg<1, 4, 2>(a, bl, s);
-            case 221: return launch_cfg<2, 2, 1>(a, bl, s);
-            default: break;
-        }
-    }
     // measured on MI355X at M = 5,000 (tools/gemm_bench.py): 64 x 64 tiles beat every wider strip for
     // N = 128 ... 1088 and K = 128 ... 2048 (more, shorter blocks: the chip is latency- not MFMA-bound here)
     if (nt >= 2) return launch_cfg<2, 2, 1>(a, bl, s);
@@ -802,7 +787,7 @@ bool linear_splitk(const float* x, int64_t ldx, const float* w, const float* b, 
                    float* scratch, size_t scratch_floats, hipStream_t stream, int* status, SplitkNext* next) {
     *status = MPNHIP_OK;
     // (fp32 MFMAs: exact fp32 products -- also what the split precision may use; the bf16-operand mode must round its operands)
-    if (g_precision == 1 || getenv("MPNHIP_NO_SPLITK")) return false;
+    if (g_precision == 1) return false;
     const int64_t tiles = ((m + 63) / 64) * ((n + 63) / 64);
     if (!scratch || m <= 0 || m > SPLITK_MAX_ROWS || k < 512 || k % 4 != 0 || ldx % 4 != 0 || tiles >= SPLITK_MAX_TILES || (((uintptr_t)x | (uintptr_t)w) & 15)) return false;
     int S = (int)(splitk_blocks(tiles) / tiles);

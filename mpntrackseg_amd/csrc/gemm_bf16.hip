@@ -306,8 +306,7 @@ __global__ __launch_bounds__(GB_THREADS, 4) void gemm_bf16_kernel(GemmArgs args,
 // rows in memory nothing has to pass through registers:
 //   * one 768-thread block per CU, persistent (8 multiplying waves + 4 loader waves): the XCD's 32 blocks walk the XCD's contiguous
 //     run of tiles;
-//   * block tile 128 x 128 (waves 2 x 4, wave tile 64 x 32); a 256 x 128 form (waves 4 x 2, wave tile 64 x 64: 16 MFMAs per wave between
-//     two barriers) is instantiated behind MPNHIP_GEMM_RING_TILE=256 -- measured no faster;
+//   * block tile 128 x 128 (waves 2 x 4, wave tile 64 x 32);
 //   * a ring of NST stages (A rows [BM][64] | B rows [BN][64], 128-byte rows, 16-byte chunks XOR-swizzled by (row >> 1) & 7 through
 //     the per-lane SOURCE address: the LDS-DMA destination is lane-linear; conflict-free for the ds_read_b128 lane groups), filled
 //     by global_load_lds_dwordx4 in 1 KiB pieces, NST - 1 stages ahead -- across tile boundaries: the next tile's first stages
@@ -324,7 +323,6 @@ struct RingArgs {
     const float* bias; float* C;
     int lda, lda2, ldb, ldc;
     int M, N, K, ksplit, relu, nbx, nby;
-    int debug;   // timing ablations (MPNHIP_GEMM_RING_DEBUG; results wrong): 1 no operand fetch / MFMA, 2 no DMA, 4 no stores, 8 linear chunks
 };
 
 template <int OFF>
@@ -405,16 +403,14 @@ __global__ __launch_bounds__(64 * (8 + NLW), (8 + NLW) * BPC / 4) void gemm_bf16
             const bool seg2 = k0 >= a.ksplit;
             const unsigned short* ab = seg2 ? a.A2 : a.A;
             char* const dst = smem + is_slot * STAGE;
-            if (!(a.debug & 2)) {
 #pragma unroll
-                for (int j = 0; j < PA; ++j)
-                    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(ab + (seg2 ? oA2[j] : oA1[j]) + k0),
-                                                     (__attribute__((address_space(3))) void*)(dst + (PA * lw + j) * 1024), 16, 0, 0);
+            for (int j = 0; j < PA; ++j)
+                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(ab + (seg2 ? oA2[j] : oA1[j]) + k0),
+                                                 (__attribute__((address_space(3))) void*)(dst + (PA * lw + j) * 1024), 16, 0, 0);
 #pragma unroll
-                for (int j = 0; j < PB; ++j)
-                    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(a.B + oB[j] + k0),
-                                                     (__attribute__((address_space(3))) void*)(dst + BM * 128 + (PB * lw + j) * 1024), 16, 0, 0);
-            }
+            for (int j = 0; j < PB; ++j)
+                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(a.B + oB[j] + k0),
+                                                 (__attribute__((address_space(3))) void*)(dst + BM * 128 + (PB * lw + j) * 1024), 16, 0, 0);
             is_slot = is_slot == NST - 1 ? 0 : is_slot + 1;
             if (++is_kt == nk) { is_kt = 0; ++is_i; }
         };
@@ -458,7 +454,6 @@ __global__ __launch_bounds__(64 * (8 + NLW), (8 + NLW) * BPC / 4) void gemm_bf16
                 for (int r = 0; r < 16; ++r) acc[q][u][r] = 0.f;
         for (int kt = 0; kt < nk; ++kt) {
             __builtin_amdgcn_s_barrier();
-            if (a.debug & 1) { slot_off = slot_off == (NST - 1) * STAGE ? 0u : slot_off + STAGE; continue; }
             bf16x8 av[4][TM], bv[4][TN];
 #pragma unroll
             for (int kb = 0; kb < 4; ++kb) {
@@ -484,7 +479,6 @@ __global__ __launch_bounds__(64 * (8 + NLW), (8 + NLW) * BPC / 4) void gemm_bf16
         // Straight from the accumulator layout: register r of a 32 x 32 tile holds rows (r & 3) + 8 (r >> 2) + 4 lh at column li, so
         // one store instruction writes two whole 128-byte lines.  No LDS patch here (a compiler-visible LDS access next to an
         // LDS-DMA target draws s_waitcnt vmcnt(0)); the biases come out of LDS by inline assembly for the same reason.
-        if (a.debug & 4) { asm volatile("" :: "v"(acc[0][0][0]), "v"(acc[1][0][5])); continue; }
         const bool interior = by * BM + BM <= M && bx * BN + BN <= N;     // block-uniform: no per-store predicates
 #pragma unroll
         for (int u = 0; u < TN; ++u) {
@@ -518,25 +512,19 @@ int launch_ring(const GemmArgs& a, hipStream_t s) {
     r.bias = g.bias; r.C = g.C;
     r.lda = (int)g.lda; r.lda2 = g.A2 ? (int)g.lda2 : (int)g.lda; r.ldb = (int)g.ldb; r.ldc = (int)g.ldc;
     r.M = (int)a.m_upper; r.N = a.N; r.K = a.K; r.ksplit = g.A2 ? a.ksplit : a.K; r.relu = a.relu;
-    // 128 x 128 tiles; MPNHIP_GEMM_RING_TILE=256: the 256 x 128 form (measured over four boxes at the projections' shape,
-    // 20,000 x 2,176 x 512: 76-80 us against 72-85 -- no faster on average and less even; 40 against 46 us at 20,000 x 256 x 2,176)
-    bool big = false;
-    if (const char* e = getenv("MPNHIP_GEMM_RING_TILE")) big = atoi(e) == 256;
-    const int bm = big ? 256 : 128;
-    r.nbx = (a.N + 127) / 128; r.nby = (int)((a.m_upper + bm - 1) / bm);
+    // 128 x 128 tiles (a 256 x 128 form measured no faster on average and less even over four boxes at the projections' shape,
+    // 20,000 x 2,176 x 512: 76-80 us against 72-85; 40 against 46 us at 20,000 x 256 x 2,176)
+    r.nbx = (a.N + 127) / 128; r.nby = (int)((a.m_upper + 127) / 128);
     const int64_t total = (int64_t)r.nbx * r.nby;
-    int grid = total >= 256 ? 256 : (int)((total + 7) / 8 * 8);
-    if (const char* e = getenv("MPNHIP_GEMM_RING_DEBUG")) r.debug = atoi(e);
-    if (const char* e = getenv("MPNHIP_GEMM_RING_BLOCKS")) { const int v = atoi(e); if (v >= 8 && v <= 1024) grid = v / 8 * 8; }
-    if (big) MPN_LAUNCH_PROFILED((gemm_bf16_ring_kernel<4, 2, 2, 2, 3, 4, 1>), dim3((unsigned)grid), dim3(768), s, r);
-    else MPN_LAUNCH_PROFILED((gemm_bf16_ring_kernel<2, 4, 2, 1, 4, 4, 1>), dim3((unsigned)grid), dim3(768), s, r);
+    const int grid = total >= 256 ? 256 : (int)((total + 7) / 8 * 8);
+    MPN_LAUNCH_PROFILED((gemm_bf16_ring_kernel<2, 4, 2, 1, 4, 4, 1>), dim3((unsigned)grid), dim3(768), s, r);
     MPN_LAUNCH_CHECK();
     return MPNHIP_OK;
 }
 
 // the ring kernel's shapes: both operands bf16 rows, one group over static rows, plain epilogue, whole 64-deep K steps
 bool ring_eligible(const GemmArgs& a, bool a16, bool b16, bool full) {
-    if (!a16 || !b16 || full || a.ngroups != 1 || getenv("MPNHIP_NO_GEMM_BF16_RING")) return false;
+    if (!a16 || !b16 || full || a.ngroups != 1) return false;
     const GemmGroup& g = a.g[0];
     if (g.row_begin || g.row_end || g.a_idx || g.c_idx || g.C16 || g.m_static != a.m_upper) return false;
     if (a.K % 64 != 0 || a.ksplit % 64 != 0 || a.N > RG_BIAS_MAX || a.N % 4 != 0) return false;

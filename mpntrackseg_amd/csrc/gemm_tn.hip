@@ -289,7 +289,7 @@ __global__ __launch_bounds__(256) void gemm_tn_narrowk_kernel(TnArgs args) {
         sl[k_in] = acc[8];
     }
 }
-static inline bool tn_narrowk(int n_out, int k_in) { return k_in <= 8 && n_out > 32 && n_out <= 256 && !getenv("MPNHIP_TN_NO_NARROWK"); }
+static inline bool tn_narrowk(int n_out, int k_in) { return k_in <= 8 && n_out > 32 && n_out <= 256; }
 
 // Narrow outputs (n_out <= 32, k_in <= 32: the reference's 18-wide edge encoder, the [1 x hc] classifier output layer): the
 // any-shape kernel above is latency-bound there (one dependent gather chain per row and lane).  Here a block stages 64 rows of
@@ -478,8 +478,7 @@ void tn_plan(TnArgs& a) {
     int tiles = ((a.n_out + TBM - 1) / TBM) * ((a.k_in + tbn - 1) / tbn) * a.nbatch;
     // measured on MI355X (cfg-B / C / D training steps): 1024 blocks for the long products (>= 100k rows over the batch: the
     // edge-level ones), 1536 for the short ones (node level, small graphs), which need the extra row chunks to fill the chip
-    static const int blocks_env = [] { const char* e = getenv("MPNHIP_TN_BLOCKS"); const int v = e ? atoi(e) : 0; return v >= 64 ? v : 0; }();  // tuning override
-    const int blocks_wanted = blocks_env ? blocks_env : (a.m_upper * a.nbatch >= 100000 ? 1024 : 1536);
+    const int blocks_wanted = a.m_upper * a.nbatch >= 100000 ? 1024 : 1536;
     int target = blocks_wanted / (tiles > 0 ? tiles : 1);
     if (target < 1) target = 1;
     // narrow outputs (the reference's 18-wide edge encoder, the classifier's output layer): one block per 64-row staging round.
@@ -513,7 +512,8 @@ int launch_gemm_tn(const TnArgs& a_in, hipStream_t s) {
                g.h2_bstride % 4 == 0;
     }
     tn_plan(a);
-    count_path(fast ? PC_TN_MFMA : (a.n_out <= 32 && a.k_in <= 32 && a.csplit == a.k_in && !getenv("MPNHIP_TN_NO_SMALL") ? PC_TN_SMALL : PC_TN_GENERIC));
+    const bool small = a.n_out <= 32 && a.k_in <= 32 && a.csplit == a.k_in;
+    count_path(fast ? PC_TN_MFMA : (small ? PC_TN_SMALL : PC_TN_GENERIC));
     if (fast) {
         const int tbn = a.k_in <= 64 ? 64 : 128;
         a.tiles = ((a.n_out + TBM - 1) / TBM) * ((a.k_in + tbn - 1) / tbn);
@@ -522,7 +522,6 @@ int launch_gemm_tn(const TnArgs& a_in, hipStream_t s) {
         // of output tiles share every H row (edge layer 1, 5 tiles: 282 -> 259 us) and costs a little elsewhere (3 tiles: 156 ->
         // 176 us; 128 tiles: 140 -> 173 us -- there the chunks' tiles no longer start together)
         a.xcd_map = a.tiles >= 4 && a.tiles <= 8 ? 1 : 0;
-        if (const char* e = getenv("MPNHIP_TN_XCD")) a.xcd_map = e[0] == '1';   // A-B switch for measurements
         const unsigned nblocks = (unsigned)(a.tiles * a.ny8 * a.ngroups);
         prof_begin(PROF_TN, s, a.flops);
         if (tbn == 64)
@@ -532,7 +531,7 @@ int launch_gemm_tn(const TnArgs& a_in, hipStream_t s) {
         prof_end(PROF_TN, s);
     } else if (tn_narrowk(a.n_out, a.k_in) && a.csplit == a.k_in) {
         hipLaunchKernelGGL(gemm_tn_narrowk_kernel, dim3(1, a.nsplit * a.nbatch, a.ngroups), dim3(256), 0, s, a);
-    } else if (a.n_out <= 32 && a.k_in <= 32 && a.csplit == a.k_in && !getenv("MPNHIP_TN_NO_SMALL")) {
+    } else if (small) {
         hipLaunchKernelGGL(gemm_tn_small_kernel, dim3(1, a.nsplit * a.nbatch, a.ngroups), dim3(256), 0, s, a);
     } else {
         const int64_t nout_total = (int64_t)a.n_out * (a.k_in + 1);
@@ -604,7 +603,7 @@ static int weight_grad_args(const float* dZ, const float* H, int64_t rows, int n
 
 // precision MPNHIP_PREC_FP32_SPLIT: the row-panel kernel with three-piece bf16 operands (wgrad_panel.hip) where the shape allows it
 static int weight_grad_run(const TnArgs& a, int precision, void* workspace, size_t workspace_bytes, hipStream_t s) {
-    if ((precision == MPNHIP_PREC_FP32_SPLIT || precision == MPNHIP_PREC_BF16) && !getenv("MPNHIP_NO_WGRAD_PANEL")) {
+    if (precision == MPNHIP_PREC_FP32_SPLIT || precision == MPNHIP_PREC_BF16) {
         const TnGroup& g = a.g[0];
         WpProduct p = {g.dZ, g.ldz, g.z_bstride, g.H, g.ldh, g.h_bstride, nullptr, nullptr, a.m_upper, a.nbatch, a.n_out, a.k_in,
                        g.grad_w, g.ldw, g.grad_b, nullptr, nullptr, nullptr, 0, 0, 0, precision == MPNHIP_PREC_BF16 ? 1 : 3};

@@ -562,7 +562,7 @@ __global__ __launch_bounds__(64) void k_pack_node_units(const float* __restrict_
 }  // namespace
 
 bool node_chain_supported(int dn, int pw, int kx) {
-    return (dn == 64 || dn == 128) && pw % 32 == 0 && pw >= 32 && kx == 2 * dn && !getenv("MPNHIP_NO_NODE_CHAIN");
+    return (dn == 64 || dn == 128) && pw % 32 == 0 && pw >= 32 && kx == 2 * dn;
 }
 size_t node_chain_image_shorts(int dn, int pw, size_t* off_wx) {
     const size_t wu = (size_t)(dn / 32) * (2 * dn / 16) * 3 * 512;
@@ -589,11 +589,7 @@ int launch_node_chain(const NodeChainArgs& a_in, hipStream_t s) {
     const NodeChainArgs& a = a_in;
 #endif
     const unsigned blocks = (unsigned)((a.N + 31) / 32);
-    // (MPNHIP_NODE_CHAIN_WAVES=4: round 3's four-wave blocks, A-B)
-    static const int nwv = getenv("MPNHIP_NODE_CHAIN_WAVES") ? atoi(getenv("MPNHIP_NODE_CHAIN_WAVES")) : 8;
-    if (a.dn == 128 && nwv == 4) MPN_LAUNCH_PROFILED((node_chain_kernel<4, 4>), dim3(blocks), dim3(256), s, a);
-    else if (a.dn == 128) MPN_LAUNCH_PROFILED((node_chain_kernel<4, 8>), dim3(blocks), dim3(512), s, a);
-    else if (a.dn == 64 && nwv == 4) MPN_LAUNCH_PROFILED((node_chain_kernel<2, 4>), dim3(blocks), dim3(256), s, a);
+    if (a.dn == 128) MPN_LAUNCH_PROFILED((node_chain_kernel<4, 8>), dim3(blocks), dim3(512), s, a);
     else if (a.dn == 64) MPN_LAUNCH_PROFILED((node_chain_kernel<2, 8>), dim3(blocks), dim3(512), s, a);
     else { set_error("node_chain: unsupported width %d", a.dn); return MPNHIP_ERR_UNSUPPORTED; }
     MPN_LAUNCH_CHECK();
@@ -628,13 +624,10 @@ int launch_node_chain_bwd(const NodeChainBwdArgs& a_in, hipStream_t s) {
     const NodeChainBwdArgs& a = a_in;
 #endif
     const unsigned blocks = (unsigned)((a.N + 31) / 32);
-    // (4 or 8 waves per block -- one or two per SIMD -- measure the same, 21.3 / 21.0 us at cfg-B: the launch is bound by the weight
-    // units every block streams from L2, see below; 4 is the default for its smaller LDS footprint beside the side stream's blocks)
-    static const int nwv = getenv("MPNHIP_NODE_BWD_WAVES") ? atoi(getenv("MPNHIP_NODE_BWD_WAVES")) : 4;
-    if (a.dn == 128 && nwv == 4) hipLaunchKernelGGL((node_chain_bwd_kernel<4, 4>), dim3(blocks), dim3(256), 0, s, a);
-    else if (a.dn == 128) hipLaunchKernelGGL((node_chain_bwd_kernel<4, 8>), dim3(blocks), dim3(512), 0, s, a);
-    else if (a.dn == 64 && nwv == 4) hipLaunchKernelGGL((node_chain_bwd_kernel<2, 4>), dim3(blocks), dim3(256), 0, s, a);
-    else if (a.dn == 64) hipLaunchKernelGGL((node_chain_bwd_kernel<2, 8>), dim3(blocks), dim3(512), 0, s, a);
+    // (four waves per block, one per SIMD: eight measured the same, 21.3 / 21.0 us at cfg-B -- the launch is bound by the weight
+    // units every block streams from L2, see below -- and four leave a smaller LDS footprint beside the side stream's blocks)
+    if (a.dn == 128) hipLaunchKernelGGL((node_chain_bwd_kernel<4, 4>), dim3(blocks), dim3(256), 0, s, a);
+    else if (a.dn == 64) hipLaunchKernelGGL((node_chain_bwd_kernel<2, 4>), dim3(blocks), dim3(256), 0, s, a);
     else { set_error("node_chain_bwd: unsupported width %d", a.dn); return MPNHIP_ERR_UNSUPPORTED; }
     MPN_LAUNCH_CHECK();
     return MPNHIP_OK;

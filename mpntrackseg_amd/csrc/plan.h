@@ -157,8 +157,6 @@ struct FwdPlan {
     unsigned short* Wnode16;
     unsigned short* Wu16;
     unsigned short* xb_hist;
-    float* P_alt;  // [N, pw] (inference, dn = 32) or nullptr
-    int* barrier;  // 4 words: grid barrier of the one-launch step loop
     float* P0;     // [N, pw] step-invariant half of the per-node projections: x0 Wnode[:, :dn]^T + bnode
     float* Q0;     // [E, he] step-invariant share of the edge MLP's first layer: e0 W1[:, e0 columns]^T (fused chain only)
     float* enc_n[2];
@@ -252,12 +250,10 @@ static inline size_t plan_forward(const mpnhip_model& m, const Dims& d, int64_t 
         p.nc_img = reinterpret_cast<unsigned short*>(a.f((node_chain_image_shorts(d.dn, d.pw, nullptr) + 1) / 2));
     // (bf16 rows for the tiled / ring GEMM kernels: 16-byte pieces of 8 elements)
     // (d.pw % 4: launch_gemm's bf16-row path stores 16-byte result vectors -- N = pw of the projections, N = dn of the node update)
-    const bool rows16 = m.precision == MPNHIP_PREC_BF16 && d.kx % 8 == 0 && d.dn % 8 == 0 && d.pw % 4 == 0 && m.node.n_layers == 1 && !getenv("MPNHIP_NO_GEMM_BF16_ROWS");
+    const bool rows16 = m.precision == MPNHIP_PREC_BF16 && d.kx % 8 == 0 && d.dn % 8 == 0 && d.pw % 4 == 0 && m.node.n_layers == 1;
     p.Wnode16 = rows16 ? reinterpret_cast<unsigned short*>(a.f(((size_t)d.pw * d.kx + 1) / 2)) : nullptr;
     p.Wu16 = rows16 ? reinterpret_cast<unsigned short*>(a.f(((size_t)d.dn * 2 * d.dn + 1) / 2)) : nullptr;
     p.P0 = a.f((size_t)N * d.pw);
-    p.P_alt = (!save && d.dn == 32) ? a.f((size_t)N * d.pw) : nullptr;   // second projection buffer of the one-launch step loop (persist32.hip)
-    p.barrier = a.i(4);
     p.Q0 = a.f((size_t)E * d.he);
     int hn_ = max_hidden(m.enc_node), he_ = max_hidden(m.enc_edge);
     if (save) {

@@ -675,7 +675,7 @@ int segment_reduce_csr2_x3(const SegReduce2 c[3], int64_t total_rows, hipStream_
             nb[i] = a[i].nseg > 0 && a[i].dim > 0 ? seg_short_geometry(a[i], &v[i]) : 0;
             if (nb[i] == 0) v[i] = true;
         }
-        if (!blk && v[0] && v[1] && v[2] && nb[0] + nb[1] + nb[2] > 0 && !getenv("MPNHIP_NO_SEG3")) {
+        if (!blk && v[0] && v[1] && v[2] && nb[0] + nb[1] + nb[2] > 0) {
             count_path(PC_SEG_SHORT3);
             hipLaunchKernelGGL(k_segment_reduce3, dim3(nb[0] + nb[1] + nb[2]), dim3(256), 0, stream, a[0], a[1], a[2], (int)nb[0], (int)(nb[0] + nb[1]));
             MPN_LAUNCH_CHECK();

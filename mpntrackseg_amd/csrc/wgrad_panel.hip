@@ -170,7 +170,7 @@ __device__ __forceinline__ void wp_block(const WpJob& J, const int tile, const i
     float4 bsum = make_float4(0.f, 0.f, 0.f, 0.f);
     // stages in flight under the current one's products: ONE for the wide variants (a stage is 20 - 24 registers there; two fit
     // without spills since the loops exist once per operand form, and measure the same: 118.7 / 113.2 us against 114.2 / 110.3 on
-    // the edge-level products, the step unchanged -- the kernel is not bound by its bytes in flight),
+    // the edge-level products, the step unchanged -- the kernel is not bound by its bytes in flight, see DESIGN_HISTORY.md section 4d),
     // two or four for the narrow ones (a <1, 1> stage is 16 rows x 128 columns = 8 KB per block: with one in flight the kernel waits out
     // the HBM latency every 16 rows -- 1.4 TB/s on the 32-d products of the reference's configuration)
     // (bf16 source rows: a stage is half the registers -- two in flight up to eight accumulator tiles; with ten they spill)
@@ -433,7 +433,7 @@ __device__ __forceinline__ void wp_block(const WpJob& J, const int tile, const i
         run(products1);
     } else {
         if (one) run(products1);
-        else if (D == 1 && J.lds2) run_pipelined();
+        else if (D == 1) run_pipelined();
         else run(products6);
     }
 
@@ -785,9 +785,7 @@ void wp_choose(int n_out, int k_in, int* variant, int* tiles_o, int* tiles_c, bo
 // 256 / 320; cfg-C 1.82 - 1.83 / 1.75 / 1.74 - 1.76 at 128 / 192 / 256; cfg-E (every job) 33.74 - 33.85 / 33.48 - 33.57 / 33.02 - 33.24 /
 // 33.47 - 33.58 / 33.40 - 33.57 at 128 / 160 / 192 / 224 / 256 (round 3, before the dispatch order: 5.43 / 5.37 / 5.29 at 320 / 192 / 128)
 int wp_target_blocks(bool batched) {
-    static const int alone = [] { const char* e = getenv("MPNHIP_WP_BLOCKS"); const int x = e ? atoi(e) : 0; return x >= 16 ? x : 512; }();
-    static const int shared = [] { const char* e = getenv("MPNHIP_WP_BLOCKS_BATCH"); const int x = e ? atoi(e) : 0; return x >= 16 ? x : 192; }();
-    return batched ? shared : alone;
+    return batched ? 192 : 512;
 }
 
 // rows per chunk / chunks per batch of one job: ~wp_target_blocks() blocks per job, chunks of at least 256 rows
@@ -801,8 +799,7 @@ void wp_plan(int64_t rows_expected, int64_t rows_upper, int nbatch, int tiles, b
     int want = wp_target_blocks(batched) / (nbatch * tiles);
     if (want < 1) want = 1;
     int64_t c = (rows_expected + want - 1) / want;
-    static const bool cap = !getenv("MPNHIP_WP_NO_LIGHT_CAP");
-    if (light && cap && c > 4096) c = 4096;
+    if (light && c > 4096) c = 4096;
     if (c < min_chunk) c = min_chunk;
     c = (c + WP_KB - 1) / WP_KB * WP_KB;
     *chunk = (int)c;
@@ -815,12 +812,8 @@ bool wp_light(int variant, int n_out, int k_in) { return variant < 16 && (size_t
 thread_local WpBatch* g_wp = nullptr;
 
 size_t wp_lds_bytes() {
-    // the largest variant image (BO + BC = 384): 39 KB.  MPNHIP_WP_LDS=<bytes> asks for more than the kernel uses: above 80 KB
-    // only ONE block of this kernel fits a CU, which leaves the other wave slot of every SIMD to the caller's stream (A-B switch)
-    // (two stage images: the pipelined split loop; MPNHIP_WP_ONE_IMAGE=1: the older two-barrier loop on one image)
-    static const size_t need = (getenv("MPNHIP_WP_ONE_IMAGE") ? 1 : 2) * 3 * WP_KB * wp_pitch(320, 64);
-    static const size_t ask = [] { const char* e = getenv("MPNHIP_WP_LDS"); const long x = e ? atol(e) : 0; return (size_t)(x > 0 ? x : 0); }();
-    return ask > need ? ask : need;
+    // two stage images (the pipelined split loop) of the largest variant (BO + BC = 384): 39 KB each
+    return 2 * 3 * WP_KB * wp_pitch(320, 64);
 }
 
 }  // namespace
@@ -907,12 +900,7 @@ bool wp_batch_add(const WpProduct* ps, int n) {
         if (!wp_eligible(ps[i])) return false;
         need += wp_slab_floats(ps[i].n_out, ps[i].k_in, ps[i].rows, ps[i].nbatch, ps[i].row_begin || ps[i].row_end, b->batched, ps[i].src16 != 0);
     }
-    if (b->used + need > b->slab_floats) {
-        if (getenv("MPNHIP_WP_TRACE"))
-            fprintf(stderr, "wp batch: job %d [%d x %d] rows %lld x%d needs %zu slab floats, %zu of %zu used\n", b->tab.njobs, ps[0].n_out, ps[0].k_in,
-                    (long long)ps[0].rows, ps[0].nbatch, need, b->used, b->slab_floats);
-        return false;
-    }
+    if (b->used + need > b->slab_floats) return false;
     for (int i = 0; i < n; ++i) {
         const WpProduct& p = ps[i];
         const bool ranged = p.row_begin || p.row_end;
@@ -928,7 +916,6 @@ bool wp_batch_add(const WpProduct* ps, int n) {
         J.dZ = p.dZ; J.H = p.H; J.ldz = p.ldz; J.ldh = p.ldh; J.z_bstride = p.z_bstride; J.h_bstride = p.h_bstride;
         J.H2 = p.H2; J.ldh2 = p.ldh2; J.h2_bstride = p.h2_bstride; J.csplit = p.H2 ? p.csplit : p.k_in;
         J.pieces = p.pieces == 1 ? 1 : 3;
-        J.lds2 = getenv("MPNHIP_WP_ONE_IMAGE") ? 0 : 1;
         J.row_begin = p.row_begin; J.row_end = p.row_end; J.m_static = p.rows; J.dz_idx = p.dz_idx; J.h_idx = p.h_idx;
         J.slab = b->slab + b->used;
         J.grad_w = p.grad_w; J.ldw = p.ldw; J.grad_b = p.grad_b;
@@ -965,23 +952,13 @@ int wp_batch_flush(hipStream_t s) {
     (void)attr_set;
     count_path(PC_TN_PANEL_LAUNCH);
     if (const char* e = getenv("MPNHIP_WP_DEBUG")) b->tab.debug = atoi(e); else b->tab.debug = 0;
-    static const bool trace = getenv("MPNHIP_WP_TRACE") != nullptr;   // diagnosis: the jobs of every flush, one line each
-    if (trace) {
-        for (int i = 0; i < b->tab.njobs; ++i) {
-            const WpJob& J = b->tab.job[i];
-            fprintf(stderr, "wp job %2d/%d: rows %lld x%d  [%d x %d]  variant %d tiles %dx%d chunk %d nsplit %d  %s pieces %d%s%s\n", i, b->tab.njobs,
-                    (long long)J.m_static, J.nbatch, J.n_out, J.k_in, J.variant, J.tiles_o, J.tiles_c, J.chunk, J.nsplit, J.src16 ? "bf16 rows" : "fp32 rows",
-                    J.pieces, (J.row_begin || J.row_end) ? " ranged" : "", (J.dz_idx || J.h_idx) ? " gathered" : "");
-        }
-    }
     // Blocks are dispatched in index order: the jobs with the longest blocks get the lowest indices, so that a launch ends on its short
     // blocks (longest-processing-time-first; the order the products were recorded in put the widest -- edge layer 0 / 1, the per-node
-    // projections -- last).  A block's length ~ its chunk's rows x the columns it stages per row.  MPNHIP_WP_NO_LPT=1: recording order.
+    // projections -- last).  A block's length ~ its chunk's rows x the columns it stages per row.
     // A launch of narrow jobs only (the reference's own widths, d = 32): every MFMA job re-tiled to <1, 1> (64 x 64) tiles -- slabs and
     // chunks are untouched by the tiling -- and run by the four-blocks-per-CU instantiation.  Taken when the re-tiling re-reads
     // at most 15 % more operand columns over the whole launch (a [80 x 32] product as 2 x 1 tiles reads its 32 H columns twice).
-    static const bool narrow_on = !getenv("MPNHIP_WP_NO_NARROW");
-    bool narrow = narrow_on && b->nblocks > 0;
+    bool narrow = b->nblocks > 0;
     const int narrow_lds = WP_NARROW_LDS;
     {
         double cols = 0.0, extra = 0.0;
@@ -1007,36 +984,33 @@ int wp_batch_flush(hipStream_t s) {
             count_path(PC_TN_PANEL_NARROW);
         }
     }
-    static const bool lpt = !getenv("MPNHIP_WP_NO_LPT");
-    {   // (block counts follow the tiling: recomputed here, in recording order unless re-indexed below)
+    {   // (block counts follow the tiling: recomputed here, then re-indexed below)
         int n1 = 0, n2 = 0;
         for (int i = 0; i < b->tab.njobs; ++i) {
-            WpJob& J = b->tab.job[i];
+            const WpJob& J = b->tab.job[i];
             const int nb = J.tiles_o * J.tiles_c * J.nsplit * J.nbatch;
-            if (J.variant >= 16) { J.block0 = n2; n2 += nb; } else { J.block0 = n1; n1 += nb; }
+            if (J.variant >= 16) n2 += nb; else n1 += nb;
         }
         b->nblocks = n1;
         b->nblocks2 = n2;
     }
-    if (lpt) {
-        for (int pass = 0; pass < 2; ++pass) {   // the row-panel kernel's jobs, then wgrad_rows16.hip's: each launch has its own indices
-            int idx[WP_MAX_JOBS], n = 0;
-            double w[WP_MAX_JOBS];
-            for (int i = 0; i < b->tab.njobs; ++i) {
-                const WpJob& J = b->tab.job[i];
-                if ((J.variant >= 16) != (pass == 1)) continue;
-                const double rows = (J.row_begin || J.row_end) ? 0.5 * J.chunk : (double)J.chunk;
-                w[n] = rows * ((double)J.n_out / J.tiles_o + (double)J.k_in / J.tiles_c);
-                idx[n++] = i;
-            }
-            for (int a = 1; a < n; ++a)   // (insertion sort, stable: equal weights keep the recording order)
-                for (int c = a; c > 0 && w[c] > w[c - 1]; --c) { std::swap(w[c], w[c - 1]); std::swap(idx[c], idx[c - 1]); }
-            int next = 0;
-            for (int a = 0; a < n; ++a) {
-                WpJob& J = b->tab.job[idx[a]];
-                J.block0 = next;
-                next += J.tiles_o * J.tiles_c * J.nsplit * J.nbatch;
-            }
+    for (int pass = 0; pass < 2; ++pass) {   // the row-panel kernel's jobs, then wgrad_rows16.hip's: each launch has its own indices
+        int idx[WP_MAX_JOBS], n = 0;
+        double w[WP_MAX_JOBS];
+        for (int i = 0; i < b->tab.njobs; ++i) {
+            const WpJob& J = b->tab.job[i];
+            if ((J.variant >= 16) != (pass == 1)) continue;
+            const double rows = (J.row_begin || J.row_end) ? 0.5 * J.chunk : (double)J.chunk;
+            w[n] = rows * ((double)J.n_out / J.tiles_o + (double)J.k_in / J.tiles_c);
+            idx[n++] = i;
+        }
+        for (int a = 1; a < n; ++a)   // (insertion sort, stable: equal weights keep the recording order)
+            for (int c = a; c > 0 && w[c] > w[c - 1]; --c) { std::swap(w[c], w[c - 1]); std::swap(idx[c], idx[c - 1]); }
+        int next = 0;
+        for (int a = 0; a < n; ++a) {
+            WpJob& J = b->tab.job[idx[a]];
+            J.block0 = next;
+            next += J.tiles_o * J.tiles_c * J.nsplit * J.nbatch;
         }
     }
     if (b->nblocks2 > 0) {

@@ -207,7 +207,10 @@ __device__ __forceinline__ void r16_block(const WpJob& J, const int tile_o, cons
             const int s2 = slot == 0 ? R16_NST - 1 : slot - 1;
             issue(r0 + (st + R16_NST - 1) * R16_KB, s2, R16_KB);
         }
-        if (!(dbg & 1)) products((unsigned)(slot * STAGE));
+#ifdef MPNHIP_WP_ABLATE
+        if (!(dbg & 1))   // (ablation build, MPNHIP_WP_DEBUG bit 1: no products)
+#endif
+            products((unsigned)(slot * STAGE));
         slot = slot == R16_NST - 1 ? 0 : slot + 1;
     }
     if (tail > 0) {
@@ -289,12 +292,11 @@ int r16_variant(int n_out, int k_in, int* tiles_o, int* tiles_c) {
     if (getenv("MPNHIP_NO_WGRAD_ROWS16") || n_out % 8 != 0 || k_in % 8 != 0) return -1;
     const int bo[4] = {640, 128, 448, 256}, bc[4] = {128, 640, 128, 256};
     int v = -1, to = 1, tc = 1;
-    static const bool tiled = !getenv("MPNHIP_NO_WGRAD_ROWS16_TILED");
     if (n_out > 512 && n_out <= 640 && k_in <= 128) v = 16;
     else if (n_out <= 128 && k_in > 512 && k_in <= 640) v = 17;
     else if (n_out > 256 && n_out <= 448 && k_in <= 128) v = 18;
     else if (n_out > 128 && n_out <= 256 && k_in > 256 && k_in <= 512) { tc = 2; v = 19; }
-    else if (tiled && ((n_out > 640 && k_in > 128) || (n_out > 128 && k_in > 640))) {
+    else if (((n_out > 640 && k_in > 128) || (n_out > 128 && k_in > 640))) {
         to = (n_out + 255) / 256;
         tc = (k_in + 255) / 256;
         v = 19;

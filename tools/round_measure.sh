@@ -12,7 +12,6 @@ python $R/bench.py --full --config E --precision bf16 --mode train --steps 3 --w
 python $R/tools/wgrad_bench.py --check --split > $O/wgrad_bench_split_$RND.txt 2>&1
 python $R/tools/gemm_bf16_bench.py > $O/gemm_bf16_bench_$RND.txt 2>&1
 python $R/tools/wgrad_rows16_bench.py --check > $O/wgrad_rows16_bench_$RND.txt 2>&1
-python $R/tools/gemm_ring_ablate.py > $O/gemm_ring_ablate_$RND.txt 2>&1
 python $R/tools/wgrad_bench.py --check > $O/wgrad_bench_fp32_$RND.txt 2>&1
 python $R/bench.py --full --mode fwd --no-cpu-baseline --no-extras 2>&1 | tail -1 > $O/bench_fwd_$RND.json
 python $R/bench.py --full --config C --mode train --no-cpu-baseline 2>&1 | tail -1 > $O/bench_cfgC_train_$RND.json
