@@ -396,6 +396,12 @@ int mpnhip_time_valid_conn_count(const int64_t* frame_num, int n_nodes, int64_t 
                                  void* workspace, size_t workspace_bytes, void* stream);
 int mpnhip_time_valid_conn_fill(const int64_t* frame_num, int n_nodes, int64_t max_frame_dist, const int64_t* offsets,
                                 int64_t n_pairs, int64_t* edge_ixs, void* stream);
+/* return_undirected=False (utils/graph.py:30-32): ALL ordered pairs (row, col), both directions of every pair, in the row-major
+ * order of torch.where on the dense condition.  Same two calls, same workspace size; edge_ixs [2, n_pairs] = row then col. */
+int mpnhip_time_valid_conn_directed_count(const int64_t* frame_num, int n_nodes, int64_t max_frame_dist, int64_t* offsets,
+                                          void* workspace, size_t workspace_bytes, void* stream);
+int mpnhip_time_valid_conn_directed_fill(const int64_t* frame_num, int n_nodes, int64_t max_frame_dist, const int64_t* offsets,
+                                         int64_t n_pairs, int64_t* edge_ixs, void* stream);
 /* compute_edge_feats_dict (utils/graph.py:90-124): edge_feats [E, 5] = secs_time_dists, norm_feet_x_dists,
  * norm_feet_y_dists, bb_height_dists, bb_width_dists (the dict's order) for edge_ixs [2, E]; per-node columns of
  * the detection frame: frame_num int64 [N], bb_height / bb_width / feet_x / feet_y float32 [N]. */
@@ -448,6 +454,36 @@ int mpnhip_window_accumulate(const float* logits, const int32_t* kept_ids, int64
                              float* overall_num_preds, void* stream);
 /* final_edge_preds = overall_edge_preds / overall_num_preds, NaN -> 0 (mpn_tracker.py:195-197). */
 int mpnhip_average_preds(const float* overall_preds, const float* overall_num, int64_t n, float* final_preds, void* stream);
+
+/* The rest of _evaluate_graph_in_batches (mpn_tracker.py:199-210): node masks, undirected merge, edge pruning.
+ *
+ * Node masks.  accumulate: overall_node_preds[node_begin + i, :] += sigmoid(mask_logits[i, :]) and
+ * overall_num_node_preds[node_begin + i] += 1 for the n_rows nodes of ONE window (mask_logits [n_rows, row_len] =
+ * mask_predictions[-1] of the window, row_len = H * W; the accumulators cover all n_nodes of the sequence).  Windows overlap in
+ * nodes: one call per window, in window order on one stream -- no atomics, a fixed summation order.  16-byte accesses when the
+ * window's block is 16-byte aligned and a multiple of 4 floats, a scalar path otherwise.
+ * average: node_preds [n_nodes, row_len] = overall_node_preds / overall_num_node_preds per row.  A node that was in no window
+ * gives 0 / 0 = NaN, as the reference's torch.div does (the reference zeroes NaN for EDGES only, mpn_tracker.py:204). */
+int mpnhip_node_mask_accumulate(const float* mask_logits, int64_t n_rows, int64_t row_len, int64_t node_begin, int64_t n_nodes,
+                                float* overall_node_preds, float* overall_num_node_preds, void* stream);
+int mpnhip_node_mask_average(const float* overall_node_preds, const float* overall_num_node_preds, int64_t n_nodes, int64_t row_len,
+                             float* node_preds, void* stream);
+/* to_undirected_graph (utils/graph.py:165-186) in two calls, because the caller allocates the results:
+ *   sort: keys (min(r, c) << 32) | max(r, c) of edge_index [2, E], one stable radix sort with the edge ids; inverse [E] (int32) =
+ *         column of every directed edge in the unique list (torch.unique's return_inverse), n_unique (device int32) = U.  n_nodes
+ *         > 0 promises every id < n_nodes and limits the sorted bits to what such ids need; 0 = ids up to 2^32 - 1.
+ *   fill: edge_index_u [2, U] (pairs with row < col in lexicographic order = torch.unique(dim=1)'s columns; NULL: skip) and, for
+ *         one attribute attr [E] (NULL: skip), attr_u [U] = mean over the pair's directed copies, summed in ascending edge id
+ *         and divided by their number (scatter_mean; for the normal two copies exactly (a + b) / 2).  One call per attribute;
+ *         `workspace` is the sort's, untouched in between.  The reference's assertion is the caller's E == 2 U. */
+size_t mpnhip_undirected_merge_workspace_bytes(int64_t n_edges);
+int mpnhip_undirected_merge_sort(const int64_t* edge_index, int64_t n_edges, int64_t n_nodes, int32_t* inverse, int32_t* n_unique,
+                                 void* workspace, size_t workspace_bytes, void* stream);
+int mpnhip_undirected_merge_fill(int64_t n_edges, int64_t n_unique, const void* workspace, size_t workspace_bytes,
+                                 int64_t* edge_index_u, const float* attr, float* attr_u, void* stream);
+/* flags [n] = preds[i] >= threshold (utils/graph.py:205; NaN -> 0 as in torch); the selection itself is mpnhip_compact +
+ * mpnhip_gather_edges / mpnhip_gather_rows. */
+int mpnhip_threshold_flags(const float* preds, int64_t n, float threshold, unsigned char* flags, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Measurement helpers used by bench.py (HIP events on the launch stream; these synchronise).

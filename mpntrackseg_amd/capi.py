@@ -117,6 +117,8 @@ SIGNATURES = {
     "mpnhip_time_valid_conn_workspace_bytes": (_Z, [_I]),
     "mpnhip_time_valid_conn_count": (_I, [_P, _I, _L, _P, _P, _Z, _P]),
     "mpnhip_time_valid_conn_fill": (_I, [_P, _I, _L, _P, _L, _P, _P]),
+    "mpnhip_time_valid_conn_directed_count": (_I, [_P, _I, _L, _P, _P, _Z, _P]),
+    "mpnhip_time_valid_conn_directed_fill": (_I, [_P, _I, _L, _P, _L, _P, _P]),
     "mpnhip_edge_features": (_I, [_P, _L, _I, _P, C.c_float, _P, _P, _P, _P, _P, _P]),
     "mpnhip_pairwise_distance": (_I, [_P, _L, _I, _P, _L, C.c_float, _P, _P]),
     "mpnhip_embedding_keep": (_I, [_P, _L, _L, _P, _L, _P, _P]),
@@ -130,6 +132,12 @@ SIGNATURES = {
     "mpnhip_gather_edges": (_I, [_P, _L, _P, _L, _L, _P, _P]),
     "mpnhip_window_accumulate": (_I, [_P, _P, _L, _P, _L, _I, _P, _P, _P]),
     "mpnhip_average_preds": (_I, [_P, _P, _L, _P, _P]),
+    "mpnhip_node_mask_accumulate": (_I, [_P, _L, _L, _L, _L, _P, _P, _P]),
+    "mpnhip_node_mask_average": (_I, [_P, _P, _L, _L, _P, _P]),
+    "mpnhip_undirected_merge_workspace_bytes": (_Z, [_L]),
+    "mpnhip_undirected_merge_sort": (_I, [_P, _L, _L, _P, _P, _P, _Z, _P]),
+    "mpnhip_undirected_merge_fill": (_I, [_L, _L, _P, _Z, _P, _P, _P, _P]),
+    "mpnhip_threshold_flags": (_I, [_P, _L, C.c_float, _P, _P]),
     "mpnhip_profile_enable": (_I, [_I]),
     "mpnhip_edge_chain_active": (_I, [C.POINTER(Model)]),
     "mpnhip_profile_read": (_I, [C.POINTER(C.c_float), C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(C.c_int),

@@ -14,8 +14,9 @@ namespace mpnhip {
 namespace {
 
 // pairs (i, j), i < j, with 0 < |frame[i] - frame[j]| <= max_dist (max_dist < 0: no upper limit).  One wavefront
-// per row i; lanes stride over j.  pass 0 counts, pass 1 writes at offs[i] in ascending j.
-template <bool FILL>
+// per row i; lanes stride over j.  pass 0 counts, pass 1 writes at offs[i] in ascending j.  DIRECTED: all ordered pairs
+// (i, j), j on either side of i (return_undirected=False, graph.py:30-32: torch.where's row-major order).
+template <bool FILL, bool DIRECTED = false>
 __global__ __launch_bounds__(256) void k_time_pairs(const int64_t* __restrict__ frame, int n, int64_t max_dist,
                                                     int64_t* __restrict__ counts, const int64_t* __restrict__ offs,
                                                     int64_t* __restrict__ out_row, int64_t* __restrict__ out_col) {
@@ -25,7 +26,7 @@ __global__ __launch_bounds__(256) void k_time_pairs(const int64_t* __restrict__ 
     const int64_t fi = frame[i];
     int64_t base = FILL ? offs[i] : 0;
     int64_t total = 0;
-    for (int j0 = i + 1; j0 < n; j0 += 64) {
+    for (int j0 = DIRECTED ? 0 : i + 1; j0 < n; j0 += 64) {
         const int j = j0 + lane;
         bool ok = false;
         if (j < n) {
@@ -135,9 +136,8 @@ extern "C" size_t mpnhip_time_valid_conn_workspace_bytes(int n_nodes) {
     return align_up(((size_t)n_nodes + 1) * 8, 256) + align_up(scan_temp(n_nodes + 1), 256) + 256;
 }
 
-extern "C" int mpnhip_time_valid_conn_count(const int64_t* frame_num, int n_nodes, int64_t max_frame_dist, int64_t* offsets,
-                                            void* workspace, size_t workspace_bytes, void* stream_) {
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
+static int time_pairs_count(bool directed, const int64_t* frame_num, int n_nodes, int64_t max_frame_dist, int64_t* offsets,
+                            void* workspace, size_t workspace_bytes, hipStream_t stream) {
     MPN_CHECK_ARG(n_nodes >= 0, "time_valid_conn: bad node count");
     MPN_CHECK_ARG(offsets, "time_valid_conn: null offsets");
     if (n_nodes == 0) {
@@ -154,24 +154,54 @@ extern "C" int mpnhip_time_valid_conn_count(const int64_t* frame_num, int n_node
     void* tmp = w + align_up(((size_t)n_nodes + 1) * 8, 256);
     size_t tmp_bytes = scan_temp(n_nodes + 1);
     MPN_HIP(hipMemsetAsync(counts, 0, ((size_t)n_nodes + 1) * 8, stream));
-    hipLaunchKernelGGL(k_time_pairs<false>, dim3((unsigned)((n_nodes + 3) / 4)), dim3(256), 0, stream, frame_num, n_nodes,
-                       max_frame_dist, counts, nullptr, nullptr, nullptr);
+    const dim3 grid((unsigned)((n_nodes + 3) / 4));
+    if (directed)
+        hipLaunchKernelGGL((k_time_pairs<false, true>), grid, dim3(256), 0, stream, frame_num, n_nodes, max_frame_dist, counts, nullptr,
+                           nullptr, nullptr);
+    else
+        hipLaunchKernelGGL((k_time_pairs<false, false>), grid, dim3(256), 0, stream, frame_num, n_nodes, max_frame_dist, counts, nullptr,
+                           nullptr, nullptr);
     MPN_LAUNCH_CHECK();
     // offsets[i] = pairs of rows < i; offsets[N] = number of pairs
     MPN_HIP(rocprim::exclusive_scan(tmp, tmp_bytes, counts, offsets, (int64_t)0, (size_t)n_nodes + 1, rocprim::plus<int64_t>(), stream));
     return MPNHIP_OK;
 }
 
-extern "C" int mpnhip_time_valid_conn_fill(const int64_t* frame_num, int n_nodes, int64_t max_frame_dist,
-                                           const int64_t* offsets, int64_t n_pairs, int64_t* edge_ixs, void* stream_) {
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
+static int time_pairs_fill(bool directed, const int64_t* frame_num, int n_nodes, int64_t max_frame_dist, const int64_t* offsets,
+                           int64_t n_pairs, int64_t* edge_ixs, hipStream_t stream) {
     MPN_CHECK_ARG(n_nodes >= 0 && n_pairs >= 0, "time_valid_conn: bad sizes");
     if (n_nodes == 0 || n_pairs == 0) return MPNHIP_OK;
     MPN_CHECK_ARG(frame_num && offsets && edge_ixs, "time_valid_conn: null pointer");
-    hipLaunchKernelGGL(k_time_pairs<true>, dim3((unsigned)((n_nodes + 3) / 4)), dim3(256), 0, stream, frame_num, n_nodes,
-                       max_frame_dist, nullptr, offsets, edge_ixs, edge_ixs + n_pairs);
+    const dim3 grid((unsigned)((n_nodes + 3) / 4));
+    if (directed)
+        hipLaunchKernelGGL((k_time_pairs<true, true>), grid, dim3(256), 0, stream, frame_num, n_nodes, max_frame_dist, nullptr, offsets,
+                           edge_ixs, edge_ixs + n_pairs);
+    else
+        hipLaunchKernelGGL((k_time_pairs<true, false>), grid, dim3(256), 0, stream, frame_num, n_nodes, max_frame_dist, nullptr, offsets,
+                           edge_ixs, edge_ixs + n_pairs);
     MPN_LAUNCH_CHECK();
     return MPNHIP_OK;
+}
+
+extern "C" int mpnhip_time_valid_conn_count(const int64_t* frame_num, int n_nodes, int64_t max_frame_dist, int64_t* offsets,
+                                            void* workspace, size_t workspace_bytes, void* stream) {
+    return time_pairs_count(false, frame_num, n_nodes, max_frame_dist, offsets, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int mpnhip_time_valid_conn_fill(const int64_t* frame_num, int n_nodes, int64_t max_frame_dist,
+                                           const int64_t* offsets, int64_t n_pairs, int64_t* edge_ixs, void* stream) {
+    return time_pairs_fill(false, frame_num, n_nodes, max_frame_dist, offsets, n_pairs, edge_ixs, static_cast<hipStream_t>(stream));
+}
+
+// return_undirected=False: the same two calls over all ordered pairs (both directions of every pair)
+extern "C" int mpnhip_time_valid_conn_directed_count(const int64_t* frame_num, int n_nodes, int64_t max_frame_dist, int64_t* offsets,
+                                                     void* workspace, size_t workspace_bytes, void* stream) {
+    return time_pairs_count(true, frame_num, n_nodes, max_frame_dist, offsets, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int mpnhip_time_valid_conn_directed_fill(const int64_t* frame_num, int n_nodes, int64_t max_frame_dist,
+                                                    const int64_t* offsets, int64_t n_pairs, int64_t* edge_ixs, void* stream) {
+    return time_pairs_fill(true, frame_num, n_nodes, max_frame_dist, offsets, n_pairs, edge_ixs, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int mpnhip_edge_features(const int64_t* edge_ixs, int64_t n_edges, int n_nodes, const int64_t* frame_num, float fps,

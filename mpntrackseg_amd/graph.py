@@ -63,10 +63,10 @@ def gather_edges(edge_index, ids, node_begin):
 @capi.on_tensor_device
 def get_time_valid_conn_ixs(frame_num, max_frame_dist, use_cuda=True, return_undirected=True):
     """utils/graph.py:6-37.  ``frame_num``: int tensor [N]; ``max_frame_dist``: int or ``'max'``.
-    Returns int64 ``[2, num_pairs]`` with row < col, on the device (the reference moves it back to the CPU)."""
+    Returns int64 ``[2, num_pairs]`` with row < col, on the device (the reference moves it back to the CPU); with
+    ``return_undirected=False`` the reference's ``(row, col)`` tuple over ALL ordered pairs (both directions, the row-major
+    order of ``torch.where``), on the device as well."""
     assert isinstance(max_frame_dist, (int, np.integer)) or max_frame_dist == 'max'
-    if not return_undirected:
-        raise MpnhipError("get_time_valid_conn_ixs: only return_undirected=True is implemented (the only use in the reference)")
     lib = capi.load()
     dev = frame_num.device if isinstance(frame_num, torch.Tensor) and frame_num.is_cuda else _dev()
     frames = torch.as_tensor(frame_num).to(device=dev, dtype=torch.int64).contiguous().view(-1)
@@ -75,13 +75,13 @@ def get_time_valid_conn_ixs(frame_num, max_frame_dist, use_cuda=True, return_und
     offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)
     nbytes = lib.mpnhip_time_valid_conn_workspace_bytes(n)
     ws = capi.workspace(nbytes, dev, "graph_build")
-    check(lib.mpnhip_time_valid_conn_count(ptr(frames), n, maxd, ptr(offsets), ptr(ws), ws.numel(), stream_ptr()),
-          "mpnhip_time_valid_conn_count")
+    count, fill = ((lib.mpnhip_time_valid_conn_count, lib.mpnhip_time_valid_conn_fill) if return_undirected else
+                   (lib.mpnhip_time_valid_conn_directed_count, lib.mpnhip_time_valid_conn_directed_fill))
+    check(count(ptr(frames), n, maxd, ptr(offsets), ptr(ws), ws.numel(), stream_ptr()), "mpnhip_time_valid_conn_count")
     n_pairs = int(offsets[n].item())  # the one host read: the result has to be allocated
     out = torch.empty((2, n_pairs), dtype=torch.int64, device=dev)
-    check(lib.mpnhip_time_valid_conn_fill(ptr(frames), n, maxd, ptr(offsets), n_pairs, ptr(out), stream_ptr()),
-          "mpnhip_time_valid_conn_fill")
-    return out
+    check(fill(ptr(frames), n, maxd, ptr(offsets), n_pairs, ptr(out), stream_ptr()), "mpnhip_time_valid_conn_fill")
+    return out if return_undirected else (out[0], out[1])
 
 
 @capi.on_tensor_device
@@ -160,3 +160,84 @@ def construct_graph(det_df, reid_embeddings, fps, max_frame_dist, edge_feats_to_
     return dict(edge_index=torch.cat((edge_ixs, torch.stack((edge_ixs[1], edge_ixs[0]))), dim=1),
                 edge_attr=torch.cat((edge_feats, edge_feats), dim=0),
                 reid_emb_dists=torch.cat((emb_dists, emb_dists)))
+
+
+@capi.on_tensor_device
+def merge_undirected(edge_index, attrs=(), num_nodes=None):
+    """Functional form of ``to_undirected_graph`` (utils/graph.py:176-186).  ``edge_index`` [2, E] lists every pair in both
+    directions; ``attrs``: float tensors [E].  Returns ``(edge_index_u [2, E / 2] int64, [attr_u ...], inverse [E] int32)``:
+    the pairs with row < col in lexicographic order (``torch.unique(dim=1)``'s columns), per attribute the mean over each
+    pair's directed copies (summed in ascending edge id: the same bits on every call, and for two copies the reference's
+    ``(a + b) / 2``), and the reference's ``orig_indices``.  ``num_nodes`` (optional; every id must be below it) limits the
+    bits the sort looks at.  Raises like the reference's assertion when E != 2 U."""
+    lib = capi.load()
+    capi.require_device(edge_index, *attrs)
+    dev = edge_index.device
+    ei = edge_index.to(torch.int64).contiguous()
+    E = ei.shape[1]
+    attrs = [capi.f32c(a).view(-1) for a in attrs]
+    for a in attrs:
+        assert a.numel() == E, "one attribute value per directed edge"
+    inverse = torch.empty(max(E, 1), dtype=torch.int32, device=dev)[:E]
+    count = torch.empty(1, dtype=torch.int32, device=dev)
+    ws = capi.workspace(lib.mpnhip_undirected_merge_workspace_bytes(E), dev, "undirected")
+    check(lib.mpnhip_undirected_merge_sort(ptr(ei), E, 0 if num_nodes is None else int(num_nodes), ptr(inverse), ptr(count), ptr(ws),
+                                           ws.numel(), stream_ptr()), "mpnhip_undirected_merge_sort")
+    U = int(count.item())  # the one host read: sizes the outputs and serves the reference's check
+    if E != 2 * U:
+        raise MpnhipError("Some edges were not duplicated (%d directed edges, %d distinct pairs)" % (E, U))
+    ei_u = torch.empty((2, U), dtype=torch.int64, device=dev)
+    outs = [torch.empty(U, dtype=torch.float32, device=dev) for _ in attrs]
+    for i in range(max(len(attrs), 1)):
+        a, o = (attrs[i], outs[i]) if attrs else (None, None)
+        check(lib.mpnhip_undirected_merge_fill(E, U, ptr(ws), ws.numel(), ptr(ei_u) if i == 0 else None, ptr(a), ptr(o),
+                                               stream_ptr()), "mpnhip_undirected_merge_fill")
+    return ei_u, outs, inverse
+
+
+@capi.on_tensor_device
+def prune_edges(edge_index, edge_preds, threshold=0.5):
+    """Functional form of the pruning in ``to_lightweight_graph`` (utils/graph.py:204-207): the edges with
+    ``edge_preds >= threshold`` (NaN is dropped, as in torch).  Returns ``(edge_index_kept [2, K], edge_preds_kept [K],
+    kept_ids [K] int32)``."""
+    lib = capi.load()
+    capi.require_device(edge_index, edge_preds)
+    ei = edge_index.to(torch.int64).contiguous()
+    p = capi.f32c(edge_preds).view(-1)
+    n = p.numel()
+    assert ei.shape[1] == n, "one score per edge"
+    if n == 0:
+        return ei, p, torch.empty(0, dtype=torch.int32, device=p.device)
+    flags = torch.empty(n, dtype=torch.uint8, device=p.device)
+    check(lib.mpnhip_threshold_flags(ptr(p), n, C.c_float(float(threshold)), ptr(flags), stream_ptr()), "mpnhip_threshold_flags")
+    kept, _ = compact(flags)
+    return gather_edges(ei, kept, 0), gather_rows(p.view(-1, 1), kept).view(-1), kept
+
+
+def to_undirected_graph(mot_graph, attrs_to_update=('edge_preds', 'edge_labels')):
+    """utils/graph.py:165-186, in place on ``mot_graph.graph_obj``: every pair of directed edges (i, j) / (j, i) becomes one
+    edge with i < j; the attributes in ``attrs_to_update`` that the graph has become the mean over the pair.  Returns the
+    inverse map (the reference's local ``orig_indices``) for callers that want it."""
+    g = mot_graph.graph_obj
+    names = [a for a in attrs_to_update if hasattr(g, a)]
+    ei_u, outs, inverse = merge_undirected(g.edge_index, [getattr(g, a) for a in names])
+    g.edge_index = ei_u
+    for a, o in zip(names, outs):
+        setattr(g, a, o)
+    return inverse
+
+
+def to_lightweight_graph(mot_graph, attrs_to_del=('reid_emb_dists', 'x', 'edge_attr', 'edge_labels')):
+    """utils/graph.py:188-207, in place on ``mot_graph.graph_obj``: ``node_names = arange(num_nodes)``, the attributes in
+    ``attrs_to_del`` are deleted, and only the edges with ``edge_preds >= 0.5`` stay."""
+    g = mot_graph.graph_obj
+    n = int(g.num_nodes)
+    try:
+        g.num_nodes = n   # (pins the count before ``x`` goes, graph.py:196; containers without a setter keep deriving it)
+    except AttributeError:
+        pass
+    g.node_names = torch.arange(n, device=g.edge_index.device)
+    for a in attrs_to_del:
+        if hasattr(g, a):
+            delattr(g, a)
+    g.edge_index, g.edge_preds, _ = prune_edges(g.edge_index, g.edge_preds, 0.5)

@@ -587,27 +587,36 @@ class MOTMPNet(nn.Module):
         E = logits.shape[1]
         L, k = int(self.num_enc_steps), int(self.num_class_steps)
         x_ext = getattr(data, 'x_ext', None)
-        mask_branch = self.has_mask_branch and x_ext is not None
         outputs_dict = {'classified_edges': [], 'mask_predictions': []}
-        if mask_branch:
-            latent_node_ext_feats = self.node_ext_encoder(x_ext)                       # mpn.py:356
-            initial_node_ext_feats = latent_node_ext_feats
         first_class_step = L - k + 1
-        for step in range(1, L + 1):
-            if mask_branch:
-                if self.reattach_initial_nodes:                                         # mpn.py:373
-                    latent_node_ext_feats = torch.cat((initial_node_ext_feats, latent_node_ext_feats), dim=1)
-                latent_node_ext_feats = self.MPAttentionNet.aggregate(latent_node_ext_feats, edge_index,
-                                                                      logits[step - 1], holder=data)   # mpn.py:377
-            if step >= first_class_step:
-                outputs_dict['classified_edges'].append(logits[step - 1].view(E, 1))
-                if mask_branch:
-                    outputs_dict['mask_predictions'].append(self.mask_predictor(x_ext, latent_node_ext_feats))
+        for step in range(max(first_class_step, 1), L + 1):
+            outputs_dict['classified_edges'].append(logits[step - 1].view(E, 1))
         if L == 0:
             outputs_dict['classified_edges'].append(logits[0].view(E, 1))
-            if mask_branch:
-                outputs_dict['mask_predictions'].append(self.mask_predictor(x_ext, latent_node_ext_feats))
+        if self.has_mask_branch and x_ext is not None:
+            outputs_dict['mask_predictions'] = self.mask_predictions(x_ext, edge_index, logits, holder=data)
         return outputs_dict
+
+    def mask_predictions(self, x_ext, edge_index, logits, holder=None, last_only=False):
+        """The attention / mask branch of ``forward`` (mpn.py:356,373-392) for hot-path ``logits`` [max(L, 1), E]: the list of
+        ``mask_predictions`` [N, 1, H, W], one per class step.  ``last_only``: evaluate ``mask_predictor`` for the last step
+        alone (a one-element list, bitwise the full list's ``[-1]``) -- inference reads nothing else (mpn_tracker.py:132), and
+        the attention chain over all the steps, which it depends on, still runs."""
+        L, k = int(self.num_enc_steps), int(self.num_class_steps)
+        latent_node_ext_feats = self.node_ext_encoder(x_ext)                           # mpn.py:356
+        initial_node_ext_feats = latent_node_ext_feats
+        first_class_step = L - k + 1
+        preds = []
+        for step in range(1, L + 1):
+            if self.reattach_initial_nodes:                                             # mpn.py:373
+                latent_node_ext_feats = torch.cat((initial_node_ext_feats, latent_node_ext_feats), dim=1)
+            latent_node_ext_feats = self.MPAttentionNet.aggregate(latent_node_ext_feats, edge_index,
+                                                                  logits[step - 1], holder=holder)   # mpn.py:377
+            if step >= first_class_step and (step == L or not last_only):
+                preds.append(self.mask_predictor(x_ext, latent_node_ext_feats))
+        if L == 0:
+            preds.append(self.mask_predictor(x_ext, latent_node_ext_feats))
+        return preds
 
 
 def avg_pool(x):

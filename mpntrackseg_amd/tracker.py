@@ -9,9 +9,18 @@ appeared in.  Windows are independent, so several can be evaluated in ONE forwar
 (``windows_per_launch``; the sub-graphs do not interact, ``tests/test_gpu_parity.py::test_batched_graphs``), and they
 shard round-robin over ranks (``rank`` / ``world_size``) with one final sum of the two accumulators.
 
-The projection of the averaged scores onto trajectories (``_project_graph_model_output`` and after: LP / greedy
-rounding, pandas bookkeeping) stays in the reference; so does the mask head's per-node averaging (``:191-192``),
-which consumes ``MOTMPNet.forward``'s ``mask_predictions`` unchanged."""
+``evaluate_sequence`` goes on to the end of ``_evaluate_graph_in_batches`` (``:199-210``): the mask branch of every window
+(``MOTMPNet.mask_predictions``, the mask head for the last step only) is accumulated per node and averaged over the windows a
+node was in (``node_preds``; a node that was in no window is 0 / 0 = NaN as in the reference, which zeroes NaN for edges
+only), the directed scores are merged into one score per undirected pair (``graph.merge_undirected``) and the pairs below
+``prune_threshold`` are dropped (``graph.prune_edges``) -- the object the reference hands to its projectors, built on the
+device.  ``evaluate_graph_in_batches`` stays the directed edge scores alone.
+
+The projection of the scores onto trajectories (``_project_graph_model_output`` and after: LP / greedy rounding, pandas
+bookkeeping) stays in the reference."""
+import collections
+import types
+
 import numpy as np
 import torch
 
@@ -68,11 +77,61 @@ def evaluate_graph_in_batches(model, x, edge_index, edge_attr, reid_emb_dists, f
     # the weights do not change during one sequence: pack their images once for all its windows
     with model.frozen_weights():
         return _evaluate_windows(model, x, edge_index, edge_attr, reid_emb_dists, frame_num_per_node, frames_per_graph, top_k_nns,
-                                 reciprocal_k_nns, set_pruned_edges_to_inactive, windows_per_launch, rank, world_size, reduce_fn)
+                                 reciprocal_k_nns, set_pruned_edges_to_inactive, windows_per_launch, rank, world_size, reduce_fn)[0]
+
+
+SequenceResult = collections.namedtuple('SequenceResult', ['final_edge_preds', 'edge_index', 'edge_preds', 'node_preds'])
+
+
+@torch.no_grad()
+@capi.on_tensor_device
+def evaluate_sequence(model, x, edge_index, edge_attr, reid_emb_dists, frame_num_per_node, frames_per_graph, top_k_nns,
+                      reciprocal_k_nns=True, set_pruned_edges_to_inactive=False, windows_per_launch=1, rank=0, world_size=1,
+                      reduce_fn=None, x_ext=None, prune_threshold=0.5):
+    """``_evaluate_graph_in_batches`` to its end (mpn_tracker.py:143-210).  Arguments as ``evaluate_graph_in_batches``, plus
+    ``x_ext`` [N, C, h, w] (the RoI features of the mask branch; optional) and ``prune_threshold``.  Returns a
+    ``SequenceResult``:
+
+    ``final_edge_preds`` [E]         directed, what ``evaluate_graph_in_batches`` returns for the same arguments
+    ``edge_index`` [2, K], ``edge_preds`` [K]   undirected (row < col, lexicographic) and pruned at ``prune_threshold``
+    ``node_preds`` [N, 1, H, W]      averaged mask probabilities; ``None`` without a mask branch or without ``x_ext``
+
+    With ``rank`` / ``world_size`` the node accumulators are summed by ``reduce_fn`` like the edge accumulators."""
+    capi.require_device(x, edge_index, edge_attr, reid_emb_dists, x_ext)
+    from .graph import merge_undirected, prune_edges
+    if not getattr(model, 'has_mask_branch', False):
+        x_ext = None
+    with model.frozen_weights():
+        final, node_preds = _evaluate_windows(model, x, edge_index, edge_attr, reid_emb_dists, frame_num_per_node, frames_per_graph,
+                                              top_k_nns, reciprocal_k_nns, set_pruned_edges_to_inactive, windows_per_launch, rank,
+                                              world_size, reduce_fn, x_ext=x_ext)
+    ei_u, (preds_u,), _ = merge_undirected(edge_index, [final], num_nodes=x.shape[0])
+    ei_k, preds_k, _ = prune_edges(ei_u, preds_u, prune_threshold)
+    return SequenceResult(final, ei_k, preds_k, node_preds)
+
+
+def _accumulate_node_masks(model, x_ext_b, ei_b, logits, group, node_acc):
+    """The mask branch of one launch (one window, or several as a block-diagonal batch: the attention aggregation and the
+    mask head run once; the holder lets the attention steps share one prepared graph), then one accumulation per window:
+    windows overlap in nodes, the stream orders the launches."""
+    lib = capi.load()
+    masks = model.mask_predictions(x_ext_b, ei_b, logits, holder=types.SimpleNamespace(), last_only=True)[-1]   # mpn_tracker.py:132
+    masks = capi.f32c(masks)
+    row_len = int(masks[0].numel())
+    if node_acc[0] is None:   # the spatial size of the masks is the model's to say
+        N = node_acc[2]
+        node_acc[0] = torch.zeros((N,) + tuple(masks.shape[1:]), dtype=torch.float32, device=masks.device)
+        node_acc[1] = torch.zeros(max(N, 1), dtype=torch.float32, device=masks.device)[:N]
+    r0 = 0
+    for (n0, n1) in group:
+        check(lib.mpnhip_node_mask_accumulate(ptr(masks[r0:r0 + (n1 - n0)]), n1 - n0, row_len, n0, node_acc[2], ptr(node_acc[0]),
+                                              ptr(node_acc[1]), stream_ptr()), "mpnhip_node_mask_accumulate")
+        r0 += n1 - n0
 
 
 def _evaluate_windows(model, x, edge_index, edge_attr, reid_emb_dists, frame_num_per_node, frames_per_graph, top_k_nns,
-                      reciprocal_k_nns, set_pruned_edges_to_inactive, windows_per_launch, rank, world_size, reduce_fn):
+                      reciprocal_k_nns, set_pruned_edges_to_inactive, windows_per_launch, rank, world_size, reduce_fn, x_ext=None):
+    """The window loop.  Returns ``(final_edge_preds, node_preds)``; ``node_preds`` is None unless ``x_ext`` is given."""
     lib = capi.load()
     edge_index = edge_index.to(torch.int64).contiguous()
     x = capi.f32c(x)
@@ -81,6 +140,7 @@ def _evaluate_windows(model, x, edge_index, edge_attr, reid_emb_dists, frame_num
     overall_num = torch.zeros(max(E, 1), dtype=torch.float32, device=x.device)[:E]
     windows = frame_windows(frame_num_per_node, frames_per_graph)[rank::world_size]
     L = max(int(model.num_enc_steps), 1)
+    node_acc = [None, None, int(x.shape[0])]   # overall_node_preds, overall_num_node_preds (allocated by the first window), N
     for g0 in range(0, len(windows), max(int(windows_per_launch), 1)):
         group = windows[g0:g0 + max(int(windows_per_launch), 1)]
         parts, node_off = [], 0
@@ -97,9 +157,14 @@ def _evaluate_windows(model, x, edge_index, edge_attr, reid_emb_dists, frame_num
             x_b = torch.cat([x[p[4]:p[5]] for p in parts], dim=0)
         if ei_b.shape[1] > 0:
             # (the window's indices were built here, inside [0, n): no error-flag read-back, the host keeps running ahead)
-            logits = model.hot_path(x_b, ei_b, attr_b, validate=False)[L - 1]  # classified_edges[-1] (mpn_tracker.py:132)
+            all_logits = model.hot_path(x_b, ei_b, attr_b, validate=False)
+            logits = all_logits[L - 1]  # classified_edges[-1] (mpn_tracker.py:132)
         else:
             logits = torch.empty(0, dtype=torch.float32, device=x.device)
+        if x_ext is not None:
+            all_logits = all_logits if ei_b.shape[1] > 0 else torch.empty((L, 0), dtype=torch.float32, device=x.device)
+            x_ext_b = x_ext[group[0][0]:group[0][1]] if len(group) == 1 else torch.cat([x_ext[n0:n1] for (n0, n1) in group], dim=0)
+            _accumulate_node_masks(model, x_ext_b, ei_b, all_logits, group, node_acc)
         e_off = 0
         for (ei_k, attr_k, win_ids, kept_ids, n0, n1) in parts:
             k = kept_ids.numel()
@@ -113,4 +178,39 @@ def _evaluate_windows(model, x, edge_index, edge_attr, reid_emb_dists, frame_num
         reduce_fn(overall_num)
     final = torch.empty_like(overall_preds)
     check(lib.mpnhip_average_preds(ptr(overall_preds), ptr(overall_num), E, ptr(final), stream_ptr()), "mpnhip_average_preds")
-    return final
+    if x_ext is None:
+        return final, None
+    return final, _average_node_masks(model, x_ext, node_acc, reduce_fn if world_size > 1 else None)
+
+
+def _average_node_masks(model, x_ext, node_acc, reduce_fn):
+    """final_node_preds = overall_node_preds / overall_num_node_preds (mpn_tracker.py:209-210)."""
+    lib = capi.load()
+    N = node_acc[2]
+    if node_acc[0] is None:
+        # this rank evaluated no window: the accumulators are zeros of the shape the mask head gives
+        hw = _mask_output_size(model, x_ext)
+        node_acc[0] = torch.zeros((N, 1) + hw, dtype=torch.float32, device=x_ext.device)
+        node_acc[1] = torch.zeros(max(N, 1), dtype=torch.float32, device=x_ext.device)[:N]
+    if reduce_fn is not None:
+        reduce_fn(node_acc[0])
+        reduce_fn(node_acc[1])
+    out = torch.empty_like(node_acc[0])
+    row_len = int(node_acc[0][0].numel()) if N else 0
+    check(lib.mpnhip_node_mask_average(ptr(node_acc[0]), ptr(node_acc[1]), N, row_len, ptr(out), stream_ptr()),
+          "mpnhip_node_mask_average")
+    return out
+
+
+def _mask_output_size(model, x_ext):
+    """(H, W) of ``model.mask_predictor``'s output for RoI features of ``x_ext``'s size, from its convolutions' geometry."""
+    mm = model.mask_predictor
+    hw = [int(x_ext.shape[2]), int(x_ext.shape[3])]
+    for part in (mm.feature_encoder, mm.mask_head, mm.mask_predictor):
+        for m in part.modules():
+            if isinstance(m, torch.nn.ConvTranspose2d):
+                hw = [(v - 1) * m.stride[i] - 2 * m.padding[i] + m.dilation[i] * (m.kernel_size[i] - 1) + m.output_padding[i] + 1
+                      for i, v in enumerate(hw)]
+            elif isinstance(m, torch.nn.Conv2d):
+                hw = [(v + 2 * m.padding[i] - m.dilation[i] * (m.kernel_size[i] - 1) - 1) // m.stride[i] + 1 for i, v in enumerate(hw)]
+    return tuple(hw)

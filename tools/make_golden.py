@@ -24,6 +24,8 @@ Fixtures:
   g12_dense_knn_{agg}.npz      dense reciprocal-kNN graph (E / N = 64, d = 32, 12 steps): sampled logits + reference autograd.
   g9_loss_metrics.npz          MOTNeuralSolver._compute_loss (+ autograd) and compute_perform_metrics / compute_constr_satisfaction_rate.
   g10_windows.npz              MPNTracker._evaluate_graph_in_batches on a synthetic sequence with the reference model.
+  g17_window_tail.npz          the same call to its END: the undirected merge, the pruned edge list and the averaged node masks, on g10's
+  (+ g17_window_tail_masks)    sequence and a longer one; get_time_valid_conn_ixs(return_undirected=False).  Only with --only g17.
   g7_graph_utils.npz           the reference's utils/graph.py on a synthetic detection table (synth.make_detections):
                                get_time_valid_conn_ixs ('max' and 3 frames), compute_edge_feats_dict, F.pairwise_distance,
                                get_knn_mask (reciprocal on/off; one direction per pair and both directions).
@@ -726,13 +728,12 @@ def gen_g16():
     print("g16 ok:", {k: float(v) for k, v in rec.items() if k.endswith(":loss")})
 
 
-def gen_g10():
-    """MPNTracker._evaluate_graph_in_batches + _predict_edges_and_masks (tracker/mpn_tracker.py:96-210) on a synthetic sequence,
-    driven with the REFERENCE model (mask branch included) on CPU.  Two redirections, because the code hard-codes the device:
-    the module's `torch.device('cuda')` resolves to the CPU and get_knn_mask is called with use_cuda=False."""
+def _tracker_redirections():
+    """The reference's tracker module with the two redirections its hard-coded device needs on a CPU: the module's
+    `torch.device('cuda')` resolves to the CPU and get_knn_mask is called with use_cuda=False.  ``captured["final_edge_preds"]`` is
+    the directed average just before to_undirected_graph."""
     EV, TR, PL = _import_tracking_stack()
     from mot_neural_solver.utils import graph as G
-    import torch.nn.functional as F
     mpn = import_reference()
 
     class _TorchProxy:
@@ -746,54 +747,147 @@ def gen_g10():
     real_knn = G.get_knn_mask
     TR.get_knn_mask = lambda **kw: real_knn(**dict(kw, use_cuda=False))
     captured = {}
-    real_undirected = TR.to_undirected_graph
+    real_undirected = G.to_undirected_graph
 
     def capture_then_undirected(mot_graph, attrs_to_update=("edge_preds", "edge_labels")):
         captured["final_edge_preds"] = mot_graph.graph_obj.edge_preds.clone()
         return real_undirected(mot_graph, attrs_to_update=attrs_to_update)
     TR.to_undirected_graph = capture_then_undirected
+    return TR, G, mpn, captured
 
+
+def _tracker_sequence(TR, G, mpn, det, inactive, recip, fpg, top_k, wrap_model=None):
+    """One synthetic sequence through MPNTracker._evaluate_graph_in_batches with the reference model (mask branch included).
+    Returns ``(full_graph, inputs)``: the MOTGraph stand-in after the call, and the arrays that went in."""
+    import pandas as pd
+    import torch.nn.functional as F
+    n = det["frame"].shape[0]
+    df = pd.DataFrame({k: det[k] for k in ("frame", "bb_height", "bb_width", "feet_x", "feet_y")})
+    ei = G.get_time_valid_conn_ixs(torch.from_numpy(det["frame"]), "max", use_cuda=False)
+    feats = G.compute_edge_feats_dict(ei, df, 25.0, use_cuda=False)
+    ef = torch.stack([feats[k] for k in ("secs_time_dists", "norm_feet_x_dists", "norm_feet_y_dists", "bb_height_dists",
+                                         "bb_width_dists")]).T
+    emb = torch.from_numpy(det["reid"])
+    dist = F.pairwise_distance(emb[ei[0]], emb[ei[1]]).view(-1, 1)
+    ef = torch.cat((ef, dist), dim=1)
+    edge_index = torch.cat((ei, torch.stack((ei[1], ei[0]))), dim=1)
+    edge_attr = torch.cat((ef, ef), dim=0)
+    emb_dists = torch.cat((dist, dist))
+    params = synth.model_params(32, 4, "sum", num_class_steps=2, node_in_dim=64)
+    W = synth.make_weights(params, seed=7, gain=0.6)
+    W.update(synth.make_mask_weights(seed=17))
+    full = dict(params)
+    full.update(MASK_PARAMS)
+    model = mpn.MOTMPNet(full)
+    model.load_state_dict({k: torch.from_numpy(v) for k, v in W.items()}, strict=True)
+    x = torch.from_numpy(det["x"]).view(n, 64, 1, 1)
+    x_ext = torch.from_numpy(synth.normal(9, (n, 256, 14, 14), stream=1, std=0.5))
+    from mot_neural_solver.data.mot_graph import Graph
+    graph_obj = Graph(x=x, x_ext=x_ext, edge_attr=edge_attr, reid_emb_dists=emb_dists, edge_index=edge_index)
+    full_graph = types.SimpleNamespace(frames=sorted(set(det["frame"].tolist())), graph_df=df, graph_obj=graph_obj,
+                                       frames_per_graph=fpg)
+    tracker = TR.MPNTracker(dataset=None, graph_model=model if wrap_model is None else wrap_model(model), use_gt=False,
+                            eval_params={"set_pruned_edges_to_inactive": inactive},
+                            dataset_params={"top_k_nns": top_k, "reciprocal_k_nns": recip, "gt_mask_spatial_size": [56, 56]})
+    tracker.full_graph = full_graph
+    tracker._evaluate_graph_in_batches()
+    inputs = {"frame": det["frame"], "x": det["x"], "edge_index": edge_index.numpy(), "edge_attr": edge_attr.numpy(),
+              "reid_emb_dists": emb_dists.numpy()}
+    return full_graph, inputs
+
+
+def gen_g10():
+    """MPNTracker._evaluate_graph_in_batches + _predict_edges_and_masks (tracker/mpn_tracker.py:96-210) on a synthetic sequence,
+    driven with the REFERENCE model (mask branch included) on CPU (redirections: _tracker_redirections)."""
+    TR, G, mpn, captured = _tracker_redirections()
     rec = {}
     for tag, inactive, recip, fpg, top_k in (("w1", False, True, 5, 6), ("w2", True, False, 4, 4)):
         det = synth.make_detections(frames=9, dets_lo=3, dets_hi=6, seed=5, emb_dim=32, node_in_dim=64, frame_stride=2)
-        n = det["frame"].shape[0]
-        import pandas as pd
-        df = pd.DataFrame({k: det[k] for k in ("frame", "bb_height", "bb_width", "feet_x", "feet_y")})
-        ei = G.get_time_valid_conn_ixs(torch.from_numpy(det["frame"]), "max", use_cuda=False)
-        feats = G.compute_edge_feats_dict(ei, df, 25.0, use_cuda=False)
-        ef = torch.stack([feats[k] for k in ("secs_time_dists", "norm_feet_x_dists", "norm_feet_y_dists", "bb_height_dists",
-                                             "bb_width_dists")]).T
-        emb = torch.from_numpy(det["reid"])
-        dist = F.pairwise_distance(emb[ei[0]], emb[ei[1]]).view(-1, 1)
-        ef = torch.cat((ef, dist), dim=1)
-        edge_index = torch.cat((ei, torch.stack((ei[1], ei[0]))), dim=1)
-        edge_attr = torch.cat((ef, ef), dim=0)
-        emb_dists = torch.cat((dist, dist))
-        params = synth.model_params(32, 4, "sum", num_class_steps=2, node_in_dim=64)
-        W = synth.make_weights(params, seed=7, gain=0.6)
-        W.update(synth.make_mask_weights(seed=17))
-        full = dict(params)
-        full.update(MASK_PARAMS)
-        model = mpn.MOTMPNet(full)
-        model.load_state_dict({k: torch.from_numpy(v) for k, v in W.items()}, strict=True)
-        x = torch.from_numpy(det["x"]).view(n, 64, 1, 1)
-        x_ext = torch.from_numpy(synth.normal(9, (n, 256, 14, 14), stream=1, std=0.5))
-        from mot_neural_solver.data.mot_graph import Graph
-        graph_obj = Graph(x=x, x_ext=x_ext, edge_attr=edge_attr, reid_emb_dists=emb_dists, edge_index=edge_index)
-        full_graph = types.SimpleNamespace(frames=sorted(set(det["frame"].tolist())), graph_df=df, graph_obj=graph_obj,
-                                           frames_per_graph=fpg)
-        tracker = TR.MPNTracker(dataset=None, graph_model=model, use_gt=False,
-                                eval_params={"set_pruned_edges_to_inactive": inactive},
-                                dataset_params={"top_k_nns": top_k, "reciprocal_k_nns": recip, "gt_mask_spatial_size": [56, 56]})
-        tracker.full_graph = full_graph
-        tracker._evaluate_graph_in_batches()
-        rec.update({f"{tag}:frame": det["frame"], f"{tag}:x": det["x"], f"{tag}:edge_index": edge_index.numpy(),
-                    f"{tag}:edge_attr": edge_attr.numpy(), f"{tag}:reid_emb_dists": emb_dists.numpy(),
-                    f"{tag}:final_edge_preds": captured["final_edge_preds"].numpy(),
+        full_graph, inputs = _tracker_sequence(TR, G, mpn, det, inactive, recip, fpg, top_k)
+        rec.update({f"{tag}:{k}": v for k, v in inputs.items()})
+        rec.update({f"{tag}:final_edge_preds": captured["final_edge_preds"].numpy(),
                     f"{tag}:cfg": np.array([int(inactive), int(recip), fpg, top_k], np.int64)})
-        print("g10", tag, "nodes", n, "edges", edge_index.shape[1], "mean pred", float(captured["final_edge_preds"].mean()),
-              "windows", len(full_graph.frames) - fpg + 1)
+        print("g10", tag, "nodes", det["frame"].shape[0], "edges", inputs["edge_index"].shape[1], "mean pred",
+              float(captured["final_edge_preds"].mean()), "windows", len(full_graph.frames) - fpg + 1)
     np.savez_compressed(os.path.join(GOLD, "g10_windows.npz"), **rec)
+
+
+G17_TOL = 2e-5          # the tolerance of the end-to-end edge scores (tests/test_gpu_tracker.py): pairs whose reference score is
+G17_MAX_NEAR = 0.01     # this close to 0.5 may flip in the kept set; at most this fraction of a case's pairs may be that close
+
+
+def gen_g17():
+    """MPNTracker._evaluate_graph_in_batches to its END (tracker/mpn_tracker.py:143-210): the directed scores as g10 captures them,
+    the graph after to_undirected_graph (edge_index, edge_preds and the inverse map scatter_mean receives), after
+    to_lightweight_graph (the edges with edge_preds >= 0.5), the averaged node masks and the largest |mask_predictions[-1]| any
+    window saw.  g10's two configurations on g10's sequence (s*) and on a longer one (l*: 16 frames, 104 nodes, 10,088 directed
+    edges; node_preds for the first 16 nodes plus a float64 sum per node).  The inputs of a sequence are stored once.  The full
+    node_preds of the short cases go into a file of their own (g17_window_tail_masks.npz) to keep every file under 1 MiB.  Also get_time_valid_conn_ixs(return_undirected=False) for 'max' and a bounded distance."""
+    TR, G, mpn, captured = _tracker_redirections()
+    real_light, real_mean = G.to_lightweight_graph, G.scatter_mean
+
+    def capture_mean(src, index, *a, **k):
+        captured["orig_indices"] = index.clone()
+        return real_mean(src, index, *a, **k)
+    G.scatter_mean = capture_mean
+
+    def capture_then_light(mot_graph, *a, **k):
+        captured["edge_index_u"] = mot_graph.graph_obj.edge_index.clone()
+        captured["edge_preds_u"] = mot_graph.graph_obj.edge_preds.clone()
+        return real_light(mot_graph, *a, **k)
+    TR.to_lightweight_graph = capture_then_light
+
+    class wrap_model:
+        """The model as MPNTracker sees it, recording the largest |mask_predictions[-1]| of the windows."""
+        def __init__(self, model):
+            self.model = model
+
+        def eval(self):
+            self.model.eval()
+            return self
+
+        def __call__(self, subgraph):
+            out = self.model(subgraph)
+            captured["max_abs_mask_logit"] = max(captured.get("max_abs_mask_logit", 0.0), float(out["mask_predictions"][-1].abs().max()))
+            return out
+
+    rec, masks = {}, {}
+    seqs = {"s": dict(frames=9, dets_lo=3, dets_hi=6, seed=5), "l": dict(frames=16, dets_lo=4, dets_hi=9, seed=11)}
+    for sq, kw in seqs.items():
+        det = synth.make_detections(emb_dim=32, node_in_dim=64, frame_stride=2, **kw)
+        rec[f"{sq}:seq"] = np.array([kw["frames"], kw["dets_lo"], kw["dets_hi"], kw["seed"]], np.int64)
+        for i, (inactive, recip, fpg, top_k) in enumerate(((False, True, 5, 6), (True, False, 4, 4))):
+            tag = f"{sq}{i + 1}"
+            captured.pop("max_abs_mask_logit", None)
+            full_graph, inputs = _tracker_sequence(TR, G, mpn, det, inactive, recip, fpg, top_k, wrap_model=wrap_model)
+            go = full_graph.graph_obj
+            rec.update({f"{sq}:{k}": v for k, v in inputs.items()})
+            pu = captured["edge_preds_u"].numpy()
+            near = int((np.abs(pu - 0.5) <= G17_TOL).sum())
+            assert near <= G17_MAX_NEAR * pu.size, (tag, near, pu.size)
+            node_preds = go.node_preds.numpy()
+            rec.update({f"{tag}:cfg": np.array([int(inactive), int(recip), fpg, top_k], np.int64),
+                        f"{tag}:final_edge_preds": captured["final_edge_preds"].numpy(),
+                        f"{tag}:edge_index_u": captured["edge_index_u"].numpy(), f"{tag}:edge_preds_u": pu,
+                        f"{tag}:orig_indices": captured["orig_indices"].numpy(),
+                        f"{tag}:edge_index": go.edge_index.numpy(), f"{tag}:edge_preds": go.edge_preds.numpy(),
+                        f"{tag}:max_abs_mask_logit": np.float64(captured["max_abs_mask_logit"])})
+            if sq == "s":
+                masks[tag] = node_preds
+            else:
+                rec[f"{tag}:node_preds_head"] = node_preds[:16]
+                rec[f"{tag}:node_preds_sum"] = node_preds.astype(np.float64).sum(axis=(1, 2, 3))
+            gap = np.abs(pu - 0.5)
+            print("g17", tag, "nodes", node_preds.shape[0], "edges", inputs["edge_index"].shape[1], "kept", go.edge_index.shape[1],
+                  "pairs within tol of 0.5:", near, "smallest gaps", np.sort(gap)[:2], "node preds", float(node_preds.min()),
+                  float(node_preds.max()), "max |mask logit|", captured["max_abs_mask_logit"])
+        if sq == "l":
+            for name, mfd in (("tv_max", "max"), ("tv_3", 3)):
+                row, col = G.get_time_valid_conn_ixs(torch.from_numpy(det["frame"]), mfd, use_cuda=False, return_undirected=False)
+                rec[f"{name}:row"], rec[f"{name}:col"] = row.numpy(), col.numpy()
+                rec[f"{name}:max_frame_dist"] = np.int64(-1 if mfd == "max" else mfd)
+    np.savez_compressed(os.path.join(GOLD, "g17_window_tail.npz"), **rec)
+    np.savez_compressed(os.path.join(GOLD, "g17_window_tail_masks.npz"), **{f"{tag}:node_preds": arr for tag, arr in masks.items()})
 
 
 def gen_g14():
@@ -865,6 +959,7 @@ def main():
     if "g14" in only: gen_g14()
     if "g15" in only: gen_g15(mpn)
     if "g16" in only: gen_g16()
+    if "g17" in only: gen_g17()
 
 
 if __name__ == "__main__":
