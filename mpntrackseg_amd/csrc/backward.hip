@@ -497,94 +497,106 @@ struct Operand {        // one side of a (batched) weight-gradient product
     int64_t bstride;    // floats between consecutive batches (0: same block every batch)
 };
 
-// set by mpnhip_backward for a model in MPNHIP_PREC_FP32_SPLIT: weight gradients in the three-piece operand form (wgrad_panel.hip)
-static thread_local bool g_wgrad_split = false;
-// MPNHIP_PREC_BF16 (training): every product of the backward rounds its operands to bf16 like the forward's -- the activation
-// gradients dH = dZ W through the K-contiguous bf16 GEMM (the weight block transposed into g_wt_scratch first: the kernel takes
-// nn.Linear-style [out][in] operands), the weight gradients through the row-panel kernel with ONE bf16 piece per operand
-static thread_local bool g_bwd_bf16 = false;
-// set around the products whose operands are bf16 rows (WpProduct::src16): the dZ blocks / saved activations of the fused bf16 chain
-static thread_local bool g_wg_src16 = false;
-struct Src16Scope { bool old; explicit Src16Scope(bool v) : old(g_wg_src16) { g_wg_src16 = v; } ~Src16Scope() { g_wg_src16 = old; } };
-static thread_local float* g_wt_scratch = nullptr;
-static thread_local size_t g_wt_scratch_floats = 0;
-// ... and two blocks that are KEPT for the whole backward: the node update's and the per-node projections' weights are the operands of
-// an activation-gradient product in every step (22 transpositions of the same two blocks per cfg-E step before round 4, 25 - 30 us each)
-struct WtKeep { float* wt; size_t floats; bool valid; unsigned short* wt16; };
-static thread_local WtKeep g_wt_keep[2] = {{nullptr, 0, false, nullptr}, {nullptr, 0, false, nullptr}};
+// one weight-gradient product  dW += dZ^T [H | H2] (+ bias)  for one or two direction groups, over nbatch row blocks: the shared part,
+// then grad_w / grad_b / the device-side row range of each group (g[1].grad_w == nullptr: one group)
+struct WgGroup { float* grad_w; float* grad_b; RowRange rr; };
+struct WgProduct {
+    Operand dZ;
+    const int* dz_idx;  // optional row gather
+    Operand H, H2;      // H2: the columns >= csplit of the layer input (H2.p == nullptr: none, csplit unused)
+    int csplit;
+    const int* h_idx;   // optional row gather
+    int n_out, k_in;
+    int64_t ldw, rows;
+    int nbatch;
+    bool src16;         // the operands are bf16 rows (WpProduct::src16): the dZ blocks / saved activations of the fused bf16 chain
+    WgGroup g[2];
+};
 
-// dW += dZ^T [H | H2] (+ bias) for one or two groups, over nbatch row blocks
-static int weight_grad(const BwdPlan& p, float* slab_base, int ngroups, Operand dZ, const int* dz_idx, Operand H, Operand H2, int csplit,
-                       const int* h_idx, int n_out, int k_in, float* const gw[2], int64_t ldw, float* const gb[2],
-                       const RowRange rr[2], int64_t rows, int nbatch, hipStream_t s) {
-    if (g_wgrad_split && rows > 0) {
-        // MPNHIP_PREC_FP32_SPLIT: the row-panel kernel (wgrad_panel.hip) -- recorded into the open batch (all products of a group of
-        // steps: one product launch + one slab-sum launch), or run as a batch of its own
+// ... two weight blocks that are KEPT transposed for the whole backward: the node update's and the per-node projections' weights are the
+// operands of an activation-gradient product in every step (22 transpositions of the same two blocks per cfg-E step before round 4,
+// 25 - 30 us each)
+struct WtKeep { float* wt; size_t floats; bool valid; unsigned short* wt16; };
+// what the helpers of one mpnhip_backward_flags call share (built once, after plan_backward; it lives in that call's frame)
+struct BwdCtx {
+    const BwdPlan* p;
+    // a model in MPNHIP_PREC_FP32_SPLIT / _WGSPLIT / _BF16: weight gradients in the three-piece operand form (wgrad_panel.hip)
+    bool wgrad_split;
+    // MPNHIP_PREC_BF16 (training): every product of the backward rounds its operands to bf16 like the forward's -- the activation
+    // gradients dH = dZ W through the K-contiguous bf16 GEMM (the weight block transposed into p->wt_scratch first: the kernel takes
+    // nn.Linear-style [out][in] operands), the weight gradients through the row-panel kernel with ONE bf16 piece per operand
+    bool bf16;
+    WtKeep wt_keep[2];  // (valid only inside this call: the blocks live in this call's workspace)
+};
+
+// batch: where the product is recorded (all products of a group of steps: one product launch + one slab-sum launch); nullptr: run now,
+// as a batch of its own on slab_base
+static int weight_grad(const BwdCtx& c, float* slab_base, WpBatch* batch, const WgProduct& w, hipStream_t s) {
+    const int ngroups = w.g[1].grad_w ? 2 : 1;
+    if (c.wgrad_split && w.rows > 0) {
+        // MPNHIP_PREC_FP32_SPLIT: the row-panel kernel (wgrad_panel.hip)
         WpProduct wp[2];
         for (int q = 0; q < ngroups; ++q)
-            wp[q] = {dZ.p, dZ.ld, dZ.bstride, H.p, H.ld, H.bstride, rr ? rr[q].begin : nullptr, rr ? rr[q].end : nullptr, rows, nbatch,
-                     n_out, k_in, gw[q], ldw, gb ? gb[q] : nullptr, dz_idx, h_idx, H2.p, H2.ld, H2.bstride, csplit, g_bwd_bf16 ? 1 : 3,
-                     g_wg_src16 ? 1 : 0};
-        if (wp_batch_open()) {
-            if (wp_batch_add(wp, ngroups)) return MPNHIP_OK;
+            wp[q] = {w.dZ.p, w.dZ.ld, w.dZ.bstride, w.H.p, w.H.ld, w.H.bstride, w.g[q].rr.begin, w.g[q].rr.end, w.rows, w.nbatch,
+                     w.n_out, w.k_in, w.g[q].grad_w, w.ldw, w.g[q].grad_b, w.dz_idx, w.h_idx, w.H2.p, w.H2.ld, w.H2.bstride, w.csplit,
+                     c.bf16 ? 1 : 3, w.src16 ? 1 : 0};
+        if (batch) {
+            if (wp_batch_add(batch, wp, ngroups)) return MPNHIP_OK;
             bool eligible = true;
             for (int q = 0; q < ngroups; ++q) eligible = eligible && wp_eligible(wp[q]);
             if (eligible) {
-                // the open batch is full (more than WP_MAX_JOBS jobs in a group of steps: deeper MLPs; or its slab region): run it
+                // the batch is full (more than WP_MAX_JOBS jobs in a group of steps: deeper MLPs; or its slab region): run it
                 // and go on in a fresh one rather than switch kernels in the middle of a group
                 int st = MPNHIP_OK;
-                if (wp_batch_roll(&st) && wp_batch_add(wp, ngroups)) return MPNHIP_OK;
+                if (wp_batch_roll(batch, &st) && wp_batch_add(batch, wp, ngroups)) return MPNHIP_OK;
                 MPN_TRY(st);
             }
-            // not a shape / alignment of the row-panel kernel (or the batch cannot be rolled): the fp32 kernel below, counted
-            count_path(PC_TN_PANEL_FALLBACK);
-            if (g_wg_src16) { set_error("backward (bf16): a product over bf16 rows [%d x %d] is not covered by the row-panel kernel", n_out, k_in); return MPNHIP_ERR_UNSUPPORTED; }
         } else {
             WpBatch own;
-            WpBatchGuard guard;
-            wp_batch_begin(&own, slab_base, 2 * p.slab_floats_per_group, false);
-            if (wp_batch_add(wp, ngroups)) return wp_batch_flush(s);
-            wp_batch_abort();
-            count_path(PC_TN_PANEL_FALLBACK);
-            if (g_wg_src16) { set_error("backward (bf16): a product over bf16 rows [%d x %d] is not covered by the row-panel kernel", n_out, k_in); return MPNHIP_ERR_UNSUPPORTED; }
+            wp_batch_init(&own, slab_base, 2 * c.p->slab_floats_per_group, false, nullptr);
+            if (wp_batch_add(&own, wp, ngroups)) return wp_batch_flush(&own, s);
         }
+        // not a shape / alignment of the row-panel kernel (or the batch cannot be rolled): the fp32 kernel below, counted
+        count_path(PC_TN_PANEL_FALLBACK);
+        if (w.src16) { set_error("backward (bf16): a product over bf16 rows [%d x %d] is not covered by the row-panel kernel", w.n_out, w.k_in); return MPNHIP_ERR_UNSUPPORTED; }
     }
+    const bool ranged = w.g[0].rr.begin || w.g[0].rr.end;
     TnArgs a = {};
     a.ngroups = ngroups;
-    a.n_out = n_out;
-    a.k_in = k_in;
-    a.csplit = H2.p ? csplit : k_in;
-    a.m_upper = rows;
-    a.nbatch = nbatch;
+    a.n_out = w.n_out;
+    a.k_in = w.k_in;
+    a.csplit = w.H2.p ? w.csplit : w.k_in;
+    a.m_upper = w.rows;
+    a.nbatch = w.nbatch;
     // (with device-side row ranges the groups partition the `rows` rows between them; without, each group covers all of them)
-    a.flops = 2.0 * (double)rows * (rr ? 1 : ngroups) * nbatch * n_out * k_in;
+    a.flops = 2.0 * (double)w.rows * (ranged ? 1 : ngroups) * w.nbatch * w.n_out * w.k_in;
     for (int q = 0; q < ngroups; ++q) {
         TnGroup& g = a.g[q];
-        g.dZ = dZ.p;
-        g.ldz = dZ.ld;
-        g.z_bstride = dZ.bstride;
-        g.dz_idx = dz_idx;
-        g.H = H.p;
-        g.ldh = H.ld;
-        g.h_bstride = H.bstride;
-        g.H2 = H2.p;
-        g.ldh2 = H2.ld;
-        g.h2_bstride = H2.bstride;
-        g.h_idx = h_idx;
-        g.row_begin = rr ? rr[q].begin : nullptr;
-        g.row_end = rr ? rr[q].end : nullptr;
-        g.m_static = rows;
-        g.slab = slab_base + q * p.slab_floats_per_group;
-        g.grad_w = gw[q];
-        g.ldw = ldw;
-        g.grad_b = gb ? gb[q] : nullptr;
+        g.dZ = w.dZ.p;
+        g.ldz = w.dZ.ld;
+        g.z_bstride = w.dZ.bstride;
+        g.dz_idx = w.dz_idx;
+        g.H = w.H.p;
+        g.ldh = w.H.ld;
+        g.h_bstride = w.H.bstride;
+        g.H2 = w.H2.p;
+        g.ldh2 = w.H2.ld;
+        g.h2_bstride = w.H2.bstride;
+        g.h_idx = w.h_idx;
+        g.row_begin = w.g[q].rr.begin;
+        g.row_end = w.g[q].rr.end;
+        g.m_static = w.rows;
+        g.slab = slab_base + q * c.p->slab_floats_per_group;
+        g.grad_w = w.g[q].grad_w;
+        g.ldw = w.ldw;
+        g.grad_b = w.g[q].grad_b;
     }
     return launch_gemm_tn(a, s);
 }
 
 // C = mask( A B (+ C) ) with B given as weight rows: B[k][n] = W[k * ldw + n]  (dH = dZ W)
 // a16: A is bf16 rows in memory (unsigned shorts behind the pointer, lda counts them; MPNHIP_PREC_BF16 only: gemm_bf16.hip reads them)
-static int act_grad(int ngroups, const float* A, int64_t lda, const int* a_idx, const float* const W[2], int64_t ldw, int K,
+static int act_grad(BwdCtx& c, int ngroups, const float* A, int64_t lda, const int* a_idx, const float* const W[2], int64_t ldw, int K,
                     int N, float* C, int64_t ldc, const int* c_idx, const float* mask, int64_t ldmask, int accumulate,
                     const RowRange rr[2], int64_t rows, hipStream_t s, int keep = -1, bool a16 = false) {
     GemmArgs a = {};
@@ -595,8 +607,8 @@ static int act_grad(int ngroups, const float* A, int64_t lda, const int* a_idx, 
     a.relu = 0;
     a.accumulate = accumulate;
     a.m_upper = rows;
-    const bool bf16 = g_bwd_bf16 && rows > 0 && (size_t)ngroups * K * N <= g_wt_scratch_floats;
-    if (g_bwd_bf16 && !bf16 && rows > 0) { set_error("backward (bf16): weight block %d x %d exceeds the transposition scratch", K, N); return MPNHIP_ERR_WORKSPACE; }
+    const bool bf16 = c.bf16 && rows > 0 && (size_t)ngroups * K * N <= c.p->wt_scratch_floats;
+    if (c.bf16 && !bf16 && rows > 0) { set_error("backward (bf16): weight block %d x %d exceeds the transposition scratch", K, N); return MPNHIP_ERR_WORKSPACE; }
     for (int q = 0; q < ngroups; ++q) {
         GemmGroup& g = a.g[q];
         init_group(g);
@@ -608,10 +620,11 @@ static int act_grad(int ngroups, const float* A, int64_t lda, const int* a_idx, 
         g.ldb = ldw;
         if (bf16) {
             // WT[n][k] = W[k][n]: the block as an nn.Linear weight of the product C = A WT^T (bf16 operands, K-contiguous)
-            float* wt = g_wt_scratch + (size_t)q * K * N;
-            WtKeep* kp = (keep >= 0 && ngroups == 1 && g_wt_keep[keep].wt && (size_t)K * N <= g_wt_keep[keep].floats) ? &g_wt_keep[keep] : nullptr;
+            float* wt = c.p->wt_scratch + (size_t)q * K * N;
+            WtKeep* kp = (keep >= 0 && ngroups == 1 && c.wt_keep[keep].wt && (size_t)K * N <= c.wt_keep[keep].floats) ? &c.wt_keep[keep] : nullptr;
             if (kp) wt = kp->wt;
-            if (!kp || !kp->valid) MPN_TRY(transpose_padded(W[q], ldw, 0, K, N, wt, K, N, s));
+            // (launched now, not recorded: the product below reads the block)
+            if (!kp || !kp->valid) MPN_TRY(transpose_padded(W[q], ldw, 0, K, N, wt, K, N, nullptr, s));
             // the kept blocks also as bf16 rows (rounded once per backward instead of in every block of every step's product)
             // (N % 4: launch_gemm's bf16-row path needs whole 16-byte result vectors; otherwise the fp32 image on the register-staged path)
             const bool img16 = kp && kp->wt16 && K % 8 == 0 && N % 4 == 0 && ((size_t)K * N) % 4 == 0;
@@ -630,36 +643,33 @@ static int act_grad(int ngroups, const float* A, int64_t lda, const int* a_idx, 
         g.row_begin = rr ? rr[q].begin : nullptr;
         g.row_end = rr ? rr[q].end : nullptr;
     }
-    if (bf16) {
-        struct Scope { int old; Scope() : old(gemm_precision()) { set_gemm_precision(MPNHIP_PREC_BF16); } ~Scope() { set_gemm_precision(old); } } scope;
-        return launch_gemm(a, A_KCONTIG, B_KCONTIG, s);
-    }
-    return launch_gemm(a, A_KCONTIG, B_NCONTIG, s);
+    if (bf16) return launch_gemm(a, A_KCONTIG, B_KCONTIG, MPNHIP_PREC_BF16, s);
+    return launch_gemm(a, A_KCONTIG, B_NCONTIG, MPNHIP_PREC_FP32, s);
 }
 
 // dZ_{i-1} = (dZ_i W_i) (.) [H_{i-1} > 0] for i = n-1 .. 1.  dz[i] / hidden[i]: this step's blocks.
-static int mlp_chain_backward(const mpnhip_mlp& m0, const mpnhip_mlp* m1, float* const* dz, float* const* hidden,
+static int mlp_chain_backward(BwdCtx& c, const mpnhip_mlp& m0, const mpnhip_mlp* m1, float* const* dz, float* const* hidden,
                               const RowRange* rr, int64_t rows, hipStream_t s) {
     const int ng = m1 ? 2 : 1;
     for (int i = m0.n_layers - 1; i >= 1; --i) {
         const int n_out = m0.out_dims[i], k_in = m0.out_dims[i - 1];
         const float* Wq[2] = {m0.weight[i], m1 ? m1->weight[i] : nullptr};
-        MPN_TRY(act_grad(ng, dz[i], n_out, nullptr, Wq, k_in, n_out, k_in, dz[i - 1], k_in, nullptr,
+        MPN_TRY(act_grad(c, ng, dz[i], n_out, nullptr, Wq, k_in, n_out, k_in, dz[i - 1], k_in, nullptr,
                          k_in != 1 ? hidden[i - 1] : nullptr, k_in, 0, rr, rows, s));
     }
     return MPNHIP_OK;
 }
 
 // batched weight gradients of layers >= 1 of an MLP whose dZ / hidden blocks repeat every step
-static int mlp_weight_grads(const BwdPlan& p, float* slab_base, const mpnhip_mlp& m0, const mpnhip_mlp* m1, float* const* dz_all,
-                            float* const* hidden0, int64_t hidden_bstride, const RowRange* rr, int64_t rows, int nbatch,
-                            hipStream_t s) {
+static int mlp_weight_grads(const BwdCtx& c, float* slab_base, WpBatch* batch, const mpnhip_mlp& m0, const mpnhip_mlp* m1,
+                            float* const* dz_all, float* const* hidden0, int64_t hidden_bstride, const RowRange* rr, int64_t rows,
+                            int nbatch, hipStream_t s) {
     for (int i = m0.n_layers - 1; i >= 1; --i) {
         const int n_out = m0.out_dims[i], k_in = m0.out_dims[i - 1];
-        float* gw[2] = {m0.grad_weight[i], m1 ? m1->grad_weight[i] : nullptr};
-        float* gb[2] = {m0.grad_bias[i], m1 ? m1->grad_bias[i] : nullptr};
-        MPN_TRY(weight_grad(p, slab_base, m1 ? 2 : 1, {dz_all[i], n_out, rows * n_out}, nullptr, {hidden0[i - 1], k_in, hidden_bstride},
-                            {nullptr, 0, 0}, k_in, nullptr, n_out, k_in, gw, k_in, gb, rr, rows, nbatch, s));
+        WgProduct w = {.dZ = {dz_all[i], n_out, rows * n_out}, .H = {hidden0[i - 1], k_in, hidden_bstride}, .n_out = n_out, .k_in = k_in,
+                       .ldw = k_in, .rows = rows, .nbatch = nbatch, .g = {{m0.grad_weight[i], m0.grad_bias[i], rr ? rr[0] : RowRange{}}}};
+        if (m1) w.g[1] = {m1->grad_weight[i], m1->grad_bias[i], rr[1]};
+        MPN_TRY(weight_grad(c, slab_base, batch, w, s));
     }
     return MPNHIP_OK;
 }
@@ -720,37 +730,37 @@ struct Rows16Later {
         return d;
     }
 };
-static thread_local Rows16Later* g_rows16_later = nullptr;
 
-// one weight-gradient product of an encoder layer: over bf16 rows when a Rows16Later is open and the shape is one of the tiled ones
-static int encoder_weight_grad(const BwdPlan& p, const float* dz, const float* h, int n_out, int k_in, float* gw0, float* gb0, int64_t rows,
-                               hipStream_t s) {
-    float* gw[2] = {gw0, nullptr};
-    float* gb[2] = {gb0, nullptr};
-    Rows16Later* L16 = g_rows16_later;
+// one weight-gradient product of an encoder layer, recorded into the tail batch (or nullptr: run now): over bf16 rows when a
+// Rows16Later is given (with the batch its roundings run ahead of) and the shape is one of the tiled ones
+static int encoder_weight_grad(const BwdCtx& c, WpBatch* batch, Rows16Later* L16, const float* dz, const float* h, int n_out, int k_in,
+                               float* gw, float* gb, int64_t rows, hipStream_t s) {
+    WgProduct w = {.dZ = {dz, n_out, 0}, .H = {h, k_in, 0}, .n_out = n_out, .k_in = k_in, .ldw = k_in, .rows = rows, .nbatch = 1, .g = {{gw, gb}}};
     int to = 1, tc = 1;
-    if (L16 && wp_batch_open() && (int64_t)n_out * k_in >= 65536 && r16_variant(n_out, k_in, &to, &tc) >= 16 && L16->n + 2 <= 2 * MPNHIP_MAX_LAYERS &&
+    if (L16 && batch && (int64_t)n_out * k_in >= 65536 && r16_variant(n_out, k_in, &to, &tc) >= 16 && L16->n + 2 <= 2 * MPNHIP_MAX_LAYERS &&
         L16->used + (size_t)rows * (n_out + k_in) <= L16->pool_elems) {
         const unsigned short* z16 = L16->take(dz, rows * n_out);
         const unsigned short* h16 = z16 ? L16->take(h, rows * k_in) : nullptr;
         if (z16 && h16) {
-            Src16Scope rows16(true);
-            return weight_grad(p, p.slab, 1, {reinterpret_cast<const float*>(z16), n_out, 0}, nullptr, {reinterpret_cast<const float*>(h16), k_in, 0},
-                               {nullptr, 0, 0}, k_in, nullptr, n_out, k_in, gw, k_in, gb, nullptr, rows, 1, s);
+            w.dZ.p = reinterpret_cast<const float*>(z16);
+            w.H.p = reinterpret_cast<const float*>(h16);
+            w.src16 = true;
+        } else if (z16) {   // (the partner did not qualify: fp32 rows for both)
+            --L16->n;
+            L16->used -= (size_t)rows * n_out;
         }
-        if (z16) { --L16->n; L16->used -= (size_t)rows * n_out; }   // (the partner did not qualify: fp32 rows for both)
     }
-    return weight_grad(p, p.slab, 1, {dz, n_out, 0}, nullptr, {h, k_in, 0}, {nullptr, 0, 0}, k_in, nullptr, n_out, k_in, gw, k_in, gb, nullptr, rows, 1, s);
+    return weight_grad(c, c.p->slab, batch, w, s);
 }
 
-static int mlp_tail_backward(const BwdPlan& p, float* const* T, const mpnhip_mlp& m0, float* const* hidden, const float** dz, int* cur_buf,
-                             int64_t rows, hipStream_t s) {
+static int mlp_tail_backward(BwdCtx& c, WpBatch* batch, Rows16Later* L16, float* const* T, const mpnhip_mlp& m0, float* const* hidden,
+                             const float** dz, int* cur_buf, int64_t rows, hipStream_t s) {
     for (int i = m0.n_layers - 1; i >= 1; --i) {
         const int n_out = m0.out_dims[i], k_in = m0.out_dims[i - 1];
-        MPN_TRY(encoder_weight_grad(p, *dz, hidden[i - 1], n_out, k_in, m0.grad_weight[i], m0.grad_bias[i], rows, s));
+        MPN_TRY(encoder_weight_grad(c, batch, L16, *dz, hidden[i - 1], n_out, k_in, m0.grad_weight[i], m0.grad_bias[i], rows, s));
         const float* Wq[2] = {m0.weight[i], nullptr};
         float* dst = T[(*cur_buf + 1) % 3];
-        MPN_TRY(act_grad(1, *dz, n_out, nullptr, Wq, k_in, n_out, k_in, dst, k_in, nullptr,
+        MPN_TRY(act_grad(c, 1, *dz, n_out, nullptr, Wq, k_in, n_out, k_in, dst, k_in, nullptr,
                          k_in != 1 ? hidden[i - 1] : nullptr, k_in, 0, nullptr, rows, s));
         *cur_buf = (*cur_buf + 1) % 3;
         *dz = dst;
@@ -815,16 +825,6 @@ extern "C" int mpnhip_backward_flags(const mpnhip_model* model, const void* grap
             for (int i = 0; i < q->n_layers; ++i)
                 MPN_CHECK_ARG(q->grad_weight[i] && q->grad_bias[i], "backward: null gradient buffer");
     }
-    struct WgradScope {
-        bool old;
-        explicit WgradScope(bool v) : old(g_wgrad_split) { g_wgrad_split = v; }
-        ~WgradScope() { g_wgrad_split = old; }
-    } wgrad_scope((m.precision == MPNHIP_PREC_FP32_SPLIT || m.precision == MPNHIP_PREC_FP32_WGSPLIT || m.precision == MPNHIP_PREC_BF16));
-    struct Bf16Scope {
-        bool old; float* olds; size_t oldn;
-        Bf16Scope(bool v) : old(g_bwd_bf16), olds(g_wt_scratch), oldn(g_wt_scratch_floats) { g_bwd_bf16 = v; }
-        ~Bf16Scope() { g_bwd_bf16 = old; g_wt_scratch = olds; g_wt_scratch_floats = oldn; }
-    } bf16_scope(m.precision == MPNHIP_PREC_BF16);
     FwdPlan f;
     size_t fneed = plan_forward(m, d, N, E, 1, fwd_workspace, &f);
     if (!fwd_workspace || fwd_workspace_bytes < fneed) {
@@ -837,12 +837,9 @@ extern "C" int mpnhip_backward_flags(const mpnhip_model* model, const void* grap
         set_error("backward: workspace %zu < %zu", bwd_workspace_bytes, need);
         return MPNHIP_ERR_WORKSPACE;
     }
-    g_wt_scratch = p.wt_scratch;
-    g_wt_scratch_floats = p.wt_scratch_floats;
-    struct KeepScope {   // (valid only inside this call: the blocks live in this call's workspace)
-        KeepScope(const BwdPlan& q) { for (int i = 0; i < 2; ++i) g_wt_keep[i] = {q.wt_keep_floats[i] ? q.wt_keep[i] : nullptr, q.wt_keep_floats[i], false, q.wt_keep_floats[i] ? q.wt_keep16[i] : nullptr}; }
-        ~KeepScope() { for (int i = 0; i < 2; ++i) g_wt_keep[i] = {nullptr, 0, false, nullptr}; }
-    } keep_scope(p);
+    BwdCtx c = {&p, m.precision == MPNHIP_PREC_FP32_SPLIT || m.precision == MPNHIP_PREC_FP32_WGSPLIT || m.precision == MPNHIP_PREC_BF16,
+                m.precision == MPNHIP_PREC_BF16, {}};
+    for (int i = 0; i < 2; ++i) c.wt_keep[i] = {p.wt_keep_floats[i] ? p.wt_keep[i] : nullptr, p.wt_keep_floats[i], false, p.wt_keep_floats[i] ? p.wt_keep16[i] : nullptr};
     GraphView g;
     graph_layout(n_nodes, n_edges, &g, const_cast<void*>(graph_buf));
     const int he = d.he, hn = d.hn, dn = d.dn, de = d.de, kx = d.kx, ke = d.ke, pw = d.pw, L = d.L;
@@ -902,38 +899,34 @@ extern "C" int mpnhip_backward_flags(const mpnhip_model* model, const void* grap
             // the same logical images (rows = contraction index n, columns = k) as split images (edge_chain.hip, split8);
             // recorded and packed by one launch (pack_split cannot fail once its sizes are valid: nothing returns before the flush)
             SplitBatch sb;
-            SplitBatchGuard sbg;
-            split_batch_begin(&sb);
             for (int q = 0; q < 2; ++q) {
-                MPN_TRY(pack_split(fl[q]->weight[1], hn, 1, dn, hn, DN, HN, p.wf2p[q], s));
-                MPN_TRY(pack_split(fl[q]->weight[0] + kx, fl[q]->in_dim, 1, hn, de, HN, DE, p.wfep[q], s));
+                MPN_TRY(pack_split(fl[q]->weight[1], hn, 1, dn, hn, DN, HN, p.wf2p[q], &sb, s));
+                MPN_TRY(pack_split(fl[q]->weight[0] + kx, fl[q]->in_dim, 1, hn, de, HN, DE, p.wfep[q], &sb, s));
             }
-            MPN_TRY(pack_split(m.classifier.weight[0], de, 1, m.classifier.out_dims[0], de, 32, DE, p.wc1p, s));
-            MPN_TRY(pack_split(m.edge.weight[1], he, 1, de, he, DE, HE, p.w2p, s));
+            MPN_TRY(pack_split(m.classifier.weight[0], de, 1, m.classifier.out_dims[0], de, 32, DE, p.wc1p, &sb, s));
+            MPN_TRY(pack_split(m.edge.weight[1], he, 1, de, he, DE, HE, p.w2p, &sb, s));
             for (int hlf = 0; hlf < d.ef; ++hlf) {
                 const int col0 = hlf * DE;
                 MPN_TRY(pack_split(m.edge.weight[0] + 2 * kx + hlf * de, m.edge.in_dim, 1, he, de, HE, DE,
-                                   p.w1ep + (int64_t)(col0 / 64) * HE * ncol6 * 3 / 2, s, ncol6 / 32, (col0 % 64) / 32));
+                                   p.w1ep + (int64_t)(col0 / 64) * HE * ncol6 * 3 / 2, &sb, s, ncol6 / 32, (col0 % 64) / 32));
             }
-            MPN_TRY(split_batch_flush(s));
+            MPN_TRY(split_batch_flush(&sb, s));
         } else {
-            PackBatch pb;
-            PackBatchGuard pbg;
-            pack_batch_begin(&pb);   // (the eight images as one launch)
+            PackBatch pb;   // (the eight images as one launch)
             for (int q = 0; q < 2; ++q) {
-                MPN_TRY(pack_padded(fl[q]->weight[1], hn, 0, dn, hn, p.wf2p[q], DN, HN, HN, 0, s));
-                MPN_TRY(pack_padded(fl[q]->weight[0], fl[q]->in_dim, kx, hn, de, p.wfep[q], HN, DE, DE, 0, s));
+                MPN_TRY(pack_padded(fl[q]->weight[1], hn, 0, dn, hn, p.wf2p[q], DN, HN, HN, 0, &pb, s));
+                MPN_TRY(pack_padded(fl[q]->weight[0], fl[q]->in_dim, kx, hn, de, p.wfep[q], HN, DE, DE, 0, &pb, s));
             }
-            MPN_TRY(pack_padded(m.classifier.weight[0], de, 0, m.classifier.out_dims[0], de, p.wc1p, 32, DE, DE, 0, s));
-            MPN_TRY(pack_padded(m.edge.weight[1], he, 0, de, he, p.w2p, DE, HE, HE, 0, s));
+            MPN_TRY(pack_padded(m.classifier.weight[0], de, 0, m.classifier.out_dims[0], de, p.wc1p, 32, DE, DE, 0, &pb, s));
+            MPN_TRY(pack_padded(m.edge.weight[1], he, 0, de, he, p.w2p, DE, HE, HE, 0, &pb, s));
             // e-part columns of edge layer 0 as one image [HE][ncol6] per pass of <= 64 (padded) columns of [e0 | e_{s-1}]
             // (the kernel streams whole rows of one pass image)
             for (int hlf = 0; hlf < d.ef; ++hlf) {
                 const int col0 = hlf * DE;
                 MPN_TRY(pack_padded(m.edge.weight[0], m.edge.in_dim, 2 * kx + hlf * de, he, de,
-                                    p.w1ep + (int64_t)(col0 / 64) * HE * ncol6, HE, DE, ncol6, col0 % 64, s));
+                                    p.w1ep + (int64_t)(col0 / 64) * HE * ncol6, HE, DE, ncol6, col0 % 64, &pb, s));
             }
-            MPN_TRY(pack_batch_flush(s));
+            MPN_TRY(pack_batch_flush(&pb, s));
         }
     }
 
@@ -947,10 +940,10 @@ extern "C" int mpnhip_backward_flags(const mpnhip_model* model, const void* grap
             const float* A = top ? dlog : dzc[i];
             const float* Wq[2] = {cls.weight[i], nullptr};
             if (i == 0)
-                MPN_TRY(act_grad(1, A, top ? 1 : n_out, top ? g.perm : nullptr, Wq, k_in, n_out, k_in, dEdst, de, nullptr, mask, de,
+                MPN_TRY(act_grad(c, 1, A, top ? 1 : n_out, top ? g.perm : nullptr, Wq, k_in, n_out, k_in, dEdst, de, nullptr, mask, de,
                                  1, nullptr, E, s));
             else
-                MPN_TRY(act_grad(1, A, top ? 1 : n_out, top ? g.perm : nullptr, Wq, k_in, n_out, k_in, dzc[i - 1], k_in, nullptr,
+                MPN_TRY(act_grad(c, 1, A, top ? 1 : n_out, top ? g.perm : nullptr, Wq, k_in, n_out, k_in, dzc[i - 1], k_in, nullptr,
                                  k_in != 1 ? HC[i - 1] : nullptr, k_in, 0, nullptr, E, s));
         }
         return MPNHIP_OK;
@@ -979,31 +972,27 @@ extern "C" int mpnhip_backward_flags(const mpnhip_model* model, const void* grap
         // MPNHIP_PREC_FP32_SPLIT: the products below are recorded and run as ONE product launch + ONE slab-sum launch at the end
         // (calls are serialised on `st`, so successive groups may share the slab region)
         WpBatch wpb;
-        WpBatchGuard wpg;
-        if (g_wgrad_split) { wp_batch_begin(&wpb, p.slab_wp, p.slab_wp_floats, true); wp_batch_set_stream(st); }
-        auto finish = [&]() -> int { return wp_batch_open() ? wp_batch_flush(st) : MPNHIP_OK; };
+        if (c.wgrad_split) wp_batch_init(&wpb, p.slab_wp, p.slab_wp_floats, true, &st);
+        WpBatch* const batch = c.wgrad_split ? &wpb : nullptr;
+        auto finish = [&]() -> int { return batch ? wp_batch_flush(batch, st) : MPNHIP_OK; };
         {   // node update Linear
-            float* gw[2] = {m.node.grad_weight[0], nullptr};
-            float* gb[2] = {m.node.grad_bias[0], nullptr};
+            WgProduct w = {.dZ = {p.dZn + zb * xs, dn, (int64_t)xs}, .H = {f.step0.AGG + zb * sstride, 2 * dn, sstride}, .n_out = dn, .k_in = 2 * dn,
+                           .ldw = 2 * dn, .rows = N, .nbatch = nb, .g = {{m.node.grad_weight[0], m.node.grad_bias[0]}}};
             if (node16 && p.dZn16 && sstride % 4 == 0) {
                 // bf16 rows (rounded here, on the products' own stream, ahead of the recorded batch): [dn x 2 dn] = two column tiles of
                 // the LDS-DMA kernel instead of 2 x 4 tiles of the row-panel kernel over fp32 rows
                 MPN_TRY(to_bf16_rows(p.dZn + zb * xs, p.dZn16 + zb * xs, (int64_t)nb * xs, st));
                 for (int q = 0; q < nb; ++q)
                     MPN_TRY(to_bf16_rows(f.step0.AGG + (zb + q) * sstride, p.AGG16 + (zb + q) * N * 2 * dn, N * 2 * dn, st));
-                Src16Scope rows16(true);
-                MPN_TRY(weight_grad(p, slab, 1, {reinterpret_cast<const float*>(p.dZn16 + zb * xs), dn, (int64_t)xs}, nullptr,
-                                    {reinterpret_cast<const float*>(p.AGG16 + zb * N * 2 * dn), 2 * dn, N * 2 * dn}, {nullptr, 0, 0}, 2 * dn, nullptr, dn,
-                                    2 * dn, gw, 2 * dn, gb, nullptr, N, nb, st));
-            } else {
-                MPN_TRY(weight_grad(p, slab, 1, {p.dZn + zb * xs, dn, (int64_t)xs}, nullptr, {f.step0.AGG + zb * sstride, 2 * dn, sstride},
-                                    {nullptr, 0, 0}, 2 * dn, nullptr, dn, 2 * dn, gw, 2 * dn, gb, nullptr, N, nb, st));
+                w.dZ = {reinterpret_cast<const float*>(p.dZn16 + zb * xs), dn, (int64_t)xs};
+                w.H = {reinterpret_cast<const float*>(p.AGG16 + zb * N * 2 * dn), 2 * dn, N * 2 * dn};
+                w.src16 = true;
             }
+            MPN_TRY(weight_grad(c, slab, batch, w, st));
         }
         if (use_b16) {
             // every operand of these products is a bf16 row block: the backward chain kernel's dZ outputs, the forward chain kernel's
             // saved activations and the bf16 mirror of e_hist (WpProduct::src16: loaded as they are, one product per k block)
-            Src16Scope src16(true);
             const int hcw = cls.out_dims[0];
             const int64_t ss16 = 2 * sstride;   // unsigned shorts between two steps' saved activations
             const float* dZF = u16(p.dZfl[0], zb * E * hn); const float* dZM = u16(p.dZfl[1], zb * E * dn);
@@ -1013,41 +1002,29 @@ extern "C" int mpnhip_backward_flags(const mpnhip_model* model, const void* grap
             const float* HCb = u16(f.step0.HC[0], zb * ss16);
             const float* eb_new = reinterpret_cast<const float*>(f.eb_hist + es * (zb + 1));
             const float* eb_prev = reinterpret_cast<const float*>(f.eb_hist + es * zb);
-            const Operand none = {nullptr, 0, 0};
-            {   // flow layer 1, both directions
-                float* gw[2] = {m.flow_out.grad_weight[1], m.flow_in.grad_weight[1]};
-                float* gb[2] = {m.flow_out.grad_bias[1], m.flow_in.grad_bias[1]};
-                MPN_TRY(weight_grad(p, slab, 2, {dZM, dn, (int64_t)E * dn}, nullptr, {HFb, hn, ss16}, none, hn, nullptr, dn, hn, gw, hn, gb, dir_rr, E, nb, st));
-            }
-            {   // flow layer 0: e' columns [kx, kx + de) and the bias (folded into P in the forward)
-                float* gw[2] = {m.flow_out.grad_weight[0] + kx, m.flow_in.grad_weight[0] + kx};
-                float* gb[2] = {m.flow_out.grad_bias[0], m.flow_in.grad_bias[0]};
-                MPN_TRY(weight_grad(p, slab, 2, {dZF, hn, (int64_t)E * hn}, nullptr, {eb_new, de, (int64_t)es}, none, de, nullptr, hn, de, gw, m.flow_out.in_dim, gb,
-                                    dir_rr, E, nb, st));
-            }
-            {   // classifier output layer [1 x hc]: dZ = grad_logits (fp32, original order -> perm), H = HC rows (bf16)
-                float* gw[2] = {cls.grad_weight[1], nullptr};
-                float* gb[2] = {cls.grad_bias[1], nullptr};
-                MPN_TRY(weight_grad(p, slab, 1, {grad_logits + zb * E, 1, (int64_t)E}, g.perm, {HCb, hcw, ss16}, none, hcw, nullptr, 1, hcw, gw, hcw, gb, nullptr, E,
-                                    nb, st));
-            }
-            {   // classifier layer 0
-                float* gw[2] = {cls.grad_weight[0], nullptr};
-                float* gb[2] = {cls.grad_bias[0], nullptr};
-                MPN_TRY(weight_grad(p, slab, 1, {dZc, hcw, (int64_t)E * hcw}, nullptr, {eb_new, de, (int64_t)es}, none, de, nullptr, hcw, de, gw, de, gb, nullptr, E, nb,
-                                    st));
-            }
-            {   // edge layer 1
-                float* gw[2] = {m.edge.grad_weight[1], nullptr};
-                float* gb[2] = {m.edge.grad_bias[1], nullptr};
-                MPN_TRY(weight_grad(p, slab, 1, {dZ2, de, (int64_t)E * de}, nullptr, {H1, he, ss16}, none, he, nullptr, de, he, gw, he, gb, nullptr, E, nb, st));
-            }
-            {   // edge layer 0: the e_{s-1} columns and the bias (the e0 columns: one product with the summed dZ1 after the loop)
-                float* gw[2] = {m.edge.grad_weight[0] + 2 * kx + de, nullptr};
-                float* gb[2] = {m.edge.grad_bias[0], nullptr};
-                MPN_TRY(weight_grad(p, slab, 1, {dZ1, he, (int64_t)E * he}, nullptr, {eb_prev, de, (int64_t)es}, none, de, nullptr, he, de, gw, m.edge.in_dim, gb,
-                                    nullptr, E, nb, st));
-            }
+            // flow layer 1, both directions
+            MPN_TRY(weight_grad(c, slab, batch, {.dZ = {dZM, dn, (int64_t)E * dn}, .H = {HFb, hn, ss16}, .n_out = dn, .k_in = hn, .ldw = hn, .rows = E,
+                                                 .nbatch = nb, .src16 = true,
+                                                 .g = {{m.flow_out.grad_weight[1], m.flow_out.grad_bias[1], dir_rr[0]},
+                                                       {m.flow_in.grad_weight[1], m.flow_in.grad_bias[1], dir_rr[1]}}}, st));
+            // flow layer 0: e' columns [kx, kx + de) and the bias (folded into P in the forward)
+            MPN_TRY(weight_grad(c, slab, batch, {.dZ = {dZF, hn, (int64_t)E * hn}, .H = {eb_new, de, (int64_t)es}, .n_out = hn, .k_in = de,
+                                                 .ldw = m.flow_out.in_dim, .rows = E, .nbatch = nb, .src16 = true,
+                                                 .g = {{m.flow_out.grad_weight[0] + kx, m.flow_out.grad_bias[0], dir_rr[0]},
+                                                       {m.flow_in.grad_weight[0] + kx, m.flow_in.grad_bias[0], dir_rr[1]}}}, st));
+            // classifier output layer [1 x hc]: dZ = grad_logits (fp32, original order -> perm), H = HC rows (bf16)
+            MPN_TRY(weight_grad(c, slab, batch, {.dZ = {grad_logits + zb * E, 1, (int64_t)E}, .dz_idx = g.perm, .H = {HCb, hcw, ss16}, .n_out = 1, .k_in = hcw,
+                                                 .ldw = hcw, .rows = E, .nbatch = nb, .src16 = true, .g = {{cls.grad_weight[1], cls.grad_bias[1]}}}, st));
+            // classifier layer 0
+            MPN_TRY(weight_grad(c, slab, batch, {.dZ = {dZc, hcw, (int64_t)E * hcw}, .H = {eb_new, de, (int64_t)es}, .n_out = hcw, .k_in = de, .ldw = de,
+                                                 .rows = E, .nbatch = nb, .src16 = true, .g = {{cls.grad_weight[0], cls.grad_bias[0]}}}, st));
+            // edge layer 1
+            MPN_TRY(weight_grad(c, slab, batch, {.dZ = {dZ2, de, (int64_t)E * de}, .H = {H1, he, ss16}, .n_out = de, .k_in = he, .ldw = he, .rows = E,
+                                                 .nbatch = nb, .src16 = true, .g = {{m.edge.grad_weight[1], m.edge.grad_bias[1]}}}, st));
+            // edge layer 0: the e_{s-1} columns and the bias (the e0 columns: one product with the summed dZ1 after the loop)
+            MPN_TRY(weight_grad(c, slab, batch, {.dZ = {dZ1, he, (int64_t)E * he}, .H = {eb_prev, de, (int64_t)es}, .n_out = he, .k_in = de,
+                                                 .ldw = m.edge.in_dim, .rows = E, .nbatch = nb, .src16 = true,
+                                                 .g = {{m.edge.grad_weight[0] + 2 * kx + de, m.edge.grad_bias[0]}}}, st));
         } else if (E > 0) {
             float* dzfl_b[MPNHIP_MAX_LAYERS];
             float* dzed_b[MPNHIP_MAX_LAYERS];
@@ -1055,62 +1032,54 @@ extern "C" int mpnhip_backward_flags(const mpnhip_model* model, const void* grap
             float* he_b[MPNHIP_MAX_LAYERS];
             for (int i = 0; i < nfl; ++i) { dzfl_b[i] = p.dZfl[i] + zb * E * m.flow_in.out_dims[i]; hf_b[i] = f.step0.HF[i] ? f.step0.HF[i] + zb * sstride : nullptr; }
             for (int i = 0; i < ne; ++i) { dzed_b[i] = p.dZed[i] + zb * E * m.edge.out_dims[i]; he_b[i] = f.step0.HE[i] ? f.step0.HE[i] + zb * sstride : nullptr; }
-            MPN_TRY(mlp_weight_grads(p, slab, m.flow_out, &m.flow_in, dzfl_b, hf_b, sstride, dir_rr, E, nb, st));
-            {   // flow layer 0: e-part columns [kx, kx + de) and the bias (folded into P in the forward)
-                float* gw[2] = {m.flow_out.grad_weight[0] + kx, m.flow_in.grad_weight[0] + kx};
-                float* gb[2] = {m.flow_out.grad_bias[0], m.flow_in.grad_bias[0]};
-                MPN_TRY(weight_grad(p, slab, 2, {dzfl_b[0], hn, (int64_t)E * hn}, nullptr, {f.e_hist + es * (zb + 1), de, (int64_t)es},
-                                    {nullptr, 0, 0}, de, nullptr, hn, de, gw, m.flow_out.in_dim, gb, dir_rr, E, nb, st));
-            }
+            MPN_TRY(mlp_weight_grads(c, slab, batch, m.flow_out, &m.flow_in, dzfl_b, hf_b, sstride, dir_rr, E, nb, st));
+            // flow layer 0: e-part columns [kx, kx + de) and the bias (folded into P in the forward)
+            MPN_TRY(weight_grad(c, slab, batch, {.dZ = {dzfl_b[0], hn, (int64_t)E * hn}, .H = {f.e_hist + es * (zb + 1), de, (int64_t)es}, .n_out = hn,
+                                                 .k_in = de, .ldw = m.flow_out.in_dim, .rows = E, .nbatch = nb,
+                                                 .g = {{m.flow_out.grad_weight[0] + kx, m.flow_out.grad_bias[0], dir_rr[0]},
+                                                       {m.flow_in.grad_weight[0] + kx, m.flow_in.grad_bias[0], dir_rr[1]}}}, st));
             // classifier: dZ of the last layer is grad_logits ([L, E], original order -> perm)
             for (int i = nc - 1; i >= 0; --i) {
                 const int n_out = cls.out_dims[i], k_in = i == 0 ? de : cls.out_dims[i - 1];
                 const bool top = i == nc - 1;
-                float* gw[2] = {cls.grad_weight[i], nullptr};
-                float* gb[2] = {cls.grad_bias[i], nullptr};
                 Operand dz = top ? Operand{grad_logits + zb * E, 1, (int64_t)E} : Operand{p.dZcl[i] + zb * E * n_out, n_out, (int64_t)E * n_out};
                 Operand h = i == 0 ? Operand{f.e_hist + es * (zb + 1), de, (int64_t)es} : Operand{f.step0.HC[i - 1] + zb * sstride, k_in, sstride};
-                MPN_TRY(weight_grad(p, slab, 1, dz, top ? g.perm : nullptr, h, {nullptr, 0, 0}, k_in, nullptr, n_out, k_in, gw, k_in, gb,
-                                    nullptr, E, nb, st));
+                MPN_TRY(weight_grad(c, slab, batch, {.dZ = dz, .dz_idx = top ? g.perm : nullptr, .H = h, .n_out = n_out, .k_in = k_in, .ldw = k_in, .rows = E,
+                                                     .nbatch = nb, .g = {{cls.grad_weight[i], cls.grad_bias[i]}}}, st));
             }
-            MPN_TRY(mlp_weight_grads(p, slab, m.edge, nullptr, dzed_b, he_b, sstride, nullptr, E, nb, st));
+            MPN_TRY(mlp_weight_grads(c, slab, batch, m.edge, nullptr, dzed_b, he_b, sstride, nullptr, E, nb, st));
             if (hoist_e0) {
                 // edge layer 0: the e_{s-1} columns [2kx + de, 2kx + 2 de) and the bias; the e0 columns follow after the loop
-                float* gw[2] = {m.edge.grad_weight[0] + 2 * kx + de, nullptr};
-                float* gb[2] = {m.edge.grad_bias[0], nullptr};
-                MPN_TRY(weight_grad(p, slab, 1, {dzed_b[0], he, (int64_t)E * he}, nullptr, {f.e_hist + es * zb, de, (int64_t)es},
-                                    {nullptr, 0, 0}, de, nullptr, he, de, gw, m.edge.in_dim, gb, nullptr, E, nb, st));
+                MPN_TRY(weight_grad(c, slab, batch, {.dZ = {dzed_b[0], he, (int64_t)E * he}, .H = {f.e_hist + es * zb, de, (int64_t)es}, .n_out = he,
+                                                     .k_in = de, .ldw = m.edge.in_dim, .rows = E, .nbatch = nb,
+                                                     .g = {{m.edge.grad_weight[0] + 2 * kx + de, m.edge.grad_bias[0]}}}, st));
             } else {   // edge layer 0: e-part columns [2kx, 2kx + ke) = [e0 | e_{s-1}], and the bias
-                float* gw[2] = {m.edge.grad_weight[0] + 2 * kx, nullptr};
-                float* gb[2] = {m.edge.grad_bias[0], nullptr};
                 const bool two = d.ef == 2;
                 Operand h1 = two ? Operand{e0, de, 0} : Operand{f.e_hist + es * zb, de, (int64_t)es};
                 Operand h2 = two ? Operand{f.e_hist + es * zb, de, (int64_t)es} : Operand{nullptr, 0, 0};
-                MPN_TRY(weight_grad(p, slab, 1, {dzed_b[0], he, (int64_t)E * he}, nullptr, h1, h2, de, nullptr, he, ke, gw, m.edge.in_dim,
-                                    gb, nullptr, E, nb, st));
+                MPN_TRY(weight_grad(c, slab, batch, {.dZ = {dzed_b[0], he, (int64_t)E * he}, .H = h1, .H2 = h2, .csplit = de, .n_out = he, .k_in = ke,
+                                                     .ldw = m.edge.in_dim, .rows = E, .nbatch = nb,
+                                                     .g = {{m.edge.grad_weight[0] + 2 * kx, m.edge.grad_bias[0]}}}, st));
             }
         }
         {   // per-node projections (packed), accumulated into gWnode
             if (hoist_x) {
                 // columns [dn, 2 dn) (the current features) here; the x0 columns are one product with the summed dP after the loop
-                float* gw[2] = {p.gWnode + dn, nullptr};
+                WgProduct w = {.dZ = {p.dP + zb * N * pw, pw, (int64_t)N * pw}, .H = {f.x_hist + xs * zb, dn, (int64_t)xs}, .n_out = pw, .k_in = dn,
+                               .ldw = kx, .rows = N, .nbatch = nb, .g = {{p.gWnode + dn, nullptr}}};
                 if (node16) {
-                    Src16Scope rows16(true);
-                    MPN_TRY(weight_grad(p, slab, 1, {reinterpret_cast<const float*>(p.dP16 + zb * N * pw), pw, (int64_t)N * pw}, nullptr,
-                                        {reinterpret_cast<const float*>(f.xb_hist + xs * zb), dn, (int64_t)xs}, {nullptr, 0, 0}, dn, nullptr, pw, dn, gw, kx,
-                                        nullptr, nullptr, N, nb, st));
-                    return finish();
+                    w.dZ.p = reinterpret_cast<const float*>(p.dP16 + zb * N * pw);
+                    w.H.p = reinterpret_cast<const float*>(f.xb_hist + xs * zb);
+                    w.src16 = true;
                 }
-                MPN_TRY(weight_grad(p, slab, 1, {p.dP + zb * N * pw, pw, (int64_t)N * pw}, nullptr, {f.x_hist + xs * zb, dn, (int64_t)xs},
-                                    {nullptr, 0, 0}, dn, nullptr, pw, dn, gw, kx, nullptr, nullptr, N, nb, st));
+                MPN_TRY(weight_grad(c, slab, batch, w, st));
                 return finish();
             }
-            float* gw[2] = {p.gWnode, nullptr};
             const bool two = d.nf == 2;
             Operand h1 = two ? Operand{x0, dn, 0} : Operand{f.x_hist + xs * zb, dn, (int64_t)xs};
             Operand h2 = two ? Operand{f.x_hist + xs * zb, dn, (int64_t)xs} : Operand{nullptr, 0, 0};
-            MPN_TRY(weight_grad(p, slab, 1, {p.dP + zb * N * pw, pw, (int64_t)N * pw}, nullptr, h1, h2, dn, nullptr, pw, kx, gw, kx, nullptr,
-                                nullptr, N, nb, st));
+            MPN_TRY(weight_grad(c, slab, batch, {.dZ = {p.dP + zb * N * pw, pw, (int64_t)N * pw}, .H = h1, .H2 = h2, .csplit = dn, .n_out = pw, .k_in = kx,
+                                                 .ldw = kx, .rows = N, .nbatch = nb, .g = {{p.gWnode, nullptr}}}, st));
         }
         return finish();
     };
@@ -1132,7 +1101,7 @@ extern "C" int mpnhip_backward_flags(const mpnhip_model* model, const void* grap
     int gsize[3] = {0};
     int ngroups = 1;
     if (want_fork) {
-        if (L >= 6 && (double)E * dn * dn >= 3e8 && !g_wgrad_split) {
+        if (L >= 6 && (double)E * dn * dn >= 3e8 && !c.wgrad_split) {
             // (enough work per group to pay for a third round of ~30 launches: cfg-B 8e8; the reference's 32-d widths, 8e7 at
             // cfg-C, do better with two groups -- measured 2.59 -> 2.48 ms.  The row-panel products of MPNHIP_PREC_FP32_SPLIT are
             // two launches per group whatever its size, and a larger group needs fewer slabs per row: two groups there,
@@ -1161,13 +1130,13 @@ extern "C" int mpnhip_backward_flags(const mpnhip_model* model, const void* grap
     bool node_a_done = false;   // dZn / dAGG of the coming step were already produced by node_step32_bwd
     // (k_node_step32_bwd stages the weights in LDS: 128 pw + 8 KB + ... <= 64 KB, 16-byte aligned rows)
     // wider models in the split precision: the same three launches as one MFMA kernel (node_chain.hip, node_chain_bwd_kernel)
-    const bool fuse_node_chain_bwd = p.ncb_img && !g_bwd_bf16 && N > 0 && L > 1 && d.nf == 2;
+    const bool fuse_node_chain_bwd = p.ncb_img && !c.bf16 && N > 0 && L > 1 && d.nf == 2;
     size_t ncb_off_wu = 0;
     if (fuse_node_chain_bwd) {
         node_chain_bwd_image_shorts(dn, pw, &ncb_off_wu);
         MPN_TRY(pack_node_chain_bwd(m.node.weight[0], f.Wnode, dn, pw, kx, p.ncb_img, s));
     }
-    const bool fuse_node_bwd = !g_bwd_bf16 && dn == 32 && N <= 4096 && pw <= 384 && kx % 4 == 0 &&
+    const bool fuse_node_bwd = !c.bf16 && dn == 32 && N <= 4096 && pw <= 384 && kx % 4 == 0 &&
                                ((((uintptr_t)f.Wnode) | ((uintptr_t)m.node.weight[0])) & 15) == 0 && !getenv("MPNHIP_NO_NODE_FUSION");
 
     for (int step = L; step >= 1; --step) {
@@ -1190,7 +1159,7 @@ extern "C" int mpnhip_backward_flags(const mpnhip_model* model, const void* grap
         if (!node_a_done) {
             MPN_TRY(relu_mask(dXc, x_s, dZn, (int64_t)xs, s, dx_split ? p.dXh : nullptr));
             const float* Wq[2] = {m.node.weight[0], nullptr};
-            MPN_TRY(act_grad(1, dZn, dn, nullptr, Wq, 2 * dn, dn, 2 * dn, p.dAGG, 2 * dn, nullptr, nullptr, 0, 0, nullptr, N, s, 0));
+            MPN_TRY(act_grad(c, 1, dZn, dn, nullptr, Wq, 2 * dn, dn, 2 * dn, p.dAGG, 2 * dn, nullptr, nullptr, 0, 0, nullptr, N, s, 0));
         }
         dx_split = false;
         node_a_done = false;
@@ -1264,25 +1233,25 @@ extern "C" int mpnhip_backward_flags(const mpnhip_model* model, const void* grap
                 MPN_LAUNCH_CHECK();
             }
             // ---- C. flow MLPs (both directions grouped) -------------------------------------------
-            MPN_TRY(mlp_chain_backward(m.flow_out, &m.flow_in, dzfl, b.HF, dir_rr, E, s));
+            MPN_TRY(mlp_chain_backward(c, m.flow_out, &m.flow_in, dzfl, b.HF, dir_rr, E, s));
             {
                 // layer 0:  Z = e_s Wfe^T + Pf[col];  dPf[n] = sum over the direction's edges with col == n
                 // (index_put_ of x[flow_col], mpn.py:87,93)
                 MPN_TRY(segment_reduce_csr2(dzfl[0], hn, g.cperm, g.cseg_ptr, 2 * (int)N, hn, dP, pw, (int)N, 2 * he, 2 * he + hn, s, E));
                 const float* Wq[2] = {m.flow_out.weight[0] + kx, m.flow_in.weight[0] + kx};
-                MPN_TRY(act_grad(2, dzfl[0], hn, nullptr, Wq, m.flow_out.in_dim, hn, de, dEc, de, nullptr, nullptr, 0, 1, dir_rr, E, s));
+                MPN_TRY(act_grad(c, 2, dzfl[0], hn, nullptr, Wq, m.flow_out.in_dim, hn, de, dEc, de, nullptr, nullptr, 0, 1, dir_rr, E, s));
             }
             // ---- D. classifier (mpn.py:377 -> :114); also applies the ReLU mask of e_s -------------
             MPN_TRY(classifier_chain(b.HC, dzcl, grad_logits + (size_t)b_ * E, dEc, de != 1 ? e_s : nullptr));
             // ---- E. edge MLP (EdgeModel, mpn.py:67-69) ----------------------------------------------
-            MPN_TRY(mlp_chain_backward(m.edge, nullptr, dzed, b.HE, nullptr, E, s));
+            MPN_TRY(mlp_chain_backward(c, m.edge, nullptr, dzed, b.HE, nullptr, E, s));
             {
                 // dPr / dPc: index_put_(accumulate) of x[row], x[col] (mpn.py:69)
                 MPN_TRY(segment_reduce_csr2(dzed[0], he, g.rperm, g.rseg_ptr, (int)N, he, dP, pw, (int)N, 0, 0, s, E));
                 MPN_TRY(segment_reduce_csr2(dzed[0], he, g.cperm_all, g.cseg_all, (int)N, he, dP, pw, (int)N, he, he, s, E));
                 // gradient w.r.t. [e0 | e_{s-1}]: one product, then split (e_0 IS e0 at step 1)
                 const float* Wa[2] = {m.edge.weight[0] + 2 * kx, nullptr};
-                MPN_TRY(act_grad(1, dzed[0], he, nullptr, Wa, m.edge.in_dim, he, ke, p.dCat, ke, nullptr, nullptr, 0, 0, nullptr, E, s));
+                MPN_TRY(act_grad(c, 1, dzed[0], he, nullptr, Wa, m.edge.in_dim, he, ke, p.dCat, ke, nullptr, nullptr, 0, 0, nullptr, E, s));
                 float* dEp = step == 1 ? p.dE0 : p.dZed[ne - 1] + (size_t)(b_ - 1) * es;
                 hipLaunchKernelGGL(k_split_cat, dim3((unsigned)((es + 255) / 256)), dim3(256), 0, s, p.dCat, E, de, d.ef == 2 ? 1 : 0,
                                    p.dE0, dEp, step == 1 ? 1 : 0);
@@ -1305,7 +1274,7 @@ extern "C" int mpnhip_backward_flags(const mpnhip_model* model, const void* grap
                                       p.dZn + (size_t)(b_ - 1) * xs, p.dAGG};
                 MPN_TRY(launch_node_chain_bwd(a, s));
                 node_a_done = true;
-            } else if (hoist_x && step > 1 && pw % 8 == 0 && N * 2 < 2000000000 && !g_bwd_bf16) {
+            } else if (hoist_x && step > 1 && pw % 8 == 0 && N * 2 < 2000000000 && !c.bf16) {
                 // [N, pw] x [pw, dn] is 157 tiles of 64 x 64 at cfg-B -- not enough blocks for 256 CUs and 34 K steps each: the two K
                 // halves run as the two groups of ONE grouped launch into dXp / dXh; the next step's ReLU-mask kernel adds them
                 GemmArgs a = {};
@@ -1318,17 +1287,17 @@ extern "C" int mpnhip_backward_flags(const mpnhip_model* model, const void* grap
                     G.C = q == 0 ? dXp : p.dXh; G.ldc = dn;
                     G.m_static = N;
                 }
-                MPN_TRY(launch_gemm(a, A_KCONTIG, B_NCONTIG, s));
+                MPN_TRY(launch_gemm(a, A_KCONTIG, B_NCONTIG, MPNHIP_PREC_FP32, s));
                 dx_split = true;
             } else if (hoist_x) {
                 // only the x_{s-1} columns here (at step 1 x_0 IS x0); the re-attached x0's columns take the SUM of the steps'
                 // dP after the loop: one product instead of L
                 const float* Wa[2] = {f.Wnode + dn, nullptr};
-                MPN_TRY(act_grad(1, dP, pw, nullptr, Wa, kx, pw, dn, step == 1 ? p.dX0 : dXp, dn, nullptr, nullptr, 0, step == 1 ? 1 : 0,
+                MPN_TRY(act_grad(c, 1, dP, pw, nullptr, Wa, kx, pw, dn, step == 1 ? p.dX0 : dXp, dn, nullptr, nullptr, 0, step == 1 ? 1 : 0,
                                  nullptr, N, s, 1));
             } else {
                 const float* Wa[2] = {f.Wnode, nullptr};
-                MPN_TRY(act_grad(1, dP, pw, nullptr, Wa, kx, pw, kx, p.dCat, kx, nullptr, nullptr, 0, 0, nullptr, N, s));
+                MPN_TRY(act_grad(c, 1, dP, pw, nullptr, Wa, kx, pw, kx, p.dCat, kx, nullptr, nullptr, 0, 0, nullptr, N, s));
                 if (xs) {
                     hipLaunchKernelGGL(k_split_cat, dim3((unsigned)((xs + 255) / 256)), dim3(256), 0, s, p.dCat, N, dn, d.nf == 2 ? 1 : 0,
                                        p.dX0, step == 1 ? p.dX0 : dXp, step == 1 ? 1 : 0);
@@ -1361,11 +1330,13 @@ extern "C" int mpnhip_backward_flags(const mpnhip_model* model, const void* grap
     // as separate launches and only the hoisted shares are batched: there the side stream's order must end with the
     // message-passing modules' gradients (a trainer puts their all-reduce behind it while the encoder's backward still runs).
     WpBatch tailb;
-    WpBatchGuard tail_guard;
-    const bool defer_tail = g_wgrad_split && L > 0 && forked;
+    const bool defer_tail = c.wgrad_split && L > 0 && forked;
     const bool defer_encoder = defer_tail && !(flags & MPNHIP_BWD_DEFER_SIDE_JOIN) && m.enc_node.n_layers <= 3 && m.enc_edge.n_layers <= 3;
-    if (defer_tail) wp_batch_begin(&tailb, p.slab_tail, p.slab_tail_floats, true);
-    // flush_tail runs what was recorded and closes the batch (its "+=" go to gradient columns disjoint from the groups': it may run
+    if (defer_tail) wp_batch_init(&tailb, p.slab_tail, p.slab_tail_floats, true, nullptr);   // (no stream yet: a full tail batch is not rolled)
+    // where the tail's products are recorded: the hoisted shares' while the batch exists, the encoder's only when it stays to the end
+    WpBatch* const tail_hoist = defer_tail ? &tailb : nullptr;
+    WpBatch* const tail_enc = defer_encoder ? &tailb : nullptr;
+    // flush_tail runs what was recorded (its "+=" go to gradient columns disjoint from the groups': it may run
     // beside the last group of steps).  Where it runs.  With the encoder's products deferred to the end anyway (no MPNHIP_BWD_DEFER_SIDE_JOIN) it runs on the
     // CALLER's stream itself, then the join, the unpacking and whatever the caller enqueues next: no hop ahead of the batch (event
     // record -> wait: 10 - 18 us each) and one instead of two behind it.  Same-box A-B, three runs each, second side stream / caller's
@@ -1380,7 +1351,7 @@ extern "C" int mpnhip_backward_flags(const mpnhip_model* model, const void* grap
     later16.pool = p.enc16;
     later16.pool_elems = p.enc16_elems;
     auto flush_tail = [&]() -> int {
-        if (!wp_batch_open()) return MPNHIP_OK;
+        if (!defer_tail) return MPNHIP_OK;
         hipStream_t st = tail_inline ? s : tail_beside ? side->stream2 : side->stream;
         if (!tail_inline) {
             MPN_HIP(hipEventRecord(side->ready, s));
@@ -1388,7 +1359,7 @@ extern "C" int mpnhip_backward_flags(const mpnhip_model* model, const void* grap
         }
         for (int i = 0; i < later16.n; ++i) MPN_TRY(to_bf16_rows(later16.item[i].src, later16.item[i].dst, later16.item[i].n, st));
         later16.n = 0;
-        MPN_TRY(wp_batch_flush(st));
+        MPN_TRY(wp_batch_flush(&tailb, st));
         if (tail_beside) {
             MPN_HIP(hipEventRecord(side->done2, side->stream2));
             MPN_HIP(hipStreamWaitEvent(side->stream, side->done2, 0));
@@ -1400,19 +1371,17 @@ extern "C" int mpnhip_backward_flags(const mpnhip_model* model, const void* grap
         hipLaunchKernelGGL(k_sum_blocks, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, p.dP, N * pw, (int)L, n4, p.dPsum);
         MPN_LAUNCH_CHECK();
         const float* Wa[2] = {f.Wnode, nullptr};
-        MPN_TRY(act_grad(1, p.dPsum, pw, nullptr, Wa, kx, pw, dn, p.dX0, dn, nullptr, nullptr, 0, 1, nullptr, N, s));
+        MPN_TRY(act_grad(c, 1, p.dPsum, pw, nullptr, Wa, kx, pw, dn, p.dX0, dn, nullptr, nullptr, 0, 1, nullptr, N, s));
         // ... and the x0 columns [0, dn) of the packed projection weight's gradient: (sum of dP)^T x0 (disjoint from the columns the
         // side stream accumulates; main-stream slab buffer)
-        float* gw[2] = {p.gWnode, nullptr};
+        WgProduct w = {.dZ = {p.dPsum, pw, 0}, .H = {x0, dn, 0}, .n_out = pw, .k_in = dn, .ldw = kx, .rows = N, .nbatch = 1, .g = {{p.gWnode, nullptr}}};
         if (node16) {
             MPN_TRY(to_bf16_rows(p.dPsum, p.dPsum16, N * pw, s));
-            Src16Scope rows16(true);
-            MPN_TRY(weight_grad(p, p.slab, 1, {reinterpret_cast<const float*>(p.dPsum16), pw, 0}, nullptr, {reinterpret_cast<const float*>(f.xb_hist), dn, 0},
-                                {nullptr, 0, 0}, dn, nullptr, pw, dn, gw, kx, nullptr, nullptr, N, 1, s));
-        } else {
-            MPN_TRY(weight_grad(p, p.slab, 1, {p.dPsum, pw, 0}, nullptr, {x0, dn, 0}, {nullptr, 0, 0}, dn, nullptr, pw, dn, gw, kx, nullptr, nullptr,
-                                N, 1, s));
+            w.dZ.p = reinterpret_cast<const float*>(p.dPsum16);
+            w.H.p = reinterpret_cast<const float*>(f.xb_hist);
+            w.src16 = true;
         }
+        MPN_TRY(weight_grad(c, p.slab, tail_hoist, w, s));
     }
     if (hoist_e0) {
         // S = sum_s dZ1_s (the blocks are all kept for the weight gradients);  dE0 += S W1[:, e0 columns];  dW1[:, e0 columns] += S^T e0
@@ -1428,16 +1397,10 @@ extern "C" int mpnhip_backward_flags(const mpnhip_model* model, const void* grap
         else hipLaunchKernelGGL(k_sum_blocks, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, p.dZed[0], E * he, (int)L, n4, p.dZ1sum);
         MPN_LAUNCH_CHECK();
         const float* Wa[2] = {m.edge.weight[0] + 2 * kx, nullptr};
-        MPN_TRY(act_grad(1, p.dZ1sum, he, nullptr, Wa, m.edge.in_dim, he, de, p.dE0, de, nullptr, nullptr, 0, 1, nullptr, E, s, -1, s16));
-        float* gw[2] = {m.edge.grad_weight[0] + 2 * kx, nullptr};
-        if (s16) {
-            Src16Scope rows16(true);
-            MPN_TRY(weight_grad(p, p.slab, 1, {p.dZ1sum, he, 0}, nullptr, {reinterpret_cast<const float*>(f.eb_hist), de, 0}, {nullptr, 0, 0}, de, nullptr,
-                                he, de, gw, m.edge.in_dim, nullptr, nullptr, E, 1, s));
-        } else {
-            MPN_TRY(weight_grad(p, p.slab, 1, {p.dZ1sum, he, 0}, nullptr, {e0, de, 0}, {nullptr, 0, 0}, de, nullptr, he, de, gw, m.edge.in_dim,
-                                nullptr, nullptr, E, 1, s));
-        }
+        MPN_TRY(act_grad(c, 1, p.dZ1sum, he, nullptr, Wa, m.edge.in_dim, he, de, p.dE0, de, nullptr, nullptr, 0, 1, nullptr, E, s, -1, s16));
+        MPN_TRY(weight_grad(c, p.slab, tail_hoist, {.dZ = {p.dZ1sum, he, 0}, .H = {s16 ? reinterpret_cast<const float*>(f.eb_hist) : e0, de, 0}, .n_out = he,
+                                                    .k_in = de, .ldw = m.edge.in_dim, .rows = E, .nbatch = 1, .src16 = s16,
+                                                    .g = {{m.edge.grad_weight[0] + 2 * kx, nullptr}}}, s));
     }
     auto unpack_node_grads = [&](hipStream_t us) -> int {
         // the packed node-projection gradient [W1r; W1c; Wfo_x; Wfi_x] back into the layers' grads (their biases were handled above)
@@ -1488,12 +1451,11 @@ extern "C" int mpnhip_backward_flags(const mpnhip_model* model, const void* grap
         for (int i = nc - 1; i >= 0 && E > 0; --i) {
             const int n_out = cls.out_dims[i], k_in = i == 0 ? de : cls.out_dims[i - 1];
             const bool top = i == nc - 1;
-            float* gw[2] = {cls.grad_weight[i], nullptr};
-            float* gb[2] = {cls.grad_bias[i], nullptr};
             Operand dz = top ? Operand{grad_logits, 1, 0} : Operand{p.dZcl[i], n_out, 0};
             Operand h = i == 0 ? Operand{e0, de, 0} : Operand{b.HC[i - 1], k_in, 0};
-            MPN_TRY(weight_grad(p, p.slab, 1, dz, top ? g.perm : nullptr, h, {nullptr, 0, 0}, k_in, nullptr, n_out, k_in, gw, k_in, gb, nullptr,
-                                E, 1, s));
+            // (L == 0: nothing was forked, no tail batch)
+            MPN_TRY(weight_grad(c, p.slab, nullptr, {.dZ = dz, .dz_idx = top ? g.perm : nullptr, .H = h, .n_out = n_out, .k_in = k_in, .ldw = k_in, .rows = E,
+                                                     .nbatch = 1, .g = {{cls.grad_weight[i], cls.grad_bias[i]}}}, s));
         }
         // incoming gradients of the final latents ARE gradients of the encoder outputs
         if (xs) {
@@ -1519,13 +1481,12 @@ extern "C" int mpnhip_backward_flags(const mpnhip_model* model, const void* grap
                 dz = p.Tn[0];
             }
             // (bf16-operand training with the deferred tail batch: the wide layers' products over bf16 rows, rounded on the tail's stream)
-            struct LaterScope { explicit LaterScope(Rows16Later* l) { g_rows16_later = l; } ~LaterScope() { g_rows16_later = nullptr; } };
-            LaterScope later_scope(defer_encoder && node16 && p.enc16 ? &later16 : nullptr);
-            MPN_TRY(mlp_tail_backward(p, p.Tn, en, hid, &dz, &cur, N, s));
-            MPN_TRY(encoder_weight_grad(p, dz, x, en.out_dims[0], en.in_dim, en.grad_weight[0], en.grad_bias[0], N, s));
+            Rows16Later* const later = defer_encoder && node16 && p.enc16 ? &later16 : nullptr;
+            MPN_TRY(mlp_tail_backward(c, tail_enc, later, p.Tn, en, hid, &dz, &cur, N, s));
+            MPN_TRY(encoder_weight_grad(c, tail_enc, later, dz, x, en.out_dims[0], en.in_dim, en.grad_weight[0], en.grad_bias[0], N, s));
             if (grad_x) {
                 const float* Wq[2] = {en.weight[0], nullptr};
-                MPN_TRY(act_grad(1, dz, en.out_dims[0], nullptr, Wq, en.in_dim, en.out_dims[0], en.in_dim, grad_x, en.in_dim,
+                MPN_TRY(act_grad(c, 1, dz, en.out_dims[0], nullptr, Wq, en.in_dim, en.out_dims[0], en.in_dim, grad_x, en.in_dim,
                                  nullptr, nullptr, 0, 0, nullptr, N, s));
             }
         }
@@ -1537,7 +1498,7 @@ extern "C" int mpnhip_backward_flags(const mpnhip_model* model, const void* grap
         const mpnhip_mlp& ee = m.enc_edge;
         const float* dz = p.dE0;
         int cur = 0;
-        const bool ref_encoder = !g_bwd_bf16 && ee.n_layers == 3 && ee.in_dim == 6 && ee.out_dims[0] == 18 && ee.out_dims[1] == 18 && ee.out_dims[2] == 16 &&
+        const bool ref_encoder = !c.bf16 && ee.n_layers == 3 && ee.in_dim == 6 && ee.out_dims[0] == 18 && ee.out_dims[1] == 18 && ee.out_dims[2] == 16 &&
                                  p.t_width >= 52 && !getenv("MPNHIP_NO_ENCODER_FUSION");
         if (E > 0 && ref_encoder) {
             // the reference's edge encoder: all three activation gradients in one launch (dz2 | dz1 | dz0 side by side in T[0]),
@@ -1549,33 +1510,26 @@ extern "C" int mpnhip_backward_flags(const mpnhip_model* model, const void* grap
             hipLaunchKernelGGL((k_edge_encoder_bwd<18, 18, 16>), dim3((unsigned)((E + 255) / 256)), dim3(256), 0, s, p.dE0, e0, hid[1], hid[0],
                                ee.weight[2], ee.weight[1], E, dz2, dz1, dz0);
             MPN_LAUNCH_CHECK();
-            {
-                float* gw[2] = {ee.grad_weight[2], nullptr};
-                float* gb[2] = {ee.grad_bias[2], nullptr};
-                MPN_TRY(weight_grad(p, p.slab, 1, {dz2, 16, 0}, nullptr, {hid[1], 18, 0}, {nullptr, 0, 0}, 18, nullptr, 16, 18, gw, 18, gb, nullptr, E, 1, s));
-            }
-            {
-                float* gw[2] = {ee.grad_weight[1], nullptr};
-                float* gb[2] = {ee.grad_bias[1], nullptr};
-                MPN_TRY(weight_grad(p, p.slab, 1, {dz1, 18, 0}, nullptr, {hid[0], 18, 0}, {nullptr, 0, 0}, 18, nullptr, 18, 18, gw, 18, gb, nullptr, E, 1, s));
-            }
+            MPN_TRY(weight_grad(c, p.slab, tail_enc, {.dZ = {dz2, 16, 0}, .H = {hid[1], 18, 0}, .n_out = 16, .k_in = 18, .ldw = 18, .rows = E, .nbatch = 1,
+                                                      .g = {{ee.grad_weight[2], ee.grad_bias[2]}}}, s));
+            MPN_TRY(weight_grad(c, p.slab, tail_enc, {.dZ = {dz1, 18, 0}, .H = {hid[0], 18, 0}, .n_out = 18, .k_in = 18, .ldw = 18, .rows = E, .nbatch = 1,
+                                                      .g = {{ee.grad_weight[1], ee.grad_bias[1]}}}, s));
             dz = dz0;
         } else if (E > 0) {
             if (ee.out_dims[ee.n_layers - 1] != 1) {
                 MPN_TRY(relu_mask(p.dE0, e0, p.T[0], (int64_t)es, s));
                 dz = p.T[0];
             }
-            MPN_TRY(mlp_tail_backward(p, p.T, ee, hid, &dz, &cur, E, s));
+            MPN_TRY(mlp_tail_backward(c, tail_enc, nullptr, p.T, ee, hid, &dz, &cur, E, s));
         }
         if (E > 0) {
-            float* gw[2] = {ee.grad_weight[0], nullptr};
-            float* gb[2] = {ee.grad_bias[0], nullptr};
             // layer 0 read edge_attr through the sort permutation
-            MPN_TRY(weight_grad(p, p.slab, 1, {dz, ee.out_dims[0], 0}, nullptr, {edge_attr, ee.in_dim, 0}, {nullptr, 0, 0}, ee.in_dim,
-                                g.perm, ee.out_dims[0], ee.in_dim, gw, ee.in_dim, gb, nullptr, E, 1, s));
+            MPN_TRY(weight_grad(c, p.slab, tail_enc, {.dZ = {dz, ee.out_dims[0], 0}, .H = {edge_attr, ee.in_dim, 0}, .h_idx = g.perm, .n_out = ee.out_dims[0],
+                                                      .k_in = ee.in_dim, .ldw = ee.in_dim, .rows = E, .nbatch = 1,
+                                                      .g = {{ee.grad_weight[0], ee.grad_bias[0]}}}, s));
             if (grad_edge_attr) {
                 const float* Wq[2] = {ee.weight[0], nullptr};
-                MPN_TRY(act_grad(1, dz, ee.out_dims[0], nullptr, Wq, ee.in_dim, ee.out_dims[0], ee.in_dim, grad_edge_attr,
+                MPN_TRY(act_grad(c, 1, dz, ee.out_dims[0], nullptr, Wq, ee.in_dim, ee.out_dims[0], ee.in_dim, grad_edge_attr,
                                  ee.in_dim, g.perm, nullptr, 0, 0, nullptr, E, s));
             }
         }

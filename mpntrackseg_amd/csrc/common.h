@@ -91,12 +91,10 @@ struct GemmArgs {
     int small_tiles;       // 1: take the 64 x 64 configuration whatever m_upper says (two K halves as two groups: m_upper = 2 M)
 };
 
-int launch_gemm(const GemmArgs& args, int a_layout, int b_layout, hipStream_t stream);
+// prec: the operand form (MPNHIP_PREC_FP32 / _BF16 / _FP32_SPLIT: bf16 operands / fp32 accumulate, three-piece bf16 operands)
+int launch_gemm(const GemmArgs& args, int a_layout, int b_layout, int prec, hipStream_t stream);
 // MPNHIP_PREC_BF16 at large row counts / with bf16 rows in memory (gemm_bf16.hip); false: not a shape of that kernel
 bool launch_gemm_bf16_tiled(const GemmArgs& args, hipStream_t stream, int* status);
-// operand precision of the calling thread's GEMMs (mpnhip_model.precision): 0 fp32, 1 bf16 operands / fp32 accumulate
-void set_gemm_precision(int p);
-int gemm_precision();
 
 // ------------------------------------------------------------------------------------ weight gradients
 // dW[o, c] += sum_m dZ[m, o] * H[m, c], db[o] += sum_m dZ[m, o] over a (device-resident) row range.
@@ -175,35 +173,33 @@ struct WpProduct {         // host-side description of one product
 };
 // (nblocks2 / bytes2: the jobs of wgrad_rows16.hip's kernel -- variant >= 16, their block0 counts inside that launch)
 struct WpBatch { WpTable tab; float* slab; size_t slab_floats, used; double flops, bytes, bytes2; int nblocks, nblocks2, nred; bool batched;
-                 hipStream_t stream; bool has_stream; };   // has_stream: the stream every flush of this batch goes to is known (wp_batch_roll)
+                 hipStream_t stream; bool has_stream; };   // has_stream: every flush of this batch goes to `stream` (wp_batch_roll)
 bool wp_eligible(const WpProduct& p);
 // wgrad_rows16.hip: the one-pass LDS-DMA kernel for bf16 rows at the 256-d widths
 int r16_variant(int n_out, int k_in, int* tiles_o, int* tiles_c);
 int launch_wgrad_rows16(const WpTable& tab, int nblocks, hipStream_t s);
 // (batched: the job shares its launch with the other products of a group of steps -- fewer row chunks per job)
 size_t wp_slab_floats(int n_out, int k_in, int64_t rows, int nbatch, bool ranged, bool batched, bool src16 = false);
-void wp_batch_begin(WpBatch* b, float* slab, size_t slab_floats, bool batched);   // opens b for the calling thread
-void wp_batch_set_stream(hipStream_t s);     // the open batch will be flushed on `s` (allows wp_batch_roll)
-// the open batch is full (job table or slab space) for these eligible products: run what it holds on its stream and reopen it
-// empty -- launches on one stream are serial, so the slab region is reused; false: not possible (no stream set / nothing recorded)
-bool wp_batch_roll(int* status);
-bool wp_batch_open();
-bool wp_batch_add(const WpProduct& p);       // true: recorded (a batch is open, the product is eligible, table and slab space suffice)
-bool wp_batch_add(const WpProduct* ps, int n);   // all n (the direction groups of one product) or none
-int wp_batch_flush(hipStream_t stream);      // product launch + slab-sum launch; closes the batch
-void wp_batch_abort();
-struct WpBatchGuard { ~WpBatchGuard() { wp_batch_abort(); } };
+// A WpBatch is an object its caller holds (on its stack) and passes to whatever records into it; nothing else refers to it.
+// init: empty, over `slab`.  stream (or nullptr): the one stream every flush of this batch will go to, which allows wp_batch_roll
+void wp_batch_init(WpBatch* b, float* slab, size_t slab_floats, bool batched, const hipStream_t* stream);
+// b is full (job table or slab space) for these eligible products: run what it holds on its stream and empty it -- launches on
+// one stream are serial, so the slab region is reused; false: not possible (no stream given at init / nothing recorded)
+bool wp_batch_roll(WpBatch* b, int* status);
+// true: recorded -- all n (the direction groups of one product) or none: every product eligible, table and slab space suffice
+bool wp_batch_add(WpBatch* b, const WpProduct* ps, int n);
+int wp_batch_flush(WpBatch* b, hipStream_t stream);   // product launch + slab-sum launch of what was recorded
 
 // few rows, long K (node encoder at the reference's graph sizes): split-K into `scratch`, then a fixed-order sum (gemm.hip)
 // `next` (optional): the Linear layer that follows ([next->n x n] weights, output next->y): evaluated in the summing launch when it is
 // narrow enough (next->done is set); otherwise untouched
 struct SplitkNext { const float* w; const float* b; int n; int relu; float* y; int64_t ldy; bool done; };
 bool linear_splitk(const float* x, int64_t ldx, const float* w, const float* b, float* y, int64_t ldy, int64_t m, int n, int k, int relu,
-                   float* scratch, size_t scratch_floats, hipStream_t stream, int* status, SplitkNext* next = nullptr);
+                   int prec, float* scratch, size_t scratch_floats, hipStream_t stream, int* status, SplitkNext* next = nullptr);
 size_t linear_splitk_scratch_floats(int64_t m, int n, int k);
 // Convenience: y = act(x W^T + b)
 int linear(const float* x, int64_t ldx, const float* w, const float* b, float* y, int64_t ldy, int64_t m, int n, int k,
-           int relu, hipStream_t stream);
+           int relu, int prec, hipStream_t stream);
 
 // ------------------------------------------------------------------------------------ graph
 // Layout of the prepared graph buffer (all int32 arrays; offsets in bytes from the buffer start are
@@ -307,8 +303,9 @@ bool prof_launch_events(hipEvent_t* start, hipEvent_t* stop);
     } while (0)
 
 // Deferred weight packing: the ~15-25 tiny copy / pad / transpose launches that build the packed weight images of a forward (and the
-// 8 of a backward) are RECORDED while a batch is open and run as ONE launch at the flush (k_pack_multi, mpn.hip) -- at the
-// reference's graph sizes those launches, ~5 us apart, were 6 % of a training step.
+// 8 of a backward) are RECORDED into a PackBatch and run as ONE launch at its flush (k_pack_multi, mpn.hip) -- at the
+// reference's graph sizes those launches, ~5 us apart, were 6 % of a training step.  The batch is an object on its caller's
+// stack (it starts empty) that the packing functions are handed; given nullptr they launch at once.
 struct PackOp {
     const float* src;   // nullptr: zeros
     float* dst;
@@ -320,13 +317,10 @@ struct PackOp {
 struct PackBatch {
     static constexpr int MAX = 32;
     PackOp op[MAX];
-    int n;
+    int n = 0;
 };
-void pack_batch_begin(PackBatch* b);            // opens `b` for the calling thread (n = 0)
-bool pack_batch_add(const PackOp& op);          // true: recorded (a batch is open and has room)
-int pack_batch_flush(hipStream_t stream);       // launches what was recorded, closes the batch
-void pack_batch_abort();                        // closes an open batch without launching it
-struct PackBatchGuard { ~PackBatchGuard() { pack_batch_abort(); } };   // declare beside the batch (error returns before the flush)
+bool pack_batch_add(PackBatch* b, const PackOp& op);        // true: recorded (b is given and has room)
+int pack_batch_flush(const PackBatch* b, hipStream_t stream);   // launches what was recorded
 
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 

@@ -102,21 +102,19 @@ int launch_edge_encoder_mfma(const float* x, const int* idx, int64_t rows, int i
 // Split image of the logical operand A[k][n] = src[k * sk + n * sn] (zero beyond K x N), padded to Kp x Np (multiples of
 // 16 / 32): Kp Np 6 bytes at dst, in the unit order edge_chain.hip documents.  ntr_image / t0: the Np / 32 column tiles are
 // tiles t0 .. of an image with ntr_image tiles per k block (default: the whole image).
-int pack_split(const float* src, int64_t sk, int64_t sn, int K, int N, int Kp, int Np, float* dst, hipStream_t s,
-               int ntr_image = 0, int t0 = 0);
-// The split images of one forward / backward as ONE launch: pack_split() calls between split_batch_begin and split_batch_flush
-// are recorded (up to 16) and run together (13 + 7 launches of ~4.5 us per cfg-B training step otherwise).
+// The split images of one forward / backward as ONE launch: a SplitBatch on the caller's stack starts empty; the pack_split()
+// calls it is passed to are recorded (up to 16) and run together by split_batch_flush (13 + 7 launches of ~4.5 us per cfg-B
+// training step otherwise).  batch == nullptr (or a full one): launched now.
 struct SplitOp { const float* src; int64_t sk, sn; int K, N, Kp, Np; unsigned short* dst; int ntr_image, t0; };
-struct SplitBatch { static constexpr int MAX = 16; SplitOp op[MAX]; int n; };
-void split_batch_begin(SplitBatch* b);
-int split_batch_flush(hipStream_t s);
-void split_batch_abort();                                              // closes an open batch without launching it
-struct SplitBatchGuard { ~SplitBatchGuard() { split_batch_abort(); } }; // declare beside the batch: an error return between
-                                                                       // begin and flush must not leave the thread's batch
-                                                                       // pointer on a dead stack frame
-int transpose_padded(const float* W, int64_t ldw, int k0, int n_rows, int k_cols, float* WT, int n_pad, int k_pad, hipStream_t s);
+struct SplitBatch { static constexpr int MAX = 16; SplitOp op[MAX]; int n = 0; };
+int pack_split(const float* src, int64_t sk, int64_t sn, int K, int N, int Kp, int Np, float* dst, SplitBatch* batch, hipStream_t s,
+               int ntr_image = 0, int t0 = 0);
+int split_batch_flush(const SplitBatch* b, hipStream_t s);
+// batch (common.h: PackBatch): recorded there; nullptr (or a full one): launched now
+int transpose_padded(const float* W, int64_t ldw, int k0, int n_rows, int k_cols, float* WT, int n_pad, int k_pad, PackBatch* batch,
+                     hipStream_t s);
 int pack_padded(const float* src, int64_t lds, int c0, int rows, int cols, float* dst, int rows_pad, int cols_pad, int ldd,
-                int dst_c0, hipStream_t s);
+                int dst_c0, PackBatch* batch, hipStream_t s);
 
 
 // ---- bf16-operand forward chain (edge_chain_bf16.hip): N-tiled hidden layers, widths up to BASELINE.json configs[4] (256-d)

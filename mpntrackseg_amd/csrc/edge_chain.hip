@@ -1123,16 +1123,8 @@ __global__ __launch_bounds__(256) void k_pack_split_multi(SplitBatch b) {
     }
 }
 
-static thread_local SplitBatch* g_split_batch = nullptr;
-void split_batch_begin(SplitBatch* b) {
-    b->n = 0;
-    g_split_batch = b;
-}
-void split_batch_abort() { g_split_batch = nullptr; }
-int split_batch_flush(hipStream_t s) {
-    SplitBatch* b = g_split_batch;
-    g_split_batch = nullptr;
-    if (!b || b->n == 0) return MPNHIP_OK;
+int split_batch_flush(const SplitBatch* b, hipStream_t s) {
+    if (b->n == 0) return MPNHIP_OK;
     int64_t mx = 0;
     for (int i = 0; i < b->n; ++i) {
         const int64_t n = (int64_t)(b->op[i].Kp / 16) * (b->op[i].Np / 32) * 512;
@@ -1143,14 +1135,15 @@ int split_batch_flush(hipStream_t s) {
     return MPNHIP_OK;
 }
 
-int pack_split(const float* src, int64_t sk, int64_t sn, int K, int N, int Kp, int Np, float* dst, hipStream_t s, int ntr_image, int t0) {
+int pack_split(const float* src, int64_t sk, int64_t sn, int K, int N, int Kp, int Np, float* dst, SplitBatch* batch, hipStream_t s, int ntr_image,
+               int t0) {
     if (ntr_image <= 0) ntr_image = Np / 32;
     const int64_t n = (int64_t)(Kp / 16) * (Np / 32) * 512;
     if (n <= 0) return MPNHIP_OK;
     if (Kp % 16 != 0 || Np % 32 != 0) { set_error("pack_split: padded sizes must be multiples of 16 x 32"); return MPNHIP_ERR_ARG; }
     const SplitOp o = {src, sk, sn, K, N, Kp, Np, reinterpret_cast<unsigned short*>(dst), ntr_image, t0};
-    if (g_split_batch && g_split_batch->n < SplitBatch::MAX) {
-        g_split_batch->op[g_split_batch->n++] = o;
+    if (batch && batch->n < SplitBatch::MAX) {
+        batch->op[batch->n++] = o;
         return MPNHIP_OK;
     }
     hipLaunchKernelGGL(k_pack_split, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, o);
@@ -1158,20 +1151,21 @@ int pack_split(const float* src, int64_t sk, int64_t sn, int K, int N, int Kp, i
     return MPNHIP_OK;
 }
 
-int transpose_padded(const float* W, int64_t ldw, int k0, int n_rows, int k_cols, float* WT, int n_pad, int k_pad, hipStream_t s) {
+int transpose_padded(const float* W, int64_t ldw, int k0, int n_rows, int k_cols, float* WT, int n_pad, int k_pad, PackBatch* batch,
+                     hipStream_t s) {
     const int64_t n = (int64_t)n_pad * k_pad;
     if (n <= 0) return MPNHIP_OK;
-    if (pack_batch_add({W, WT, ldw, k0, k_cols, n_rows, k_pad, n_pad, n_pad, 0, 1})) return MPNHIP_OK;
+    if (pack_batch_add(batch, {W, WT, ldw, k0, k_cols, n_rows, k_pad, n_pad, n_pad, 0, 1})) return MPNHIP_OK;
     hipLaunchKernelGGL(k_transpose_padded, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, W, ldw, k0, n_rows, k_cols, WT, n_pad, k_pad);
     MPN_LAUNCH_CHECK();
     return MPNHIP_OK;
 }
 
 int pack_padded(const float* src, int64_t lds, int c0, int rows, int cols, float* dst, int rows_pad, int cols_pad, int ldd,
-                int dst_c0, hipStream_t s) {
+                int dst_c0, PackBatch* batch, hipStream_t s) {
     const int64_t n = (int64_t)rows_pad * cols_pad;
     if (n <= 0) return MPNHIP_OK;
-    if (pack_batch_add({src, dst, lds, c0, rows, cols, rows_pad, cols_pad, ldd, dst_c0, 0})) return MPNHIP_OK;
+    if (pack_batch_add(batch, {src, dst, lds, c0, rows, cols, rows_pad, cols_pad, ldd, dst_c0, 0})) return MPNHIP_OK;
     hipLaunchKernelGGL(k_pack_padded, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, src, lds, c0, rows, cols, dst, rows_pad,
                        cols_pad, ldd, dst_c0);
     MPN_LAUNCH_CHECK();

@@ -36,13 +36,10 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 
-// Operand precision of the MFMA products of the calling thread's current forward (set by mpnhip_forward from
-// mpnhip_model.precision): 0 = fp32 operands (v_mfma_f32_32x32x2_f32), 1 = operands rounded to bf16 (RNE) when they
+// Operand precision of an MFMA product (launch_gemm's `prec` argument; mpnhip_forward passes what
+// mpnhip_model.precision asks for): 0 = fp32 operands (v_mfma_f32_32x32x2_f32), 1 = operands rounded to bf16 (RNE) when they
 // are staged into LDS, fp32 accumulation (v_mfma_f32_32x32x16_bf16) -- BASELINE.json's "bf16 MLP GEMMs on MFMA" mode;
 // 2 = MPNHIP_PREC_FP32_SPLIT: fp32 operands split into three bf16 pieces as they are staged, six products per multiply.
-static thread_local int g_precision = 0;
-void set_gemm_precision(int p) { g_precision = p; }
-int gemm_precision() { return g_precision; }
 
 constexpr int BK = 32;
 constexpr int PKB = 40;  // bf16 images: row pitch in elements (32 k + 8 pad = 80 bytes: 16-byte aligned rows)
@@ -500,11 +497,10 @@ __global__ __launch_bounds__(NTHREADS) void gemm_smallk_kernel(GemmArgs args, in
 }
 
 template <int WM, int WN, int TN>
-static int launch_cfg(const GemmArgs& a, int bl, hipStream_t s) {
+static int launch_cfg(const GemmArgs& a, int bl, int prec, hipStream_t s) {
     constexpr int BM = 32 * WM, BN = 32 * TN * WN;
     int64_t nby = (a.m_upper + BM - 1) / BM + (a.ngroups > 1 ? 1 : 0);
     dim3 grid((a.N + BN - 1) / BN, (unsigned)nby, 1);
-    int prec = g_precision;
     // FP32_SPLIT (three-piece bf16 operands, six products: split3): pays where the product is large enough to be MFMA-bound --
     // measured on MI355X (tools/gemm_bench.py --check): 5000 x 1088 x 256 38.9 -> 31.6 us, 5000 x 512 x 2048 141 -> 122 us,
     // 50000 x 320 x 128 65.6 -> 48.5 us; narrow outputs (N = 128) and short K lose to the fp32 MFMA kernel's smaller LDS image
@@ -525,7 +521,7 @@ static int launch_cfg(const GemmArgs& a, int bl, hipStream_t s) {
 
 static bool al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 
-int launch_gemm(const GemmArgs& a_in, int al, int bl, hipStream_t s) {
+int launch_gemm(const GemmArgs& a_in, int al, int bl, int prec, hipStream_t s) {
     GemmArgs a = a_in;
     MPN_CHECK_ARG(a.ngroups == 1 || a.ngroups == 2, "gemm: ngroups %d", a.ngroups);
     MPN_CHECK_ARG(a.K >= 0 && a.N >= 0 && a.ksplit >= 0 && a.ksplit <= a.K, "gemm: bad N/K/ksplit");
@@ -565,14 +561,14 @@ int launch_gemm(const GemmArgs& a_in, int al, int bl, hipStream_t s) {
             // (a thread's 4 x K weights are 28 scalar loads: at least eight row passes per block to pay for them)
             int64_t nb = ((a.m_upper + rpp - 1) / rpp + 7) / 8;
             nb = nb > 256 * 16 ? 256 * 16 : (nb < 1 ? 1 : nb);
-            hipLaunchKernelGGL(gemm_smallk_kernel, dim3((unsigned)nb), dim3(NTHREADS), 0, s, a, g_precision == 1 ? 1 : 0);
+            hipLaunchKernelGGL(gemm_smallk_kernel, dim3((unsigned)nb), dim3(NTHREADS), 0, s, a, prec == 1 ? 1 : 0);
             MPN_LAUNCH_CHECK();
             return MPNHIP_OK;
         }
         int64_t total = a.m_upper * a.N;
         unsigned blocks = (unsigned)((total + NTHREADS - 1) / NTHREADS);
         if (blocks > 65535u * 16) blocks = 65535u * 16;
-        hipLaunchKernelGGL(gemm_generic_kernel, dim3(blocks), dim3(NTHREADS), 0, s, a, bl, g_precision == 1 ? 1 : 0);
+        hipLaunchKernelGGL(gemm_generic_kernel, dim3(blocks), dim3(NTHREADS), 0, s, a, bl, prec == 1 ? 1 : 0);
         MPN_LAUNCH_CHECK();
         return MPNHIP_OK;
     }
@@ -584,12 +580,12 @@ int launch_gemm(const GemmArgs& a_in, int al, int bl, hipStream_t s) {
         // rows in memory (only that kernel reads them)
         bool rows16 = false;
         for (int i = 0; i < a.ngroups; ++i) rows16 = rows16 || a.g[i].a16 || a.g[i].b16 || a.g[i].C16;
-        int prec = g_precision;
-        if (const char* e = getenv("MPNHIP_GEMM_PREC")) prec = atoi(e);
+        int tiled_prec = prec;
+        if (const char* e = getenv("MPNHIP_GEMM_PREC")) tiled_prec = atoi(e);
         // (short K with a ragged column count -- the edge encoder's 144 / 160-wide layers over 400,000 rows -- stays on the strip
         // kernel: 122 against 170 us at 400,000 x 160 x 144, tools/gemm_bf16_bench.py)
         const bool shape_ok = a.K >= 192 && (N % 128 == 0 || N >= 384);
-        if (bl == B_KCONTIG && (rows16 || (prec == 1 && M >= 4096 && !a.small_tiles && shape_ok))) {
+        if (bl == B_KCONTIG && (rows16 || (tiled_prec == 1 && M >= 4096 && !a.small_tiles && shape_ok))) {
             int st = MPNHIP_OK;
             if (launch_gemm_bf16_tiled(a, s, &st)) {
                 if (st == MPNHIP_OK) count_path(PC_GEMM_BF16);
@@ -613,25 +609,25 @@ int launch_gemm(const GemmArgs& a_in, int al, int bl, hipStream_t s) {
             while (best > 1 && rb * ((nt + best - 1) / best) < 256) best = (best + 1) / 2;
         }
         switch (best) {
-            case 8: return launch_cfg<4, 1, 8>(a, bl, s);
-            case 7: return launch_cfg<4, 1, 7>(a, bl, s);
-            case 6: return launch_cfg<4, 1, 6>(a, bl, s);
-            case 5: return launch_cfg<4, 1, 5>(a, bl, s);
-            case 4: return launch_cfg<4, 1, 4>(a, bl, s);
-            case 3: return launch_cfg<4, 1, 3>(a, bl, s);
-            case 2: return launch_cfg<4, 1, 2>(a, bl, s);
-            default: return launch_cfg<4, 1, 1>(a, bl, s);
+            case 8: return launch_cfg<4, 1, 8>(a, bl, prec, s);
+            case 7: return launch_cfg<4, 1, 7>(a, bl, prec, s);
+            case 6: return launch_cfg<4, 1, 6>(a, bl, prec, s);
+            case 5: return launch_cfg<4, 1, 5>(a, bl, prec, s);
+            case 4: return launch_cfg<4, 1, 4>(a, bl, prec, s);
+            case 3: return launch_cfg<4, 1, 3>(a, bl, prec, s);
+            case 2: return launch_cfg<4, 1, 2>(a, bl, prec, s);
+            default: return launch_cfg<4, 1, 1>(a, bl, prec, s);
         }
     }
     // few rows (node-level products): spread the columns over the waves so that the grid fills the chip
     // measured on MI355X at M = 5,000 (tools/gemm_bench.py): 64 x 64 tiles beat every wider strip for
     // N = 128 ... 1088 and K = 128 ... 2048 (more, shorter blocks: the chip is latency- not MFMA-bound here)
-    if (nt >= 2) return launch_cfg<2, 2, 1>(a, bl, s);
-    return launch_cfg<4, 1, 1>(a, bl, s);
+    if (nt >= 2) return launch_cfg<2, 2, 1>(a, bl, prec, s);
+    return launch_cfg<4, 1, 1>(a, bl, prec, s);
 }
 
 int linear(const float* x, int64_t ldx, const float* w, const float* b, float* y, int64_t ldy, int64_t m, int n, int k,
-           int relu, hipStream_t stream) {
+           int relu, int prec, hipStream_t stream) {
     GemmArgs a = {};
     a.ngroups = 1;
     a.N = n;
@@ -648,7 +644,7 @@ int linear(const float* x, int64_t ldx, const float* w, const float* b, float* y
     g.C = y;
     g.ldc = ldy;
     g.m_static = m;
-    return launch_gemm(a, A_KCONTIG, B_KCONTIG, stream);
+    return launch_gemm(a, A_KCONTIG, B_KCONTIG, prec, stream);
 }
 
 // ---- few rows, long K: split-K ------------------------------------------------------------------------------------------
@@ -784,10 +780,10 @@ constexpr int64_t SPLITK_MAX_ROWS = 8192, SPLITK_MAX_TILES = 320;
 static inline int64_t splitk_blocks(int64_t tiles) { return tiles < 96 ? 384 : 768; }
 
 bool linear_splitk(const float* x, int64_t ldx, const float* w, const float* b, float* y, int64_t ldy, int64_t m, int n, int k, int relu,
-                   float* scratch, size_t scratch_floats, hipStream_t stream, int* status, SplitkNext* next) {
+                   int prec, float* scratch, size_t scratch_floats, hipStream_t stream, int* status, SplitkNext* next) {
     *status = MPNHIP_OK;
     // (fp32 MFMAs: exact fp32 products -- also what the split precision may use; the bf16-operand mode must round its operands)
-    if (g_precision == 1) return false;
+    if (prec == 1) return false;
     const int64_t tiles = ((m + 63) / 64) * ((n + 63) / 64);
     if (!scratch || m <= 0 || m > SPLITK_MAX_ROWS || k < 512 || k % 4 != 0 || ldx % 4 != 0 || tiles >= SPLITK_MAX_TILES || (((uintptr_t)x | (uintptr_t)w) & 15)) return false;
     int S = (int)(splitk_blocks(tiles) / tiles);

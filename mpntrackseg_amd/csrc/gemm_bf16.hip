@@ -604,8 +604,7 @@ int linear_bf16_call(const mpnhip_linear_bf16_args* p, hipStream_t s) {
     g.C = p->y; g.ldc = p->ldy;
     g.C16 = p->y16; g.ldc16 = p->ldy16;
     g.m_static = p->m;
-    struct Scope { int old; Scope() : old(gemm_precision()) { set_gemm_precision(MPNHIP_PREC_BF16); } ~Scope() { set_gemm_precision(old); } } scope;
-    return launch_gemm(a, A_KCONTIG, B_KCONTIG, s);
+    return launch_gemm(a, A_KCONTIG, B_KCONTIG, MPNHIP_PREC_BF16, s);
 }
 }  // namespace
 

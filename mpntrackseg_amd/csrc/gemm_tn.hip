@@ -608,10 +608,8 @@ static int weight_grad_run(const TnArgs& a, int precision, void* workspace, size
         WpProduct p = {g.dZ, g.ldz, g.z_bstride, g.H, g.ldh, g.h_bstride, nullptr, nullptr, a.m_upper, a.nbatch, a.n_out, a.k_in,
                        g.grad_w, g.ldw, g.grad_b, nullptr, nullptr, nullptr, 0, 0, 0, precision == MPNHIP_PREC_BF16 ? 1 : 3};
         WpBatch b;
-        WpBatchGuard guard;
-        wp_batch_begin(&b, g.slab, (workspace_bytes - 256) / sizeof(float), false);
-        if (wp_batch_add(p)) return wp_batch_flush(s);
-        wp_batch_abort();
+        wp_batch_init(&b, g.slab, (workspace_bytes - 256) / sizeof(float), false, nullptr);
+        if (wp_batch_add(&b, &p, 1)) return wp_batch_flush(&b, s);
     }
     return launch_gemm_tn(a, s);
 }
@@ -639,10 +637,8 @@ extern "C" int mpnhip_weight_grad_bf16_rows(const uint16_t* dZ, const uint16_t* 
     WpProduct p = {reinterpret_cast<const float*>(dZ), n_out, rows * n_out, reinterpret_cast<const float*>(H), k_in, rows * k_in, nullptr, nullptr,
                    rows, nbatch, n_out, k_in, grad_w, k_in, grad_b, nullptr, nullptr, nullptr, 0, 0, 0, 1, 1};
     WpBatch b;
-    WpBatchGuard guard;
-    wp_batch_begin(&b, slab, (workspace_bytes - 256) / sizeof(float), false);
-    if (wp_batch_add(p)) return wp_batch_flush(static_cast<hipStream_t>(stream));
-    wp_batch_abort();
+    wp_batch_init(&b, slab, (workspace_bytes - 256) / sizeof(float), false, nullptr);
+    if (wp_batch_add(&b, &p, 1)) return wp_batch_flush(&b, static_cast<hipStream_t>(stream));
     set_error("weight_grad_bf16_rows: [%d x %d] over bf16 rows is not a shape of the row-panel kernel (multiples of 4, 8-byte aligned rows)", n_out, k_in);
     return MPNHIP_ERR_UNSUPPORTED;
 }

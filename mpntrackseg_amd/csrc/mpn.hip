@@ -134,8 +134,6 @@ __global__ void k_avgpool(const float* __restrict__ x, int64_t rows, int hw, flo
 }
 
 // ------------------------------------------------------------------------------------ deferred packing (common.h)
-static thread_local PackBatch* g_pack_batch = nullptr;
-
 __device__ __forceinline__ void pack_one(const PackOp& o, int64_t i) {
     const int64_t n = (int64_t)o.rows_pad * o.cols_pad;
     if (i >= n) return;
@@ -159,23 +157,14 @@ __global__ __launch_bounds__(256) void k_pack_multi(PackBatch b) {
     }
 }
 
-void pack_batch_begin(PackBatch* b) {
-    b->n = 0;
-    g_pack_batch = b;
-}
-
-bool pack_batch_add(const PackOp& op) {
-    PackBatch* b = g_pack_batch;
+bool pack_batch_add(PackBatch* b, const PackOp& op) {
     if (!b || b->n >= PackBatch::MAX) return false;
     if ((int64_t)op.rows_pad * op.cols_pad > 0) b->op[b->n++] = op;
     return true;
 }
 
-void pack_batch_abort() { g_pack_batch = nullptr; }
-int pack_batch_flush(hipStream_t s) {
-    PackBatch* b = g_pack_batch;
-    g_pack_batch = nullptr;
-    if (!b || b->n == 0) return MPNHIP_OK;
+int pack_batch_flush(const PackBatch* b, hipStream_t s) {
+    if (b->n == 0) return MPNHIP_OK;
     int64_t mx = 0;
     for (int i = 0; i < b->n; ++i) {
         const int64_t n = (int64_t)b->op[i].rows_pad * b->op[i].cols_pad;
@@ -186,17 +175,17 @@ int pack_batch_flush(hipStream_t s) {
     return MPNHIP_OK;
 }
 
-static int copy_block(const float* src, int64_t lds, int c0, float* dst, int64_t ldd, int rows, int cols, hipStream_t s) {
+static int copy_block(const float* src, int64_t lds, int c0, float* dst, int64_t ldd, int rows, int cols, PackBatch* batch, hipStream_t s) {
     int64_t n = (int64_t)rows * cols;
     if (n <= 0) return MPNHIP_OK;
-    if (pack_batch_add({src, dst, lds, c0, rows, cols, rows, cols, (int)ldd, 0, 0})) return MPNHIP_OK;
+    if (pack_batch_add(batch, {src, dst, lds, c0, rows, cols, rows, cols, (int)ldd, 0, 0})) return MPNHIP_OK;
     hipLaunchKernelGGL(k_copy_block, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, src, lds, c0, dst, ldd, rows, cols);
     MPN_LAUNCH_CHECK();
     return MPNHIP_OK;
 }
-static int copy_vec(const float* src, float* dst, int n, hipStream_t s) {
+static int copy_vec(const float* src, float* dst, int n, PackBatch* batch, hipStream_t s) {
     if (n <= 0) return MPNHIP_OK;
-    if (pack_batch_add({src, dst, n, 0, 1, n, 1, n, n, 0, 0})) return MPNHIP_OK;
+    if (pack_batch_add(batch, {src, dst, n, 0, 1, n, 1, n, n, 0, 0})) return MPNHIP_OK;
     hipLaunchKernelGGL(k_copy_vec, dim3((n + 255) / 256), dim3(256), 0, s, src, dst, n);
     MPN_LAUNCH_CHECK();
     return MPNHIP_OK;
@@ -214,7 +203,7 @@ static int scatter_rows(const float* src, const int* idx, float* dst, int64_t ro
 // hidden / output layers i >= 1 of an MLP on [rows, :] activations; `two` = direction-grouped run
 // of the flow MLPs (group 0: flow_out weights on rows [0, E_out), group 1: flow_in on [E_out, E_out+E_in)).
 static int mlp_tail(const mpnhip_mlp& m0, const mpnhip_mlp* m1, const GraphView* g, float* const* hidden,
-                    float* out_last, int64_t ld_last, const int* c_idx_last, int64_t rows, hipStream_t s) {
+                    float* out_last, int64_t ld_last, const int* c_idx_last, int64_t rows, int prec, hipStream_t s) {
     for (int i = 1; i < m0.n_layers; ++i) {
         GemmArgs a = {};
         a.ngroups = m1 ? 2 : 1;
@@ -242,25 +231,25 @@ static int mlp_tail(const mpnhip_mlp& m0, const mpnhip_mlp* m1, const GraphView*
                 G.row_end = q == 0 ? g->header + 4 : g->header + 5;
             }
         }
-        MPN_TRY(launch_gemm(a, A_KCONTIG, B_KCONTIG, s));
+        MPN_TRY(launch_gemm(a, A_KCONTIG, B_KCONTIG, prec, s));
     }
     return MPNHIP_OK;
 }
 
-static int pack_node_weights(const mpnhip_model& m, const Dims& d, float* Wnode, float* bnode, hipStream_t s) {
+static int pack_node_weights(const mpnhip_model& m, const Dims& d, float* Wnode, float* bnode, PackBatch* batch, hipStream_t s) {
     const int he = d.he, hn = d.hn, kx = d.kx;
-    MPN_TRY(copy_block(m.edge.weight[0], m.edge.in_dim, 0, Wnode, kx, he, kx, s));                         // W1 row part
-    MPN_TRY(copy_block(m.edge.weight[0], m.edge.in_dim, kx, Wnode + (size_t)he * kx, kx, he, kx, s));      // W1 col part
-    MPN_TRY(copy_block(m.flow_out.weight[0], m.flow_out.in_dim, 0, Wnode + (size_t)2 * he * kx, kx, hn, kx, s));
-    MPN_TRY(copy_block(m.flow_in.weight[0], m.flow_in.in_dim, 0, Wnode + (size_t)(2 * he + hn) * kx, kx, hn, kx, s));
-    MPN_TRY(copy_vec(m.edge.bias[0], bnode, he, s));
-    MPN_TRY(copy_vec(nullptr, bnode + he, he, s));
-    MPN_TRY(copy_vec(m.flow_out.bias[0], bnode + 2 * he, hn, s));
-    MPN_TRY(copy_vec(m.flow_in.bias[0], bnode + 2 * he + hn, hn, s));
+    MPN_TRY(copy_block(m.edge.weight[0], m.edge.in_dim, 0, Wnode, kx, he, kx, batch, s));                         // W1 row part
+    MPN_TRY(copy_block(m.edge.weight[0], m.edge.in_dim, kx, Wnode + (size_t)he * kx, kx, he, kx, batch, s));      // W1 col part
+    MPN_TRY(copy_block(m.flow_out.weight[0], m.flow_out.in_dim, 0, Wnode + (size_t)2 * he * kx, kx, hn, kx, batch, s));
+    MPN_TRY(copy_block(m.flow_in.weight[0], m.flow_in.in_dim, 0, Wnode + (size_t)(2 * he + hn) * kx, kx, hn, kx, batch, s));
+    MPN_TRY(copy_vec(m.edge.bias[0], bnode, he, batch, s));
+    MPN_TRY(copy_vec(nullptr, bnode + he, he, batch, s));
+    MPN_TRY(copy_vec(m.flow_out.bias[0], bnode + 2 * he, hn, batch, s));
+    MPN_TRY(copy_vec(m.flow_in.bias[0], bnode + 2 * he + hn, hn, batch, s));
     return MPNHIP_OK;
 }
 
-static int pack_chain_weights(const mpnhip_model& m, const Dims& d, ChainWeights& cw, hipStream_t s) {
+static int pack_chain_weights(const mpnhip_model& m, const Dims& d, ChainWeights& cw, PackBatch* batch, SplitBatch* split_batch, hipStream_t s) {
     cw.ok = chain_shapes_ok(m, d);
     if (!cw.ok) return MPNHIP_OK;
     const int HE = pad32(d.he), DE = pad32(d.de), HN = pad32(d.hn), DN = pad32(d.dn);
@@ -269,32 +258,32 @@ static int pack_chain_weights(const mpnhip_model& m, const Dims& d, ChainWeights
     cw.split = chain_split(m);
     if (cw.split) {
         // the same logical images WT[k][n] = W[n][k0 + k] as below, as split images (3/2 the size, offsets scale alike)
-        MPN_TRY(pack_split(m.edge.weight[0] + 2 * d.kx, 1, m.edge.in_dim, d.ke, d.he, d.ke, HE, cw.w1T, s));
-        MPN_TRY(pack_split(m.edge.weight[1], 1, d.he, d.he, d.de, HE, DE, cw.w2T, s));
-        MPN_TRY(pack_split(m.classifier.weight[0], 1, d.de, d.de, hc, DE, 32, cw.wc1T, s));
+        MPN_TRY(pack_split(m.edge.weight[0] + 2 * d.kx, 1, m.edge.in_dim, d.ke, d.he, d.ke, HE, cw.w1T, split_batch, s));
+        MPN_TRY(pack_split(m.edge.weight[1], 1, d.he, d.he, d.de, HE, DE, cw.w2T, split_batch, s));
+        MPN_TRY(pack_split(m.classifier.weight[0], 1, d.de, d.de, hc, DE, 32, cw.wc1T, split_batch, s));
         for (int q = 0; q < 2; ++q) {
             for (int n0 = 0; n0 < HN; n0 += 64) {
                 const int ncw = HN - n0 < 64 ? HN - n0 : 64;
                 const int rows = d.hn - n0 < 0 ? 0 : (d.hn - n0 < ncw ? d.hn - n0 : ncw);
                 MPN_TRY(pack_split(fl[q]->weight[0] + (int64_t)n0 * fl[q]->in_dim + d.kx, 1, fl[q]->in_dim, d.de, rows, DE, ncw,
-                                   cw.wf1T[q] + (int64_t)DE * n0 * 3 / 2, s));
+                                   cw.wf1T[q] + (int64_t)DE * n0 * 3 / 2, split_batch, s));
             }
-            MPN_TRY(pack_split(fl[q]->weight[1], 1, d.hn, d.hn, d.dn, HN, DN, cw.wf2T[q], s));
+            MPN_TRY(pack_split(fl[q]->weight[1], 1, d.hn, d.hn, d.dn, HN, DN, cw.wf2T[q], split_batch, s));
         }
         return MPNHIP_OK;
     }
-    MPN_TRY(transpose_padded(m.edge.weight[0], m.edge.in_dim, 2 * d.kx, d.he, d.ke, cw.w1T, HE, d.ke, s));
-    MPN_TRY(transpose_padded(m.edge.weight[1], d.he, 0, d.de, d.he, cw.w2T, DE, HE, s));
-    MPN_TRY(transpose_padded(m.classifier.weight[0], d.de, 0, hc, d.de, cw.wc1T, 32, DE, s));
+    MPN_TRY(transpose_padded(m.edge.weight[0], m.edge.in_dim, 2 * d.kx, d.he, d.ke, cw.w1T, HE, d.ke, batch, s));
+    MPN_TRY(transpose_padded(m.edge.weight[1], d.he, 0, d.de, d.he, cw.w2T, DE, HE, batch, s));
+    MPN_TRY(transpose_padded(m.classifier.weight[0], d.de, 0, hc, d.de, cw.wc1T, 32, DE, batch, s));
     for (int q = 0; q < 2; ++q) {
         // flow layer 0, e'-part: one image [DE][<= 64] per block of 64 output features (the kernel streams whole blocks)
         for (int n0 = 0; n0 < HN; n0 += 64) {
             const int ncw = HN - n0 < 64 ? HN - n0 : 64;
             const int rows = d.hn - n0 < 0 ? 0 : (d.hn - n0 < ncw ? d.hn - n0 : ncw);
             MPN_TRY(transpose_padded(fl[q]->weight[0] + (int64_t)n0 * fl[q]->in_dim, fl[q]->in_dim, d.kx, rows, d.de,
-                                     cw.wf1T[q] + (int64_t)DE * n0, ncw, DE, s));
+                                     cw.wf1T[q] + (int64_t)DE * n0, ncw, DE, batch, s));
         }
-        MPN_TRY(transpose_padded(fl[q]->weight[1], d.hn, 0, d.dn, d.hn, cw.wf2T[q], DN, HN, s));
+        MPN_TRY(transpose_padded(fl[q]->weight[1], d.hn, 0, d.dn, d.hn, cw.wf2T[q], DN, HN, batch, s));
     }
     return MPNHIP_OK;
 }
@@ -360,7 +349,7 @@ struct StepIO {
 struct StepE16 { const unsigned short* e0; const unsigned short* cur; unsigned short* out; bool write_e32; };
 
 static int run_step(const mpnhip_model& m, const Dims& d, const GraphView& g, const float* Wnode, const float* bnode,
-                    const StepIO& io, const StepBufs& b, bool save_arg, hipStream_t s, const ChainWeights* cw = nullptr,
+                    const StepIO& io, const StepBufs& b, bool save_arg, int prec, hipStream_t s, const ChainWeights* cw = nullptr,
                     bool save_acts = false, const ChainBf16* cb = nullptr, const StepE16* e16 = nullptr) {
     unsigned short* const save_eb = e16 ? e16->out : nullptr;
     const int64_t N = g.N, E = g.E;
@@ -389,7 +378,7 @@ static int run_step(const mpnhip_model& m, const Dims& d, const GraphView& g, co
             G.B = Wnode; G.ldb = d.kx; G.bias = bnode;
         }
         G.C = b.P; G.ldc = d.pw; G.m_static = N;
-        MPN_TRY(launch_gemm(a, A_KCONTIG, B_KCONTIG, s));
+        MPN_TRY(launch_gemm(a, A_KCONTIG, B_KCONTIG, prec, s));
     }
     const bool chain = cw && cw->ok && E > 0 && io.logits && !io.e_idx && !io.e_new_idx && !io.e_new_read_idx;
     bool agg_done = false;   // the chain kernel aggregated the messages itself
@@ -473,10 +462,10 @@ static int run_step(const mpnhip_model& m, const Dims& d, const GraphView& g, co
             G.C = last ? io.e_new : b.HE[0]; G.ldc = last ? d.de : he; G.c_idx = last ? io.e_new_idx : nullptr;
             G.m_static = E;
             prof_begin(PROF_GEMM, s);
-            MPN_TRY(launch_gemm(a, A_KCONTIG, B_KCONTIG, s));
+            MPN_TRY(launch_gemm(a, A_KCONTIG, B_KCONTIG, prec, s));
             prof_end(PROF_GEMM, s);
         }
-        MPN_TRY(mlp_tail(m.edge, nullptr, nullptr, b.HE, io.e_new, d.de, io.e_new_idx, E, s));
+        MPN_TRY(mlp_tail(m.edge, nullptr, nullptr, b.HE, io.e_new, d.de, io.e_new_idx, E, prec, s));
         // (3) classifier on the NEW edge features (mpn.py:377 -> :114)
         if (io.logits) {
             const mpnhip_mlp& c = m.classifier;
@@ -487,8 +476,8 @@ static int run_step(const mpnhip_model& m, const Dims& d, const GraphView& g, co
             G.A = io.e_new; G.lda = d.de; G.a_idx = io.e_new_read_idx; G.B = c.weight[0]; G.ldb = d.de; G.bias = c.bias[0];
             bool last = c.n_layers == 1;
             G.C = last ? io.logits : b.HC[0]; G.ldc = last ? 1 : a.N; G.c_idx = last ? g.perm : nullptr; G.m_static = E;
-            MPN_TRY(launch_gemm(a, A_KCONTIG, B_KCONTIG, s));
-            MPN_TRY(mlp_tail(c, nullptr, nullptr, b.HC, io.logits, 1, g.perm, E, s));
+            MPN_TRY(launch_gemm(a, A_KCONTIG, B_KCONTIG, prec, s));
+            MPN_TRY(mlp_tail(c, nullptr, nullptr, b.HC, io.logits, 1, g.perm, E, prec, s));
         }
         // (4) flow MLP layer 0, both directions in one grouped launch (TimeAwareNodeModel, mpn.py:85-94)
         {
@@ -507,9 +496,9 @@ static int run_step(const mpnhip_model& m, const Dims& d, const GraphView& g, co
                 G.row_begin = q == 0 ? nullptr : g.header + 4;
                 G.row_end = q == 0 ? g.header + 4 : g.header + 5;
             }
-            MPN_TRY(launch_gemm(a, A_KCONTIG, B_KCONTIG, s));
+            MPN_TRY(launch_gemm(a, A_KCONTIG, B_KCONTIG, prec, s));
         }
-        MPN_TRY(mlp_tail(m.flow_out, &m.flow_in, &g, b.HF, b.M, d.dn, nullptr, E, s));
+        MPN_TRY(mlp_tail(m.flow_out, &m.flow_in, &g, b.HF, b.M, d.dn, nullptr, E, prec, s));
     }
     // (5) aggregation (node_agg_fn, mpn.py:89,96) and node update (mpn.py:97-99)
     if (io.fuse_node && io.nc_img) {
@@ -541,9 +530,9 @@ static int run_step(const mpnhip_model& m, const Dims& d, const GraphView& g, co
         init_group(G);
         G.A = b.AGG; G.lda = 2 * d.dn; G.B = reinterpret_cast<const float*>(io.Wu16); G.ldb = 2 * d.dn; G.b16 = 1;
         G.bias = m.node.bias[0]; G.C = io.x_new; G.ldc = d.dn; G.C16 = io.x_new16; G.ldc16 = d.dn; G.m_static = N;
-        return launch_gemm(a, A_KCONTIG, B_KCONTIG, s);
+        return launch_gemm(a, A_KCONTIG, B_KCONTIG, prec, s);
     }
-    MPN_TRY(linear(b.AGG, 2 * d.dn, m.node.weight[0], m.node.bias[0], io.x_new, d.dn, N, d.dn, 2 * d.dn, 1, s));
+    MPN_TRY(linear(b.AGG, 2 * d.dn, m.node.weight[0], m.node.bias[0], io.x_new, d.dn, N, d.dn, 2 * d.dn, 1, prec, s));
     return MPNHIP_OK;
 }
 
@@ -626,7 +615,7 @@ static bool edge_encoder_fused(const mpnhip_mlp& m, const float* x, const int* i
 
 // full MLP (all layers) with ping-pong or per-layer hidden buffers; a_idx permutes the input rows
 static int mlp_forward(const mpnhip_mlp& m, const float* x, int64_t ldx, const int* a_idx, float* const* hidden, float* y,
-                       int64_t rows, hipStream_t s, float* splitk = nullptr, size_t splitk_floats = 0) {
+                       int64_t rows, int prec, hipStream_t s, float* splitk = nullptr, size_t splitk_floats = 0) {
     for (int i = 0; i < m.n_layers; ++i) {
         if (splitk && !a_idx) {
             int st = MPNHIP_OK;
@@ -636,7 +625,7 @@ static int mlp_forward(const mpnhip_mlp& m, const float* x, int64_t ldx, const i
             const bool has_next = i + 2 == m.n_layers;
             if (has_next) nx = {m.weight[i + 1], m.bias[i + 1], m.out_dims[i + 1], m.out_dims[i + 1] != 1, y, m.out_dims[i + 1], false};
             if (linear_splitk(i == 0 ? x : hidden[i - 1], i == 0 ? ldx : k_in, m.weight[i], m.bias[i], i == m.n_layers - 1 ? y : hidden[i],
-                              m.out_dims[i], rows, m.out_dims[i], k_in, m.out_dims[i] != 1, splitk, splitk_floats, s, &st,
+                              m.out_dims[i], rows, m.out_dims[i], k_in, m.out_dims[i] != 1, prec, splitk, splitk_floats, s, &st,
                               has_next ? &nx : nullptr)) {
                 if (st != MPNHIP_OK) return st;
                 if (nx.done) ++i;   // both layers are evaluated
@@ -661,7 +650,7 @@ static int mlp_forward(const mpnhip_mlp& m, const float* x, int64_t ldx, const i
         G.C = i == m.n_layers - 1 ? y : hidden[i];
         G.ldc = a.N;
         G.m_static = rows;
-        MPN_TRY(launch_gemm(a, A_KCONTIG, B_KCONTIG, s));
+        MPN_TRY(launch_gemm(a, A_KCONTIG, B_KCONTIG, prec, s));
     }
     return MPNHIP_OK;
 }
@@ -710,13 +699,9 @@ extern "C" int mpnhip_forward(const mpnhip_model* model, const void* graph_buf, 
     graph_layout(n_nodes, n_edges, &g, const_cast<void*>(graph_buf));
     MPN_CHECK_ARG(m.precision == MPNHIP_PREC_FP32 || m.precision == MPNHIP_PREC_BF16 || m.precision == MPNHIP_PREC_FP32_SPLIT ||
                   m.precision == MPNHIP_PREC_FP32_WGSPLIT, "forward: unknown precision %d", m.precision);
-    // every product of this call rounds its operands as the model asks (restored on every exit path)
-    struct PrecisionScope {
-        int old;
-        explicit PrecisionScope(int p) : old(gemm_precision()) { set_gemm_precision(p); }
-        ~PrecisionScope() { set_gemm_precision(old); }
-    } precision_scope(m.precision == MPNHIP_PREC_FP32_WGSPLIT ? MPNHIP_PREC_FP32 : m.precision);  // (FP32_SPLIT: the fused chain
-    // kernels, and the larger K-contiguous GEMMs -- gemm.hip; FP32_WGSPLIT differs from FP32 in the backward's weight gradients only)
+    // every product of this call rounds its operands as the model asks (FP32_SPLIT: the fused chain kernels, and the larger
+    // K-contiguous GEMMs -- gemm.hip; FP32_WGSPLIT differs from FP32 in the backward's weight gradients only)
+    const int prec = m.precision == MPNHIP_PREC_FP32_WGSPLIT ? MPNHIP_PREC_FP32 : m.precision;
 
     if (m.weights_prepacked && !save) {
         p.cw.ok = chain_shapes_ok(m, d);  // the images are already at the head of the workspace
@@ -724,17 +709,13 @@ extern "C" int mpnhip_forward(const mpnhip_model* model, const void* graph_buf, 
         p.cb.ok = p.cb.img && chain_bf16_ok(m, d);
     } else {
         count_path(PC_WEIGHT_PACK);
-        PackBatch pb;
-        SplitBatch sb;
-        PackBatchGuard pbg;
-        SplitBatchGuard sbg;
-        pack_batch_begin(&pb);   // (the fp32 images' copies / transposes are recorded and run as one launch,
-        split_batch_begin(&sb);  //  the split images as another)
-        int rc = pack_node_weights(m, d, p.Wnode, p.bnode, s);
-        if (rc == MPNHIP_OK) rc = pack_chain_weights(m, d, p.cw, s);
+        PackBatch pb;   // (the fp32 images' copies / transposes are recorded and run as one launch,
+        SplitBatch sb;  //  the split images as another)
+        int rc = pack_node_weights(m, d, p.Wnode, p.bnode, &pb, s);
+        if (rc == MPNHIP_OK) rc = pack_chain_weights(m, d, p.cw, &pb, &sb, s);
         if (rc == MPNHIP_OK) rc = pack_chain_bf16_weights(m, d, p.cb, s);
-        const int rf = pack_batch_flush(s);
-        const int rs = split_batch_flush(s);
+        const int rf = pack_batch_flush(&pb, s);
+        const int rs = split_batch_flush(&sb, s);
         MPN_TRY(rc);
         MPN_TRY(rf);
         MPN_TRY(rs);
@@ -755,13 +736,13 @@ extern "C" int mpnhip_forward(const mpnhip_model* model, const void* graph_buf, 
     float* x0 = p.x_hist;
     float* e0 = p.e_hist;
     hidden_ptrs(m.enc_node, p.enc_n, N, save != 0, hid);
-    MPN_TRY(mlp_forward(m.enc_node, x, m.enc_node.in_dim, nullptr, hid, x0, N, s, p.splitk, p.splitk_floats));
+    MPN_TRY(mlp_forward(m.enc_node, x, m.enc_node.in_dim, nullptr, hid, x0, N, prec, s, p.splitk, p.splitk_floats));
     hidden_ptrs(m.enc_edge, p.enc_e, E, save != 0, hid);
     {
         int st = MPNHIP_OK;
         // (bf16-operand mode: every Linear product rounds its operands -- the GEMM path does that, the fused kernel is fp32)
         if (m.precision == MPNHIP_PREC_BF16 || !edge_encoder_fused(m.enc_edge, edge_attr, g.perm, hid, save != 0, e0, E, s, &st))
-            MPN_TRY(mlp_forward(m.enc_edge, edge_attr, m.enc_edge.in_dim, g.perm, hid, e0, E, s));
+            MPN_TRY(mlp_forward(m.enc_edge, edge_attr, m.enc_edge.in_dim, g.perm, hid, e0, E, prec, s));
         else if (st != MPNHIP_OK) return st;
     }
 
@@ -780,7 +761,7 @@ extern "C" int mpnhip_forward(const mpnhip_model* model, const void* graph_buf, 
         GemmGroup& G = a.g[0];
         init_group(G);
         G.A = x0; G.lda = d.dn; G.B = p.Wnode; G.ldb = d.kx; G.bias = p.bnode; G.C = p.P0; G.ldc = d.pw; G.m_static = N;
-        MPN_TRY(launch_gemm(a, A_KCONTIG, B_KCONTIG, s));
+        MPN_TRY(launch_gemm(a, A_KCONTIG, B_KCONTIG, prec, s));
     }
     // the same for the edge side of the fused chain: Q0 = e0 W1[:, e0 columns]^T, [E, he] (64 MB at cfg-B), saves a
     // quarter of the chain's first-layer MFMAs in every step
@@ -795,7 +776,7 @@ extern "C" int mpnhip_forward(const mpnhip_model* model, const void* graph_buf, 
         GemmGroup& G = a.g[0];
         init_group(G);
         G.A = e0; G.lda = d.de; G.B = m.edge.weight[0] + 2 * d.kx; G.ldb = m.edge.in_dim; G.C = p.Q0; G.ldc = d.he; G.m_static = E;
-        MPN_TRY(launch_gemm(a, A_KCONTIG, B_KCONTIG, s));
+        MPN_TRY(launch_gemm(a, A_KCONTIG, B_KCONTIG, prec, s));
     }
     // the reference's node width: the three node-side kernels of a step in one launch (segment.hip, node_step32); needs the
     // hoisted P0 form of the projections and 16-byte aligned weights; training with max aggregation keeps the separate
@@ -846,7 +827,7 @@ extern "C" int mpnhip_forward(const mpnhip_model* model, const void* graph_buf, 
         const bool e16_on = p.eb_hist && p.cb.ok && (!save || p.b16) && E > 0;
         const StepE16 e16 = {p.eb_hist, p.eb_hist ? p.eb_hist + es * prev : nullptr, p.eb_hist ? p.eb_hist + es * cur : nullptr,
                              step + 1 == d.L};
-        MPN_TRY(run_step(m, d, g, p.Wnode, p.bnode, io, b, save && m.agg == MPNHIP_AGG_MAX, s, &p.cw, save != 0, &p.cb, e16_on ? &e16 : nullptr));
+        MPN_TRY(run_step(m, d, g, p.Wnode, p.bnode, io, b, save && m.agg == MPNHIP_AGG_MAX, prec, s, &p.cw, save != 0, &p.cb, e16_on ? &e16 : nullptr));
         prev = cur;
     }
     if (d.L == 0 && E > 0) {
@@ -862,11 +843,11 @@ extern "C" int mpnhip_forward(const mpnhip_model* model, const void* graph_buf, 
             init_group(G);
             G.A = e0; G.lda = d.de; G.B = c.weight[0]; G.ldb = d.de; G.bias = c.bias[0];
             G.C = logits; G.ldc = 1; G.c_idx = g.perm; G.m_static = E;
-            MPN_TRY(launch_gemm(a, A_KCONTIG, B_KCONTIG, s));
+            MPN_TRY(launch_gemm(a, A_KCONTIG, B_KCONTIG, prec, s));
         } else {
             MPN_TRY(linear(e0, d.de, c.weight[0], c.bias[0], hidc[0], c.out_dims[0], E, c.out_dims[0], d.de,
-                           c.out_dims[0] != 1, s));
-            MPN_TRY(mlp_tail(c, nullptr, nullptr, hidc, logits, 1, g.perm, E, s));
+                           c.out_dims[0] != 1, prec, s));
+            MPN_TRY(mlp_tail(c, nullptr, nullptr, hidc, logits, 1, g.perm, E, prec, s));
         }
     }
     if (x_out && N > 0) MPN_HIP(hipMemcpyAsync(x_out, p.x_hist + xs * prev, xs * sizeof(float), hipMemcpyDeviceToDevice, s));
@@ -911,14 +892,14 @@ extern "C" int mpnhip_meta_layer_forward(const mpnhip_model* model, const void* 
     }
     GraphView g;
     graph_layout(n_nodes, n_edges, &g, const_cast<void*>(graph_buf));
-    MPN_TRY(pack_node_weights(*model, d, Wnode, bnode, s));
+    MPN_TRY(pack_node_weights(*model, d, Wnode, bnode, nullptr, s));
     StepIO io = {};
     io.xa = x; io.ldxa = d.kx;
     io.ea = e; io.ldea = d.ke; io.e_idx = g.perm;
     io.e_new = e_new; io.e_new_idx = g.perm; io.e_new_read_idx = g.perm;
     io.x_new = x_new;
     io.logits = nullptr;
-    return run_step(*model, d, g, Wnode, bnode, io, b, false, s);
+    return run_step(*model, d, g, Wnode, bnode, io, b, false, MPNHIP_PREC_FP32, s);
 }
 
 // ------------------------------------------------------------------------------------ Linear / MLP ops
@@ -927,7 +908,7 @@ extern "C" int mpnhip_linear(const float* x, int64_t ldx, const float* w, const 
     MPN_CHECK_ARG(m >= 0 && n >= 1 && k >= 1, "linear: bad sizes");
     if (m == 0) return MPNHIP_OK;
     MPN_CHECK_ARG(x && w && y, "linear: null pointer");
-    return linear(x, ldx, w, b, y, ldy, m, n, k, relu, static_cast<hipStream_t>(stream_));
+    return linear(x, ldx, w, b, y, ldy, m, n, k, relu, MPNHIP_PREC_FP32, static_cast<hipStream_t>(stream_));
 }
 
 extern "C" size_t mpnhip_mlp_workspace_bytes(const mpnhip_mlp* mlp, int64_t m) {
@@ -950,7 +931,7 @@ extern "C" int mpnhip_mlp_forward(const mpnhip_mlp* mlp, const float* x, float* 
     float* two[2] = {static_cast<float*>(workspace), reinterpret_cast<float*>(static_cast<char*>(workspace) + need / 2)};
     float* hid[MPNHIP_MAX_LAYERS];
     hidden_ptrs(*mlp, two, m, false, hid);
-    return mlp_forward(*mlp, x, mlp->in_dim, nullptr, hid, y, m, static_cast<hipStream_t>(stream_));
+    return mlp_forward(*mlp, x, mlp->in_dim, nullptr, hid, y, m, MPNHIP_PREC_FP32, static_cast<hipStream_t>(stream_));
 }
 
 extern "C" int mpnhip_avgpool(const float* x, int64_t rows, int hw, float* y, void* stream_) {
@@ -1132,9 +1113,9 @@ extern "C" int mpnhip_time_linear(const float* x, const float* w, const float* b
     hipEvent_t t0, t1;
     MPN_HIP(hipEventCreate(&t0));
     MPN_HIP(hipEventCreate(&t1));
-    MPN_TRY(linear(x, k, w, b, y, n, m, n, k, 1, s));
+    MPN_TRY(linear(x, k, w, b, y, n, m, n, k, 1, MPNHIP_PREC_FP32, s));
     MPN_HIP(hipEventRecord(t0, s));
-    for (int i = 0; i < iters; ++i) MPN_TRY(linear(x, k, w, b, y, n, m, n, k, 1, s));
+    for (int i = 0; i < iters; ++i) MPN_TRY(linear(x, k, w, b, y, n, m, n, k, 1, MPNHIP_PREC_FP32, s));
     MPN_HIP(hipEventRecord(t1, s));
     MPN_HIP(hipEventSynchronize(t1));
     float ms = 0.f;

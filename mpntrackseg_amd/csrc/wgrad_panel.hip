@@ -809,8 +809,6 @@ void wp_plan(int64_t rows_expected, int64_t rows_upper, int nbatch, int tiles, b
 
 bool wp_light(int variant, int n_out, int k_in) { return variant < 16 && (size_t)n_out * tn_kpad(k_in) <= 16384; }
 
-thread_local WpBatch* g_wp = nullptr;
-
 size_t wp_lds_bytes() {
     // two stage images (the pipelined split loop) of the largest variant (BO + BC = 384): 39 KB each
     return 2 * 3 * WP_KB * wp_pitch(320, 64);
@@ -854,7 +852,7 @@ size_t wp_slab_floats(int n_out, int k_in, int64_t rows, int nbatch, bool ranged
     return need;
 }
 
-void wp_batch_begin(WpBatch* b, float* slab, size_t slab_floats, bool batched) {
+void wp_batch_init(WpBatch* b, float* slab, size_t slab_floats, bool batched, const hipStream_t* stream) {
     b->batched = batched;
     b->tab.njobs = 0;
     b->slab = slab;
@@ -866,35 +864,23 @@ void wp_batch_begin(WpBatch* b, float* slab, size_t slab_floats, bool batched) {
     b->nblocks2 = 0;
     b->bytes2 = 0.0;
     b->nred = 0;
-    b->stream = nullptr;
-    b->has_stream = false;
-    g_wp = b;
+    b->stream = stream ? *stream : nullptr;
+    b->has_stream = stream != nullptr;
 }
-void wp_batch_set_stream(hipStream_t s) {
-    if (g_wp) { g_wp->stream = s; g_wp->has_stream = true; }
-}
-bool wp_batch_roll(int* status) {
-    WpBatch* b = g_wp;
+bool wp_batch_roll(WpBatch* b, int* status) {
     *status = MPNHIP_OK;
-    if (!b || !b->has_stream || b->tab.njobs == 0) return false;
-    float* slab = b->slab;
-    const size_t fl = b->slab_floats;
-    const bool batched = b->batched;
+    if (!b->has_stream || b->tab.njobs == 0) return false;
     const hipStream_t s = b->stream;
-    *status = wp_batch_flush(s);
-    wp_batch_begin(b, slab, fl, batched);
-    wp_batch_set_stream(s);
+    *status = wp_batch_flush(b, s);
+    wp_batch_init(b, b->slab, b->slab_floats, b->batched, &s);
     return *status == MPNHIP_OK;
 }
-bool wp_batch_open() { return g_wp != nullptr; }
-void wp_batch_abort() { g_wp = nullptr; }
 
 static bool ranged_gather(const WpProduct& p) { return p.dz_idx || p.h_idx || p.H2; }
 
 // records the n (1 or 2: the direction groups of one product) jobs, or none of them
-bool wp_batch_add(const WpProduct* ps, int n) {
-    WpBatch* b = g_wp;
-    if (!b || b->tab.njobs + n > WP_MAX_JOBS) return false;
+bool wp_batch_add(WpBatch* b, const WpProduct* ps, int n) {
+    if (b->tab.njobs + n > WP_MAX_JOBS) return false;
     size_t need = 0;
     for (int i = 0; i < n; ++i) {
         if (!wp_eligible(ps[i])) return false;
@@ -939,12 +925,9 @@ bool wp_batch_add(const WpProduct* ps, int n) {
     }
     return true;
 }
-bool wp_batch_add(const WpProduct& p) { return wp_batch_add(&p, 1); }
 
-int wp_batch_flush(hipStream_t s) {
-    WpBatch* b = g_wp;
-    g_wp = nullptr;
-    if (!b || b->tab.njobs == 0) return MPNHIP_OK;
+int wp_batch_flush(WpBatch* b, hipStream_t s) {
+    if (b->tab.njobs == 0) return MPNHIP_OK;
     static const bool attr_set = [] {
         return hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_panel_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                    (int)wp_lds_bytes()) == hipSuccess;
