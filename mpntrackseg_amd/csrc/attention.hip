@@ -138,7 +138,9 @@ __global__ void k_max_seg_len(const int* __restrict__ seg_ptr, int nseg, int* __
 using namespace mpnhip;
 
 // The dynamic LDS holds one segment's weights; sized for the worst case the graph can have (<= E), capped at
-// 60 KB (15,360 neighbours in one direction) -- larger segments are rejected.
+// 60 KB (15,360 neighbours in one direction).  A longer (hub) segment is not rejected: k_attention_fwd leaves the
+// buffer alone for it and recomputes expf(l - max) / den per edge while it streams the rows
+// (tests/test_gpu_attention.py runs segments of 15,360 and 15,361 edges).
 static int attention_lds_bytes(int64_t n_edges) {
     int64_t b = n_edges * 4;
     return (int)(b < 60 * 1024 ? (b < 256 ? 256 : b) : 60 * 1024);
@@ -168,6 +170,9 @@ extern "C" int mpnhip_attention_aggregate_backward(const void* graph_buf, int n_
     MPN_CHECK_ARG(feat > 0 && feat % 4 == 0, "attention_backward: feature size must be a multiple of 4");
     if (n_nodes == 0) return MPNHIP_OK;
     MPN_CHECK_ARG(x && grad_in && grad_out, "attention_backward: null tensor");
+    // k_attention_dx reads the weights too, not only the grad_logits branch
+    MPN_CHECK_ARG(n_edges == 0 || !(grad_x || grad_logits) || weights, "attention_backward: null weights");
+    MPN_CHECK_ARG(n_edges == 0 || !grad_logits || workspace_dw, "attention_backward: null workspace");
     GraphView g;
     graph_layout(n_nodes, n_edges, &g, const_cast<void*>(graph_buf));
     if (grad_x) {
@@ -175,7 +180,6 @@ extern "C" int mpnhip_attention_aggregate_backward(const void* graph_buf, int n_
         MPN_LAUNCH_CHECK();
     }
     if (grad_logits && n_edges > 0) {
-        MPN_CHECK_ARG(weights && workspace_dw, "attention_backward: null weights / workspace");
         hipLaunchKernelGGL(k_attention_dw, dim3((unsigned)n_edges), dim3(AT), 0, s, g, x, feat, grad_in, grad_out, workspace_dw);
         MPN_LAUNCH_CHECK();
         hipLaunchKernelGGL(k_attention_dlogit, dim3(2 * n_nodes), dim3(AT), 0, s, g, weights, workspace_dw, grad_logits);

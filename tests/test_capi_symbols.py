@@ -92,3 +92,38 @@ def test_new_entry_points_argument_checks_without_gpu():
     assert l.mpnhip_embedding_keep(None, 17, 5, None, 0, None, None) != 0
     assert b"embedding_keep" in l.mpnhip_last_error()
     assert l.mpnhip_embedding_check(None, 17, None, 0, None, None, None) != 0   # the mismatch counter is always required
+
+
+def test_attention_and_avgpool_argument_checks_without_gpu():
+    """The host-side checks of the mask branch's entry points: everything below returns before a kernel is launched (the
+    non-null pointers are host dummies that are never dereferenced)."""
+    l = capi.load()
+    dummy = ctypes.create_string_buffer(256)
+    p = ctypes.cast(dummy, ctypes.c_void_p)
+    # forward: feature size not a multiple of 4, null graph
+    assert l.mpnhip_attention_aggregate(p, 3, 5, p, 6, p, p, p, p, None) != 0
+    assert b"attention" in l.mpnhip_last_error()
+    assert l.mpnhip_attention_aggregate(p, 3, 5, p, 0, p, p, p, p, None) != 0
+    assert l.mpnhip_attention_aggregate(None, 3, 5, p, 8, p, p, p, p, None) != 0
+    assert b"attention" in l.mpnhip_last_error()
+    assert l.mpnhip_attention_aggregate(p, 3, 5, None, 8, p, p, p, p, None) != 0      # null x with nodes
+    assert l.mpnhip_attention_aggregate(p, 3, 5, p, 8, None, p, p, p, None) != 0      # null logits with edges
+    # no nodes: a successful no-op with a non-null graph buffer, whatever else is null
+    assert l.mpnhip_attention_aggregate(p, 0, 0, None, 8, None, None, None, None, None) == 0
+    assert l.mpnhip_attention_aggregate_backward(p, 0, 0, None, 8, None, None, None, None, 0, None, None, None) == 0
+    # backward: the same two refusals ...
+    assert l.mpnhip_attention_aggregate_backward(p, 3, 5, p, 6, p, p, p, p, 0, p, p, None) != 0
+    assert b"attention" in l.mpnhip_last_error()
+    assert l.mpnhip_attention_aggregate_backward(None, 3, 5, p, 8, p, p, p, p, 0, p, p, None) != 0
+    # ... and null weights with edges are refused whichever gradient is requested (k_attention_dx reads them as well)
+    for gx, gl in ((p, None), (None, p), (p, p)):
+        assert l.mpnhip_attention_aggregate_backward(p, 3, 5, p, 8, None, p, p, gx, 0, gl, p, None) != 0
+        assert b"null weights" in l.mpnhip_last_error()
+    assert l.mpnhip_attention_aggregate_backward(p, 3, 5, p, 8, p, p, p, None, 0, p, None, None) != 0   # grad_logits without workspace
+    assert b"null workspace" in l.mpnhip_last_error()
+    # avgpool: hw = 0 and negative rows are refused, rows = 0 is a no-op, null pointers with rows are refused
+    assert l.mpnhip_avgpool(p, 4, 0, p, None) != 0
+    assert b"avgpool" in l.mpnhip_last_error()
+    assert l.mpnhip_avgpool(p, -1, 4, p, None) != 0
+    assert l.mpnhip_avgpool(None, 0, 4, None, None) == 0
+    assert l.mpnhip_avgpool(None, 4, 4, p, None) != 0

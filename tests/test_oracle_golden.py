@@ -408,3 +408,48 @@ def test_g16_graph_batched_loss_oracle_against_the_reference_per_graph_loss(gold
         a, b = int(ptr[g]), int(ptr[g + 1])
         li = LO.tracking_loss([logits.detach()[s, a:b] for s in range(k)], labels[a:b], weight=w)
         assert abs(float(li) - float(z[f"{tag}:per_graph"][g])) <= 1e-6 * max(1.0, abs(float(z[f"{tag}:per_graph"][g])))
+
+
+def _g18_oracle(z, dtype):
+    """oracle/attention_oracle.py on g18's inputs, composed as the reference composes it: identity node_model over
+    cat(x, flow_in, flow_out), loss = sum(flow * upstream); returns flow_in, flow_out, total grad_x, grad_logits."""
+    from oracle import attention_oracle as AO
+    x = torch.from_numpy(z["x"]).to(dtype).requires_grad_(True)
+    lg = torch.from_numpy(z["logits"]).to(dtype).requires_grad_(True)
+    fi, fo, w = AO.attention_aggregate(x, torch.from_numpy(z["edge_index"]), lg, dtype)
+    assert fi.dtype == dtype and fi.shape == x.shape and w.shape == (lg.numel(),)
+    flow = torch.cat((x, fi, fo), dim=1)
+    gx, gl = torch.autograd.grad((flow * torch.from_numpy(z["upstream"]).to(dtype)).sum(), [x, lg])
+    return fi.detach().numpy(), fo.detach().numpy(), gx.numpy(), gl.numpy(), w.detach().numpy()
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float64])
+def test_g18_attention_oracle_against_reference_attention_model(golden, dtype):
+    """oracle/attention_oracle.py against the reference's own TimeAwareAttentionModel.forward and its autograd
+    (tests/golden/g18_attention.npz, tools/make_golden.py gen_g18).  Error measure of the operator tests: max |got - ref| /
+    max |ref| per tensor.  The float32 oracle evaluates the same formula with the same CPU ops: 1e-6.  The float64 oracle
+    differs from the float32 fixture by the fixture's own rounding: the segments here hold at most a few tens of edges, i.e. a
+    few tens of float32 roundings (6e-8 each) per element, so the same 1e-6 holds."""
+    z = golden("g18_attention.npz")
+    ei = z["edge_index"]
+    # the case really has what it is there for: self loops, duplicate edges, an isolated node, a node that is only a neighbour
+    assert ei.shape == (2, 400) and z["x"].shape == (40, 4, 2, 2)
+    assert int((ei[0] == ei[1]).sum()) >= 6 and len({(int(a), int(b)) for a, b in ei.T}) < 400
+    assert 0 not in ei and 1 not in ei[0] and 1 in ei[1]
+    fi, fo, gx, gl, w = _g18_oracle(z, dtype)
+
+    def err(a, b):
+        return float(np.abs(a.astype(np.float64) - b).max() / max(float(np.abs(b).max()), 1e-30))
+    errs = {"flow_in": err(fi, z["flow_in"]), "flow_out": err(fo, z["flow_out"]), "grad_x": err(gx, z["grad_x_total"]),
+            "grad_logits": err(gl, z["grad_logits"])}
+    print("g18", dtype, errs)
+    assert max(errs.values()) < 1e-6, errs
+    # rows of empty segments are exactly zero in the reference and in the oracle; self loops carry no weight and no gradient
+    assert not z["flow_in"][:2].any() and not z["flow_out"][:2].any() and not fi[:2].any() and not fo[:2].any()
+    loops = ei[0] == ei[1]
+    assert not w[loops].any() and not gl[loops].any() and not z["grad_logits"][loops].any()
+    # every non-empty segment's weights sum to 1 (up to the 1e-12 of the composite)
+    for mask in (ei[0] > ei[1], ei[0] < ei[1]):
+        s = np.zeros(40)
+        np.add.at(s, ei[0][mask], w[mask].astype(np.float64))
+        assert np.abs(s[np.unique(ei[0][mask])] - 1.0).max() < (1e-6 if dtype == torch.float32 else 1e-11)

@@ -33,6 +33,9 @@ Fixtures:
                                running statistics in float64 (three aggregations).
   g6_mask_branch.npz           full forward WITH the attention / mask branch (deterministic weights for all 54
                                tensors): mask predictions + reference-autograd gradients through both branches.
+  g18_attention.npz            TimeAwareAttentionModel.forward alone (identity node_model, given logits) on a 40-node / 400-edge graph
+                               with self loops, duplicate edges and empty segments: flow_in / flow_out + reference autograd.  Only
+                               with --only g18.
 
 Usage:  python tools/make_golden.py [--only g1,g2,...]
 """
@@ -245,6 +248,43 @@ def gen_g6(mpn):
         rec["Gn:" + k] = np.float64(np.sqrt((a.astype(np.float64) ** 2).sum()))
     np.savez_compressed(os.path.join(GOLD, "g6_mask_branch.npz"), **rec)
     print("g6 ok; |mask| per step", rec["mask_abssum"])
+
+
+def g18_graph():
+    """The small operator-level graph of g18: 40 nodes, 400 edges.  Node 0 is isolated; node 1 is only ever a neighbour
+    (``col``), never a ``row``: both its segments are empty while its features are gathered; the last node has only past
+    neighbours.  380 random (row, col) pairs with row in [2, N) and col in [1, N) (self loops occur), 14 of them stored a
+    second time at the end, and 6 forced self loops."""
+    N = 40
+    row = 2 + (synth.uniform01(18, 380, stream=0) * (N - 2)).astype(np.int64)
+    col = 1 + (synth.uniform01(18, 380, stream=1) * (N - 1)).astype(np.int64)
+    dup = (synth.uniform01(18, 14, stream=2) * 380).astype(np.int64)
+    loops = np.array([2, 5, 5, 17, 38, 39], dtype=np.int64)
+    ei = np.stack([np.concatenate([row, row[dup], loops]), np.concatenate([col, col[dup], loops])]).astype(np.int64)
+    assert ei.shape == (2, 400) and 0 not in ei and 1 not in ei[0] and 1 in ei[1]
+    assert (ei[0] == ei[1]).sum() >= 6 and (ei[0] == N - 1).any()
+    return N, ei
+
+
+def gen_g18(mpn):
+    """TimeAwareAttentionModel.forward (mpn.py:111-137) ALONE, on the CPU: identity ``node_model``, a ``cls_net`` that returns
+    the given logits -- the operator ``mpnhip_attention_aggregate`` computes, without any convolution behind it.  Recorded: the
+    inputs, the concatenated output split back into flow_in / flow_out, and the reference's autograd gradients of x (total:
+    the concatenation passes x through as well) and of the logits under a fixed random upstream gradient."""
+    N, ei = g18_graph()
+    E = ei.shape[1]
+    x = torch.from_numpy(synth.normal(18, (N, 4, 2, 2), stream=3)).requires_grad_(True)
+    logits = torch.from_numpy(synth.normal(18, (E, 1), stream=4, std=2.0)).requires_grad_(True)
+    up = torch.from_numpy(synth.normal(18, (N, 12, 2, 2), stream=5))
+    model = mpn.TimeAwareAttentionModel(torch.nn.Identity(), None, None)
+    flow, dec = model(x, torch.from_numpy(ei), logits, lambda edge_attr: (edge_attr, None))
+    assert flow.shape == (N, 12, 2, 2) and dec is logits and torch.equal(flow[:, :4], x)
+    gx, gl = torch.autograd.grad((flow * up).sum(), [x, logits])
+    rec = {"edge_index": ei, "x": x.detach().numpy(), "logits": logits.detach().numpy(), "upstream": up.numpy(),
+           "flow_in": flow[:, 4:8].detach().numpy(), "flow_out": flow[:, 8:12].detach().numpy(),
+           "grad_x_total": gx.numpy(), "grad_logits": gl.numpy()}
+    np.savez_compressed(os.path.join(GOLD, "g18_attention.npz"), **rec)
+    print("g18 ok: N", N, "E", E, "self loops", int((ei[0] == ei[1]).sum()), "max|flow|", float(flow[:, 4:].detach().abs().max()))
 
 
 def structure_graph():
@@ -960,6 +1000,7 @@ def main():
     if "g15" in only: gen_g15(mpn)
     if "g16" in only: gen_g16()
     if "g17" in only: gen_g17()
+    if "g18" in only: gen_g18(mpn)
 
 
 if __name__ == "__main__":
