@@ -486,6 +486,45 @@ int mpnhip_undirected_merge_fill(int64_t n_edges, int64_t n_unique, const void* 
 int mpnhip_threshold_flags(const float* preds, int64_t n, float threshold, unsigned char* flags, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * From edge scores to track ids: the projectors (tracker/projectors.py), MPNTracker._assign_ped_ids
+ * (tracker/mpn_tracker.py:231-248) and Postprocessor.drop_short_trajectories (tracker/postprocessing.py:14-18).
+ * edge_index [2, K] int64 is an undirected list with row < col per edge (mpnhip_undirected_merge_fill's, pruned or not), in any
+ * edge order; n_nodes, n_edges < 2^30.  An edge with an id outside [0, n_nodes) is never followed: it is counted
+ * (counters[3]) and otherwise skipped.  Integer and compare-only arithmetic throughout: the same bits on every call.
+ * ------------------------------------------------------------------------------------------- */
+/* compute_constr_satisfaction_rate(undirected_edges=False, return_flow_vals=True) (utils/evaluation.py:370-414) up to its last
+ * division: round_preds [K] = edge_preds > 0.5 as 0 / 1 (NaN -> 0), flow_out / flow_in [n_nodes] (int32) = active edges per row /
+ * column, counters (device int32 [8]) = { #(flow_out > 1), #(flow_in > 1), num_constraints = distinct rows + distinct cols,
+ * edges with an id out of range, 0 ... }.  constr_sat_rate = 1 - (counters[0] + counters[1]) / counters[2] is the caller's.
+ * With n_edges == 0 and n_nodes == 0 nothing is written. */
+size_t mpnhip_project_round_count_workspace_bytes(int64_t n_nodes);
+int mpnhip_project_round_count(const int64_t* edge_index, int64_t n_edges, int64_t n_nodes, const float* edge_preds,
+                               float* round_preds, int32_t* flow_out, int32_t* flow_in, int32_t* counters, void* workspace,
+                               size_t workspace_bytes, void* stream);
+/* The loop of GreedyProjector.project (projectors.py:41-60) as two edge-parallel passes, in place on round_preds (as
+ * mpnhip_project_round_count left it, with its flow counts): A. every node with flow_out > 1 keeps its active outgoing edge with
+ * the largest edge_preds -- the lowest edge id on a tie -- and loses the others; B. the same over the incoming edges of every
+ * node whose in-count is still above 1 after A.  Per node one 64-bit atomicMax on (score bits << 32) | ~edge id. */
+size_t mpnhip_project_greedy_workspace_bytes(int64_t n_nodes);
+int mpnhip_project_greedy(const int64_t* edge_index, int64_t n_edges, int64_t n_nodes, const float* edge_preds, float* round_preds,
+                          const int32_t* flow_out, const int32_t* flow_in, void* workspace, size_t workspace_bytes, void* stream);
+/* The sub-problem of ExactProjector.project (projectors.py:92-93): nodes_mask [n_nodes] = flow_in > 1 | flow_out > 1,
+ * edges_mask [K] = nodes_mask[row] | nodes_mask[col]; the selection itself is mpnhip_compact + the gathers. */
+int mpnhip_project_violated_masks(const int64_t* edge_index, int64_t n_edges, int64_t n_nodes, const int32_t* flow_out,
+                                  const int32_t* flow_in, unsigned char* nodes_mask, unsigned char* edges_mask, void* stream);
+/* scipy.sparse.csgraph.connected_components(directed=False) over the edges with edge_preds == 1 (_assign_ped_ids): labels
+ * [n_nodes] (int64) = rank of the component's smallest node among all components' smallest nodes, n_components (device int32,
+ * may be NULL).  Lock-free union-find in one launch (the larger root goes under the smaller by compare-and-swap), one pass
+ * that resolves every node's root, a scan over the root flags.  Any undirected graph: cycles, duplicate edges, isolated nodes. */
+size_t mpnhip_connected_components_workspace_bytes(int64_t n_nodes);
+int mpnhip_connected_components(const int64_t* edge_index, int64_t n_edges, int64_t n_nodes, const float* edge_preds, int64_t* labels,
+                                int32_t* n_components, void* workspace, size_t workspace_bytes, void* stream);
+/* drop_short_trajectories: counts [n_nodes] (int32) = nodes per label (labels in [0, n_nodes)), keep [n_nodes] =
+ * counts[labels[v]] >= min_track_len.  Labels are not renumbered. */
+int mpnhip_track_lengths(const int64_t* labels, int64_t n_nodes, int64_t min_track_len, int32_t* counts, unsigned char* keep,
+                         void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Measurement helpers used by bench.py (HIP events on the launch stream; these synchronise).
  * ------------------------------------------------------------------------------------------- */
 /* In-stream kernel timing of the real hot path: while enabled, mpnhip_forward brackets (a) the first-layer

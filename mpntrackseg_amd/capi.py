@@ -138,6 +138,14 @@ SIGNATURES = {
     "mpnhip_undirected_merge_sort": (_I, [_P, _L, _L, _P, _P, _P, _Z, _P]),
     "mpnhip_undirected_merge_fill": (_I, [_L, _L, _P, _Z, _P, _P, _P, _P]),
     "mpnhip_threshold_flags": (_I, [_P, _L, C.c_float, _P, _P]),
+    "mpnhip_project_round_count_workspace_bytes": (_Z, [_L]),
+    "mpnhip_project_round_count": (_I, [_P, _L, _L, _P, _P, _P, _P, _P, _P, _Z, _P]),
+    "mpnhip_project_greedy_workspace_bytes": (_Z, [_L]),
+    "mpnhip_project_greedy": (_I, [_P, _L, _L, _P, _P, _P, _P, _P, _Z, _P]),
+    "mpnhip_project_violated_masks": (_I, [_P, _L, _L, _P, _P, _P, _P, _P]),
+    "mpnhip_connected_components_workspace_bytes": (_Z, [_L]),
+    "mpnhip_connected_components": (_I, [_P, _L, _L, _P, _P, _P, _P, _Z, _P]),
+    "mpnhip_track_lengths": (_I, [_P, _L, _L, _P, _P, _P]),
     "mpnhip_profile_enable": (_I, [_I]),
     "mpnhip_edge_chain_active": (_I, [C.POINTER(Model)]),
     "mpnhip_profile_read": (_I, [C.POINTER(C.c_float), C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(C.c_int),

@@ -16,8 +16,11 @@ only), the directed scores are merged into one score per undirected pair (``grap
 ``prune_threshold`` are dropped (``graph.prune_edges``) -- the object the reference hands to its projectors, built on the
 device.  ``evaluate_graph_in_batches`` stays the directed edge scores alone.
 
-The projection of the scores onto trajectories (``_project_graph_model_output`` and after: LP / greedy rounding, pandas
-bookkeeping) stays in the reference."""
+``track_sequence`` adds the next three lines of ``MPNTracker.track``: the projection of the scores onto trajectories
+(``_project_graph_model_output``, ``projectors.py`` here: greedy rounding on the device, or the exact rounding whose linear
+program runs on the host), ``assign_ped_ids`` (``_assign_ped_ids``, ``:231-248``: connected components of the rounded graph, a
+lock-free union-find in ``csrc/projection.hip``) and ``drop_short_trajectories`` (``tracker/postprocessing.py:14-18``) --
+detections in, track ids out.  Mask pasting, RLE encoding and the data-frame / text output stay in the reference."""
 import collections
 import types
 
@@ -214,3 +217,72 @@ def _mask_output_size(model, x_ext):
             elif isinstance(m, torch.nn.Conv2d):
                 hw = [(v + 2 * m.padding[i] - m.dilation[i] * (m.kernel_size[i] - 1) - 1) // m.stride[i] + 1 for i, v in enumerate(hw)]
     return tuple(hw)
+
+
+@capi.on_tensor_device
+def assign_ped_ids(edge_index, edge_preds, num_nodes):
+    """``MPNTracker._assign_ped_ids`` (mpn_tracker.py:231-248): int64 [num_nodes] labels of the connected components over the edges
+    with ``edge_preds == 1``, numbered as ``scipy.sparse.csgraph.connected_components(directed=False)`` numbers them (by smallest
+    node).  Any undirected edge list; no host read."""
+    lib = capi.load()
+    capi.require_device(edge_index, edge_preds)
+    ei = edge_index.to(torch.int64).contiguous()
+    p = capi.f32c(edge_preds).view(-1)
+    K, N, dev = ei.shape[1], int(num_nodes), ei.device
+    if p.numel() != K:
+        raise MpnhipError("one score per edge (%d scores, %d edges)" % (p.numel(), K))
+    labels = torch.empty(max(N, 1), dtype=torch.int64, device=dev)[:N]
+    ws = capi.workspace(lib.mpnhip_connected_components_workspace_bytes(N), dev, "components")
+    check(lib.mpnhip_connected_components(ptr(ei), K, N, ptr(p), ptr(labels), None, ptr(ws), ws.numel(), stream_ptr()),
+          "mpnhip_connected_components")
+    return labels
+
+
+@capi.on_tensor_device
+def drop_short_trajectories(ped_ids, min_track_len):
+    """``Postprocessor.drop_short_trajectories`` (tracker/postprocessing.py:14-18) as a mask: bool [N], True for the detections
+    whose id occurs at least ``min_track_len`` times.  The ids are not renumbered, as in the reference."""
+    lib = capi.load()
+    capi.require_device(ped_ids)
+    labels = ped_ids.to(torch.int64).contiguous().view(-1)
+    N = labels.numel()
+    counts = torch.empty(max(N, 1), dtype=torch.int32, device=labels.device)[:N]
+    keep = torch.empty(max(N, 1), dtype=torch.uint8, device=labels.device)[:N]
+    check(lib.mpnhip_track_lengths(ptr(labels), N, int(min_track_len), ptr(counts), ptr(keep), stream_ptr()), "mpnhip_track_lengths")
+    return keep.bool()
+
+
+TrackResult = collections.namedtuple('TrackResult', ['ped_ids', 'keep', 'edge_index', 'edge_preds', 'node_preds', 'constr_satisf_rate',
+                                                     'final_edge_preds'])
+
+
+@capi.on_tensor_device
+def track_sequence(model, x, edge_index, edge_attr, reid_emb_dists, frame_num_per_node, frames_per_graph, top_k_nns,
+                   reciprocal_k_nns=True, set_pruned_edges_to_inactive=False, windows_per_launch=1, rank=0, world_size=1,
+                   reduce_fn=None, x_ext=None, prune_threshold=0.5, rounding_method='greedy', min_track_len=2, solver=None):
+    """``evaluate_sequence``, then ``_project_graph_model_output``, ``_assign_ped_ids`` and ``drop_short_trajectories``
+    (mpn_tracker.py:212-248, postprocessing.py:14-18).  Arguments as ``evaluate_sequence``, plus ``rounding_method`` ('greedy' or
+    'exact'), ``min_track_len`` and ``solver`` (for 'exact': see ``projectors.ExactProjector``).  Returns a ``TrackResult``:
+
+    ``ped_ids`` [N] int64            track id of every detection
+    ``keep`` [N] bool                False for the detections of tracks shorter than ``min_track_len``
+    ``edge_index`` [2, K], ``edge_preds`` [K]   ``evaluate_sequence``'s undirected pruned list with the ROUNDED scores
+    ``node_preds``, ``final_edge_preds``        as ``evaluate_sequence`` returns them
+    ``constr_satisf_rate``           share of the flow constraints the thresholded scores satisfied before the rounding
+
+    With 'greedy' this adds one host read (the two constraint counters) to ``evaluate_sequence``'s."""
+    from . import projectors
+    if rounding_method not in ('greedy', 'exact'):
+        raise RuntimeError("Rounding type for projector not understood")
+    seq = evaluate_sequence(model, x, edge_index, edge_attr, reid_emb_dists, frame_num_per_node, frames_per_graph, top_k_nns,
+                            reciprocal_k_nns=reciprocal_k_nns, set_pruned_edges_to_inactive=set_pruned_edges_to_inactive,
+                            windows_per_launch=windows_per_launch, rank=rank, world_size=world_size, reduce_fn=reduce_fn, x_ext=x_ext,
+                            prune_threshold=prune_threshold)
+    N = int(x.shape[0])
+    if rounding_method == 'greedy':
+        rounded, rate = projectors.greedy_round(seq.edge_index, seq.edge_preds, N)
+    else:
+        rounded, rate = projectors.exact_round(seq.edge_index, seq.edge_preds, N, solver=solver)
+    ped_ids = assign_ped_ids(seq.edge_index, rounded, N)
+    keep = drop_short_trajectories(ped_ids, min_track_len)
+    return TrackResult(ped_ids, keep, seq.edge_index, rounded, seq.node_preds, rate, seq.final_edge_preds)

@@ -36,6 +36,9 @@ Fixtures:
   g18_attention.npz            TimeAwareAttentionModel.forward alone (identity node_model, given logits) on a 40-node / 400-edge graph
                                with self loops, duplicate edges and empty segments: flow_in / flow_out + reference autograd.  Only
                                with --only g18.
+  g19_projection.npz           GreedyProjector.project, MPNTracker._assign_ped_ids and Postprocessor.drop_short_trajectories (min_track_len
+                               2 and 5) on three 48-node score graphs (one with tied scores), a 650-node graph with a hub of > 256 active
+                               edges on each side, and the pruned undirected outputs of g17.  Only with --only g19.
 
 Usage:  python tools/make_golden.py [--only g1,g2,...]
 """
@@ -930,6 +933,109 @@ def gen_g17():
     np.savez_compressed(os.path.join(GOLD, "g17_window_tail_masks.npz"), **{f"{tag}:node_preds": arr for tag, arr in masks.items()})
 
 
+def _g19_score_graph(rng, frames, dets, p_edge, max_dist=None, tied=False):
+    """Cross-frame pairs (row < col, detections ordered by frame) kept with probability p_edge; 35 % of the scores in (0.5, 1], the
+    rest in [0, 0.5]; ``tied``: scores rounded to multiples of 1/8."""
+    n = frames * dets
+    frame = np.arange(n) // dets
+    i, j = np.triu_indices(n, 1)
+    ok = frame[i] != frame[j]
+    if max_dist is not None:
+        ok &= (frame[j] - frame[i]) <= max_dist
+    ok &= rng.random(i.size) < p_edge
+    ei = np.stack((i[ok], j[ok])).astype(np.int64)
+    K = ei.shape[1]
+    u = rng.random(K)
+    p = np.where(rng.random(K) < 0.35, 0.5 + 0.5 * (1.0 - u), 0.5 * u).astype(np.float32)
+    if tied:
+        p = (np.round(p * 8) / 8).astype(np.float32)
+    return ei, p, n
+
+
+def _g19_stats(ei, p, n):
+    """Violated out- / in-constraints of the thresholded scores, the in-constraints that the out-pass alone clears, and the
+    arg-maxes (of either pass) that several edges attain -- plain numpy, for the generator's assertions."""
+    rp = (p > np.float32(0.5)).astype(np.float32)
+    v_out = int((np.bincount(ei[0][rp == 1], minlength=n) > 1).sum())
+    v_in = int((np.bincount(ei[1][rp == 1], minlength=n) > 1).sum())
+    ties = 0
+    for side in (0, 1):
+        if side == 1:
+            still = int((np.bincount(ei[1][rp == 1], minlength=n) > 1).sum())
+        for node in range(n):
+            act = np.flatnonzero((ei[side] == node) & (rp == 1))
+            if act.size > 1:
+                ties += int((p[act] == p[act].max()).sum() > 1)
+                rp[act] = 0
+                rp[act[np.argmax(p[act])]] = 1
+    return v_out, v_in, v_in - still, ties
+
+
+def gen_g19():
+    """GreedyProjector.project (tracker/projectors.py:19-67), MPNTracker._assign_ped_ids (tracker/mpn_tracker.py:231-248, called
+    unbound on a namespace carrying full_graph) and Postprocessor.drop_short_trajectories (tracker/postprocessing.py:14-18,
+    min_track_len 2 and 5) of the reference itself.  Inputs and outputs are stored per case, with the numbers of violated out- and
+    in-constraints, of in-constraints the out-pass clears and of arg-maxes decided by edge id."""
+    import pandas as pd
+    EV, TR, PL = _import_tracking_stack()
+    from mot_neural_solver.tracker import projectors as PJ
+    from mot_neural_solver.tracker.postprocessing import Postprocessor
+    rng = np.random.default_rng(19)
+    cases = {}
+    for tag, tied in (("a", False), ("b", False), ("t", True)):
+        cases[tag] = _g19_score_graph(rng, 8, 6, 0.6, tied=tied)
+    # the hub: a sparse background, one mid-sequence node joined to every node of every other frame with scores above 0.5
+    ei, p, n = _g19_score_graph(rng, 130, 5, 0.3, max_dist=2)
+    hub = 65 * 5 + 2
+    others = np.array([v for v in range(n) if v // 5 != hub // 5], dtype=np.int64)
+    hub_ei = np.stack((np.minimum(others, hub), np.maximum(others, hub)))
+    background = ~((ei[0] == hub) | (ei[1] == hub))
+    ei = np.concatenate((ei[:, background], hub_ei), axis=1)
+    p = np.concatenate((p[background], (0.55 + 0.4 * rng.random(others.size)).astype(np.float32)))
+    order = rng.permutation(ei.shape[1])
+    cases["hub"] = (np.ascontiguousarray(ei[:, order]), p[order], n)
+    z = np.load(os.path.join(GOLD, "g17_window_tail.npz"))
+    for tag in ("s1", "s2", "l1", "l2"):
+        cases["g17_" + tag] = (z[f"{tag}:edge_index"], z[f"{tag}:edge_preds"], int(z[f"{tag[0]}:frame"].shape[0]))
+    rec = {"cases": np.array(list(cases))}
+    for tag, (ei, p, n) in cases.items():
+        assert (ei[0] < ei[1]).all() and p.dtype == np.float32
+        graph_obj = _GeoData(edge_index=torch.from_numpy(ei), edge_preds=torch.from_numpy(p).clone())
+        graph_obj.num_nodes = n
+        df = pd.DataFrame({"frame": np.arange(n) // 5})
+        full_graph = types.SimpleNamespace(graph_obj=graph_obj, graph_df=df)
+        proj = PJ.GreedyProjector(full_graph)
+        proj.project()
+        round_preds = graph_obj.edge_preds.numpy().copy()
+        rate = np.float32(proj.constr_satisf_rate)
+        assert float(rate) == proj.constr_satisf_rate or np.isnan(rate)
+        graph_obj.edge_preds, graph_obj.edge_index = round_preds, ei     # (graph_obj.numpy() of _project_graph_model_output)
+        me = types.SimpleNamespace(full_graph=full_graph)
+        TR.MPNTracker._assign_ped_ids(me)
+        labels = np.asarray(me.final_projected_output["ped_id"], dtype=np.int64)
+        rec.update({f"{tag}:edge_index": ei, f"{tag}:edge_preds": p, f"{tag}:num_nodes": np.int64(n), f"{tag}:round_preds": round_preds,
+                    f"{tag}:constr_satisf_rate": rate, f"{tag}:ped_ids": labels})
+        for mtl in (2, 5):
+            pp = Postprocessor(me.final_projected_output.copy(), None, {"min_track_len": mtl})
+            pp.drop_short_trajectories()
+            keep = np.zeros(n, dtype=bool)
+            keep[pp.traj_df.index.to_numpy()] = True
+            rec[f"{tag}:keep{mtl}"] = keep
+        stats = _g19_stats(ei, p, n)
+        rec[f"{tag}:stats"] = np.array(stats, np.int64)
+        if not tag.startswith("g17"):
+            assert min(stats[:3]) >= 10, (tag, stats)
+        if tag == "t":
+            assert stats[3] >= 1 and (p == 0.5).any(), (tag, stats)
+        if tag == "hub":
+            act = p > 0.5
+            assert int((act & (ei[0] == hub)).sum()) > 256 and int((act & (ei[1] == hub)).sum()) > 256
+        print("g19", tag, "nodes", n, "edges", ei.shape[1], "violated out / in, cleared by the out-pass, ties:", stats, "rate", float(rate),
+              "active after", int(round_preds.sum()), "tracks", int(labels.max()) + 1, "kept (2, 5)", int(rec[f"{tag}:keep2"].sum()),
+              int(rec[f"{tag}:keep5"].sum()))
+    np.savez_compressed(os.path.join(GOLD, "g19_projection.npz"), **rec)
+
+
 def gen_g14():
     """MOTGraph._get_edge_ixs + construct_graph_object (data/mot_graph.py:195-218, 283-317) of the reference itself, on synthetic
     detections with the appearance data supplied directly (``_load_appearance_data`` replaced: it reads image crops / .pt files,
@@ -1001,6 +1107,7 @@ def main():
     if "g16" in only: gen_g16()
     if "g17" in only: gen_g17()
     if "g18" in only: gen_g18(mpn)
+    if "g19" in only: gen_g19()
 
 
 if __name__ == "__main__":
