@@ -147,6 +147,29 @@ int mpnhip_debug_backward_saved(const mpnhip_model* model, int n_nodes, int64_t 
                                 size_t bwd_workspace_bytes, int what, int step, int layer, float* out, int64_t* rows,
                                 int* width, void* stream);
 
+/* Test instrumentation: ONE call of the forward neighbour aggregation of a message-passing step on a prepared graph
+ * (mpnhip_time_aggregate without its timing loop): src [E, dim] in SORTED edge order, out [N, 2 * dim] = [flow_in | flow_out],
+ * argmax (optional, int32, same geometry as out): for MAX the sorted position of the row chosen (first maximum, -1 for empty
+ * segments).  Reaches k_segment_reduce_block (E >= 48 * 2N, dim % 4 == 0, dim <= 256), else k_aggregate (dim % 4 == 0), else
+ * the scalar short-segment kernel. */
+int mpnhip_debug_aggregate(const void* graph_buf, int n_nodes, int64_t n_edges, const float* src, int dim, int agg, float* out,
+                           int32_t* argmax, void* stream);
+
+/* Test instrumentation: the three segmented sums of a backward step (the index_put_(accumulate) of the gathers x[flow_col],
+ * x[row], x[col]) as mpnhip_backward issues them.  One job sums, for every segment s < nseg, the rows
+ * src[list ? list[j] : j] (j in [ptr[s], ptr[s + 1]); with runs > 1 and no list: the union of the runs
+ * [ptr[s + r * run_stride], ptr[s + r * run_stride + 1]), r < runs) into out[(s % nmod) * ldo + (s / nmod == 0 ? off0 : off1)
+ * + 0 .. dim).  total_rows is the number of source rows the dispatch compares with 48 * nseg to choose between the
+ * block-per-segment and the short-segment kernels.  bf16_rows != 0: src holds bf16 rows (lds counts bf16 elements), always the
+ * short-segment kernel, and out16 (optional, leading dimension ldo16) receives the sums rounded to nearest-even bf16 as well;
+ * out16 / ldo16 are ignored for fp32 rows.  Arguments are checked on the host before any launch (MPNHIP_ERR_ARG): null jobs,
+ * negative nseg / dim, null src / ptr / out with nseg > 0 and dim > 0, runs > 1 together with a list, nmod <= 0 with nseg > 0. */
+typedef struct mpnhip_seg_job {
+    const void* src; int64_t lds; const int32_t* list; const int32_t* ptr; int nseg; int dim; float* out; int64_t ldo;
+    int nmod; int off0; int off1; int runs; int run_stride; uint16_t* out16; int64_t ldo16;
+} mpnhip_seg_job;
+int mpnhip_debug_segment_reduce3(const mpnhip_seg_job jobs[3], int64_t total_rows, int bf16_rows, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Graph preparation -- replaces the six boolean-mask indexings per step of
  * TimeAwareNodeModel.forward (models/mpn.py:85-87,91-93) and the implicit index structures behind
@@ -285,7 +308,9 @@ int mpnhip_weight_grad_bf16_rows(const uint16_t* dZ, const uint16_t* H, int64_t 
 
 /* The gradient of node_agg_fn (models/mpn.py:266-273; torch_scatter's scatter_add / scatter_mean / scatter_max backward), gather
  * form: grad_src[j] = grad_out[row[j]] (sum), / count[row[j]] (mean; count int32 [x_size]), or only where argmax[row[j]][d] == j
- * (max; `argmax` as mpnhip_segment_reduce returned it).  grad_out [x_size, dim], grad_src [M, dim]. */
+ * (max; `argmax` as mpnhip_segment_reduce returned it).  grad_out [x_size, dim], grad_src [M, dim].  A row[j] outside
+ * [0, x_size) contributed nothing to the forward (mpnhip_segment_reduce parks it behind the last segment): its grad_src row
+ * is written as 0 and grad_out / count / argmax are not read for it. */
 int mpnhip_segment_reduce_backward(const float* grad_out, const int64_t* row, const int32_t* argmax, const int32_t* count, int64_t m,
                                    int dim, int x_size, int agg, float* grad_src, void* stream);
 

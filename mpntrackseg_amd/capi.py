@@ -58,6 +58,15 @@ class LinearBf16Args(C.Structure):
     ]
 
 
+class SegJob(C.Structure):
+    """``mpnhip_seg_job`` (include/mpnhip.h): one segmented sum of ``mpnhip_debug_segment_reduce3``."""
+    _fields_ = [
+        ("src", C.c_void_p), ("lds", C.c_int64), ("list", C.c_void_p), ("ptr", C.c_void_p), ("nseg", C.c_int), ("dim", C.c_int),
+        ("out", C.c_void_p), ("ldo", C.c_int64), ("nmod", C.c_int), ("off0", C.c_int), ("off1", C.c_int), ("runs", C.c_int),
+        ("run_stride", C.c_int), ("out16", C.c_void_p), ("ldo16", C.c_int64),
+    ]
+
+
 # name -> (restype, argtypes); mirrors include/mpnhip.h one to one (tests/test_capi_symbols.py
 # checks that every function the header declares is listed here and exported by the library)
 _P, _I, _L, _Z = C.c_void_p, C.c_int, C.c_int64, C.c_size_t
@@ -68,6 +77,8 @@ SIGNATURES = {
     "mpnhip_debug_counter_name": (C.c_char_p, [_I]),
     "mpnhip_debug_saved": (_I, [C.POINTER(Model), _P, _I, _L, _P, _Z, _I, _I, _I, _P, C.POINTER(C.c_int64), C.POINTER(C.c_int), _P]),
     "mpnhip_debug_backward_saved": (_I, [C.POINTER(Model), _I, _L, _P, _Z, _I, _I, _I, _P, C.POINTER(C.c_int64), C.POINTER(C.c_int), _P]),
+    "mpnhip_debug_aggregate": (_I, [_P, _I, _L, _P, _I, _I, _P, _P, _P]),
+    "mpnhip_debug_segment_reduce3": (_I, [C.POINTER(SegJob), _L, _I, _P]),
     "mpnhip_graph_bytes": (_Z, [_I, _L]),
     "mpnhip_graph_prep_workspace_bytes": (_Z, [_I, _L]),
     "mpnhip_graph_prep": (_I, [_P, _I, _L, _P, _Z, _P, _Z, _P]),

@@ -225,12 +225,14 @@ namespace mpnhip {
 namespace {
 __global__ __launch_bounds__(256) void k_segment_reduce_bwd(const float* __restrict__ dout, const int64_t* __restrict__ row,
                                                             const int32_t* __restrict__ argmax, const int32_t* __restrict__ count,
-                                                            int64_t m, int dim, int agg, float* __restrict__ dsrc) {
+                                                            int64_t m, int dim, int x_size, int agg, float* __restrict__ dsrc) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= m * dim) return;
     const int64_t j = i / dim;
     const int d = (int)(i - j * dim);
     const int64_t r = row[j];
+    // a row outside [0, x_size) was parked behind the last segment by the forward (k_row_keys) and read by nobody: zero gradient
+    if (r < 0 || r >= x_size) { dsrc[i] = 0.f; return; }
     float g = dout[r * dim + d];
     if (agg == MPNHIP_AGG_MEAN) { const int c = count[r]; g /= (float)(c > 0 ? c : 1); }
     else if (agg == MPNHIP_AGG_MAX) g = argmax[r * dim + d] == (int32_t)j ? g : 0.f;
@@ -249,7 +251,7 @@ extern "C" int mpnhip_segment_reduce_backward(const float* grad_out, const int64
     MPN_CHECK_ARG(agg != MPNHIP_AGG_MAX || argmax, "segment_reduce_backward: max needs the forward's argmax");
     MPN_CHECK_ARG(agg != MPNHIP_AGG_MEAN || count, "segment_reduce_backward: mean needs the segment counts");
     hipLaunchKernelGGL(k_segment_reduce_bwd, dim3((unsigned)((m * dim + 255) / 256)), dim3(256), 0, s, grad_out, row, argmax, count, m,
-                       dim, agg, grad_src);
+                       dim, x_size, agg, grad_src);
     MPN_LAUNCH_CHECK();
     return MPNHIP_OK;
 }

@@ -808,3 +808,38 @@ extern "C" int mpnhip_time_aggregate(const void* graph_buf, int n_nodes, int64_t
     (void)hipEventDestroy(t1);
     return MPNHIP_OK;
 }
+
+// ---- test instrumentation: the internal dispatchers behind the C ABI, one call each --------------------------------------
+extern "C" int mpnhip_debug_aggregate(const void* graph_buf, int n_nodes, int64_t n_edges, const float* src, int dim, int agg,
+                                      float* out, int32_t* argmax, void* stream_) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    MPN_CHECK_ARG(n_nodes >= 0 && n_edges >= 0 && dim >= 1, "debug_aggregate: bad sizes");
+    MPN_CHECK_ARG(agg >= 0 && agg <= 2, "debug_aggregate: unknown aggregation %d", agg);
+    MPN_CHECK_ARG(graph_buf, "debug_aggregate: null graph");
+    if (n_nodes == 0) return MPNHIP_OK;
+    MPN_CHECK_ARG(out && (src || n_edges == 0), "debug_aggregate: null pointer");
+    GraphView g;
+    graph_layout(n_nodes, n_edges, &g, const_cast<void*>(graph_buf));
+    return aggregate(g, src, dim, agg, out, argmax, stream);
+}
+
+static_assert(sizeof(mpnhip_seg_job) == sizeof(SegReduce2), "mpnhip_seg_job mirrors SegReduce2");
+
+extern "C" int mpnhip_debug_segment_reduce3(const mpnhip_seg_job jobs[3], int64_t total_rows, int bf16_rows, void* stream_) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    MPN_CHECK_ARG(jobs, "debug_segment_reduce3: null jobs");
+    MPN_CHECK_ARG(total_rows >= 0, "debug_segment_reduce3: negative total_rows");
+    SegReduce2 c[3];
+    for (int i = 0; i < 3; ++i) {
+        const mpnhip_seg_job& j = jobs[i];
+        MPN_CHECK_ARG(j.nseg >= 0 && j.dim >= 0, "debug_segment_reduce3: job %d: negative nseg / dim", i);
+        const bool work = j.nseg > 0 && j.dim > 0;
+        MPN_CHECK_ARG(!work || (j.src && j.ptr && j.out), "debug_segment_reduce3: job %d: null src / ptr / out", i);
+        MPN_CHECK_ARG(!(j.runs > 1 && j.list), "debug_segment_reduce3: job %d: runs > 1 takes no list", i);
+        MPN_CHECK_ARG(j.nseg == 0 || j.nmod > 0, "debug_segment_reduce3: job %d: nmod must be positive", i);
+        MPN_CHECK_ARG(j.runs <= 1 || j.run_stride >= 0, "debug_segment_reduce3: job %d: negative run_stride", i);
+        c[i] = {static_cast<const float*>(j.src), j.lds, j.list, j.ptr, j.nseg, j.dim, j.out, j.ldo, j.nmod, j.off0, j.off1,
+                j.runs, j.run_stride, bf16_rows ? j.out16 : nullptr, bf16_rows ? j.ldo16 : 0};
+    }
+    return bf16_rows ? segment_reduce_csr2_x3_bf16(c, stream) : segment_reduce_csr2_x3(c, total_rows, stream);
+}

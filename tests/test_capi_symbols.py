@@ -59,6 +59,21 @@ def test_linear_bf16_args_layout_matches_c():
     assert capi.LinearBf16Args.m.offset == 120 and capi.LinearBf16Args.n.offset == 128 and capi.LinearBf16Args.accumulate.offset == 152
 
 
+def test_seg_job_layout_matches_c():
+    # mpnhip_seg_job: 4 pointers / int64, 2 ints, pointer, int64, 5 ints (+ 4 bytes of padding), pointer, int64
+    J = capi.SegJob
+    assert ctypes.sizeof(J) == 4 * 8 + 2 * 4 + 2 * 8 + 5 * 4 + 4 + 2 * 8 == 96
+    offsets = dict(src=0, lds=8, list=16, ptr=24, nseg=32, dim=36, out=40, ldo=48, nmod=56, off0=60, off1=64, runs=68,
+                   run_stride=72, out16=80, ldo16=88)
+    assert [f[0] for f in J._fields_] == list(offsets)
+    for name, off in offsets.items():
+        assert getattr(J, name).offset == off, name
+    # the header declares the fields in the same order
+    src = open(os.path.join(REPO, "include", "mpnhip.h")).read()
+    body = re.search(r"typedef struct mpnhip_seg_job \{(.*?)\} mpnhip_seg_job;", src, flags=re.S).group(1)
+    assert re.findall(r"(\w+);", body) == list(offsets)
+
+
 def test_precision_codes_match_header():
     src = open(os.path.join(REPO, "include", "mpnhip.h")).read()
     codes = {m.group(1).lower(): int(m.group(2)) for m in re.finditer(r"#define MPNHIP_PREC_([A-Z0-9_]+) (\d+)", src)}
@@ -127,3 +142,45 @@ def test_attention_and_avgpool_argument_checks_without_gpu():
     assert l.mpnhip_avgpool(p, -1, 4, p, None) != 0
     assert l.mpnhip_avgpool(None, 0, 4, None, None) == 0
     assert l.mpnhip_avgpool(None, 4, 4, p, None) != 0
+
+
+def test_segment_debug_entries_argument_checks_without_gpu():
+    """mpnhip_debug_aggregate and mpnhip_debug_segment_reduce3 check their arguments on the host: everything below returns
+    before a kernel is launched (the non-null pointers are host dummies that are never dereferenced)."""
+    l = capi.load()
+    dummy = ctypes.create_string_buffer(256)
+    p = ctypes.cast(dummy, ctypes.c_void_p)
+    # aggregate: null graph, bad sizes, unknown aggregation, null pointers with nodes; no nodes is a no-op
+    assert l.mpnhip_debug_aggregate(None, 3, 5, p, 8, 0, p, None, None) != 0
+    assert b"debug_aggregate" in l.mpnhip_last_error()
+    assert l.mpnhip_debug_aggregate(p, -1, 5, p, 8, 0, p, None, None) != 0
+    assert l.mpnhip_debug_aggregate(p, 3, 5, p, 0, 0, p, None, None) != 0
+    assert l.mpnhip_debug_aggregate(p, 3, 5, p, 8, 3, p, None, None) != 0
+    assert l.mpnhip_debug_aggregate(p, 3, 5, None, 8, 0, p, None, None) != 0
+    assert l.mpnhip_debug_aggregate(p, 3, 5, p, 8, 0, None, None, None) != 0
+    assert l.mpnhip_debug_aggregate(p, 0, 0, None, 8, 0, None, None, None) == 0
+
+    def jobs(**kw):
+        arr = (capi.SegJob * 3)()
+        for j in arr:
+            j.src, j.ptr, j.out, j.lds, j.ldo, j.nseg, j.dim, j.nmod = p.value, p.value, p.value, 8, 8, 4, 8, 4
+        for k, v in kw.items():
+            setattr(arr[1], k, v)
+        return arr
+    for fp16 in (0, 1):
+        assert l.mpnhip_debug_segment_reduce3(None, 10, fp16, None) != 0
+        assert b"null jobs" in l.mpnhip_last_error()
+        for bad in (dict(nseg=-1), dict(dim=-4), dict(src=None), dict(ptr=None), dict(out=None), dict(runs=3, list=p.value),
+                    dict(nmod=0), dict(nmod=-2)):
+            assert l.mpnhip_debug_segment_reduce3(jobs(**bad), 10, fp16, None) == -1, bad
+            assert b"debug_segment_reduce3: job 1" in l.mpnhip_last_error(), bad
+    assert l.mpnhip_debug_segment_reduce3(jobs(), -1, 0, None) == -1
+    # nothing to do: three empty jobs, null pointers allowed
+    empty = jobs()
+    for j in empty:
+        j.src, j.ptr, j.out, j.nseg, j.nmod = None, None, None, 0, 0
+    assert l.mpnhip_debug_segment_reduce3(empty, 0, 0, None) == 0
+    assert l.mpnhip_debug_segment_reduce3(empty, 0, 1, None) == 0
+    # bf16 rows: a width that is no multiple of 4 is refused by the alignment check, before any launch
+    assert l.mpnhip_debug_segment_reduce3(jobs(dim=82), 10, 1, None) == -1
+    assert b"alignment" in l.mpnhip_last_error()

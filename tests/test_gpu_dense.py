@@ -213,8 +213,10 @@ def test_g11_cfgB_sum_o1_against_reference_autograd(golden, precision):
 # ------------------------------------------------------------------------------------ long-segment kernels in isolation
 @pytest.mark.parametrize("agg", ["sum", "mean", "max"])
 def test_block_per_segment_aggregation_matches_sequential_order_oracle(agg):
-    """node_agg_fn over long segments (the block-per-segment kernel with its fixed LDS tree) against the oracle's sequential
-    scatter; max must be exact (and its ties at 0 resolve to the earliest edge like the sequential scan)."""
+    """node_agg_fn over long segments (200 rows on average) against the oracle's sequential scatter.  NodeAggFn goes through
+    mpnhip_segment_reduce, which always launches the SHORT-segment kernel (k_segment_reduce, sequential order) however long the
+    segments are; the block-per-segment kernel and its LDS tree are covered by tests/test_gpu_segment.py.  max must be exact
+    (and its ties at 0 resolve to the earliest edge like the sequential scan)."""
     from mpntrackseg_amd.mpn import NodeAggFn
     m, dim, x_size = 20000, 32, 100
     src = np.maximum(synth.normal(4, (m, dim), stream=1), 0)
@@ -229,4 +231,4 @@ def test_block_per_segment_aggregation_matches_sequential_order_oracle(agg):
     else:
         assert nerr(out, ref) < 2e-6
     assert (out[7] == 0).all()
-    print(counts)
+    assert counts["segment_reduce"] == 1 and counts["segment_reduce_block"] == 0 and counts["aggregate_block"] == 0, counts
