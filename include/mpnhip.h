@@ -550,6 +550,39 @@ int mpnhip_track_lengths(const int64_t* labels, int64_t n_nodes, int64_t min_tra
                          void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * From RoI masks to MOTS run-length masks: MPNTracker._to_full_masks (tracker/mpn_tracker.py:267-298) =
+ * torchvision's paste_masks_in_image(padding = 1), ensure_unique_masks (utils/mots.py:5-25), >= mask_threshold and the run
+ * boundaries of COCO's RLE.  One launch covers n_frames frames of one image size (img_h * img_w < 2^31, at most 65535 frames);
+ * its detections are a list of n_dets entries grouped by frame: frame_ptr [n_frames + 1] (device int32, ascending, frame f owns
+ * the entries [frame_ptr[f], frame_ptr[f + 1])), det_ids [n_dets] (device int32; NULL = identity) = row of masks [n_rows, mh, mw]
+ * (float32) and boxes [n_rows, 4] (float64: left, top, right, bottom) of every entry.  An entry whose row leaves [0, n_rows) or
+ * whose box is not finite pastes nothing; expanded coordinates are clamped to +-2^29.  Unfused IEEE arithmetic in a fixed order,
+ * integer counts, a stable sort: the same bits on every call (tests/full_masks_ref.py restates them in numpy).
+ * ------------------------------------------------------------------------------------------- */
+/* Bytes that any of the three calls below needs for these sizes (hw = img_h * img_w; n_events = 0 while it is not known: enough
+ * for mpnhip_paste_unique_masks and mpnhip_mask_run_events_count).  0 for sizes the calls refuse. */
+size_t mpnhip_full_masks_workspace_bytes(int64_t n_dets, int64_t n_frames, int64_t hw, int64_t n_events);
+/* labels [n_frames, img_w, img_h] (int32, column-major images: position p = x * img_h + y): the list entry that owns the pixel, or
+ * -1.  Per pixel the entries of the frame are walked in list order; an entry's value is the bilinear sample (align_corners =
+ * False, no antialiasing) of its zero-padded mask resized to its expanded box, 0 outside the box; an entry replaces the winner
+ * iff its value is greater, or is NaN while the winner's is not (np.argmax); the label is the winner if its value >=
+ * mask_threshold (> 0; NaN compares false).  values (NULL: skip), same shape, float32: the winner's value. */
+int mpnhip_paste_unique_masks(const float* masks, int64_t n_rows, int mh, int mw, const double* boxes, const int32_t* det_ids,
+                              int64_t n_dets, const int32_t* frame_ptr, int64_t n_frames, int img_h, int img_w, float mask_threshold,
+                              int32_t* labels, float* values, void* workspace, size_t workspace_bytes, void* stream);
+/* The run boundaries of every entry's mask (labels == entry) in two calls, because the caller allocates the result.  Position p
+ * of a frame is an event of entry d when exactly one of labels[p - 1], labels[p] is d (labels[-1] = -1; a run continues across
+ * column ends; nothing at p = hw; labels outside [0, n_dets) count as -1).
+ *   count: det_counts [n_dets] (device int32) = events per entry, n_events (device int32) = their sum.
+ *   fill:  event_pos [n_events] (int32) = the positions, sorted by (entry, position): entry d owns the det_counts[d] positions
+ *          after those of the entries before it.  n_events is the count's.  COCO's counts for d are the differences of
+ *          (0, its positions ..., hw). */
+int mpnhip_mask_run_events_count(const int32_t* labels, int64_t n_frames, int64_t hw, int64_t n_dets, int32_t* det_counts,
+                                 int32_t* n_events, void* workspace, size_t workspace_bytes, void* stream);
+int mpnhip_mask_run_events(const int32_t* labels, int64_t n_frames, int64_t hw, int64_t n_dets, int64_t n_events, int32_t* event_pos,
+                           void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Measurement helpers used by bench.py (HIP events on the launch stream; these synchronise).
  * ------------------------------------------------------------------------------------------- */
 /* In-stream kernel timing of the real hot path: while enabled, mpnhip_forward brackets (a) the first-layer

@@ -157,6 +157,10 @@ SIGNATURES = {
     "mpnhip_connected_components_workspace_bytes": (_Z, [_L]),
     "mpnhip_connected_components": (_I, [_P, _L, _L, _P, _P, _P, _P, _Z, _P]),
     "mpnhip_track_lengths": (_I, [_P, _L, _L, _P, _P, _P]),
+    "mpnhip_full_masks_workspace_bytes": (_Z, [_L, _L, _L, _L]),
+    "mpnhip_paste_unique_masks": (_I, [_P, _L, _I, _I, _P, _P, _L, _P, _L, _I, _I, C.c_float, _P, _P, _P, _Z, _P]),
+    "mpnhip_mask_run_events_count": (_I, [_P, _L, _L, _L, _P, _P, _P, _Z, _P]),
+    "mpnhip_mask_run_events": (_I, [_P, _L, _L, _L, _L, _P, _P, _Z, _P]),
     "mpnhip_profile_enable": (_I, [_I]),
     "mpnhip_edge_chain_active": (_I, [C.POINTER(Model)]),
     "mpnhip_profile_read": (_I, [C.POINTER(C.c_float), C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(C.c_int),

@@ -20,7 +20,14 @@ device.  ``evaluate_graph_in_batches`` stays the directed edge scores alone.
 (``_project_graph_model_output``, ``projectors.py`` here: greedy rounding on the device, or the exact rounding whose linear
 program runs on the host), ``assign_ped_ids`` (``_assign_ped_ids``, ``:231-248``: connected components of the rounded graph, a
 lock-free union-find in ``csrc/projection.hip``) and ``drop_short_trajectories`` (``tracker/postprocessing.py:14-18``) --
-detections in, track ids out.  Mask pasting, RLE encoding and the data-frame / text output stay in the reference."""
+detections in, track ids out.
+
+``to_full_masks`` and ``save_results_to_file`` are the last two steps (``_to_full_masks``, ``:267-298``, and ``save_results_to_file``,
+``:398-417``): the RoI masks of the surviving detections are pasted into their frames, made disjoint and thresholded on the device
+(``masks.py``, ``csrc/full_masks.hip``: one label per pixel instead of one image per detection), leave it as run boundaries and
+become COCO run-length strings on the host; the text file has the MOTS challenge's rows.  ``mots_sequence`` is ``track_sequence``
+followed by ``to_full_masks``: detections in, MOTS rows out.  What stays in the reference needs a second network or files of its
+detector (``_predict_nan_masks``, ``_add_tracktor_detects``), or is commented out there (the trajectory interpolation)."""
 import collections
 import types
 
@@ -286,3 +293,76 @@ def track_sequence(model, x, edge_index, edge_attr, reid_emb_dists, frame_num_pe
     ped_ids = assign_ped_ids(seq.edge_index, rounded, N)
     keep = drop_short_trajectories(ped_ids, min_track_len)
     return TrackResult(ped_ids, keep, seq.edge_index, rounded, seq.node_preds, rate, seq.final_edge_preds)
+
+
+@capi.on_tensor_device
+def to_full_masks(node_preds, boxes, frame_num_per_node, keep, img_shape, mask_threshold=0.5, frames_per_launch=8):
+    """``MPNTracker._to_full_masks`` (mpn_tracker.py:267-298): an object array [N] with the COCO run-length string of every kept
+    detection's full-frame mask (``None`` for the dropped ones).  Per frame: ``paste_masks_in_image`` of the kept detections' RoI
+    masks in node order, ``ensure_unique_masks``, ``>= mask_threshold``, ``rletools.encode`` -- see ``masks.py``.
+
+    ``node_preds`` [N, 1, mh, mw] (device), ``boxes`` [N, 4] (left, top, right, bottom), ``frame_num_per_node`` [N], ``keep`` [N]
+    bool, ``img_shape`` = (H, W).  The kept detections are grouped by frame with a stable sort (the identity for frame-ordered
+    nodes) and ``frames_per_launch`` frames share a launch: the label workspace is 4 B x H x W x frames_per_launch, and the result
+    does not depend on it.  Host reads: ``keep`` once, then per launch the number of run boundaries and the boundaries."""
+    from . import masks as M
+    capi.require_device(node_preds)
+    N = int(node_preds.shape[0])
+    H, W = int(img_shape[0]), int(img_shape[1])
+    as_np = lambda v: np.asarray(v.detach().cpu() if isinstance(v, torch.Tensor) else v).reshape(-1)
+    keep_h, frame_h = as_np(keep).astype(bool), as_np(frame_num_per_node)
+    if keep_h.size != N or frame_h.size != N or len(boxes) != N:
+        raise MpnhipError("one box, frame number and keep flag per detection (%d detections)" % N)
+    out = np.full(N, None, dtype=object)
+    kept = np.flatnonzero(keep_h)
+    kept = kept[np.argsort(frame_h[kept], kind="stable")]
+    if kept.size == 0:
+        return out
+    _, first, per_frame = np.unique(frame_h[kept], return_index=True, return_counts=True)
+    step = max(int(frames_per_launch), 1)
+    for g0 in range(0, first.size, step):
+        cnt = per_frame[g0:g0 + step]
+        ids = kept[first[g0]:first[g0] + int(cnt.sum())]
+        frame_ptr = np.concatenate(([0], np.cumsum(cnt)))
+        labels = M.paste_unique_masks(node_preds, boxes, frame_ptr, (H, W), mask_threshold, det_ids=ids)
+        pos, counts = M.mask_run_events(labels, ids.size)
+        ends = np.cumsum(counts)
+        for j, node in enumerate(ids):
+            out[node] = M.rle_string(M.rle_counts_from_events(pos[ends[j] - counts[j]:ends[j]], H * W))
+    return out
+
+
+def save_results_to_file(path, frame, ped_ids, label, img_shape, rles, keep):
+    """``MPNTracker.save_results_to_file`` (mpn_tracker.py:398-417) without its date-stamped second copy: one row
+    ``frame id label img_height img_width rle`` per kept detection, space-separated, no header, sorted by (frame, id), where
+    id = ped_id + label * 1000 + 1 (the MOTS id format).  ``label`` is one class id or one per detection; returns the rows."""
+    as_np = lambda v: np.asarray(v.detach().cpu() if isinstance(v, torch.Tensor) else v)
+    frame, ped = as_np(frame).reshape(-1).astype(np.int64), as_np(ped_ids).reshape(-1).astype(np.int64)
+    keep = as_np(keep).reshape(-1).astype(bool)
+    lab = np.broadcast_to(as_np(label).astype(np.int64).reshape(-1), ped.shape) if np.ndim(as_np(label)) else np.full(ped.shape, int(label), np.int64)
+    if not (frame.size == ped.size == keep.size == len(rles)):
+        raise MpnhipError("one frame, id, keep flag and run-length string per detection")
+    ids = ped + lab * 1000 + 1
+    sel = np.flatnonzero(keep)
+    sel = sel[np.lexsort((ids[sel], frame[sel]))]
+    rows = []
+    for i in sel:
+        if rles[i] is None:
+            raise MpnhipError("detection %d is kept but has no mask" % int(i))
+        rows.append("%d %d %d %d %d %s" % (frame[i], ids[i], lab[i], int(img_shape[0]), int(img_shape[1]), rles[i]))
+    with open(path, "w") as fh:
+        fh.write("".join(r + "\n" for r in rows))
+    return rows
+
+
+@capi.on_tensor_device
+def mots_sequence(model, x, edge_index, edge_attr, reid_emb_dists, frame_num_per_node, frames_per_graph, top_k_nns, x_ext, boxes,
+                  img_shape, mask_threshold=0.5, frames_per_launch=8, **track_args):
+    """``track_sequence`` (``track_args``: its remaining keyword arguments), then ``to_full_masks``: ``(TrackResult, rles)``."""
+    res = track_sequence(model, x, edge_index, edge_attr, reid_emb_dists, frame_num_per_node, frames_per_graph, top_k_nns, x_ext=x_ext,
+                         **track_args)
+    if res.node_preds is None:
+        raise MpnhipError("mots_sequence needs the mask branch: a model with one and the RoI features x_ext")
+    rles = to_full_masks(res.node_preds, boxes, frame_num_per_node, res.keep, img_shape, mask_threshold=mask_threshold,
+                         frames_per_launch=frames_per_launch)
+    return res, rles

@@ -39,6 +39,10 @@ Fixtures:
   g19_projection.npz           GreedyProjector.project, MPNTracker._assign_ped_ids and Postprocessor.drop_short_trajectories (min_track_len
                                2 and 5) on three 48-node score graphs (one with tied scores), a 650-node graph with a hub of > 256 active
                                edges on each side, and the pruned undirected outputs of g17.  Only with --only g19.
+  g20_full_masks.npz           MPNTracker._to_full_masks on 3 frames of at most 6 RoI masks (56 x 56, image 96 x 128): the binary masks of
+                               the reference's ensure_unique_masks over the literal paste (tests/full_masks_ref.py literal_paste: torch's
+                               own CPU resize), bit-packed, their COCO strings, and the sample line of the MOTS evaluation kit's README.
+                               Only with --only g20.
 
 Usage:  python tools/make_golden.py [--only g1,g2,...]
 """
@@ -1080,6 +1084,54 @@ def gen_g14():
     np.savez_compressed(os.path.join(GOLD, "g14_construct_graph.npz"), **rec)
 
 
+def gen_g20():
+    """The tail of MPNTracker._to_full_masks (tracker/mpn_tracker.py:284-297) per frame: paste_masks_in_image as
+    tests/full_masks_ref.py restates it literally (torchvision is not installed; the resize is torch's own F.interpolate on the
+    CPU), then the reference's OWN ensure_unique_masks (utils/mots.py:5-25) and the threshold of 0.5.  pycocotools is not installed
+    either: the strings are the restated codec's, which the sample line of the MOTS evaluation kit's README (stored with its
+    height and width) pins -- it decodes to counts that sum to height x width and encodes back to the same characters."""
+    _import_tracking_stack()
+    from mot_neural_solver.utils.mots import ensure_unique_masks
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    import full_masks_ref as R
+    rng = np.random.default_rng(20)
+    H, W, thr = 96, 128, 0.5
+    per_frame = [6, 1, 4]
+    n = sum(per_frame)
+    masks = R.blob_masks(rng, n)
+    boxes = R.random_boxes(rng, n, H, W, lo=10.0, hi=90.0)
+    boxes[0] = (20.25, 10.5, 70.75, 80.0)           # two large overlapping boxes in the first frame
+    boxes[1] = (40.0, 25.0, 110.5, 95.75)
+    frame_ptr = np.concatenate(([0], np.cumsum(per_frame))).astype(np.int32)
+    bits, strings, shapes = [], [], []
+    for f in range(len(per_frame)):
+        a, b = int(frame_ptr[f]), int(frame_ptr[f + 1])
+        frame_masks = R.literal_paste(masks[a:b], boxes[a:b], H, W)
+        frame_masks = ensure_unique_masks(frame_masks)
+        frame_masks = np.where(frame_masks >= thr, 1, 0).astype(np.uint8)
+        assert frame_masks.sum(axis=0).max() <= 1
+        for m in frame_masks:
+            counts = R.np_rle_counts(m)
+            assert sum(counts) == H * W
+            strings.append(R.np_rle_string(counts))
+            assert R.np_rle_from_string(strings[-1]) == counts
+        bits.append(np.packbits(frame_masks.reshape(-1)))
+        shapes.append(frame_masks.shape[0])
+    readme = open("/root/reference/MOTChallengeEvalKit/src/MOTChallengeEvalKit/MOTS/README.md").read().splitlines()[66].split()
+    assert len(readme) == 6 and readme[1] == "1005"
+    sample, sh, sw = readme[5], int(readme[3]), int(readme[4])
+    sample_counts = R.np_rle_from_string(sample)
+    assert sum(sample_counts) == sh * sw and min(sample_counts) >= 0 and R.np_rle_string(sample_counts) == sample
+    rec = {"masks": masks, "boxes": boxes, "frame_ptr": frame_ptr, "img_shape": np.array([H, W], np.int64),
+           "mask_threshold": np.float32(thr), "binary_bits": np.concatenate(bits), "rle": np.array(strings),
+           "sample_rle": np.array(sample), "sample_shape": np.array([sh, sw], np.int64)}
+    covered = int(np.unpackbits(rec["binary_bits"]).sum())
+    print("g20: masks per frame", shapes, "set pixels", covered, "string lengths", [len(s) for s in strings], "sample counts",
+          len(sample_counts))
+    assert covered > 2000 and min(len(s) for s in strings) >= 1
+    np.savez_compressed(os.path.join(GOLD, "g20_full_masks.npz"), **rec)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", default="g0,g1,g4,g5,g6,g7,g8,g2,g3,g11,g12,g10,g9")
@@ -1108,6 +1160,7 @@ def main():
     if "g17" in only: gen_g17()
     if "g18" in only: gen_g18(mpn)
     if "g19" in only: gen_g19()
+    if "g20" in only: gen_g20()
 
 
 if __name__ == "__main__":
