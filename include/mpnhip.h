@@ -371,6 +371,37 @@ int mpnhip_tracking_loss_graphs(const float* logits, const float* labels, const 
 int mpnhip_step_metrics(const void* graph_buf, int n_nodes, int64_t n_edges, const float* logits, const float* labels,
                         int32_t* counts, void* stream);
 
+/* MOTGraph.assign_edge_labels (data/mot_graph.py:223-262): labels [E] float32 in {0, 1} from edge_index (int64 [2, E]) and the
+ * track id of every node (ids, int64 [N]; -1 = no track).  same_id = ids[row] == ids[col] && ids[row] != -1.
+ *   MPNHIP_LABELS_ALL:      label = same_id;
+ *   MPNHIP_LABELS_CLOSEST:  label = same_id && (col is the smallest col > row, or the largest col < row, over the same-id EDGES of
+ *                           that row) -- what the reference's scatter_min over |row - col| selects; stored duplicates of the active
+ *                           edge are all labelled, a self loop never is.
+ * Integer atomics only: the same bits on every call.  An endpoint outside [0, N) is never used as an index: its edge gets label 0
+ * and *status (one device int32, overwritten) becomes non-zero -- the reference's gather raises IndexError there.
+ * workspace: 2 N ints ('closest' only).  Nothing is read back; n_edges == 0 is a successful no-op. */
+#define MPNHIP_LABELS_ALL 0
+#define MPNHIP_LABELS_CLOSEST 1
+size_t mpnhip_edge_labels_workspace_bytes(int64_t n_nodes);
+int mpnhip_edge_labels(const int64_t* edge_index, int64_t n_edges, const int64_t* ids, int64_t n_nodes, int mode, float* labels,
+                       int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Segmentation term of MOTNeuralSolver._compute_loss (pl_module/pl_module.py:108-118):
+ *   loss = weight * sum_s mean over the valid rows and their row_floats elements of BCEWithLogits(preds[s], labels).
+ * preds / grads: HOST arrays of n_steps device pointers (n_steps <= 16; the kernel takes them by value), each [N, row_floats]
+ * contiguous; labels [N, row_floats] (any float in [0, 1]); valid [N] bytes (non-zero = the row has a ground-truth mask).
+ * grads[s] is written in full: (sigmoid(z) - y) * weight / (n_valid * row_floats) on valid rows, 0 on the others.
+ * loss_out [1 + n_steps] (device): total, then per step.  No valid row: loss 0, gradients 0.
+ * node_graph (int32 [N], optional) with n_graphs (1 .. 1024): the rows belong to the graphs of one block-diagonal batch -- every
+ * graph its own mean over its own valid rows, a graph without one contributes nothing, the n_graphs losses averaged (as
+ * mpnhip_tracking_loss_graphs).  Without it n_graphs must be 1.
+ * All steps run in ONE launch; 16-byte accesses when every base pointer and row_floats allow them, 4-byte ones otherwise.
+ * Per-block partial sums are added in double in a fixed order: the loss is bitwise reproducible.  No host read. */
+size_t mpnhip_mask_loss_workspace_bytes(int n_steps, int64_t n_nodes, int64_t row_floats, int n_graphs);
+int mpnhip_mask_loss(const float* const* preds, int n_steps, const float* labels, const uint8_t* valid, const int32_t* node_graph,
+                     int n_graphs, int64_t n_nodes, int64_t row_floats, float weight, float* loss_out, float* const* grads,
+                     void* workspace, size_t workspace_bytes, void* stream);
+
 /* Mask branch: the neighbour aggregation of TimeAwareAttentionModel.forward
  * (models/mpn.py:117-134): per (node, direction) segment w = scatter_softmax(logits) and
  * out_dir[n] = sum_j w_j x[col_j], x [N, feat] with feat = C*H*W (64*14*14).  logits [E] in edge_index order (the

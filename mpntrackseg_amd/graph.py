@@ -162,6 +162,58 @@ def construct_graph(det_df, reid_embeddings, fps, max_frame_dist, edge_feats_to_
                 reid_emb_dists=torch.cat((emb_dists, emb_dists)))
 
 
+LABEL_MODES = {'all': 0, 'closest': 1}   # MPNHIP_LABELS_* (include/mpnhip.h); dataset_params['true_edge_labels']
+
+
+@capi.on_tensor_device
+def assign_edge_labels(edge_index, ids, mode='closest', validate=True):
+    """``MOTGraph.assign_edge_labels`` (data/mot_graph.py:223-262): float32 ``[E]`` on the device from ``edge_index`` (int64
+    [2, E]) and the track id of every node (``graph_df.id``: tensor, array or pandas column; -1 = no track).
+
+    ``'all'``: every edge between two detections of one track.  ``'closest'``: of those, per node only the edge to the nearest
+    later and the one to the nearest earlier detection that it HAS an edge to (the reference's ``scatter_min`` over
+    ``|row - col|``, taken over the edges that survived the kNN pruning).  Stored duplicates of an active edge are all
+    labelled; a self loop is labelled under ``'all'`` only.
+
+    ``validate=True`` reads one device flag and raises ``IndexError`` when an endpoint lies outside ``[0, len(ids))``, as the
+    reference's gather would; ``validate=False`` reads nothing back (such an edge gets label 0)."""
+    if mode not in LABEL_MODES:
+        raise MpnhipError("assign_edge_labels: unknown mode %r ('all' or 'closest')" % (mode,))
+    capi.require_device(edge_index)
+    if edge_index.dtype != torch.int64 or edge_index.dim() != 2 or edge_index.shape[0] != 2:
+        raise MpnhipError("edge_index must be int64 [2, E] (reference data/mot_graph.py:312)")
+    lib = capi.load()
+    dev = edge_index.device
+    ei = edge_index.contiguous()
+    if isinstance(ids, torch.Tensor):
+        node_ids = ids.to(device=dev, dtype=torch.int64).contiguous().view(-1)
+    else:
+        node_ids = _col({'id': ids}, 'id', torch.int64, dev).view(-1)
+    e, n = ei.shape[1], node_ids.numel()
+    labels = torch.empty(e, dtype=torch.float32, device=dev)
+    flag = torch.empty(1, dtype=torch.int32, device=dev)
+    ws = capi.workspace(lib.mpnhip_edge_labels_workspace_bytes(n), dev, "labels")
+    check(lib.mpnhip_edge_labels(ptr(ei), e, ptr(node_ids), n, LABEL_MODES[mode], ptr(labels), ptr(flag), ptr(ws), ws.numel(),
+                                 stream_ptr()), "mpnhip_edge_labels")
+    if validate and e and int(flag.item()) != 0:
+        raise IndexError("index out of range in edge_index: entries must lie in [0, %d) (reference mot_graph.py:230 gathers "
+                         "ids[edge_index])" % n)
+    return labels
+
+
+def assign_mask_labels(det_df, seq_info_dict, gt_dir=None):
+    """``MOTGraph.assign_mask_labels`` (data/mot_graph.py:264-281): the stored ground-truth RoI masks and the flags of the
+    detections that have one, selected on the device.  Returns ``(mask_labels [N, 1, H, W], mask_gt_ixs bool [N])``."""
+    import os.path as osp
+    from .embeddings import load_precomputed_embeddings
+    gt_dir = osp.join('gt', 'gt_mask') if gt_dir is None else gt_dir
+    mask_labels = load_precomputed_embeddings(det_df=det_df, seq_info_dict=seq_info_dict, embeddings_dir=osp.join(gt_dir, 'masks'),
+                                              embedding_dim='3D')
+    mask_gt_ixs = load_precomputed_embeddings(det_df=det_df, seq_info_dict=seq_info_dict,
+                                              embeddings_dir=osp.join(gt_dir, 'valid_ixs'))
+    return mask_labels, mask_gt_ixs.view(-1).bool()
+
+
 @capi.on_tensor_device
 def merge_undirected(edge_index, attrs=(), num_nodes=None):
     """Functional form of ``to_undirected_graph`` (utils/graph.py:176-186).  ``edge_index`` [2, E] lists every pair in both

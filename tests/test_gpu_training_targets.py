@@ -1,0 +1,246 @@
+"""csrc/train_targets.hip on the device against what the REFERENCE functions themselves produced
+(tests/golden/g21_training_targets.npz: MOTGraph.assign_edge_labels, MOTNeuralSolver._compute_loss with autograd): edge labels
+bit-equal, the segmentation loss with the bounds of tests/test_gpu_loss.py, ``loss.compute_loss`` under autograd, and the whole
+training loss end to end through g6's model (bounds of tests/test_gpu_mask_branch.py)."""
+import numpy as np
+import pytest
+import torch
+
+import training_targets_ref as R
+from mpntrackseg_amd import synth
+from mpntrackseg_amd.graph import assign_edge_labels
+from mpntrackseg_amd.loss import compute_loss, mask_loss_and_grad, tracking_loss
+from mpntrackseg_amd.mpn import MOTMPNet
+
+pytestmark = pytest.mark.gpu
+dev = lambda: torch.device("cuda:0")
+W = R.LOSS_WEIGHTS
+
+
+@pytest.fixture(scope="module")
+def z(golden):
+    return golden("g21_training_targets.npz")
+
+
+def on(a):
+    return torch.from_numpy(np.ascontiguousarray(a)).to(dev())
+
+
+# ------------------------------------------------------------------------------------------------ edge labels
+@pytest.mark.parametrize("mode", R.MODES)
+@pytest.mark.parametrize("tag", R.LABEL_CASES)
+def test_edge_labels_equal_the_reference_bit_for_bit(z, tag, mode):
+    ei, ids = on(z[f"lab:{tag}:edge_index"]), on(z[f"lab:{tag}:ids"])
+    got = assign_edge_labels(ei, ids, mode=mode)
+    assert got.dtype == torch.float32 and got.is_cuda and got.shape == (ei.shape[1],)
+    assert got.cpu().numpy().tobytes() == z[f"lab:{tag}:{mode}"].tobytes()
+    # the same bytes on a second call, and without the flag read; ids as the host column the reference holds
+    again = assign_edge_labels(ei, z[f"lab:{tag}:ids"], mode=mode, validate=False)
+    assert again.cpu().numpy().tobytes() == got.cpu().numpy().tobytes()
+
+
+@pytest.mark.parametrize("mode", R.MODES)
+def test_an_endpoint_out_of_range_raises_or_gets_label_zero(z, mode):
+    ei, ids = z["lab:base:edge_index"].copy(), z["lab:base:ids"]
+    want = R.edge_labels(ei, ids, mode)
+    hit = [int(np.nonzero(want == 1)[0][0]), 7, 399]
+    ei[0, hit[0]], ei[1, hit[1]], ei[0, hit[2]] = 48, -1, 2 ** 40
+    with pytest.raises(IndexError):
+        assign_edge_labels(on(ei), on(ids), mode=mode)
+    got = assign_edge_labels(on(ei), on(ids), mode=mode, validate=False).cpu().numpy()
+    assert got[hit].tolist() == [0, 0, 0]
+    # the other edges: the labels of the graph without those three edges
+    keep = np.ones(400, bool)
+    keep[hit] = False
+    assert np.array_equal(got[keep], R.edge_labels(ei[:, keep], ids, mode))
+
+
+# ------------------------------------------------------------------------------------------------ segmentation loss
+def check_mask_loss(z, tag, preds, mlab, valid, node_graph=None, n_graphs=1, pred_tensors=None):
+    ref_lv, _ = R.mask_loss(list(preds), mlab, valid, W["segmentation"], node_graph, n_graphs)
+    pt = pred_tensors if pred_tensors is not None else [on(p) for p in preds]   # separate allocations
+    ng = None if node_graph is None else on(node_graph)
+    lv, grads = mask_loss_and_grad(pt, on(mlab), on(valid), W["segmentation"], node_graph=ng, n_graphs=n_graphs)
+    lv2, _ = mask_loss_and_grad(pt, on(mlab), on(valid), W["segmentation"], node_graph=ng, n_graphs=n_graphs)
+    assert lv.cpu().numpy().tobytes() == lv2.cpu().numpy().tobytes()
+    got = lv.cpu().numpy()
+    assert got.shape == (1 + len(preds),)
+    for i in range(1 + len(preds)):
+        print(tag, "loss", i, got[i], ref_lv[i])
+        assert abs(got[i] - ref_lv[i]) <= 1e-5 * max(1.0, abs(ref_lv[i]))
+    rows = R.sample_rows(valid)
+    inv = ~np.asarray(valid, bool)
+    for s, g in enumerate(grads):
+        g = g.cpu().numpy()
+        assert g.shape == preds[s].shape
+        want = z[f"{tag}:gmask_rows"][s]
+        tol = 1e-6 * max(1.0, float(np.abs(want).max()))
+        assert np.abs(g[rows] - want).max() <= tol
+        assert not g[inv].any()   # exactly zero where the reference leaves no gradient
+        # whole-tensor figures (every row, not only the sampled ones): each element is within a few float32 roundings of the
+        # reference's (sigmoid, one subtraction, one scale: < 1e-6 of the largest), so a norm or a row sum is within 1e-5
+        g64 = g.astype(np.float64)
+        nrm = float(z[f"{tag}:gmask_norm"][s])
+        assert abs(np.sqrt((g64 ** 2).sum()) - nrm) <= 1e-5 * max(nrm, 1e-30)
+        rs = np.abs(g64).reshape(g.shape[0], -1).sum(axis=1)
+        assert np.abs(rs - z[f"{tag}:gmask_row_abssum"][s]).max() <= 1e-5 * max(float(z[f"{tag}:gmask_row_abssum"][s].max()), 1e-30)
+    return lv, grads
+
+
+@pytest.mark.parametrize("tag", sorted(R.LOSS_CASES))
+def test_mask_loss_against_the_reference(z, tag):
+    logits, labels, preds, mlab, valid = R.loss_inputs(tag)
+    lv, _ = check_mask_loss(z, tag, preds, mlab, valid)
+    # with the tracking term: the reference's total
+    track = tracking_loss([on(logits[s]).view(-1, 1) for s in range(logits.shape[0])], on(labels), weight=W["tracking"])
+    ref = float(z[f"{tag}:loss"])
+    assert abs(float(track) + float(lv[0]) - ref) <= 1e-5 * max(1.0, abs(ref))
+    if int(valid.sum()) == 0:
+        assert float(lv[0]) == 0.0
+
+
+def test_mask_loss_on_a_misaligned_slice(z):
+    """The 3 x 5 rows (no multiple of 16 bytes) out of ONE larger tensor, starting 4 bytes into it: the scalar path on views;
+    and 56 x 56 rows at such an offset, where only the base keeps the vector path away."""
+    logits, labels, preds, mlab, valid = R.loss_inputs("scalar")
+    k, n = preds.shape[:2]
+    stride = n * 15 + 1   # (136 floats: every view starts 4 bytes past a 16-byte boundary)
+    big = torch.zeros(1 + k * stride, dtype=torch.float32, device=dev())
+    views = [big[1 + s * stride:1 + s * stride + n * 15].view(n, 1, 3, 5) for s in range(k)]
+    for s in range(k):
+        views[s].copy_(on(preds[s]))
+    assert all(v.data_ptr() % 16 == 4 for v in views) and all(v.is_contiguous() for v in views)
+    check_mask_loss(z, "scalar", preds, mlab, valid, pred_tensors=views)
+    logits, labels, preds, mlab, valid = R.loss_inputs("mid")
+    k, n = preds.shape[:2]
+    big = torch.zeros(1 + preds.size, dtype=torch.float32, device=dev())
+    big[1:] = on(preds).view(-1)
+    views = [big[1 + s * n * 3136:1 + (s + 1) * n * 3136].view(n, 1, 56, 56) for s in range(k)]
+    assert all(v.data_ptr() % 16 == 4 for v in views)
+    check_mask_loss(z, "mid", preds, mlab, valid, pred_tensors=views)
+
+
+def test_mask_loss_over_the_graphs_of_a_batch(z):
+    logits, labels, preds, mlab, valid, node_graph, edge_graph = R.graph_inputs()
+    check_mask_loss(z, "graphs", preds, mlab, valid, node_graph, 3)
+
+
+def test_more_steps_than_one_launch_takes_are_split(z):
+    logits, labels, preds, mlab, valid = R.loss_inputs("scalar")
+    pt = [on(preds[s % 2]) for s in range(19)]
+    lv, grads = mask_loss_and_grad(pt, on(mlab), on(valid), W["segmentation"])
+    one, g1 = mask_loss_and_grad(pt[:2], on(mlab), on(valid), W["segmentation"])
+    assert lv.shape == (20,) and len(grads) == 19
+    for s in range(19):
+        assert float(lv[1 + s]) == float(one[1 + s % 2]) and torch.equal(grads[s], g1[s % 2])
+    assert abs(float(lv[0]) - float(lv[1:].double().sum())) <= 1e-6 * float(lv[0])
+
+
+# ------------------------------------------------------------------------------------------------ compute_loss
+class Batch:
+    pass
+
+
+def make_batch(labels, mlab, valid):
+    b = Batch()
+    b.edge_labels, b.mask_labels, b.mask_gt_ixs = on(labels), on(mlab), on(valid)
+    return b
+
+
+@pytest.mark.parametrize("tag", ["mid", "novalid", "graphs"])
+def test_compute_loss_under_autograd(z, tag):
+    kw = {}
+    if tag == "graphs":
+        logits, labels, preds, mlab, valid, node_graph, edge_graph = R.graph_inputs()
+        kw = dict(edge_graph=on(edge_graph), node_graph=on(node_graph), n_graphs=3)
+    else:
+        logits, labels, preds, mlab, valid = R.loss_inputs(tag)
+    k = logits.shape[0]
+    lg = on(logits).requires_grad_(True)
+    pr = [on(preds[s]).requires_grad_(True) for s in range(k)]
+    outputs = {"classified_edges": [lg[s].view(-1, 1) for s in range(k)], "mask_predictions": pr}
+    batch = make_batch(labels, mlab, valid)
+    loss = compute_loss(outputs, batch, W, **kw)
+    assert loss.dim() == 0 and loss.requires_grad
+    (2.0 * loss).backward()   # (the incoming gradient scales both lists)
+    ref = float(z[f"{tag}:loss"])
+    assert abs(float(loss.detach()) - ref) <= 1e-5 * max(1.0, abs(ref))
+    want = z[f"{tag}:glogits"]
+    assert float(np.abs(lg.grad.cpu().numpy() / 2 - want).max()) <= 1e-6 * max(1.0, float(np.abs(want).max()))
+    rows = R.sample_rows(valid)
+    for s in range(k):
+        assert pr[s].grad is not None and pr[s].grad.shape == pr[s].shape
+        want = z[f"{tag}:gmask_rows"][s]
+        assert float(np.abs(pr[s].grad.cpu().numpy()[rows] / 2 - want).max()) <= 1e-6 * max(1.0, float(np.abs(want).max()))
+    if tag == "mid":   # the sum of the two native terms, bit for bit
+        track = tracking_loss([on(logits[s]).view(-1, 1) for s in range(k)], on(labels), weight=W["tracking"])
+        lv, _ = mask_loss_and_grad([on(preds[s]) for s in range(k)], on(mlab), on(valid), W["segmentation"])
+        assert float(loss.detach()) == float(track + lv[0])
+        # outputs without a mask branch: the tracking term alone
+        only = compute_loss({"classified_edges": [on(logits[s]).view(-1, 1) for s in range(k)]}, batch, W)
+        assert float(only) == float(track)
+
+
+# ------------------------------------------------------------------------------------------------ end to end
+def nerr(a, b):
+    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
+    return float(np.abs(a - b).max() / max(float(np.abs(b).max()), 1e-6))
+
+
+def g6_model_and_data():
+    """g6's model, graph and weights (tests/test_gpu_mask_branch.py build)"""
+    N, E, L, nin = 40, 360, 3, 64
+    params = synth.model_params(32, L, "sum", num_class_steps=2, node_in_dim=nin)
+    params.update(synth.MASK_PARAMS)
+    Wt = synth.make_weights(params, seed=7)
+    Wt.update(synth.make_mask_weights(seed=17))
+    model = MOTMPNet(params)
+    model.load_state_dict({k: torch.from_numpy(v) for k, v in Wt.items()}, strict=True)
+    g = synth.make_graph(N, E, T=8, seed=4, node_in_dim=nin)
+    d = Batch()
+    d.x = on(g["x"]).view(N, nin, 1, 1)
+    d.x_ext = on(synth.normal(5, (N, 256, 14, 14), stream=1, std=0.5))
+    d.edge_index = on(g["edge_index"])
+    d.edge_attr = on(g["edge_attr"])
+    d.mask_labels = on((synth.uniform01(65, N * 56 * 56).reshape(N, 1, 56, 56) < 0.4).astype(np.float32))
+    d.mask_gt_ixs = on(R.first_valid(25, N))
+    return model.to(dev()).train(), d
+
+
+def e2e_errors(z, loss_fn):
+    """{parameter: (max error / max |reference|, relative norm error)} of g6's model under ``loss_fn(outputs, batch)`` -- the native
+    loss here, the stock-torch one as well in tools/train_targets_bench.py --e2e"""
+    model, d = g6_model_and_data()
+    d.edge_labels = assign_edge_labels(d.edge_index, z["e2e:ids"], mode="closest")
+    assert d.edge_labels.cpu().numpy().tobytes() == z["e2e:edge_labels"].tobytes()
+    loss = loss_fn(model(d), d)
+    loss.backward()
+    pd = dict(model.named_parameters())
+    errs = {}
+    for key in z.files:
+        if not key.startswith("e2e:G:"):
+            continue
+        k = key[6:]
+        got, ref = pd[k].grad.cpu().numpy(), z[key]
+        if got.size != ref.size:
+            got = got.reshape(-1)[:ref.size]
+        nrm, want = float(torch.sqrt((pd[k].grad.double() ** 2).sum())), float(z["e2e:Gn:" + k])
+        errs[k] = (nerr(got.reshape(ref.shape), ref), abs(nrm - want) / want)
+    return float(loss.detach()), errs
+
+
+def test_training_loss_end_to_end_through_both_branches(z):
+    """Forward of g6's model, the native labels, the native loss, backward through both branches, against the reference's forward,
+    _compute_loss and autograd: 5e-4 for the hot-path parameters, 5e-3 for the mask branch's convolutions (the bounds of
+    test_gradients_through_both_branches; measured 5.6e-6 and 1.2e-3 at most.  The same forward under stock torch's
+    binary_cross_entropy_with_logits: ``python tools/train_targets_bench.py --e2e``, figures in DESIGN.md)."""
+    loss, errs = e2e_errors(z, lambda out, d: compute_loss(out, d, W))
+    ref = float(z["e2e:loss"])
+    print("e2e loss native %.8g reference %.8g" % (loss, ref))
+    for k, (e, n) in errs.items():
+        print("e2e %-60s %.3e / %.3e" % (k, e, n))
+    assert abs(loss - ref) <= 1e-5 * max(1.0, abs(ref))
+    assert len(errs) >= 10
+    for k, (e, n) in errs.items():
+        tol = 5e-4 if k.startswith(("encoder.", "MPNet.", "classifier.")) else 5e-3
+        assert e < tol and n < tol, (k, e, n)

@@ -43,6 +43,10 @@ Fixtures:
                                the reference's ensure_unique_masks over the literal paste (tests/full_masks_ref.py literal_paste: torch's
                                own CPU resize), bit-packed, their COCO strings, and the sample line of the MOTS evaluation kit's README.
                                Only with --only g20.
+  g21_training_targets.npz     MOTGraph.assign_edge_labels ('all' and 'closest') on seven graphs (gaps, unmatched nodes, stored duplicates,
+                               self loops, a batch, several blocks of edges) and MOTNeuralSolver._compute_loss WITH its segmentation term
+                               (+ autograd w.r.t. the logits and the mask predictions) on six cases incl. a batch of three graphs, and end
+                               to end through g6's model.  Inputs come from tests/training_targets_ref.py.  Only with --only g21.
 
 Usage:  python tools/make_golden.py [--only g1,g2,...]
 """
@@ -1132,6 +1136,167 @@ def gen_g20():
     np.savez_compressed(os.path.join(GOLD, "g20_full_masks.npz"), **rec)
 
 
+def _real_scatter_min(src, index, dim=-1, out=None, dim_size=None):
+    """torch_scatter.scatter_min for 1-D inputs: (min, arg) with arg = src.numel() for an empty segment -- the position of the
+    -1 the reference appends (data/mot_graph.py:246-248).  Ties: the first position (they cannot change a label: equal
+    distances on one side of a row are stored duplicates of ONE edge, and the reference compares node ids, not positions)."""
+    assert src.dim() == 1 and index.shape == src.shape
+    n = int(dim_size)
+    mn = torch.full((n,), torch.iinfo(src.dtype).max, dtype=src.dtype)
+    arg = torch.full((n,), src.numel(), dtype=torch.long)
+    for j in range(src.numel() - 1, -1, -1):
+        i = int(index[j])
+        if src[j] <= mn[i]:
+            mn[i], arg[i] = src[j], j
+    return mn, arg
+
+
+def gen_g21():
+    """The reference's OWN MOTGraph.assign_edge_labels (data/mot_graph.py:223-262, unbound on a namespace) and
+    MOTNeuralSolver._compute_loss (pl_module/pl_module.py:88-120) with autograd; inputs from tests/training_targets_ref.py."""
+    EV, TR, PL = _import_tracking_stack()
+    import pandas as pd
+    from mot_neural_solver.data import mot_graph as MG
+    MG.scatter_min = _real_scatter_min   # (mot_graph.py binds the name at import; the shim's raises)
+    mpn = import_reference()
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    import training_targets_ref as R
+    rec = {}
+
+    def ref_labels(ei, ids, mode):
+        x = torch.zeros((len(ids), 1))
+        ns = types.SimpleNamespace(dataset_params={"true_edge_labels": mode}, graph_df=pd.DataFrame({"id": np.asarray(ids, np.int64)}),
+                                   graph_obj=_GeoData(edge_index=torch.from_numpy(np.ascontiguousarray(ei)), x=x))
+        MG.MOTGraph.assign_edge_labels(ns)
+        return ns.graph_obj.edge_labels.numpy().astype(np.float32)
+
+    # ---- label cases
+    g = synth.make_graph(48, 400, T=8, seed=21, node_in_dim=4)
+    ids = R.track_ids(g["frame"], 21)
+    ei = g["edge_index"]
+    lab_all, lab_cl = ref_labels(ei, ids, "all"), ref_labels(ei, ids, "closest")
+    # what the case is for: unmatched nodes, gaps of >= 2 frames inside a track, and a node whose nearest same-id detection in time
+    # has no edge to it while a farther one has
+    assert (ids == -1).any()
+    fr = g["frame"]
+    assert any(np.diff(np.unique(fr[ids == t])).max() >= 2 for t in np.unique(ids[ids >= 0]) if (ids == t).sum() > 1)
+    skipped = 0
+    for n in range(48):
+        later = [m for m in range(n + 1, 48) if ids[m] == ids[n] and ids[n] != -1]
+        cols = set(ei[1][(ei[0] == n)].tolist())
+        if later and later[0] not in cols and any(m in cols for m in later[1:]):
+            skipped += 1
+    assert skipped >= 1 and 0 < lab_cl.sum() < lab_all.sum()
+    cases = {"base": (ei, ids)}
+    act = np.nonzero(lab_cl == 1)[0][:3]
+    oth = np.nonzero(lab_cl == 0)[0][:3]
+    real = np.nonzero(ids >= 0)[0][[0, 5, 11, 17]]
+    cases["dups"] = (np.concatenate([ei, ei[:, act], ei[:, oth], np.stack([real, real])], axis=1), ids)
+    cases["unique"] = (ei, np.arange(48, dtype=np.int64))
+    cases["one"] = (np.array([[0], [1]], np.int64), np.array([3, 3], np.int64))
+    cases["none"] = (np.zeros((2, 0), np.int64), np.array([3, 3, -1], np.int64))
+    gs = [synth.make_graph(20, 120, T=5, seed=30 + i, node_in_dim=4) for i in range(3)]
+    b = synth.batch_graphs(gs)
+    cases["batch"] = (b["edge_index"], np.concatenate([R.track_ids(x["frame"], 33 + i) for i, x in enumerate(gs)]))
+    gb = synth.make_graph(300, 3000, T=12, seed=23, node_in_dim=4)
+    cases["big"] = (gb["edge_index"], R.track_ids(gb["frame"], 24))
+    assert tuple(cases) == R.LABEL_CASES
+    for tag, (e, i) in cases.items():
+        rec[f"lab:{tag}:edge_index"], rec[f"lab:{tag}:ids"] = e.astype(np.int64), i.astype(np.int64)
+        for mode in R.MODES:
+            rec[f"lab:{tag}:{mode}"] = ref_labels(e, i, mode)
+            assert np.array_equal(rec[f"lab:{tag}:{mode}"], R.edge_labels(e, i, mode)), (tag, mode)
+    assert rec["lab:dups:all"][-4:].sum() == 4 and rec["lab:dups:closest"][-4:].sum() == 0 and rec["lab:dups:closest"][400:403].sum() == 3
+    assert rec["lab:unique:all"].sum() == 0 and rec["lab:big:closest"].sum() > 0
+
+    # ---- loss cases
+    solver = types.SimpleNamespace(hparams={"train_params": {"loss_weights": dict(R.LOSS_WEIGHTS)}})
+
+    def ref_loss(logits, labels, preds, mlab, valid):
+        k = logits.shape[0]
+        lg = torch.from_numpy(logits).clone().requires_grad_(True)
+        pr = [torch.from_numpy(np.ascontiguousarray(preds[s])).clone().requires_grad_(True) for s in range(k)]
+        outputs = {"classified_edges": [lg[s].view(-1, 1) for s in range(k)], "mask_predictions": pr}
+        batch = types.SimpleNamespace(edge_labels=torch.from_numpy(labels), mask_labels=torch.from_numpy(mlab),
+                                      mask_gt_ixs=torch.from_numpy(valid))
+        return PL.MOTNeuralSolver._compute_loss(solver, outputs, batch), lg, pr
+
+    def store_mask_grads(tag, grads, valid):
+        rows = R.sample_rows(valid)
+        rec[f"{tag}:gmask_rows"] = np.stack([gm[rows] for gm in grads])
+        rec[f"{tag}:gmask_norm"] = np.array([np.sqrt((gm.astype(np.float64) ** 2).sum()) for gm in grads])
+        rec[f"{tag}:gmask_row_abssum"] = np.stack([np.abs(gm.astype(np.float64)).reshape(gm.shape[0], -1).sum(axis=1) for gm in grads])
+
+    for tag in R.LOSS_CASES:
+        logits, labels, preds, mlab, valid = R.loss_inputs(tag)
+        loss, lg, pr = ref_loss(logits, labels, preds, mlab, valid)
+        loss.backward()
+        grads = [p_.grad.numpy() if p_.grad is not None else np.zeros(p_.shape, np.float32) for p_ in pr]
+        if tag == "novalid":
+            assert all(p_.grad is None for p_ in pr)
+        if tag == "extreme":
+            assert float(np.abs(preds).max()) >= 80.0
+        rec[f"{tag}:loss"], rec[f"{tag}:glogits"] = np.float64(float(loss.detach())), lg.grad.numpy()
+        store_mask_grads(tag, grads, valid)
+    # the graphs variant: the reference called once per graph, the losses averaged (g16's recipe)
+    logits, labels, preds, mlab, valid, node_graph, edge_graph = R.graph_inputs()
+    k = logits.shape[0]
+    lg = torch.from_numpy(logits).clone().requires_grad_(True)
+    pr = torch.from_numpy(preds).clone().requires_grad_(True)
+    total, per_graph = 0, []
+    for i in range(3):
+        er, nr = edge_graph == i, node_graph == i
+        outputs = {"classified_edges": [lg[s][torch.from_numpy(er)].view(-1, 1) for s in range(k)],
+                   "mask_predictions": [pr[s][torch.from_numpy(nr)] for s in range(k)]}
+        batch = types.SimpleNamespace(edge_labels=torch.from_numpy(labels[er]), mask_labels=torch.from_numpy(mlab[nr]),
+                                      mask_gt_ixs=torch.from_numpy(valid[nr]))
+        li = PL.MOTNeuralSolver._compute_loss(solver, outputs, batch)
+        per_graph.append(float(li.detach()))
+        total = total + li
+    loss = total / 3
+    loss.backward()
+    rec["graphs:loss"], rec["graphs:per_graph"], rec["graphs:glogits"] = np.float64(float(loss.detach())), np.array(per_graph), lg.grad.numpy()
+    store_mask_grads("graphs", [pr.grad[s].numpy() for s in range(k)], valid)
+
+    # ---- end to end: g6's model, graph and weights under the reference's own loss
+    N, E, L, nin = 40, 360, 3, 64
+    params = synth.model_params(32, L, "sum", num_class_steps=2, node_in_dim=nin)
+    W = synth.make_weights(params, seed=7)
+    W.update(synth.make_mask_weights(seed=17))
+    full = dict(params)
+    full.update(MASK_PARAMS)
+    model = mpn.MOTMPNet(full)
+    model.load_state_dict({k_: torch.from_numpy(v) for k_, v in W.items()}, strict=True)
+    g = synth.make_graph(N, E, T=8, seed=4, node_in_dim=nin)
+    d = Data()
+    d.x = torch.from_numpy(g["x"]).view(N, nin, 1, 1)
+    d.x_ext = torch.from_numpy(synth.normal(5, (N, 256, 14, 14), stream=1, std=0.5))
+    d.edge_index = torch.from_numpy(g["edge_index"])
+    d.edge_attr = torch.from_numpy(g["edge_attr"])
+    ids = R.track_ids(g["frame"], 6)
+    d.edge_labels = torch.from_numpy(ref_labels(g["edge_index"], ids, "closest"))
+    assert float(d.edge_labels.sum()) >= 4
+    d.mask_labels = torch.from_numpy((synth.uniform01(65, N * 56 * 56).reshape(N, 1, 56, 56) < 0.4).astype(np.float32))
+    valid = R.first_valid(25, N)
+    d.mask_gt_ixs = torch.from_numpy(valid)
+    out = model(d)
+    loss = PL.MOTNeuralSolver._compute_loss(solver, out, d)
+    names = [k_ for k_ in W if k_.startswith(("encoder.", "MPNet.", "classifier."))] + ["MPAttentionNet.node_model.layers.0.weight",
+                                                                                      "mask_predictor.mask_head.layers.0.bias"]
+    pd_ = dict(model.named_parameters())
+    grads = torch.autograd.grad(loss, [pd_[k_] for k_ in names])
+    rec.update({"e2e:ids": ids, "e2e:edge_labels": d.edge_labels.numpy(), "e2e:loss": np.float64(float(loss.detach()))})
+    for k_, gr in zip(names, grads):
+        a = gr.numpy()
+        rec["e2e:G:" + k_] = a if a.size < 20000 else a.reshape(-1)[:20000]
+        rec["e2e:Gn:" + k_] = np.float64(np.sqrt((a.astype(np.float64) ** 2).sum()))
+    path = os.path.join(GOLD, "g21_training_targets.npz")
+    np.savez_compressed(path, **rec)
+    print("g21 ok:", {k_: round(float(v), 6) for k_, v in rec.items() if k_.endswith(":loss")}, "positives",
+          {t: (int(rec[f"lab:{t}:all"].sum()), int(rec[f"lab:{t}:closest"].sum())) for t in R.LABEL_CASES}, "skipped-nearest nodes", skipped,
+          "bytes", os.path.getsize(path))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", default="g0,g1,g4,g5,g6,g7,g8,g2,g3,g11,g12,g10,g9")
@@ -1161,6 +1326,7 @@ def main():
     if "g18" in only: gen_g18(mpn)
     if "g19" in only: gen_g19()
     if "g20" in only: gen_g20()
+    if "g21" in only: gen_g21()
 
 
 if __name__ == "__main__":
