@@ -19,7 +19,16 @@ void set_error(const char* fmt, ...);
         }                                 \
     } while (0)
 
-#define MPN_HIP(call)                                                                      \
+// name: the operator, a string literal; refuses a null workspace or one smaller than the layout function's size
+#define MPN_CHECK_WORKSPACE(name, workspace, workspace_bytes, need)                                              \
+    do {                                                                                                          \
+        if (!(workspace) || (workspace_bytes) < (need)) {                                                         \
+            mpnhip::set_error(name ": workspace %zu < %zu", (size_t)(workspace_bytes), (size_t)(need));           \
+            return MPNHIP_ERR_WORKSPACE;                                                                          \
+        }                                                                                                         \
+    } while (0)
+
+#define MPN_HIP(call)                                                                     \
     do {                                                                                   \
         hipError_t _e = (call);                                                            \
         if (_e != hipSuccess) {                                                            \
@@ -323,6 +332,48 @@ bool pack_batch_add(PackBatch* b, const PackOp& op);        // true: recorded (b
 int pack_batch_flush(const PackBatch* b, hipStream_t stream);   // launches what was recorded
 
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+// An operator's workspace is described ONCE, by a layout function that walks a Carver over it: with a null base it only sizes
+// (mpnhip_X_workspace_bytes), with the caller's buffer it hands out the regions (the operator).  Every region starts on a
+// 256-byte boundary of the buffer.
+struct Carver {
+    char* base;
+    size_t off = 0;
+    explicit Carver(void* workspace) : base(static_cast<char*>(workspace)) {}
+    template <class T>
+    T* take(size_t count) {
+        T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
+        off += align_up(count * sizeof(T), 256);
+        return p;
+    }
+    size_t bytes() const { return off; }
+};
+
+// bits needed to represent max_value (1 .. 64): the end bit of a radix sort whose largest key is max_value
+static inline unsigned key_bits(uint64_t max_value) {
+    unsigned b = 1;
+    while (b < 64 && (max_value >> b)) ++b;
+    return b;
+}
+
+static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+// blocks of 256 threads, one thread per item
+static inline unsigned blocks_for(int64_t n) { return (unsigned)((n + 255) / 256); }
+
+// blocks of 256 threads for a grid-stride stream over `items` work items: enough to fill the chip, never more than the work
+inline unsigned stream_blocks(int64_t items) {
+    static int cus = 0;
+    if (cus == 0) {
+        int dev = 0, n = 0;
+        if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0)
+            cus = n;
+        else
+            cus = 256;
+    }
+    const int64_t need = (items + 255) / 256, cap = (int64_t)cus * 8;
+    return (unsigned)(need < 1 ? 1 : (need < cap ? need : cap));
+}
 
 // Host-side counters of the kernel variants launched (mpnhip_debug_counters): test instrumentation that lets a parity test
 // assert WHICH code path produced the result it checked.  One relaxed atomic add per launch site.

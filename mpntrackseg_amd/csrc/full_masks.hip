@@ -12,11 +12,9 @@
 // truncated coordinate, one in the interpolation a thresholded pixel.
 #pragma clang fp contract(off)
 
-#include "common.h"
+#include "device_prims.h"
 
 #include <rocprim/block/block_scan.hpp>
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
 
 namespace mpnhip {
 namespace {
@@ -233,39 +231,27 @@ __global__ __launch_bounds__(EV_THREADS) void k_event_fill(const int* __restrict
     });
 }
 
-static size_t ev_sort_temp(int64_t n) {
-    size_t bytes = 0;
-    unsigned* k = nullptr;
-    int* v = nullptr;
-    (void)rocprim::radix_sort_pairs(nullptr, bytes, k, k, v, v, (size_t)(n > 0 ? n : 1), 0, 32, (hipStream_t)0);
-    return bytes;
-}
-static size_t ev_scan_temp(int64_t n) {
-    size_t bytes = 0;
-    int* p = nullptr;
-    (void)rocprim::exclusive_scan(nullptr, bytes, p, p, 0, (size_t)(n > 0 ? n : 1), rocprim::plus<int>(), (hipStream_t)0);
-    return bytes;
-}
 static int64_t ev_blocks(int64_t n_frames, int64_t hw) { return (n_frames * hw + EV_PER_BLOCK - 1) / EV_PER_BLOCK; }
 
 // the event workspace: block counts and offsets [blocks + 1] each, rocprim's scratch, then (fill only) the unsorted keys and
 // positions and the sorted keys
 struct EvView { int* counts; int* offsets; void* tmp; size_t tmp_bytes; unsigned* keys; int* vals; unsigned* skeys; size_t bytes; };
 static EvView ev_view(void* workspace, int64_t n_frames, int64_t hw, int64_t n_events) {
-    char* base = static_cast<char*>(workspace);
-    size_t off = 0;
-    auto take = [&](size_t bytes) { char* p = base ? base + off : nullptr; off += align_up(bytes, 256); return p; };
+    Carver c(workspace);
     const int64_t nb = ev_blocks(n_frames, hw);
-    EvView v;
-    v.counts = reinterpret_cast<int*>(take((size_t)(nb + 1) * 4));
-    v.offsets = reinterpret_cast<int*>(take((size_t)(nb + 1) * 4));
-    const size_t a = ev_scan_temp(nb + 1), b = ev_sort_temp(n_events);
-    v.tmp_bytes = a > b ? a : b;
-    v.tmp = take(v.tmp_bytes);
-    v.keys = reinterpret_cast<unsigned*>(take((size_t)n_events * 4));
-    v.vals = reinterpret_cast<int*>(take((size_t)n_events * 4));
-    v.skeys = reinterpret_cast<unsigned*>(take((size_t)n_events * 4));
-    v.bytes = off;
+    const size_t a = exclusive_scan_temp<int>(nb + 1), b = sort_pairs_temp<unsigned>(n_events), tmp_bytes = a > b ? a : b, n = (size_t)n_events;
+    EvView v = {c.take<int>((size_t)(nb + 1)), c.take<int>((size_t)(nb + 1)), c.take<char>(tmp_bytes), tmp_bytes,
+                c.take<unsigned>(n), c.take<int>(n), c.take<unsigned>(n), 0};
+    v.bytes = c.bytes();
+    return v;
+}
+
+// the paste workspace: the detections' expanded boxes
+struct PasteView { int* boxes; size_t bytes; };
+static PasteView paste_view(void* workspace, int64_t n_dets) {
+    Carver c(workspace);
+    PasteView v = {c.take<int>((size_t)n_dets * BOX_INTS), 0};
+    v.bytes = c.bytes();
     return v;
 }
 
@@ -275,14 +261,13 @@ static bool sizes_ok(int64_t n_dets, int64_t n_frames, int64_t hw) {
 }
 
 // block counts -> exclusive offsets, offsets[blocks] = number of events
-static int count_and_scan(const int* labels, int64_t n_frames, int64_t hw, int64_t n_dets, const EvView& v, int* det_counts,
+static int count_and_scan(const int* labels, int64_t n_frames, int64_t hw, int64_t n_dets, EvView& v, int* det_counts,
                           hipStream_t stream) {
     const int64_t total = n_frames * hw, nb = ev_blocks(n_frames, hw);
     MPN_HIP(hipMemsetAsync(v.counts + nb, 0, 4, stream));
     hipLaunchKernelGGL(k_event_count, dim3((unsigned)nb), dim3(EV_THREADS), 0, stream, labels, total, hw, (int)n_dets, v.counts, det_counts);
     MPN_LAUNCH_CHECK();
-    size_t tmp_bytes = v.tmp_bytes;
-    MPN_HIP(rocprim::exclusive_scan(v.tmp, tmp_bytes, v.counts, v.offsets, 0, (size_t)(nb + 1), rocprim::plus<int>(), stream));
+    MPN_HIP(rocprim::exclusive_scan(v.tmp, v.tmp_bytes, v.counts, v.offsets, 0, (size_t)(nb + 1), rocprim::plus<int>(), stream));
     return MPNHIP_OK;
 }
 
@@ -293,7 +278,7 @@ using namespace mpnhip;
 
 extern "C" size_t mpnhip_full_masks_workspace_bytes(int64_t n_dets, int64_t n_frames, int64_t hw, int64_t n_events) {
     if (!sizes_ok(n_dets, n_frames, hw) || n_events < 0 || n_events >= (1LL << 31)) return 0;
-    const size_t paste = align_up((size_t)n_dets * BOX_INTS * 4, 256);
+    const size_t paste = paste_view(nullptr, n_dets).bytes;
     const size_t events = (n_frames == 0 || hw == 0) ? 0 : ev_view(nullptr, n_frames, hw, n_events).bytes;
     const size_t need = paste > events ? paste : events;
     return need ? need + 256 : 0;
@@ -312,14 +297,11 @@ extern "C" int mpnhip_paste_unique_masks(const float* masks, int64_t n_rows, int
     MPN_CHECK_ARG(mh >= 1 && mw >= 1, "paste_unique_masks: the RoI masks need mh, mw >= 1");
     MPN_CHECK_ARG(labels && frame_ptr, "paste_unique_masks: null labels / frame_ptr");
     MPN_CHECK_ARG(n_dets == 0 || (masks && boxes), "paste_unique_masks: null masks / boxes");
-    const size_t need = align_up((size_t)n_dets * BOX_INTS * 4, 256);
-    if (n_dets > 0 && (!workspace || workspace_bytes < need)) {
-        set_error("paste_unique_masks: workspace %zu < %zu", workspace_bytes, need);
-        return MPNHIP_ERR_WORKSPACE;
-    }
-    int* bx = static_cast<int*>(workspace);
+    const PasteView pv = paste_view(workspace, n_dets);
+    if (n_dets > 0) MPN_CHECK_WORKSPACE("paste_unique_masks", workspace, workspace_bytes, pv.bytes);
+    int* bx = pv.boxes;
     if (n_dets > 0) {
-        hipLaunchKernelGGL(k_expand_boxes, dim3((unsigned)((n_dets + 255) / 256)), dim3(256), 0, stream, boxes, det_ids, n_dets, n_rows, mw, bx);
+        hipLaunchKernelGGL(k_expand_boxes, dim3(blocks_for(n_dets)), dim3(256), 0, stream, boxes, det_ids, n_dets, n_rows, mw, bx);
         MPN_LAUNCH_CHECK();
     }
     const int tiles_y = (img_h + TILE_Y - 1) / TILE_Y, tiles_x = (img_w + TILE_X - 1) / TILE_X;
@@ -344,12 +326,8 @@ extern "C" int mpnhip_mask_run_events_count(const int32_t* labels, int64_t n_fra
         return MPNHIP_OK;
     }
     MPN_CHECK_ARG(labels && det_counts && n_events, "mask_run_events_count: null pointer");
-    const size_t need = ev_view(nullptr, n_frames, hw, 0).bytes;
-    if (!workspace || workspace_bytes < need) {
-        set_error("mask_run_events_count: workspace %zu < %zu", workspace_bytes, need);
-        return MPNHIP_ERR_WORKSPACE;
-    }
-    const EvView v = ev_view(workspace, n_frames, hw, 0);
+    EvView v = ev_view(workspace, n_frames, hw, 0);
+    MPN_CHECK_WORKSPACE("mask_run_events_count", workspace, workspace_bytes, v.bytes);
     MPN_HIP(hipMemsetAsync(det_counts, 0, (size_t)n_dets * 4, stream));
     MPN_TRY(count_and_scan(labels, n_frames, hw, n_dets, v, det_counts, stream));
     hipLaunchKernelGGL(k_event_total, dim3(1), dim3(64), 0, stream, v.offsets, ev_blocks(n_frames, hw), n_events);
@@ -364,12 +342,8 @@ extern "C" int mpnhip_mask_run_events(const int32_t* labels, int64_t n_frames, i
                   "mask_run_events: bad sizes (H * W and the number of events must stay below 2^31)");
     if (n_events == 0 || n_frames == 0 || hw == 0 || n_dets == 0) return MPNHIP_OK;
     MPN_CHECK_ARG(labels && event_pos, "mask_run_events: null pointer");
-    const size_t need = ev_view(nullptr, n_frames, hw, n_events).bytes;
-    if (!workspace || workspace_bytes < need) {
-        set_error("mask_run_events: workspace %zu < %zu", workspace_bytes, need);
-        return MPNHIP_ERR_WORKSPACE;
-    }
-    const EvView v = ev_view(workspace, n_frames, hw, n_events);
+    EvView v = ev_view(workspace, n_frames, hw, n_events);
+    MPN_CHECK_WORKSPACE("mask_run_events", workspace, workspace_bytes, v.bytes);
     MPN_TRY(count_and_scan(labels, n_frames, hw, n_dets, v, nullptr, stream));
     // (slots the image does not fill -- a count that is not its own -- sort behind every detection)
     MPN_HIP(hipMemsetAsync(v.keys, 0xFF, (size_t)n_events * 4, stream));
@@ -379,9 +353,6 @@ extern "C" int mpnhip_mask_run_events(const int32_t* labels, int64_t n_frames, i
     MPN_LAUNCH_CHECK();
     // the fill is in position order inside a frame and a detection belongs to one frame: a STABLE sort by detection alone leaves
     // every detection's positions ascending; only the bits a detection index needs are sorted (the filler key has them all set)
-    unsigned bits = 1;
-    while (bits < 32 && (1LL << bits) <= n_dets) ++bits;
-    size_t tmp_bytes = v.tmp_bytes;
-    MPN_HIP(rocprim::radix_sort_pairs(v.tmp, tmp_bytes, v.keys, v.skeys, v.vals, event_pos, (size_t)n_events, 0, bits, stream));
+    MPN_HIP(rocprim::radix_sort_pairs(v.tmp, v.tmp_bytes, v.keys, v.skeys, v.vals, event_pos, (size_t)n_events, 0, key_bits((uint64_t)n_dets), stream));
     return MPNHIP_OK;
 }

@@ -6,9 +6,7 @@
 // its partners, an exclusive scan turns the counts into offsets and a second pass writes the pairs -- same pairs,
 // same (row, col) order, no N x N array.  All integer results are bit-exact; the features follow the reference's
 // operation order in fp32 (log via logf, the embedding norm re-associated across a wavefront).
-#include "common.h"
-
-#include <rocprim/device/device_scan.hpp>
+#include "device_prims.h"
 
 namespace mpnhip {
 namespace {
@@ -98,11 +96,14 @@ __global__ __launch_bounds__(256) void k_pairwise_dist(const float* __restrict__
     if (lane == 0) out[e] = sqrtf(acc);
 }
 
-static size_t scan_temp(int n) {
-    size_t bytes = 0;
-    int64_t* p = nullptr;
-    (void)rocprim::exclusive_scan(nullptr, bytes, p, p, (int64_t)0, (size_t)(n > 0 ? n : 1), rocprim::plus<int64_t>(), (hipStream_t)0);
-    return bytes;
+// time_pairs_count's workspace: the rows' pair counts [N + 1] (the last one 0), rocprim's scratch
+struct PairsView { int64_t* counts; void* tmp; size_t tmp_bytes; size_t bytes; };
+static PairsView pairs_view(void* workspace, int n_nodes) {
+    Carver c(workspace);
+    PairsView v = {c.take<int64_t>((size_t)n_nodes + 1), nullptr, exclusive_scan_temp<int64_t>(n_nodes + 1), 0};
+    v.tmp = c.take<char>(v.tmp_bytes);
+    v.bytes = c.bytes() + 256;
+    return v;
 }
 
 }  // namespace
@@ -133,7 +134,7 @@ __global__ void k_embedding_check(const float* __restrict__ stored, int64_t ld, 
 using namespace mpnhip;
 
 extern "C" size_t mpnhip_time_valid_conn_workspace_bytes(int n_nodes) {
-    return align_up(((size_t)n_nodes + 1) * 8, 256) + align_up(scan_temp(n_nodes + 1), 256) + 256;
+    return pairs_view(nullptr, n_nodes).bytes;
 }
 
 static int time_pairs_count(bool directed, const int64_t* frame_num, int n_nodes, int64_t max_frame_dist, int64_t* offsets,
@@ -145,25 +146,19 @@ static int time_pairs_count(bool directed, const int64_t* frame_num, int n_nodes
         return MPNHIP_OK;
     }
     MPN_CHECK_ARG(frame_num, "time_valid_conn: null frames");
-    if (!workspace || workspace_bytes < mpnhip_time_valid_conn_workspace_bytes(n_nodes)) {
-        set_error("time_valid_conn: workspace %zu < %zu", workspace_bytes, mpnhip_time_valid_conn_workspace_bytes(n_nodes));
-        return MPNHIP_ERR_WORKSPACE;
-    }
-    char* w = static_cast<char*>(workspace);
-    int64_t* counts = reinterpret_cast<int64_t*>(w);
-    void* tmp = w + align_up(((size_t)n_nodes + 1) * 8, 256);
-    size_t tmp_bytes = scan_temp(n_nodes + 1);
-    MPN_HIP(hipMemsetAsync(counts, 0, ((size_t)n_nodes + 1) * 8, stream));
+    PairsView v = pairs_view(workspace, n_nodes);
+    MPN_CHECK_WORKSPACE("time_valid_conn", workspace, workspace_bytes, v.bytes);
+    MPN_HIP(hipMemsetAsync(v.counts, 0, ((size_t)n_nodes + 1) * 8, stream));
     const dim3 grid((unsigned)((n_nodes + 3) / 4));
     if (directed)
-        hipLaunchKernelGGL((k_time_pairs<false, true>), grid, dim3(256), 0, stream, frame_num, n_nodes, max_frame_dist, counts, nullptr,
+        hipLaunchKernelGGL((k_time_pairs<false, true>), grid, dim3(256), 0, stream, frame_num, n_nodes, max_frame_dist, v.counts, nullptr,
                            nullptr, nullptr);
     else
-        hipLaunchKernelGGL((k_time_pairs<false, false>), grid, dim3(256), 0, stream, frame_num, n_nodes, max_frame_dist, counts, nullptr,
+        hipLaunchKernelGGL((k_time_pairs<false, false>), grid, dim3(256), 0, stream, frame_num, n_nodes, max_frame_dist, v.counts, nullptr,
                            nullptr, nullptr);
     MPN_LAUNCH_CHECK();
     // offsets[i] = pairs of rows < i; offsets[N] = number of pairs
-    MPN_HIP(rocprim::exclusive_scan(tmp, tmp_bytes, counts, offsets, (int64_t)0, (size_t)n_nodes + 1, rocprim::plus<int64_t>(), stream));
+    MPN_HIP(rocprim::exclusive_scan(v.tmp, v.tmp_bytes, v.counts, offsets, (int64_t)0, (size_t)n_nodes + 1, rocprim::plus<int64_t>(), stream));
     return MPNHIP_OK;
 }
 
@@ -212,7 +207,7 @@ extern "C" int mpnhip_edge_features(const int64_t* edge_ixs, int64_t n_edges, in
     if (n_edges == 0) return MPNHIP_OK;
     MPN_CHECK_ARG(edge_ixs && frame_num && bb_height && bb_width && feet_x && feet_y && edge_feats, "edge_features: null pointer");
     MPN_CHECK_ARG(fps > 0.f, "edge_features: fps must be positive");
-    hipLaunchKernelGGL(k_edge_feats, dim3((unsigned)((n_edges + 255) / 256)), dim3(256), 0, stream, edge_ixs, n_edges, frame_num,
+    hipLaunchKernelGGL(k_edge_feats, dim3(blocks_for(n_edges)), dim3(256), 0, stream, edge_ixs, n_edges, frame_num,
                        fps, bb_height, bb_width, feet_x, feet_y, edge_feats);
     MPN_LAUNCH_CHECK();
     return MPNHIP_OK;
@@ -236,7 +231,7 @@ extern "C" int mpnhip_embedding_keep(const float* stored, int64_t ld, int64_t n_
     MPN_CHECK_ARG(n_stored >= 0 && n_det >= 0 && ld >= 1, "embedding_keep: bad sizes");
     if (n_stored == 0) return MPNHIP_OK;
     MPN_CHECK_ARG(stored && keep && (det_ids_sorted || n_det == 0), "embedding_keep: null pointer");
-    hipLaunchKernelGGL(k_embedding_keep, dim3((unsigned)((n_stored + 255) / 256)), dim3(256), 0, stream, stored, ld, n_stored,
+    hipLaunchKernelGGL(k_embedding_keep, dim3(blocks_for(n_stored)), dim3(256), 0, stream, stored, ld, n_stored,
                        det_ids_sorted, n_det, keep);
     MPN_LAUNCH_CHECK();
     return MPNHIP_OK;
@@ -250,7 +245,7 @@ extern "C" int mpnhip_embedding_check(const float* stored, int64_t ld, const int
     MPN_HIP(hipMemsetAsync(mismatch, 0, sizeof(int32_t), stream));
     if (n == 0) return MPNHIP_OK;
     MPN_CHECK_ARG(stored && rows && det_ids, "embedding_check: null pointer");
-    hipLaunchKernelGGL(k_embedding_check, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, stored, ld, rows, n, det_ids, mismatch);
+    hipLaunchKernelGGL(k_embedding_check, dim3(blocks_for(n)), dim3(256), 0, stream, stored, ld, rows, n, det_ids, mismatch);
     MPN_LAUNCH_CHECK();
     return MPNHIP_OK;
 }

@@ -5,39 +5,28 @@
 // (ascending edge id inside a segment).
 #include <cstring>
 
-#include "common.h"
-
-#include <rocprim/device/device_radix_sort.hpp>
+#include "device_prims.h"
 
 namespace mpnhip {
 
 size_t graph_layout(int N, int64_t E, GraphView* v, void* base) {
-    size_t off = 0;
-    auto take = [&](size_t n_ints) {
-        size_t o = off;
-        off = align_up(off + n_ints * sizeof(int), 256);
-        return o;
-    };
-    size_t o_header = take(8), o_perm = take(E), o_srow = take(E), o_scol = take(E), o_seg = take(3 * (size_t)N + 1);
-    size_t o_cperm = take(E), o_cseg = take(3 * (size_t)N + 1), o_rperm = take(E), o_rseg = take((size_t)N + 1);
-    size_t o_call = take(E), o_csall = take((size_t)N + 1);
-    if (v) {
-        char* b = static_cast<char*>(base);
-        v->N = N;
-        v->E = E;
-        v->header = reinterpret_cast<int*>(b + o_header);
-        v->perm = reinterpret_cast<int*>(b + o_perm);
-        v->srow = reinterpret_cast<int*>(b + o_srow);
-        v->scol = reinterpret_cast<int*>(b + o_scol);
-        v->seg_ptr = reinterpret_cast<int*>(b + o_seg);
-        v->cperm = reinterpret_cast<int*>(b + o_cperm);
-        v->cseg_ptr = reinterpret_cast<int*>(b + o_cseg);
-        v->rperm = reinterpret_cast<int*>(b + o_rperm);
-        v->rseg_ptr = reinterpret_cast<int*>(b + o_rseg);
-        v->cperm_all = reinterpret_cast<int*>(b + o_call);
-        v->cseg_all = reinterpret_cast<int*>(b + o_csall);
-    }
-    return off;
+    Carver c(base);
+    GraphView g;
+    g.N = N;
+    g.E = E;
+    g.header = c.take<int>(8);
+    g.perm = c.take<int>((size_t)E);
+    g.srow = c.take<int>((size_t)E);
+    g.scol = c.take<int>((size_t)E);
+    g.seg_ptr = c.take<int>(3 * (size_t)N + 1);
+    g.cperm = c.take<int>((size_t)E);
+    g.cseg_ptr = c.take<int>(3 * (size_t)N + 1);
+    g.rperm = c.take<int>((size_t)E);
+    g.rseg_ptr = c.take<int>((size_t)N + 1);
+    g.cperm_all = c.take<int>((size_t)E);
+    g.cseg_all = c.take<int>((size_t)N + 1);
+    if (v) *v = g;
+    return c.bytes();
 }
 
 __global__ void k_make_keys(const int64_t* __restrict__ ei, int64_t E, int N, unsigned* __restrict__ keys,
@@ -104,18 +93,15 @@ __global__ void k_keys2(const int* __restrict__ srow, const int* __restrict__ sc
     vals[i] = (int)i;
 }
 
-static int bits_for(unsigned maxkey) {
-    int b = 1;
-    while (b < 32 && (maxkey >> b)) ++b;
-    return b;
-}
-
-static size_t sort_temp_bytes(int64_t E) {
-    size_t bytes = 0;
-    unsigned* k = nullptr;
-    int* v = nullptr;
-    (void)rocprim::radix_sort_pairs(nullptr, bytes, k, k, v, v, (size_t)(E > 0 ? E : 1), 0, 32, (hipStream_t)0);
-    return bytes;
+// the sort's workspace: unsorted keys, sorted keys, unsorted values [max(E, 1)] each, rocprim's scratch
+struct PrepView { unsigned* keys_in; unsigned* keys_out; int* vals_in; void* tmp; size_t tmp_bytes; size_t bytes; };
+static PrepView prep_view(void* workspace, int64_t E) {
+    Carver c(workspace);
+    const size_t e = (size_t)(E > 0 ? E : 1);
+    PrepView v = {c.take<unsigned>(e), c.take<unsigned>(e), c.take<int>(e), nullptr, sort_pairs_temp<unsigned>(E), 0};
+    v.tmp = c.take<char>(v.tmp_bytes);
+    v.bytes = c.bytes() + 256;
+    return v;
 }
 
 }  // namespace mpnhip
@@ -127,8 +113,7 @@ extern "C" size_t mpnhip_graph_bytes(int n_nodes, int64_t n_edges) {
 }
 
 extern "C" size_t mpnhip_graph_prep_workspace_bytes(int n_nodes, int64_t n_edges) {
-    size_t e = (size_t)(n_edges > 0 ? n_edges : 1);
-    return 3 * align_up(e * 4, 256) + align_up(sort_temp_bytes(n_edges), 256) + 256;
+    return prep_view(nullptr, n_edges).bytes;
 }
 
 static int graph_prep_impl(const int64_t* edge_index, int n_nodes, int64_t n_edges, void* graph_buf, size_t graph_bytes,
@@ -156,15 +141,13 @@ static int graph_prep_impl(const int64_t* edge_index, int n_nodes, int64_t n_edg
         set_error("graph_prep: graph buffer %zu < %zu", graph_bytes, mpnhip_graph_bytes(N, E));
         return MPNHIP_ERR_WORKSPACE;
     }
-    if (workspace_bytes < mpnhip_graph_prep_workspace_bytes(N, E) || (!workspace && E > 0)) {
-        set_error("graph_prep: workspace %zu < %zu", workspace_bytes, mpnhip_graph_prep_workspace_bytes(N, E));
-        return MPNHIP_ERR_WORKSPACE;
-    }
+    PrepView w = prep_view(workspace, E);
+    if (E > 0 || workspace_bytes < w.bytes) MPN_CHECK_WORKSPACE("graph_prep", workspace, workspace_bytes, w.bytes);   // (no edges: may be null)
     GraphView g;
     graph_layout(N, E, &g, graph_buf);
     MPN_HIP(hipMemsetAsync(g.header, 0, 8 * sizeof(int), stream));
     const int T = 256;
-    const unsigned nbE = (unsigned)((E + T - 1) / T);
+    const unsigned nbE = blocks_for(E);
     if (E == 0) {
         MPN_HIP(hipMemsetAsync(g.seg_ptr, 0, (3 * (size_t)N + 1) * sizeof(int), stream));
         MPN_HIP(hipMemsetAsync(g.cseg_ptr, 0, (3 * (size_t)N + 1) * sizeof(int), stream));
@@ -172,22 +155,14 @@ static int graph_prep_impl(const int64_t* edge_index, int n_nodes, int64_t n_edg
         MPN_HIP(hipMemsetAsync(g.cseg_all, 0, ((size_t)N + 1) * sizeof(int), stream));
         return MPNHIP_OK;
     }
-    char* ws = static_cast<char*>(workspace);
-    size_t esz = align_up((size_t)E * 4, 256);
-    unsigned* keys_in = reinterpret_cast<unsigned*>(ws);
-    unsigned* keys_out = reinterpret_cast<unsigned*>(ws + esz);
-    int* vals_in = reinterpret_cast<int*>(ws + 2 * esz);
-    void* tmp = ws + 3 * esz;
-    size_t tmp_bytes = workspace_bytes - 3 * esz;
-
     // primary order: (direction, row), stable
-    hipLaunchKernelGGL(k_make_keys, dim3(nbE), dim3(T), 0, stream, edge_index, E, N, keys_in, vals_in, g.header);
+    hipLaunchKernelGGL(k_make_keys, dim3(nbE), dim3(T), 0, stream, edge_index, E, N, w.keys_in, w.vals_in, g.header);
     MPN_LAUNCH_CHECK();
-    MPN_HIP(rocprim::radix_sort_pairs(tmp, tmp_bytes, keys_in, keys_out, vals_in, g.perm, (size_t)E, 0,
-                                      bits_for(3u * (unsigned)N), stream));
+    MPN_HIP(rocprim::radix_sort_pairs(w.tmp, w.tmp_bytes, w.keys_in, w.keys_out, w.vals_in, g.perm, (size_t)E, 0,
+                                      key_bits(3u * (unsigned)N), stream));
     hipLaunchKernelGGL(k_gather_rc, dim3(nbE), dim3(T), 0, stream, edge_index, E, N, g.perm, g.srow, g.scol);
     MPN_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_lower_bound, dim3((3 * N + 1 + T) / T), dim3(T), 0, stream, keys_out, E, 3 * N, g.seg_ptr);
+    hipLaunchKernelGGL(k_lower_bound, dim3((3 * N + 1 + T) / T), dim3(T), 0, stream, w.keys_out, E, 3 * N, g.seg_ptr);
     MPN_LAUNCH_CHECK();
     hipLaunchKernelGGL(k_header, dim3(1), dim3(64), 0, stream, g.seg_ptr, N, E, g.header);
     MPN_LAUNCH_CHECK();
@@ -197,11 +172,11 @@ static int graph_prep_impl(const int64_t* edge_index, int n_nodes, int64_t n_edg
     struct { int mode; int* perm; int* ptr; int nkeys; } sec[3] = {
         {0, g.cperm, g.cseg_ptr, 3 * N}, {1, g.rperm, g.rseg_ptr, N}, {2, g.cperm_all, g.cseg_all, N}};
     for (auto& s : sec) {
-        hipLaunchKernelGGL(k_keys2, dim3(nbE), dim3(T), 0, stream, g.srow, g.scol, E, N, s.mode, keys_in, vals_in);
+        hipLaunchKernelGGL(k_keys2, dim3(nbE), dim3(T), 0, stream, g.srow, g.scol, E, N, s.mode, w.keys_in, w.vals_in);
         MPN_LAUNCH_CHECK();
-        MPN_HIP(rocprim::radix_sort_pairs(tmp, tmp_bytes, keys_in, keys_out, vals_in, s.perm, (size_t)E, 0,
-                                          bits_for((unsigned)s.nkeys), stream));
-        hipLaunchKernelGGL(k_lower_bound, dim3((s.nkeys + 1 + T) / T), dim3(T), 0, stream, keys_out, E, s.nkeys, s.ptr);
+        MPN_HIP(rocprim::radix_sort_pairs(w.tmp, w.tmp_bytes, w.keys_in, w.keys_out, w.vals_in, s.perm, (size_t)E, 0,
+                                          key_bits((unsigned)s.nkeys), stream));
+        hipLaunchKernelGGL(k_lower_bound, dim3((s.nkeys + 1 + T) / T), dim3(T), 0, stream, w.keys_out, E, s.nkeys, s.ptr);
         MPN_LAUNCH_CHECK();
     }
     return MPNHIP_OK;

@@ -185,13 +185,24 @@ __global__ void k_flow_constraints(GraphView g, const float* __restrict__ logits
     if (c_in > 0) atomicAdd(out + 7, 1);
 }
 
+// the tracking loss' workspace: a 256-byte head (the positive count), the blocks' partial sums [steps][blocks], and for the
+// per-graph form (per_graph) the graphs' {edges, positives} counts behind them
+struct LossView { float* pos; float* partial; int* counts; size_t bytes; };
+static LossView loss_view(void* workspace, int n_steps, int64_t n_edges, bool per_graph, int n_graphs) {
+    Carver c(workspace);
+    const size_t nblk = (size_t)((n_edges + 255) / 256);
+    LossView v = {c.take<float>(1), c.take<float>((size_t)(n_steps > 0 ? n_steps : 1) * (nblk > 0 ? nblk : 1)),
+                  per_graph ? c.take<int>((size_t)2 * (n_graphs > 0 ? n_graphs : 1)) : nullptr, 0};
+    v.bytes = c.bytes();
+    return v;
+}
+
 }  // namespace mpnhip
 
 using namespace mpnhip;
 
 extern "C" size_t mpnhip_tracking_loss_workspace_bytes(int n_steps, int64_t n_edges) {
-    const size_t nblk = (size_t)((n_edges + 255) / 256);
-    return 256 + align_up((size_t)(n_steps > 0 ? n_steps : 1) * (nblk > 0 ? nblk : 1) * sizeof(float), 256);
+    return loss_view(nullptr, n_steps, n_edges, false, 0).bytes;
 }
 
 extern "C" int mpnhip_tracking_loss(const float* logits, const float* labels, int n_steps, int64_t n_edges, int first_step,
@@ -205,24 +216,20 @@ extern "C" int mpnhip_tracking_loss(const float* logits, const float* labels, in
         return MPNHIP_OK;
     }
     MPN_CHECK_ARG(logits && labels && grad_logits, "tracking_loss: null tensor");
-    if (!workspace || workspace_bytes < mpnhip_tracking_loss_workspace_bytes(n_steps, n_edges)) {
-        set_error("tracking_loss: workspace %zu < %zu", workspace_bytes, mpnhip_tracking_loss_workspace_bytes(n_steps, n_edges));
-        return MPNHIP_ERR_WORKSPACE;
-    }
-    float* pos = static_cast<float*>(workspace);
-    float* partial = reinterpret_cast<float*>(static_cast<char*>(workspace) + 256);
-    const int nblk = (int)((n_edges + 255) / 256);
-    hipLaunchKernelGGL(k_count_pos, dim3(1), dim3(1024), 0, s, labels, n_edges, pos);
+    const LossView v = loss_view(workspace, n_steps, n_edges, false, 0);
+    MPN_CHECK_WORKSPACE("tracking_loss", workspace, workspace_bytes, v.bytes);
+    const int nblk = (int)blocks_for(n_edges);
+    hipLaunchKernelGGL(k_count_pos, dim3(1), dim3(1024), 0, s, labels, n_edges, v.pos);
     MPN_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_bce, dim3(nblk, n_steps), dim3(256), 0, s, logits, labels, n_edges, first_step, weight, pos, grad_logits, partial);
+    hipLaunchKernelGGL(k_bce, dim3(nblk, n_steps), dim3(256), 0, s, logits, labels, n_edges, first_step, weight, v.pos, grad_logits, v.partial);
     MPN_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_loss_reduce, dim3(1), dim3(256), 0, s, partial, nblk, n_steps, n_edges, weight, loss_out);
+    hipLaunchKernelGGL(k_loss_reduce, dim3(1), dim3(256), 0, s, v.partial, nblk, n_steps, n_edges, weight, loss_out);
     MPN_LAUNCH_CHECK();
     return MPNHIP_OK;
 }
 
 extern "C" size_t mpnhip_tracking_loss_graphs_workspace_bytes(int n_steps, int64_t n_edges, int n_graphs) {
-    return mpnhip_tracking_loss_workspace_bytes(n_steps, n_edges) + align_up((size_t)2 * (n_graphs > 0 ? n_graphs : 1) * sizeof(int), 256);
+    return loss_view(nullptr, n_steps, n_edges, true, n_graphs).bytes;
 }
 
 extern "C" int mpnhip_tracking_loss_graphs(const float* logits, const float* labels, const int32_t* edge_graph, int n_graphs, int n_steps,
@@ -236,23 +243,17 @@ extern "C" int mpnhip_tracking_loss_graphs(const float* logits, const float* lab
         return MPNHIP_OK;
     }
     MPN_CHECK_ARG(logits && labels && grad_logits && edge_graph, "tracking_loss_graphs: null tensor");
-    const size_t need = mpnhip_tracking_loss_graphs_workspace_bytes(n_steps, n_edges, n_graphs);
-    if (!workspace || workspace_bytes < need) {
-        set_error("tracking_loss_graphs: workspace %zu < %zu", workspace_bytes, need);
-        return MPNHIP_ERR_WORKSPACE;
-    }
-    const size_t base = mpnhip_tracking_loss_workspace_bytes(n_steps, n_edges);
-    float* partial = reinterpret_cast<float*>(static_cast<char*>(workspace) + 256);
-    int* counts = reinterpret_cast<int*>(static_cast<char*>(workspace) + base);
-    const int nblk = (int)((n_edges + 255) / 256);
-    MPN_HIP(hipMemsetAsync(counts, 0, (size_t)2 * n_graphs * sizeof(int), s));
-    hipLaunchKernelGGL(k_graph_counts, dim3(nblk), dim3(256), (size_t)2 * n_graphs * sizeof(int), s, labels, edge_graph, n_edges, n_graphs, counts);
+    const LossView v = loss_view(workspace, n_steps, n_edges, true, n_graphs);
+    MPN_CHECK_WORKSPACE("tracking_loss_graphs", workspace, workspace_bytes, v.bytes);
+    const int nblk = (int)blocks_for(n_edges);
+    MPN_HIP(hipMemsetAsync(v.counts, 0, (size_t)2 * n_graphs * sizeof(int), s));
+    hipLaunchKernelGGL(k_graph_counts, dim3(nblk), dim3(256), (size_t)2 * n_graphs * sizeof(int), s, labels, edge_graph, n_edges, n_graphs, v.counts);
     MPN_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_bce_graphs, dim3(nblk, n_steps), dim3(256), 0, s, logits, labels, edge_graph, n_edges, n_graphs, first_step, weight, counts,
-                       grad_logits, partial);
+    hipLaunchKernelGGL(k_bce_graphs, dim3(nblk, n_steps), dim3(256), 0, s, logits, labels, edge_graph, n_edges, n_graphs, first_step, weight, v.counts,
+                       grad_logits, v.partial);
     MPN_LAUNCH_CHECK();
     // (the per-edge terms were divided by their graph's edge count: E = 1 here; the mean over the graphs goes into the weight)
-    hipLaunchKernelGGL(k_loss_reduce, dim3(1), dim3(256), 0, s, partial, nblk, n_steps, (int64_t)1, weight / (float)n_graphs, loss_out);
+    hipLaunchKernelGGL(k_loss_reduce, dim3(1), dim3(256), 0, s, v.partial, nblk, n_steps, (int64_t)1, weight / (float)n_graphs, loss_out);
     MPN_LAUNCH_CHECK();
     return MPNHIP_OK;
 }
@@ -266,7 +267,7 @@ extern "C" int mpnhip_step_metrics(const void* graph_buf, int n_nodes, int64_t n
     MPN_CHECK_ARG(logits && labels, "step_metrics: null tensor");
     GraphView g;
     graph_layout(n_nodes, n_edges, &g, const_cast<void*>(graph_buf));
-    hipLaunchKernelGGL(k_confusion, dim3((unsigned)((n_edges + 255) / 256)), dim3(256), 0, s, logits, labels, n_edges, counts);
+    hipLaunchKernelGGL(k_confusion, dim3(blocks_for(n_edges)), dim3(256), 0, s, logits, labels, n_edges, counts);
     MPN_LAUNCH_CHECK();
     hipLaunchKernelGGL(k_flow_constraints, dim3((n_nodes + 255) / 256), dim3(256), 0, s, g, logits, counts);
     MPN_LAUNCH_CHECK();
@@ -315,7 +316,7 @@ extern "C" int mpnhip_adam_step_counted(float* params, const float* grads, float
     MPN_CHECK_ARG(params && grads && exp_avg && exp_avg_sq, "adam_step: null pointer");
     const float bc1 = 1.f - powf(beta1, (float)calls);
     const float bc2_sqrt = sqrtf(1.f - powf(beta2, (float)calls));
-    hipLaunchKernelGGL(mpnhip::k_adam, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, params, grads, exp_avg, exp_avg_sq, n,
+    hipLaunchKernelGGL(mpnhip::k_adam, dim3(blocks_for(n)), dim3(256), 0, stream, params, grads, exp_avg, exp_avg_sq, n,
                        lr, beta1, beta2, eps, weight_decay, bc1, bc2_sqrt, skip_flag, calls, skipped_calls);
     MPN_LAUNCH_CHECK();
     return MPNHIP_OK;

@@ -17,9 +17,7 @@
 // compare-and-swap, retrying from the value it lost to.  parent[v] <= v always holds, so there is no cycle and the root of a
 // component is its smallest node; one launch, no host loop, no flag read.  Then root[v] = find(v), the roots are flagged, an
 // exclusive scan ranks them, and label[v] = rank[root[v]] -- scipy's connected_components(directed=False) labels.
-#include "common.h"
-
-#include <rocprim/device/device_scan.hpp>
+#include "device_prims.h"
 
 namespace mpnhip {
 namespace {
@@ -194,14 +192,37 @@ __global__ void k_label_keep(const int64_t* __restrict__ labels, int64_t N, cons
     keep[v] = (l >= 0 && l < N && (int64_t)counts[l] >= min_len) ? 1 : 0;
 }
 
-static size_t scan_temp(int64_t n) {
-    size_t bytes = 0;
-    int* p = nullptr;
-    (void)rocprim::exclusive_scan(nullptr, bytes, p, p, 0, (size_t)(n > 0 ? n : 1), rocprim::plus<int>(), (hipStream_t)0);
-    return bytes;
+// project_round_count's workspace: the "has an outgoing / incoming edge" marks, one byte per node (zeroed as one block)
+struct RoundView { unsigned char* seen_out; unsigned char* seen_in; size_t bytes; };
+static RoundView round_view(void* workspace, int64_t n_nodes) {
+    if (n_nodes <= 0) return {};
+    Carver c(workspace);
+    RoundView v = {c.take<unsigned char>((size_t)n_nodes), c.take<unsigned char>((size_t)n_nodes), 0};
+    v.bytes = c.bytes();
+    return v;
 }
 
-static unsigned blocks_for(int64_t n) { return (unsigned)((n + 255) / 256); }
+// project_greedy's workspace: the arg-max keys and the in-counts as pass A leaves them, per node
+struct GreedyView { unsigned long long* best; int* in_now; size_t bytes; };
+static GreedyView greedy_view(void* workspace, int64_t n_nodes) {
+    if (n_nodes <= 0) return {};
+    Carver c(workspace);
+    GreedyView v = {c.take<unsigned long long>((size_t)n_nodes), c.take<int>((size_t)n_nodes), 0};
+    v.bytes = c.bytes();
+    return v;
+}
+
+// connected_components' workspace: parent, root, root flags, ranks per node, rocprim's scratch
+struct CcView { int* parent; int* root; int* is_root; int* rank; void* tmp; size_t tmp_bytes, bytes; };
+static CcView cc_view(void* workspace, int64_t n_nodes) {
+    if (n_nodes <= 0) return {};
+    Carver c(workspace);
+    const size_t n = (size_t)n_nodes;
+    CcView v = {c.take<int>(n), c.take<int>(n), c.take<int>(n), c.take<int>(n), nullptr, exclusive_scan_temp<int>(n_nodes), 0};
+    v.tmp = c.take<char>(v.tmp_bytes);
+    v.bytes = c.bytes() + 256;
+    return v;
+}
 
 static const int64_t MAX_IDS = 1LL << 30;   // node ids are kept as int32, edge ids as the low word of the arg-max key
 
@@ -211,8 +232,7 @@ static const int64_t MAX_IDS = 1LL << 30;   // node ids are kept as int32, edge 
 using namespace mpnhip;
 
 extern "C" size_t mpnhip_project_round_count_workspace_bytes(int64_t n_nodes) {
-    if (n_nodes <= 0) return 0;
-    return 2 * align_up((size_t)n_nodes, 256);
+    return round_view(nullptr, n_nodes).bytes;
 }
 
 extern "C" int mpnhip_project_round_count(const int64_t* edge_index, int64_t n_edges, int64_t n_nodes, const float* edge_preds,
@@ -224,35 +244,30 @@ extern "C" int mpnhip_project_round_count(const int64_t* edge_index, int64_t n_e
     MPN_CHECK_ARG(counters, "project_round_count: null counters");
     MPN_CHECK_ARG(n_nodes == 0 || (flow_out && flow_in), "project_round_count: null flow pointer");
     MPN_CHECK_ARG(n_edges == 0 || (edge_index && edge_preds && round_preds), "project_round_count: null pointer");
-    if (n_nodes > 0 && (!workspace || workspace_bytes < mpnhip_project_round_count_workspace_bytes(n_nodes))) {
-        set_error("project_round_count: workspace %zu < %zu", workspace_bytes, mpnhip_project_round_count_workspace_bytes(n_nodes));
-        return MPNHIP_ERR_WORKSPACE;
-    }
+    const RoundView v = round_view(workspace, n_nodes);
+    if (n_nodes > 0) MPN_CHECK_WORKSPACE("project_round_count", workspace, workspace_bytes, v.bytes);
     MPN_HIP(hipMemsetAsync(counters, 0, 8 * sizeof(int32_t), stream));
     // (every edge of a graph without nodes has ids out of range: counted in counters[3], nothing else touched)
-    unsigned char* seen_out = static_cast<unsigned char*>(workspace);
-    unsigned char* seen_in = n_nodes > 0 ? seen_out + align_up((size_t)n_nodes, 256) : nullptr;
     if (n_nodes > 0) {
         MPN_HIP(hipMemsetAsync(flow_out, 0, (size_t)n_nodes * 4, stream));
         MPN_HIP(hipMemsetAsync(flow_in, 0, (size_t)n_nodes * 4, stream));
-        MPN_HIP(hipMemsetAsync(workspace, 0, 2 * align_up((size_t)n_nodes, 256), stream));
+        MPN_HIP(hipMemsetAsync(workspace, 0, v.bytes, stream));
     }
     if (n_edges > 0) {
         hipLaunchKernelGGL(k_round_count, dim3(blocks_for(n_edges)), dim3(256), 0, stream, edge_index, n_edges, n_nodes, edge_preds,
-                           round_preds, flow_out, flow_in, seen_out, seen_in, counters);
+                           round_preds, flow_out, flow_in, v.seen_out, v.seen_in, counters);
         MPN_LAUNCH_CHECK();
     }
     if (n_nodes > 0 && n_edges > 0) {
         const unsigned blocks = blocks_for(n_nodes) < 1024 ? blocks_for(n_nodes) : 1024;
-        hipLaunchKernelGGL(k_constraint_counts, dim3(blocks), dim3(256), 0, stream, flow_out, flow_in, seen_out, seen_in, n_nodes, counters);
+        hipLaunchKernelGGL(k_constraint_counts, dim3(blocks), dim3(256), 0, stream, flow_out, flow_in, v.seen_out, v.seen_in, n_nodes, counters);
         MPN_LAUNCH_CHECK();
     }
     return MPNHIP_OK;
 }
 
 extern "C" size_t mpnhip_project_greedy_workspace_bytes(int64_t n_nodes) {
-    if (n_nodes <= 0) return 0;
-    return align_up((size_t)n_nodes * 8, 256) + align_up((size_t)n_nodes * 4, 256);
+    return greedy_view(nullptr, n_nodes).bytes;
 }
 
 extern "C" int mpnhip_project_greedy(const int64_t* edge_index, int64_t n_edges, int64_t n_nodes, const float* edge_preds,
@@ -262,27 +277,23 @@ extern "C" int mpnhip_project_greedy(const int64_t* edge_index, int64_t n_edges,
     MPN_CHECK_ARG(n_edges >= 0 && n_edges < MAX_IDS && n_nodes >= 0 && n_nodes < MAX_IDS, "project_greedy: bad sizes");
     if (n_edges == 0 || n_nodes == 0) return MPNHIP_OK;
     MPN_CHECK_ARG(edge_index && edge_preds && round_preds && flow_out && flow_in, "project_greedy: null pointer");
-    if (!workspace || workspace_bytes < mpnhip_project_greedy_workspace_bytes(n_nodes)) {
-        set_error("project_greedy: workspace %zu < %zu", workspace_bytes, mpnhip_project_greedy_workspace_bytes(n_nodes));
-        return MPNHIP_ERR_WORKSPACE;
-    }
-    auto* best = static_cast<unsigned long long*>(workspace);
-    int* in_now = reinterpret_cast<int*>(static_cast<char*>(workspace) + align_up((size_t)n_nodes * 8, 256));
+    const GreedyView v = greedy_view(workspace, n_nodes);
+    MPN_CHECK_WORKSPACE("project_greedy", workspace, workspace_bytes, v.bytes);
     const unsigned blocks = blocks_for(n_edges);
     // pass A: the out-constraints; the in-counts follow the edges it zeroes
-    MPN_HIP(hipMemsetAsync(best, 0, (size_t)n_nodes * 8, stream));
-    MPN_HIP(hipMemcpyAsync(in_now, flow_in, (size_t)n_nodes * 4, hipMemcpyDeviceToDevice, stream));
-    hipLaunchKernelGGL(k_argmax<0>, dim3(blocks), dim3(256), 0, stream, edge_index, n_edges, n_nodes, edge_preds, round_preds, flow_out, best);
+    MPN_HIP(hipMemsetAsync(v.best, 0, (size_t)n_nodes * 8, stream));
+    MPN_HIP(hipMemcpyAsync(v.in_now, flow_in, (size_t)n_nodes * 4, hipMemcpyDeviceToDevice, stream));
+    hipLaunchKernelGGL(k_argmax<0>, dim3(blocks), dim3(256), 0, stream, edge_index, n_edges, n_nodes, edge_preds, round_preds, flow_out, v.best);
     MPN_LAUNCH_CHECK();
     hipLaunchKernelGGL(k_keep_winner<0>, dim3(blocks), dim3(256), 0, stream, edge_index, n_edges, n_nodes, edge_preds, round_preds,
-                       flow_out, best, in_now);
+                       flow_out, v.best, v.in_now);
     MPN_LAUNCH_CHECK();
     // pass B: the in-constraints that are still violated
-    MPN_HIP(hipMemsetAsync(best, 0, (size_t)n_nodes * 8, stream));
-    hipLaunchKernelGGL(k_argmax<1>, dim3(blocks), dim3(256), 0, stream, edge_index, n_edges, n_nodes, edge_preds, round_preds, in_now, best);
+    MPN_HIP(hipMemsetAsync(v.best, 0, (size_t)n_nodes * 8, stream));
+    hipLaunchKernelGGL(k_argmax<1>, dim3(blocks), dim3(256), 0, stream, edge_index, n_edges, n_nodes, edge_preds, round_preds, v.in_now, v.best);
     MPN_LAUNCH_CHECK();
     hipLaunchKernelGGL(k_keep_winner<1>, dim3(blocks), dim3(256), 0, stream, edge_index, n_edges, n_nodes, edge_preds, round_preds,
-                       in_now, best, (int*)nullptr);
+                       v.in_now, v.best, (int*)nullptr);
     MPN_LAUNCH_CHECK();
     return MPNHIP_OK;
 }
@@ -306,9 +317,7 @@ extern "C" int mpnhip_project_violated_masks(const int64_t* edge_index, int64_t 
 }
 
 extern "C" size_t mpnhip_connected_components_workspace_bytes(int64_t n_nodes) {
-    if (n_nodes <= 0) return 0;
-    // parent, root, root flags, ranks, rocprim's scratch
-    return 4 * align_up((size_t)n_nodes * 4, 256) + align_up(scan_temp(n_nodes), 256) + 256;
+    return cc_view(nullptr, n_nodes).bytes;
 }
 
 extern "C" int mpnhip_connected_components(const int64_t* edge_index, int64_t n_edges, int64_t n_nodes, const float* edge_preds,
@@ -321,29 +330,19 @@ extern "C" int mpnhip_connected_components(const int64_t* edge_index, int64_t n_
         return MPNHIP_OK;
     }
     MPN_CHECK_ARG(labels && (n_edges == 0 || (edge_index && edge_preds)), "connected_components: null pointer");
-    if (!workspace || workspace_bytes < mpnhip_connected_components_workspace_bytes(n_nodes)) {
-        set_error("connected_components: workspace %zu < %zu", workspace_bytes, mpnhip_connected_components_workspace_bytes(n_nodes));
-        return MPNHIP_ERR_WORKSPACE;
-    }
-    char* w = static_cast<char*>(workspace);
-    auto take = [&](size_t bytes) { char* p = w; w += align_up(bytes, 256); return p; };
-    int* parent = reinterpret_cast<int*>(take((size_t)n_nodes * 4));
-    int* root = reinterpret_cast<int*>(take((size_t)n_nodes * 4));
-    int* is_root = reinterpret_cast<int*>(take((size_t)n_nodes * 4));
-    int* rank = reinterpret_cast<int*>(take((size_t)n_nodes * 4));
-    void* tmp = w;
+    CcView v = cc_view(workspace, n_nodes);
+    MPN_CHECK_WORKSPACE("connected_components", workspace, workspace_bytes, v.bytes);
     const unsigned nb = blocks_for(n_nodes);
-    hipLaunchKernelGGL(k_cc_init, dim3(nb), dim3(256), 0, stream, parent, n_nodes);
+    hipLaunchKernelGGL(k_cc_init, dim3(nb), dim3(256), 0, stream, v.parent, n_nodes);
     MPN_LAUNCH_CHECK();
     if (n_edges > 0) {
-        hipLaunchKernelGGL(k_cc_union, dim3(blocks_for(n_edges)), dim3(256), 0, stream, edge_index, n_edges, n_nodes, edge_preds, parent);
+        hipLaunchKernelGGL(k_cc_union, dim3(blocks_for(n_edges)), dim3(256), 0, stream, edge_index, n_edges, n_nodes, edge_preds, v.parent);
         MPN_LAUNCH_CHECK();
     }
-    hipLaunchKernelGGL(k_cc_roots, dim3(nb), dim3(256), 0, stream, parent, n_nodes, root, is_root);
+    hipLaunchKernelGGL(k_cc_roots, dim3(nb), dim3(256), 0, stream, v.parent, n_nodes, v.root, v.is_root);
     MPN_LAUNCH_CHECK();
-    size_t tmp_bytes = scan_temp(n_nodes);
-    MPN_HIP(rocprim::exclusive_scan(tmp, tmp_bytes, is_root, rank, 0, (size_t)n_nodes, rocprim::plus<int>(), stream));
-    hipLaunchKernelGGL(k_cc_labels, dim3(nb), dim3(256), 0, stream, root, is_root, rank, n_nodes, labels, n_components);
+    MPN_HIP(rocprim::exclusive_scan(v.tmp, v.tmp_bytes, v.is_root, v.rank, 0, (size_t)n_nodes, rocprim::plus<int>(), stream));
+    hipLaunchKernelGGL(k_cc_labels, dim3(nb), dim3(256), 0, stream, v.root, v.is_root, v.rank, n_nodes, labels, n_components);
     MPN_LAUNCH_CHECK();
     return MPNHIP_OK;
 }

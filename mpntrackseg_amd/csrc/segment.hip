@@ -9,9 +9,7 @@
 // bit-reproducible and independent of the launch geometry.
 #include <cstring>
 
-#include "common.h"
-
-#include <rocprim/device/device_radix_sort.hpp>
+#include "device_prims.h"
 
 namespace mpnhip {
 
@@ -732,12 +730,16 @@ __global__ void k_lower_bound_u32(const unsigned* __restrict__ skeys, int64_t M,
     ptr[k] = (int)lo;
 }
 
-static size_t seg_sort_temp(int64_t M) {
-    size_t bytes = 0;
-    unsigned* k = nullptr;
-    int* v = nullptr;
-    (void)rocprim::radix_sort_pairs(nullptr, bytes, k, k, v, v, (size_t)(M > 0 ? M : 1), 0, 32, (hipStream_t)0);
-    return bytes;
+// mpnhip_segment_reduce's workspace: the sort's keys and values, the sorted row list [max(m, 1)] each, the CSR pointers, rocprim's scratch
+struct SegSortView { unsigned* keys_in; unsigned* keys_out; int* vals_in; int* list; int* ptr; void* tmp; size_t tmp_bytes; size_t bytes; };
+static SegSortView seg_sort_view(void* workspace, int64_t m, int x_size) {
+    Carver c(workspace);
+    const size_t e = (size_t)(m > 0 ? m : 1);
+    SegSortView v = {c.take<unsigned>(e), c.take<unsigned>(e), c.take<int>(e), c.take<int>(e), c.take<int>((size_t)x_size + 2), nullptr,
+                     sort_pairs_temp<unsigned>(m), 0};
+    v.tmp = c.take<char>(v.tmp_bytes);
+    v.bytes = c.bytes() + 256;
+    return v;
 }
 
 }  // namespace mpnhip
@@ -745,8 +747,7 @@ static size_t seg_sort_temp(int64_t M) {
 using namespace mpnhip;
 
 extern "C" size_t mpnhip_segment_reduce_workspace_bytes(int64_t m, int x_size) {
-    size_t e = align_up((size_t)(m > 0 ? m : 1) * 4, 256);
-    return 4 * e + align_up(((size_t)x_size + 2) * 4, 256) + align_up(seg_sort_temp(m), 256) + 256;
+    return seg_sort_view(nullptr, m, x_size).bytes;
 }
 
 extern "C" int mpnhip_segment_reduce(const float* src, const int64_t* row, int64_t m, int dim, int x_size, int agg,
@@ -762,29 +763,16 @@ extern "C" int mpnhip_segment_reduce(const float* src, const int64_t* row, int64
         return MPNHIP_OK;
     }
     MPN_CHECK_ARG(src && row, "segment_reduce: null input");
-    if (!workspace || workspace_bytes < mpnhip_segment_reduce_workspace_bytes(m, x_size)) {
-        set_error("segment_reduce: workspace %zu < %zu", workspace_bytes, mpnhip_segment_reduce_workspace_bytes(m, x_size));
-        return MPNHIP_ERR_WORKSPACE;
-    }
-    char* ws = static_cast<char*>(workspace);
-    size_t e = align_up((size_t)m * 4, 256);
-    unsigned* keys_in = reinterpret_cast<unsigned*>(ws);
-    unsigned* keys_out = reinterpret_cast<unsigned*>(ws + e);
-    int* vals_in = reinterpret_cast<int*>(ws + 2 * e);
-    int* list = reinterpret_cast<int*>(ws + 3 * e);
-    int* ptr = reinterpret_cast<int*>(ws + 4 * e);
-    size_t poff = 4 * e + align_up(((size_t)x_size + 2) * 4, 256);
-    void* tmp = ws + poff;
-    size_t tmp_bytes = workspace_bytes - poff;
+    SegSortView v = seg_sort_view(workspace, m, x_size);
+    MPN_CHECK_WORKSPACE("segment_reduce", workspace, workspace_bytes, v.bytes);
     const int T = 256;
-    hipLaunchKernelGGL(k_row_keys, dim3((unsigned)((m + T - 1) / T)), dim3(T), 0, stream, row, m, x_size, keys_in, vals_in);
+    hipLaunchKernelGGL(k_row_keys, dim3(blocks_for(m)), dim3(T), 0, stream, row, m, x_size, v.keys_in, v.vals_in);
     MPN_LAUNCH_CHECK();
-    int bits = 1;
-    while (bits < 32 && ((unsigned)x_size >> bits)) ++bits;
-    MPN_HIP(rocprim::radix_sort_pairs(tmp, tmp_bytes, keys_in, keys_out, vals_in, list, (size_t)m, 0, bits, stream));
-    hipLaunchKernelGGL(k_lower_bound_u32, dim3((x_size + 1 + T) / T), dim3(T), 0, stream, keys_out, m, x_size, ptr);
+    // (parked rows carry the key x_size)
+    MPN_HIP(rocprim::radix_sort_pairs(v.tmp, v.tmp_bytes, v.keys_in, v.keys_out, v.vals_in, v.list, (size_t)m, 0, key_bits((unsigned)x_size), stream));
+    hipLaunchKernelGGL(k_lower_bound_u32, dim3((x_size + 1 + T) / T), dim3(T), 0, stream, v.keys_out, m, x_size, v.ptr);
     MPN_LAUNCH_CHECK();
-    return segment_reduce_csr(src, dim, list, ptr, x_size, dim, agg, out, dim, argmax, 0, stream);
+    return segment_reduce_csr(src, dim, v.list, v.ptr, x_size, dim, agg, out, dim, argmax, 0, stream);
 }
 
 extern "C" int mpnhip_time_aggregate(const void* graph_buf, int n_nodes, int64_t n_edges, const float* src, int dim,

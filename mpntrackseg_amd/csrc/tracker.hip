@@ -6,9 +6,8 @@
 // position inside its row's run -- and the transpose needed by the reciprocal test is a binary search in the entries
 // sorted by (row, col).  Ties in distance resolve by column index (what a stable argsort gives); the reference's
 // torch.argsort leaves them unspecified.
-#include "common.h"
+#include "device_prims.h"
 
-#include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_select.hpp>
 #include <rocprim/iterator/counting_iterator.hpp>
 
@@ -137,13 +136,6 @@ __global__ void k_average(const float* __restrict__ preds, const float* __restri
     out[i] = v != v ? 0.f : v;  // final_edge_preds[isnan] = 0  (mpn_tracker.py:197)
 }
 
-static size_t sort64_temp(int64_t M) {
-    size_t bytes = 0;
-    unsigned long long* k = nullptr;
-    int* v = nullptr;
-    (void)rocprim::radix_sort_pairs(nullptr, bytes, k, k, v, v, (size_t)(M > 0 ? M : 1), 0, 64, (hipStream_t)0);
-    return bytes;
-}
 static size_t select_temp(int64_t n) {
     size_t bytes = 0;
     int* out = nullptr;
@@ -152,14 +144,43 @@ static size_t select_temp(int64_t n) {
     return bytes;
 }
 
+
+// knn_mask's workspace over M + 1 entries: the two sorts' unsorted and sorted keys, their values, the rank flags, rocprim's scratch
+struct KnnView {
+    unsigned long long *k_a, *rc_keys, *k_b, *rd_keys;
+    int *v_a, *rc_vals, *rd_vals;
+    unsigned char* in_k;
+    void* tmp;
+    size_t tmp_bytes, bytes;
+};
+static KnnView knn_view(void* workspace, int64_t n_edges, int symmetric_edges) {
+    Carver c(workspace);
+    const size_t m1 = (size_t)(symmetric_edges ? n_edges : 2 * n_edges) + 1;
+    KnnView v = {c.take<unsigned long long>(m1), c.take<unsigned long long>(m1), c.take<unsigned long long>(m1), c.take<unsigned long long>(m1),
+                 c.take<int>(m1), c.take<int>(m1), c.take<int>(m1), c.take<unsigned char>(m1), nullptr,
+                 sort_pairs_temp<unsigned long long>((int64_t)m1), 0};
+    v.tmp = c.take<char>(v.tmp_bytes);
+    v.bytes = c.bytes() + 256;
+    return v;
+}
+
+// compact's workspace: rocprim's scratch alone
+struct CompactView { void* tmp; size_t tmp_bytes, bytes; };
+static CompactView compact_view(void* workspace, int64_t n) {
+    Carver c(workspace);
+    CompactView v = {nullptr, select_temp(n), 0};
+    v.tmp = c.take<char>(v.tmp_bytes);
+    v.bytes = c.bytes() + 256;
+    return v;
+}
+
 }  // namespace
 }  // namespace mpnhip
 
 using namespace mpnhip;
 
 extern "C" size_t mpnhip_knn_mask_workspace_bytes(int64_t n_edges, int symmetric_edges) {
-    const size_t M = (size_t)(symmetric_edges ? n_edges : 2 * n_edges) + 1;
-    return 4 * align_up(M * 8, 256) + 3 * align_up(M * 4, 256) + align_up(M, 256) + align_up(sort64_temp((int64_t)M), 256) + 256;
+    return knn_view(nullptr, n_edges, symmetric_edges).bytes;
 }
 
 extern "C" int mpnhip_knn_mask(const float* pwise_dist, const int64_t* edge_ixs, int n_nodes, int64_t n_edges, int top_k_nns,
@@ -170,36 +191,22 @@ extern "C" int mpnhip_knn_mask(const float* pwise_dist, const int64_t* edge_ixs,
     MPN_CHECK_ARG(top_k_nns >= 0, "knn_mask: negative top_k_nns");
     if (n_edges == 0) return MPNHIP_OK;
     MPN_CHECK_ARG(pwise_dist && edge_ixs && pruned_mask, "knn_mask: null pointer");
-    if (!workspace || workspace_bytes < mpnhip_knn_mask_workspace_bytes(n_edges, symmetric_edges)) {
-        set_error("knn_mask: workspace %zu < %zu", workspace_bytes, mpnhip_knn_mask_workspace_bytes(n_edges, symmetric_edges));
-        return MPNHIP_ERR_WORKSPACE;
-    }
+    KnnView v = knn_view(workspace, n_edges, symmetric_edges);
+    MPN_CHECK_WORKSPACE("knn_mask", workspace, workspace_bytes, v.bytes);
     const int64_t E = n_edges, M = symmetric_edges ? E : 2 * E;
-    char* w = static_cast<char*>(workspace);
-    auto take = [&](size_t bytes) { char* p = w; w += align_up(bytes, 256); return p; };
-    auto* k_a = reinterpret_cast<unsigned long long*>(take((size_t)(M + 1) * 8));
-    auto* rc_keys = reinterpret_cast<unsigned long long*>(take((size_t)(M + 1) * 8));
-    auto* k_b = reinterpret_cast<unsigned long long*>(take((size_t)(M + 1) * 8));
-    auto* rd_keys = reinterpret_cast<unsigned long long*>(take((size_t)(M + 1) * 8));
-    int* v_a = reinterpret_cast<int*>(take((size_t)(M + 1) * 4));
-    int* rc_vals = reinterpret_cast<int*>(take((size_t)(M + 1) * 4));
-    int* rd_vals = reinterpret_cast<int*>(take((size_t)(M + 1) * 4));
-    auto* in_k = reinterpret_cast<unsigned char*>(take((size_t)(M + 1)));
-    void* tmp = w;
-    size_t tmp_bytes = sort64_temp(M + 1);
-    const unsigned blocks = (unsigned)((M + 255) / 256);
+    const unsigned blocks = blocks_for(M);
     // (1) entries sorted by (row, col): the transpose lookup table, and the tie order of (2)
-    hipLaunchKernelGGL(k_knn_keys_rc, dim3(blocks), dim3(256), 0, stream, edge_ixs, E, M, k_a, v_a);
+    hipLaunchKernelGGL(k_knn_keys_rc, dim3(blocks), dim3(256), 0, stream, edge_ixs, E, M, v.k_a, v.v_a);
     MPN_LAUNCH_CHECK();
-    MPN_HIP(rocprim::radix_sort_pairs(tmp, tmp_bytes, k_a, rc_keys, v_a, rc_vals, (size_t)M, 0, 64, stream));
+    MPN_HIP(rocprim::radix_sort_pairs(v.tmp, v.tmp_bytes, v.k_a, v.rc_keys, v.v_a, v.rc_vals, (size_t)M, 0, 64, stream));
     // (2) stable sort of that order by (row, distance): position inside the row's run = the entry's rank
-    hipLaunchKernelGGL(k_knn_keys_rd, dim3(blocks), dim3(256), 0, stream, edge_ixs, pwise_dist, E, M, rc_vals, k_b);
+    hipLaunchKernelGGL(k_knn_keys_rd, dim3(blocks), dim3(256), 0, stream, edge_ixs, pwise_dist, E, M, v.rc_vals, v.k_b);
     MPN_LAUNCH_CHECK();
-    MPN_HIP(rocprim::radix_sort_pairs(tmp, tmp_bytes, k_b, rd_keys, rc_vals, rd_vals, (size_t)M, 0, 64, stream));
-    hipLaunchKernelGGL(k_knn_rank, dim3(blocks), dim3(256), 0, stream, rd_keys, rd_vals, M, top_k_nns, in_k);
+    MPN_HIP(rocprim::radix_sort_pairs(v.tmp, v.tmp_bytes, v.k_b, v.rd_keys, v.rc_vals, v.rd_vals, (size_t)M, 0, 64, stream));
+    hipLaunchKernelGGL(k_knn_rank, dim3(blocks), dim3(256), 0, stream, v.rd_keys, v.rd_vals, M, top_k_nns, v.in_k);
     MPN_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_knn_mask, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, stream, edge_ixs, E, M, symmetric_edges,
-                       reciprocal_k_nns, rc_keys, rc_vals, in_k, pruned_mask);
+    hipLaunchKernelGGL(k_knn_mask, dim3(blocks_for(E)), dim3(256), 0, stream, edge_ixs, E, M, symmetric_edges,
+                       reciprocal_k_nns, v.rc_keys, v.rc_vals, v.in_k, pruned_mask);
     MPN_LAUNCH_CHECK();
     return MPNHIP_OK;
 }
@@ -210,13 +217,13 @@ extern "C" int mpnhip_window_flags(const int64_t* edge_index, int64_t n_edges, i
     MPN_CHECK_ARG(n_edges >= 0, "window_flags: bad sizes");
     if (n_edges == 0) return MPNHIP_OK;
     MPN_CHECK_ARG(edge_index && flags, "window_flags: null pointer");
-    hipLaunchKernelGGL(k_window_flags, dim3((unsigned)((n_edges + 255) / 256)), dim3(256), 0, stream, edge_index, n_edges,
+    hipLaunchKernelGGL(k_window_flags, dim3(blocks_for(n_edges)), dim3(256), 0, stream, edge_index, n_edges,
                        node_begin, node_end, flags);
     MPN_LAUNCH_CHECK();
     return MPNHIP_OK;
 }
 
-extern "C" size_t mpnhip_compact_workspace_bytes(int64_t n) { return align_up(select_temp(n), 256) + 256; }
+extern "C" size_t mpnhip_compact_workspace_bytes(int64_t n) { return compact_view(nullptr, n).bytes; }
 
 extern "C" int mpnhip_compact(const unsigned char* flags, int64_t n, int32_t* ids, int32_t* count, void* workspace,
                               size_t workspace_bytes, void* stream_) {
@@ -228,12 +235,9 @@ extern "C" int mpnhip_compact(const unsigned char* flags, int64_t n, int32_t* id
         return MPNHIP_OK;
     }
     MPN_CHECK_ARG(flags && ids, "compact: null pointer");
-    if (!workspace || workspace_bytes < mpnhip_compact_workspace_bytes(n)) {
-        set_error("compact: workspace %zu < %zu", workspace_bytes, mpnhip_compact_workspace_bytes(n));
-        return MPNHIP_ERR_WORKSPACE;
-    }
-    size_t tmp_bytes = select_temp(n);
-    MPN_HIP(rocprim::select(workspace, tmp_bytes, rocprim::counting_iterator<int>(0), ids, count, (size_t)n, FlagSet{flags}, stream));
+    CompactView v = compact_view(workspace, n);
+    MPN_CHECK_WORKSPACE("compact", workspace, workspace_bytes, v.bytes);
+    MPN_HIP(rocprim::select(v.tmp, v.tmp_bytes, rocprim::counting_iterator<int>(0), ids, count, (size_t)n, FlagSet{flags}, stream));
     return MPNHIP_OK;
 }
 
@@ -242,7 +246,7 @@ extern "C" int mpnhip_gather_rows(const float* src, int64_t ld, const int32_t* i
     MPN_CHECK_ARG(n >= 0 && dim >= 0 && ld >= dim, "gather_rows: bad sizes");
     if (n == 0 || dim == 0) return MPNHIP_OK;
     MPN_CHECK_ARG(src && ids && out, "gather_rows: null pointer");
-    hipLaunchKernelGGL(k_gather_rows, dim3((unsigned)((n * dim + 255) / 256)), dim3(256), 0, stream, src, ld, ids, n, dim, out);
+    hipLaunchKernelGGL(k_gather_rows, dim3(blocks_for(n * dim)), dim3(256), 0, stream, src, ld, ids, n, dim, out);
     MPN_LAUNCH_CHECK();
     return MPNHIP_OK;
 }
@@ -253,7 +257,7 @@ extern "C" int mpnhip_gather_edges(const int64_t* edge_index, int64_t n_edges, c
     MPN_CHECK_ARG(n >= 0 && n_edges >= 0, "gather_edges: bad sizes");
     if (n == 0) return MPNHIP_OK;
     MPN_CHECK_ARG(edge_index && ids && out, "gather_edges: null pointer");
-    hipLaunchKernelGGL(k_gather_edges, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, edge_index, n_edges, ids, n, node_begin,
+    hipLaunchKernelGGL(k_gather_edges, dim3(blocks_for(n)), dim3(256), 0, stream, edge_index, n_edges, ids, n, node_begin,
                        out);
     MPN_LAUNCH_CHECK();
     return MPNHIP_OK;
@@ -268,12 +272,12 @@ extern "C" int mpnhip_window_accumulate(const float* logits, const int32_t* kept
     MPN_CHECK_ARG(window_ids && overall_edge_preds && overall_num_preds, "window_accumulate: null pointer");
     MPN_CHECK_ARG(n_kept == 0 || logits, "window_accumulate: null logits");
     if (n_kept > 0) {
-        hipLaunchKernelGGL(k_accumulate, dim3((unsigned)((n_kept + 255) / 256)), dim3(256), 0, stream, logits, kept_ids, n_kept,
+        hipLaunchKernelGGL(k_accumulate, dim3(blocks_for(n_kept)), dim3(256), 0, stream, logits, kept_ids, n_kept,
                            window_ids, set_pruned_edges_to_inactive ? 0 : 1, overall_edge_preds, overall_num_preds);
         MPN_LAUNCH_CHECK();
     }
     if (set_pruned_edges_to_inactive) {  // every edge of the window counts as predicted (pruned ones as 0)
-        hipLaunchKernelGGL(k_count_window, dim3((unsigned)((n_window + 255) / 256)), dim3(256), 0, stream, window_ids, n_window,
+        hipLaunchKernelGGL(k_count_window, dim3(blocks_for(n_window)), dim3(256), 0, stream, window_ids, n_window,
                            overall_num_preds);
         MPN_LAUNCH_CHECK();
     }
@@ -285,7 +289,7 @@ extern "C" int mpnhip_average_preds(const float* overall_preds, const float* ove
     MPN_CHECK_ARG(n >= 0, "average_preds: bad size");
     if (n == 0) return MPNHIP_OK;
     MPN_CHECK_ARG(overall_preds && overall_num && final_preds, "average_preds: null pointer");
-    hipLaunchKernelGGL(k_average, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, overall_preds, overall_num, n, final_preds);
+    hipLaunchKernelGGL(k_average, dim3(blocks_for(n)), dim3(256), 0, stream, overall_preds, overall_num, n, final_preds);
     MPN_LAUNCH_CHECK();
     return MPNHIP_OK;
 }

@@ -9,10 +9,7 @@
 // run of two exactly the reference's (a + b) / 2.
 // The node-mask accumulators are plain streams over contiguous rows (16-byte accesses, grid-stride, one launch per
 // window: windows overlap in nodes, the stream orders them).
-#include "common.h"
-
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
+#include "device_prims.h"
 
 namespace mpnhip {
 namespace {
@@ -114,52 +111,23 @@ __global__ __launch_bounds__(256) void k_node_average(const float* __restrict__ 
     }
 }
 
-static size_t sort_temp(int64_t n) {
-    size_t bytes = 0;
-    unsigned long long* k = nullptr;
-    int* v = nullptr;
-    (void)rocprim::radix_sort_pairs(nullptr, bytes, k, k, v, v, (size_t)(n > 0 ? n : 1), 0, 64, (hipStream_t)0);
-    return bytes;
-}
-static size_t scan_temp(int64_t n) {
-    size_t bytes = 0;
-    int* p = nullptr;
-    (void)rocprim::inclusive_scan(nullptr, bytes, p, p, (size_t)(n > 0 ? n : 1), rocprim::plus<int>(), (hipStream_t)0);
-    return bytes;
-}
-
-// what mpnhip_undirected_merge_sort leaves at the head of the workspace for mpnhip_undirected_merge_fill
+// The merge workspace.  Its head -- sorted keys, sorted edge ids, run numbers -- is what mpnhip_undirected_merge_sort leaves for
+// mpnhip_undirected_merge_fill; behind it the sort's own: unsorted keys and ids, head flags, rocprim's scratch.
 struct MergeView {
-    unsigned long long* skeys;
-    int* svals;
-    int* run_no;
-    char* rest;
+    unsigned long long* skeys; int* svals; int* run_no;
+    unsigned long long* keys; int* vals; int* heads;
+    void* tmp;
+    size_t tmp_bytes, bytes;
 };
-static MergeView merge_view(void* workspace, int64_t E) {
-    char* w = static_cast<char*>(workspace);
-    MergeView v;
-    v.skeys = reinterpret_cast<unsigned long long*>(w); w += align_up((size_t)E * 8, 256);
-    v.svals = reinterpret_cast<int*>(w); w += align_up((size_t)E * 4, 256);
-    v.run_no = reinterpret_cast<int*>(w); w += align_up((size_t)E * 4, 256);
-    v.rest = w;
+static MergeView merge_view(void* workspace, int64_t n_edges) {
+    Carver c(workspace);
+    const size_t E = (size_t)n_edges, a = sort_pairs_temp<unsigned long long>(n_edges), b = inclusive_scan_temp<int>(n_edges);
+    MergeView v = {c.take<unsigned long long>(E), c.take<int>(E), c.take<int>(E), c.take<unsigned long long>(E), c.take<int>(E), c.take<int>(E),
+                   nullptr, a > b ? a : b, 0};
+    v.tmp = c.take<char>(v.tmp_bytes);
+    v.bytes = c.bytes() + 256;
     return v;
 }
-
-// blocks of 256 threads for a grid-stride stream over `items` work items: enough to fill the chip, never more than the work
-static unsigned stream_blocks(int64_t items) {
-    static int cus = 0;
-    if (cus == 0) {
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0)
-            cus = n;
-        else
-            cus = 256;
-    }
-    const int64_t need = (items + 255) / 256, cap = (int64_t)cus * 8;
-    return (unsigned)(need < 1 ? 1 : (need < cap ? need : cap));
-}
-
-static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 }  // namespace
 }  // namespace mpnhip
@@ -168,10 +136,7 @@ using namespace mpnhip;
 
 extern "C" size_t mpnhip_undirected_merge_workspace_bytes(int64_t n_edges) {
     if (n_edges <= 0) return 0;
-    const size_t E = (size_t)n_edges;
-    const size_t tmp = sort_temp(n_edges) > scan_temp(n_edges) ? sort_temp(n_edges) : scan_temp(n_edges);
-    // sorted keys / ids / run numbers (kept for the fill), unsorted keys / ids / head flags, rocprim's scratch
-    return 2 * align_up(E * 8, 256) + 4 * align_up(E * 4, 256) + align_up(tmp, 256) + 256;
+    return merge_view(nullptr, n_edges).bytes;
 }
 
 extern "C" int mpnhip_undirected_merge_sort(const int64_t* edge_index, int64_t n_edges, int64_t n_nodes, int32_t* inverse,
@@ -184,33 +149,18 @@ extern "C" int mpnhip_undirected_merge_sort(const int64_t* edge_index, int64_t n
         return MPNHIP_OK;
     }
     MPN_CHECK_ARG(edge_index && inverse, "undirected_merge_sort: null pointer");
-    if (!workspace || workspace_bytes < mpnhip_undirected_merge_workspace_bytes(n_edges)) {
-        set_error("undirected_merge_sort: workspace %zu < %zu", workspace_bytes, mpnhip_undirected_merge_workspace_bytes(n_edges));
-        return MPNHIP_ERR_WORKSPACE;
-    }
     const int64_t E = n_edges;
     MergeView v = merge_view(workspace, E);
-    char* w = v.rest;
-    auto take = [&](size_t bytes) { char* p = w; w += align_up(bytes, 256); return p; };
-    auto* keys = reinterpret_cast<unsigned long long*>(take((size_t)E * 8));
-    int* vals = reinterpret_cast<int*>(take((size_t)E * 4));
-    int* heads = reinterpret_cast<int*>(take((size_t)E * 4));
-    void* tmp = w;
+    MPN_CHECK_WORKSPACE("undirected_merge_sort", workspace, workspace_bytes, v.bytes);
     // the key's low word holds max(r, c) < n_nodes and its high word min(r, c): only the bits a node id needs are sorted
-    unsigned id_bits = 32;
-    if (n_nodes > 0) {
-        id_bits = 1;
-        while (id_bits < 32 && (1LL << id_bits) < n_nodes) ++id_bits;
-    }
-    const unsigned blocks = (unsigned)((E + 255) / 256);
-    hipLaunchKernelGGL(k_pair_keys, dim3(blocks), dim3(256), 0, stream, edge_index, E, keys, vals);
+    const unsigned id_bits = n_nodes > 0 ? key_bits((uint64_t)n_nodes - 1) : 32;
+    const unsigned blocks = blocks_for(E);
+    hipLaunchKernelGGL(k_pair_keys, dim3(blocks), dim3(256), 0, stream, edge_index, E, v.keys, v.vals);
     MPN_LAUNCH_CHECK();
-    size_t tmp_bytes = sort_temp(E);
-    MPN_HIP(rocprim::radix_sort_pairs(tmp, tmp_bytes, keys, v.skeys, vals, v.svals, (size_t)E, 0, 32 + id_bits, stream));
-    hipLaunchKernelGGL(k_run_heads, dim3(blocks), dim3(256), 0, stream, v.skeys, E, heads);
+    MPN_HIP(rocprim::radix_sort_pairs(v.tmp, v.tmp_bytes, v.keys, v.skeys, v.vals, v.svals, (size_t)E, 0, 32 + id_bits, stream));
+    hipLaunchKernelGGL(k_run_heads, dim3(blocks), dim3(256), 0, stream, v.skeys, E, v.heads);
     MPN_LAUNCH_CHECK();
-    tmp_bytes = scan_temp(E);
-    MPN_HIP(rocprim::inclusive_scan(tmp, tmp_bytes, heads, v.run_no, (size_t)E, rocprim::plus<int>(), stream));
+    MPN_HIP(rocprim::inclusive_scan(v.tmp, v.tmp_bytes, v.heads, v.run_no, (size_t)E, rocprim::plus<int>(), stream));
     hipLaunchKernelGGL(k_inverse, dim3(blocks), dim3(256), 0, stream, v.svals, v.run_no, E, inverse, n_unique);
     MPN_LAUNCH_CHECK();
     return MPNHIP_OK;
@@ -223,12 +173,9 @@ extern "C" int mpnhip_undirected_merge_fill(int64_t n_edges, int64_t n_unique, c
     if (n_edges == 0 || n_unique == 0) return MPNHIP_OK;
     MPN_CHECK_ARG((attr == nullptr) == (attr_u == nullptr), "undirected_merge_fill: attr and attr_u go together");
     if (!edge_index_u && !attr) return MPNHIP_OK;
-    if (!workspace || workspace_bytes < mpnhip_undirected_merge_workspace_bytes(n_edges)) {
-        set_error("undirected_merge_fill: workspace %zu < %zu", workspace_bytes, mpnhip_undirected_merge_workspace_bytes(n_edges));
-        return MPNHIP_ERR_WORKSPACE;
-    }
-    MergeView v = merge_view(const_cast<void*>(workspace), n_edges);
-    hipLaunchKernelGGL(k_merge_fill, dim3((unsigned)((n_edges + 255) / 256)), dim3(256), 0, stream, v.skeys, v.svals, v.run_no, n_edges,
+    const MergeView v = merge_view(const_cast<void*>(workspace), n_edges);
+    MPN_CHECK_WORKSPACE("undirected_merge_fill", workspace, workspace_bytes, v.bytes);
+    hipLaunchKernelGGL(k_merge_fill, dim3(blocks_for(n_edges)), dim3(256), 0, stream, v.skeys, v.svals, v.run_no, n_edges,
                        n_unique, edge_index_u, attr, attr_u);
     MPN_LAUNCH_CHECK();
     return MPNHIP_OK;
@@ -239,7 +186,7 @@ extern "C" int mpnhip_threshold_flags(const float* preds, int64_t n, float thres
     MPN_CHECK_ARG(n >= 0, "threshold_flags: bad size");
     if (n == 0) return MPNHIP_OK;
     MPN_CHECK_ARG(preds && flags, "threshold_flags: null pointer");
-    hipLaunchKernelGGL(k_threshold, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, preds, n, threshold, flags);
+    hipLaunchKernelGGL(k_threshold, dim3(blocks_for(n)), dim3(256), 0, stream, preds, n, threshold, flags);
     MPN_LAUNCH_CHECK();
     return MPNHIP_OK;
 }

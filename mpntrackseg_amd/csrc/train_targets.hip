@@ -193,7 +193,26 @@ void mask_plan(int64_t units, int* cpr, int* chunk) {
     *chunk = (int)((units + *cpr - 1) / *cpr);
 }
 
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+// edge_labels' workspace ('closest' mode): fut[N] then past[N] as ONE block of 2 max(N, 1) ints
+struct LabelsView { int* fut; int* past; size_t bytes; };
+LabelsView labels_view(void* workspace, int64_t n_nodes) {
+    Carver c(workspace);
+    int* fut = c.take<int>((size_t)2 * (size_t)(n_nodes > 0 ? n_nodes : 1));
+    return {fut, fut ? fut + n_nodes : nullptr, c.bytes()};
+}
+
+// mask_loss' workspace: the graphs' valid-row counts, then the blocks' partial sums [steps][blocks] (sized for the scalar
+// path's plan: never fewer blocks than the vector path's)
+struct MaskLossView { int* counts; float* partial; size_t bytes; };
+MaskLossView mask_loss_view(void* workspace, int n_steps, int64_t n_nodes, int64_t row_floats, int n_graphs) {
+    int cpr, chunk;
+    mask_plan(row_floats > 0 ? row_floats : 1, &cpr, &chunk);
+    const size_t nblk = (size_t)(n_nodes > 0 ? n_nodes : 1) * (size_t)cpr;
+    Carver c(workspace);
+    MaskLossView v = {c.take<int>((size_t)(n_graphs > 0 ? n_graphs : 1)), c.take<float>((size_t)(n_steps > 0 ? n_steps : 1) * nblk), 0};
+    v.bytes = c.bytes();
+    return v;
+}
 
 }  // namespace
 }  // namespace mpnhip
@@ -201,7 +220,7 @@ bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 
 using namespace mpnhip;
 
 extern "C" size_t mpnhip_edge_labels_workspace_bytes(int64_t n_nodes) {
-    return align_up((size_t)2 * (size_t)(n_nodes > 0 ? n_nodes : 1) * sizeof(int), 256);
+    return labels_view(nullptr, n_nodes).bytes;
 }
 
 extern "C" int mpnhip_edge_labels(const int64_t* edge_index, int64_t n_edges, const int64_t* ids, int64_t n_nodes, int mode, float* labels,
@@ -216,36 +235,26 @@ extern "C" int mpnhip_edge_labels(const int64_t* edge_index, int64_t n_edges, co
     }
     MPN_CHECK_ARG(edge_index && labels && status, "edge_labels: null tensor");
     MPN_CHECK_ARG(ids || n_nodes == 0, "edge_labels: null ids");
-    const unsigned nblk = (unsigned)((n_edges + 255) / 256);
-    int* fut = nullptr;   // 'all' reads neither
-    int* past = nullptr;
+    const unsigned nblk = blocks_for(n_edges);
+    LabelsView v = {};   // 'all' reads neither
     if (mode == MPNHIP_LABELS_CLOSEST && n_nodes > 0) {
-        const size_t need = mpnhip_edge_labels_workspace_bytes(n_nodes);
-        if (!workspace || workspace_bytes < need) {
-            set_error("edge_labels: workspace %zu < %zu", workspace_bytes, need);
-            return MPNHIP_ERR_WORKSPACE;
-        }
-        fut = static_cast<int*>(workspace);
-        past = fut + n_nodes;
+        v = labels_view(workspace, n_nodes);
+        MPN_CHECK_WORKSPACE("edge_labels", workspace, workspace_bytes, v.bytes);
     }
     MPN_HIP(hipMemsetAsync(status, 0, sizeof(int32_t), s));
     if (mode == MPNHIP_LABELS_CLOSEST && n_nodes > 0) {
-        hipLaunchKernelGGL(k_labels_init, dim3((unsigned)((n_nodes + 255) / 256)), dim3(256), 0, s, fut, past, n_nodes);
+        hipLaunchKernelGGL(k_labels_init, dim3(blocks_for(n_nodes)), dim3(256), 0, s, v.fut, v.past, n_nodes);
         MPN_LAUNCH_CHECK();
-        hipLaunchKernelGGL(k_labels_closest, dim3(nblk), dim3(256), 0, s, edge_index, n_edges, ids, n_nodes, fut, past);
+        hipLaunchKernelGGL(k_labels_closest, dim3(nblk), dim3(256), 0, s, edge_index, n_edges, ids, n_nodes, v.fut, v.past);
         MPN_LAUNCH_CHECK();
     }
-    hipLaunchKernelGGL(k_labels_write, dim3(nblk), dim3(256), 0, s, edge_index, n_edges, ids, n_nodes, mode, fut, past, labels, status);
+    hipLaunchKernelGGL(k_labels_write, dim3(nblk), dim3(256), 0, s, edge_index, n_edges, ids, n_nodes, mode, v.fut, v.past, labels, status);
     MPN_LAUNCH_CHECK();
     return MPNHIP_OK;
 }
 
 extern "C" size_t mpnhip_mask_loss_workspace_bytes(int n_steps, int64_t n_nodes, int64_t row_floats, int n_graphs) {
-    int cpr, chunk;
-    mask_plan(row_floats > 0 ? row_floats : 1, &cpr, &chunk);   // (the scalar path's plan: never fewer blocks than the vector path's)
-    const size_t nblk = (size_t)(n_nodes > 0 ? n_nodes : 1) * (size_t)cpr;
-    return align_up((size_t)(n_graphs > 0 ? n_graphs : 1) * sizeof(int), 256) +
-           align_up((size_t)(n_steps > 0 ? n_steps : 1) * nblk * sizeof(float), 256);
+    return mask_loss_view(nullptr, n_steps, n_nodes, row_floats, n_graphs).bytes;
 }
 
 extern "C" int mpnhip_mask_loss(const float* const* preds, int n_steps, const float* labels, const uint8_t* valid, const int32_t* node_graph,
@@ -273,28 +282,23 @@ extern "C" int mpnhip_mask_loss(const float* const* preds, int n_steps, const fl
     mask_plan(vec ? row_floats / 4 : row_floats, &cpr, &chunk);
     MPN_CHECK_ARG(n_nodes <= (int64_t)INT_MAX / cpr, "mask_loss: %lld rows of %lld floats exceed one launch", (long long)n_nodes,
                   (long long)row_floats);
-    const size_t need = mpnhip_mask_loss_workspace_bytes(n_steps, n_nodes, row_floats, n_graphs);
-    if (!workspace || workspace_bytes < need) {
-        set_error("mask_loss: workspace %zu < %zu", workspace_bytes, need);
-        return MPNHIP_ERR_WORKSPACE;
-    }
-    int* counts = static_cast<int*>(workspace);
-    float* partial = reinterpret_cast<float*>(static_cast<char*>(workspace) + align_up((size_t)n_graphs * sizeof(int), 256));
+    const MaskLossView v = mask_loss_view(workspace, n_steps, n_nodes, row_floats, n_graphs);
+    MPN_CHECK_WORKSPACE("mask_loss", workspace, workspace_bytes, v.bytes);
     const int64_t nblk = n_nodes * cpr;
-    MPN_HIP(hipMemsetAsync(counts, 0, (size_t)n_graphs * sizeof(int), s));
-    hipLaunchKernelGGL(k_mask_counts, dim3((unsigned)((n_nodes + 255) / 256)), dim3(256), (size_t)n_graphs * sizeof(int), s, valid,
-                       node_graph, n_nodes, n_graphs, counts);
+    MPN_HIP(hipMemsetAsync(v.counts, 0, (size_t)n_graphs * sizeof(int), s));
+    hipLaunchKernelGGL(k_mask_counts, dim3(blocks_for(n_nodes)), dim3(256), (size_t)n_graphs * sizeof(int), s, valid,
+                       node_graph, n_nodes, n_graphs, v.counts);
     MPN_LAUNCH_CHECK();
     if (vec)
-        hipLaunchKernelGGL(k_mask_bce<4>, dim3((unsigned)nblk), dim3(256), 0, s, p, n_steps, labels, valid, node_graph, n_graphs, counts,
-                           row_floats, cpr, chunk, weight, partial);
+        hipLaunchKernelGGL(k_mask_bce<4>, dim3((unsigned)nblk), dim3(256), 0, s, p, n_steps, labels, valid, node_graph, n_graphs, v.counts,
+                           row_floats, cpr, chunk, weight, v.partial);
     else
-        hipLaunchKernelGGL(k_mask_bce<1>, dim3((unsigned)nblk), dim3(256), 0, s, p, n_steps, labels, valid, node_graph, n_graphs, counts,
-                           row_floats, cpr, chunk, weight, partial);
+        hipLaunchKernelGGL(k_mask_bce<1>, dim3((unsigned)nblk), dim3(256), 0, s, p, n_steps, labels, valid, node_graph, n_graphs, v.counts,
+                           row_floats, cpr, chunk, weight, v.partial);
     MPN_LAUNCH_CHECK();
     // (the block sums were divided by their graph's valid rows; the mean over a row's elements and over the graphs goes here)
     const double scale = (double)weight / ((double)row_floats * (double)n_graphs);
-    hipLaunchKernelGGL(k_mask_loss_reduce, dim3(1), dim3(256), 0, s, partial, nblk, n_steps, scale, loss_out);
+    hipLaunchKernelGGL(k_mask_loss_reduce, dim3(1), dim3(256), 0, s, v.partial, nblk, n_steps, scale, loss_out);
     MPN_LAUNCH_CHECK();
     return MPNHIP_OK;
 }
