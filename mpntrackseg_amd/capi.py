@@ -326,6 +326,34 @@ def fill_mlp(dst, linears, with_grads=False, keep=None):
     return dst
 
 
+def fill_mlp_dims(dst, in_dim, dims, pointer=None):
+    """Fill an ``Mlp`` struct with dims only; ``pointer``: an address for every weight, bias and gradient field."""
+    dst.n_layers, dst.in_dim = len(dims), int(in_dim)
+    for i, w in enumerate(dims):
+        dst.out_dims[i] = int(w)
+        dst.weight[i] = dst.bias[i] = dst.grad_weight[i] = dst.grad_bias[i] = pointer
+    return dst
+
+
+def dims_model(p, precision="fp32", pointer=None):
+    """``Model`` of the ``graph_model_params`` dict ``p`` with dims only -- all the size queries read; ``pointer``: an address to put
+    into every weight, bias and gradient field (argument checks that must pass without the pointers ever being followed)."""
+    enc, cls = p["encoder_feats_dict"], p["classifier_feats_dict"]
+    dn, de = enc["node_out_dim"], enc["edge_out_dim"]
+    nf, ef = (2 if p["reattach_initial_nodes"] else 1), (2 if p["reattach_initial_edges"] else 1)
+    m = Model()
+    m.dn, m.de, m.reattach_nodes, m.reattach_edges = dn, de, nf - 1, ef - 1
+    m.agg, m.num_enc_steps, m.precision = AGG_CODE[p["node_agg_fn"]], p["num_enc_steps"], PRECISIONS[precision]
+    fill_mlp_dims(m.enc_node, enc["node_in_dim"], list(enc["node_dims"]) + [dn], pointer)
+    fill_mlp_dims(m.enc_edge, enc["edge_in_dim"], list(enc["edge_dims"]) + [de], pointer)
+    fill_mlp_dims(m.edge, nf * 2 * dn + ef * de, p["edge_model_feats_dict"]["dims"], pointer)
+    fill_mlp_dims(m.flow_in, nf * dn + de, p["node_model_feats_dict"]["dims"], pointer)
+    fill_mlp_dims(m.flow_out, nf * dn + de, p["node_model_feats_dict"]["dims"], pointer)
+    fill_mlp_dims(m.node, 2 * dn, [dn], pointer)
+    fill_mlp_dims(m.classifier, cls["edge_in_dim"], list(cls["edge_dims"]) + [cls["edge_out_dim"]], pointer)
+    return m
+
+
 class _StatusRing:
     """Pinned host slots for the asynchronous read-back of graph-prep error flags (a pinned allocation per graph would cost
     more than the prep).  A slot that was recycled before its graph looked at it falls back to the synchronous status()."""

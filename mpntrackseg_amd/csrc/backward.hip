@@ -311,7 +311,7 @@ static int enc_maxw(const mpnhip_model& m, const Dims& d) {
     return w;
 }
 
-// slab floats of the weight-gradient products of layers first..n-1 of an MLP (layer 0's k_in given)
+// slab floats of the weight-gradient products of an MLP's layers (layer 0's k_in given: the share of the input it is taken over)
 static size_t mlp_slab(const mpnhip_mlp& m, int k_in0, int64_t rows, int nbatch) {
     size_t mx = 0;
     for (int i = 0; i < m.n_layers; ++i) {
@@ -321,166 +321,157 @@ static size_t mlp_slab(const mpnhip_mlp& m, int k_in0, int64_t rows, int nbatch)
     return mx;
 }
 
+// slab floats of one row-panel product inside a batch: its fp32-row form or, where the operands may be bf16 rows, the larger of the two
+static size_t wp_slab_either(int n_out, int k_in, int64_t rows, int nb, bool ranged, bool rows16) {
+    if (rows <= 0) return 0;
+    const size_t f32 = wp_slab_floats(n_out, k_in, rows, nb, ranged, true), f16 = rows16 ? wp_slab_floats(n_out, k_in, rows, nb, ranged, true, true) : 0;
+    return f32 > f16 ? f32 : f16;
+}
+
+// The slabs of the weight-gradient products, in three parts.  Each lists exactly the products mpnhip_backward launches in that form
+// (the slab size depends on the shape through tn_plan / the row-panel chunking); node16: the node-level products run over bf16 rows.
+// 1. one product alone on a stream: floats of the LARGEST one (BwdPlan::slab and slab_side hold two direction groups of it)
+static size_t slab_per_group(const mpnhip_model& m, const Dims& d, int64_t N, int64_t E, int L, bool b16, bool node16) {
+    size_t sl = 0;
+    auto upd = [&](size_t f) { sl = f > sl ? f : sl; };
+    upd(mlp_slab(m.enc_node, m.enc_node.in_dim, N, 1));
+    upd(mlp_slab(m.enc_edge, m.enc_edge.in_dim, E, 1));
+    upd(mlp_slab(m.edge, d.ke, E, L));
+    for (int nb = 1; nb <= L; ++nb) upd(tn_slab_floats(d.he, d.de, E, nb));   // (the e0-hoisted forms of the edge layer-0 product)
+    upd(mlp_slab(m.flow_in, d.de, E, L));
+    upd(mlp_slab(m.classifier, d.de, E, L));
+    upd(tn_slab_floats(d.dn, 2 * d.dn, N, L));
+    upd(tn_slab_floats(d.pw, d.kx, N, L));
+    // the same products in the row-panel form (MPNHIP_PREC_FP32_SPLIT); a group's share of the slab is half of it
+    auto updw = [&](int n_out, int k_in, int64_t rows, bool rows16) { if (rows > 0) upd((wp_slab_floats(n_out, k_in, rows, 1, false, false, rows16) + 1) / 2); };
+    for (int i = 0; i < m.enc_node.n_layers; ++i) updw(m.enc_node.out_dims[i], layer_in(m.enc_node, i), N, false);
+    for (int i = 0; i < m.enc_edge.n_layers; ++i) updw(m.enc_edge.out_dims[i], layer_in(m.enc_edge, i), E, false);
+    updw(d.he, d.de, E, false);
+    if (b16) updw(d.he, d.de, E, true);      // (the hoisted e0 share over bf16 rows)
+    updw(d.pw, d.dn, N, false);
+    if (node16) updw(d.pw, d.dn, N, true);   // (the hoisted x0 share over bf16 rows)
+    for (int i = 0; i < m.classifier.n_layers; ++i) updw(m.classifier.out_dims[i], layer_in(m.classifier, i), E, false);
+    return sl;
+}
+
+// 2. all products of a group of nb steps in one batch (mp_weight_grads): every job has its own slabs, so their SUM
+static size_t slab_batched(const mpnhip_model& m, const Dims& d, int64_t N, int64_t E, int nb, bool b16) {
+    size_t t = 0;
+    auto wp = [&](int n_out, int k_in, int64_t rows, bool ranged) { return wp_slab_either(n_out, k_in, rows, nb, ranged, b16); };
+    t += wp(d.dn, 2 * d.dn, N, false);
+    for (int i = 1; i < m.flow_in.n_layers; ++i) t += 2 * wp(m.flow_in.out_dims[i], layer_in(m.flow_in, i), E, true);   // (flow_in and flow_out)
+    t += 2 * wp(d.hn, d.de, E, true);
+    for (int i = 0; i < m.classifier.n_layers; ++i) t += wp(m.classifier.out_dims[i], layer_in(m.classifier, i), E, false);
+    for (int i = 1; i < m.edge.n_layers; ++i) t += wp(m.edge.out_dims[i], layer_in(m.edge, i), E, false);
+    // (a product that runs in one of two forms -- the first-layer inputs whole or with the re-attached share hoisted -- reserves
+    // the larger of the two: a narrower k_in can mean MORE row chunks, i.e. more slabs)
+    auto larger = [](size_t x, size_t y) { return x > y ? x : y; };
+    t += larger(wp(d.he, d.ke, E, false), wp(d.he, d.de, E, false));
+    t += larger(wp(d.pw, d.kx, N, false), wp(d.pw, d.dn, N, false));
+    return t;
+}
+
+// 3. the tail batch: hoisted shares + encoder layers, their sum
+static size_t slab_tail(const mpnhip_model& m, const Dims& d, int64_t N, int64_t E, bool b16, bool node16) {
+    size_t t = 0;
+    t += wp_slab_either(d.pw, d.dn, N, 1, false, node16);
+    t += wp_slab_either(d.he, d.de, E, 1, false, b16);   // (bf16-operand training keeps S = sum_s dZ1_s as bf16 rows: the bf16-row kernels' chunking)
+    for (int i = 0; i < m.enc_node.n_layers; ++i) t += wp_slab_either(m.enc_node.out_dims[i], layer_in(m.enc_node, i), N, 1, false, node16);
+    for (int i = 0; i < m.enc_edge.n_layers; ++i) t += wp_slab_either(m.enc_edge.out_dims[i], layer_in(m.enc_edge, i), E, 1, false, false);
+    return t;
+}
+
 static size_t plan_backward(const mpnhip_model& m, const Dims& d, int64_t N, int64_t E, void* base, BwdPlan* out) {
-    Arena a = {static_cast<char*>(base), 0};
+    Carver a(base);
     BwdPlan p = {};
     const size_t L = d.L > 0 ? d.L : 1;
     // (what every backward starts from as zeros lies side by side -- dX[0] | dX0 | dE0 | gWnode: ONE fill instead of four, ~12 us of
     // the 0.5 ms step of a KITTIMOTS-size graph)
-    p.dX[0] = a.f((size_t)N * d.dn);
-    p.dX0 = a.f((size_t)N * d.dn);
-    p.dE0 = a.f((size_t)E * d.de);
-    p.gWnode = a.f((size_t)d.pw * d.kx);
-    p.zero_end = a.f(0);
-    p.dX[1] = a.f((size_t)N * d.dn);
-    p.dXh = a.f((size_t)N * d.dn);
-    p.dPsum = a.f((size_t)N * d.pw);
-    p.dZ1sum = a.f((size_t)E * d.he);
-    p.dAGG = a.f((size_t)N * 2 * d.dn);
+    p.dX[0] = a.take<float>((size_t)N * d.dn);
+    p.dX0 = a.take<float>((size_t)N * d.dn);
+    p.dE0 = a.take<float>((size_t)E * d.de);
+    p.gWnode = a.take<float>((size_t)d.pw * d.kx);
+    p.zero_end = a.take<float>(0);
+    p.dX[1] = a.take<float>((size_t)N * d.dn);
+    p.dXh = a.take<float>((size_t)N * d.dn);
+    p.dPsum = a.take<float>((size_t)N * d.pw);
+    p.dZ1sum = a.take<float>((size_t)E * d.he);
+    p.dAGG = a.take<float>((size_t)N * 2 * d.dn);
     {
         size_t a1 = (size_t)E * d.ke, a2 = (size_t)N * d.kx;
-        p.dCat = a.f(a1 > a2 ? a1 : a2);
+        p.dCat = a.take<float>(a1 > a2 ? a1 : a2);
     }
-    p.dZn = a.f(L * N * d.dn);
-    p.dP = a.f(L * N * d.pw);
+    p.dZn = a.take<float>(L * N * d.dn);
+    p.dP = a.take<float>(L * N * d.pw);
     p.b16 = chain_bf16_train_ok(m, d);
     p.dP16 = p.dPsum16 = p.dZn16 = p.AGG16 = p.enc16 = nullptr;
     p.enc16_elems = 0;
     const bool node16 = p.b16 && d.pw % 8 == 0 && d.dn % 8 == 0;   // (not `p.dP16 != nullptr`: a size query plans without a base)
     if (node16) {
-        p.dP16 = reinterpret_cast<unsigned short*>(a.f((L * N * d.pw + 1) / 2));
-        p.dPsum16 = reinterpret_cast<unsigned short*>(a.f(((size_t)N * d.pw + 1) / 2));
-        p.dZn16 = reinterpret_cast<unsigned short*>(a.f((L * N * d.dn + 1) / 2));
-        p.AGG16 = reinterpret_cast<unsigned short*>(a.f((L * N * 2 * d.dn + 1) / 2));
+        p.dP16 = a.take<unsigned short>(L * N * d.pw);
+        p.dPsum16 = a.take<unsigned short>((size_t)N * d.pw);
+        p.dZn16 = a.take<unsigned short>(L * N * d.dn);
+        p.AGG16 = a.take<unsigned short>(L * N * 2 * d.dn);
         size_t w = 0;
-        for (int i = 0; i < m.enc_node.n_layers; ++i) w += (size_t)m.enc_node.out_dims[i] + (i == 0 ? m.enc_node.in_dim : m.enc_node.out_dims[i - 1]);
+        for (int i = 0; i < m.enc_node.n_layers; ++i) w += (size_t)m.enc_node.out_dims[i] + layer_in(m.enc_node, i);
         p.enc16_elems = (size_t)N * w;
-        p.enc16 = reinterpret_cast<unsigned short*>(a.f((p.enc16_elems + 1) / 2));
+        p.enc16 = a.take<unsigned short>(p.enc16_elems);
     }
-    auto dzb = [&](int width) { return a.f(p.b16 ? (L * E * width + 1) / 2 : L * E * width); };
+    // (b16: the dZ blocks are bf16 rows)
+    auto dzb = [&](int width) { return a.take_as<float>(L * E * width, p.b16 ? sizeof(unsigned short) : sizeof(float)); };
     for (int i = 0; i < m.flow_in.n_layers; ++i) p.dZfl[i] = dzb(m.flow_in.out_dims[i]);
     for (int i = 0; i < m.edge.n_layers; ++i) p.dZed[i] = dzb(m.edge.out_dims[i]);
     for (int i = 0; i + 1 < m.classifier.n_layers; ++i) p.dZcl[i] = dzb(m.classifier.out_dims[i]);
     p.dEpp[0] = p.dEpp[1] = nullptr;
     p.cb16_img = nullptr;
     if (p.b16) {
-        for (int i = 0; i < 2; ++i) p.dEpp[i] = a.f((size_t)E * d.de);
-        const size_t bytes = chain_bf16_bwd_image_bytes(d.he, d.de, d.hn, d.dn, m.classifier.out_dims[0], &p.cb16_off_cls, &p.cb16_off_flow[0],
-                                                        &p.cb16_off_flow[1]);
-        p.cb16_img = reinterpret_cast<char*>(a.f(bytes / 4));
+        for (int i = 0; i < 2; ++i) p.dEpp[i] = a.take<float>((size_t)E * d.de);
+        p.cb16_img = a.take<char>(chain_bf16_bwd_image_bytes(d.he, d.de, d.hn, d.dn, m.classifier.out_dims[0], &p.cb16_off_cls, &p.cb16_off_flow[0],
+                                                             &p.cb16_off_flow[1]));
     }
     int mw = enc_maxw(m, d);
     if (mw < 52) mw = 52;   // (the fused reference edge encoder keeps dz2 | dz1 | dz0 side by side in T[0])
-    for (int i = 0; i < 3; ++i) p.T[i] = a.f((size_t)E * mw);
-    for (int i = 0; i < 3; ++i) p.Tn[i] = a.f((size_t)N * mw);
+    for (int i = 0; i < 3; ++i) p.T[i] = a.take<float>((size_t)E * mw);
+    for (int i = 0; i < 3; ++i) p.Tn[i] = a.take<float>((size_t)N * mw);
     p.t_width = (int)mw;
     {
         const size_t HE = pad32(d.he), DE = pad32(d.de), HN = pad32(d.hn), DN = pad32(d.dn);
         // (sized for the split images, 3/2 of the fp32 ones)
-        for (int q = 0; q < 2; ++q) { p.wf2p[q] = a.f(DN * HN * 3 / 2); p.wfep[q] = a.f(HN * DE * 3 / 2); }
-        p.wc1p = a.f(32 * DE * 3 / 2);
-        p.w2p = a.f(DE * HE * 3 / 2);
-        p.w1ep = a.f(HE * 2 * DE * 3 / 2);
+        for (int q = 0; q < 2; ++q) { p.wf2p[q] = a.take<float>(DN * HN * 3 / 2); p.wfep[q] = a.take<float>(HN * DE * 3 / 2); }
+        p.wc1p = a.take<float>(32 * DE * 3 / 2);
+        p.w2p = a.take<float>(DE * HE * 3 / 2);
+        p.w1ep = a.take<float>(HE * 2 * DE * 3 / 2);
     }
     p.ncb_img = nullptr;
     if (node_chain_bwd_supported(d.dn, d.pw, d.kx) && m.node.n_layers == 1 && m.precision == MPNHIP_PREC_FP32_SPLIT)
-        p.ncb_img = reinterpret_cast<unsigned short*>(a.f((node_chain_bwd_image_shorts(d.dn, d.pw, nullptr) + 1) / 2));
+        p.ncb_img = a.take<unsigned short>(node_chain_bwd_image_shorts(d.dn, d.pw, nullptr));
     {   // MPNHIP_PREC_BF16: transposition scratch of the activation-gradient products (two direction groups of the largest weight)
         size_t mx = (size_t)d.pw * d.kx;
         const mpnhip_mlp* all[] = {&m.enc_node, &m.enc_edge, &m.edge, &m.flow_in, &m.flow_out, &m.node, &m.classifier};
         for (const mpnhip_mlp* q : all)
             for (int i = 0; i < q->n_layers; ++i) {
-                const size_t w = (size_t)q->out_dims[i] * (i == 0 ? q->in_dim : q->out_dims[i - 1]);
+                const size_t w = (size_t)q->out_dims[i] * layer_in(*q, i);
                 mx = w > mx ? w : mx;
             }
         p.wt_scratch_floats = m.precision == MPNHIP_PREC_BF16 ? 2 * mx : 0;
-        p.wt_scratch = a.f(p.wt_scratch_floats);
+        p.wt_scratch = a.take<float>(p.wt_scratch_floats);
         p.wt_keep_floats[0] = m.precision == MPNHIP_PREC_BF16 && m.node.n_layers >= 1 ? (size_t)d.dn * m.node.in_dim : 0;
         p.wt_keep_floats[1] = m.precision == MPNHIP_PREC_BF16 ? (size_t)d.pw * d.dn : 0;
-        for (int i = 0; i < 2; ++i) p.wt_keep[i] = a.f(p.wt_keep_floats[i]);
-        for (int i = 0; i < 2; ++i) p.wt_keep16[i] = reinterpret_cast<unsigned short*>(a.f((p.wt_keep_floats[i] + 1) / 2));
+        for (int i = 0; i < 2; ++i) p.wt_keep[i] = a.take<float>(p.wt_keep_floats[i]);
+        for (int i = 0; i < 2; ++i) p.wt_keep16[i] = a.take<unsigned short>(p.wt_keep_floats[i]);
     }
-    size_t sl = 0;
-    auto upd = [&](size_t f) { sl = f > sl ? f : sl; };
-    // exactly the products mpnhip_backward launches (the slab size depends on the shape through tn_plan)
-    upd(mlp_slab(m.enc_node, m.enc_node.in_dim, N, 1));
-    upd(mlp_slab(m.enc_edge, m.enc_edge.in_dim, E, 1));
-    upd(mlp_slab(m.edge, d.ke, E, (int)L));
-    for (int nb = 1; nb <= (int)L; ++nb) upd(tn_slab_floats(d.he, d.de, E, nb));   // (the e0-hoisted forms of the edge layer-0 product)
-    upd(mlp_slab(m.flow_in, d.de, E, (int)L));
-    upd(mlp_slab(m.classifier, d.de, E, (int)L));
-    upd(tn_slab_floats(d.dn, 2 * d.dn, N, (int)L));
-    upd(tn_slab_floats(d.pw, d.kx, N, (int)L));
-    // the same products in the row-panel form (MPNHIP_PREC_FP32_SPLIT): alone on the caller's stream ...
-    auto updw = [&](int n_out, int k_in, int64_t rows, int nb) { if (rows > 0) upd((wp_slab_floats(n_out, k_in, rows, nb, false, false) + 1) / 2); };
-    for (int i = 0; i < m.enc_node.n_layers; ++i) updw(m.enc_node.out_dims[i], i == 0 ? m.enc_node.in_dim : m.enc_node.out_dims[i - 1], N, 1);
-    for (int i = 0; i < m.enc_edge.n_layers; ++i) updw(m.enc_edge.out_dims[i], i == 0 ? m.enc_edge.in_dim : m.enc_edge.out_dims[i - 1], E, 1);
-    updw(d.he, d.de, E, 1);
-    if (p.b16 && E > 0) upd((wp_slab_floats(d.he, d.de, E, 1, false, false, true) + 1) / 2);   // (the hoisted e0 share over bf16 rows)
-    updw(d.pw, d.dn, N, 1);
-    if (node16 && N > 0) upd((wp_slab_floats(d.pw, d.dn, N, 1, false, false, true) + 1) / 2);   // (the hoisted x0 share over bf16 rows)
-    for (int i = 0; i < m.classifier.n_layers; ++i) updw(m.classifier.out_dims[i], i == 0 ? d.de : m.classifier.out_dims[i - 1], E, 1);
-    p.slab_floats_per_group = sl;
-    p.slab = a.f(2 * sl);
-    p.slab_side = a.f(2 * sl);
-    // ... and all products of a group of nb steps in one batch (mp_weight_grads): every job has its own slabs
-    size_t wpmax = 0;
+    p.slab_floats_per_group = slab_per_group(m, d, N, E, (int)L, p.b16, node16);
+    p.slab = a.take<float>(2 * p.slab_floats_per_group);
+    p.slab_side = a.take<float>(2 * p.slab_floats_per_group);
+    p.slab_wp_floats = 0;
     for (int nb = 1; nb <= (int)L; ++nb) {
-        size_t t = 0;
-        auto addw = [&](int n_out, int k_in, int64_t rows, bool ranged) {
-            if (rows <= 0) return;
-            const size_t f32 = wp_slab_floats(n_out, k_in, rows, nb, ranged, true), f16 = p.b16 ? wp_slab_floats(n_out, k_in, rows, nb, ranged, true, true) : 0;
-            t += f32 > f16 ? f32 : f16;
-        };
-        addw(d.dn, 2 * d.dn, N, false);
-        for (int i = 1; i < m.flow_in.n_layers; ++i) { addw(m.flow_in.out_dims[i], m.flow_in.out_dims[i - 1], E, true); addw(m.flow_in.out_dims[i], m.flow_in.out_dims[i - 1], E, true); }
-        addw(d.hn, d.de, E, true); addw(d.hn, d.de, E, true);
-        for (int i = 0; i < m.classifier.n_layers; ++i) addw(m.classifier.out_dims[i], i == 0 ? d.de : m.classifier.out_dims[i - 1], E, false);
-        for (int i = 1; i < m.edge.n_layers; ++i) addw(m.edge.out_dims[i], m.edge.out_dims[i - 1], E, false);
-        // (a product that runs in one of two forms -- the first-layer inputs whole or with the re-attached share hoisted -- reserves
-        // the larger of the two: a narrower k_in can mean MORE row chunks, i.e. more slabs)
-        auto addw2 = [&](int n_out, int k_a, int k_b, int64_t rows) {
-            const size_t before = t;
-            addw(n_out, k_a, rows, false);
-            const size_t fa = t - before;
-            t = before;
-            addw(n_out, k_b, rows, false);
-            if (t - before < fa) t = before + fa;
-        };
-        addw2(d.he, d.ke, d.de, E);
-        addw2(d.pw, d.kx, d.dn, N);
-        wpmax = t > wpmax ? t : wpmax;
+        const size_t t = slab_batched(m, d, N, E, nb, p.b16);
+        p.slab_wp_floats = t > p.slab_wp_floats ? t : p.slab_wp_floats;
     }
-    p.slab_wp_floats = wpmax;
-    p.slab_wp = a.f(wpmax);
-    {   // the tail batch: hoisted shares + encoder layers
-        size_t t = 0;
-        auto addt = [&](int n_out, int k_in, int64_t rows) { if (rows > 0) t += wp_slab_floats(n_out, k_in, rows, 1, false, true); };
-        if (node16 && N > 0) {
-            const size_t f32 = wp_slab_floats(d.pw, d.dn, N, 1, false, true), f16 = wp_slab_floats(d.pw, d.dn, N, 1, false, true, true);
-            t += f32 > f16 ? f32 : f16;
-        } else {
-            addt(d.pw, d.dn, N);
-        }
-        addt(d.he, d.de, E);
-        if (p.b16 && E > 0) {   // (bf16-operand training keeps S = sum_s dZ1_s as bf16 rows: the bf16-row kernels' chunking)
-            const size_t f32 = wp_slab_floats(d.he, d.de, E, 1, false, true), f16 = wp_slab_floats(d.he, d.de, E, 1, false, true, true);
-            if (f16 > f32) t += f16 - f32;
-        }
-        for (int i = 0; i < m.enc_node.n_layers; ++i) {
-            const int n_out = m.enc_node.out_dims[i], k_in = i == 0 ? m.enc_node.in_dim : m.enc_node.out_dims[i - 1];
-            if (node16 && N > 0) {
-                const size_t f32 = wp_slab_floats(n_out, k_in, N, 1, false, true), f16 = wp_slab_floats(n_out, k_in, N, 1, false, true, true);
-                t += f32 > f16 ? f32 : f16;
-            } else {
-                addt(n_out, k_in, N);
-            }
-        }
-        for (int i = 0; i < m.enc_edge.n_layers; ++i) addt(m.enc_edge.out_dims[i], i == 0 ? m.enc_edge.in_dim : m.enc_edge.out_dims[i - 1], E);
-        p.slab_tail_floats = t;
-        p.slab_tail = a.f(t);
-    }
-    p.total = a.off;
+    p.slab_wp = a.take<float>(p.slab_wp_floats);
+    p.slab_tail_floats = slab_tail(m, d, N, E, p.b16, node16);
+    p.slab_tail = a.take<float>(p.slab_tail_floats);
+    p.total = a.bytes();
     if (out) *out = p;
     return p.total;
 }
@@ -826,17 +817,11 @@ extern "C" int mpnhip_backward_flags(const mpnhip_model* model, const void* grap
                 MPN_CHECK_ARG(q->grad_weight[i] && q->grad_bias[i], "backward: null gradient buffer");
     }
     FwdPlan f;
-    size_t fneed = plan_forward(m, d, N, E, 1, fwd_workspace, &f);
-    if (!fwd_workspace || fwd_workspace_bytes < fneed) {
-        set_error("backward: forward workspace %zu < %zu (must be the save_for_backward buffer)", fwd_workspace_bytes, fneed);
-        return MPNHIP_ERR_WORKSPACE;
-    }
+    const size_t fneed = plan_forward(m, d, N, E, 1, fwd_workspace, &f);
+    MPN_CHECK_WORKSPACE_MSG("backward: forward workspace", " (must be the save_for_backward buffer)", fwd_workspace, fwd_workspace_bytes, fneed);
     BwdPlan p;
-    size_t need = plan_backward(m, d, N, E, bwd_workspace, &p);
-    if (!bwd_workspace || bwd_workspace_bytes < need) {
-        set_error("backward: workspace %zu < %zu", bwd_workspace_bytes, need);
-        return MPNHIP_ERR_WORKSPACE;
-    }
+    const size_t need = plan_backward(m, d, N, E, bwd_workspace, &p);
+    MPN_CHECK_WORKSPACE("backward", bwd_workspace, bwd_workspace_bytes, need);
     BwdCtx c = {&p, m.precision == MPNHIP_PREC_FP32_SPLIT || m.precision == MPNHIP_PREC_FP32_WGSPLIT || m.precision == MPNHIP_PREC_BF16,
                 m.precision == MPNHIP_PREC_BF16, {}};
     for (int i = 0; i < 2; ++i) c.wt_keep[i] = {p.wt_keep_floats[i] ? p.wt_keep[i] : nullptr, p.wt_keep_floats[i], false, p.wt_keep_floats[i] ? p.wt_keep16[i] : nullptr};
@@ -935,7 +920,7 @@ extern "C" int mpnhip_backward_flags(const mpnhip_model* model, const void* grap
     auto classifier_chain = [&](float* const* HC, float* const* dzc, const float* dlog, float* dEdst, const float* mask) -> int {
         if (E == 0) return MPNHIP_OK;
         for (int i = nc - 1; i >= 0; --i) {
-            const int n_out = cls.out_dims[i], k_in = i == 0 ? de : cls.out_dims[i - 1];
+            const int n_out = cls.out_dims[i], k_in = layer_in(cls, i);
             const bool top = i == nc - 1;  // dZ of the last layer is grad_logits, [E, 1] in ORIGINAL order
             const float* A = top ? dlog : dzc[i];
             const float* Wq[2] = {cls.weight[i], nullptr};
@@ -1040,7 +1025,7 @@ extern "C" int mpnhip_backward_flags(const mpnhip_model* model, const void* grap
                                                        {m.flow_in.grad_weight[0] + kx, m.flow_in.grad_bias[0], dir_rr[1]}}}, st));
             // classifier: dZ of the last layer is grad_logits ([L, E], original order -> perm)
             for (int i = nc - 1; i >= 0; --i) {
-                const int n_out = cls.out_dims[i], k_in = i == 0 ? de : cls.out_dims[i - 1];
+                const int n_out = cls.out_dims[i], k_in = layer_in(cls, i);
                 const bool top = i == nc - 1;
                 Operand dz = top ? Operand{grad_logits + zb * E, 1, (int64_t)E} : Operand{p.dZcl[i] + zb * E * n_out, n_out, (int64_t)E * n_out};
                 Operand h = i == 0 ? Operand{f.e_hist + es * (zb + 1), de, (int64_t)es} : Operand{f.step0.HC[i - 1] + zb * sstride, k_in, sstride};
@@ -1449,7 +1434,7 @@ extern "C" int mpnhip_backward_flags(const mpnhip_model* model, const void* grap
         for (int i = 0; i + 1 < nc; ++i) dzc[i] = p.dZcl[i];
         MPN_TRY(classifier_chain(b.HC, dzc, grad_logits, p.dE0, nullptr));
         for (int i = nc - 1; i >= 0 && E > 0; --i) {
-            const int n_out = cls.out_dims[i], k_in = i == 0 ? de : cls.out_dims[i - 1];
+            const int n_out = cls.out_dims[i], k_in = layer_in(cls, i);
             const bool top = i == nc - 1;
             Operand dz = top ? Operand{grad_logits, 1, 0} : Operand{p.dZcl[i], n_out, 0};
             Operand h = i == 0 ? Operand{e0, de, 0} : Operand{b.HC[i - 1], k_in, 0};
@@ -1580,10 +1565,8 @@ extern "C" int mpnhip_debug_backward_saved(const mpnhip_model* model, int n_node
     const int64_t N = n_nodes, E = n_edges;
     BwdPlan p;
     const size_t need = plan_backward(m, d, N, E, const_cast<void*>(bwd_workspace), &p);
-    if (bwd_workspace_bytes < need) {
-        set_error("debug_backward_saved: workspace %zu < %zu", bwd_workspace_bytes, need);
-        return MPNHIP_ERR_WORKSPACE;
-    }
+    // (a null buffer was refused above as a bad argument: only the size test of the macro is live here)
+    MPN_CHECK_WORKSPACE("debug_backward_saved", bwd_workspace, bwd_workspace_bytes, need);
     MPN_CHECK_ARG(step >= 1 && step <= (d.L > 0 ? d.L : 1), "debug_backward_saved: step %d", step);
     const size_t b = (size_t)(step - 1);
     const float* src = nullptr;

@@ -146,14 +146,24 @@ __global__ __launch_bounds__(256) void k_bn_bwd_apply(BnArgs a) {
 
 int nchunks(int64_t m) { return (int)((m + BN_ROWS - 1) / BN_ROWS); }
 
+// part [2][chunks][n] | colsum [2][n]: ONE region of floats (colsum follows part unpadded, the size is not rounded -- the size
+// callers have always been told), so it is not walked with a Carver
+struct BnWorkspace { float* part; float* colsum; };
+size_t bn_layout(int64_t m, int n, void* workspace, BnWorkspace* v) {
+    const size_t part = (size_t)2 * nchunks(m) * n, colsum = 2 * (size_t)n;
+    v->part = static_cast<float*>(workspace);
+    v->colsum = workspace ? v->part + part : nullptr;
+    return (part + colsum) * sizeof(float);
+}
+
 }  // namespace
 }  // namespace mpnhip
 
 using namespace mpnhip;
 
 extern "C" size_t mpnhip_bn_dropout_workspace_bytes(int64_t m, int n) {
-    if (m <= 0 || n <= 0) return 0;
-    return ((size_t)2 * nchunks(m) * n + 2 * (size_t)n) * sizeof(float);
+    BnWorkspace v;
+    return m <= 0 || n <= 0 ? 0 : bn_layout(m, n, nullptr, &v);
 }
 
 extern "C" int mpnhip_bn_relu_dropout_forward(const float* z, int64_t m, int n, int use_bn, const float* gamma, const float* beta,
@@ -172,8 +182,9 @@ extern "C" int mpnhip_bn_relu_dropout_forward(const float* z, int64_t m, int n, 
         // nn.BatchNorm1d in training mode refuses a single row ("Expected more than 1 value per channel when training")
         MPN_CHECK_ARG(m > 1, "bn_relu_dropout_forward: BatchNorm1d in training mode needs more than one row");
         MPN_CHECK_ARG(save_mean && save_invstd, "bn_relu_dropout_forward: save_mean / save_invstd required with BatchNorm");
-        MPN_CHECK_ARG(workspace && workspace_bytes >= mpnhip_bn_dropout_workspace_bytes(m, n), "bn_relu_dropout_forward: workspace too small");
-        a.gamma = gamma; a.beta = beta; a.part = static_cast<float*>(workspace);
+        BnWorkspace v;
+        MPN_CHECK_ARG(workspace && workspace_bytes >= bn_layout(m, n, workspace, &v), "bn_relu_dropout_forward: workspace too small");
+        a.gamma = gamma; a.beta = beta; a.part = v.part;
         const int nch = nchunks(m);
         const dim3 grid((unsigned)nch, (unsigned)((n + 63) / 64));
         hipLaunchKernelGGL(k_col_partial<0>, grid, dim3(256), 0, s, a);
@@ -204,10 +215,11 @@ extern "C" int mpnhip_bn_relu_dropout_backward(const float* dy, const float* z, 
     a.p = dropout_p; a.scale = 1.f / (1.f - dropout_p); a.seed = seed;
     if (use_bn) {
         MPN_CHECK_ARG(save_mean && save_invstd, "bn_relu_dropout_backward: save_mean / save_invstd required with BatchNorm");
-        MPN_CHECK_ARG(workspace && workspace_bytes >= mpnhip_bn_dropout_workspace_bytes(m, n), "bn_relu_dropout_backward: workspace too small");
-        a.gamma = gamma; a.beta = beta; a.mean = save_mean; a.invstd = save_invstd; a.part = static_cast<float*>(workspace);
+        BnWorkspace v;
+        MPN_CHECK_ARG(workspace && workspace_bytes >= bn_layout(m, n, workspace, &v), "bn_relu_dropout_backward: workspace too small");
+        a.gamma = gamma; a.beta = beta; a.mean = save_mean; a.invstd = save_invstd; a.part = v.part;
         const int nch = nchunks(m);
-        float* colsum = a.part + (size_t)2 * nch * n;
+        float* colsum = v.colsum;
         hipLaunchKernelGGL(k_col_partial<2>, dim3((unsigned)nch, (unsigned)((n + 63) / 64)), dim3(256), 0, s, a);
         hipLaunchKernelGGL(k_col_finish<2>, dim3((n + 63) / 64), dim3(64), 0, s, a.part, nch, n, m, 0.f, 0.f, colsum, colsum + n, nullptr,
                            nullptr, nullptr, dgamma, dbeta);

@@ -19,14 +19,18 @@ void set_error(const char* fmt, ...);
         }                                 \
     } while (0)
 
-// name: the operator, a string literal; refuses a null workspace or one smaller than the layout function's size
-#define MPN_CHECK_WORKSPACE(name, workspace, workspace_bytes, need)                                              \
+// what: a string literal naming the operator and the buffer ("forward: workspace"); suffix: literal text behind the two numbers.
+// Refuses a null workspace or one smaller than the layout function's size.
+#define MPN_CHECK_WORKSPACE_MSG(what, suffix, workspace, workspace_bytes, need)                                  \
     do {                                                                                                          \
         if (!(workspace) || (workspace_bytes) < (need)) {                                                         \
-            mpnhip::set_error(name ": workspace %zu < %zu", (size_t)(workspace_bytes), (size_t)(need));           \
+            mpnhip::set_error(what " %zu < %zu" suffix, (size_t)(workspace_bytes), (size_t)(need));               \
             return MPNHIP_ERR_WORKSPACE;                                                                          \
         }                                                                                                         \
     } while (0)
+// name: the operator, a string literal
+#define MPN_CHECK_WORKSPACE(name, workspace, workspace_bytes, need) \
+    MPN_CHECK_WORKSPACE_MSG(name ": workspace", "", workspace, workspace_bytes, need)
 
 #define MPN_HIP(call)                                                                     \
     do {                                                                                   \
@@ -345,6 +349,16 @@ struct Carver {
         T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
         off += align_up(count * sizeof(T), 256);
         return p;
+    }
+    // a region handed out as T* whose `count` elements are `elem_bytes` wide in memory: the blocks that hold bf16 or fp32 rows
+    // depending on the mode behind one float* field
+    template <class T>
+    T* take_as(size_t count, size_t elem_bytes) { return static_cast<T*>(static_cast<void*>(take<char>(count * elem_bytes))); }
+    // the region just taken (it began at offset `begin` and ends here) is the first of `n` equal blocks, `stride` bytes apart
+    size_t repeat(size_t begin, size_t n) {
+        const size_t stride = off - begin;
+        off = begin + stride * n;
+        return stride;
     }
     size_t bytes() const { return off; }
 };

@@ -797,7 +797,11 @@ int chain_bf16_debug_mask(const unsigned* mask, int section, const int* header, 
 }
 
 size_t chain_bf16_agg_scratch_floats(int64_t E, int dn, size_t* off_start_row) {
-    const size_t tiles = (size_t)((E + 255) / 256 + 3) * 8, DN = (size_t)(dn + 31) / 32 * 32;
+    // plan_forward (plan.h) carves the pieces and the start rows as two regions and relies on the start rows following the pieces
+    // directly: the pieces are whole 256-byte units whatever E and dn are
+    constexpr size_t TILE_GROUP = 8, DN_PAD = 32;
+    static_assert(TILE_GROUP * 2 * DN_PAD * sizeof(float) % 256 == 0, "the piece part must end on a region boundary of the Carver");
+    const size_t tiles = (size_t)((E + 255) / 256 + 3) * TILE_GROUP, DN = (size_t)(dn + DN_PAD - 1) / DN_PAD * DN_PAD;
     if (off_start_row) *off_start_row = tiles * 2 * DN;
     return tiles * 2 * DN + tiles;
 }

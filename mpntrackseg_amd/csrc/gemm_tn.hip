@@ -572,29 +572,34 @@ int launch_gemm_tn(const TnArgs& a_in, hipStream_t s) {
 
 using namespace mpnhip;
 
+// One slab -- the larger of the split-row and the row-panel form's (MPNHIP_PREC_FP32_SPLIT / _BF16); rows16: the row-panel form over
+// bf16 rows only -- behind a base the operator rounds up to 256 itself (callers may pass unaligned buffers): 256 bytes to spare.
+static size_t weight_grad_layout(int n_out, int k_in, int64_t rows, int nbatch, bool rows16, void* workspace, float** slab) {
+    const int nb = nbatch < 1 ? 1 : nbatch;
+    const size_t tn = rows16 ? 0 : tn_slab_floats(n_out, k_in, rows, nb), wp = rows > 0 ? wp_slab_floats(n_out, k_in, rows, nb, false, false, rows16) : 0;
+    const uintptr_t w = reinterpret_cast<uintptr_t>(workspace);
+    Carver c(workspace ? static_cast<char*>(workspace) + (align_up(w, 256) - w) : nullptr);
+    *slab = c.take<float>(tn > wp ? tn : wp);
+    return c.bytes() + 256;
+}
+
 extern "C" size_t mpnhip_weight_grad_workspace_bytes(int n_out, int k_in, int64_t rows, int nbatch) {
-    if (n_out < 1 || k_in < 1 || rows < 0) return 0;
-    const size_t a = tn_slab_floats(n_out, k_in, rows, nbatch < 1 ? 1 : nbatch);
-    const size_t b = rows > 0 ? wp_slab_floats(n_out, k_in, rows, nbatch < 1 ? 1 : nbatch, false, false) : 0;   // (MPNHIP_PREC_FP32_SPLIT form)
-    return align_up((a > b ? a : b) * sizeof(float), 256) + 256;
+    float* slab;
+    return n_out < 1 || k_in < 1 || rows < 0 ? 0 : weight_grad_layout(n_out, k_in, rows, nbatch, false, nullptr, &slab);
 }
 
 static int weight_grad_args(const float* dZ, const float* H, int64_t rows, int n_out, int k_in, int nbatch, float* grad_w, float* grad_b,
                             void* workspace, size_t workspace_bytes, TnArgs* out) {
     MPN_CHECK_ARG(n_out >= 1 && k_in >= 1 && rows >= 0 && nbatch >= 1, "weight_grad: bad sizes");
     MPN_CHECK_ARG((dZ && H && grad_w) || rows == 0, "weight_grad: null pointer");
-    const size_t need = mpnhip_weight_grad_workspace_bytes(n_out, k_in, rows, nbatch);
-    if (rows > 0 && (!workspace || workspace_bytes < need)) {
-        set_error("weight_grad: workspace %zu < %zu", workspace_bytes, need);
-        return MPNHIP_ERR_WORKSPACE;
-    }
     TnArgs a = {};
+    const size_t need = weight_grad_layout(n_out, k_in, rows, nbatch, false, workspace, &a.g[0].slab);
+    if (rows > 0) MPN_CHECK_WORKSPACE("weight_grad", workspace, workspace_bytes, need);
     a.ngroups = 1; a.n_out = n_out; a.k_in = k_in; a.csplit = k_in; a.m_upper = rows; a.nbatch = nbatch;
     TnGroup& g = a.g[0];
     g.dZ = dZ; g.ldz = n_out; g.z_bstride = rows * n_out;
     g.H = H; g.ldh = k_in; g.h_bstride = rows * k_in;
     g.m_static = rows;
-    g.slab = reinterpret_cast<float*>((reinterpret_cast<uintptr_t>(workspace) + 255) / 256 * 256);
     g.grad_w = grad_w; g.ldw = k_in; g.grad_b = grad_b;
     a.flops = 2.0 * (double)rows * nbatch * n_out * k_in;
     *out = a;
@@ -628,12 +633,9 @@ extern "C" int mpnhip_weight_grad_bf16_rows(const uint16_t* dZ, const uint16_t* 
     MPN_CHECK_ARG(n_out >= 1 && k_in >= 1 && rows >= 0 && nbatch >= 1, "weight_grad_bf16_rows: bad sizes");
     if (rows == 0) return MPNHIP_OK;
     MPN_CHECK_ARG(dZ && H && grad_w, "weight_grad_bf16_rows: null pointer");
-    const size_t need = align_up(wp_slab_floats(n_out, k_in, rows, nbatch, false, false, true) * sizeof(float), 256) + 256;
-    if (!workspace || workspace_bytes < need) {
-        set_error("weight_grad_bf16_rows: workspace %zu < %zu", workspace_bytes, need);
-        return MPNHIP_ERR_WORKSPACE;
-    }
-    float* slab = reinterpret_cast<float*>((reinterpret_cast<uintptr_t>(workspace) + 255) / 256 * 256);
+    float* slab;
+    const size_t need = weight_grad_layout(n_out, k_in, rows, nbatch, true, workspace, &slab);
+    MPN_CHECK_WORKSPACE("weight_grad_bf16_rows", workspace, workspace_bytes, need);
     WpProduct p = {reinterpret_cast<const float*>(dZ), n_out, rows * n_out, reinterpret_cast<const float*>(H), k_in, rows * k_in, nullptr, nullptr,
                    rows, nbatch, n_out, k_in, grad_w, k_in, grad_b, nullptr, nullptr, nullptr, 0, 0, 0, 1, 1};
     WpBatch b;
@@ -644,8 +646,8 @@ extern "C" int mpnhip_weight_grad_bf16_rows(const uint16_t* dZ, const uint16_t* 
 }
 
 extern "C" size_t mpnhip_weight_grad_bf16_rows_workspace_bytes(int n_out, int k_in, int64_t rows, int nbatch) {
-    if (n_out < 1 || k_in < 1 || rows < 0) return 0;
-    return align_up((rows > 0 ? wp_slab_floats(n_out, k_in, rows, nbatch < 1 ? 1 : nbatch, false, false, true) : 0) * sizeof(float), 256) + 256;
+    float* slab;
+    return n_out < 1 || k_in < 1 || rows < 0 ? 0 : weight_grad_layout(n_out, k_in, rows, nbatch, true, nullptr, &slab);
 }
 
 extern "C" int mpnhip_weight_grad(const float* dZ, const float* H, int64_t rows, int n_out, int k_in, int nbatch, float* grad_w,

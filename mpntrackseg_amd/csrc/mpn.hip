@@ -619,7 +619,7 @@ static int mlp_forward(const mpnhip_mlp& m, const float* x, int64_t ldx, const i
     for (int i = 0; i < m.n_layers; ++i) {
         if (splitk && !a_idx) {
             int st = MPNHIP_OK;
-            const int k_in = i == 0 ? m.in_dim : m.out_dims[i - 1];
+            const int k_in = layer_in(m, i);
             // (the layer after it rides along when it is the MLP's last and narrow: the reference's 2048 -> 128 -> 32 node encoder)
             SplitkNext nx = {};
             const bool has_next = i + 2 == m.n_layers;
@@ -635,7 +635,7 @@ static int mlp_forward(const mpnhip_mlp& m, const float* x, int64_t ldx, const i
         GemmArgs a = {};
         a.ngroups = 1;
         a.N = m.out_dims[i];
-        a.K = i == 0 ? m.in_dim : m.out_dims[i - 1];
+        a.K = layer_in(m, i);
         a.ksplit = a.K;
         a.relu = m.out_dims[i] != 1;
         a.m_upper = rows;
@@ -690,11 +690,8 @@ extern "C" int mpnhip_forward(const mpnhip_model* model, const void* graph_buf, 
     MPN_CHECK_ARG(N >= 0 && E >= 0, "forward: negative sizes");
     MPN_CHECK_ARG((x || N == 0) && (edge_attr || E == 0) && (logits || E == 0), "forward: null tensor");
     FwdPlan p;
-    size_t need = plan_forward(m, d, N, E, save, workspace, &p);
-    if (!workspace || workspace_bytes < need) {
-        set_error("forward: workspace %zu < %zu", workspace_bytes, need);
-        return MPNHIP_ERR_WORKSPACE;
-    }
+    const size_t need = plan_forward(m, d, N, E, save, workspace, &p);
+    MPN_CHECK_WORKSPACE("forward", workspace, workspace_bytes, need);
     GraphView g;
     graph_layout(n_nodes, n_edges, &g, const_cast<void*>(graph_buf));
     MPN_CHECK_ARG(m.precision == MPNHIP_PREC_FP32 || m.precision == MPNHIP_PREC_BF16 || m.precision == MPNHIP_PREC_FP32_SPLIT ||
@@ -858,13 +855,13 @@ extern "C" int mpnhip_forward(const mpnhip_model* model, const void* graph_buf, 
 // ------------------------------------------------------------------------------------ MetaLayer op
 static size_t plan_meta(const mpnhip_model& m, const Dims& d, int64_t N, int64_t E, void* base, float** Wnode,
                         float** bnode, StepBufs* sb) {
-    Arena a = {static_cast<char*>(base), 0};
-    float* w = a.f((size_t)d.pw * d.kx);
-    float* b = a.f((size_t)d.pw);
+    Carver a(base);
+    float* w = a.take<float>((size_t)d.pw * d.kx);
+    float* b = a.take<float>((size_t)d.pw);
     carve_step(a, m, d, N, E, false, false, sb);
     if (Wnode) *Wnode = w;
     if (bnode) *bnode = b;
-    return a.off;
+    return a.bytes();
 }
 
 extern "C" size_t mpnhip_meta_layer_workspace_bytes(const mpnhip_model* model, int n_nodes, int64_t n_edges) {
@@ -885,11 +882,8 @@ extern "C" int mpnhip_meta_layer_forward(const mpnhip_model* model, const void* 
     MPN_CHECK_ARG((e && e_new) || E == 0, "meta_layer: null edge tensors");
     float *Wnode, *bnode;
     StepBufs b;
-    size_t need = plan_meta(*model, d, N, E, workspace, &Wnode, &bnode, &b);
-    if (!workspace || workspace_bytes < need) {
-        set_error("meta_layer: workspace %zu < %zu", workspace_bytes, need);
-        return MPNHIP_ERR_WORKSPACE;
-    }
+    const size_t need = plan_meta(*model, d, N, E, workspace, &Wnode, &bnode, &b);
+    MPN_CHECK_WORKSPACE("meta_layer", workspace, workspace_bytes, need);
     GraphView g;
     graph_layout(n_nodes, n_edges, &g, const_cast<void*>(graph_buf));
     MPN_TRY(pack_node_weights(*model, d, Wnode, bnode, nullptr, s));
@@ -911,10 +905,17 @@ extern "C" int mpnhip_linear(const float* x, int64_t ldx, const float* w, const 
     return linear(x, ldx, w, b, y, ldy, m, n, k, relu, MPNHIP_PREC_FP32, static_cast<hipStream_t>(stream_));
 }
 
+// the two ping-pong buffers of the hidden activations, [m, widest hidden layer] each
+static size_t mlp_layout(const mpnhip_mlp& mlp, int64_t m, void* workspace, float* two[2]) {
+    Carver c(workspace);
+    const int h = max_hidden(mlp);
+    for (int i = 0; i < 2; ++i) two[i] = c.take<float>((size_t)(m > 0 ? m : 1) * (h > 0 ? h : 1));
+    return c.bytes();
+}
+
 extern "C" size_t mpnhip_mlp_workspace_bytes(const mpnhip_mlp* mlp, int64_t m) {
-    if (!mlp) return 0;
-    int h = max_hidden(*mlp);
-    return 2 * align_up((size_t)(m > 0 ? m : 1) * (h > 0 ? h : 1) * sizeof(float), 256);
+    float* two[2];
+    return mlp ? mlp_layout(*mlp, m, nullptr, two) : 0;
 }
 
 extern "C" int mpnhip_mlp_forward(const mpnhip_mlp* mlp, const float* x, float* y, int64_t m, void* workspace,
@@ -923,12 +924,9 @@ extern "C" int mpnhip_mlp_forward(const mpnhip_mlp* mlp, const float* x, float* 
     MPN_TRY(mlp_ok(*mlp, "mlp", true));
     if (m == 0) return MPNHIP_OK;
     MPN_CHECK_ARG(x && y && m > 0, "mlp_forward: null pointer");
-    size_t need = mpnhip_mlp_workspace_bytes(mlp, m);
-    if (mlp->n_layers > 1 && (!workspace || workspace_bytes < need)) {
-        set_error("mlp_forward: workspace %zu < %zu", workspace_bytes, need);
-        return MPNHIP_ERR_WORKSPACE;
-    }
-    float* two[2] = {static_cast<float*>(workspace), reinterpret_cast<float*>(static_cast<char*>(workspace) + need / 2)};
+    float* two[2];
+    const size_t need = mlp_layout(*mlp, m, workspace, two);
+    if (mlp->n_layers > 1) MPN_CHECK_WORKSPACE("mlp_forward", workspace, workspace_bytes, need);   // (one layer: no hidden activation)
     float* hid[MPNHIP_MAX_LAYERS];
     hidden_ptrs(*mlp, two, m, false, hid);
     return mlp_forward(*mlp, x, mlp->in_dim, nullptr, hid, y, m, MPNHIP_PREC_FP32, static_cast<hipStream_t>(stream_));
@@ -967,10 +965,8 @@ extern "C" int mpnhip_debug_saved(const mpnhip_model* model, const void* graph_b
     const int64_t N = n_nodes, E = n_edges;
     FwdPlan p;
     const size_t need = plan_forward(m, d, N, E, 1, const_cast<void*>(fwd_workspace), &p);
-    if (fwd_workspace_bytes < need) {
-        set_error("debug_saved: workspace %zu < %zu (must be a save_for_backward buffer)", fwd_workspace_bytes, need);
-        return MPNHIP_ERR_WORKSPACE;
-    }
+    // (a null buffer was refused above as a bad argument: only the size test of the macro is live here)
+    MPN_CHECK_WORKSPACE_MSG("debug_saved: workspace", " (must be a save_for_backward buffer)", fwd_workspace, fwd_workspace_bytes, need);
     GraphView g;
     graph_layout(n_nodes, n_edges, &g, const_cast<void*>(graph_buf));
     const size_t xs = (size_t)N * d.dn, es = (size_t)E * d.de;

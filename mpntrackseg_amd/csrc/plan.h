@@ -99,16 +99,10 @@ static inline bool chain_bf16_train_ok(const mpnhip_model& m, const Dims& d) {
 }
 
 // ------------------------------------------------------------------------------------ workspace
-struct Arena {
-    char* base;
-    size_t off;
-    float* f(size_t n) {
-        size_t o = off;
-        off = align_up(off + n * sizeof(float), 256);
-        return base ? reinterpret_cast<float*>(base + o) : nullptr;
-    }
-    int* i(size_t n) { return reinterpret_cast<int*>(f(n)); }
-};
+// The plans below walk a Carver (common.h): every region starts on a 256-byte boundary and is taken with its own element type.
+
+// input width of layer i of an MLP
+static inline int layer_in(const mpnhip_mlp& m, int i) { return i == 0 ? m.in_dim : m.out_dims[i - 1]; }
 
 // per-step activation buffers of one MetaLayer + classifier evaluation
 struct StepBufs {
@@ -174,34 +168,39 @@ struct FwdPlan {
     size_t total;
 };
 
-static inline void carve_step(Arena& a, const mpnhip_model& m, const Dims& d, int64_t N, int64_t E, bool with_cls, bool with_arg,
+static inline void carve_step(Carver& a, const mpnhip_model& m, const Dims& d, int64_t N, int64_t E, bool with_cls, bool with_arg,
                        StepBufs* sb, bool b16 = false) {
     StepBufs s = {};
-    s.P = a.f((size_t)N * d.pw);
-    // (b16: the hidden activations are kept as bf16 rows -- half the floats)
-    auto hid = [&](int64_t rows, int width) { return a.f(b16 ? ((size_t)rows * width + 1) / 2 : (size_t)rows * width); };
+    s.P = a.take<float>((size_t)N * d.pw);
+    // (b16: the hidden activations are kept as bf16 rows)
+    auto hid = [&](int64_t rows, int width) { return a.take_as<float>((size_t)rows * width, b16 ? sizeof(unsigned short) : sizeof(float)); };
     for (int i = 0; i + 1 < m.edge.n_layers; ++i) s.HE[i] = hid(E, m.edge.out_dims[i]);
     if (with_cls)
         for (int i = 0; i + 1 < m.classifier.n_layers; ++i) s.HC[i] = hid(E, m.classifier.out_dims[i]);
     for (int i = 0; i + 1 < m.flow_in.n_layers; ++i) s.HF[i] = hid(E, m.flow_in.out_dims[i]);
-    s.M = a.f((size_t)E * d.dn);
-    s.AGG = a.f((size_t)N * 2 * d.dn);
-    s.ARG = with_arg ? a.i((size_t)N * 2 * d.dn) : nullptr;
-    s.MK = a.i(b16 ? chain_bf16_mask_ints(E, d.he, d.de, d.hn, d.dn, m.classifier.n_layers >= 1 ? m.classifier.out_dims[0] : 1)
-                   : chain_mask_ints(E, d.he, d.de, d.hn, d.dn));
+    s.M = a.take<float>((size_t)E * d.dn);
+    s.AGG = a.take<float>((size_t)N * 2 * d.dn);
+    s.ARG = with_arg ? a.take<int>((size_t)N * 2 * d.dn) : nullptr;
+    s.MK = a.take<int>(b16 ? chain_bf16_mask_ints(E, d.he, d.de, d.hn, d.dn, m.classifier.n_layers >= 1 ? m.classifier.out_dims[0] : 1)
+                           : chain_mask_ints(E, d.he, d.de, d.hn, d.dn));
     if (sb) *sb = s;
+}
+
+// q moved by `bytes` (nullptr stays nullptr)
+template <class T>
+static inline T* shifted(T* q, size_t bytes) {
+    return q ? reinterpret_cast<T*>(reinterpret_cast<char*>(q) + bytes) : nullptr;
 }
 
 static inline StepBufs step_at(const FwdPlan& p, int s) {
     StepBufs b = p.step0;
-    size_t sh = p.step_stride_bytes * (size_t)s;
-    auto mv = [&](float*& q) { if (q) q = reinterpret_cast<float*>(reinterpret_cast<char*>(q) + sh); };
-    mv(b.P);
-    for (int i = 0; i < MPNHIP_MAX_LAYERS; ++i) { mv(b.HE[i]); mv(b.HC[i]); mv(b.HF[i]); }
-    mv(b.M);
-    mv(b.AGG);
-    if (b.ARG) b.ARG = reinterpret_cast<int*>(reinterpret_cast<char*>(b.ARG) + sh);
-    if (b.MK) b.MK = reinterpret_cast<int*>(reinterpret_cast<char*>(b.MK) + sh);
+    const size_t sh = p.step_stride_bytes * (size_t)s;
+    b.P = shifted(b.P, sh);
+    for (int i = 0; i < MPNHIP_MAX_LAYERS; ++i) { b.HE[i] = shifted(b.HE[i], sh); b.HC[i] = shifted(b.HC[i], sh); b.HF[i] = shifted(b.HF[i], sh); }
+    b.M = shifted(b.M, sh);
+    b.AGG = shifted(b.AGG, sh);
+    b.ARG = shifted(b.ARG, sh);
+    b.MK = shifted(b.MK, sh);
     return b;
 }
 
@@ -216,22 +215,22 @@ static inline bool node_rows16_runtime(const FwdPlan& p, const mpnhip_model& m, 
 }
 
 static inline size_t plan_forward(const mpnhip_model& m, const Dims& d, int64_t N, int64_t E, int save, void* base, FwdPlan* out) {
-    Arena a = {static_cast<char*>(base), 0};
+    Carver a(base);
     FwdPlan p = {};
     // weight images first: their offsets depend on the model's dims only, never on N / E, so a caller that keeps the
     // workspace can keep them across calls (mpnhip_model.weights_prepacked)
-    p.Wnode = a.f((size_t)d.pw * d.kx);
-    p.bnode = a.f((size_t)d.pw);
+    p.Wnode = a.take<float>((size_t)d.pw * d.kx);
+    p.bnode = a.take<float>((size_t)d.pw);
     {
         const size_t HE = pad32(d.he), DE = pad32(d.de), HN = pad32(d.hn), DN = pad32(d.dn);
         // (sized for the split images, 3/2 of the fp32 ones: ChainWeights.split)
         const size_t KE = (size_t)(d.ke + 15) / 16 * 16;
-        p.cw.w1T = a.f(KE * HE * 3 / 2);
-        p.cw.w2T = a.f(HE * DE * 3 / 2);
-        p.cw.wc1T = a.f(DE * 32 * 3 / 2);
+        p.cw.w1T = a.take<float>(KE * HE * 3 / 2);
+        p.cw.w2T = a.take<float>(HE * DE * 3 / 2);
+        p.cw.wc1T = a.take<float>(DE * 32 * 3 / 2);
         for (int q = 0; q < 2; ++q) {
-            p.cw.wf1T[q] = a.f(DE * HN * 3 / 2);
-            p.cw.wf2T[q] = a.f(HN * DN * 3 / 2);
+            p.cw.wf1T[q] = a.take<float>(DE * HN * 3 / 2);
+            p.cw.wf2T[q] = a.take<float>(HN * DN * 3 / 2);
         }
         p.cw.ok = false;
     }
@@ -240,65 +239,60 @@ static inline size_t plan_forward(const mpnhip_model& m, const Dims& d, int64_t 
         const int hc = m.classifier.n_layers >= 1 ? m.classifier.out_dims[0] : 0;
         p.cb = {};
         cb_shapes = edge_chain_bf16_supported(d.he, d.de, d.hn, d.dn, hc, d.ef);
-        if (cb_shapes) {
-            const size_t bytes = chain_bf16_image_bytes(d.he, d.de, d.hn, d.dn, hc, d.ef, &p.cb.off_cls, &p.cb.off_flow[0], &p.cb.off_flow[1]);
-            p.cb.img = reinterpret_cast<char*>(a.f(bytes / 4));
-        }
+        if (cb_shapes)
+            p.cb.img = a.take<char>(chain_bf16_image_bytes(d.he, d.de, d.hn, d.dn, hc, d.ef, &p.cb.off_cls, &p.cb.off_flow[0], &p.cb.off_flow[1]));
     }
     p.nc_img = nullptr;
     if (node_chain_supported(d.dn, d.pw, d.kx) && m.node.n_layers == 1)
-        p.nc_img = reinterpret_cast<unsigned short*>(a.f((node_chain_image_shorts(d.dn, d.pw, nullptr) + 1) / 2));
+        p.nc_img = a.take<unsigned short>(node_chain_image_shorts(d.dn, d.pw, nullptr));
     // (bf16 rows for the tiled / ring GEMM kernels: 16-byte pieces of 8 elements)
     // (d.pw % 4: launch_gemm's bf16-row path stores 16-byte result vectors -- N = pw of the projections, N = dn of the node update)
     const bool rows16 = m.precision == MPNHIP_PREC_BF16 && d.kx % 8 == 0 && d.dn % 8 == 0 && d.pw % 4 == 0 && m.node.n_layers == 1;
-    p.Wnode16 = rows16 ? reinterpret_cast<unsigned short*>(a.f(((size_t)d.pw * d.kx + 1) / 2)) : nullptr;
-    p.Wu16 = rows16 ? reinterpret_cast<unsigned short*>(a.f(((size_t)d.dn * 2 * d.dn + 1) / 2)) : nullptr;
-    p.P0 = a.f((size_t)N * d.pw);
-    p.Q0 = a.f((size_t)E * d.he);
+    p.Wnode16 = rows16 ? a.take<unsigned short>((size_t)d.pw * d.kx) : nullptr;
+    p.Wu16 = rows16 ? a.take<unsigned short>((size_t)d.dn * 2 * d.dn) : nullptr;
+    p.P0 = a.take<float>((size_t)N * d.pw);
+    p.Q0 = a.take<float>((size_t)E * d.he);
     int hn_ = max_hidden(m.enc_node), he_ = max_hidden(m.enc_edge);
     if (save) {
         // keep every encoder activation for the backward pass: one buffer per hidden layer
-        p.enc_n[0] = a.f((size_t)N * (sum_hidden(m.enc_node) > 0 ? sum_hidden(m.enc_node) : 1));
-        p.enc_e[0] = a.f((size_t)E * (sum_hidden(m.enc_edge) > 0 ? sum_hidden(m.enc_edge) : 1));
+        p.enc_n[0] = a.take<float>((size_t)N * (sum_hidden(m.enc_node) > 0 ? sum_hidden(m.enc_node) : 1));
+        p.enc_e[0] = a.take<float>((size_t)E * (sum_hidden(m.enc_edge) > 0 ? sum_hidden(m.enc_edge) : 1));
         p.enc_n[1] = p.enc_e[1] = nullptr;
     } else {
         for (int i = 0; i < 2; ++i) {
-            p.enc_n[i] = a.f((size_t)N * (hn_ > 0 ? hn_ : 1));
-            p.enc_e[i] = a.f((size_t)E * (he_ > 0 ? he_ : 1));
+            p.enc_n[i] = a.take<float>((size_t)N * (hn_ > 0 ? hn_ : 1));
+            p.enc_e[i] = a.take<float>((size_t)E * (he_ > 0 ? he_ : 1));
         }
     }
     p.hist_slots = save ? d.L + 1 : 3;
-    p.x_hist = a.f((size_t)p.hist_slots * N * d.dn);
-    p.e_hist = a.f((size_t)p.hist_slots * E * d.de);
-    p.xb_hist = rows16 ? reinterpret_cast<unsigned short*>(a.f(((size_t)p.hist_slots * N * d.dn + 1) / 2)) : nullptr;
+    p.x_hist = a.take<float>((size_t)p.hist_slots * N * d.dn);
+    p.e_hist = a.take<float>((size_t)p.hist_slots * E * d.de);
+    p.xb_hist = rows16 ? a.take<unsigned short>((size_t)p.hist_slots * N * d.dn) : nullptr;
     p.b16 = save && cb_shapes && chain_bf16_train_ok(m, d);
     // (inference in the bf16-operand mode keeps the same mirror over its three history slots: the chain kernel reads its first-layer
     // input as bf16 rows -- the values it rounds to anyway -- and writes the new features as bf16 for the next step)
     const bool eb_inf = !save && cb_shapes && chain_bf16_ok(m, d) && d.L >= 1 && d.de % 8 == 0 && !getenv("MPNHIP_NO_CHAIN_BF16_E16");
-    p.eb_hist = (p.b16 || eb_inf) ? reinterpret_cast<unsigned short*>(a.f(((size_t)p.hist_slots * E * d.de + 1) / 2)) : nullptr;
-    size_t before = a.off;
+    p.eb_hist = (p.b16 || eb_inf) ? a.take<unsigned short>((size_t)p.hist_slots * E * d.de) : nullptr;
+    const size_t step0 = a.bytes();
     carve_step(a, m, d, N, E, true, save && m.agg == MPNHIP_AGG_MAX, &p.step0, p.b16);
-    p.step_stride_bytes = 0;
-    if (save && d.L > 1) {
-        p.step_stride_bytes = a.off - before;
-        a.off = before + p.step_stride_bytes * (size_t)d.L;
-    }
+    p.step_stride_bytes = save && d.L > 1 ? a.repeat(step0, (size_t)d.L) : 0;   // (training: one block per step; inference reuses one)
     {
         size_t sk = 0;
         for (int i = 0; i < m.enc_node.n_layers; ++i) {
-            const size_t f = linear_splitk_scratch_floats(N, m.enc_node.out_dims[i], i == 0 ? m.enc_node.in_dim : m.enc_node.out_dims[i - 1]);
+            const size_t f = linear_splitk_scratch_floats(N, m.enc_node.out_dims[i], layer_in(m.enc_node, i));
             sk = f > sk ? f : sk;
         }
         p.splitk_floats = sk;
-        p.splitk = sk ? a.f(sk) : nullptr;
+        p.splitk = sk ? a.take<float>(sk) : nullptr;
     }
     if (cb_shapes && (!save || p.b16)) {
-        size_t off = 0;
-        const size_t fl = chain_bf16_agg_scratch_floats(E, d.dn, &off);
-        p.cb.piece = a.f(fl);
-        p.cb.start_row = p.cb.piece ? reinterpret_cast<int*>(p.cb.piece + off) : nullptr;
+        // (the pieces are whole 2 KiB units, so the start rows follow them directly: one scratch of chain_bf16_agg_scratch_floats())
+        size_t pieces = 0;
+        const size_t fl = chain_bf16_agg_scratch_floats(E, d.dn, &pieces);
+        p.cb.piece = a.take<float>(pieces);
+        p.cb.start_row = a.take<int>(fl - pieces);
     }
-    p.total = a.off;
+    p.total = a.bytes();
     if (out) *out = p;
     return p.total;
 }

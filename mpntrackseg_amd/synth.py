@@ -76,6 +76,18 @@ def dims_for(d, node_in_dim=2048, edge_in_dim=6):
     }
 
 
+def deeper_params(p):
+    """``p`` with MLP depths other than the shipped two-layer ones and widths that are no multiples of 4 (the model of
+    tests/test_gpu_backward.py::test_deeper_mlps_and_odd_dims), scaled with the model's width; changes and returns ``p``."""
+    d = p["encoder_feats_dict"]["node_out_dim"]
+    p["encoder_feats_dict"]["edge_dims"] = [10 * d // 32]
+    p["encoder_feats_dict"]["node_dims"] = [24 * d // 32, 12 * d // 32]
+    p["edge_model_feats_dict"]["dims"] = [40 * d // 32, 24 * d // 32, d // 2]
+    p["node_model_feats_dict"]["dims"] = [d]
+    p["classifier_feats_dict"]["edge_dims"] = [6 * d // 32, 5 * d // 32]
+    return p
+
+
 def model_params(d, L, agg="sum", num_class_steps=None, node_in_dim=2048, edge_in_dim=6):
     p = dims_for(d, node_in_dim, edge_in_dim)
     p["node_agg_fn"] = agg

@@ -18,18 +18,9 @@ from mpntrackseg_amd.autograd import native_backward, native_forward_saved
 from oracle import mpn_oracle as O
 
 
-def hip_run(model, g, r, dev):
-    """Training forward + backward through the C ABI with the forward's decisions read back.
-    Returns (logits [L,E], {name: grad}, decisions {site: CPU tensor}, path counters)."""
-    x = torch.from_numpy(g["x"]).to(dev)
-    ea = torch.from_numpy(g["edge_attr"]).to(dev)
-    ei = torch.from_numpy(g["edge_index"]).to(dev)
-    N, E = x.shape[0], ea.shape[0]
+def forward_decisions(model, pg, ws):
+    """The ReLU / arg-max decisions a training forward left in its workspace `ws`: {site: CPU tensor}."""
     L = int(model.num_enc_steps)
-    pg = capi.PreparedGraph(ei, N, validate=True)
-    logits = torch.empty((max(L, 1), E), dtype=torch.float32, device=dev)
-    capi.path_counters(reset=True)
-    ws = native_forward_saved(model, pg, x, ea, logits)
     given = {}
 
     def take(site, what, step=0, layer=0):
@@ -54,6 +45,22 @@ def hip_run(model, g, r, dev):
         take("s%d.node" % s, "x", s)
         if model.MPNet.node_model.node_agg_fn.name == "max":
             given["s%d.argmax" % s] = capi.saved_activation(model, pg, ws, "argmax", s).cpu().long()
+    return given
+
+
+def hip_run(model, g, r, dev):
+    """Training forward + backward through the C ABI with the forward's decisions read back.
+    Returns (logits [L,E], {name: grad}, decisions {site: CPU tensor}, path counters)."""
+    x = torch.from_numpy(g["x"]).to(dev)
+    ea = torch.from_numpy(g["edge_attr"]).to(dev)
+    ei = torch.from_numpy(g["edge_index"]).to(dev)
+    N, E = x.shape[0], ea.shape[0]
+    L = int(model.num_enc_steps)
+    pg = capi.PreparedGraph(ei, N, validate=True)
+    logits = torch.empty((max(L, 1), E), dtype=torch.float32, device=dev)
+    capi.path_counters(reset=True)
+    ws = native_forward_saved(model, pg, x, ea, logits)
+    given = forward_decisions(model, pg, ws)
     params = model.hot_path_parameters()
     grads = {id(p): torch.zeros_like(p) for p in params}
     gx, gea = native_backward(model, pg, x, ea, torch.from_numpy(r).to(dev), ws, grads, need_gx=True, need_gea=True)

@@ -82,17 +82,22 @@ def close_enough(a, b, tol, robust, name="", log=None):
     return grad_close(a, b, tol, robust, name, log)
 
 
-def check_against_oracle(params, W, g, seed=11, tol=GTOL, robust=False, precision="fp32", logit_check=None):
+def check_against_oracle(params, W, g, seed=11, tol=GTOL, robust=False, precision="fp32", logit_check=None, run=None):
+    """``run``: another caller of the C ABI in place of the package's path, with the signature and results of pinned.hip_run."""
     if robust:
         import test_gpu_pinned as tp
-        tp.run_case(params, W, g, precision, seed=seed)
+        tp.run_case(params, W, g, precision, seed=seed, **({"run": run} if run else {}))
         return
     L = max(params["num_enc_steps"], 1)
     E = g["edge_index"].shape[1]
     r = synth.normal(seed, (L, E))
     model = make_model(params, W)
     model.gemm_precision = precision
-    lo, gx, gea, pg = native_grads(model, g["x"], g["edge_index"], g["edge_attr"], r)
+    if run is None:
+        lo, gx, gea, pg = native_grads(model, g["x"], g["edge_index"], g["edge_attr"], r)
+    else:
+        lo, pg, _, _ = run(model, g, r, dev())
+        gx, gea = pg["grad_x"], pg["grad_edge_attr"]
     lr, rx, rea, rpg = oracle_grads(params, W, g["x"], g["edge_index"], g["edge_attr"], r)
     if logit_check is not None:
         logit_check(lo, lr)

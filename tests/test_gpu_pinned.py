@@ -35,12 +35,13 @@ def make_model(params, W, precision):
     return model
 
 
-def run_case(params, W, g, precision, seed=11, logit_tol=None):
+def run_case(params, W, g, precision, seed=11, logit_tol=None, run=hip_run):
+    """``run``: what evaluates the model -- pinned.hip_run, or another caller of the C ABI with its signature and results."""
     L = max(params["num_enc_steps"], 1)
     E = g["edge_index"].shape[1]
     r = synth.normal(seed, (L, E))
     model = make_model(params, W, precision)
-    lg, grads, given, counts = hip_run(model, g, r, dev())
+    lg, grads, given, counts = run(model, g, r, dev())
     # (1) decisions against the free-running float64 oracle
     l64, d = oracle_compare(params, W, g, r, given)
     frac = d.mismatches / max(d.units, 1)

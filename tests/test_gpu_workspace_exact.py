@@ -11,7 +11,17 @@ a radix sort over one key bit too few, shows here.  Shapes: 64 and 65 nodes with
 detections, 3 steps, 2 graphs.  The workspace itself is filled with 0xA5 as well: nothing may rely on zeros it did not write.
 
 ``mpnhip_full_masks_workspace_bytes`` is ONE size for three operators (the largest of them plus 256): there the size an
-operator refuses below is read from its own refusal message and must not exceed the advertised one."""
+operator refuses below is read from its own refusal message and must not exceed the advertised one.
+
+The message-passing core (csrc/plan.h, backward.hip: ``mpnhip_forward`` / ``mpnhip_backward``) under the same discipline, at the
+smallest shapes at which each class of region exists -- fp32 / 32-d / max / 3 steps (ARG, the unfused-width slabs), fp32_split / 64-d /
+mean / 4 steps (four steps fork the side stream: slab_side, slab_wp, slab_tail, the node-chain images) and bf16 / 64-d / sum / 4
+steps (the bf16 dZ blocks, dEpp, dP16 / dZn16 / AGG16 / enc16, wt_keep16, the backward pair images).  The layout is a function of
+the dims, not of the buffer, and the kernels sum in a fixed order: logits and EVERY gradient must be BITWISE those of the package's
+own path (``model.hot_path`` + autograd, roomy cached buffers) on the same inputs.  Two cases reuse inputs the suite checks against
+the CPU oracle (tests/test_gpu_backward.py::test_structure_graph, tests/test_gpu_split.py::test_split_gradients_match_oracle)
+and are held to the same bounds.  The small operators with a workspace (meta layer, MLP, weight gradients, BatchNorm / dropout)
+follow, against plain numpy / float64 torch at the bounds of tests/test_gpu_wgrad.py and tests/test_gpu_modular.py."""
 import ctypes as C
 import re
 
@@ -23,13 +33,16 @@ import full_masks_ref as FM
 import projection_ref as PR
 import segment_ref as SR
 import training_targets_ref as TT
-from mpntrackseg_amd import capi
+from mpntrackseg_amd import capi, synth
 from oracle import tracker_oracle as T
+from pinned import forward_decisions
+from test_gpu_backward import check_against_oracle, make_model, native_grads
+from test_gpu_split import small_batch
 from test_tracker_tail_cpu import np_merge, np_prune, same_bits
 
 pytestmark = pytest.mark.gpu
 
-ERR_WORKSPACE = -3   # include/mpnhip.h
+ERR_ARG, ERR_WORKSPACE = -1, -3   # include/mpnhip.h
 GUARD = 4096
 FILL = 0xA5
 NODES = [64, 65]
@@ -50,21 +63,25 @@ def filled(shape, dtype):
     return torch.full((max(n, 1),), FILL, dtype=torch.uint8, device=dev())[:n].view(dtype).view(shape)
 
 
-def exact_call(name, advertised, call, outputs, own_threshold=False, ws=None):
-    """``call(workspace pointer, workspace_bytes) -> status``.  Returns the workspace (a later call may read what this one left)."""
+def exact_call(name, advertised, call, outputs, own_threshold=False, ws=None, refusal=None, offset=0):
+    """``call(workspace pointer, workspace_bytes) -> status``.  Returns the workspace (a later call may read what this one left).
+    ``refusal``: (status, message) of an operator that does not answer a short workspace with MPNHIP_ERR_WORKSPACE and the two
+    numbers; ``offset``: hand the operator ``workspace + offset`` (one that accepts unaligned buffers) -- still ``advertised`` bytes."""
     lib = capi.load()
     assert advertised > 0, name
     need = advertised
     if ws is None:
-        ws = torch.full((advertised + GUARD,), FILL, dtype=torch.uint8, device=dev())
+        ws = torch.full((offset + advertised + GUARD,), FILL, dtype=torch.uint8, device=dev())
     assert ws.data_ptr() % 256 == 0
+    ws = ws[offset:]
     snapshot = [ws.clone()] + [o.clone() for o in outputs]
     if own_threshold:
         assert call(capi.ptr(ws), 0) == ERR_WORKSPACE, name
         need = int(re.search(rb": workspace 0 < (\d+)", lib.mpnhip_last_error()).group(1))
         assert 0 < need <= advertised, (name, need, advertised)
-    assert call(capi.ptr(ws), need - 1) == ERR_WORKSPACE, name
-    assert ("%s: workspace %d < %d" % (name, need - 1, need)).encode() in lib.mpnhip_last_error()
+    status, message = refusal or (ERR_WORKSPACE, "%s: workspace %d < %d" % (name, need - 1, need))
+    assert call(capi.ptr(ws), need - 1) == status, name
+    assert message.encode() in lib.mpnhip_last_error()
     torch.cuda.synchronize()
     for t, s in zip([ws] + outputs, snapshot):   # refused before any launch, memset or copy
         assert torch.equal(t.view(torch.uint8), s.view(torch.uint8)), name
@@ -384,3 +401,232 @@ def test_tracking_loss(n_graphs):
         assert abs(got[i] - want_lv[i]) <= 1e-5 * max(1.0, abs(want_lv[i])), (i, got[i], want_lv[i])
     assert np.abs(g - want_g).max() <= 1e-6 * max(1.0, float(np.abs(want_g).max()))
     assert not g[:first].any() and got[1] == 0.0
+
+
+# ------------------------------------------------------------------------------------------------ the message-passing core
+CORE = {"fp32": (32, 3, "max", "fp32"), "fp32_split": (64, 4, "mean", "fp32_split"), "bf16": (64, 4, "sum", "bf16")}
+
+
+def core_case(case, n, steps=None):
+    d, L, agg, precision = CORE[case]
+    params = synth.model_params(d, L if steps is None else steps, agg, node_in_dim=48)
+    model = make_model(params, synth.make_weights(params, seed=14))
+    model.gemm_precision = precision
+    return model, synth.make_graph(n, E, T=6, seed=30 + n, node_in_dim=48)
+
+
+def same_bytes(got, want, what):
+    got, want = np.ascontiguousarray(got, np.float32), np.ascontiguousarray(want, np.float32)
+    assert got.shape == want.shape and got.tobytes() == want.tobytes(), "%s differs from the package's path" % what
+
+
+def core_exact_run(model, g, r, device=None, decisions=True):
+    """Training forward and backward through the C ABI, each in exactly its advertised workspace, and the same through the
+    package's own path: bitwise equal.  Signature and results of pinned.hip_run.
+    What this can NOT show: an interior region running into the next one (say slab_wp into slab_tail) corrupts both paths alike,
+    since they share the layout -- that is caught by the guard behind the last region, by the oracle cases (fp32 and split; the
+    bf16 case has none here) and by tools/diag/workspace_sizes.py against a known-good build, not by the bitwise comparison."""
+    lib = capi.load()
+    x, ei, ea, gl = on(g["x"]), on(g["edge_index"]), on(g["edge_attr"]), on(r)
+    n, e, L = x.shape[0], ea.shape[0], max(int(model.num_enc_steps), 1)
+    pg = capi.PreparedGraph(ei, n, validate=True)
+    params = model.hot_path_parameters()
+    grads = {id(p): torch.zeros_like(p) for p in params}   # (the backward adds into them)
+    keep = []
+    m = model.c_model(keep, grads=grads, n_edges=e)
+    logits, gx, gea = filled((L, e), torch.float32), filled(tuple(x.shape), torch.float32), filled(tuple(ea.shape), torch.float32)
+    capi.path_counters(reset=True)
+    fneed, bneed = lib.mpnhip_forward_workspace_bytes(m, n, e, 1), lib.mpnhip_backward_workspace_bytes(m, n, e)
+    fws = exact_call("forward", fneed,
+                     lambda w, b: lib.mpnhip_forward(m, capi.ptr(pg.buf), n, e, capi.ptr(x), capi.ptr(ea), capi.ptr(logits), None, None, w, b, 1,
+                                                     capi.stream_ptr()), [logits])
+    given = forward_decisions(model, pg, fws[:fneed]) if decisions else None
+    outputs = [gx, gea] + list(grads.values())
+
+    def backward(w, b, fwd_bytes=fneed):
+        return lib.mpnhip_backward(m, capi.ptr(pg.buf), n, e, capi.ptr(x), capi.ptr(ea), capi.ptr(gl), None, None, capi.ptr(gx), capi.ptr(gea),
+                                   capi.ptr(fws), fwd_bytes, w, b, capi.stream_ptr())
+    # a forward workspace one byte short is refused first, whatever the backward's own buffer
+    bws = torch.full((bneed + GUARD,), FILL, dtype=torch.uint8, device=dev())
+    snapshot = [t.clone() for t in [fws, bws] + outputs]
+    assert backward(capi.ptr(bws), bneed, fwd_bytes=fneed - 1) == ERR_WORKSPACE
+    assert lib.mpnhip_last_error() == b"backward: forward workspace %d < %d (must be the save_for_backward buffer)" % (fneed - 1, fneed)
+    torch.cuda.synchronize()
+    for t, s in zip([fws, bws] + outputs, snapshot):
+        assert torch.equal(t.view(torch.uint8), s.view(torch.uint8))
+    exact_call("backward", bneed, backward, outputs, ws=bws)
+    assert bool((fws[fneed:] == FILL).all()), "backward: wrote past the forward workspace"
+    counts = capi.path_counters(reset=True)
+    names = {id(p): k for k, p in model.named_parameters()}
+    out = {names[i]: t.double().cpu().numpy() for i, t in grads.items()}
+    out["grad_x"], out["grad_edge_attr"] = gx.double().cpu().numpy(), gea.double().cpu().numpy()
+    lo, px, pea, ppg = native_grads(model, g["x"], g["edge_index"], g["edge_attr"], r)
+    same_bytes(logits.cpu().numpy(), lo, "logits")
+    same_bytes(gx.cpu().numpy(), px, "grad_x")
+    same_bytes(gea.cpu().numpy(), pea, "grad_edge_attr")
+    for i, t in grads.items():
+        same_bytes(t.cpu().numpy(), ppg[names[i]], names[i])
+    return logits.double().cpu().numpy(), out, given, counts
+
+
+@pytest.mark.parametrize("n", NODES)
+@pytest.mark.parametrize("case", list(CORE))
+def test_core_forward_backward(case, n):
+    model, g = core_case(case, n)
+    L = int(model.num_enc_steps)
+    _, grads, _, counts = core_exact_run(model, g, synth.normal(12, (L, E)), decisions=False)
+    assert all(np.isfinite(v).all() for v in grads.values()) and all(np.abs(v).max() > 0 for v in grads.values())
+    keep = []
+    assert capi.load().mpnhip_backward_uses_side_stream(model.c_model(keep)) == (1 if L >= 4 else 0)
+    print({k: v for k, v in counts.items() if v})
+    # the kernels whose regions the case is here for ran
+    if case == "fp32_split":
+        assert counts["edge_chain_bwd_split"] == L and counts["gemm_tn_panel"] > 0 and counts["node_chain"] == L, counts
+    elif case == "bf16":   # (chain_bf16_train_ok: the fused bf16 kernels in both directions)
+        assert counts["edge_chain_fwd_bf16"] == L and counts["edge_chain_bwd_bf16"] == L, counts
+
+
+def test_core_structure_graph_matches_oracle(golden):
+    """The inputs of tests/test_gpu_backward.py::test_structure_graph[max], at its bound; and, max being piecewise, the decision-pinned
+    comparison of tests/test_gpu_pinned.py."""
+    z = golden("g4_structure.npz")
+    params = synth.model_params(32, 3, "max", node_in_dim=64)
+    g = {"x": z["x"], "edge_index": z["edge_index"], "edge_attr": z["edge_attr"]}
+    W = synth.make_weights(params, seed=8)
+    check_against_oracle(params, W, g, run=core_exact_run)
+    check_against_oracle(params, W, g, robust=True, run=core_exact_run)
+
+
+def test_core_split_batch_matches_oracle():
+    """The inputs of tests/test_gpu_split.py::test_split_gradients_match_oracle[64-True-mean], at its bound."""
+    g = small_batch(170)
+    params = synth.model_params(64, 3, "mean", node_in_dim=48)
+    check_against_oracle(params, synth.make_weights(params, seed=13), g, precision="fp32_split", run=core_exact_run)
+
+
+@pytest.mark.parametrize("n", NODES)
+@pytest.mark.parametrize("case", list(CORE))
+def test_core_forward_only(case, n):
+    """Inference (save 0) at the model's steps, and a model of zero steps with and without saving: logits and final features bitwise
+    those of the package's inference path."""
+    lib = capi.load()
+    for steps, save in ((None, 0), (0, 0), (0, 1)):
+        model, g = core_case(case, n, steps)
+        model.eval()
+        x, ei, ea = on(g["x"]), on(g["edge_index"]), on(g["edge_attr"])
+        L = max(int(model.num_enc_steps), 1)
+        pg = capi.PreparedGraph(ei, n, validate=True, full=bool(save))
+        keep = []
+        m = model.c_model(keep, n_edges=E)
+        logits, xo, eo = filled((L, E), torch.float32), filled((n, m.dn), torch.float32), filled((E, m.de), torch.float32)
+        exact_call("forward", lib.mpnhip_forward_workspace_bytes(m, n, E, save),
+                   lambda w, b: lib.mpnhip_forward(m, capi.ptr(pg.buf), n, E, capi.ptr(x), capi.ptr(ea), capi.ptr(logits), capi.ptr(xo), capi.ptr(eo),
+                                                   w, b, save, capi.stream_ptr()), [logits, xo, eo])
+        with torch.no_grad():
+            want = model.hot_path(x, ei, ea, return_state=True)   # (the inference path; saving changes no value)
+        for got, ref, what in zip((logits, xo, eo), want, ("logits", "x_out", "e_out")):
+            same_bytes(got.cpu().numpy(), ref.cpu().numpy(), "%s (steps %s, save %d)" % (what, steps, save))
+
+
+# ------------------------------------------------------------------------------------------------ the small operators
+@pytest.mark.parametrize("n", NODES)
+def test_meta_layer(n):
+    """One MetaLayer step (mpn.py:33-54) against the float64 oracle at the activations' bound of tests/test_gpu_modular.py (1e-4)."""
+    from oracle import mpn_oracle as O
+    lib = capi.load()
+    params = synth.model_params(32, 1, "mean", node_in_dim=48)
+    W = synth.make_weights(params, seed=15)
+    model = make_model(params, W).eval()
+    ei = synth.make_graph(n, E, T=6, seed=40 + n, node_in_dim=48)["edge_index"]
+    x, e = synth.normal(16, (n, 64)), synth.normal(17, (E, 32))   # [initial | current] features: both re-attached
+    keep = []
+    m = model.MPNet.core_struct(keep)
+    m.reattach_nodes = m.reattach_edges = 1
+    pg = capi.PreparedGraph(on(ei), n, validate=True)
+    x_d, e_d, x_new, e_new = on(x), on(e), filled((n, 32), torch.float32), filled((E, 16), torch.float32)
+    exact_call("meta_layer", lib.mpnhip_meta_layer_workspace_bytes(m, n, E),
+               lambda w, b: lib.mpnhip_meta_layer_forward(m, capi.ptr(pg.buf), n, E, capi.ptr(x_d), capi.ptr(e_d), capi.ptr(x_new), capi.ptr(e_new), w, b,
+                                                          capi.stream_ptr()), [x_new, e_new])
+    W64 = {k: torch.from_numpy(v).double() for k, v in W.items()}
+    xr, er = O.meta_layer(torch.from_numpy(x).double(), torch.from_numpy(ei), torch.from_numpy(e).double(), W64, "mean")
+    for got, ref in ((x_new, xr), (e_new, er)):
+        assert float((got.double().cpu() - ref).abs().max()) / max(1.0, float(ref.abs().max())) < 1e-4
+
+
+def test_mlp_forward():
+    """Three layers (two hidden activations ping-pong through the workspace), 65 rows; a single layer needs no workspace at all."""
+    lib = capi.load()
+    rows, dims = 65, [6, 18, 18, 16]
+    ws_ = [synth.normal(18, (dims[i + 1], dims[i]), stream=i, std=(2.0 / dims[i]) ** 0.5) for i in range(3)]
+    bs_ = [synth.normal(19, (dims[i + 1],), stream=i, std=0.1) for i in range(3)]
+    x = synth.normal(20, (rows, dims[0]))
+    tensors = [(on(w), on(b)) for w, b in zip(ws_, bs_)]
+    mlp = capi.fill_mlp(capi.Mlp(), tensors)
+    x_d, y = on(x), filled((rows, dims[-1]), torch.float32)
+    exact_call("mlp_forward", lib.mpnhip_mlp_workspace_bytes(mlp, rows),
+               lambda w, b: lib.mpnhip_mlp_forward(mlp, capi.ptr(x_d), capi.ptr(y), rows, w, b, capi.stream_ptr()), [y])
+    ref = x.astype(np.float64)
+    for w, b in zip(ws_, bs_):
+        ref = np.maximum(ref @ w.astype(np.float64).T + b, 0.0)
+    assert np.abs(y.cpu().numpy() - ref).max() / max(1.0, np.abs(ref).max()) < 1e-4
+    one = capi.fill_mlp(capi.Mlp(), tensors[:1])
+    y1 = filled((rows, dims[1]), torch.float32)
+    capi.check(lib.mpnhip_mlp_forward(one, capi.ptr(x_d), capi.ptr(y1), rows, None, 0, capi.stream_ptr()), "mlp_forward")
+    torch.cuda.synchronize()
+    ref1 = np.maximum(x.astype(np.float64) @ ws_[0].astype(np.float64).T + bs_[0], 0.0)
+    assert np.abs(y1.cpu().numpy() - ref1).max() / max(1.0, np.abs(ref1).max()) < 1e-4
+
+
+@pytest.mark.parametrize("offset", [0, 16])
+@pytest.mark.parametrize("rows16", [False, True], ids=["weight_grad", "weight_grad_bf16_rows"])
+def test_weight_grad(rows16, offset):
+    """300 rows, [64 x 48], two batches; the operator rounds its workspace pointer up to 256 itself (offset 16); bound of
+    tests/test_gpu_wgrad.py (3e-6 of the largest entry).  No rows: nothing to do, no workspace asked for."""
+    lib = capi.load()
+    rows, n_out, k_in, nb = 300, 64, 48, 2
+    dz, h = on(synth.normal(21, (nb, rows, n_out))), on(synth.normal(22, (nb, rows, k_in)))
+    if rows16:
+        dz, h = dz.bfloat16(), h.bfloat16()
+    gw, gb = torch.full((n_out, k_in), 0.25, device=dev()), torch.full((n_out,), -0.5, device=dev())   # "+=" into existing values
+    name = "weight_grad_bf16_rows" if rows16 else "weight_grad"
+    fn, size = getattr(lib, "mpnhip_" + name), getattr(lib, "mpnhip_%s_workspace_bytes" % name)
+    assert fn(None, None, 0, n_out, k_in, nb, capi.ptr(gw), capi.ptr(gb), None, 0, capi.stream_ptr()) == 0
+    exact_call(name, size(n_out, k_in, rows, nb),
+               lambda w, b: fn(capi.ptr(dz), capi.ptr(h), rows, n_out, k_in, nb, capi.ptr(gw), capi.ptr(gb), w, b, capi.stream_ptr()), [gw, gb],
+               offset=offset)
+    ref, refb = torch.einsum("bmo,bmc->oc", dz.double(), h.double()), dz.double().sum((0, 1))
+    assert float((gw.double() - 0.25 - ref).abs().max()) / float(ref.abs().max()) < 3e-6
+    assert float((gb.double() + 0.5 - refb).abs().max()) / float(refb.abs().max()) < 3e-6
+
+
+def test_bn_relu_dropout():
+    """300 x 20, BatchNorm1d (training) + ReLU against float64 torch at the bounds of tests/test_gpu_modular.py: activations 1e-4,
+    gradients 2e-4, running statistics 1e-5.  A short workspace is a bad ARGUMENT to these two (MPNHIP_ERR_ARG)."""
+    lib = capi.load()
+    m, n, eps, momentum = 300, 20, 1e-5, 0.1
+    z, dy = synth.normal(23, (m, n)), synth.normal(24, (m, n))
+    gamma, beta = 1.0 + 0.3 * synth.normal(25, (n,)), 0.2 * synth.normal(26, (n,))
+    bn = torch.nn.BatchNorm1d(n, eps=eps, momentum=momentum).double().train()
+    bn.weight.data, bn.bias.data = torch.from_numpy(gamma).double(), torch.from_numpy(beta).double()
+    zr = torch.from_numpy(z).double().requires_grad_(True)
+    yr = torch.relu(bn(zr))
+    (yr * torch.from_numpy(dy).double()).sum().backward()
+    z_d, dy_d, g_d, b_d = on(z), on(dy), on(gamma), on(beta)
+    rm, rv = torch.zeros(n, device=dev()), torch.ones(n, device=dev())
+    y, mean, invstd = filled((m, n), torch.float32), filled((n,), torch.float32), filled((n,), torch.float32)
+    need = lib.mpnhip_bn_dropout_workspace_bytes(m, n)
+
+    def rel(a, b):
+        return float((a.double().cpu() - b.detach()).abs().max()) / max(1.0, float(b.detach().abs().max()))
+    exact_call("bn_relu_dropout_forward", need,
+               lambda w, b: lib.mpnhip_bn_relu_dropout_forward(capi.ptr(z_d), m, n, 1, capi.ptr(g_d), capi.ptr(b_d), capi.ptr(rm), capi.ptr(rv), momentum,
+                                                               eps, 1, 0.0, 0, capi.ptr(y), capi.ptr(mean), capi.ptr(invstd), w, b, capi.stream_ptr()),
+               [y, mean, invstd, rm, rv], refusal=(ERR_ARG, "bn_relu_dropout_forward: workspace too small"))
+    assert rel(y, yr) < 1e-4 and rel(rm, bn.running_mean) < 1e-5 and rel(rv, bn.running_var) < 1e-5
+    dz, dg, db = filled((m, n), torch.float32), torch.zeros(n, device=dev()), torch.zeros(n, device=dev())
+    exact_call("bn_relu_dropout_backward", need,
+               lambda w, b: lib.mpnhip_bn_relu_dropout_backward(capi.ptr(dy_d), capi.ptr(z_d), m, n, 1, capi.ptr(g_d), capi.ptr(b_d), capi.ptr(mean),
+                                                                capi.ptr(invstd), 1, 0.0, 0, capi.ptr(dz), capi.ptr(dg), capi.ptr(db), w, b,
+                                                                capi.stream_ptr()),
+               [dz, dg, db], refusal=(ERR_ARG, "bn_relu_dropout_backward: workspace too small"))
+    assert rel(dz, zr.grad) < 2e-4 and rel(dg, bn.weight.grad) < 2e-4 and rel(db, bn.bias.grad) < 2e-4
