@@ -614,6 +614,53 @@ int mpnhip_mask_run_events(const int32_t* labels, int64_t n_frames, int64_t hw, 
                            void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The pixel work of the MOTS metrics (sMOTSA, IDF1, ...): compute_mots_metrics (utils/evaluation.py:87-102) =
+ * MOTChallengeEvalKit/MOTS/MOTS_metrics.py.  Masks of one MOTS frame are disjoint (mots_common/io.py:57-62), so a frame is one
+ * label image per side, as above: [n_frames, img_w, img_h] int32, position p = x * img_h + y, hw = img_h * img_w < 2^31, at most
+ * 65535 frames per call.  A side's objects are a list grouped by frame (a_ptr / b_ptr [n_frames + 1], device int32, ascending:
+ * side a = ground truth, side b = prediction); a label is the list entry that owns the pixel, a label outside its frame's
+ * entry range counts as -1.  Integer atomics and integer compares only: the same bits on every call
+ * (tests/mots_metrics_ref.py restates the three operators in numpy).
+ * ------------------------------------------------------------------------------------------- */
+/* Bytes that any of the three calls below needs for these sizes (mpnhip_label_overlap needs none).  0 for sizes the calls
+ * refuse, and when nothing is needed. */
+size_t mpnhip_mots_workspace_bytes(int64_t n_runs, int64_t n_a, int64_t n_b, int64_t n_frames, int64_t hw);
+/* The inverse of mpnhip_mask_run_events: labels [n_frames, hw] = -1, then entry run_entry[r] over the positions
+ * [run_begin[r], run_end[r]) of its frame (run_* [n_runs], device int32; 0 <= begin < end <= hw; frame_ptr [n_frames + 1] of
+ * the list of n_entries entries).  A run continues across column ends, as COCO's do.  A run whose entry leaves the list or
+ * whose range leaves [0, hw] paints nothing.  Overlapping runs of different entries are the caller's error: which one a pixel
+ * keeps is unspecified.  The work is spread by painted pixel, not by run. */
+int mpnhip_paint_label_runs(const int32_t* run_entry, const int32_t* run_begin, const int32_t* run_end, int64_t n_runs,
+                            const int32_t* frame_ptr, int64_t n_entries, int64_t n_frames, int64_t hw, int32_t* labels, void* workspace,
+                            size_t workspace_bytes, void* stream);
+/* The joint histogram of two label images of the same frames (both starting on a 16-byte boundary).  table [table_cells]
+ * (int32, zeroed by the call); table_ptr [n_frames + 1] (device int64): frame f owns the (na_f + 1) x (nb_f + 1) cells at
+ * table_ptr[f], cell [(ia + 1) * (nb_f + 1) + (ib + 1)] = number of pixels whose labels are the frame's entries (ia, ib); row 0
+ * and column 0 stand for "no object".  A frame's cells sum to hw, its row sums are the areas of the a-entries, its column sums
+ * those of the b-entries.  A frame whose cells would leave the table is skipped.  table_ptr_host: the same numbers in host
+ * memory, or NULL; read only to count per frame which form of the kernel it takes (mpnhip_debug_counters: label_overlap_lds
+ * for a table of at most 4096 cells, label_overlap_global beyond).  MPNHIP_ERR_UNSUPPORTED for table_cells >= 2^31. */
+int mpnhip_label_overlap(const int32_t* labels_a, const int32_t* labels_b, const int32_t* a_ptr, int64_t n_a, const int32_t* b_ptr,
+                         int64_t n_b, const int64_t* table_ptr, const int64_t* table_ptr_host, int64_t n_frames, int64_t hw,
+                         int32_t* table, int64_t table_cells, void* stream);
+/* The kit's decisions from the table, in exact integer form.  a_ignore [n_a] (uint8, 1 = part of the frame's ignore region),
+ * a_traj [n_a] / b_traj [n_b] (int32): trajectory index of every entry, -1 = none.  With i = cell, A = row sum, B = column
+ * sum, u = A + B - i:
+ *   per a-entry that is not ignore: match_b = the b-entry (index into the list) with 2 i > u (c > 0.5, MOTS_metrics.py:253-254;
+ *       at most one among disjoint masks) or -1, inter = its i, uni = its u (0 without a match).  Ignore entries: -1, 0, 0.
+ *   per b-entry: b_matched (uint8) = some a-entry matched it, b_ignored (uint8) = 2 * (sum of i over the ignore a-entries) > B
+ *       (:272-273, intersection over the prediction's own area), b_area = B.
+ *   id_match [n_a_traj, n_b_traj] (int32, zeroed by the call): + 1 for every pair of an a-entry that is not ignore and a b-entry
+ *       of one frame with 2 i >= u and u > 0 (the complement of overlap < 0.5, :529-535) whose trajectory indices are in range.
+ * A pair of two EMPTY masks (u = 0) matches nowhere; the kit's 0 / 0 = NaN there counts as matched in its IDF1 part.
+ * MPNHIP_ERR_UNSUPPORTED for table_cells or n_a_traj * n_b_traj >= 2^31. */
+int mpnhip_mots_frame_match(const int32_t* table, int64_t table_cells, const int64_t* table_ptr, const int32_t* a_ptr, int64_t n_a,
+                            const int32_t* b_ptr, int64_t n_b, int64_t n_frames, const unsigned char* a_ignore, const int32_t* a_traj,
+                            const int32_t* b_traj, int64_t n_a_traj, int64_t n_b_traj, int32_t* match_b, int32_t* inter, int32_t* uni,
+                            unsigned char* b_matched, unsigned char* b_ignored, int32_t* b_area, int32_t* id_match, void* workspace,
+                            size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Measurement helpers used by bench.py (HIP events on the launch stream; these synchronise).
  * ------------------------------------------------------------------------------------------- */
 /* In-stream kernel timing of the real hot path: while enabled, mpnhip_forward brackets (a) the first-layer

@@ -165,6 +165,10 @@ SIGNATURES = {
     "mpnhip_paste_unique_masks": (_I, [_P, _L, _I, _I, _P, _P, _L, _P, _L, _I, _I, C.c_float, _P, _P, _P, _Z, _P]),
     "mpnhip_mask_run_events_count": (_I, [_P, _L, _L, _L, _P, _P, _P, _Z, _P]),
     "mpnhip_mask_run_events": (_I, [_P, _L, _L, _L, _L, _P, _P, _Z, _P]),
+    "mpnhip_mots_workspace_bytes": (_Z, [_L, _L, _L, _L, _L]),
+    "mpnhip_paint_label_runs": (_I, [_P, _P, _P, _L, _P, _L, _L, _L, _P, _P, _Z, _P]),
+    "mpnhip_label_overlap": (_I, [_P, _P, _P, _L, _P, _L, _P, _P, _L, _L, _P, _L, _P]),
+    "mpnhip_mots_frame_match": (_I, [_P, _L, _P, _P, _L, _P, _L, _L, _P, _P, _P, _L, _L, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _P]),
     "mpnhip_profile_enable": (_I, [_I]),
     "mpnhip_edge_chain_active": (_I, [C.POINTER(Model)]),
     "mpnhip_profile_read": (_I, [C.POINTER(C.c_float), C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(C.c_int),

@@ -366,3 +366,40 @@ def mots_sequence(model, x, edge_index, edge_attr, reid_emb_dists, frame_num_per
     rles = to_full_masks(res.node_preds, boxes, frame_num_per_node, res.keep, img_shape, mask_threshold=mask_threshold,
                          frames_per_launch=frames_per_launch)
     return res, rles
+
+
+@capi.on_tensor_device
+def evaluate_mots_sequence(node_preds, boxes, frame_num_per_node, ped_ids, label, keep, img_shape, gt, seq_length, mask_threshold=0.5,
+                           frames_per_launch=8, class_id=2, ignore_class=10, details=False):
+    """The MOTS metrics (``compute_mots_metrics``, utils/evaluation.py:87-102) of a tracked sequence against the ground truth
+    ``gt`` (a MOTS text file, or what ``mots_eval.load_mots_txt`` returns) over the frames ``0 .. seq_length``: what
+    ``mots_eval.evaluate_mots_files`` gives for the rows ``save_results_to_file`` writes for the same arguments, without the
+    run-length strings and the text file -- per launch the prediction's label images come straight from
+    ``masks.paste_unique_masks`` (every kept detection pastes, as in ``to_full_masks``) and go into the overlap kernel.
+
+    ``node_preds``, ``boxes``, ``frame_num_per_node``, ``keep``, ``img_shape``, ``mask_threshold``, ``frames_per_launch`` as
+    ``to_full_masks``; ``ped_ids`` and ``label`` as ``save_results_to_file``: a detection's trajectory is its MOTS id
+    ``ped_id + label * 1000 + 1``, and only the detections with ``label == class_id`` are scored.  Returns the dict of
+    ``mots_eval.metrics_from_matches``."""
+    from . import masks as M, mots_eval as ME
+    capi.require_device(node_preds)
+    N = int(node_preds.shape[0])
+    as_np = lambda v: np.asarray(v.detach().cpu() if isinstance(v, torch.Tensor) else v)
+    keep_h, frame_h = as_np(keep).reshape(-1).astype(bool), as_np(frame_num_per_node).reshape(-1).astype(np.int64)
+    ped = as_np(ped_ids).reshape(-1).astype(np.int64)
+    lab = np.broadcast_to(as_np(label).astype(np.int64).reshape(-1), ped.shape) if np.ndim(as_np(label)) else np.full(ped.shape, int(label), np.int64)
+    if not (keep_h.size == frame_h.size == ped.size == N == len(boxes)):
+        raise MpnhipError("one box, frame number, id and keep flag per detection (%d detections)" % N)
+    kept = np.flatnonzero(keep_h)
+    kept = kept[np.argsort(frame_h[kept], kind="stable")]
+    ids = ped[kept] + lab[kept] * 1000 + 1
+    if np.unique(np.stack((frame_h[kept], ids)), axis=1).shape[1] != kept.size:
+        raise ValueError("Multiple objects with one track id in a frame")
+    scored = lab[kept] == class_id
+    traj_ids = np.unique(ids[scored])
+    b_traj = np.where(scored, np.searchsorted(traj_ids, ids), -1).astype(np.int64)
+
+    def b_labels(frames, b_ptr, b_entries, hw):
+        return M.paste_unique_masks(node_preds, boxes, b_ptr, img_shape, mask_threshold, det_ids=kept[b_entries])
+    return ME._evaluate(ME._as_loaded(gt), seq_length, class_id, ignore_class, frames_per_launch, node_preds.device, frame_h[kept], b_traj,
+                        traj_ids, b_labels, img_shape, details)

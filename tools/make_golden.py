@@ -47,6 +47,10 @@ Fixtures:
                                self loops, a batch, several blocks of edges) and MOTNeuralSolver._compute_loss WITH its segmentation term
                                (+ autograd w.r.t. the logits and the mask predictions) on six cases incl. a batch of three graphs, and end
                                to end through g6's model.  Inputs come from tests/training_targets_ref.py.  Only with --only g21.
+  g22_mots_metrics.npz         MOTSMetrics.compute_metrics_per_sequence + compute_clearmot of the vendored MOTS evaluation kit on two scenes
+                               of id images: "cases" (12 frames of 37 x 29 with an id switch, a fragment, ignore regions, a pair at IoU
+                               exactly 0.5, ...) and "crowded" (3 frames of 64 x 48 with 110 objects a side).  pycocotools is not
+                               installed: the kit runs over a numpy stand-in built on the project's RLE codec.  Only with --only g22.
 
 Usage:  python tools/make_golden.py [--only g1,g2,...]
 """
@@ -1297,6 +1301,219 @@ def gen_g21():
           "bytes", os.path.getsize(path))
 
 
+# ------------------------------------------------------------------ g22: the MOTS evaluation kit
+def _install_pycocotools_standin():
+    """``pycocotools.mask`` as the kit uses it (area, merge, iou with the crowd flag) in numpy over the project's codec
+    (mpntrackseg_amd.masks): a mask is {'size': [h, w], 'counts': bytes}.  As in the C library, merging no masks gives a 0 x 0
+    mask, and iou is -1 for masks of different sizes -- so a frame without ignore rows ignores nothing."""
+    from mpntrackseg_amd import masks as M
+
+    def decode(m):
+        h, w = m["size"]
+        if h * w == 0:
+            return np.zeros((h, w), bool)
+        c = m["counts"]
+        return M.rle_to_mask(c.decode("ascii") if isinstance(c, bytes) else c, h, w).astype(bool)
+
+    def encode(mask):
+        h, w = mask.shape
+        flat = mask.T.reshape(-1).astype(np.int8)
+        edges = np.flatnonzero(np.diff(np.concatenate(([0], flat, [0]))))
+        return {"size": [h, w], "counts": M.rle_string(M.rle_counts_from_events(edges[edges < h * w], h * w)).encode("ascii")}
+
+    def area(m):
+        return [int(decode(x).sum()) for x in m] if isinstance(m, list) else int(decode(m).sum())
+
+    def merge(ms, intersect=False):
+        if len(ms) == 0:
+            return {"size": [0, 0], "counts": b""}
+        out = decode(ms[0])
+        for x in ms[1:]:
+            out = (out & decode(x)) if intersect else (out | decode(x))
+        return encode(out)
+
+    def iou(dt, gt, iscrowd):
+        if len(dt) == 0 or len(gt) == 0:
+            return []
+        out = np.zeros((len(dt), len(gt)), np.float64)
+        for g, gm in enumerate(gt):
+            G = decode(gm)
+            for d, dm in enumerate(dt):
+                D = decode(dm)
+                if D.shape != G.shape:
+                    out[d, g] = -1.0
+                    continue
+                i = np.float64((D & G).sum())
+                u = np.float64(D.sum()) if iscrowd[g] else np.float64(D.sum()) + np.float64(G.sum()) - i
+                with np.errstate(invalid="ignore", divide="ignore"):
+                    out[d, g] = i / u
+        return out
+
+    pkg, mod = types.ModuleType("pycocotools"), types.ModuleType("pycocotools.mask")
+    mod.area, mod.merge, mod.iou, mod.decode, mod.encode = area, merge, iou, decode, encode
+    pkg.mask = mod
+    sys.modules["pycocotools"], sys.modules["pycocotools.mask"] = pkg, mod
+
+
+def _g22_rect(img, f, obj, y0, y1, x0, x1):
+    assert (img[f, y0:y1, x0:x1] == 0).all(), (f, obj)   # masks of a frame are disjoint
+    img[f, y0:y1, x0:x1] = obj
+
+
+def _g22_cases():
+    """12 frames of 37 x 29, every case of the metric at least once (the asserts of gen_g22 check that they are there)"""
+    F, H, W = 12, 37, 29
+    gt, pr = np.zeros((F, H, W), np.uint16), np.zeros((F, H, W), np.uint16)
+    jit = (synth.uniform01(22, 4 * F * 2, stream=1) * 2).astype(np.int64).reshape(4, F, 2)   # prediction offsets in {0, 1}
+    for f in range(F):
+        if f in (0, 1, 2, 3, 4, 5, 8, 9):
+            _g22_rect(gt, f, 10000, 0, H, 22, W)                      # the ignore region (none in frames 6, 7, 10, 11)
+        if f <= 9:                                                    # 2001: tracked throughout, the prediction changes its id
+            _g22_rect(gt, f, 2001, 2, 10, 2, 7)
+            dy, dx = jit[0, f]
+            if f == 2:                                                # ... and once reaches into a second ignore patch, still matched
+                _g22_rect(gt, f, 10001, 2, 10, 7, 9)
+                _g22_rect(pr, f, 2001, 2, 10, 2, 9)
+            else:
+                _g22_rect(pr, f, 2001 if f < 6 else 2007, 2 + dy, 10 + dy, 2 + dx, 7 + dx)
+            _g22_rect(gt, f, 2002, 14, 22, 2, 7)                      # 2002: missed in frames 3-5 and 8-9 (a fragment; partly tracked)
+            if f in (0, 1, 2, 6, 7):
+                dy, dx = jit[1, f]
+                _g22_rect(pr, f, 2002, 14 + dy, 22 + dy, 2 + dx, 7 + dx)
+        if 2 <= f <= 7:
+            _g22_rect(gt, f, 2003, 26, 34, 2, 7)                      # 2003: never found
+        if f in (0, 1, 8, 9):                                         # 2004: leaves and comes back
+            dy, dx = jit[2, f]
+            _g22_rect(gt, f, 2004, 2, 10, 10, 15)
+            _g22_rect(pr, f, 2004, 2 + dy, 10 + dy, 10 + dx, 15 + dx)
+        if f in (4, 5):                                               # 2005: IoU exactly 4 / 8 in frame 4, found in frame 5
+            _g22_rect(gt, f, 2005, 14, 17, 10, 12)
+            _g22_rect(pr, f, 2005, 15 if f == 4 else 14, 18 if f == 4 else 17, 10, 12)
+        if f == 1:
+            _g22_rect(pr, f, 2009, 26, 32, 20, 26)                    # four of six columns inside the ignore region
+        if f in (3, 10):
+            _g22_rect(pr, f, 2008, 26, 30, 12, 16)                    # a false positive; frame 10 has no ground truth at all
+        if f == 6:
+            _g22_rect(gt, f, 1001, 26, 32, 12, 18)                    # a car under a prediction
+            _g22_rect(pr, f, 2010, 26, 32, 12, 18)
+        if f == 11:
+            _g22_rect(gt, f, 2006, 5, 10, 5, 10)                      # a frame without predictions
+    return gt, pr, 12   # seqlength 12: frame 12 is empty on both sides
+
+
+def _g22_crowded(n_obj=110):
+    """3 frames of 64 x 48: a 16 x 12 grid of 4 x 4 cells; n_obj cells hold a ground-truth object and a prediction (random
+    sub-rectangles of the cell), 5 a prediction alone, 3 an ignore patch (one with a prediction inside)"""
+    F, H, W, C = 3, 64, 48, 4
+    cells = (H // C) * (W // C)
+    gt, pr = np.zeros((F, H, W), np.uint16), np.zeros((F, H, W), np.uint16)
+    for f in range(F):
+        perm = np.argsort(synth.splitmix64(22, cells, stream=10 + f), kind="stable")
+        u = (synth.uniform01(22, cells * 8, stream=20 + f).reshape(cells, 8) * 2).astype(np.int64)   # {0, 1}
+
+        def sub(cell, k):   # rows / columns [a, b) of a sub-rectangle of the cell, at least 2 x 2
+            y, x = (cell // (W // C)) * C, (cell % (W // C)) * C
+            return y + u[cell, k], y + C - u[cell, k + 1], x + u[cell, k + 2], x + C - u[cell, k + 3]
+        for k in range(n_obj):
+            _g22_rect(gt, f, 2001 + k, *sub(perm[k], 0))
+            pid = 2001 + (k ^ 1 if (f == 1 and k < 20) else k)       # twenty pairs swap their ids in the middle frame
+            _g22_rect(pr, f, pid, *sub(perm[k], 4))
+        for k in range(n_obj, n_obj + 5):
+            _g22_rect(pr, f, 2001 + k + 100, *sub(perm[k], 4))
+        for j, k in enumerate(range(n_obj + 5, n_obj + 8)):
+            y, x = (perm[k] // (W // C)) * C, (perm[k] % (W // C)) * C
+            _g22_rect(gt, f, 10000 + j, y, y + C, x, x + C)
+            if j == 0:
+                _g22_rect(pr, f, 2001 + k + 100, *sub(perm[k], 4))
+    return gt, pr, F - 1
+
+
+def gen_g22():
+    """The MOTS evaluation kit's OWN MOTSMetrics.compute_metrics_per_sequence + compute_clearmot
+    (MOTChallengeEvalKit/MOTS/MOTS_metrics.py) on text files written from id images.  Two stand-ins: collections.Iterable
+    (Metrics.py:2 predates Python 3.10) and a numpy pycocotools.mask (_install_pycocotools_standin) -- so the fixture rests on
+    the project's RLE codec (mpntrackseg_amd.masks, pinned by g20's sample line) for decoding the masks.  Per-frame counts are
+    differences of the kit's totals over the sequence cut after every frame; the matched-id sequences are read off the calls
+    of its overlap function."""
+    import collections
+    import collections.abc
+    import tempfile
+    collections.Iterable = collections.abc.Iterable
+    _install_pycocotools_standin()
+    sys.path.insert(0, "/root/reference/MOTChallengeEvalKit/src")
+    from MOTChallengeEvalKit.MOTS import MOTS_metrics as MM
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    import mots_metrics_ref as R
+
+    loaded = []
+    kit_load = MM.load_txt
+
+    def keeping_load(path):
+        loaded.append(kit_load(path))
+        return loaded[-1]
+    MM.load_txt = keeping_load
+
+    def run(rows_gt, rows_pr, seq_length):
+        matched = {}
+
+        def overlap(a, b, criterion="union"):
+            c = MM.mask_iou(a, b, criterion)
+            if criterion == "union" and c > 0.5:
+                matched[id(a)] = b.track_id
+            return c
+        del loaded[:]
+        with tempfile.TemporaryDirectory() as d:
+            R.write_txt(os.path.join(d, "gt.txt"), rows_gt)
+            R.write_txt(os.path.join(d, "pred.txt"), rows_pr)
+            with open(os.path.join(d, "seqinfo.ini"), "w") as fh:
+                fh.write("[Sequence]\nname=g22\nseqlength=%d\n" % seq_length)
+            m = MM.MOTSMetrics("g22")
+            m.compute_metrics_per_sequence("g22", os.path.join(d, "pred.txt"), os.path.join(d, "gt.txt"), d, "MOTS",
+                                           overlap_function=overlap)
+            m.compute_clearmot()
+        seqs = collections.OrderedDict()
+        for f in sorted(loaded[0]):
+            for obj in loaded[0][f]:
+                if obj.class_id == MM.CLASS_ID and f <= seq_length:
+                    seqs.setdefault(obj.track_id, []).append(matched.get(id(obj), -1))
+        return m, seqs
+
+    rec = {}
+    for name, (gt, pr, seq_length) in (("cases", _g22_cases()), ("crowded", _g22_crowded())):
+        rows_gt, rows_pr = R.id_image_rows(gt), R.id_image_rows(pr)
+        m, seqs = run(rows_gt, rows_pr, seq_length)
+        cum = np.zeros((seq_length + 2, 4), np.int64)
+        for f in range(seq_length + 1):   # the kit over the frames 0 .. f alone
+            cut = lambda rows: [r for r in rows if int(r.split(" ")[0]) <= f]
+            mf, _ = run(cut(rows_gt), cut(rows_pr), f)
+            cum[f + 1] = (mf.tp, mf.fp, mf.fn, mf.n_itr)
+        assert tuple(cum[-1]) == (m.tp, m.fp, m.fn, m.n_itr)
+        rec[f"{name}:gt"], rec[f"{name}:pred"], rec[f"{name}:seq_length"] = gt, pr, np.int64(seq_length)
+        rec[f"{name}:per_frame"] = np.diff(cum, axis=0)
+        for k in m.names:
+            rec[f"{name}:m:{k}"] = np.float64(getattr(m, k))
+        gt_ids = sorted(seqs)
+        rec[f"{name}:traj_ids"] = np.asarray(gt_ids, np.int64)
+        rec[f"{name}:traj_ptr"] = np.concatenate(([0], np.cumsum([len(seqs[i]) for i in gt_ids]))).astype(np.int64)
+        rec[f"{name}:traj_matched"] = np.asarray([v for i in gt_ids for v in seqs[i]], np.int64)
+        print("g22", name, {k: getattr(m, k) for k in ("sMOTSA", "MOTSA", "MOTSP", "IDF1", "tp", "fp", "fn", "n_itr", "id_switches",
+                                                       "fragments", "MT", "PT", "ML", "IDTP")})
+        if name == "cases":
+            assert m.id_switches >= 1 and m.fragments >= 1 and m.fn >= 1 and m.fp >= 1 and m.n_itr >= 1 and min(m.MT, m.PT, m.ML) >= 1
+            L = R.scene_lists(gt, pr)
+            t, tp = R.label_overlap(L["labels_a"], L["labels_b"], L["a_ptr"], L["b_ptr"])
+            o = R.frame_match(t, tp, L["a_ptr"], L["b_ptr"], L["a_ignore"], L["a_traj"], L["b_traj"], L["n_a_traj"], L["n_b_traj"])
+            assert o["id_match"].sum() == m.tp + 1                       # the pair at IoU exactly 0.5
+            assert (o["b_ignored"] & ~o["b_matched"]).sum() == m.n_itr
+            assert seqs[2004] == [2004] * 4 and seqs[2003] == [-1] * 6   # back after a gap; never found
+        else:
+            assert all(min(len(np.unique(gt[f])), len(np.unique(pr[f]))) > 100 for f in range(gt.shape[0]))
+    MM.load_txt = kit_load
+    path = os.path.join(GOLD, "g22_mots_metrics.npz")
+    np.savez_compressed(path, **rec)
+    print("g22 bytes", os.path.getsize(path))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", default="g0,g1,g4,g5,g6,g7,g8,g2,g3,g11,g12,g10,g9")
@@ -1327,6 +1544,7 @@ def main():
     if "g19" in only: gen_g19()
     if "g20" in only: gen_g20()
     if "g21" in only: gen_g21()
+    if "g22" in only: gen_g22()
 
 
 if __name__ == "__main__":
