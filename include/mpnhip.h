@@ -661,6 +661,68 @@ int mpnhip_mots_frame_match(const int32_t* table, int64_t table_cells, const int
                             size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * HOTA of a KITTI-MOTS sequence: eval_kitti_mots (utils/evaluation.py:127-135) = TrackEval's KittiMOTS preprocessing
+ * (datasets/kitti_mots.py:299-387) and HOTA.eval_sequence (metrics/hota.py:25-117) for one class, from the tables of
+ * mpnhip_label_overlap.  Lists, a_ptr / b_ptr and the table as above.  A launch's similarities are one block of float64:
+ * frame f owns na_f x nb_f cells at sim_ptr[f] (device int64 [n_frames + 1]), cell [ia * nb_f + ib]; sim_cells is their
+ * number (< 2^31).  a_traj [n_a] / b_traj [n_b] (int32): index of the entry's id among the n_gt_ids / n_tr_ids ids of the
+ * sequence; an entry whose index is outside its range (-1: an ignore row, a prediction of another class) takes no part.  A
+ * b-entry is KEPT when its index is in range and b_removed is 0; an a-entry when its index is in range.  The accumulators
+ * (potential, gt_count, tr_count, tp, loca, matches_count) belong to the caller, who zeroes them before the first launch of a
+ * sequence; the launches are issued in frame order.  No floating-point atomics: a float64 sum is one thread adding in frame
+ * order, or a tree whose shape depends on the sizes alone -- the same bits on every call (tests/hota_ref.py restates the five
+ * operators in numpy).  Every index read from a caller's array is clamped or checked before it is used.
+ * MPNHIP_ERR_UNSUPPORTED for n_gt_ids * n_tr_ids * MPNHIP_HOTA_ALPHAS >= 2^31 or n_frames * (n_gt_ids + n_tr_ids) >= 2^31.
+ * ------------------------------------------------------------------------------------------- */
+#define MPNHIP_HOTA_ALPHAS 19   /* np.arange(0.05, 0.99, 0.05), hota.py:17 */
+/* Bytes that any of the five calls below needs for these sizes.  0 for sizes the calls refuse. */
+size_t mpnhip_hota_workspace_bytes(int64_t n_a, int64_t n_b, int64_t n_frames, int64_t n_gt_ids, int64_t n_tr_ids);
+/* a_ignore [n_a] (uint8, 1 = part of the frame's ignore region), b_scored [n_b] (uint8, 1 = a prediction of the evaluated class).
+ * With i = cell, A = row sum, B = column sum (both with the "no object" cells), u = A + B - i:
+ *   sim [sim_cells] (zeroed by the call) = double(i) / double(u) for an a-entry that is not ignore and a scored b-entry with
+ *       i > 0, else 0: an empty mask has similarity 0 with everything.
+ *   b_removed [n_b] (uint8) = scored, unmatched and 2 * (sum of i over the frame's ignore rows) > B (kitti_mots.py:336-344).
+ *       A scored b-entry is matched iff it is the FIRST column some object row is eligible with, eligible = i > 0 and
+ *       2 i >= u (the complement of "< 0.5 - eps", :329).  Masks of one side are disjoint, so the kit's assignment (:330) is
+ *       that, except for an object split exactly in half by two predictions: there the kit's choice follows scipy's tie order,
+ *       here the prediction earlier in the list is the matched one.
+ *   row_sum [n_a] / col_sum [n_b] (float64): the sums of sim over the kept entries of the other side (similarity.sum(1) /
+ *       .sum(0) of hota.py:57 after the removal); 0 for an ignore row, a removed or an unscored column. */
+int mpnhip_hota_frame_similarity(const int32_t* table, int64_t table_cells, const int64_t* table_ptr, const int32_t* a_ptr, int64_t n_a,
+                                 const int32_t* b_ptr, int64_t n_b, int64_t n_frames, const unsigned char* a_ignore,
+                                 const unsigned char* b_scored, const int64_t* sim_ptr, int64_t sim_cells, double* sim,
+                                 unsigned char* b_removed, double* row_sum, double* col_sum, void* workspace, size_t workspace_bytes,
+                                 void* stream);
+/* hota.py:53-65 for one launch: potential [n_gt_ids, n_tr_ids] (float64) += sim / (row_sum + col_sum - sim) of every kept pair
+ * of a frame where that denominator exceeds eps, frames in order; gt_count [n_gt_ids] / tr_count [n_tr_ids] (int32) += 1 per
+ * kept entry.  Two kept entries of one id in a frame are the caller's error: one of them is the id's entry. */
+int mpnhip_hota_accumulate_alignment(const double* sim, int64_t sim_cells, const int64_t* sim_ptr, const int32_t* a_ptr, int64_t n_a,
+                                     const int32_t* b_ptr, int64_t n_b, int64_t n_frames, const int32_t* a_traj, const int32_t* b_traj,
+                                     const unsigned char* b_removed, const double* row_sum, const double* col_sum, int64_t n_gt_ids,
+                                     int64_t n_tr_ids, double* potential, int32_t* gt_count, int32_t* tr_count, void* workspace,
+                                     size_t workspace_bytes, void* stream);
+/* hota.py:68, :85, once all launches are accumulated: score [sim_cells] (the layout of sim; zeroed by the call) = potential /
+ * (gt_count + tr_count - potential) * sim for a kept pair, 0 elsewhere -- the cells of the host's assignment problems. */
+int mpnhip_hota_frame_scores(const double* sim, int64_t sim_cells, const int64_t* sim_ptr, const int32_t* a_ptr, int64_t n_a,
+                             const int32_t* b_ptr, int64_t n_b, int64_t n_frames, const int32_t* a_traj, const int32_t* b_traj,
+                             const unsigned char* b_removed, int64_t n_gt_ids, int64_t n_tr_ids, const double* potential,
+                             const int32_t* gt_count, const int32_t* tr_count, double* score, void* stream);
+/* hota.py:91-101 for one launch.  match_b [n_a] (int32): the b-entry (index into the list) the host's assignment gave the
+ * a-entry, or -1; a pair counts when both are kept entries of one frame.  alphas: MPNHIP_HOTA_ALPHAS float64 in HOST memory.
+ * For every alpha with sim >= alpha - eps: tp [alphas] (int64) += 1, loca [alphas] (float64) += sim (a frame's terms through a
+ * fixed tree, the frames in order), matches_count [alphas, n_gt_ids, n_tr_ids] (int32) += 1 at the pair's ids. */
+int mpnhip_hota_alpha_accumulate(const double* sim, int64_t sim_cells, const int64_t* sim_ptr, const int32_t* a_ptr, int64_t n_a,
+                                 const int32_t* b_ptr, int64_t n_b, int64_t n_frames, const int32_t* a_traj, const int32_t* b_traj,
+                                 const unsigned char* b_removed, const int32_t* match_b, const double* alphas, int64_t n_gt_ids,
+                                 int64_t n_tr_ids, int64_t* tp, double* loca, int32_t* matches_count, void* workspace,
+                                 size_t workspace_bytes, void* stream);
+/* hota.py:105-112 without the division by max(1, TP): out [alphas, 3] (float64) = the sums over (g, t) of mc * (mc / max(1,
+ * gt_count + tr_count - mc)), mc * (mc / max(1, gt_count)) and mc * (mc / max(1, tr_count)) with mc = matches_count[alpha, g, t]
+ * (the AssA, AssRe and AssPr numerators). */
+int mpnhip_hota_association(const int32_t* matches_count, const int32_t* gt_count, const int32_t* tr_count, int64_t n_gt_ids,
+                            int64_t n_tr_ids, double* out, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Measurement helpers used by bench.py (HIP events on the launch stream; these synchronise).
  * ------------------------------------------------------------------------------------------- */
 /* In-stream kernel timing of the real hot path: while enabled, mpnhip_forward brackets (a) the first-layer

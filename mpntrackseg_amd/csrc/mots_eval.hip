@@ -8,6 +8,7 @@
 //   mots_frame_match   table -> the kit's per-object decisions (MOTS_metrics.py:251-273, :529-535) in exact integer form
 // Integer atomics and integer compares only: the same bits on every call, and the bits of tests/mots_metrics_ref.py.
 #include "device_prims.h"
+#include "label_tables.h"
 
 namespace mpnhip {
 namespace {
@@ -18,17 +19,6 @@ constexpr int OV_VEC_PER_THREAD = 8;   // 16-byte loads per thread (and image) a
 // share a CU's 160 KB
 constexpr int OV_LDS_CELLS = 4096;
 constexpr int PAINT_THREADS = 256;
-
-// largest f in [0, n_frames) with ptr[f] <= e < ptr[f + 1], or -1 (whatever ptr holds, the result stays inside [-1, n_frames))
-__device__ __forceinline__ int frame_of(const int* __restrict__ ptr, int n_frames, int e) {
-    int lo = 0, hi = n_frames;   // first f with ptr[f] > e
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (ptr[mid] <= e) lo = mid + 1; else hi = mid;
-    }
-    const int f = lo - 1;
-    return (f >= 0 && e < ptr[f + 1]) ? f : -1;
-}
 
 // ------------------------------------------------------------------------------------------------ paint
 // length of every run (0 for a run that paints nothing) and the frame of its entry
@@ -71,28 +61,6 @@ static PaintView paint_view(void* workspace, int64_t n_runs) {
     PaintView v = {c.take<int64_t>(n), c.take<int64_t>(n), c.take<int>(n), c.take<char>(tmp_bytes), tmp_bytes, 0};
     v.bytes = c.bytes();
     return v;
-}
-
-// ------------------------------------------------------------------------------------------------ tables
-// Frame f of a launch: its entries on either side (clamped into the lists) and its cells.  ok = false: the frame's cells do
-// not lie inside the table -- nothing of it is read or written.
-struct FrameTab { int a0, na, b0, nb; int64_t base; bool ok; };
-__device__ __forceinline__ void clamp_range(const int* __restrict__ ptr, int f, int n, int& first, int& count) {
-    int64_t d0 = ptr[f], d1 = ptr[f + 1];
-    d0 = d0 < 0 ? 0 : (d0 > n ? n : d0);
-    d1 = d1 < d0 ? d0 : (d1 > n ? n : d1);
-    first = (int)d0;
-    count = (int)(d1 - d0);
-}
-__device__ __forceinline__ FrameTab frame_tab(const int* __restrict__ a_ptr, const int* __restrict__ b_ptr,
-                                              const int64_t* __restrict__ table_ptr, int f, int n_a, int n_b, int64_t table_cells) {
-    FrameTab t;
-    clamp_range(a_ptr, f, n_a, t.a0, t.na);
-    clamp_range(b_ptr, f, n_b, t.b0, t.nb);
-    t.base = table_ptr[f];
-    const int64_t cells = (int64_t)(t.na + 1) * (t.nb + 1);
-    t.ok = t.base >= 0 && t.base <= table_cells && cells <= table_cells - t.base;
-    return t;
 }
 
 // ------------------------------------------------------------------------------------------------ overlap
@@ -194,60 +162,6 @@ __global__ __launch_bounds__(OV_THREADS) void k_label_overlap(const int* __restr
 }
 
 // ------------------------------------------------------------------------------------------------ match
-constexpr int MT_THREADS = 256, MT_WAVES = MT_THREADS / 64;
-
-__device__ __forceinline__ int wave_sum(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
-// one wavefront per a-entry: its area (row sum, the "no object" column included)
-__global__ __launch_bounds__(MT_THREADS) void k_row_sums(const int* __restrict__ table, const int64_t* __restrict__ table_ptr,
-                                                         const int* __restrict__ a_ptr, const int* __restrict__ b_ptr, int n_frames,
-                                                         int n_a, int n_b, int64_t table_cells, int* __restrict__ a_area) {
-    const int a = blockIdx.x * MT_WAVES + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (a >= n_a) return;
-    const int f = frame_of(a_ptr, n_frames, a);
-    int sum = 0;
-    if (f >= 0) {
-        const FrameTab ft = frame_tab(a_ptr, b_ptr, table_ptr, f, n_a, n_b, table_cells);
-        const int ia = a - ft.a0;
-        if (ft.ok && ia >= 0 && ia < ft.na) {
-            const int* __restrict__ row = table + ft.base + (int64_t)(ia + 1) * (ft.nb + 1);
-            for (int c = lane; c <= ft.nb; c += 64) sum += row[c];
-        }
-    }
-    sum = wave_sum(sum);
-    if (lane == 0) a_area[a] = sum;
-}
-
-// one thread per b-entry (neighbouring threads read neighbouring columns): its area and its share inside the ignore region
-__global__ void k_col_sums(const int* __restrict__ table, const int64_t* __restrict__ table_ptr, const int* __restrict__ a_ptr,
-                           const int* __restrict__ b_ptr, int n_frames, int n_a, int n_b, int64_t table_cells,
-                           const unsigned char* __restrict__ a_ignore, int* __restrict__ b_area, unsigned char* __restrict__ b_ignored,
-                           unsigned char* __restrict__ b_matched) {
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= n_b) return;
-    const int f = frame_of(b_ptr, n_frames, b);
-    long long area = 0, ign = 0;
-    if (f >= 0) {
-        const FrameTab ft = frame_tab(a_ptr, b_ptr, table_ptr, f, n_a, n_b, table_cells);
-        const int ib = b - ft.b0;
-        if (ft.ok && ib >= 0 && ib < ft.nb) {
-            const int* __restrict__ col = table + ft.base + (ib + 1);
-            for (int r = 0; r <= ft.na; ++r) {
-                const int n = col[(int64_t)r * (ft.nb + 1)];
-                area += n;
-                if (r > 0 && a_ignore[ft.a0 + r - 1]) ign += n;
-            }
-        }
-    }
-    b_area[b] = (int)area;
-    b_ignored[b] = 2 * ign > area ? 1 : 0;   // MOTS_metrics.py:272-273: intersection / the prediction's own area > 0.5
-    b_matched[b] = 0;
-}
-
 // one wavefront per a-entry over the frame's b-entries.  i = cell, u = A + B - i:
 //   2 i > u            c > 0.5 of MOTS_metrics.py:253-254: the CLEAR match (at most one b: the b-masks are disjoint)
 //   2 i >= u, u > 0    not (overlap < 0.5) of :529-535: one more frame the two trajectories share
@@ -299,11 +213,6 @@ static MatchView match_view(void* workspace, int64_t n_a) {
     MatchView v = {c.take<int>((size_t)n_a), 0};
     v.bytes = c.bytes();
     return v;
-}
-
-static bool list_sizes_ok(int64_t n_entries, int64_t n_frames, int64_t hw) {
-    return n_entries >= 0 && n_entries < (1LL << 30) && n_frames >= 0 && n_frames <= 65535 && hw >= 0 && hw < (1LL << 31) &&
-           n_frames * hw < (1LL << 40);
 }
 
 }  // namespace

@@ -403,3 +403,38 @@ def evaluate_mots_sequence(node_preds, boxes, frame_num_per_node, ped_ids, label
         return M.paste_unique_masks(node_preds, boxes, b_ptr, img_shape, mask_threshold, det_ids=kept[b_entries])
     return ME._evaluate(ME._as_loaded(gt), seq_length, class_id, ignore_class, frames_per_launch, node_preds.device, frame_h[kept], b_traj,
                         traj_ids, b_labels, img_shape, details)
+
+
+@capi.on_tensor_device
+def evaluate_hota_sequence(node_preds, boxes, frame_num_per_node, ped_ids, label, keep, img_shape, gt, num_timesteps, mask_threshold=0.5,
+                           frames_per_launch=8, class_id=2, ignore_class=10, details=False):
+    """HOTA (``eval_kitti_mots``, utils/evaluation.py:127-135) of a tracked KITTI-MOTS sequence against the ground truth ``gt``
+    (a MOTS text file, or what ``mots_eval.load_mots_txt`` returns) over the frames ``0 .. num_timesteps - 1``: what
+    ``hota_eval.evaluate_hota_files`` gives for the rows ``save_results_to_file`` writes for the same arguments, without the
+    run-length strings and the text file -- the twin of ``evaluate_mots_sequence``, with the prediction's label images straight
+    from ``masks.paste_unique_masks`` (every kept detection pastes; only those with ``label == class_id`` are scored).
+
+    The arguments as ``evaluate_mots_sequence``, but ``num_timesteps`` frames instead of its ``seq_length + 1``.  Returns the
+    dict of ``hota_eval.evaluate_hota_files``."""
+    from . import hota_eval as HE, masks as M
+    capi.require_device(node_preds)
+    N = int(node_preds.shape[0])
+    as_np = lambda v: np.asarray(v.detach().cpu() if isinstance(v, torch.Tensor) else v)
+    keep_h, frame_h = as_np(keep).reshape(-1).astype(bool), as_np(frame_num_per_node).reshape(-1).astype(np.int64)
+    ped = as_np(ped_ids).reshape(-1).astype(np.int64)
+    lab = np.broadcast_to(as_np(label).astype(np.int64).reshape(-1), ped.shape) if np.ndim(as_np(label)) else np.full(ped.shape, int(label), np.int64)
+    if not (keep_h.size == frame_h.size == ped.size == N == len(boxes)):
+        raise MpnhipError("one box, frame number, id and keep flag per detection (%d detections)" % N)
+    kept = np.flatnonzero(keep_h)
+    kept = kept[np.argsort(frame_h[kept], kind="stable")]   # node order inside a frame: the paste order of to_full_masks
+    ids = ped[kept] + lab[kept] * 1000 + 1
+    if np.unique(np.stack((frame_h[kept], ids)), axis=1).shape[1] != kept.size:
+        raise ValueError("Multiple objects with one track id in a frame")
+    scored = lab[kept] == class_id
+    traj_ids = np.unique(ids[scored])
+    b_traj = np.where(scored, np.searchsorted(traj_ids, ids), -1).astype(np.int64)
+
+    def b_labels(frames, b_ptr, b_entries, hw):
+        return M.paste_unique_masks(node_preds, boxes, b_ptr, img_shape, mask_threshold, det_ids=kept[b_entries])
+    return HE._evaluate(HE._as_loaded(gt), num_timesteps, class_id, ignore_class, frames_per_launch, node_preds.device, frame_h[kept],
+                        b_traj, traj_ids, b_labels, img_shape, details)

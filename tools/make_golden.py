@@ -51,6 +51,11 @@ Fixtures:
                                of id images: "cases" (12 frames of 37 x 29 with an id switch, a fragment, ignore regions, a pair at IoU
                                exactly 0.5, ...) and "crowded" (3 frames of 64 x 48 with 110 objects a side).  pycocotools is not
                                installed: the kit runs over a numpy stand-in built on the project's RLE codec.  Only with --only g22.
+  g23_hota.npz                 TrackEval's KittiMOTS preprocessing and HOTA.eval_sequence (class pedestrian) on g22's two scenes (read from
+                               g22_mots_metrics.npz, not stored again) and on "association" (12 frames of 37 x 29: a track covered by two
+                               prediction ids in turn, a swap, a prediction the global alignment assigns against the frame's IoU, IoUs at
+                               every twentieth, removals by the ignore region), and HOTA.combine_sequences over the three: every result
+                               field, the four counts and per frame the kept prediction ids.  Only with --only g23.
 
 Usage:  python tools/make_golden.py [--only g1,g2,...]
 """
@@ -1514,6 +1519,159 @@ def gen_g22():
     print("g22 bytes", os.path.getsize(path))
 
 
+# ------------------------------------------------------------------ g23: TrackEval's HOTA on KITTI-MOTS
+def _g23_association():
+    """12 frames of 37 x 29 (and an empty thirteenth timestep); the asserts of gen_g23 check that the cases are there"""
+    F, H, W = 12, 37, 29
+    gt, pr = np.zeros((F, H, W), np.uint16), np.zeros((F, H, W), np.uint16)
+    jit = (synth.uniform01(23, 3 * F * 2, stream=1) * 3).astype(np.int64).reshape(3, F, 2)   # prediction offsets in {0, 1, 2}
+    for f in range(10):
+        if f <= 5:
+            _g22_rect(gt, f, 10000, 0, H, 24, W)                      # the ignore region
+        _g22_rect(gt, f, 2001, 2, 10, 1, 5)                           # 2001: covered by prediction 2001, then by 2002
+        _g22_rect(pr, f, 2001 if f < 5 else 2002, 2 + jit[0, f, 0], 10 + jit[0, f, 0], 0 + jit[0, f, 1], 4 + jit[0, f, 1])
+        _g22_rect(gt, f, 2003, 13, 21, 1, 5)                          # 2003 / 2004: their predictions swap ids from frame 5 on
+        _g22_rect(gt, f, 2004, 25, 33, 1, 5)
+        _g22_rect(pr, f, 2003 if f < 5 else 2004, 13 + jit[1, f, 0], 21 + jit[1, f, 0], 0 + jit[1, f, 1], 4 + jit[1, f, 1])
+        _g22_rect(pr, f, 2004 if f < 5 else 2003, 25 + jit[2, f, 0], 33 + jit[2, f, 0], 0 + jit[2, f, 1], 4 + jit[2, f, 1])
+        _g22_rect(gt, f, 2005, 2, 12, 7, 12)                          # 2005 / 2006: found exactly by 2011 / 2010 ...
+        _g22_rect(gt, f, 2006, 14, 24, 7, 12)
+        if f != 7:
+            _g22_rect(pr, f, 2011, 2, 12, 7, 12)
+            _g22_rect(pr, f, 2010, 14, 24, 7, 12)
+        else:                                                         # ... but once 2010 alone lies over both: 35 / 90 and 30 / 95
+            _g22_rect(pr, f, 2010, 5, 20, 7, 12)
+        _g22_rect(gt, f, 2007, 2, 22, 15, 16)                         # two strips of 20 pixels with f + 1 and f + 10 of them found:
+        _g22_rect(pr, f, 2007, 2, 3 + f, 15, 16)                      # IoU = every twentieth from 0.05 to 0.95
+        _g22_rect(gt, f, 2008, 2, 22, 18, 19)
+        _g22_rect(pr, f, 2008, 2, 12 + f, 18, 19)
+    _g22_rect(pr, 1, 2020, 26, 32, 22, 28)                            # four of six columns inside the ignore region: removed
+    _g22_rect(pr, 2, 2021, 26, 32, 22, 26)                            # two of four: exactly half, kept
+    _g22_rect(gt, 6, 1001, 26, 32, 20, 26)                            # a car under a prediction
+    _g22_rect(pr, 6, 2030, 26, 32, 20, 26)
+    _g22_rect(pr, 10, 2002, 2, 10, 1, 5)                              # frame 10 has no ground truth,
+    _g22_rect(pr, 10, 2010, 14, 24, 7, 12)
+    _g22_rect(gt, 11, 2001, 2, 10, 1, 5)                              # frame 11 no prediction
+    _g22_rect(gt, 11, 2005, 2, 12, 7, 12)
+    return gt, pr, F + 1
+
+
+def gen_g23():
+    """TrackEval's OWN KittiMOTS._load_raw_file / get_preprocessed_seq_data and HOTA.eval_sequence / combine_sequences on text
+    files written from id images, in the KittiMOTS folder layout.  Stand-ins: the numpy pycocotools.mask of g22 and the aliases
+    np.float / np.bool / np.int where numpy no longer has them.  The prediction ids the preprocessing keeps are read off its call
+    of _calculate_mask_ious for the ignore region."""
+    import tempfile
+    for name, t in (("float", float), ("bool", bool), ("int", int)):
+        if not hasattr(np, name):
+            setattr(np, name, t)
+    _install_pycocotools_standin()
+    # a frame without ignore rows: the merged region is a 0 x 0 mask.  The C library compares bounding boxes first and leaves 0
+    # where they do not meet, so it never reaches the size check the stand-in answers with -1 (which the kit's range assertion
+    # refuses)
+    standin_iou = sys.modules["pycocotools.mask"].iou
+    sys.modules["pycocotools.mask"].iou = lambda dt, gt, iscrowd: np.maximum(standin_iou(dt, gt, iscrowd), 0.0)
+    sys.path.insert(0, "/root/reference/TrackEval")
+    import trackeval
+    from trackeval.metrics import hota as hota_module
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    import mots_metrics_ref as R
+    eps = np.finfo("float").eps
+    real_lsa = hota_module.linear_sum_assignment
+
+    def run(gt, pr, num_timesteps, noise_seed=None):
+        ds = trackeval.datasets.KittiMOTS.__new__(trackeval.datasets.KittiMOTS)
+        removed = set()
+        real_ious = ds._calculate_mask_ious
+
+        def ious(masks1, masks2, is_encoded=False, do_ioa=False):
+            out = real_ious(masks1, masks2, is_encoded=is_encoded, do_ioa=do_ioa)
+            if do_ioa:
+                removed.update(id(m) for m, v in zip(masks1, np.any(out > 0.5 + eps, axis=1)) if v)
+            return out
+        ds._calculate_mask_ious = ious
+        rng = np.random.default_rng(noise_seed)
+        assigned = []   # (rows, cols) of every frame the metric assigns, in frame order
+
+        def lsa(cost):
+            if noise_seed is not None:   # every score_mat times 1 + 1e-9 * noise: a near-tied assignment would change
+                cost = cost * (1 + 1e-9 * rng.standard_normal(cost.shape))
+            assigned.append(real_lsa(cost))
+            return assigned[-1]
+        hota_module.linear_sum_assignment = lsa
+        try:
+            with tempfile.TemporaryDirectory() as d:
+                os.makedirs(os.path.join(d, "label_02"))
+                os.makedirs(os.path.join(d, "trk", "data"))
+                R.write_txt(os.path.join(d, "label_02", "0000.txt"), R.id_image_rows(gt))
+                R.write_txt(os.path.join(d, "trk", "data", "0000.txt"), R.id_image_rows(pr))
+                ds.config = {"GT_LOC_FORMAT": "{gt_folder}/label_02/{seq}.txt"}
+                ds.gt_fol, ds.tracker_fol, ds.tracker_sub_fol, ds.data_is_zipped = d, d, "data", False
+                ds.seq_lengths = {"0000": num_timesteps}
+                ds.class_name_to_class_id = {"car": "1", "pedestrian": "2", "ignore": "10"}
+                raw = ds.get_raw_seq_data("trk", "0000")
+                data = ds.get_preprocessed_seq_data(raw, "pedestrian")
+            res = trackeval.metrics.HOTA().eval_sequence(data)
+        finally:
+            hota_module.linear_sum_assignment = real_lsa
+        kept = []
+        for t in range(num_timesteps):
+            ped = np.flatnonzero(raw["tracker_classes"][t] == 2)
+            kept.append([int(raw["tracker_ids"][t][j]) for j in ped if id(raw["tracker_dets"][t][j]) not in removed])
+            assert len(kept[-1]) == len(data["tracker_ids"][t])
+            # no ground-truth mask split exactly in half by two predictions: the one case the kit decides by scipy's tie order
+            sim = raw["similarity_scores"][t][raw["gt_classes"][t] == 2][:, ped]
+            assert ((sim >= 0.5 - eps).sum(axis=1) <= 1).all(), t
+        ids = np.unique([v for k in kept for v in k])
+        for t in range(num_timesteps):   # ... and they are the ones the kit renumbered
+            assert np.array_equal(np.searchsorted(ids, kept[t]), data["tracker_ids"][t]), t
+        counts = {k: int(data[k]) for k in ("num_gt_dets", "num_tracker_dets", "num_gt_ids", "num_tracker_ids")}
+        return res, counts, kept, assigned
+
+    g22 = np.load(os.path.join(GOLD, "g22_mots_metrics.npz"))
+    scenes = [(name, g22[name + ":gt"], g22[name + ":pred"], int(g22[name + ":seq_length"]) + 1) for name in ("cases", "crowded")]
+    scenes.append(("association",) + _g23_association())
+    rec, all_res = {}, {}
+    fields = None
+    for name, gt, pr, num_timesteps in scenes:
+        res, counts, kept, assigned = run(gt, pr, num_timesteps)
+        fields = sorted(res)
+        for seed in (1, 2, 3):
+            noisy, counts_n, _, _ = run(gt, pr, num_timesteps, noise_seed=seed)
+            assert counts_n == counts
+            for k in fields:
+                assert np.allclose(noisy[k], res[k], rtol=1e-9, atol=1e-9), (name, seed, k)
+        all_res[name] = res
+        rec[f"{name}:num_timesteps"] = np.int64(num_timesteps)
+        for k in fields:
+            rec[f"{name}:{k}"] = np.asarray(res[k], np.float64)
+        for k, v in counts.items():
+            rec[f"{name}:{k}"] = np.int64(v)
+        rec[f"{name}:kept_ptr"] = np.concatenate(([0], np.cumsum([len(k) for k in kept]))).astype(np.int64)
+        rec[f"{name}:kept_ids"] = np.asarray([v for k in kept for v in k], np.int64)
+        print("g23", name, counts, "HOTA(0) %.6f" % res["HOTA(0)"], "TP", res["HOTA_TP"].astype(int).tolist())
+        if name == "association":
+            rec[f"{name}:gt"], rec[f"{name}:pred"] = gt, pr
+            tp = res["HOTA_TP"]
+            assert (tp > 0).all() and tp[0] > tp[18] and (np.diff(tp) < 0).all()   # every alpha changes the counts
+            assert 2020 not in kept[1] and 2021 in kept[2] and 2030 in kept[6]
+            assert counts["num_tracker_ids"] == len(np.unique(pr[pr // 1000 == 2])) - 1
+            # frame 7: prediction 2010 has the higher IoU with 2005 (35 / 90 against 30 / 95) but belongs to 2006 by the global
+            # alignment, and the kit assigns it to 2006 (frames 0 .. 9 are assigned, so frame 7 is the eighth)
+            L = R.scene_lists(gt[7:8], pr[7:8])
+            t_, tp_ = R.label_overlap(L["labels_a"], L["labels_b"], L["a_ptr"], L["b_ptr"])
+            cell = lambda g, p: t_[(list(L["gt_ids"]).index(g) + 1) * (L["b_ptr"][-1] + 1) + list(L["tr_ids"]).index(p) + 1]
+            assert (cell(2005, 2010), cell(2006, 2010)) == (35, 30)
+            rows, cols = assigned[7]
+            assert len(assigned) == 10 and list(L["tr_ids"])[cols[list(rows).index(list(L["gt_ids"]).index(2006))]] == 2010
+    comb = trackeval.metrics.HOTA().combine_sequences(all_res)
+    for k in sorted(comb):
+        rec[f"combined:{k}"] = np.asarray(comb[k], np.float64)
+    path = os.path.join(GOLD, "g23_hota.npz")
+    np.savez_compressed(path, **rec)
+    print("g23 bytes", os.path.getsize(path))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", default="g0,g1,g4,g5,g6,g7,g8,g2,g3,g11,g12,g10,g9")
@@ -1545,6 +1703,7 @@ def main():
     if "g20" in only: gen_g20()
     if "g21" in only: gen_g21()
     if "g22" in only: gen_g22()
+    if "g23" in only: gen_g23()
 
 
 if __name__ == "__main__":
