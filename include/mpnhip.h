@@ -170,6 +170,52 @@ typedef struct mpnhip_seg_job {
 } mpnhip_seg_job;
 int mpnhip_debug_segment_reduce3(const mpnhip_seg_job jobs[3], int64_t total_rows, int bf16_rows, void* stream);
 
+/* Test instrumentation: ONE call of the dense product every MLP layer of the forward and every activation-gradient product of the
+ * fp32 backward goes through (csrc/gemm.hip: launch_gemm), with every term of its prologue and epilogue reachable.  For each of
+ * up to two row groups g (rows [*row_begin, *row_end) read from DEVICE memory; row_begin == NULL: 0, row_end == NULL: m_static),
+ * for every row m of the group and every column n < N:
+ *   v = sum_k a[k] * B(k, n)            a = A[i][0 .. ksplit) followed by A2[i][0 .. K - ksplit), i = a_idx ? a_idx[m] : m;
+ *                                       B(k, n) = B[n * ldb + k] (MPNHIP_GEMM_B_KCONTIG: nn.Linear weights) or B[k * ldb + n]
+ *   v += bias[n] + G1[(g1_idx ? g1_idx[m] : m) * ldg1 + n] + G2[(g2_idx ? g2_idx[m] : m) * ldg2 + n]     (each optional)
+ *   v = relu ? max(v, 0) : v
+ *   v += accumulate ? C[c * ldc + n] : 0                                                     c = c_idx ? c_idx[m] : m
+ *   C[c * ldc + n] = mask ? (mask[m * ldmask + n] > 0 ? v : 0) : v
+ * The groups share N, K, ksplit, relu and accumulate; ksplit == K when A2 is unused.  m_upper: host-side upper bound of the rows of
+ * both groups together (sizes the grid; 0: nothing is launched).  small_tiles != 0: the 64 x 64 tile whatever m_upper says.
+ * precision: MPNHIP_PREC_FP32 / _BF16 (operands rounded to bf16 as they are staged) / _FP32_SPLIT (three bf16 pieces per operand).
+ * chosen (optional) reports what ran: chosen[0] = kernel | form << 8 with kernel 0 = the MFMA strip / tile kernel (chosen[1 .. 3] =
+ * its WM, WN, TN: block tile 32 WM x 32 TN WN), 1 = the one-thread-per-output kernel, 2 = the K <= 8 kernel, 3 = the tiled bf16
+ * kernel of csrc/gemm_bf16.hip (chosen[1 .. 3] = 0 for 1 .. 3), and form the MPNHIP_PREC_* operand form actually used (the split form
+ * is demoted to fp32 unless K >= 128 and N >= 256); chosen[0] = -1 when nothing was launched.  Refused on the host before any launch
+ * (MPNHIP_ERR_ARG): null args, ngroups outside 1 .. 2, an unknown b_layout or precision, MPNHIP_GEMM_B_NCONTIG with a precision
+ * other than fp32; then the checks of launch_gemm itself (null A / B / C, ksplit without A2, operands beyond 32-bit offsets). */
+#define MPNHIP_GEMM_B_KCONTIG 0
+#define MPNHIP_GEMM_B_NCONTIG 1
+typedef struct mpnhip_debug_gemm_group {
+    const float* A; const float* A2; const int32_t* a_idx; const float* B; const float* bias; const float* G1; const int32_t* g1_idx;
+    const float* G2; const int32_t* g2_idx; const float* mask; float* C; const int32_t* c_idx; const int32_t* row_begin;
+    const int32_t* row_end; int64_t lda; int64_t lda2; int64_t ldb; int64_t ldg1; int64_t ldg2; int64_t ldmask; int64_t ldc;
+    int64_t m_static;
+} mpnhip_debug_gemm_group;
+typedef struct mpnhip_debug_gemm_args {
+    mpnhip_debug_gemm_group g[2]; int ngroups; int N; int K; int ksplit; int relu; int accumulate; int64_t m_upper; int small_tiles;
+    int b_layout; int precision;
+} mpnhip_debug_gemm_args;
+int mpnhip_debug_gemm(const mpnhip_debug_gemm_args* args, int32_t chosen[4], void* stream);
+
+/* Test instrumentation: the split-K form of y = act(x W^T + b) for few rows and long K (csrc/gemm.hip: linear_splitk; the node
+ * encoder's first layer in mpnhip_forward), optionally with the next, narrow Linear layer y2 = act2(y W2^T + b2) evaluated in the
+ * summing launch (w2 != NULL; W2 is [n2, n] row-major).  x [m, k] (leading dimension ldx), w [n, k], y [m, n] (ldy), y2 [m, n2]
+ * (ldy2); scratch: scratch_floats floats of device memory, mpnhip_debug_linear_splitk_scratch_floats(m, n, k) suffice (0: not a
+ * shape of this path).  taken_and_fused[0] = 1 when the path was taken (0: not a shape of this path -- k < 512, k or ldx not a
+ * multiple of 4, more than 8192 rows, 320 or more 64 x 64 tiles, the bf16 precision, too little scratch: nothing is launched and
+ * MPNHIP_OK is returned); taken_and_fused[1] = 1 when the next layer ran in the same launch (n % 4 == 0, n <= 256, ldy == n,
+ * n2 <= 64), 0: y2 is untouched.  Null x / w / y, an unknown precision or w2 without y2 are refused (MPNHIP_ERR_ARG). */
+size_t mpnhip_debug_linear_splitk_scratch_floats(int64_t m, int n, int k);
+int mpnhip_debug_linear_splitk(const float* x, int64_t ldx, const float* w, const float* b, float* y, int64_t ldy, int64_t m, int n,
+                               int k, int relu, int precision, const float* w2, const float* b2, int n2, int relu2, float* y2,
+                               int64_t ldy2, float* scratch, size_t scratch_floats, int32_t taken_and_fused[2], void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Graph preparation -- replaces the six boolean-mask indexings per step of
  * TimeAwareNodeModel.forward (models/mpn.py:85-87,91-93) and the implicit index structures behind

@@ -67,6 +67,21 @@ class SegJob(C.Structure):
     ]
 
 
+class DebugGemmGroup(C.Structure):
+    """``mpnhip_debug_gemm_group`` (include/mpnhip.h): one row group of ``mpnhip_debug_gemm``."""
+    _fields_ = [(n, C.c_void_p) for n in ("A", "A2", "a_idx", "B", "bias", "G1", "g1_idx", "G2", "g2_idx", "mask", "C", "c_idx",
+                                          "row_begin", "row_end")] + \
+               [(n, C.c_int64) for n in ("lda", "lda2", "ldb", "ldg1", "ldg2", "ldmask", "ldc", "m_static")]
+
+
+class DebugGemmArgs(C.Structure):
+    """``mpnhip_debug_gemm_args`` (include/mpnhip.h)."""
+    _fields_ = [
+        ("g", DebugGemmGroup * 2), ("ngroups", C.c_int), ("N", C.c_int), ("K", C.c_int), ("ksplit", C.c_int), ("relu", C.c_int),
+        ("accumulate", C.c_int), ("m_upper", C.c_int64), ("small_tiles", C.c_int), ("b_layout", C.c_int), ("precision", C.c_int),
+    ]
+
+
 # name -> (restype, argtypes); mirrors include/mpnhip.h one to one (tests/test_capi_symbols.py
 # checks that every function the header declares is listed here and exported by the library)
 _P, _I, _L, _Z = C.c_void_p, C.c_int, C.c_int64, C.c_size_t
@@ -79,6 +94,10 @@ SIGNATURES = {
     "mpnhip_debug_backward_saved": (_I, [C.POINTER(Model), _I, _L, _P, _Z, _I, _I, _I, _P, C.POINTER(C.c_int64), C.POINTER(C.c_int), _P]),
     "mpnhip_debug_aggregate": (_I, [_P, _I, _L, _P, _I, _I, _P, _P, _P]),
     "mpnhip_debug_segment_reduce3": (_I, [C.POINTER(SegJob), _L, _I, _P]),
+    "mpnhip_debug_gemm": (_I, [C.POINTER(DebugGemmArgs), C.POINTER(C.c_int32), _P]),
+    "mpnhip_debug_linear_splitk_scratch_floats": (_Z, [_L, _I, _I]),
+    "mpnhip_debug_linear_splitk": (_I, [_P, _L, _P, _P, _P, _L, _L, _I, _I, _I, _I, _P, _P, _I, _I, _P, _L, _P, _Z, C.POINTER(C.c_int32),
+                                        _P]),
     "mpnhip_graph_bytes": (_Z, [_I, _L]),
     "mpnhip_graph_prep_workspace_bytes": (_Z, [_I, _L]),
     "mpnhip_graph_prep": (_I, [_P, _I, _L, _P, _Z, _P, _Z, _P]),

@@ -104,8 +104,14 @@ struct GemmArgs {
     int small_tiles;       // 1: take the 64 x 64 configuration whatever m_upper says (two K halves as two groups: m_upper = 2 M)
 };
 
+// What launch_gemm chose (test instrumentation, mpnhip_debug_gemm): kernel 0 = gemm_kernel<wm, wn, tn> (MFMA strip / tile),
+// 1 = gemm_generic_kernel, 2 = gemm_smallk_kernel, 3 = the tiled bf16 kernel of gemm_bf16.hip (wm = wn = tn = 0 for 1 .. 3);
+// prec: the operand form the kernel was launched with (after the demotion of the split form at short K / narrow N)
+struct GemmChosen { int kernel, wm, wn, tn, prec; };
+
 // prec: the operand form (MPNHIP_PREC_FP32 / _BF16 / _FP32_SPLIT: bf16 operands / fp32 accumulate, three-piece bf16 operands)
-int launch_gemm(const GemmArgs& args, int a_layout, int b_layout, int prec, hipStream_t stream);
+// chosen (optional): filled when a kernel is launched
+int launch_gemm(const GemmArgs& args, int a_layout, int b_layout, int prec, hipStream_t stream, GemmChosen* chosen = nullptr);
 // MPNHIP_PREC_BF16 at large row counts / with bf16 rows in memory (gemm_bf16.hip); false: not a shape of that kernel
 bool launch_gemm_bf16_tiled(const GemmArgs& args, hipStream_t stream, int* status);
 

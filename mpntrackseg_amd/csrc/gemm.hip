@@ -497,7 +497,7 @@ __global__ __launch_bounds__(NTHREADS) void gemm_smallk_kernel(GemmArgs args, in
 }
 
 template <int WM, int WN, int TN>
-static int launch_cfg(const GemmArgs& a, int bl, int prec, hipStream_t s) {
+static int launch_cfg(const GemmArgs& a, int bl, int prec, hipStream_t s, GemmChosen* chosen) {
     constexpr int BM = 32 * WM, BN = 32 * TN * WN;
     int64_t nby = (a.m_upper + BM - 1) / BM + (a.ngroups > 1 ? 1 : 0);
     dim3 grid((a.N + BN - 1) / BN, (unsigned)nby, 1);
@@ -506,6 +506,7 @@ static int launch_cfg(const GemmArgs& a, int bl, int prec, hipStream_t s) {
     // 50000 x 320 x 128 65.6 -> 48.5 us; narrow outputs (N = 128) and short K lose to the fp32 MFMA kernel's smaller LDS image
     if (prec == 2 && !(a.K >= 128 && a.N >= 256)) prec = 0;
     if (const char* e = getenv("MPNHIP_GEMM_PREC")) prec = atoi(e);  // operand-form override (tools/diag/split_accuracy.py)
+    if (chosen) *chosen = {0, WM, WN, TN, bl == B_KCONTIG && (prec == 1 || prec == 2) ? prec : 0};
     count_path(bl == B_KCONTIG && prec == 2 ? PC_GEMM_SPLIT : (bl == B_KCONTIG && prec == 1 ? PC_GEMM_BF16 : PC_GEMM_FP32));
     if (bl == B_KCONTIG && prec == 2)
         MPN_LAUNCH_PROFILED((gemm_kernel<WM, WN, TN, B_KCONTIG, 2>), grid, dim3(NTHREADS), s, a);
@@ -521,7 +522,7 @@ static int launch_cfg(const GemmArgs& a, int bl, int prec, hipStream_t s) {
 
 static bool al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 
-int launch_gemm(const GemmArgs& a_in, int al, int bl, int prec, hipStream_t s) {
+int launch_gemm(const GemmArgs& a_in, int al, int bl, int prec, hipStream_t s, GemmChosen* chosen) {
     GemmArgs a = a_in;
     MPN_CHECK_ARG(a.ngroups == 1 || a.ngroups == 2, "gemm: ngroups %d", a.ngroups);
     MPN_CHECK_ARG(a.K >= 0 && a.N >= 0 && a.ksplit >= 0 && a.ksplit <= a.K, "gemm: bad N/K/ksplit");
@@ -561,6 +562,7 @@ int launch_gemm(const GemmArgs& a_in, int al, int bl, int prec, hipStream_t s) {
             // (a thread's 4 x K weights are 28 scalar loads: at least eight row passes per block to pay for them)
             int64_t nb = ((a.m_upper + rpp - 1) / rpp + 7) / 8;
             nb = nb > 256 * 16 ? 256 * 16 : (nb < 1 ? 1 : nb);
+            if (chosen) *chosen = {2, 0, 0, 0, prec == 1 ? 1 : 0};
             hipLaunchKernelGGL(gemm_smallk_kernel, dim3((unsigned)nb), dim3(NTHREADS), 0, s, a, prec == 1 ? 1 : 0);
             MPN_LAUNCH_CHECK();
             return MPNHIP_OK;
@@ -568,6 +570,7 @@ int launch_gemm(const GemmArgs& a_in, int al, int bl, int prec, hipStream_t s) {
         int64_t total = a.m_upper * a.N;
         unsigned blocks = (unsigned)((total + NTHREADS - 1) / NTHREADS);
         if (blocks > 65535u * 16) blocks = 65535u * 16;
+        if (chosen) *chosen = {1, 0, 0, 0, prec == 1 ? 1 : 0};
         hipLaunchKernelGGL(gemm_generic_kernel, dim3(blocks), dim3(NTHREADS), 0, s, a, bl, prec == 1 ? 1 : 0);
         MPN_LAUNCH_CHECK();
         return MPNHIP_OK;
@@ -589,6 +592,7 @@ int launch_gemm(const GemmArgs& a_in, int al, int bl, int prec, hipStream_t s) {
             int st = MPNHIP_OK;
             if (launch_gemm_bf16_tiled(a, s, &st)) {
                 if (st == MPNHIP_OK) count_path(PC_GEMM_BF16);
+                if (chosen) *chosen = {3, 0, 0, 0, 1};
                 return st;
             }
         }
@@ -609,21 +613,21 @@ int launch_gemm(const GemmArgs& a_in, int al, int bl, int prec, hipStream_t s) {
             while (best > 1 && rb * ((nt + best - 1) / best) < 256) best = (best + 1) / 2;
         }
         switch (best) {
-            case 8: return launch_cfg<4, 1, 8>(a, bl, prec, s);
-            case 7: return launch_cfg<4, 1, 7>(a, bl, prec, s);
-            case 6: return launch_cfg<4, 1, 6>(a, bl, prec, s);
-            case 5: return launch_cfg<4, 1, 5>(a, bl, prec, s);
-            case 4: return launch_cfg<4, 1, 4>(a, bl, prec, s);
-            case 3: return launch_cfg<4, 1, 3>(a, bl, prec, s);
-            case 2: return launch_cfg<4, 1, 2>(a, bl, prec, s);
-            default: return launch_cfg<4, 1, 1>(a, bl, prec, s);
+            case 8: return launch_cfg<4, 1, 8>(a, bl, prec, s, chosen);
+            case 7: return launch_cfg<4, 1, 7>(a, bl, prec, s, chosen);
+            case 6: return launch_cfg<4, 1, 6>(a, bl, prec, s, chosen);
+            case 5: return launch_cfg<4, 1, 5>(a, bl, prec, s, chosen);
+            case 4: return launch_cfg<4, 1, 4>(a, bl, prec, s, chosen);
+            case 3: return launch_cfg<4, 1, 3>(a, bl, prec, s, chosen);
+            case 2: return launch_cfg<4, 1, 2>(a, bl, prec, s, chosen);
+            default: return launch_cfg<4, 1, 1>(a, bl, prec, s, chosen);
         }
     }
     // few rows (node-level products): spread the columns over the waves so that the grid fills the chip
     // measured on MI355X at M = 5,000 (tools/gemm_bench.py): 64 x 64 tiles beat every wider strip for
     // N = 128 ... 1088 and K = 128 ... 2048 (more, shorter blocks: the chip is latency- not MFMA-bound here)
-    if (nt >= 2) return launch_cfg<2, 2, 1>(a, bl, prec, s);
-    return launch_cfg<4, 1, 1>(a, bl, prec, s);
+    if (nt >= 2) return launch_cfg<2, 2, 1>(a, bl, prec, s, chosen);
+    return launch_cfg<4, 1, 1>(a, bl, prec, s, chosen);
 }
 
 int linear(const float* x, int64_t ldx, const float* w, const float* b, float* y, int64_t ldy, int64_t m, int n, int k,
@@ -816,3 +820,55 @@ size_t linear_splitk_scratch_floats(int64_t m, int n, int k) {
 }
 
 }  // namespace mpnhip
+
+// ---- test instrumentation: launch_gemm and linear_splitk behind the C ABI, one call each -----------------------------------
+using namespace mpnhip;
+
+extern "C" int mpnhip_debug_gemm(const mpnhip_debug_gemm_args* args, int32_t chosen[4], void* stream_) {
+    MPN_CHECK_ARG(args, "debug_gemm: null args");
+    MPN_CHECK_ARG(args->ngroups == 1 || args->ngroups == 2, "debug_gemm: ngroups %d", args->ngroups);
+    MPN_CHECK_ARG(args->b_layout == MPNHIP_GEMM_B_KCONTIG || args->b_layout == MPNHIP_GEMM_B_NCONTIG, "debug_gemm: unknown b_layout %d",
+                  args->b_layout);
+    MPN_CHECK_ARG(args->precision == MPNHIP_PREC_FP32 || args->precision == MPNHIP_PREC_BF16 || args->precision == MPNHIP_PREC_FP32_SPLIT,
+                  "debug_gemm: unknown precision %d", args->precision);
+    MPN_CHECK_ARG(args->b_layout == MPNHIP_GEMM_B_KCONTIG || args->precision == MPNHIP_PREC_FP32,
+                  "debug_gemm: the N-contiguous B layout takes fp32 operands only");
+    GemmArgs a = {};
+    for (int i = 0; i < args->ngroups; ++i) {
+        const mpnhip_debug_gemm_group& s = args->g[i];
+        GemmGroup& g = a.g[i];
+        g.A = s.A; g.A2 = s.A2; g.a_idx = s.a_idx; g.B = s.B; g.bias = s.bias; g.G1 = s.G1; g.g1_idx = s.g1_idx; g.G2 = s.G2;
+        g.g2_idx = s.g2_idx; g.mask = s.mask; g.C = s.C; g.c_idx = s.c_idx; g.row_begin = s.row_begin; g.row_end = s.row_end;
+        g.lda = s.lda; g.lda2 = s.lda2; g.ldb = s.ldb; g.ldg1 = s.ldg1; g.ldg2 = s.ldg2; g.ldmask = s.ldmask; g.ldc = s.ldc;
+        g.m_static = s.m_static;
+    }
+    a.ngroups = args->ngroups;
+    a.N = args->N; a.K = args->K; a.ksplit = args->ksplit;
+    a.relu = args->relu; a.accumulate = args->accumulate;
+    a.m_upper = args->m_upper;
+    a.small_tiles = args->small_tiles;
+    GemmChosen c = {-1, 0, 0, 0, 0};
+    const int rc = launch_gemm(a, A_KCONTIG, args->b_layout == MPNHIP_GEMM_B_NCONTIG ? B_NCONTIG : B_KCONTIG, args->precision,
+                               static_cast<hipStream_t>(stream_), &c);
+    if (chosen) { chosen[0] = c.kernel < 0 ? -1 : (c.kernel | (c.prec << 8)); chosen[1] = c.wm; chosen[2] = c.wn; chosen[3] = c.tn; }
+    return rc;
+}
+
+extern "C" size_t mpnhip_debug_linear_splitk_scratch_floats(int64_t m, int n, int k) { return linear_splitk_scratch_floats(m, n, k); }
+
+extern "C" int mpnhip_debug_linear_splitk(const float* x, int64_t ldx, const float* w, const float* b, float* y, int64_t ldy, int64_t m, int n,
+                                          int k, int relu, int precision, const float* w2, const float* b2, int n2, int relu2, float* y2,
+                                          int64_t ldy2, float* scratch, size_t scratch_floats, int32_t taken_and_fused[2], void* stream_) {
+    if (taken_and_fused) taken_and_fused[0] = taken_and_fused[1] = 0;
+    MPN_CHECK_ARG(x && w && y, "debug_linear_splitk: null x / w / y");
+    MPN_CHECK_ARG(m >= 0 && n >= 1 && k >= 1, "debug_linear_splitk: bad sizes");
+    MPN_CHECK_ARG(precision == MPNHIP_PREC_FP32 || precision == MPNHIP_PREC_BF16 || precision == MPNHIP_PREC_FP32_SPLIT,
+                  "debug_linear_splitk: unknown precision %d", precision);
+    MPN_CHECK_ARG(!w2 || (y2 && n2 >= 1), "debug_linear_splitk: next layer without an output");
+    SplitkNext next = {w2, b2, n2, relu2, y2, ldy2, false};
+    int status = MPNHIP_OK;
+    const bool taken = linear_splitk(x, ldx, w, b, y, ldy, m, n, k, relu, precision, scratch, scratch_floats, static_cast<hipStream_t>(stream_),
+                                     &status, w2 ? &next : nullptr);
+    if (taken_and_fused) { taken_and_fused[0] = taken ? 1 : 0; taken_and_fused[1] = next.done ? 1 : 0; }
+    return status;
+}

@@ -184,3 +184,97 @@ def test_segment_debug_entries_argument_checks_without_gpu():
     # bf16 rows: a width that is no multiple of 4 is refused by the alignment check, before any launch
     assert l.mpnhip_debug_segment_reduce3(jobs(dim=82), 10, 1, None) == -1
     assert b"alignment" in l.mpnhip_last_error()
+
+
+def test_debug_gemm_layout_matches_c():
+    # mpnhip_debug_gemm_group: 14 pointers, 8 int64; mpnhip_debug_gemm_args: two groups, 6 ints, int64, 3 ints (+ 4 bytes of padding)
+    G, A = capi.DebugGemmGroup, capi.DebugGemmArgs
+    g_fields = ["A", "A2", "a_idx", "B", "bias", "G1", "g1_idx", "G2", "g2_idx", "mask", "C", "c_idx", "row_begin", "row_end",
+                "lda", "lda2", "ldb", "ldg1", "ldg2", "ldmask", "ldc", "m_static"]
+    assert ctypes.sizeof(G) == 22 * 8 == 176
+    assert [f[0] for f in G._fields_] == g_fields
+    for i, name in enumerate(g_fields):
+        assert getattr(G, name).offset == 8 * i, name
+    offsets = dict(g=0, ngroups=352, N=356, K=360, ksplit=364, relu=368, accumulate=372, m_upper=376, small_tiles=384, b_layout=388,
+                   precision=392)
+    assert ctypes.sizeof(A) == 2 * 176 + 6 * 4 + 8 + 3 * 4 + 4 == 400
+    assert [f[0] for f in A._fields_] == list(offsets)
+    for name, off in offsets.items():
+        assert getattr(A, name).offset == off, name
+    # the header declares the fields in the same order
+    src = open(os.path.join(REPO, "include", "mpnhip.h")).read()
+    body = re.search(r"typedef struct mpnhip_debug_gemm_group \{(.*?)\} mpnhip_debug_gemm_group;", src, flags=re.S).group(1)
+    assert re.findall(r"(\w+);", body) == g_fields
+    body = re.search(r"typedef struct mpnhip_debug_gemm_args \{(.*?)\} mpnhip_debug_gemm_args;", src, flags=re.S).group(1)
+    assert re.findall(r"(\w+)(?:\[2\])?;", body) == list(offsets)
+    layouts = {m.group(1): int(m.group(2)) for m in re.finditer(r"#define MPNHIP_GEMM_B_([A-Z]+) (\d+)", src)}
+    assert layouts == {"KCONTIG": 0, "NCONTIG": 1}
+
+
+def test_gemm_debug_entries_argument_checks_without_gpu():
+    """mpnhip_debug_gemm and mpnhip_debug_linear_splitk check their arguments on the host: everything below returns before a kernel
+    is launched (the non-null pointers are host dummies that are never dereferenced)."""
+    l = capi.load()
+    dummy = ctypes.create_string_buffer(256)
+    p = ctypes.cast(dummy, ctypes.c_void_p).value
+
+    def args(**kw):
+        a = capi.DebugGemmArgs()
+        a.ngroups, a.N, a.K, a.ksplit, a.m_upper = 1, 8, 8, 8, 16
+        for g in a.g:
+            g.A, g.B, g.C, g.lda, g.ldb, g.ldc, g.m_static = p, p, p, 8, 8, 8, 16
+        for k, v in kw.items():
+            setattr(a, k, v)
+        return a
+    chosen = (ctypes.c_int32 * 4)(7, 7, 7, 7)
+    assert l.mpnhip_debug_gemm(None, chosen, None) == -1
+    assert b"debug_gemm: null args" in l.mpnhip_last_error()
+    for bad, msg in ((dict(ngroups=0), b"ngroups"), (dict(ngroups=3), b"ngroups"), (dict(ngroups=-1), b"ngroups"),
+                     (dict(b_layout=2), b"b_layout"), (dict(b_layout=-1), b"b_layout"),
+                     (dict(precision=3), b"precision"), (dict(precision=-1), b"precision"),
+                     (dict(b_layout=1, precision=1), b"fp32 operands only"), (dict(b_layout=1, precision=2), b"fp32 operands only")):
+        assert l.mpnhip_debug_gemm(ctypes.byref(args(**bad)), chosen, None) == -1, bad
+        err = l.mpnhip_last_error()
+        assert b"debug_gemm" in err and msg in err, (bad, err)
+    assert list(chosen) == [7, 7, 7, 7]     # a refusal of the entry itself leaves `chosen` alone
+    # launch_gemm's own checks follow: ksplit beyond K, ksplit without A2, a null operand
+    assert l.mpnhip_debug_gemm(ctypes.byref(args(ksplit=12)), None, None) == -1
+    assert b"gemm: bad N/K/ksplit" in l.mpnhip_last_error()
+    assert l.mpnhip_debug_gemm(ctypes.byref(args(ksplit=4)), None, None) == -1
+    assert b"second A segment" in l.mpnhip_last_error()
+    a = args()
+    a.g[0].B = None
+    assert l.mpnhip_debug_gemm(ctypes.byref(a), None, None) == -1
+    assert b"null operand" in l.mpnhip_last_error()
+    # no rows: a successful no-op in every layout / precision, nothing chosen
+    for bl, prec in ((0, 0), (0, 1), (0, 2), (1, 0)):
+        for ng in (1, 2):
+            assert l.mpnhip_debug_gemm(ctypes.byref(args(m_upper=0, b_layout=bl, precision=prec, ngroups=ng)), chosen, None) == 0
+            assert list(chosen) == [-1, 0, 0, 0]
+
+    # split-K scratch: 0 for k < 512, more than 8192 rows, 320 or more 64 x 64 tiles; positive otherwise
+    sf = l.mpnhip_debug_linear_splitk_scratch_floats
+    assert sf(140, 128, 508) == 0 and sf(140, 128, 512) > 0
+    assert sf(8193, 64, 2048) == 0 and sf(8192, 64, 2048) > 0
+    assert sf(64 * 319, 64, 2048) == 0              # more than 8192 rows
+    assert sf(64 * 20, 64 * 16, 2048) == 0          # 20 x 16 = 320 tiles
+    assert sf(64 * 20 + 1, 64 * 16, 2048) == 0      # 336 tiles
+    assert sf(64 * 20, 64 * 16 - 1, 2048) == 0      # still 320 tiles
+    assert sf(64 * 20, 64 * 15 + 63, 2048) == 0
+    assert sf(64 * 19 + 63, 64 * 16, 2048) == 0
+    assert sf(64 * 29, 64 * 11, 2048) > 0           # 319 tiles
+    assert sf(0, 64, 2048) == 0
+    for m, n, k in ((1, 36, 512), (65, 100, 704), (140, 128, 2048), (5000, 128, 2048)):
+        assert sf(m, n, k) >= 2 * m * n, (m, n, k)
+    # the entry: refusals, and shapes that are not this path's return MPNHIP_OK with taken = 0 before any launch
+    tf = (ctypes.c_int32 * 2)(5, 5)
+    assert l.mpnhip_debug_linear_splitk(None, 512, p, None, p, 8, 4, 8, 512, 0, 0, None, None, 0, 0, None, 0, p, 1 << 20, tf, None) == -1
+    assert b"debug_linear_splitk" in l.mpnhip_last_error() and list(tf) == [0, 0]
+    assert l.mpnhip_debug_linear_splitk(p, 512, p, None, p, 8, 4, 8, 512, 0, 3, None, None, 0, 0, None, 0, p, 1 << 20, tf, None) == -1
+    assert l.mpnhip_debug_linear_splitk(p, 512, p, None, p, 8, 4, 8, 512, 0, 0, p, None, 4, 0, None, 0, p, 1 << 20, tf, None) == -1
+    for kw in (dict(k=508), dict(prec=1), dict(scratch=None), dict(floats=7), dict(m=0), dict(m=8193), dict(ldx=514), dict(k=514, ldx=516)):
+        m, k, prec, floats = kw.get("m", 4), kw.get("k", 512), kw.get("prec", 0), kw.get("floats", 1 << 20)
+        tf[0] = tf[1] = 5
+        assert l.mpnhip_debug_linear_splitk(p, kw.get("ldx", k), p, None, p, 8, m, 8, k, 0, prec, None, None, 0, 0, None, 0,
+                                            kw.get("scratch", p), floats, tf, None) == 0, kw
+        assert list(tf) == [0, 0], kw
