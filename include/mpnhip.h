@@ -465,6 +465,44 @@ int mpnhip_attention_aggregate_backward(const void* graph_buf, int n_nodes, int6
  * the hw contiguous spatial positions (rows = N * C). */
 int mpnhip_avgpool(const float* x, int64_t rows, int hw, float* y, void* stream);
 
+/* Mask branch, inference: the convolution-type layers of models/cnn.py and MaskModel (models/mpn.py:180-206) without autograd.
+ * Everything is NCHW fp32; products are exact fp32 with fp32 accumulation in a fixed k order (input channel, then tap), one
+ * block per (image, output tile, output-channel group): a pixel's value does not depend on how many images the call holds or
+ * where its image sits among them.  No workspace.
+ *
+ * The input is the channel-wise concatenation of n_segments (1 .. MPNHIP_CONV_MAX_SEGMENTS) tensors that is never
+ * materialised: segment s holds seg_channels[s] channels of every image, image i at seg_data[s] + i * seg_stride[s] (floats),
+ * channels and pixels dense behind it ([channels][H][W]).  The output image i starts at out + i * out_stride (floats) and is
+ * dense [cout][Hout][Wout]: a stride wider than that writes a channel slice of a wider tensor and leaves the rest alone.
+ *
+ *   transposed == 0: nn.Conv2d(cin, cout, ksize, stride 1, padding ksize / 2), ksize 1 or 3; weight [cout][cin][ksize][ksize];
+ *                    Hout = H, Wout = W.  cout <= 8 takes a plain (non-MFMA) kernel with the same summation order.
+ *   transposed != 0: nn.ConvTranspose2d(cin, cout, 2, stride 2, padding 0), ksize must be 2; weight [cin][cout][2][2];
+ *                    Hout = 2 H, Wout = 2 W.
+ * bias [cout] or NULL (no bias); relu != 0: max(., 0) at the end.
+ *
+ * Checked on the host before any launch (MPNHIP_ERR_ARG): null args; n_images < 0; (n_images == 0 is a successful no-op, nothing
+ * else is looked at;) n_segments outside 1 .. 4; a segment with a null pointer, no channels or a negative stride; H, W or
+ * cout < 1; a kernel size other than the ones above; null weight or out; and any stride, image size (cin * H * W,
+ * cout * Hout * Wout) or weight count beyond INT32_MAX -- the kernels index inside an image with 32 bits. */
+#define MPNHIP_CONV_MAX_SEGMENTS 4
+typedef struct mpnhip_conv_args {
+    const float* seg_data[4]; int64_t seg_stride[4]; int seg_channels[4]; int n_segments;
+    int H; int W; int cout; int ksize; int transposed; int relu;
+    int64_t n_images; const float* weight; const float* bias; float* out; int64_t out_stride;
+} mpnhip_conv_args;
+int mpnhip_conv2d_forward(const mpnhip_conv_args* args, void* stream);
+
+/* nn.LayerNorm over the trailing [C][H][W] of every image (MaskModel.layer_norm), elementwise affine of that same shape:
+ * out = (x - mean) / sqrt(var + eps) * weight + bias with the biased variance of the centred values (two passes: the mean first).
+ * The input is a segment list as above (C = the sum of seg_channels, hw = H * W), weight / bias [C * hw] (both or neither may
+ * be NULL: no affine), out image i at out + i * out_stride.  Refusals as for the convolution: null lists, n_segments outside
+ * 1 .. 4, null / empty segments, hw < 1, eps < 0 or not finite, null out, sizes or strides beyond INT32_MAX; n_images == 0 is
+ * a successful no-op. */
+int mpnhip_layer_norm_forward(const float* const* seg_data, const int64_t* seg_stride, const int* seg_channels, int n_segments,
+                              int64_t n_images, int64_t hw, const float* weight, const float* bias, float eps, float* out,
+                              int64_t out_stride, void* stream);
+
 /* torch.optim.Adam(lr, betas, eps, weight_decay).step() (the optimizer of pl_module.py:76-77, configs/tracking_cfg.yaml:6-10)
  * over FLAT fp32 buffers of n elements: parameters, gradients (as the backward / all-reduce left them) and the two
  * moment buffers (zero before step 1); step = 1, 2, ... counts the calls. */

@@ -1,9 +1,17 @@
 """Host-side mirror of the reference's conv stacks of the mask branch
 (``/root/reference/src/mot_neural_solver/models/cnn.py``): same constructor arguments and the same
-``layers`` Sequential indices, so the reference's ``state_dict`` keys load.  These stay stock PyTorch-ROCm
-(MIOpen) modules -- SURVEY.md section 2.2 leaves the convolutions to the vendor library; the native part of the
-mask branch is the attention aggregation (``mpnhip_attention_aggregate``)."""
+``layers`` Sequential indices, so the reference's ``state_dict`` keys load.
+
+``forward`` runs the stock PyTorch-ROCm (MIOpen) modules: training and everything that records gradients goes there.
+``forward_native`` is the no-grad inference forward through ``mpnhip_conv2d_forward`` (csrc/conv.hip): one native call per
+(transposed) convolution with its bias and ReLU fused, the input given as a list of channel segments so that a ``torch.cat`` in
+front of the stack is never materialised.  ``native_supported()`` says whether the stack is one the kernels cover."""
+import ctypes as C
+
+import torch
 from torch import nn
+
+from . import capi
 
 
 def _check_lists(**kw):
@@ -11,6 +19,122 @@ def _check_lists(**kw):
         assert isinstance(v, (list, tuple)), '%s must be either a list or a tuple, but got %s' % (name, type(v))
     lens = {len(v) for v in kw.values()}
     assert len(lens) == 1, 'Number of elements mismatch between dims, kernel_sizes and strides'
+
+
+def _image_dense(t):
+    """[N, C, H, W] float32 whose images are dense [C][H][W] blocks at any image stride (a channel slice of a wider tensor is)."""
+    n, c, h, w = t.shape
+    if t.dtype != torch.float32:
+        return False
+    return t.numel() == 0 or ((w == 1 or t.stride(3) == 1) and (h == 1 or t.stride(2) == w) and (c == 1 or t.stride(1) == h * w))
+
+
+def _segments(tensors):
+    """The segment list of a native call: the tensors themselves where their images are dense, contiguous copies otherwise."""
+    capi.require_device(*tensors)
+    if not 1 <= len(tensors) <= capi.CONV_MAX_SEGMENTS:
+        raise capi.MpnhipError("a native convolution takes 1 .. %d channel segments, not %d" % (capi.CONV_MAX_SEGMENTS, len(tensors)))
+    segs = [t if _image_dense(t) else capi.f32c(t) for t in tensors]
+    if any(s.dim() != 4 or s.shape[0] != segs[0].shape[0] or s.shape[2:] != segs[0].shape[2:] or s.device != segs[0].device
+           for s in segs):
+        raise capi.MpnhipError("channel segments must be [N, C_s, H, W] tensors of one N, H, W and device")
+    return segs
+
+
+def _out_tensor(out, shape, like):
+    if out is None:
+        return torch.empty(shape, dtype=torch.float32, device=like.device)
+    if tuple(out.shape) != tuple(shape) or not out.is_cuda or out.device != like.device or not _image_dense(out):
+        raise capi.MpnhipError("out must be a float32 %s device tensor with dense images (a channel slice is)" % (tuple(shape),))
+    return out
+
+
+def conv2d_native(segments, weight, bias, relu=False, transposed=False, out=None):
+    """``mpnhip_conv2d_forward`` on the channel concatenation of ``segments``: Conv2d(k = 1 | 3, stride 1, padding k // 2) with
+    ``weight`` [cout, cin, k, k], or ConvTranspose2d(2, stride 2) with ``weight`` [cin, cout, 2, 2].  No autograd."""
+    segs = _segments(list(segments))
+    w = capi.f32c(weight.detach())
+    b = capi.f32c(bias.detach()) if bias is not None else None
+    capi.require_device(w, b)
+    n, _, h, wd = segs[0].shape
+    cin = sum(int(s.shape[1]) for s in segs)
+    cout = int(w.shape[1] if transposed else w.shape[0])
+    if int(w.shape[0] if transposed else w.shape[1]) != cin or w.shape[2] != w.shape[3]:
+        raise capi.MpnhipError("weight %s does not fit %d input channels" % (tuple(w.shape), cin))
+    scale = 2 if transposed else 1
+    y = _out_tensor(out, (n, cout, scale * h, scale * wd), segs[0])
+    a = capi.ConvArgs()
+    for i, s in enumerate(segs):
+        a.seg_data[i], a.seg_stride[i], a.seg_channels[i] = s.data_ptr(), s.stride(0), int(s.shape[1])
+    a.n_segments, a.H, a.W, a.cout, a.ksize, a.transposed, a.relu = len(segs), int(h), int(wd), cout, int(w.shape[2]), int(transposed), int(relu)
+    a.n_images, a.weight, a.bias, a.out, a.out_stride = int(n), w.data_ptr(), (b.data_ptr() if b is not None else None), y.data_ptr(), y.stride(0)
+    with torch.cuda.device(y.device):
+        capi.check(capi.load().mpnhip_conv2d_forward(C.byref(a), capi.stream_ptr()), "mpnhip_conv2d_forward")
+    return y
+
+
+def layer_norm_native(segments, weight, bias, eps, out=None):
+    """``mpnhip_layer_norm_forward``: nn.LayerNorm over the trailing [C, H, W] of the channel concatenation of ``segments``."""
+    segs = _segments(list(segments))
+    n, _, h, wd = segs[0].shape
+    c = sum(int(s.shape[1]) for s in segs)
+    w = capi.f32c(weight.detach()) if weight is not None else None
+    b = capi.f32c(bias.detach()) if bias is not None else None
+    capi.require_device(w, b)
+    if w is not None and (b is None or w.numel() != c * h * wd or b.numel() != w.numel()):
+        raise capi.MpnhipError("the LayerNorm affine must have the input's [%d, %d, %d] elements" % (c, h, wd))
+    y = _out_tensor(out, (n, c, h, wd), segs[0])
+    k = len(segs)
+    data = (C.c_void_p * k)(*[s.data_ptr() for s in segs])
+    stride = (C.c_int64 * k)(*[s.stride(0) for s in segs])
+    chans = (C.c_int * k)(*[int(s.shape[1]) for s in segs])
+    with torch.cuda.device(y.device):
+        capi.check(capi.load().mpnhip_layer_norm_forward(data, stride, chans, k, int(n), int(h * wd), capi.ptr(w), capi.ptr(b), float(eps),
+                                                         capi.ptr(y), y.stride(0), capi.stream_ptr()), "mpnhip_layer_norm_forward")
+    return y
+
+
+def _pair(v):
+    return tuple(v) if isinstance(v, (tuple, list)) else (v, v)
+
+
+def _conv_native_supported(m):
+    if m.weight.dtype != torch.float32 or _pair(m.dilation) != (1, 1) or m.groups != 1:
+        return False
+    k, st, pad = _pair(m.kernel_size), _pair(m.stride), _pair(m.padding)
+    if isinstance(m, nn.ConvTranspose2d):
+        return k == (2, 2) and st == (2, 2) and pad == (0, 0) and _pair(m.output_padding) == (0, 0)
+    return k in ((1, 1), (3, 3)) and st == (1, 1) and pad == (k[0] // 2, k[0] // 2) and m.padding_mode == 'zeros'
+
+
+def _layers_native_supported(layers):
+    """The predicate of ``native_supported`` on a ``layers`` Sequential."""
+    for m in layers:
+        if isinstance(m, (nn.Conv2d, nn.ConvTranspose2d)):
+            if not _conv_native_supported(m):
+                return False
+        elif isinstance(m, (nn.Dropout, nn.Dropout2d)):
+            if m.p != 0 and m.training:
+                return False
+        elif not isinstance(m, nn.ReLU):
+            return False       # BatchNorm2d and anything else the kernels do not cover
+    return True
+
+
+def _layers_forward_native(layers, segments, out):
+    """One native call per convolution of ``layers``, the ReLU that follows it fused; ``out``: where the LAST one writes."""
+    mods = list(layers)
+    convs = [i for i, m in enumerate(mods) if isinstance(m, (nn.Conv2d, nn.ConvTranspose2d))]
+    if not convs:
+        raise capi.MpnhipError("forward_native: the stack has no convolution")
+    x = list(segments)
+    for i in convs:
+        m = mods[i]
+        relu = i + 1 < len(mods) and isinstance(mods[i + 1], nn.ReLU)
+        y = conv2d_native(x, m.weight, m.bias, relu=relu, transposed=isinstance(m, nn.ConvTranspose2d),
+                          out=out if i == convs[-1] else None)
+        x = [y]
+    return x[0]
 
 
 class CNN(nn.Module):
@@ -35,6 +159,18 @@ class CNN(nn.Module):
     def forward(self, input):
         return self.layers(input)
 
+    def native_supported(self):
+        """Whether ``forward_native`` covers this stack: every convolution has stride 1 and kernel 1 or 3 with padding k // 2, there
+        is no BatchNorm, and Dropout is off (p = 0 or eval mode)."""
+        return _layers_native_supported(self.layers)
+
+    def forward_native(self, segments, out=None):
+        """Inference forward (no autograd) on the channel concatenation of ``segments`` (a list of [N, C_s, H, W] device tensors,
+        channel slices allowed); the last convolution writes into ``out`` when given (it may be a channel slice too)."""
+        if not self.native_supported():
+            raise capi.MpnhipError("this CNN is not covered by the native convolutions (see native_supported)")
+        return _layers_forward_native(self.layers, segments, out)
+
 
 class MaskRCNNPredictor(nn.Module):
     """cnn.py:47-84: (transposed) convolutions with a ReLU after every layer but the last."""
@@ -55,3 +191,13 @@ class MaskRCNNPredictor(nn.Module):
 
     def forward(self, input):
         return self.layers(input)
+
+    def native_supported(self):
+        """As ``CNN.native_supported``; a transposed convolution must have kernel 2, stride 2, padding 0."""
+        return _layers_native_supported(self.layers)
+
+    def forward_native(self, segments, out=None):
+        """As ``CNN.forward_native``."""
+        if not self.native_supported():
+            raise capi.MpnhipError("this MaskRCNNPredictor is not covered by the native convolutions (see native_supported)")
+        return _layers_forward_native(self.layers, segments, out)

@@ -13,7 +13,7 @@ import torch
 from torch import nn
 
 from . import capi
-from .cnn import CNN, MaskRCNNPredictor
+from .cnn import CNN, MaskRCNNPredictor, layer_norm_native
 from .mlp import MLP
 
 
@@ -297,13 +297,24 @@ class TimeAwareAttentionModel(nn.Module):
         flow = torch.cat((x, flow_in, flow_out), dim=1)          # mpn.py:136
         return self.node_model(flow)
 
+    def aggregate_native(self, x, edge_index, dec_edge_feats, holder=None, out=None):
+        """``aggregate`` for inference without autograd: ``node_model`` through the native convolutions on the segments
+        (x, flow_in, flow_out) -- no ``torch.cat``; its last convolution writes into ``out`` when given (a channel slice of ``x``
+        is allowed as long as ``node_model`` has more than one convolution: the first one has read ``x`` by then)."""
+        capi.require_device(x, edge_index, dec_edge_feats)
+        g = _prepared(edge_index, x.shape[0], holder)
+        flow_in, flow_out = _AttentionAggregate.apply(g, x, dec_edge_feats)
+        return self.node_model.forward_native([x, flow_in.view_as(x), flow_out.view_as(x)], out=out)
+
     def forward(self, x, edge_index, edge_attr, cls_net):
         dec_edge_feats, _ = cls_net(edge_attr)                    # mpn.py:114
         return self.aggregate(x, edge_index, dec_edge_feats), dec_edge_feats
 
 
 class MaskModel(nn.Module):
-    """mpn.py:180-206 (stock convolutions / LayerNorm)."""
+    """mpn.py:180-206.  ``forward``: stock convolutions / LayerNorm (training, autograd).  ``forward_native``: the same layers
+    for inference through ``mpnhip_conv2d_forward`` / ``mpnhip_layer_norm_forward``, the concatenation in front of the LayerNorm
+    read as two segments."""
 
     def __init__(self, mask_model_params):
         super(MaskModel, self).__init__()
@@ -316,6 +327,20 @@ class MaskModel(nn.Module):
         x = torch.cat((self.feature_encoder(feature_embeds), node_embeds), dim=1)
         return self.mask_predictor(self.mask_head(self.layer_norm(x)))
 
+    def native_supported(self):
+        return self.feature_encoder.native_supported() and self.mask_head.native_supported() and \
+            self.mask_predictor.native_supported() and len(self.layer_norm.normalized_shape) == 3
+
+    def forward_native(self, feature_embeds, node_embeds):
+        """``forward`` without autograd; ``node_embeds`` may be a channel slice of a wider tensor."""
+        ln = self.layer_norm
+        feats = self.feature_encoder.forward_native([feature_embeds])
+        shape = (feats.shape[1] + node_embeds.shape[1],) + tuple(feats.shape[2:])
+        if shape != tuple(ln.normalized_shape):
+            raise capi.MpnhipError("LayerNorm(%s) does not fit the %s features" % (tuple(ln.normalized_shape), shape))
+        x = layer_norm_native([feats, node_embeds], ln.weight, ln.bias, ln.eps)
+        return self.mask_predictor.forward_native([self.mask_head.forward_native([x])])
+
 
 class MOTMPNet(nn.Module):
     """mpn.py:209-394.  ``MOTMPNet(model_params, bb_encoder=None)``; ``forward(data)`` returns
@@ -324,7 +349,11 @@ class MOTMPNet(nn.Module):
     The encoder -> message passing -> classifier loop (the hot path) is ONE native call.  The x_ext /
     attention / mask branch of the reference (mpn.py:102-137,180-206) never feeds back into the edge logits
     (SURVEY.md section 3.3), so it runs AFTER the hot path, step by step, on the per-step logits: its neighbour
-    aggregation is native (``mpnhip_attention_aggregate``), its convolutions are stock PyTorch-ROCm modules.
+    aggregation is native (``mpnhip_attention_aggregate``).  Its convolutions, transposed convolutions and LayerNorm are
+    stock PyTorch-ROCm modules by default (``mask_convs = 'stock'``: training, autograd); with ``mask_convs = 'native'`` a
+    no-grad call of ``mask_predictions`` runs all of them through ``mpnhip_conv2d_forward`` / ``mpnhip_layer_norm_forward``
+    (csrc/conv.hip) and falls back to the stock modules, silently, whenever gradients are being recorded, a tensor is not
+    on the device or a module is outside what the kernels cover (``native_supported``).
     It is built only when ``model_params`` carries the mask-branch dicts (as configs/tracking_cfg.yaml does) and
     evaluated only when ``data.x_ext`` is present; otherwise ``mask_predictions`` is an empty list.
     """
@@ -351,6 +380,8 @@ class MOTMPNet(nn.Module):
         # inference only: keep the packed weight images between calls (see frozen_weights()); off by default, because an
         # in-place write through ``p.data`` / a raw pointer does not move ``p._version`` and would go unnoticed
         self.keep_packed_weights = False
+        # 'stock' | 'native': how mask_predictions runs the mask branch's convolutions and LayerNorm (see the class docstring)
+        self.mask_convs = 'stock'
 
     def _build_core_MPNet(self, model_params, encoder_feats_dict):
         """mpn.py:254-317."""
@@ -603,6 +634,10 @@ class MOTMPNet(nn.Module):
         alone (a one-element list, bitwise the full list's ``[-1]``) -- inference reads nothing else (mpn_tracker.py:132), and
         the attention chain over all the steps, which it depends on, still runs."""
         L, k = int(self.num_enc_steps), int(self.num_class_steps)
+        if self.mask_convs not in ('stock', 'native'):
+            raise capi.MpnhipError("mask_convs must be 'stock' or 'native', not %r" % (self.mask_convs,))
+        if self.mask_convs == 'native' and self._mask_native_ok(x_ext, edge_index, logits):
+            return self._mask_predictions_native(x_ext, edge_index, logits, holder, last_only)
         latent_node_ext_feats = self.node_ext_encoder(x_ext)                           # mpn.py:356
         initial_node_ext_feats = latent_node_ext_feats
         first_class_step = L - k + 1
@@ -616,6 +651,52 @@ class MOTMPNet(nn.Module):
                 preds.append(self.mask_predictor(x_ext, latent_node_ext_feats))
         if L == 0:
             preds.append(self.mask_predictor(x_ext, latent_node_ext_feats))
+        return preds
+
+    def _mask_modules(self):
+        return (self.node_ext_encoder, self.MPAttentionNet.node_model, self.mask_predictor)
+
+    def _mask_native_ok(self, x_ext, edge_index, logits):
+        """The conditions of the native mask branch: device tensors, modules the kernels cover, no gradient being recorded."""
+        tensors = (x_ext, edge_index, logits)
+        if not all(isinstance(t, torch.Tensor) and t.is_cuda for t in tensors) or x_ext.dim() != 4 or x_ext.dtype != torch.float32:
+            return False
+        params = [p for m in self._mask_modules() for p in m.parameters()]
+        if not all(p.is_cuda for p in params) or not all(m.native_supported() for m in self._mask_modules()):
+            return False
+        return not (torch.is_grad_enabled() and any(t.requires_grad for t in (x_ext, logits) + tuple(params)))
+
+    def _mask_predictions_native(self, x_ext, edge_index, logits, holder, last_only):
+        """``mask_predictions`` through the native convolutions.  With ``reattach_initial_nodes`` one [N, 2 c, H, W] buffer holds
+        ``initial || latent``: the encoder writes the first half, every step's node model the second -- no ``torch.cat``."""
+        L, k = int(self.num_enc_steps), int(self.num_class_steps)
+        first_class_step = L - k + 1
+        node_model = self.MPAttentionNet.node_model
+        n_convs = sum(isinstance(m, nn.Conv2d) for m in node_model.layers)
+        with torch.no_grad():
+            x_ext = x_ext.detach()
+            buf = None
+            if self.reattach_initial_nodes and L > 0:
+                c = [m for m in self.node_ext_encoder.layers if isinstance(m, nn.Conv2d)][-1].out_channels
+                buf = torch.empty((x_ext.shape[0], 2 * c) + tuple(x_ext.shape[2:]), dtype=torch.float32, device=x_ext.device)
+                self.node_ext_encoder.forward_native([x_ext], out=buf[:, :c])           # mpn.py:356
+                latent = buf[:, c:]
+                latent.copy_(buf[:, :c])
+            else:
+                latent = self.node_ext_encoder.forward_native([x_ext])
+            preds = []
+            for step in range(1, L + 1):
+                if buf is not None:                                                     # mpn.py:373: initial || latent, in place
+                    new = self.MPAttentionNet.aggregate_native(buf, edge_index, logits[step - 1].detach(), holder=holder,
+                                                               out=latent if n_convs > 1 else None)
+                    if new is not latent:
+                        latent.copy_(new)
+                else:
+                    latent = self.MPAttentionNet.aggregate_native(latent, edge_index, logits[step - 1].detach(), holder=holder)
+                if step >= first_class_step and (step == L or not last_only):
+                    preds.append(self.mask_predictor.forward_native(x_ext, latent))
+            if L == 0:
+                preds.append(self.mask_predictor.forward_native(x_ext, latent))
         return preds
 
 
