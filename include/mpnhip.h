@@ -807,6 +807,40 @@ int mpnhip_hota_association(const int32_t* matches_count, const int32_t* gt_coun
                             int64_t n_tr_ids, double* out, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Batched rectangular linear sum assignment: scipy.optimize.linear_sum_assignment(cost, maximize) for n_problems problems in
+ * one launch, in the layout of the HOTA calls above (a score block goes in as it is).  Problem f owns the a-entries a_ptr[f] ..
+ * a_ptr[f + 1] and the b-entries b_ptr[f] .. b_ptr[f + 1] of two lists (device int32 [n_problems + 1]) and na_f x nb_f float64
+ * cells at cell_ptr[f] (device int64 [n_problems + 1]), cell [ia * nb_f + ib]; cells is their number (< 2^31).  a_keep [n_a] /
+ * b_keep [n_b] (uint8, 1 = the entry takes part; NULL = all of them).
+ *   match_b [n_a] (int32): the b-entry (index into the whole list, b_ptr[f] + ib) assigned to the a-entry, or -1;
+ *   match_a [n_b] (int32; may be NULL): its inverse.  Both are filled with -1 by the call first.
+ * Over its kept rows and columns a problem gets a complete assignment of min(kept rows, kept columns) pairs of optimal total
+ * cost; a problem with no kept row or no kept column gets nothing and status 0.
+ *   status [n_problems] (int32): 0 solved; 1 the costs are not finite -- a NaN among the kept cells, or a search that finds no
+ *   column at a finite distance (-inf, or only +inf left); 2 more than MPNHIP_LSA_MAX_SIDE kept rows or kept columns (the lists
+ *   are device arrays, so this refusal happens on the device); 3 the problem's cells do not lie inside cost.  A problem with a
+ *   status other than 0 gets only -1; the other problems of the launch are not affected.
+ * The algorithm is the shortest augmenting path of Crouse 2016 (scipy's) in float64 on c = maximize ? -cost : cost, with more
+ * kept rows than kept columns on the transpose (by index, nothing is copied): rows in list order, r = ((minval + c[i][j]) - u[i])
+ * - v[j] taken only if r < shortest[j], the next column the unscanned one of lowest shortest -- among equals an unassigned one,
+ * lowest index first, otherwise the lowest index.  Where the optimum is unique the pairs are scipy's; among ties they need not
+ * be (the total is).  One wavefront per problem, no floating-point atomics, no sums in a tree: the same bits on every call
+ * (tests/lsa_ref.py restates it in numpy).  Every loop is bounded by a counter: at most kept rows x kept columns column scans
+ * per problem.  Every index read from a caller's array is clamped or checked before it is used.
+ * n_problems == 0, or n_a == 0 and n_b == 0: a successful no-op (status is not written).  MPNHIP_ERR_UNSUPPORTED for
+ * cells >= 2^31.
+ * ------------------------------------------------------------------------------------------- */
+/* largest number of kept rows, or of kept columns, of one problem: its state (u, v, shortest, path, col4row, row4col, the two
+ * lists of kept entries, the two scanned sets: 46 B per row or column) stays in the LDS of one workgroup, 160 KiB on gfx950 */
+#define MPNHIP_LSA_MAX_SIDE 2048
+/* Bytes mpnhip_lsa_batched needs for these sizes (a small constant: the state lives in LDS).  0 for sizes the call refuses. */
+size_t mpnhip_lsa_workspace_bytes(int64_t n_a, int64_t n_b, int64_t n_problems);
+int mpnhip_lsa_batched(const double* cost, int64_t cells, const int64_t* cell_ptr, const int32_t* a_ptr, int64_t n_a,
+                       const int32_t* b_ptr, int64_t n_b, int64_t n_problems, const unsigned char* a_keep, const unsigned char* b_keep,
+                       int maximize, int32_t* match_b, int32_t* match_a, int32_t* status, void* workspace, size_t workspace_bytes,
+                       void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Measurement helpers used by bench.py (HIP events on the launch stream; these synchronise).
  * ------------------------------------------------------------------------------------------- */
 /* In-stream kernel timing of the real hot path: while enabled, mpnhip_forward brackets (a) the first-layer

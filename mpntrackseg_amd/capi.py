@@ -210,6 +210,8 @@ SIGNATURES = {
     "mpnhip_hota_frame_scores": (_I, [_P, _L, _P, _P, _L, _P, _L, _L, _P, _P, _P, _L, _L, _P, _P, _P, _P, _P]),
     "mpnhip_hota_alpha_accumulate": (_I, [_P, _L, _P, _P, _L, _P, _L, _L, _P, _P, _P, _P, _P, _L, _L, _P, _P, _P, _P, _Z, _P]),
     "mpnhip_hota_association": (_I, [_P, _P, _P, _L, _L, _P, _P, _Z, _P]),
+    "mpnhip_lsa_workspace_bytes": (_Z, [_L, _L, _L]),
+    "mpnhip_lsa_batched": (_I, [_P, _L, _P, _P, _L, _P, _L, _L, _P, _P, _I, _P, _P, _P, _P, _Z, _P]),
     "mpnhip_profile_enable": (_I, [_I]),
     "mpnhip_edge_chain_active": (_I, [C.POINTER(Model)]),
     "mpnhip_profile_read": (_I, [C.POINTER(C.c_float), C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(C.c_int),

@@ -7,9 +7,12 @@ A frame is one int32 label per pixel on either side, and all its mask intersecti
 -- the pixel work of ``mots_eval``, run once per frame.  Everything HOTA does with the tables stays on the device: the IoU block
 of every frame and the predictions the preprocessing removes (``frame_similarity``), the global alignment of the ids
 (``accumulate_alignment``), the cells of the per-frame assignment problems (``frame_scores``), the counts per alpha
-(``alpha_accumulate``) and the association sums (``association``).  The assignment itself is
-``scipy.optimize.linear_sum_assignment`` on the host, as the IDF1 assignment of ``mots_eval`` is: per launch the score cells come
-down in one copy and the chosen prediction of every ground-truth entry goes up in one.  ``pycocotools`` is not needed.
+(``alpha_accumulate``) and the association sums (``association``).  The assignment itself is, by default
+(``assignment='host'``), ``scipy.optimize.linear_sum_assignment`` on the host, as the IDF1 assignment of ``mots_eval`` is: per
+launch the score cells come down in one copy and the chosen prediction of every ground-truth entry goes up in one.  With
+``assignment='device'`` it is ``assignment.linear_sum_assignment_batched`` on the score block as it lies, one problem per frame:
+no score cell comes down and no match goes up, only the solver's status per frame, once per sequence.  Where a frame's optimum
+is not unique the two may choose different pairs of the same total.  ``pycocotools`` is not needed.
 
 The alignment needs every frame before the first assignment, so each launch's similarity block stays on the device between the
 two passes: 8 B x (sum over the frames of objects x predictions), plus 8 B per entry -- about 3 MB for a thousand frames of
@@ -130,8 +133,9 @@ def accumulate_alignment(S, a_traj, b_traj, acc):
               "mpnhip_hota_accumulate_alignment")
 
 
-def frame_scores(S, a_traj, b_traj, acc):
-    """The score cells of the launch ``S`` (the layout of ``sim``) as a host array (``mpnhip_hota_frame_scores``)."""
+def frame_scores(S, a_traj, b_traj, acc, host=True):
+    """The score cells of the launch ``S`` (the layout of ``sim``; ``mpnhip_hota_frame_scores``) as a host array, or with
+    ``host=False`` as the device tensor."""
     lib = capi.load()
     dev = S["sim"].device
     with torch.cuda.device(dev):
@@ -141,7 +145,7 @@ def frame_scores(S, a_traj, b_traj, acc):
                                            S["n_b"], S["F"], ptr(at), ptr(bt), ptr(S["b_removed"]), acc["n_gt"], acc["n_tr"],
                                            ptr(acc["potential"]), ptr(acc["gt_count"]), ptr(acc["tr_count"]), ptr(score), stream_ptr()),
               "mpnhip_hota_frame_scores")
-        return score.cpu().numpy()
+        return score.cpu().numpy() if host else score
 
 
 def alpha_accumulate(S, a_traj, b_traj, match_b, alphas, acc):
@@ -242,6 +246,30 @@ def assign_frames(S, a_traj, b_traj, score):
     return match_b
 
 
+def assign_frames_device(S, a_traj, b_traj, score_dev):
+    """``assign_frames`` without the host: ``match_b`` [n_a] (int32, device) from the device tensor of ``frame_scores``, one
+    problem of ``assignment.linear_sum_assignment_batched`` per frame over the score block as it lies.  Nothing is read back here:
+    the solver's status per frame stays on the device as ``S["assign_status"]`` ([F] int32; an unsolved frame has only -1 in
+    ``match_b``) for ``check_assignment_status``."""
+    from . import assignment
+    dev = score_dev.device
+    with torch.cuda.device(dev):
+        at, bt = _traj(S, a_traj, b_traj, dev)
+        match_b, _, status = assignment.linear_sum_assignment_batched(score_dev, S["_sim_ptr"], S["_a_ptr"], S["_b_ptr"], at >= 0,
+                                                                      (bt >= 0) & (S["b_removed"] == 0), maximize=True)
+        S["assign_status"] = status
+    return match_b
+
+
+def check_assignment_status(launches):
+    """One read for a sequence: raises ``MpnhipError`` if ``assign_frames_device`` left a frame of the launches (dicts of
+    ``frame_similarity``) unsolved -- more than ``assignment.MAX_SIDE`` kept entries on a side, scores that are not finite."""
+    from . import assignment
+    status = [S["assign_status"] for S in launches if S.get("assign_status") is not None]
+    if status:
+        assignment.raise_on_status(torch.cat(status), "hota_eval.assign_frames_device")
+
+
 # ------------------------------------------------------------------------------------------------ sequences
 def _check_frames(frames, num_timesteps, what):
     bad = np.unique(frames[(frames < 0) | (frames >= num_timesteps)])
@@ -250,12 +278,15 @@ def _check_frames(frames, num_timesteps, what):
 
 
 def _evaluate(gt_rows, num_timesteps, class_id, ignore_class, frames_per_launch, device, b_frame, b_traj, b_ids, b_labels,
-              img_shape, details=False, ops=None):
+              img_shape, details=False, ops=None, assignment="host"):
     """The two passes over the launches of a sequence.  The b-side as in ``mots_eval._evaluate``: its frames' entries
     (``b_frame`` ascending, ``b_traj``; -1: an entry that only occupies pixels) and ``b_labels(frames, b_ptr, b_entries, hw)``
     -> the label images of ascending ``frames``.  ``ops``: the operators (this module's and ``mots_eval``'s two; the tests' numpy
-    restatements have no device to run on)."""
+    restatements have no device to run on).  ``assignment``: ``'host'`` (``assign_frames``) or ``'device'``
+    (``ops.assign_frames_device``)."""
     ops = ops or sys.modules[__name__]
+    if assignment not in ("host", "device"):
+        raise ValueError("assignment is 'host' or 'device' (%r)" % (assignment,))
     _check_frames(gt_rows["frame"], num_timesteps, "Ground-truth")
     _check_frames(b_frame, num_timesteps, "Tracking")
     b_traj = np.asarray(b_traj, np.int64)
@@ -291,8 +322,13 @@ def _evaluate(gt_rows, num_timesteps, class_id, ignore_class, frames_per_launch,
         res = hota_from_accumulators(None, None, None, *counts)
     else:
         for S, at, bt in launches:                        # pass 2: the assignments and the counts per alpha
-            match_b = assign_frames(S, at, bt, ops.frame_scores(S, at, bt, acc))
+            if assignment == "device":
+                match_b = ops.assign_frames_device(S, at, bt, ops.frame_scores(S, at, bt, acc, host=False))
+            else:
+                match_b = assign_frames(S, at, bt, ops.frame_scores(S, at, bt, acc))
             ops.alpha_accumulate(S, at, bt, match_b, ALPHAS, acc)
+        if assignment == "device":
+            check_assignment_status([S for S, _, _ in launches])   # (before the sums are read: no silent fallback)
         out = ops.association(acc)
         res = hota_from_accumulators(out["tp"], out["loca"], out["ass"], *counts)
     if details:   # {frame: the prediction ids the preprocessing keeps, ascending}
@@ -302,7 +338,7 @@ def _evaluate(gt_rows, num_timesteps, class_id, ignore_class, frames_per_launch,
 
 
 def evaluate_hota_files(pred_txt, gt_txt, num_timesteps, class_id=CLASS_ID, ignore_class=IGNORE_CLASS, frames_per_launch=8,
-                        device="cuda", details=False, _ops=None):
+                        device="cuda", details=False, _ops=None, assignment="host"):
     """``eval_kitti_mots`` for one sequence and one class: HOTA of the MOTS result file ``pred_txt`` against the ground truth
     ``gt_txt`` (paths, or what ``mots_eval.load_mots_txt`` returns) over the frames ``0 .. num_timesteps - 1``; a row of
     another frame is refused.  Ground-truth rows of ``class_id`` are the objects and those of ``ignore_class`` the frames'
@@ -313,7 +349,10 @@ def evaluate_hota_files(pred_txt, gt_txt, num_timesteps, class_id=CLASS_ID, igno
     ``HOTALocA(0)``, and ``num_gt_dets``, ``num_tracker_dets``, ``num_gt_ids``, ``num_tracker_ids`` after the preprocessing.
     ``frames_per_launch`` frames share a launch (the label workspace is 2 x 4 B x H x W x frames_per_launch; the similarity
     blocks of ALL launches stay on the device until the end, see the module's docstring), and the result does not depend on it.
-    ``details``: also ``kept_tracker_ids`` ({frame: the prediction ids left after the preprocessing})."""
+    ``details``: also ``kept_tracker_ids`` ({frame: the prediction ids left after the preprocessing}).  ``assignment``: where
+    the frames' assignment problems are solved -- ``'host'`` (scipy, the default) or ``'device'`` (``assign_frames_device``: no
+    copy of score cells or matches; a frame with more than ``assignment.MAX_SIDE`` kept entries on a side raises); any other
+    value is a ``ValueError``."""
     gt, pred = _as_loaded(gt_txt), _as_loaded(pred_txt)
     _check_frames(pred["frame"], num_timesteps, "Tracking")
     b = _Side(pred, pred["class_id"] == class_id, (class_id,))
@@ -322,4 +361,4 @@ def evaluate_hota_files(pred_txt, gt_txt, num_timesteps, class_id=CLASS_ID, igno
         _, entries, (re_, rb, ren) = b.launch(frames)
         return (_ops or sys.modules[__name__]).paint_label_runs(re_, rb, ren, b_ptr, entries.size, hw, device)
     return _evaluate(gt, num_timesteps, class_id, ignore_class, frames_per_launch, device, b.frame, b.traj, b.ids, b_labels,
-                     _image_size(b), details, ops=_ops)
+                     _image_size(b), details, ops=_ops, assignment=assignment)

@@ -407,15 +407,15 @@ def evaluate_mots_sequence(node_preds, boxes, frame_num_per_node, ped_ids, label
 
 @capi.on_tensor_device
 def evaluate_hota_sequence(node_preds, boxes, frame_num_per_node, ped_ids, label, keep, img_shape, gt, num_timesteps, mask_threshold=0.5,
-                           frames_per_launch=8, class_id=2, ignore_class=10, details=False):
+                           frames_per_launch=8, class_id=2, ignore_class=10, details=False, assignment="host"):
     """HOTA (``eval_kitti_mots``, utils/evaluation.py:127-135) of a tracked KITTI-MOTS sequence against the ground truth ``gt``
     (a MOTS text file, or what ``mots_eval.load_mots_txt`` returns) over the frames ``0 .. num_timesteps - 1``: what
     ``hota_eval.evaluate_hota_files`` gives for the rows ``save_results_to_file`` writes for the same arguments, without the
     run-length strings and the text file -- the twin of ``evaluate_mots_sequence``, with the prediction's label images straight
     from ``masks.paste_unique_masks`` (every kept detection pastes; only those with ``label == class_id`` are scored).
 
-    The arguments as ``evaluate_mots_sequence``, but ``num_timesteps`` frames instead of its ``seq_length + 1``.  Returns the
-    dict of ``hota_eval.evaluate_hota_files``."""
+    The arguments as ``evaluate_mots_sequence``, but ``num_timesteps`` frames instead of its ``seq_length + 1``; ``assignment``
+    ('host' or 'device') as ``hota_eval.evaluate_hota_files``.  Returns the dict of ``hota_eval.evaluate_hota_files``."""
     from . import hota_eval as HE, masks as M
     capi.require_device(node_preds)
     N = int(node_preds.shape[0])
@@ -437,4 +437,4 @@ def evaluate_hota_sequence(node_preds, boxes, frame_num_per_node, ped_ids, label
     def b_labels(frames, b_ptr, b_entries, hw):
         return M.paste_unique_masks(node_preds, boxes, b_ptr, img_shape, mask_threshold, det_ids=kept[b_entries])
     return HE._evaluate(HE._as_loaded(gt), num_timesteps, class_id, ignore_class, frames_per_launch, node_preds.device, frame_h[kept],
-                        b_traj, traj_ids, b_labels, img_shape, details)
+                        b_traj, traj_ids, b_labels, img_shape, details, assignment=assignment)
