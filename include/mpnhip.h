@@ -665,6 +665,57 @@ int mpnhip_track_lengths(const int64_t* labels, int64_t n_nodes, int64_t min_tra
                          void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The linear program of ExactProjector (projectors.py:92-113, PuLPMinCostFlowSolver :129-160) on the device, as batched linear
+ * assignment.  The LP -- minimise sum x_e (1 - 2 p_e), 0 <= x <= 1, in-flow <= 1 and out-flow <= 1 per node, over the edges of
+ * edges_mask (mpnhip_project_violated_masks) -- is a maximum-weight matching of out-copies against in-copies of the nodes: an
+ * edge with p <= 0.5 costs >= 0 and is 0 in an optimum, the ACTIVE edges (edges_mask set, ids in [0, n_nodes), p > 0.5; NaN is
+ * not active) split into connected components of that bipartite graph, and each component is one dense assignment whose cells
+ * are 1 - 2 p for an edge and 0 for "unmatched".  Where the LP's optimum is unique, so is the assignment's and they agree; among
+ * optima of equal total mpnhip_lsa_batched decides by its own tie rule (below); the total is the LP's either way.
+ *
+ *   mpnhip_project_exact_plan     the problems and their layout
+ *   mpnhip_project_exact_fill     the cost cells
+ *   mpnhip_lsa_batched(cost, cells, cell_ptr, a_ptr, n_a, b_ptr, n_b, n_problems, NULL, NULL, maximize = 0, match_b, ...)
+ *   mpnhip_project_exact_apply    the edge values
+ * The names follow the greedy family (mpnhip_project_*).  The three calls take ONE workspace of
+ * mpnhip_project_exact_workspace_bytes(n_nodes, n_edges) bytes (0 for sizes the calls refuse); the fill leaves one winner flag
+ * per edge at its head, which the apply reads: hand both the same buffer.  edge_index as above ([2, K], row < col, any order;
+ * n_nodes, n_edges < 2^30); an edge with an id outside [0, n_nodes) is skipped and counted (sizes[5]).  Integer and compare-only
+ * arithmetic apart from the float64 cost cells, integer atomics only, sorts and scans by rocprim: the same bits on every call
+ * and for every order of the edge list (duplicate pairs excepted: their tie goes by edge id).
+ * ------------------------------------------------------------------------------------------- */
+size_t mpnhip_project_exact_workspace_bytes(int64_t n_nodes, int64_t n_edges);
+/* The bipartite graph has the vertices u (out-copy) and n_nodes + v (in-copy) of every active edge (u, v); its components come
+ * from the union-find of mpnhip_connected_components over 2 n_nodes vertices.  A PROBLEM is a component with an active edge;
+ * problems are ordered by their smallest vertex, a problem's rows are its out-copies and its columns its in-copies, both by
+ * ascending node id.  Outputs (device):
+ *   a_slot, b_slot [n_nodes] (int32)  position of the node's out-copy in the list of all rows / of its in-copy in the list of
+ *                                     all columns (problem after problem), or -1
+ *   a_ptr, b_ptr (int32), cell_ptr (int64)  prefix lists over the problems, CAPACITY n_nodes + 1 each: entry f for f <=
+ *                                     n_problems, and the totals in every entry behind; problem f owns the rows a_ptr[f] ..
+ *                                     a_ptr[f + 1], the columns b_ptr[f] .. b_ptr[f + 1] and na_f x nb_f cells at cell_ptr[f]
+ *   sizes [6] (int64)                 { n_problems, n_a (rows), n_b (columns), max_side (the longest side of a problem),
+ *                                       cells, skipped_edges }
+ * n_nodes == 0: no problem, one zero in each prefix list. */
+int mpnhip_project_exact_plan(const int64_t* edge_index, int64_t n_edges, int64_t n_nodes, const float* edge_preds,
+                              const unsigned char* edges_mask, int32_t* a_slot, int32_t* b_slot, int32_t* a_ptr, int32_t* b_ptr,
+                              int64_t* cell_ptr, int64_t* sizes, void* workspace, size_t workspace_bytes, void* stream);
+/* cost [cells] (float64; n_problems, n_a, n_b, cells: the plan's sizes): cell (a, b) of problem f, cost[cell_ptr[f] + a * nb_f
+ * + b], is 1.0 - 2.0 * (double)p_e for the active edge between that row and that column and 0.0 for every other pair.  Several
+ * active edges of one pair: the one with the largest score is the cell's WINNER, the lowest edge id among equal scores (the tie
+ * order of mpnhip_project_greedy); the others count as 0.  An edge whose slots or cell do not lie inside the lists (a plan of
+ * other inputs) is left out. */
+int mpnhip_project_exact_fill(const int64_t* edge_index, int64_t n_edges, int64_t n_nodes, const float* edge_preds,
+                              const unsigned char* edges_mask, const int32_t* a_slot, const int32_t* b_slot, const int32_t* a_ptr,
+                              const int32_t* b_ptr, const int64_t* cell_ptr, int64_t n_problems, int64_t n_a, int64_t n_b,
+                              double* cost, int64_t cells, void* workspace, size_t workspace_bytes, void* stream);
+/* out [K] (float32): round_preds[e] for an edge outside edges_mask; for a masked edge 1.0 iff it is active, its cell's winner and
+ * match_b[a_slot[u]] == b_slot[v] (match_b [n_a]: mpnhip_lsa_batched's, entries of the whole lists), else 0.0. */
+int mpnhip_project_exact_apply(const int64_t* edge_index, int64_t n_edges, int64_t n_nodes, const unsigned char* edges_mask,
+                               const float* round_preds, const int32_t* a_slot, const int32_t* b_slot, const int32_t* match_b,
+                               int64_t n_a, float* out, const void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * From RoI masks to MOTS run-length masks: MPNTracker._to_full_masks (tracker/mpn_tracker.py:267-298) =
  * torchvision's paste_masks_in_image(padding = 1), ensure_unique_masks (utils/mots.py:5-25), >= mask_threshold and the run
  * boundaries of COCO's RLE.  One launch covers n_frames frames of one image size (img_h * img_w < 2^31, at most 65535 frames);

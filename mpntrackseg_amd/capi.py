@@ -196,6 +196,10 @@ SIGNATURES = {
     "mpnhip_connected_components_workspace_bytes": (_Z, [_L]),
     "mpnhip_connected_components": (_I, [_P, _L, _L, _P, _P, _P, _P, _Z, _P]),
     "mpnhip_track_lengths": (_I, [_P, _L, _L, _P, _P, _P]),
+    "mpnhip_project_exact_workspace_bytes": (_Z, [_L, _L]),
+    "mpnhip_project_exact_plan": (_I, [_P, _L, _L, _P, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _P]),
+    "mpnhip_project_exact_fill": (_I, [_P, _L, _L, _P, _P, _P, _P, _P, _P, _P, _L, _L, _L, _P, _L, _P, _Z, _P]),
+    "mpnhip_project_exact_apply": (_I, [_P, _L, _L, _P, _P, _P, _P, _P, _L, _P, _P, _Z, _P]),
     "mpnhip_full_masks_workspace_bytes": (_Z, [_L, _L, _L, _L]),
     "mpnhip_paste_unique_masks": (_I, [_P, _L, _I, _I, _P, _P, _L, _P, _L, _I, _I, C.c_float, _P, _P, _P, _Z, _P]),
     "mpnhip_mask_run_events_count": (_I, [_P, _L, _L, _L, _P, _P, _P, _Z, _P]),

@@ -18,14 +18,13 @@
 // component is its smallest node; one launch, no host loop, no flag read.  Then root[v] = find(v), the roots are flagged, an
 // exclusive scan ranks them, and label[v] = rank[root[v]] -- scipy's connected_components(directed=False) labels.
 #include "device_prims.h"
+#include "projection_common.h"
 
 namespace mpnhip {
 namespace {
 
 // counters of mpnhip_project_round_count (int32 [8])
 enum { CNT_VIOL_OUT = 0, CNT_VIOL_IN = 1, CNT_CONSTRAINTS = 2, CNT_BAD_IDS = 3 };
-
-__device__ __forceinline__ bool ids_ok(int64_t r, int64_t c, int64_t N) { return r >= 0 && r < N && c >= 0 && c < N; }
 
 // round_preds = edge_preds > 0.5 (NaN -> 0 as in torch); flow_out[row] / flow_in[col] += 1 per active edge; seen_* mark the nodes
 // that have an outgoing / incoming edge at all (every writer stores the same 1)
@@ -73,10 +72,6 @@ __global__ __launch_bounds__(256) void k_constraint_counts(const int* __restrict
         if (vi) atomicAdd(&counters[CNT_VIOL_IN], vi);
         if (nc) atomicAdd(&counters[CNT_CONSTRAINTS], nc);
     }
-}
-
-__device__ __forceinline__ unsigned long long pack_key(float score, int64_t e) {
-    return ((unsigned long long)__float_as_uint(score) << 32) | (unsigned long long)(~(unsigned)e);
 }
 
 // SIDE 0: the out-constraints (node = row), 1: the in-constraints (node = col).  count[node] is the number of active edges of
@@ -129,44 +124,14 @@ __global__ void k_edges_mask(const int64_t* __restrict__ ei, int64_t K, int64_t 
 }
 
 // ------------------------------------------------------------------------------------------------ connected components
-__global__ void k_cc_init(int* __restrict__ parent, int64_t N) {
-    const int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (v < N) parent[v] = (int)v;
-}
-
-// every value ever stored in parent[x] is an ancestor of x and <= x, so a stale read only lengthens the walk
-__device__ __forceinline__ int cc_find(int* parent, int x) {
-    for (;;) {
-        const int p = __atomic_load_n(&parent[x], __ATOMIC_RELAXED);
-        if (p == x) return x;
-        x = p;
-    }
-}
-
+// (the union-find itself: projection_common.h)
 __global__ void k_cc_union(const int64_t* __restrict__ ei, int64_t K, int64_t N, const float* __restrict__ preds, int* parent) {
     const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= K) return;
     if (preds[e] != 1.f) return;
     const int64_t r = ei[e], c = ei[K + e];
     if (!ids_ok(r, c, N)) return;
-    int a = (int)r, b = (int)c;
-    for (;;) {
-        a = cc_find(parent, a);
-        b = cc_find(parent, b);
-        if (a == b) return;
-        if (a < b) { const int t = a; a = b; b = t; }   // a: the larger root, goes under b
-        const int old = atomicCAS(&parent[a], a, b);
-        if (old == a) return;
-        a = old;   // a was linked meanwhile (to something smaller): go on from there
-    }
-}
-
-__global__ void k_cc_roots(int* parent, int64_t N, int* __restrict__ root, int* __restrict__ is_root) {
-    const int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (v >= N) return;
-    const int r = cc_find(parent, (int)v);
-    root[v] = r;
-    is_root[v] = r == (int)v ? 1 : 0;
+    cc_link(parent, (int)r, (int)c);
 }
 
 __global__ void k_cc_labels(const int* __restrict__ root, const int* __restrict__ is_root, const int* __restrict__ rank, int64_t N,

@@ -8,13 +8,16 @@ outgoing edge.
 ``tracker.evaluate_sequence`` returns), in any edge order; tensors live on the HIP device (there is no CPU fallback).
 
 The greedy rounding runs on the device (``csrc/projection.hip``: two edge-parallel passes instead of the reference's Python
-loop); of the exact one, the flow counts and the violated sub-problem do, and the linear program itself stays on the host."""
+loop); of the exact one, the flow counts and the violated sub-problem do.  Its linear program runs on the host by default
+(``pulp`` or scipy's HiGHS, or a caller's ``solver`` callable) and, with ``solver='device'``, on the device as well: the LP is a
+maximum-weight bipartite matching, which ``csrc/exact_projection.hip`` splits into connected components and hands to the batched
+linear assignment of ``csrc/assignment.hip`` -- no edge list, score or match leaves the device (``exact_round``)."""
 import collections
 
 import numpy as np
 import torch
 
-from . import capi
+from . import assignment, capi
 from .capi import MpnhipError, check, ptr, stream_ptr
 from .graph import compact as _compact, gather_edges as _gather_edges, gather_rows as _gather_rows
 
@@ -86,6 +89,18 @@ def greedy_round(edge_index, edge_preds, num_nodes):
     return rp, _read_counters(counters, N)[3]
 
 
+def _violated_masks(ei, p, num_nodes):
+    """``_round_and_count`` and ``mpnhip_project_violated_masks``: ``(round_preds, counters, nodes_mask, edges_mask)`` on the
+    device (the masks as uint8)."""
+    lib = capi.load()
+    K, N, dev = ei.shape[1], int(num_nodes), p.device
+    rp, flow_out, flow_in, counters = _round_and_count(ei, p, N)
+    nodes_mask, edges_mask = _empty(N, torch.uint8, dev), _empty(K, torch.uint8, dev)
+    check(lib.mpnhip_project_violated_masks(ptr(ei), K, N, ptr(flow_out), ptr(flow_in), ptr(nodes_mask), ptr(edges_mask), stream_ptr()),
+          "mpnhip_project_violated_masks")
+    return rp, counters, nodes_mask, edges_mask
+
+
 Subproblem = collections.namedtuple('Subproblem', ['nodes_mask', 'edges_mask', 'edge_ids', 'edge_index', 'edge_preds', 'round_preds',
                                                    'constr_satisf_rate'])
 
@@ -95,13 +110,9 @@ def violated_subproblem(edge_index, edge_preds, num_nodes):
     """The graph ``ExactProjector.project`` hands to its solver (projectors.py:83-98), as a ``Subproblem``: ``nodes_mask`` [N] =
     ``flow_in > 1 | flow_out > 1``, ``edges_mask`` [K] = an end point in it (both bool), ``edge_ids`` [M] int32 ascending,
     ``edge_index`` [2, M] / ``edge_preds`` [M] of those edges, plus the rounded scores of ALL edges and the rate."""
-    lib = capi.load()
     ei, p = _edge_inputs(edge_index, edge_preds)
     K, N, dev = ei.shape[1], int(num_nodes), p.device
-    rp, flow_out, flow_in, counters = _round_and_count(ei, p, N)
-    nodes_mask, edges_mask = _empty(N, torch.uint8, dev), _empty(K, torch.uint8, dev)
-    check(lib.mpnhip_project_violated_masks(ptr(ei), K, N, ptr(flow_out), ptr(flow_in), ptr(nodes_mask), ptr(edges_mask), stream_ptr()),
-          "mpnhip_project_violated_masks")
+    rp, counters, nodes_mask, edges_mask = _violated_masks(ei, p, N)
     rate = _read_counters(counters, N)[3]
     if K == 0:
         return Subproblem(nodes_mask.bool(), edges_mask.bool(), torch.empty(0, dtype=torch.int32, device=dev), ei, p, rp, rate)
@@ -179,10 +190,107 @@ def snap(values, tol=1e-6):
     return v
 
 
+ExactPlan = collections.namedtuple('ExactPlan', ['a_slot', 'b_slot', 'a_ptr', 'b_ptr', 'cell_ptr', 'n_problems', 'n_a', 'n_b', 'max_side',
+                                                 'cells', 'skipped_edges'])
+
+DEVICE_SOLVER = 'device'
+
+
+def _exact_plan(ei, p, num_nodes, edges_mask):
+    """Launches ``mpnhip_project_exact_plan``; returns the device tensors ``(a_slot, b_slot, a_ptr, b_ptr, cell_ptr, sizes)`` (the
+    prefix lists at their capacity of ``num_nodes + 1``) and the workspace that the fill and the apply go on with."""
+    lib = capi.load()
+    K, N, dev = ei.shape[1], int(num_nodes), p.device
+    a_slot, b_slot = _empty(N, torch.int32, dev), _empty(N, torch.int32, dev)
+    a_ptr, b_ptr = torch.empty(N + 1, dtype=torch.int32, device=dev), torch.empty(N + 1, dtype=torch.int32, device=dev)
+    cell_ptr, sizes = torch.empty(N + 1, dtype=torch.int64, device=dev), torch.empty(6, dtype=torch.int64, device=dev)
+    need = lib.mpnhip_project_exact_workspace_bytes(N, K)
+    if need == 0 and (N or K):
+        raise MpnhipError("%d nodes and %d edges are not supported" % (N, K))
+    ws = capi.workspace(need, dev, "project_exact")   # (a tag of its own: the winner flags at its head outlive the assignment's launch)
+    check(lib.mpnhip_project_exact_plan(ptr(ei), K, N, ptr(p), ptr(edges_mask), ptr(a_slot), ptr(b_slot), ptr(a_ptr), ptr(b_ptr),
+                                        ptr(cell_ptr), ptr(sizes), ptr(ws), ws.numel(), stream_ptr()), "mpnhip_project_exact_plan")
+    return a_slot, b_slot, a_ptr, b_ptr, cell_ptr, sizes, ws
+
+
+def _read_counters_and_sizes(counters, sizes, num_nodes):
+    """ONE host read of the constraint counters and the plan's sizes: ``(constr_satisf_rate, sizes as six ints)``."""
+    both = torch.cat((counters.to(torch.int64), sizes)).tolist()
+    v_out, v_in, n_constr, bad = both[:4]
+    if bad:
+        raise IndexError("index out of range in edge_index: %d edges have an end point outside [0, %d)" % (bad, int(num_nodes)))
+    return (1 - torch.tensor(v_out + v_in).float() / n_constr).item(), both[8:]
+
+
+@capi.on_tensor_device
+def exact_plan(edge_index, edge_preds, num_nodes, edges_mask=None):
+    """The assignment problems the device solver makes of the violated sub-problem (``mpnhip_project_exact_plan``), as an
+    ``ExactPlan``: ``a_slot`` / ``b_slot`` [N] int32 (position of a node's out-copy among all rows / of its in-copy among all
+    columns, or -1), ``a_ptr`` / ``b_ptr`` (int32) / ``cell_ptr`` (int64) [n_problems + 1], all on the device, and the sizes as
+    Python ints.  ``edges_mask`` [K] (bool or uint8): the edges that take part; None: the violated sub-problem's."""
+    ei, p = _edge_inputs(edge_index, edge_preds)
+    _, counters, _, mask = _violated_masks(ei, p, num_nodes)
+    if edges_mask is not None:
+        mask = edges_mask.to(p.device).contiguous().view(-1)
+        mask = mask.view(torch.uint8) if mask.dtype == torch.bool else mask.ne(0).view(torch.uint8)
+        if mask.numel() != ei.shape[1]:
+            raise MpnhipError("one mask flag per edge")
+    a_slot, b_slot, a_ptr, b_ptr, cell_ptr, sizes, _ = _exact_plan(ei, p, num_nodes, mask)
+    _, sz = _read_counters_and_sizes(counters, sizes, num_nodes)
+    F = sz[0]
+    return ExactPlan(a_slot, b_slot, a_ptr[:F + 1], b_ptr[:F + 1], cell_ptr[:F + 1], *sz)
+
+
+def _exact_round_device(ei, p, num_nodes):
+    """``exact_round`` with the LP as batched assignment on the device.  Two host reads of a few integers: the constraint
+    counters with the plan's sizes (the cost buffer's size is among them), and the assignment's status."""
+    lib = capi.load()
+    K, N, dev = ei.shape[1], int(num_nodes), p.device
+    rp, counters, _, edges_mask = _violated_masks(ei, p, N)
+    a_slot, b_slot, a_ptr, b_ptr, cell_ptr, sizes, ws = _exact_plan(ei, p, N, edges_mask)
+    rate, (F, n_a, n_b, max_side, cells, _) = _read_counters_and_sizes(counters, sizes, N)
+    if F == 0:   # nothing violated: the rounded scores
+        return rp, rate
+    refusal = None
+    if max_side > assignment.MAX_SIDE:
+        refusal = "a component of %d rows or columns (at most %d)" % (max_side, assignment.MAX_SIDE)
+    elif lib.mpnhip_lsa_workspace_bytes(n_a, n_b, F) == 0 or cells >= 1 << 31:
+        refusal = "%d components with %d cells (at most 65535 components, fewer than 2^31 cells)" % (F, cells)
+    if refusal:
+        raise MpnhipError("exact_round(solver='device'): the violated sub-problem has %s; use a host solver (solver=None: pulp or "
+                          "scipy, or solver=projectors.solve_with_scipy)" % refusal)
+    cost = torch.empty(cells, dtype=torch.float64, device=dev)
+    check(lib.mpnhip_project_exact_fill(ptr(ei), K, N, ptr(p), ptr(edges_mask), ptr(a_slot), ptr(b_slot), ptr(a_ptr), ptr(b_ptr),
+                                        ptr(cell_ptr), F, n_a, n_b, ptr(cost), cells, ptr(ws), ws.numel(), stream_ptr()),
+          "mpnhip_project_exact_fill")
+    match_b, status = torch.empty(n_a, dtype=torch.int32, device=dev), torch.zeros(F, dtype=torch.int32, device=dev)
+    lsa_ws = capi.workspace(lib.mpnhip_lsa_workspace_bytes(n_a, n_b, F), dev, "lsa")
+    check(lib.mpnhip_lsa_batched(ptr(cost), cells, ptr(cell_ptr), ptr(a_ptr), n_a, ptr(b_ptr), n_b, F, None, None, 0, ptr(match_b), None,
+                                 ptr(status), ptr(lsa_ws), lsa_ws.numel(), stream_ptr()), "mpnhip_lsa_batched")
+    out = _empty(K, torch.float32, dev)
+    check(lib.mpnhip_project_exact_apply(ptr(ei), K, N, ptr(edges_mask), ptr(rp), ptr(a_slot), ptr(b_slot), ptr(match_b), n_a, ptr(out),
+                                         ptr(ws), ws.numel(), stream_ptr()), "mpnhip_project_exact_apply")
+    assignment.raise_on_status(status, "exact_round(solver='device')")
+    return out, rate
+
+
+def check_solver(solver):
+    if isinstance(solver, str) and solver != DEVICE_SOLVER:
+        raise ValueError("solver must be None, a callable or %r (got %r)" % (DEVICE_SOLVER, solver))
+
+
 @capi.on_tensor_device
 def exact_round(edge_index, edge_preds, num_nodes, solver=None):
     """``ExactProjector.project``: edges outside the violated sub-problem take the rounded value, the others the solver's
-    (snapped).  Returns ``(edge_preds [K] float32 on the device, constr_satisf_rate)``."""
+    (snapped).  Returns ``(edge_preds [K] float32 on the device, constr_satisf_rate)``.
+
+    ``solver``: None (``default_solver()`` on the host), a callable (see ``ExactProjector``), or ``'device'``: the LP as batched
+    linear assignment without leaving the device (``csrc/exact_projection.hip`` + ``mpnhip_lsa_batched``).  Where the LP's optimum
+    is unique both give it; among optima of equal objective they may pick different ones.  A component of the violated
+    sub-problem with more than ``assignment.MAX_SIDE`` rows or columns is refused (``MpnhipError``): there is no silent fall-back."""
+    check_solver(solver)
+    if solver == DEVICE_SOLVER:
+        return _exact_round_device(*_edge_inputs(edge_index, edge_preds), num_nodes)
     sub = violated_subproblem(edge_index, edge_preds, num_nodes)
     out = sub.round_preds
     M = sub.edge_ids.numel()
@@ -211,11 +319,13 @@ class GreedyProjector:
 class ExactProjector:
     """Rounds the sub-graph of all nodes involved in a violated constraint with a min-cost-flow linear program
     (https://arxiv.org/pdf/1912.07515.pdf, Appendix B.2; projectors.py:69-113).  ``solver``: a callable ``(edge_index_sub [2, M]
-    numpy, edge_preds_sub [M] numpy) -> values [M]``; None picks ``default_solver()``."""
+    numpy, edge_preds_sub [M] numpy) -> values [M]``; None picks ``default_solver()``; ``'device'`` (or ``solver_backend='device'``)
+    solves on the device (``exact_round``)."""
 
     def __init__(self, full_graph, solver_backend='pulp', solver=None):
         self.final_graph = full_graph.graph_obj
         self.num_nodes = full_graph.graph_obj.num_nodes
+        check_solver(solver)
         self.solver_backend = solver_backend
         self.solver = solver
 
@@ -223,4 +333,5 @@ class ExactProjector:
         if self.solver_backend == 'gurobi':
             raise Exception('Uncomment gurobi code to run gorubi solver')
         g = self.final_graph
-        g.edge_preds, self.constr_satisf_rate = exact_round(g.edge_index, g.edge_preds, self.num_nodes, solver=self.solver)
+        solver = DEVICE_SOLVER if self.solver is None and self.solver_backend == DEVICE_SOLVER else self.solver
+        g.edge_preds, self.constr_satisf_rate = exact_round(g.edge_index, g.edge_preds, self.num_nodes, solver=solver)

@@ -269,7 +269,8 @@ def track_sequence(model, x, edge_index, edge_attr, reid_emb_dists, frame_num_pe
                    reduce_fn=None, x_ext=None, prune_threshold=0.5, rounding_method='greedy', min_track_len=2, solver=None):
     """``evaluate_sequence``, then ``_project_graph_model_output``, ``_assign_ped_ids`` and ``drop_short_trajectories``
     (mpn_tracker.py:212-248, postprocessing.py:14-18).  Arguments as ``evaluate_sequence``, plus ``rounding_method`` ('greedy' or
-    'exact'), ``min_track_len`` and ``solver`` (for 'exact': see ``projectors.ExactProjector``).  Returns a ``TrackResult``:
+    'exact'), ``min_track_len`` and ``solver`` (for 'exact': None, a callable or 'device', see ``projectors.exact_round``).  Returns a
+    ``TrackResult``:
 
     ``ped_ids`` [N] int64            track id of every detection
     ``keep`` [N] bool                False for the detections of tracks shorter than ``min_track_len``
@@ -277,10 +278,14 @@ def track_sequence(model, x, edge_index, edge_attr, reid_emb_dists, frame_num_pe
     ``node_preds``, ``final_edge_preds``        as ``evaluate_sequence`` returns them
     ``constr_satisf_rate``           share of the flow constraints the thresholded scores satisfied before the rounding
 
-    With 'greedy' this adds one host read (the two constraint counters) to ``evaluate_sequence``'s."""
+    With 'greedy' this adds one host read (the two constraint counters) to ``evaluate_sequence``'s; with 'exact' and
+    ``solver='device'`` two (those counters with the sizes of the assignment problems, and the assignment's status), and the
+    pipeline stays on the device from the windows to the track ids."""
     from . import projectors
     if rounding_method not in ('greedy', 'exact'):
         raise RuntimeError("Rounding type for projector not understood")
+    if rounding_method == 'exact':
+        projectors.check_solver(solver)
     seq = evaluate_sequence(model, x, edge_index, edge_attr, reid_emb_dists, frame_num_per_node, frames_per_graph, top_k_nns,
                             reciprocal_k_nns=reciprocal_k_nns, set_pruned_edges_to_inactive=set_pruned_edges_to_inactive,
                             windows_per_launch=windows_per_launch, rank=rank, world_size=world_size, reduce_fn=reduce_fn, x_ext=x_ext,
