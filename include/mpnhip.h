@@ -216,6 +216,47 @@ int mpnhip_debug_linear_splitk(const float* x, int64_t ldx, const float* w, cons
                                int k, int relu, int precision, const float* w2, const float* b2, int n2, int relu2, float* y2,
                                int64_t ldy2, float* scratch, size_t scratch_floats, int32_t taken_and_fused[2], void* stream);
 
+/* Test instrumentation: the weight-gradient products of mpnhip_backward, through the backward's own routing (csrc/gemm_tn.hip:
+ * weight_grad_route, the function every product of the backward goes through).  Each of the n_products (1 .. 16) descriptions is, for
+ * each of one or two groups g (g[1].grad_w == NULL: one group), every batch b < nbatch and every row
+ * r in [*row_begin, *row_end) (read from DEVICE memory; NULL: 0 / rows) intersected with [0, rows):
+ *   z[o] = dZ[b * z_bstride + (dz_idx ? dz_idx[r] : r) * ldz + o]                                                 o < n_out
+ *   h[c] = c < csplit ? H[b * h_bstride + i * ldh + c] : H2[b * h2_bstride + i * ldh2 + c - csplit]    i = h_idx ? h_idx[r] : r
+ *   grad_w[o * ldw + c] += z[o] * h[c]       (c < k_in;  H2 == NULL: csplit = k_in)
+ *   grad_b[o] += z[o]                        (grad_b may be NULL)
+ * dz_idx / h_idx are the same for every batch.  src16 != 0: dZ and H are bf16 rows (leading dimensions and batch strides count bf16
+ * elements; the [1 x k] form keeps an fp32 dZ).  precision: MPNHIP_PREC_FP32 -> the fp32 kernels (launch_gemm_tn);
+ * MPNHIP_PREC_FP32_SPLIT -> the row-panel kernels with three bf16 pieces per operand; MPNHIP_PREC_BF16 -> one piece (both operands of a
+ * product rounded to nearest-even bf16; the bias sum is not rounded).  one_launch != 0: all products are recorded into one batch on
+ * `stream` and flushed once (batched: with the chunk plan of a job that shares its launch); one_launch == 0: batched != 0 -> every
+ * product is a batch of its own with that chunk plan, batched == 0 -> every product is run at once, as the backward's unbatched
+ * products are.  MPNHIP_PREC_FP32 records nothing: there is no batch, every product is launched at once and one_launch, batched and
+ * batch_slab_floats are ignored.  batch_slab_floats > 0 caps the slab region of the batch (a batch that runs out of it is flushed and refilled);
+ * 0: room for all products.  Workspace: mpnhip_debug_weight_grad_batch_workspace_bytes with the same arguments.
+ * chosen (optional, n_products x 2 x 10 ints) reports per product and group what ran:
+ *   [0] path: 0 row-panel kernel, 1 LDS-DMA kernel over bf16 rows (wgrad_rows16.hip), 2 gemm_tn_kernel (MFMA), 3 gemm_tn_narrowk_kernel,
+ *       4 gemm_tn_small_kernel, 5 gemm_tn_generic_kernel, -1 nothing ran
+ *   [1] variant: the block variant after any narrow re-tiling (row-panel: 0 <5,1>, 1 <1,5>, 2 <4,1>, 3 <1,1>, 5 <2,2>, 6 [1 x k], 7 small
+ *       shapes, 8 .. 15 bf16 rows; 16 .. 19 the LDS-DMA kernel's), or the column tile (64 / 128) of gemm_tn_kernel, else 0
+ *   [2] tiles_o  [3] tiles_c  [4] chunk (rows per chunk)  [5] nsplit (chunks per batch)
+ *   [6] narrow: the job ran in the four-blocks-per-CU launch     [7] rolled: the batch was flushed to make room for this product
+ *   [8] xcd_map, [9] red_ny: the fp32 path's XCD-aware block mapping and the partial sums of its two-stage slab sum (1: one stage)
+ * Refused on the host before any launch (MPNHIP_ERR_ARG): null products, n_products outside 1 .. 16, an unknown precision, src16 with
+ * a precision other than bf16, csplit outside (0, k_in) when H2 is given, bad sizes / null operands; a workspace that is too small
+ * (MPNHIP_ERR_WORKSPACE).  A product over bf16 rows that the row-panel kernels do not cover returns MPNHIP_ERR_UNSUPPORTED. */
+typedef struct mpnhip_wgrad_group { float* grad_w; float* grad_b; const int32_t* row_begin; const int32_t* row_end; } mpnhip_wgrad_group;
+typedef struct mpnhip_wgrad_product {
+    const void* dZ; int64_t ldz; int64_t z_bstride; const int32_t* dz_idx;
+    const void* H; int64_t ldh; int64_t h_bstride; const int32_t* h_idx;
+    const void* H2; int64_t ldh2; int64_t h2_bstride;
+    int64_t ldw; int64_t rows; int csplit; int n_out; int k_in; int nbatch; int src16;
+    mpnhip_wgrad_group g[2];
+} mpnhip_wgrad_product;
+size_t mpnhip_debug_weight_grad_batch_workspace_bytes(const mpnhip_wgrad_product* products, int n_products, int precision, int batched,
+                                                      int64_t batch_slab_floats);
+int mpnhip_debug_weight_grad_batch(const mpnhip_wgrad_product* products, int n_products, int precision, int batched, int one_launch,
+                                   int64_t batch_slab_floats, void* workspace, size_t workspace_bytes, int32_t* chosen, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Graph preparation -- replaces the six boolean-mask indexings per step of
  * TimeAwareNodeModel.forward (models/mpn.py:85-87,91-93) and the implicit index structures behind

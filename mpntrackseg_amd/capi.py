@@ -82,6 +82,22 @@ class DebugGemmArgs(C.Structure):
     ]
 
 
+class WgradGroup(C.Structure):
+    """``mpnhip_wgrad_group`` (include/mpnhip.h)."""
+    _fields_ = [(n, C.c_void_p) for n in ("grad_w", "grad_b", "row_begin", "row_end")]
+
+
+class WgradProduct(C.Structure):
+    """``mpnhip_wgrad_product`` (include/mpnhip.h): one product of ``mpnhip_debug_weight_grad_batch``."""
+    _fields_ = [
+        ("dZ", C.c_void_p), ("ldz", C.c_int64), ("z_bstride", C.c_int64), ("dz_idx", C.c_void_p),
+        ("H", C.c_void_p), ("ldh", C.c_int64), ("h_bstride", C.c_int64), ("h_idx", C.c_void_p),
+        ("H2", C.c_void_p), ("ldh2", C.c_int64), ("h2_bstride", C.c_int64),
+        ("ldw", C.c_int64), ("rows", C.c_int64), ("csplit", C.c_int), ("n_out", C.c_int), ("k_in", C.c_int), ("nbatch", C.c_int),
+        ("src16", C.c_int), ("g", WgradGroup * 2),
+    ]
+
+
 CONV_MAX_SEGMENTS = 4
 
 
@@ -111,6 +127,8 @@ SIGNATURES = {
     "mpnhip_debug_linear_splitk_scratch_floats": (_Z, [_L, _I, _I]),
     "mpnhip_debug_linear_splitk": (_I, [_P, _L, _P, _P, _P, _L, _L, _I, _I, _I, _I, _P, _P, _I, _I, _P, _L, _P, _Z, C.POINTER(C.c_int32),
                                         _P]),
+    "mpnhip_debug_weight_grad_batch_workspace_bytes": (_Z, [C.POINTER(WgradProduct), _I, _I, _I, _L]),
+    "mpnhip_debug_weight_grad_batch": (_I, [C.POINTER(WgradProduct), _I, _I, _I, _I, _L, _P, _Z, C.POINTER(C.c_int32), _P]),
     "mpnhip_graph_bytes": (_Z, [_I, _L]),
     "mpnhip_graph_prep_workspace_bytes": (_Z, [_I, _L]),
     "mpnhip_graph_prep": (_I, [_P, _I, _L, _P, _Z, _P, _Z, _P]),
@@ -273,6 +291,39 @@ def saved_activation(model, graph, fwd_ws, what, step=0, layer=0):
         check(lib.mpnhip_debug_saved(m, ptr(graph.buf), graph.N, graph.E, ptr(fwd_ws), fwd_ws.numel(), SAVED[what], int(step), int(layer),
                                      ptr(out), C.byref(rows), C.byref(width), stream_ptr()), "mpnhip_debug_saved")
     return out
+
+
+WG_PATHS = {-1: None, 0: "panel", 1: "rows16", 2: "tn_mfma", 3: "tn_narrowk", 4: "tn_small", 5: "tn_generic"}
+WG_CHOSEN_FIELDS = ("path", "variant", "tiles_o", "tiles_c", "chunk", "nsplit", "narrow", "rolled", "xcd_map", "red_ny")
+
+
+def debug_weight_grad_batch(products, precision, batched=False, one_launch=False, batch_slab_floats=0, fill=None):
+    """The backward's weight-gradient routing over a list of ``WgradProduct`` (``mpnhip_debug_weight_grad_batch``); test
+    instrumentation.  ``fill``: byte pattern the workspace is prefilled with.  Returns ``(rc, chosen)``: the status code (not
+    raised: refusals are part of what the tests check) and per product a list of two dicts (``WG_CHOSEN_FIELDS``, ``path`` as a
+    name of ``WG_PATHS``)."""
+    lib = load()
+    n = len(products)
+    arr = (WgradProduct * n)(*products)
+    prec = PRECISIONS[precision]
+    need = lib.mpnhip_debug_weight_grad_batch_workspace_bytes(arr, n, prec, int(batched), int(batch_slab_floats))
+    ws = torch.empty(max(int(need), 256), dtype=torch.uint8, device="cuda")
+    if fill is not None:
+        ws.fill_(fill)
+    out = (C.c_int32 * (n * 2 * len(WG_CHOSEN_FIELDS)))()
+    rc = lib.mpnhip_debug_weight_grad_batch(arr, n, prec, int(batched), int(one_launch), int(batch_slab_floats), ptr(ws), ws.numel(), out,
+                                            stream_ptr())
+    torch.cuda.synchronize()
+    nf = len(WG_CHOSEN_FIELDS)
+    chosen = []
+    for i in range(n):
+        pair = []
+        for q in range(2):
+            d = dict(zip(WG_CHOSEN_FIELDS, out[(i * 2 + q) * nf:(i * 2 + q + 1) * nf]))
+            d["path"] = WG_PATHS[d["path"]]
+            pair.append(d)
+        chosen.append(pair)
+    return rc, chosen
 
 
 BWD_SAVED = {"dz_node": 0, "dp": 1, "dz_flow": 2, "dz_edge": 3, "dz_cls": 4}

@@ -477,33 +477,7 @@ static size_t plan_backward(const mpnhip_model& m, const Dims& d, int64_t N, int
 }
 
 // ------------------------------------------------------------------------------------ helpers
-struct RowRange {
-    const int* begin;
-    const int* end;
-};
-
-struct Operand {        // one side of a (batched) weight-gradient product
-    const float* p;
-    int64_t ld;
-    int64_t bstride;    // floats between consecutive batches (0: same block every batch)
-};
-
-// one weight-gradient product  dW += dZ^T [H | H2] (+ bias)  for one or two direction groups, over nbatch row blocks: the shared part,
-// then grad_w / grad_b / the device-side row range of each group (g[1].grad_w == nullptr: one group)
-struct WgGroup { float* grad_w; float* grad_b; RowRange rr; };
-struct WgProduct {
-    Operand dZ;
-    const int* dz_idx;  // optional row gather
-    Operand H, H2;      // H2: the columns >= csplit of the layer input (H2.p == nullptr: none, csplit unused)
-    int csplit;
-    const int* h_idx;   // optional row gather
-    int n_out, k_in;
-    int64_t ldw, rows;
-    int nbatch;
-    bool src16;         // the operands are bf16 rows (WpProduct::src16): the dZ blocks / saved activations of the fused bf16 chain
-    WgGroup g[2];
-};
-
+// (RowRange, Operand, WgProduct: common.h)
 // ... two weight blocks that are KEPT transposed for the whole backward: the node update's and the per-node projections' weights are the
 // operands of an activation-gradient product in every step (22 transpositions of the same two blocks per cfg-E step before round 4,
 // 25 - 30 us each)
@@ -523,66 +497,7 @@ struct BwdCtx {
 // batch: where the product is recorded (all products of a group of steps: one product launch + one slab-sum launch); nullptr: run now,
 // as a batch of its own on slab_base
 static int weight_grad(const BwdCtx& c, float* slab_base, WpBatch* batch, const WgProduct& w, hipStream_t s) {
-    const int ngroups = w.g[1].grad_w ? 2 : 1;
-    if (c.wgrad_split && w.rows > 0) {
-        // MPNHIP_PREC_FP32_SPLIT: the row-panel kernel (wgrad_panel.hip)
-        WpProduct wp[2];
-        for (int q = 0; q < ngroups; ++q)
-            wp[q] = {w.dZ.p, w.dZ.ld, w.dZ.bstride, w.H.p, w.H.ld, w.H.bstride, w.g[q].rr.begin, w.g[q].rr.end, w.rows, w.nbatch,
-                     w.n_out, w.k_in, w.g[q].grad_w, w.ldw, w.g[q].grad_b, w.dz_idx, w.h_idx, w.H2.p, w.H2.ld, w.H2.bstride, w.csplit,
-                     c.bf16 ? 1 : 3, w.src16 ? 1 : 0};
-        if (batch) {
-            if (wp_batch_add(batch, wp, ngroups)) return MPNHIP_OK;
-            bool eligible = true;
-            for (int q = 0; q < ngroups; ++q) eligible = eligible && wp_eligible(wp[q]);
-            if (eligible) {
-                // the batch is full (more than WP_MAX_JOBS jobs in a group of steps: deeper MLPs; or its slab region): run it
-                // and go on in a fresh one rather than switch kernels in the middle of a group
-                int st = MPNHIP_OK;
-                if (wp_batch_roll(batch, &st) && wp_batch_add(batch, wp, ngroups)) return MPNHIP_OK;
-                MPN_TRY(st);
-            }
-        } else {
-            WpBatch own;
-            wp_batch_init(&own, slab_base, 2 * c.p->slab_floats_per_group, false, nullptr);
-            if (wp_batch_add(&own, wp, ngroups)) return wp_batch_flush(&own, s);
-        }
-        // not a shape / alignment of the row-panel kernel (or the batch cannot be rolled): the fp32 kernel below, counted
-        count_path(PC_TN_PANEL_FALLBACK);
-        if (w.src16) { set_error("backward (bf16): a product over bf16 rows [%d x %d] is not covered by the row-panel kernel", w.n_out, w.k_in); return MPNHIP_ERR_UNSUPPORTED; }
-    }
-    const bool ranged = w.g[0].rr.begin || w.g[0].rr.end;
-    TnArgs a = {};
-    a.ngroups = ngroups;
-    a.n_out = w.n_out;
-    a.k_in = w.k_in;
-    a.csplit = w.H2.p ? w.csplit : w.k_in;
-    a.m_upper = w.rows;
-    a.nbatch = w.nbatch;
-    // (with device-side row ranges the groups partition the `rows` rows between them; without, each group covers all of them)
-    a.flops = 2.0 * (double)w.rows * (ranged ? 1 : ngroups) * w.nbatch * w.n_out * w.k_in;
-    for (int q = 0; q < ngroups; ++q) {
-        TnGroup& g = a.g[q];
-        g.dZ = w.dZ.p;
-        g.ldz = w.dZ.ld;
-        g.z_bstride = w.dZ.bstride;
-        g.dz_idx = w.dz_idx;
-        g.H = w.H.p;
-        g.ldh = w.H.ld;
-        g.h_bstride = w.H.bstride;
-        g.H2 = w.H2.p;
-        g.ldh2 = w.H2.ld;
-        g.h2_bstride = w.H2.bstride;
-        g.h_idx = w.h_idx;
-        g.row_begin = w.g[q].rr.begin;
-        g.row_end = w.g[q].rr.end;
-        g.m_static = w.rows;
-        g.slab = slab_base + q * c.p->slab_floats_per_group;
-        g.grad_w = w.g[q].grad_w;
-        g.ldw = w.ldw;
-        g.grad_b = w.g[q].grad_b;
-    }
-    return launch_gemm_tn(a, s);
+    return weight_grad_route({c.wgrad_split, c.bf16, c.p->slab_floats_per_group}, slab_base, batch, w, s);
 }
 
 // C = mask( A B (+ C) ) with B given as weight rows: B[k][n] = W[k * ldw + n]  (dH = dZ W)

@@ -145,11 +145,20 @@ struct TnArgs {
     int xcd_map;           // 1: XCD-aware block -> (tile, chunk) mapping
     int tiles, ny8;        // filled by launch_gemm_tn: output tiles, row chunks x batches padded to a multiple of 8 (XCD mapping)
 };
+// What the weight-gradient routing ran for one direction group of one product (test instrumentation,
+// mpnhip_debug_weight_grad_batch; every other caller leaves the pointer null).  path: WG_PATH_*; variant: the row-panel / rows16 block
+// variant after any narrow re-tiling (wgrad_panel.hip kVariants), or the column tile width (64 / 128) of gemm_tn_kernel, else 0;
+// narrow: the product ran in the four-blocks-per-CU launch; rolled: its batch was flushed to make room for it; xcd_map / red_ny: the fp32
+// path's block mapping and the partial sums of its two-stage slab sum (1: one stage)
+enum { WG_PATH_NONE = -1, WG_PATH_PANEL = 0, WG_PATH_ROWS16 = 1, WG_PATH_TN_MFMA = 2, WG_PATH_TN_NARROWK = 3, WG_PATH_TN_SMALL = 4,
+       WG_PATH_TN_GENERIC = 5 };
+struct WgChosen { int path, variant, tiles_o, tiles_c, chunk, nsplit, narrow, rolled, xcd_map, red_ny; };
 void tn_plan(TnArgs& a);
 // pitch of a slab image's rows: k_in weight columns + the bias column, padded to whole 16-byte columns
 __host__ __device__ static inline int tn_kpad(int k_in) { return (k_in + 4) & ~3; }
 size_t tn_slab_floats(int n_out, int k_in, int64_t m_upper, int nbatch);
-int launch_gemm_tn(const TnArgs& args, hipStream_t stream);
+// chosen (optional): one entry per group, filled when a kernel is launched
+int launch_gemm_tn(const TnArgs& args, hipStream_t stream, WgChosen* chosen = nullptr);
 
 // ---- three-piece operand form, row-panel blocks, all products of a group of steps in one launch (wgrad_panel.hip) ----
 struct WpJob {             // one product (one direction group of it), as the kernels see it
@@ -192,7 +201,8 @@ struct WpProduct {         // host-side description of one product
 };
 // (nblocks2 / bytes2: the jobs of wgrad_rows16.hip's kernel -- variant >= 16, their block0 counts inside that launch)
 struct WpBatch { WpTable tab; float* slab; size_t slab_floats, used; double flops, bytes, bytes2; int nblocks, nblocks2, nred; bool batched;
-                 hipStream_t stream; bool has_stream; };   // has_stream: every flush of this batch goes to `stream` (wp_batch_roll)
+                 hipStream_t stream; bool has_stream;      // has_stream: every flush of this batch goes to `stream` (wp_batch_roll)
+                 WgChosen* chosen[WP_MAX_JOBS]; };         // per job, or null: filled by the flush (the tiling is final only there)
 bool wp_eligible(const WpProduct& p);
 // wgrad_rows16.hip: the one-pass LDS-DMA kernel for bf16 rows at the 256-d widths
 int r16_variant(int n_out, int k_in, int* tiles_o, int* tiles_c);
@@ -206,8 +216,41 @@ void wp_batch_init(WpBatch* b, float* slab, size_t slab_floats, bool batched, co
 // one stream are serial, so the slab region is reused; false: not possible (no stream given at init / nothing recorded)
 bool wp_batch_roll(WpBatch* b, int* status);
 // true: recorded -- all n (the direction groups of one product) or none: every product eligible, table and slab space suffice
-bool wp_batch_add(WpBatch* b, const WpProduct* ps, int n);
+// chosen (optional): n entries, written when the batch is flushed -- they must live until then
+bool wp_batch_add(WpBatch* b, const WpProduct* ps, int n, WgChosen* chosen = nullptr);
 int wp_batch_flush(WpBatch* b, hipStream_t stream);   // product launch + slab-sum launch of what was recorded
+
+// ---- one weight-gradient product as the backward describes it, and the routing every such product goes through (gemm_tn.hip) ----
+struct RowRange {
+    const int* begin;
+    const int* end;
+};
+struct Operand {        // one side of a (batched) weight-gradient product
+    const float* p;
+    int64_t ld;
+    int64_t bstride;    // floats between consecutive batches (0: same block every batch)
+};
+// dW += dZ^T [H | H2] (+ bias)  for one or two direction groups, over nbatch row blocks: the shared part, then grad_w / grad_b / the
+// device-side row range of each group (g[1].grad_w == nullptr: one group)
+struct WgGroup { float* grad_w; float* grad_b; RowRange rr; };
+struct WgProduct {
+    Operand dZ;
+    const int* dz_idx;  // optional row gather
+    Operand H, H2;      // H2: the columns >= csplit of the layer input (H2.p == nullptr: none, csplit unused)
+    int csplit;
+    const int* h_idx;   // optional row gather
+    int n_out, k_in;
+    int64_t ldw, rows;
+    int nbatch;
+    bool src16;         // the operands are bf16 rows (WpProduct::src16): the dZ blocks / saved activations of the fused bf16 chain
+    WgGroup g[2];
+};
+// what the routing needs to know of its caller: wgrad_split -- the row-panel kernels (three-piece operands, or one piece with bf16);
+// slab_floats_per_group: a group's share of slab_base (which holds two), for a product that runs on its own
+struct WgRouting { bool wgrad_split, bf16; size_t slab_floats_per_group; };
+// batch: where the product is recorded (all products of a group of steps: one product launch + one slab-sum launch); nullptr: run now,
+// as a batch of its own on slab_base.  chosen (optional): two entries; those of a recorded product are written when its batch is flushed
+int weight_grad_route(const WgRouting& r, float* slab_base, WpBatch* batch, const WgProduct& w, hipStream_t s, WgChosen* chosen = nullptr);
 
 // few rows, long K (node encoder at the reference's graph sizes): split-K into `scratch`, then a fixed-order sum (gemm.hip)
 // `next` (optional): the Linear layer that follows ([next->n x n] weights, output next->y): evaluated in the summing launch when it is

@@ -11,6 +11,7 @@
 // H may come as two column segments (the reference's torch.cat([initial, current]) input), rows of
 // either operand may be gathered through an index (edge_attr / dlogits live in original edge order).
 #include <cstdlib>
+#include <cstring>
 
 #include "common.h"
 
@@ -497,7 +498,7 @@ void tn_plan(TnArgs& a) {
     if (a.nsplit < 1) a.nsplit = 1;
 }
 
-int launch_gemm_tn(const TnArgs& a_in, hipStream_t s) {
+int launch_gemm_tn(const TnArgs& a_in, hipStream_t s, WgChosen* chosen) {
     TnArgs a = a_in;
     MPN_CHECK_ARG(a.ngroups == 1 || a.ngroups == 2, "gemm_tn: ngroups");
     MPN_CHECK_ARG(a.n_out >= 1 && a.k_in >= 1 && a.csplit >= 0 && a.csplit <= a.k_in, "gemm_tn: dims");
@@ -514,14 +515,17 @@ int launch_gemm_tn(const TnArgs& a_in, hipStream_t s) {
     tn_plan(a);
     const bool small = a.n_out <= 32 && a.k_in <= 32 && a.csplit == a.k_in;
     count_path(fast ? PC_TN_MFMA : (small ? PC_TN_SMALL : PC_TN_GENERIC));
+    WgChosen ch = {WG_PATH_TN_GENERIC, 0, 1, 1, a.chunk, a.nsplit, 0, 0, 0, 1};
     if (fast) {
         const int tbn = a.k_in <= 64 ? 64 : 128;
         a.tiles = ((a.n_out + TBM - 1) / TBM) * ((a.k_in + tbn - 1) / tbn);
+        ch.path = WG_PATH_TN_MFMA; ch.variant = tbn; ch.tiles_o = (a.n_out + TBM - 1) / TBM; ch.tiles_c = (a.k_in + tbn - 1) / tbn;
         a.ny8 = (a.nsplit * a.nbatch + 7) / 8 * 8;   // (row chunks x batches, padded to the 8 XCDs: see the kernel's block mapping)
         // measured on MI355X (tools/wgrad_bench.py, cfg-B shapes, 5 steps per product): the XCD-aware mapping pays where a handful
         // of output tiles share every H row (edge layer 1, 5 tiles: 282 -> 259 us) and costs a little elsewhere (3 tiles: 156 ->
         // 176 us; 128 tiles: 140 -> 173 us -- there the chunks' tiles no longer start together)
         a.xcd_map = a.tiles >= 4 && a.tiles <= 8 ? 1 : 0;
+        ch.xcd_map = a.xcd_map;
         const unsigned nblocks = (unsigned)(a.tiles * a.ny8 * a.ngroups);
         prof_begin(PROF_TN, s, a.flops);
         if (tbn == 64)
@@ -530,8 +534,10 @@ int launch_gemm_tn(const TnArgs& a_in, hipStream_t s) {
             MPN_LAUNCH_PROFILED(gemm_tn_kernel<128>, dim3(nblocks), dim3(TNT), s, a);
         prof_end(PROF_TN, s);
     } else if (tn_narrowk(a.n_out, a.k_in) && a.csplit == a.k_in) {
+        ch.path = WG_PATH_TN_NARROWK;
         hipLaunchKernelGGL(gemm_tn_narrowk_kernel, dim3(1, a.nsplit * a.nbatch, a.ngroups), dim3(256), 0, s, a);
     } else if (small) {
+        ch.path = WG_PATH_TN_SMALL;
         hipLaunchKernelGGL(gemm_tn_small_kernel, dim3(1, a.nsplit * a.nbatch, a.ngroups), dim3(256), 0, s, a);
     } else {
         const int64_t nout_total = (int64_t)a.n_out * (a.k_in + 1);
@@ -552,6 +558,7 @@ int launch_gemm_tn(const TnArgs& a_in, hipStream_t s) {
             ny = ny > 32 ? 32 : ny;
             ny = ny > nslab_upper / 8 ? nslab_upper / 8 : ny;
             if (ny >= 2) {
+                ch.red_ny = ny;
                 a.red_ny = ny;
                 a.red_stage = 1;
                 hipLaunchKernelGGL(slab_reduce_kernel, dim3(bx, ny, a.ngroups), dim3(256), 0, s, a);
@@ -565,7 +572,78 @@ int launch_gemm_tn(const TnArgs& a_in, hipStream_t s) {
         hipLaunchKernelGGL(slab_reduce_scalar_kernel, dim3((unsigned)((total + 255) / 256), 1, a.ngroups), dim3(256), 0, s, a);
     }
     MPN_LAUNCH_CHECK();
+    if (chosen)
+        for (int i = 0; i < a.ngroups; ++i) chosen[i] = ch;
     return MPNHIP_OK;
+}
+
+int weight_grad_route(const WgRouting& c, float* slab_base, WpBatch* batch, const WgProduct& w, hipStream_t s, WgChosen* chosen) {
+    const int ngroups = w.g[1].grad_w ? 2 : 1;
+    if (chosen)
+        for (int q = 0; q < 2; ++q) chosen[q] = {WG_PATH_NONE, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    if (c.wgrad_split && w.rows > 0) {
+        // MPNHIP_PREC_FP32_SPLIT: the row-panel kernel (wgrad_panel.hip)
+        WpProduct wp[2];
+        for (int q = 0; q < ngroups; ++q)
+            wp[q] = {w.dZ.p, w.dZ.ld, w.dZ.bstride, w.H.p, w.H.ld, w.H.bstride, w.g[q].rr.begin, w.g[q].rr.end, w.rows, w.nbatch,
+                     w.n_out, w.k_in, w.g[q].grad_w, w.ldw, w.g[q].grad_b, w.dz_idx, w.h_idx, w.H2.p, w.H2.ld, w.H2.bstride, w.csplit,
+                     c.bf16 ? 1 : 3, w.src16 ? 1 : 0};
+        if (batch) {
+            if (wp_batch_add(batch, wp, ngroups, chosen)) return MPNHIP_OK;
+            bool eligible = true;
+            for (int q = 0; q < ngroups; ++q) eligible = eligible && wp_eligible(wp[q]);
+            if (eligible) {
+                // the batch is full (more than WP_MAX_JOBS jobs in a group of steps: deeper MLPs; or its slab region): run it
+                // and go on in a fresh one rather than switch kernels in the middle of a group
+                int st = MPNHIP_OK;
+                if (wp_batch_roll(batch, &st) && wp_batch_add(batch, wp, ngroups, chosen)) {
+                    if (chosen)
+                        for (int q = 0; q < ngroups; ++q) chosen[q].rolled = 1;
+                    return MPNHIP_OK;
+                }
+                MPN_TRY(st);
+            }
+        } else {
+            WpBatch own;
+            wp_batch_init(&own, slab_base, 2 * c.slab_floats_per_group, false, nullptr);
+            if (wp_batch_add(&own, wp, ngroups, chosen)) return wp_batch_flush(&own, s);
+        }
+        // not a shape / alignment of the row-panel kernel (or the batch cannot be rolled): the fp32 kernel below, counted
+        count_path(PC_TN_PANEL_FALLBACK);
+        if (w.src16) { set_error("backward (bf16): a product over bf16 rows [%d x %d] is not covered by the row-panel kernel", w.n_out, w.k_in); return MPNHIP_ERR_UNSUPPORTED; }
+    }
+    const bool ranged = w.g[0].rr.begin || w.g[0].rr.end;
+    TnArgs a = {};
+    a.ngroups = ngroups;
+    a.n_out = w.n_out;
+    a.k_in = w.k_in;
+    a.csplit = w.H2.p ? w.csplit : w.k_in;
+    a.m_upper = w.rows;
+    a.nbatch = w.nbatch;
+    // (with device-side row ranges the groups partition the `rows` rows between them; without, each group covers all of them)
+    a.flops = 2.0 * (double)w.rows * (ranged ? 1 : ngroups) * w.nbatch * w.n_out * w.k_in;
+    for (int q = 0; q < ngroups; ++q) {
+        TnGroup& g = a.g[q];
+        g.dZ = w.dZ.p;
+        g.ldz = w.dZ.ld;
+        g.z_bstride = w.dZ.bstride;
+        g.dz_idx = w.dz_idx;
+        g.H = w.H.p;
+        g.ldh = w.H.ld;
+        g.h_bstride = w.H.bstride;
+        g.H2 = w.H2.p;
+        g.ldh2 = w.H2.ld;
+        g.h2_bstride = w.H2.bstride;
+        g.h_idx = w.h_idx;
+        g.row_begin = w.g[q].rr.begin;
+        g.row_end = w.g[q].rr.end;
+        g.m_static = w.rows;
+        g.slab = slab_base + q * c.slab_floats_per_group;
+        g.grad_w = w.g[q].grad_w;
+        g.ldw = w.ldw;
+        g.grad_b = w.g[q].grad_b;
+    }
+    return launch_gemm_tn(a, s, chosen);
 }
 
 }  // namespace mpnhip
@@ -683,4 +761,94 @@ extern "C" int mpnhip_time_weight_grad(const float* dZ, const float* H, int64_t 
                                        float* grad_b, void* workspace, size_t workspace_bytes, int iters, float* avg_us, void* stream_) {
     return mpnhip_time_weight_grad_prec(dZ, H, rows, n_out, k_in, nbatch, MPNHIP_PREC_FP32, grad_w, grad_b, workspace, workspace_bytes, iters,
                                         avg_us, stream_);
+}
+
+// ---- test instrumentation: the backward's weight-gradient routing (weight_grad_route) behind the C ABI ---------------------------
+// Workspace: [ two groups' slabs for a product that runs on its own (and the fp32 kernels) | the slab region of the batch ]
+namespace {
+struct WgDebugLayout { float* own; size_t per_group; float* batch; size_t batch_floats; };
+bool wg_ranged(const mpnhip_wgrad_product& p) { return p.g[0].row_begin || p.g[0].row_end; }
+size_t wg_debug_layout(const mpnhip_wgrad_product* ps, int n, int precision, int batched, int64_t batch_slab_floats, void* workspace,
+                       WgDebugLayout* out) {
+    size_t per_group = 0, sum = 0;
+    for (int i = 0; i < n; ++i) {
+        const mpnhip_wgrad_product& p = ps[i];
+        if (p.rows <= 0 || p.n_out < 1 || p.k_in < 1 || p.nbatch < 1) continue;
+        const size_t tn = p.src16 ? 0 : tn_slab_floats(p.n_out, p.k_in, p.rows, p.nbatch);
+        const size_t own = wp_slab_floats(p.n_out, p.k_in, p.rows, p.nbatch, wg_ranged(p), false, p.src16 != 0);
+        per_group = std::max(per_group, std::max(tn, own));
+        sum += (p.g[1].grad_w ? 2 : 1) * wp_slab_floats(p.n_out, p.k_in, p.rows, p.nbatch, wg_ranged(p), batched != 0, p.src16 != 0);
+    }
+    per_group = (per_group + 63) / 64 * 64;
+    const uintptr_t w = reinterpret_cast<uintptr_t>(workspace);
+    Carver c(workspace ? static_cast<char*>(workspace) + (align_up(w, 256) - w) : nullptr);
+    out->per_group = per_group;
+    out->own = c.take<float>(2 * per_group);
+    out->batch_floats = precision == MPNHIP_PREC_FP32 ? 0 : (batch_slab_floats > 0 ? (size_t)batch_slab_floats : sum);
+    out->batch = c.take<float>(out->batch_floats);
+    return c.bytes() + 256;
+}
+int wg_debug_check(const mpnhip_wgrad_product* ps, int n, int precision) {
+    MPN_CHECK_ARG(ps, "debug_weight_grad_batch: null products");
+    MPN_CHECK_ARG(n >= 1 && n <= WP_MAX_JOBS, "debug_weight_grad_batch: %d products (1 .. %d)", n, WP_MAX_JOBS);
+    MPN_CHECK_ARG(precision == MPNHIP_PREC_FP32 || precision == MPNHIP_PREC_FP32_SPLIT || precision == MPNHIP_PREC_BF16,
+                  "debug_weight_grad_batch: unknown precision %d", precision);
+    for (int i = 0; i < n; ++i) {
+        const mpnhip_wgrad_product& p = ps[i];
+        MPN_CHECK_ARG(p.n_out >= 1 && p.k_in >= 1 && p.rows >= 0 && p.nbatch >= 1 && p.ldw >= p.k_in, "debug_weight_grad_batch: product %d: bad sizes", i);
+        MPN_CHECK_ARG(p.rows == 0 || (p.dZ && p.H && p.g[0].grad_w), "debug_weight_grad_batch: product %d: null dZ / H / grad_w", i);
+        MPN_CHECK_ARG(!p.src16 || precision == MPNHIP_PREC_BF16, "debug_weight_grad_batch: product %d: src16 needs the bf16 precision", i);
+        MPN_CHECK_ARG(!p.H2 || (p.csplit > 0 && p.csplit < p.k_in), "debug_weight_grad_batch: product %d: csplit %d outside (0, %d)", i, p.csplit,
+                      p.k_in);
+    }
+    return MPNHIP_OK;
+}
+}  // namespace
+
+extern "C" size_t mpnhip_debug_weight_grad_batch_workspace_bytes(const mpnhip_wgrad_product* products, int n_products, int precision,
+                                                                 int batched, int64_t batch_slab_floats) {
+    if (wg_debug_check(products, n_products, precision) != MPNHIP_OK) return 0;
+    WgDebugLayout L;
+    return wg_debug_layout(products, n_products, precision, batched, batch_slab_floats, nullptr, &L);
+}
+
+extern "C" int mpnhip_debug_weight_grad_batch(const mpnhip_wgrad_product* products, int n_products, int precision, int batched, int one_launch,
+                                              int64_t batch_slab_floats, void* workspace, size_t workspace_bytes, int32_t* chosen,
+                                              void* stream_) {
+    MPN_TRY(wg_debug_check(products, n_products, precision));
+    WgDebugLayout L;
+    const size_t need = wg_debug_layout(products, n_products, precision, batched, batch_slab_floats, workspace, &L);
+    MPN_CHECK_WORKSPACE("debug_weight_grad_batch", workspace, workspace_bytes, need);
+    hipStream_t s = static_cast<hipStream_t>(stream_);
+    const WgRouting r = {precision != MPNHIP_PREC_FP32, precision == MPNHIP_PREC_BF16, L.per_group};
+    static_assert(sizeof(WgChosen) == 10 * sizeof(int32_t), "the chosen report is ten ints per group");
+    WgChosen ch[WP_MAX_JOBS][2];
+    for (int i = 0; i < n_products; ++i)
+        for (int q = 0; q < 2; ++q) ch[i][q] = {WG_PATH_NONE, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    // one_launch: one batch for all products; else batched: a batch per product (a job with the batched chunk plan, alone in its
+    // launch); else: no batch -- the routing runs the product now, on a batch of its own
+    WpBatch wpb;
+    const bool use_batch = r.wgrad_split && (one_launch || batched);
+    if (use_batch) wp_batch_init(&wpb, L.batch, L.batch_floats, batched != 0, &s);
+    int rc = MPNHIP_OK;
+    for (int i = 0; i < n_products && rc == MPNHIP_OK; ++i) {
+        const mpnhip_wgrad_product& p = products[i];
+        WgProduct w = {};
+        w.dZ = {static_cast<const float*>(p.dZ), p.ldz, p.z_bstride};
+        w.dz_idx = p.dz_idx;
+        w.H = {static_cast<const float*>(p.H), p.ldh, p.h_bstride};
+        w.H2 = {static_cast<const float*>(p.H2), p.ldh2, p.h2_bstride};
+        w.csplit = p.csplit;
+        w.h_idx = p.h_idx;
+        w.n_out = p.n_out; w.k_in = p.k_in; w.ldw = p.ldw; w.rows = p.rows; w.nbatch = p.nbatch; w.src16 = p.src16 != 0;
+        for (int q = 0; q < 2; ++q) w.g[q] = {p.g[q].grad_w, p.g[q].grad_b, {p.g[q].row_begin, p.g[q].row_end}};
+        rc = weight_grad_route(r, L.own, use_batch ? &wpb : nullptr, w, s, ch[i]);
+        if (rc == MPNHIP_OK && use_batch && !one_launch) {
+            rc = wp_batch_flush(&wpb, s);
+            wp_batch_init(&wpb, L.batch, L.batch_floats, batched != 0, &s);
+        }
+    }
+    if (rc == MPNHIP_OK && use_batch && one_launch) rc = wp_batch_flush(&wpb, s);
+    if (chosen) memcpy(chosen, ch, sizeof(WgChosen) * 2 * (size_t)n_products);
+    return rc;
 }

@@ -866,6 +866,7 @@ void wp_batch_init(WpBatch* b, float* slab, size_t slab_floats, bool batched, co
     b->nred = 0;
     b->stream = stream ? *stream : nullptr;
     b->has_stream = stream != nullptr;
+    for (int i = 0; i < WP_MAX_JOBS; ++i) b->chosen[i] = nullptr;
 }
 bool wp_batch_roll(WpBatch* b, int* status) {
     *status = MPNHIP_OK;
@@ -879,7 +880,7 @@ bool wp_batch_roll(WpBatch* b, int* status) {
 static bool ranged_gather(const WpProduct& p) { return p.dz_idx || p.h_idx || p.H2; }
 
 // records the n (1 or 2: the direction groups of one product) jobs, or none of them
-bool wp_batch_add(WpBatch* b, const WpProduct* ps, int n) {
+bool wp_batch_add(WpBatch* b, const WpProduct* ps, int n, WgChosen* chosen) {
     if (b->tab.njobs + n > WP_MAX_JOBS) return false;
     size_t need = 0;
     for (int i = 0; i < n; ++i) {
@@ -918,6 +919,7 @@ bool wp_batch_add(WpBatch* b, const WpProduct* ps, int n) {
         J.red_block0 = b->nred;
         b->nred += (int)(((int64_t)p.n_out * tn_kpad(p.k_in) / 4 + 31) / 32);
         b->used += wp_slab_floats(p.n_out, p.k_in, p.rows, p.nbatch, ranged, b->batched, p.src16 != 0);
+        b->chosen[b->tab.njobs] = chosen ? chosen + i : nullptr;
         b->flops += 2.0 * (ranged ? p.rows / 2.0 : (double)p.rows) * p.nbatch * p.n_out * p.k_in;
         b->bytes += (p.src16 ? 2.0 : 4.0) * (ranged ? p.rows / 2.0 : (double)p.rows) * p.nbatch * (p.n_out + p.k_in);
         ++b->tab.njobs;
@@ -967,6 +969,13 @@ int wp_batch_flush(WpBatch* b, hipStream_t s) {
             count_path(PC_TN_PANEL_NARROW);
         }
     }
+    for (int i = 0; i < b->tab.njobs; ++i)
+        if (WgChosen* c = b->chosen[i]) {
+            const WpJob& J = b->tab.job[i];
+            c->path = J.variant >= 16 ? WG_PATH_ROWS16 : WG_PATH_PANEL;
+            c->variant = J.variant; c->tiles_o = J.tiles_o; c->tiles_c = J.tiles_c; c->chunk = J.chunk; c->nsplit = J.nsplit;
+            c->narrow = narrow && J.variant < 16 ? 1 : 0;
+        }
     {   // (block counts follow the tiling: recomputed here, then re-indexed below)
         int n1 = 0, n2 = 0;
         for (int i = 0; i < b->tab.njobs; ++i) {

@@ -278,3 +278,80 @@ def test_gemm_debug_entries_argument_checks_without_gpu():
         assert l.mpnhip_debug_linear_splitk(p, kw.get("ldx", k), p, None, p, 8, m, 8, k, 0, prec, None, None, 0, 0, None, 0,
                                             kw.get("scratch", p), floats, tf, None) == 0, kw
         assert list(tf) == [0, 0], kw
+
+
+def test_wgrad_product_layout_matches_c():
+    # mpnhip_wgrad_group: 4 pointers; mpnhip_wgrad_product: 13 pointers / int64, 5 ints (+ 4 bytes of padding), two groups
+    G, P = capi.WgradGroup, capi.WgradProduct
+    assert ctypes.sizeof(G) == 32 and [f[0] for f in G._fields_] == ["grad_w", "grad_b", "row_begin", "row_end"]
+    offsets = dict(dZ=0, ldz=8, z_bstride=16, dz_idx=24, H=32, ldh=40, h_bstride=48, h_idx=56, H2=64, ldh2=72, h2_bstride=80, ldw=88,
+                   rows=96, csplit=104, n_out=108, k_in=112, nbatch=116, src16=120, g=128)
+    assert ctypes.sizeof(P) == 13 * 8 + 5 * 4 + 4 + 2 * 32 == 192
+    assert [f[0] for f in P._fields_] == list(offsets)
+    for name, off in offsets.items():
+        assert getattr(P, name).offset == off, name
+    src = open(os.path.join(REPO, "include", "mpnhip.h")).read()
+    body = re.search(r"typedef struct mpnhip_wgrad_group \{(.*?)\} mpnhip_wgrad_group;", src, flags=re.S).group(1)
+    assert re.findall(r"(\w+);", body) == [f[0] for f in G._fields_]
+    body = re.search(r"typedef struct mpnhip_wgrad_product \{(.*?)\} mpnhip_wgrad_product;", src, flags=re.S).group(1)
+    assert re.findall(r"(\w+)(?:\[2\])?;", body) == list(offsets)
+    assert len(capi.WG_CHOSEN_FIELDS) == 10 and sorted(capi.WG_PATHS) == [-1, 0, 1, 2, 3, 4, 5]
+
+
+def test_weight_grad_batch_debug_entry_argument_checks_without_gpu():
+    """mpnhip_debug_weight_grad_batch checks its arguments on the host: everything below returns before a kernel is launched (the
+    non-null pointers are host dummies that are never dereferenced)."""
+    l = capi.load()
+    dummy = ctypes.create_string_buffer(256)
+    p = ctypes.cast(dummy, ctypes.c_void_p).value
+    big = 1 << 30        # a workspace size that is never too small (the dummy is not touched before the checks have passed)
+
+    def prod(**kw):
+        a = capi.WgradProduct()
+        a.dZ, a.ldz, a.z_bstride, a.H, a.ldh, a.h_bstride = p, 8, 0, p, 8, 0
+        a.ldw, a.rows, a.n_out, a.k_in, a.nbatch = 8, 100, 8, 8, 1
+        a.g[0].grad_w = p
+        for k, v in kw.items():
+            setattr(a, k, v)
+        return a
+
+    def call(products, n=None, prec=2, ws=p, ws_bytes=big, chosen=None):
+        arr = (capi.WgradProduct * max(len(products), 1))(*products)
+        n = len(products) if n is None else n
+        return l.mpnhip_debug_weight_grad_batch(arr if products else None, n, prec, 0, 1, 0, ws, ws_bytes, chosen, None)
+    chosen = (ctypes.c_int32 * 20)(*([7] * 20))
+    assert call([], n=1, chosen=chosen) == -1
+    assert b"debug_weight_grad_batch: null products" in l.mpnhip_last_error()
+    for n in (0, -1, 17):
+        assert call([prod()] * 17, n=n, chosen=chosen) == -1, n
+        assert b"products (1 .. 16)" in l.mpnhip_last_error()
+    for prec in (-1, 3, 4):
+        assert call([prod()], prec=prec, chosen=chosen) == -1, prec
+        assert b"unknown precision" in l.mpnhip_last_error()
+    for prec in (0, 2):
+        assert call([prod(src16=1)], prec=prec, chosen=chosen) == -1, prec
+        assert b"src16 needs the bf16 precision" in l.mpnhip_last_error()
+    for cs in (0, 8, 9, -4):
+        assert call([prod(), prod(H2=p, ldh2=8, csplit=cs)], chosen=chosen) == -1, cs
+        assert b"product 1: csplit" in l.mpnhip_last_error()
+    for bad in (dict(n_out=0), dict(k_in=0), dict(rows=-1), dict(nbatch=0), dict(ldw=7), dict(dZ=None), dict(H=None)):
+        assert call([prod(**bad)], chosen=chosen) == -1, bad
+        assert b"debug_weight_grad_batch: product 0" in l.mpnhip_last_error()
+    # the workspace: null, or smaller than the size query says, through the common refusal (MPNHIP_ERR_WORKSPACE)
+    for prec in (0, 1, 2):
+        arr = (capi.WgradProduct * 2)(prod(), prod(rows=5000, n_out=64, k_in=64, ldz=64, ldh=64, ldw=64))
+        need = l.mpnhip_debug_weight_grad_batch_workspace_bytes(arr, 2, prec, 0, 0)
+        assert need > 256
+        assert l.mpnhip_debug_weight_grad_batch(arr, 2, prec, 0, 1, 0, p, need - 1, chosen, None) == -3
+        assert b"debug_weight_grad_batch: workspace" in l.mpnhip_last_error()
+        assert l.mpnhip_debug_weight_grad_batch(arr, 2, prec, 0, 1, 0, None, need, chosen, None) == -3
+        # more rows, more batches, a batched plan with fewer chunks: the size follows the chunk plans
+        assert l.mpnhip_debug_weight_grad_batch_workspace_bytes(arr, 1, prec, 0, 0) < need
+    assert list(chosen) == [7] * 20      # a refusal leaves `chosen` alone
+    # the size query refuses the same descriptions with 0
+    assert l.mpnhip_debug_weight_grad_batch_workspace_bytes(None, 1, 2, 0, 0) == 0
+    assert l.mpnhip_debug_weight_grad_batch_workspace_bytes((capi.WgradProduct * 1)(prod(src16=1)), 1, 2, 0, 0) == 0
+    # no rows: a successful no-op, nothing chosen
+    for prec in (0, 1, 2):
+        assert call([prod(rows=0)], prec=prec, chosen=chosen) == 0
+        assert list(chosen)[:10] == [-1] + [0] * 9
