@@ -12,6 +12,7 @@
 #include <cstdlib>
 #include <mutex>
 
+#include "backward_plan.h"
 #include "common.h"
 #include "edge_chain.h"
 #include "plan.h"
@@ -249,240 +250,14 @@ struct SideJoin {
     }
 };
 
-// ------------------------------------------------------------------------------------ plan
-// Pre-activation gradients (dZ) of EVERY step are kept ([L][rows][width] blocks): the activation-gradient
-// chain of a step reads its predecessor's block, and after the step loop each weight's gradient is ONE
-// batched split-row product over all L steps (12x fewer launches and slab reductions than per step).
-struct BwdPlan {
-    float* dX[2];                       // [N, dn] ping-pong: gradient w.r.t. x_s
-    float* dXh;                         // [N, dn] second K half of the per-node projection's activation gradient (split product)
-    float* dX0;                         // [N, dn] gradient w.r.t. the encoder's node output
-    float* dE0;                         // [E, de]
-    float* dAGG;                        // [N, 2dn]
-    float* dCat;                        // [max(E ke, N kx)] gradient w.r.t. the concatenated [initial | current] features
-    float* dPsum;                       // [N, pw] sum over the steps of dP (the re-attached x0's share is one product)
-    float* dZ1sum;                      // [E, he] sum over the steps of the edge MLP's first-layer dZ (the re-attached e0's share)
-    float* dZn;                         // [L][N, dn]
-    float* dP;                          // [L][N, pw]
-    unsigned short* dP16;               // bf16-operand training: the same blocks rounded to bf16 rows (the node-level weight-gradient
-    unsigned short* dPsum16;            // products over bf16 rows, wgrad_rows16.hip), and the rounded sum over the steps [N, pw]
-    unsigned short* dZn16;              // ... and the node update's operands: [L][N, dn] pre-activation gradients, [L][N, 2 dn] aggregated
-    unsigned short* AGG16;              // messages, rounded on the side stream just before the group's products
-    unsigned short* enc16;              // ... and the node encoder's dZ / input blocks [N, sum of (out_i + in_i)] (rounded on the tail's stream)
-    size_t enc16_elems;
-    float* dZfl[MPNHIP_MAX_LAYERS];     // flow MLP layer i:   [L][E, out_i]
-    float* dZed[MPNHIP_MAX_LAYERS];     // edge MLP layer i:   [L][E, out_i]  (last layer: the masked dE_s)
-    float* dZcl[MPNHIP_MAX_LAYERS];     // classifier layer i: [L][E, out_i]  (i < n-1; the last one is grad_logits)
-    float* T[3];                        // edge-encoder chain scratch [E, max encoder width], rotating (layer i -> buffer (n - 1 - i) % 3)
-    float* Tn[3];                       // node-encoder chain scratch [N, max encoder width]: chains of <= 3 layers never overwrite a
-                                        // dZ block, so their weight-gradient products may run later, on another stream
-    int t_width;                        // that width (floats per row)
-    // zero-padded copies of the per-edge weights for the fused backward chain (native [n][k] orientation)
-    float* wf2p[2]; float* wfep[2]; float* wc1p; float* w2p; float* w1ep;
-    float* gWnode;                      // [pw, kx] gradient of the packed node-projection weights
-    float* zero_end;                    // end of the run dX[0] | dX0 | dE0 | gWnode that a backward zero-fills at once
-    unsigned short* ncb_img;            // unit images of the fused node-side backward kernel (node_chain.hip) or nullptr
-    float* wt_scratch;                  // MPNHIP_PREC_BF16: transposed weight blocks of the activation-gradient products
-    size_t wt_scratch_floats;
-    float* wt_keep[2];                  // ... the node update's (0) and the projections' (1) blocks, transposed once per backward
-    size_t wt_keep_floats[2];
-    unsigned short* wt_keep16[2];       // ... and their bf16 images: the B operand of the tiled bf16 GEMM as bf16 rows (gemm_bf16.hip)
-    // bf16-operand training on the fused kernels (FwdPlan::b16): the dZ blocks above are bf16 rows (half the floats), the gradient
-    // w.r.t. e_s travels between the steps in two fp32 buffers, and the backward chain kernel has its own pair images
-    bool b16;
-    float* dEpp[2];                     // [E, de] fp32 ping-pong
-    char* cb16_img;                     // backward pair images (edge | classifier | flow_out | flow_in)
-    size_t cb16_off_cls, cb16_off_flow[2];
-    float* slab;                        // split partials of the weight-gradient products (2 groups)
-    float* slab_side;                   // the same for the products issued on the side stream
-    size_t slab_floats_per_group;
-    float* slab_wp;                     // slabs of a batch of row-panel products (all jobs of one group of steps)
-    size_t slab_wp_floats;
-    float* slab_tail;                   // slabs of the tail batch (hoisted shares + encoder layers)
-    size_t slab_tail_floats;
-    size_t total;
-};
-
-static int enc_maxw(const mpnhip_model& m, const Dims& d) {
-    int w = d.dn > d.de ? d.dn : d.de;
-    const mpnhip_mlp* all[] = {&m.enc_node, &m.enc_edge};
-    for (const mpnhip_mlp* p : all)
-        for (int i = 0; i < p->n_layers; ++i) w = p->out_dims[i] > w ? p->out_dims[i] : w;
-    return w;
-}
-
-// slab floats of the weight-gradient products of an MLP's layers (layer 0's k_in given: the share of the input it is taken over)
-static size_t mlp_slab(const mpnhip_mlp& m, int k_in0, int64_t rows, int nbatch) {
-    size_t mx = 0;
-    for (int i = 0; i < m.n_layers; ++i) {
-        size_t f = tn_slab_floats(m.out_dims[i], i == 0 ? k_in0 : m.out_dims[i - 1], rows, nbatch);
-        mx = f > mx ? f : mx;
-    }
-    return mx;
-}
-
-// slab floats of one row-panel product inside a batch: its fp32-row form or, where the operands may be bf16 rows, the larger of the two
-static size_t wp_slab_either(int n_out, int k_in, int64_t rows, int nb, bool ranged, bool rows16) {
-    if (rows <= 0) return 0;
-    const size_t f32 = wp_slab_floats(n_out, k_in, rows, nb, ranged, true), f16 = rows16 ? wp_slab_floats(n_out, k_in, rows, nb, ranged, true, true) : 0;
-    return f32 > f16 ? f32 : f16;
-}
-
-// The slabs of the weight-gradient products, in three parts.  Each lists exactly the products mpnhip_backward launches in that form
-// (the slab size depends on the shape through tn_plan / the row-panel chunking); node16: the node-level products run over bf16 rows.
-// 1. one product alone on a stream: floats of the LARGEST one (BwdPlan::slab and slab_side hold two direction groups of it)
-static size_t slab_per_group(const mpnhip_model& m, const Dims& d, int64_t N, int64_t E, int L, bool b16, bool node16) {
-    size_t sl = 0;
-    auto upd = [&](size_t f) { sl = f > sl ? f : sl; };
-    upd(mlp_slab(m.enc_node, m.enc_node.in_dim, N, 1));
-    upd(mlp_slab(m.enc_edge, m.enc_edge.in_dim, E, 1));
-    upd(mlp_slab(m.edge, d.ke, E, L));
-    for (int nb = 1; nb <= L; ++nb) upd(tn_slab_floats(d.he, d.de, E, nb));   // (the e0-hoisted forms of the edge layer-0 product)
-    upd(mlp_slab(m.flow_in, d.de, E, L));
-    upd(mlp_slab(m.classifier, d.de, E, L));
-    upd(tn_slab_floats(d.dn, 2 * d.dn, N, L));
-    upd(tn_slab_floats(d.pw, d.kx, N, L));
-    // the same products in the row-panel form (MPNHIP_PREC_FP32_SPLIT); a group's share of the slab is half of it
-    auto updw = [&](int n_out, int k_in, int64_t rows, bool rows16) { if (rows > 0) upd((wp_slab_floats(n_out, k_in, rows, 1, false, false, rows16) + 1) / 2); };
-    for (int i = 0; i < m.enc_node.n_layers; ++i) updw(m.enc_node.out_dims[i], layer_in(m.enc_node, i), N, false);
-    for (int i = 0; i < m.enc_edge.n_layers; ++i) updw(m.enc_edge.out_dims[i], layer_in(m.enc_edge, i), E, false);
-    updw(d.he, d.de, E, false);
-    if (b16) updw(d.he, d.de, E, true);      // (the hoisted e0 share over bf16 rows)
-    updw(d.pw, d.dn, N, false);
-    if (node16) updw(d.pw, d.dn, N, true);   // (the hoisted x0 share over bf16 rows)
-    for (int i = 0; i < m.classifier.n_layers; ++i) updw(m.classifier.out_dims[i], layer_in(m.classifier, i), E, false);
-    return sl;
-}
-
-// 2. all products of a group of nb steps in one batch (mp_weight_grads): every job has its own slabs, so their SUM
-static size_t slab_batched(const mpnhip_model& m, const Dims& d, int64_t N, int64_t E, int nb, bool b16) {
-    size_t t = 0;
-    auto wp = [&](int n_out, int k_in, int64_t rows, bool ranged) { return wp_slab_either(n_out, k_in, rows, nb, ranged, b16); };
-    t += wp(d.dn, 2 * d.dn, N, false);
-    for (int i = 1; i < m.flow_in.n_layers; ++i) t += 2 * wp(m.flow_in.out_dims[i], layer_in(m.flow_in, i), E, true);   // (flow_in and flow_out)
-    t += 2 * wp(d.hn, d.de, E, true);
-    for (int i = 0; i < m.classifier.n_layers; ++i) t += wp(m.classifier.out_dims[i], layer_in(m.classifier, i), E, false);
-    for (int i = 1; i < m.edge.n_layers; ++i) t += wp(m.edge.out_dims[i], layer_in(m.edge, i), E, false);
-    // (a product that runs in one of two forms -- the first-layer inputs whole or with the re-attached share hoisted -- reserves
-    // the larger of the two: a narrower k_in can mean MORE row chunks, i.e. more slabs)
-    auto larger = [](size_t x, size_t y) { return x > y ? x : y; };
-    t += larger(wp(d.he, d.ke, E, false), wp(d.he, d.de, E, false));
-    t += larger(wp(d.pw, d.kx, N, false), wp(d.pw, d.dn, N, false));
-    return t;
-}
-
-// 3. the tail batch: hoisted shares + encoder layers, their sum
-static size_t slab_tail(const mpnhip_model& m, const Dims& d, int64_t N, int64_t E, bool b16, bool node16) {
-    size_t t = 0;
-    t += wp_slab_either(d.pw, d.dn, N, 1, false, node16);
-    t += wp_slab_either(d.he, d.de, E, 1, false, b16);   // (bf16-operand training keeps S = sum_s dZ1_s as bf16 rows: the bf16-row kernels' chunking)
-    for (int i = 0; i < m.enc_node.n_layers; ++i) t += wp_slab_either(m.enc_node.out_dims[i], layer_in(m.enc_node, i), N, 1, false, node16);
-    for (int i = 0; i < m.enc_edge.n_layers; ++i) t += wp_slab_either(m.enc_edge.out_dims[i], layer_in(m.enc_edge, i), E, 1, false, false);
-    return t;
-}
-
-static size_t plan_backward(const mpnhip_model& m, const Dims& d, int64_t N, int64_t E, void* base, BwdPlan* out) {
-    Carver a(base);
-    BwdPlan p = {};
-    const size_t L = d.L > 0 ? d.L : 1;
-    // (what every backward starts from as zeros lies side by side -- dX[0] | dX0 | dE0 | gWnode: ONE fill instead of four, ~12 us of
-    // the 0.5 ms step of a KITTIMOTS-size graph)
-    p.dX[0] = a.take<float>((size_t)N * d.dn);
-    p.dX0 = a.take<float>((size_t)N * d.dn);
-    p.dE0 = a.take<float>((size_t)E * d.de);
-    p.gWnode = a.take<float>((size_t)d.pw * d.kx);
-    p.zero_end = a.take<float>(0);
-    p.dX[1] = a.take<float>((size_t)N * d.dn);
-    p.dXh = a.take<float>((size_t)N * d.dn);
-    p.dPsum = a.take<float>((size_t)N * d.pw);
-    p.dZ1sum = a.take<float>((size_t)E * d.he);
-    p.dAGG = a.take<float>((size_t)N * 2 * d.dn);
-    {
-        size_t a1 = (size_t)E * d.ke, a2 = (size_t)N * d.kx;
-        p.dCat = a.take<float>(a1 > a2 ? a1 : a2);
-    }
-    p.dZn = a.take<float>(L * N * d.dn);
-    p.dP = a.take<float>(L * N * d.pw);
-    p.b16 = chain_bf16_train_ok(m, d);
-    p.dP16 = p.dPsum16 = p.dZn16 = p.AGG16 = p.enc16 = nullptr;
-    p.enc16_elems = 0;
-    const bool node16 = p.b16 && d.pw % 8 == 0 && d.dn % 8 == 0;   // (not `p.dP16 != nullptr`: a size query plans without a base)
-    if (node16) {
-        p.dP16 = a.take<unsigned short>(L * N * d.pw);
-        p.dPsum16 = a.take<unsigned short>((size_t)N * d.pw);
-        p.dZn16 = a.take<unsigned short>(L * N * d.dn);
-        p.AGG16 = a.take<unsigned short>(L * N * 2 * d.dn);
-        size_t w = 0;
-        for (int i = 0; i < m.enc_node.n_layers; ++i) w += (size_t)m.enc_node.out_dims[i] + layer_in(m.enc_node, i);
-        p.enc16_elems = (size_t)N * w;
-        p.enc16 = a.take<unsigned short>(p.enc16_elems);
-    }
-    // (b16: the dZ blocks are bf16 rows)
-    auto dzb = [&](int width) { return a.take_as<float>(L * E * width, p.b16 ? sizeof(unsigned short) : sizeof(float)); };
-    for (int i = 0; i < m.flow_in.n_layers; ++i) p.dZfl[i] = dzb(m.flow_in.out_dims[i]);
-    for (int i = 0; i < m.edge.n_layers; ++i) p.dZed[i] = dzb(m.edge.out_dims[i]);
-    for (int i = 0; i + 1 < m.classifier.n_layers; ++i) p.dZcl[i] = dzb(m.classifier.out_dims[i]);
-    p.dEpp[0] = p.dEpp[1] = nullptr;
-    p.cb16_img = nullptr;
-    if (p.b16) {
-        for (int i = 0; i < 2; ++i) p.dEpp[i] = a.take<float>((size_t)E * d.de);
-        p.cb16_img = a.take<char>(chain_bf16_bwd_image_bytes(d.he, d.de, d.hn, d.dn, m.classifier.out_dims[0], &p.cb16_off_cls, &p.cb16_off_flow[0],
-                                                             &p.cb16_off_flow[1]));
-    }
-    int mw = enc_maxw(m, d);
-    if (mw < 52) mw = 52;   // (the fused reference edge encoder keeps dz2 | dz1 | dz0 side by side in T[0])
-    for (int i = 0; i < 3; ++i) p.T[i] = a.take<float>((size_t)E * mw);
-    for (int i = 0; i < 3; ++i) p.Tn[i] = a.take<float>((size_t)N * mw);
-    p.t_width = (int)mw;
-    {
-        const size_t HE = pad32(d.he), DE = pad32(d.de), HN = pad32(d.hn), DN = pad32(d.dn);
-        // (sized for the split images, 3/2 of the fp32 ones)
-        for (int q = 0; q < 2; ++q) { p.wf2p[q] = a.take<float>(DN * HN * 3 / 2); p.wfep[q] = a.take<float>(HN * DE * 3 / 2); }
-        p.wc1p = a.take<float>(32 * DE * 3 / 2);
-        p.w2p = a.take<float>(DE * HE * 3 / 2);
-        p.w1ep = a.take<float>(HE * 2 * DE * 3 / 2);
-    }
-    p.ncb_img = nullptr;
-    if (node_chain_bwd_supported(d.dn, d.pw, d.kx) && m.node.n_layers == 1 && m.precision == MPNHIP_PREC_FP32_SPLIT)
-        p.ncb_img = a.take<unsigned short>(node_chain_bwd_image_shorts(d.dn, d.pw, nullptr));
-    {   // MPNHIP_PREC_BF16: transposition scratch of the activation-gradient products (two direction groups of the largest weight)
-        size_t mx = (size_t)d.pw * d.kx;
-        const mpnhip_mlp* all[] = {&m.enc_node, &m.enc_edge, &m.edge, &m.flow_in, &m.flow_out, &m.node, &m.classifier};
-        for (const mpnhip_mlp* q : all)
-            for (int i = 0; i < q->n_layers; ++i) {
-                const size_t w = (size_t)q->out_dims[i] * layer_in(*q, i);
-                mx = w > mx ? w : mx;
-            }
-        p.wt_scratch_floats = m.precision == MPNHIP_PREC_BF16 ? 2 * mx : 0;
-        p.wt_scratch = a.take<float>(p.wt_scratch_floats);
-        p.wt_keep_floats[0] = m.precision == MPNHIP_PREC_BF16 && m.node.n_layers >= 1 ? (size_t)d.dn * m.node.in_dim : 0;
-        p.wt_keep_floats[1] = m.precision == MPNHIP_PREC_BF16 ? (size_t)d.pw * d.dn : 0;
-        for (int i = 0; i < 2; ++i) p.wt_keep[i] = a.take<float>(p.wt_keep_floats[i]);
-        for (int i = 0; i < 2; ++i) p.wt_keep16[i] = a.take<unsigned short>(p.wt_keep_floats[i]);
-    }
-    p.slab_floats_per_group = slab_per_group(m, d, N, E, (int)L, p.b16, node16);
-    p.slab = a.take<float>(2 * p.slab_floats_per_group);
-    p.slab_side = a.take<float>(2 * p.slab_floats_per_group);
-    p.slab_wp_floats = 0;
-    for (int nb = 1; nb <= (int)L; ++nb) {
-        const size_t t = slab_batched(m, d, N, E, nb, p.b16);
-        p.slab_wp_floats = t > p.slab_wp_floats ? t : p.slab_wp_floats;
-    }
-    p.slab_wp = a.take<float>(p.slab_wp_floats);
-    p.slab_tail_floats = slab_tail(m, d, N, E, p.b16, node16);
-    p.slab_tail = a.take<float>(p.slab_tail_floats);
-    p.total = a.bytes();
-    if (out) *out = p;
-    return p.total;
-}
-
 // ------------------------------------------------------------------------------------ helpers
+// (BwdPlan, plan_backward: backward_plan.h)
 // (RowRange, Operand, WgProduct: common.h)
 // ... two weight blocks that are KEPT transposed for the whole backward: the node update's and the per-node projections' weights are the
 // operands of an activation-gradient product in every step (22 transpositions of the same two blocks per cfg-E step before round 4,
 // 25 - 30 us each)
 struct WtKeep { float* wt; size_t floats; bool valid; unsigned short* wt16; };
-// what the helpers of one mpnhip_backward_flags call share (built once, after plan_backward; it lives in that call's frame)
+// what the helpers of one mpnhip_backward_flags call share (BackwardRun::c: built once, in init() after plan_backward; it lives in that call's frame)
 struct BwdCtx {
     const BwdPlan* p;
     // a model in MPNHIP_PREC_FP32_SPLIT / _WGSPLIT / _BF16: weight gradients in the three-piece operand form (wgrad_panel.hip)
@@ -580,7 +355,6 @@ static int mlp_weight_grads(const BwdCtx& c, float* slab_base, WpBatch* batch, c
     return MPNHIP_OK;
 }
 
-// encoder-style chain with ping-pong scratch (one batch): returns dZ of layer 0 in *dz
 // ---- the reference's edge encoder (6 -> 18 -> 18 -> 16) backwards: the three activation gradients of an edge in one thread ------
 //   dz2 = dE0 (.) [e0 > 0];   dz1 = (dz2 W2) (.) [H2 > 0];   dz0 = (dz1 W1) (.) [H1 > 0]
 // (instead of a ReLU-mask kernel and two launches of the any-shape GEMM kernel; the weight-gradient products read dz2 / dz1 / dz0)
@@ -659,6 +433,7 @@ static int encoder_weight_grad(const BwdCtx& c, WpBatch* batch, Rows16Later* L16
     return weight_grad(c, c.p->slab, batch, w, s);
 }
 
+// encoder-style chain with ping-pong scratch (one batch): returns dZ of layer 0 in *dz
 static int mlp_tail_backward(BwdCtx& c, WpBatch* batch, Rows16Later* L16, float* const* T, const mpnhip_mlp& m0, float* const* hidden,
                              const float** dz, int* cur_buf, int64_t rows, hipStream_t s) {
     for (int i = m0.n_layers - 1; i >= 1; --i) {
@@ -674,166 +449,443 @@ static int mlp_tail_backward(BwdCtx& c, WpBatch* batch, Rows16Later* L16, float*
     return MPNHIP_OK;
 }
 
-}  // namespace mpnhip
-
-using namespace mpnhip;
-
-extern "C" size_t mpnhip_backward_workspace_bytes(const mpnhip_model* model, int n_nodes, int64_t n_edges) {
-    Dims d;
-    if (!model) return 256;  // non-zero: "the backward pass is built into this library"
-    if (check_full(*model, &d, false) != MPNHIP_OK) return 0;
-    return plan_backward(*model, d, n_nodes, n_edges, nullptr, nullptr);
+// ------------------------------------------------------------------------------------ one backward call
+// bf16 rows: pointer `elems` unsigned shorts into a buffer the plans type as float*
+static inline const float* u16(const float* p0, int64_t elems) {
+    return reinterpret_cast<const float*>(reinterpret_cast<const unsigned short*>(p0) + elems);
 }
+static inline unsigned short* w16(float* p0, int64_t elems) { return reinterpret_cast<unsigned short*>(p0) + elems; }
 
 static bool backward_forks(const mpnhip_model& m) { return m.num_enc_steps >= 4; }
 
-extern "C" int mpnhip_backward_uses_side_stream(const mpnhip_model* model) { return model && backward_forks(*model) ? 1 : 0; }
-
-extern "C" void* mpnhip_side_stream(void) {
-    SideStream* side = nullptr;
-    std::lock_guard<std::mutex> lock(g_side_mu);
-    return side_stream_ready(&side) == MPNHIP_OK ? static_cast<void*>(side->stream) : nullptr;
-}
-
-extern "C" int mpnhip_side_stream_join(void* stream_) {
-    SideStream* side = nullptr;
-    std::lock_guard<std::mutex> lock(g_side_mu);
-    MPN_TRY(side_stream_ready(&side));
-    MPN_HIP(hipEventRecord(side->done, side->stream));
-    MPN_HIP(hipStreamWaitEvent(static_cast<hipStream_t>(stream_), side->done, 0));
-    return MPNHIP_OK;
-}
-
-extern "C" int mpnhip_backward(const mpnhip_model* model, const void* graph_buf, int n_nodes, int64_t n_edges,
-                               const float* x, const float* edge_attr, const float* grad_logits, const float* grad_x_out,
-                               const float* grad_e_out, float* grad_x, float* grad_edge_attr, void* fwd_workspace,
-                               size_t fwd_workspace_bytes, void* bwd_workspace, size_t bwd_workspace_bytes, void* stream_) {
-    return mpnhip_backward_flags(model, graph_buf, n_nodes, n_edges, x, edge_attr, grad_logits, grad_x_out, grad_e_out, grad_x,
-                                 grad_edge_attr, fwd_workspace, fwd_workspace_bytes, bwd_workspace, bwd_workspace_bytes, 0, stream_);
-}
-
-extern "C" int mpnhip_backward_flags(const mpnhip_model* model, const void* graph_buf, int n_nodes, int64_t n_edges,
-                                     const float* x, const float* edge_attr, const float* grad_logits, const float* grad_x_out,
-                                     const float* grad_e_out, float* grad_x, float* grad_edge_attr, void* fwd_workspace,
-                                     size_t fwd_workspace_bytes, void* bwd_workspace, size_t bwd_workspace_bytes, int flags,
-                                     void* stream_) {
-    hipStream_t s = static_cast<hipStream_t>(stream_);
-    MPN_CHECK_ARG(model && graph_buf, "backward: null model / graph");
-    const mpnhip_model& m = *model;
+// One call of mpnhip_backward_flags: constructed in that call's frame, its methods are the phases of the backward in the order
+// mpnhip_backward_flags calls them.  Every method returns an MPNHIP_* status; after a failure the object is only destroyed (which
+// orders the caller's stream behind whatever was forked: SideJoin).
+struct BackwardRun {
+    // ---- what the caller gave
+    const mpnhip_model& m;
+    const float* const x;
+    const float* const edge_attr;
+    const float* const grad_logits;
+    const float* const grad_x_out;
+    const float* const grad_e_out;
+    float* const grad_x;
+    float* const grad_edge_attr;
+    const int flags;
+    const hipStream_t s;   // the caller's stream: the step loop, the hoisted shares' sums and the encoder chains run here
+    // ---- init(): plans, widths, modes
     Dims d;
-    MPN_TRY(check_full(m, &d));
-    const int64_t N = n_nodes, E = n_edges;
-    MPN_CHECK_ARG(N >= 0 && E >= 0, "backward: negative sizes");
-    MPN_CHECK_ARG((x || N == 0) && (edge_attr || E == 0) && (grad_logits || E == 0), "backward: null tensor");
-    {
-        const mpnhip_mlp* all[] = {&m.enc_node, &m.enc_edge, &m.edge, &m.flow_in, &m.flow_out, &m.node, &m.classifier};
-        for (const mpnhip_mlp* q : all)
-            for (int i = 0; i < q->n_layers; ++i)
-                MPN_CHECK_ARG(q->grad_weight[i] && q->grad_bias[i], "backward: null gradient buffer");
-    }
     FwdPlan f;
-    const size_t fneed = plan_forward(m, d, N, E, 1, fwd_workspace, &f);
-    MPN_CHECK_WORKSPACE_MSG("backward: forward workspace", " (must be the save_for_backward buffer)", fwd_workspace, fwd_workspace_bytes, fneed);
     BwdPlan p;
-    const size_t need = plan_backward(m, d, N, E, bwd_workspace, &p);
-    MPN_CHECK_WORKSPACE("backward", bwd_workspace, bwd_workspace_bytes, need);
-    BwdCtx c = {&p, m.precision == MPNHIP_PREC_FP32_SPLIT || m.precision == MPNHIP_PREC_FP32_WGSPLIT || m.precision == MPNHIP_PREC_BF16,
-                m.precision == MPNHIP_PREC_BF16, {}};
-    for (int i = 0; i < 2; ++i) c.wt_keep[i] = {p.wt_keep_floats[i] ? p.wt_keep[i] : nullptr, p.wt_keep_floats[i], false, p.wt_keep_floats[i] ? p.wt_keep16[i] : nullptr};
     GraphView g;
-    graph_layout(n_nodes, n_edges, &g, const_cast<void*>(graph_buf));
-    const int he = d.he, hn = d.hn, dn = d.dn, de = d.de, kx = d.kx, ke = d.ke, pw = d.pw, L = d.L;
-    const size_t xs = (size_t)N * dn, es = (size_t)E * de;
-    const RowRange dir_rr[2] = {{nullptr, g.header + 4}, {g.header + 4, g.header + 5}};
-    const mpnhip_mlp& cls = m.classifier;
-    const int ne = m.edge.n_layers, nfl = m.flow_in.n_layers, nc = cls.n_layers;
-    const int64_t sstride = (int64_t)(f.step_stride_bytes / sizeof(float));  // floats between two steps' saved activations
+    // the ONE BwdCtx of the call: act_grad flips wt_keep[].valid in it -- a copy per phase would transpose the kept blocks again
+    BwdCtx c;
+    int64_t N = 0, E = 0;
+    int he = 0, hn = 0, dn = 0, de = 0, kx = 0, ke = 0, pw = 0, L = 0;
+    size_t xs = 0, es = 0;          // floats of one [N, dn] / [E, de] block
+    RowRange dir_rr[2];             // device-side row ranges of the two flow directions
+    int ne = 0, nfl = 0, nc = 0;    // layers of the edge MLP, the flow MLPs, the classifier
+    int64_t sstride = 0;            // floats between two steps' saved activations
+    const float* x0 = nullptr;      // the encoder's outputs (x_hist[0], e_hist[0])
+    const float* e0 = nullptr;
+    bool use_b16 = false;       // bf16-operand training on the fused kernels (plan.h: chain_bf16_train_ok)
+    bool use_chain = false;     // the fused fp32 edge chain (edge_chain.hip)
+    bool bwd_split = false;     // ... on split images
+    bool hoist_x = false;       // the re-attached x0's share of dX / gWnode: once, from the sum of the steps' dP (hoisted_shares)
+    bool hoist_e0 = false;      // the same for the re-attached e0 on the edge side
+    bool node16 = false;        // bf16-operand training: the node-level weight-gradient products over bf16 rows
+    bool fuse_node_chain_bwd = false;   // F + the next step's A as one MFMA kernel (node_chain.hip)
+    bool fuse_node_bwd = false;         // the same at the reference's node width (segment.hip, node_step32_bwd)
+    size_t ncb_off_wu = 0;      // set by pack_weights: offset of the node update's units in p.ncb_img
+    // ---- schedule_groups(): the side stream and the groups of steps
+    SideStream* side = nullptr;
+    // g_side_mu is locked (schedule_groups) before the first hipEventRecord(side->ready, ...) and held until the call returns.
+    // Members are destroyed in reverse order of declaration: side_lock stands BEFORE join, so ~SideJoin runs under the lock on
+    // every exit path.
+    std::unique_lock<std::mutex> side_lock{g_side_mu, std::defer_lock};
+    // join.forked becomes true (fork_group_if_due) BEFORE the first mp_weight_grads on the side stream: a failure inside that call
+    // must still order the caller's stream behind the side stream.  join.joined: set at the join -- under tail_inline that is ahead
+    // of the unpacking (flush_tail_and_unpack), and join() finds it true.
+    SideJoin join;
+    int gsize[3] = {0, 0, 0};   // group sizes in steps, first-finished group first
+    int ngroups = 1;
+    // ---- loop state
+    int cx = 0;                 // p.dX[cx] holds the gradient w.r.t. x_s: flipped at the end of step(); read by node_update_bwd, projection_bwd
+    int ce = 0;                 // p.dEpp[ce] holds the gradient w.r.t. e_s (bf16 chain): flipped and read by edge_side_bf16
+    bool dx_split = false;      // set by projection_bwd (the gradient w.r.t. x_s arrived as two K halves, p.dX[cx] + p.dXh); read and
+                                // cleared by the next step's node_update_bwd
+    bool node_a_done = false;   // set by projection_bwd (its fused kernel already produced dZn / dAGG of the coming step); read and
+                                // cleared by the next step's node_update_bwd
+    int next_group = 0;         // the next group to fork: advanced and read by fork_group_if_due
+    // ---- the tail batch (plan_tail)
+    // tailb is initialised only when defer_tail holds; tail_hoist / tail_enc are null otherwise.  later16 is drained only in
+    // flush_tail, on the tail's stream.
+    WpBatch tailb;
+    Rows16Later later16;
+    bool defer_tail = false, defer_encoder = false, tail_beside = false, tail_inline = false;
+    WpBatch* tail_hoist = nullptr;   // where the hoisted shares' products are recorded (nullptr: run now)
+    WpBatch* tail_enc = nullptr;     // ... and the encoder's: only when the batch stays to the end
+    bool unpack_pending = false;     // set by finish_message_passing (the unpacking waits for the tail batch); read by flush_tail_and_unpack
 
-    // ---- seeds ----------------------------------------------------------------------------------
-    int cx = 0;
-    // zeros: dX[0] (unless the caller seeds it) | dX0 | dE0 | gWnode, contiguous in the plan -- and, below, the seed of the gradient
-    // w.r.t. e_L: ONE launch of a plain kernel for both (hipMemsetAsync's fill was preceded by ~18 us of idle queue in every step
-    // of the cfg-D timeline; two of them opened every backward)
-    char* const z0 = reinterpret_cast<char*>(grad_x_out ? p.dX0 : p.dX[0]);
-    const size_t z0_bytes = (size_t)(reinterpret_cast<char*>(p.zero_end) - z0);
-    if (grad_x_out) MPN_HIP(hipMemcpyAsync(p.dX[0], grad_x_out, xs * 4, hipMemcpyDeviceToDevice, s));
-    // the gradient w.r.t. e_s lives in the LAST edge-layer dZ block of step s (it becomes that dZ once masked)
-    if (f.b16 != p.b16) { set_error("backward: the forward workspace was saved in another mode (bf16 fused training %d vs %d)", (int)f.b16, (int)p.b16); return MPNHIP_ERR_ARG; }
-    const bool use_b16 = p.b16 && E > 0 && L > 0;   // bf16-operand training on the fused kernels (plan.h: chain_bf16_train_ok)
-    int ce = 0;                                      // ... the gradient w.r.t. e_s travels in p.dEpp[ce]
-    float* dE_last = use_b16 ? p.dEpp[0] : (L > 0 ? p.dZed[ne - 1] + (size_t)(L - 1) * es : p.dE0);
-    {
-        bool zero_e = !(grad_e_out && es) && es && L > 0;
-        if (zero_e && ((((uintptr_t)dE_last) & 15) != 0 || (es * 4) % 16 != 0)) {   // (odd E de: a block inside the dZ array is not 16-byte aligned)
-            MPN_HIP(hipMemsetAsync(dE_last, 0, es * 4, s));
-            zero_e = false;
+    // (model and the graph buffer are not null: mpnhip_backward_flags checks both before it constructs the object)
+    BackwardRun(const mpnhip_model& model, const float* x_, const float* edge_attr_, const float* grad_logits_, const float* grad_x_out_,
+                const float* grad_e_out_, float* grad_x_, float* grad_edge_attr_, int flags_, hipStream_t stream)
+        : m(model), x(x_), edge_attr(edge_attr_), grad_logits(grad_logits_), grad_x_out(grad_x_out_), grad_e_out(grad_e_out_),
+          grad_x(grad_x_), grad_edge_attr(grad_edge_attr_), flags(flags_), s(stream) {}
+    BackwardRun(const BackwardRun&) = delete;
+    BackwardRun& operator=(const BackwardRun&) = delete;
+
+    // the blocks of one step (batch index b_ = step - 1) in the forward's saves and in the kept dZ arrays
+    struct StepView {
+        int step, b_;
+        StepBufs b;
+        const float* x_s;
+        const float* e_s;
+        float* dZn;
+        float* dP;
+        float* dzfl[MPNHIP_MAX_LAYERS];
+        float* dzed[MPNHIP_MAX_LAYERS];
+        float* dzcl[MPNHIP_MAX_LAYERS];
+        float* dEc;   // gradient w.r.t. e_s (seeded by the later step / the caller)
+    };
+
+    // ---- checks, both plans, the modes (host only: nothing is launched) --------------------------------------------------------
+    // The environment switches are read on every call (tests flip them between calls).
+    int init(const void* graph_buf, int n_nodes, int64_t n_edges, void* fwd_workspace, size_t fwd_workspace_bytes, void* bwd_workspace,
+             size_t bwd_workspace_bytes) {
+        MPN_TRY(check_full(m, &d));
+        N = n_nodes;
+        E = n_edges;
+        MPN_CHECK_ARG(N >= 0 && E >= 0, "backward: negative sizes");
+        MPN_CHECK_ARG((x || N == 0) && (edge_attr || E == 0) && (grad_logits || E == 0), "backward: null tensor");
+        {
+            const mpnhip_mlp* all[] = {&m.enc_node, &m.enc_edge, &m.edge, &m.flow_in, &m.flow_out, &m.node, &m.classifier};
+            for (const mpnhip_mlp* q : all)
+                for (int i = 0; i < q->n_layers; ++i)
+                    MPN_CHECK_ARG(q->grad_weight[i] && q->grad_bias[i], "backward: null gradient buffer");
         }
-        const int64_t n0 = (int64_t)(z0_bytes / 16), n1 = zero_e ? (int64_t)(es * 4 / 16) : 0;   // (arena blocks: 256-byte multiples)
-        if (n0 + n1 > 0) {
-            int64_t blocks = (n0 + n1 + 255) / 256;
-            blocks = blocks > 4096 ? 4096 : blocks;
-            hipLaunchKernelGGL(k_zero_pair, dim3((unsigned)blocks), dim3(256), 0, s, reinterpret_cast<uint4*>(z0), n0, reinterpret_cast<uint4*>(dE_last), n1);
+        const size_t fneed = plan_forward(m, d, N, E, 1, fwd_workspace, &f);
+        MPN_CHECK_WORKSPACE_MSG("backward: forward workspace", " (must be the save_for_backward buffer)", fwd_workspace, fwd_workspace_bytes, fneed);
+        const size_t need = plan_backward(m, d, N, E, bwd_workspace, &p);
+        MPN_CHECK_WORKSPACE("backward", bwd_workspace, bwd_workspace_bytes, need);
+        c = {&p, m.precision == MPNHIP_PREC_FP32_SPLIT || m.precision == MPNHIP_PREC_FP32_WGSPLIT || m.precision == MPNHIP_PREC_BF16,
+             m.precision == MPNHIP_PREC_BF16, {}};
+        for (int i = 0; i < 2; ++i) c.wt_keep[i] = {p.wt_keep_floats[i] ? p.wt_keep[i] : nullptr, p.wt_keep_floats[i], false, p.wt_keep_floats[i] ? p.wt_keep16[i] : nullptr};
+        graph_layout(n_nodes, n_edges, &g, const_cast<void*>(graph_buf));
+        he = d.he; hn = d.hn; dn = d.dn; de = d.de; kx = d.kx; ke = d.ke; pw = d.pw; L = d.L;
+        xs = (size_t)N * dn;
+        es = (size_t)E * de;
+        dir_rr[0] = {nullptr, g.header + 4};
+        dir_rr[1] = {g.header + 4, g.header + 5};
+        ne = m.edge.n_layers;
+        nfl = m.flow_in.n_layers;
+        nc = m.classifier.n_layers;
+        sstride = (int64_t)(f.step_stride_bytes / sizeof(float));
+        x0 = f.x_hist;
+        e0 = f.e_hist;
+        if (f.b16 != p.b16) { set_error("backward: the forward workspace was saved in another mode (bf16 fused training %d vs %d)", (int)f.b16, (int)p.b16); return MPNHIP_ERR_ARG; }
+        use_b16 = p.b16 && E > 0 && L > 0;
+        use_chain = chain_shapes_ok(m, d) && E > 0 && L > 0;
+        bwd_split = use_chain && chain_split(m);
+        // The re-attached x0 does not change from step to step: its share of dX (and of the packed projection weight's gradient)
+        // comes from the SUM of the steps' dP, once, after the loop
+        hoist_x = d.nf == 2 && L > 1 && N > 0 && pw % 4 == 0 && dn % 4 == 0;
+        // The same for the re-attached e0 on the edge side (fused chain, whole 64-column passes: 32 < de <= 64): the gradient w.r.t. e0
+        // through the edge MLP's first layer and the e0 columns of that layer's weight gradient are ONE product each with
+        // S = sum_s dZ1_s after the loop -- 2 E he de MACs less in every step's backward chain and in every step's weight gradient
+        // (2 x 2.05 of ~31 GFLOP per step at cfg-B), for one pass over the kept dZ1 blocks.
+        // (the bf16 backward chain kernel never contracts the e0 columns: always hoisted there, also at L = 1)
+        hoist_e0 = use_b16 || (use_chain && d.ef == 2 && L > 1 && pad32(de) == 64 && he % 4 == 0 && de % 4 == 0);
+        // bf16-operand training: the per-node projections' weight gradient over bf16 ROWS -- dP_s rounded once by the scatter-add kernel that
+        // produces it, x_{s-1} from the forward's bf16 mirror -- on the LDS-DMA kernel in 256 x 256 output tiles (wgrad_rows16.hip)
+        // (f.xb_hist is filled under the forward's own run-time test: plan.h node_rows16_runtime, the one definition both sides use)
+        node16 = use_b16 && hoist_x && p.dP16 && node_rows16_runtime(f, m, d) && !getenv("MPNHIP_NO_NODE_ROWS16");
+        // (k_node_step32_bwd stages the weights in LDS: 128 pw + 8 KB + ... <= 64 KB, 16-byte aligned rows)
+        // wider models in the split precision: the same three launches as one MFMA kernel (node_chain.hip, node_chain_bwd_kernel)
+        fuse_node_chain_bwd = p.ncb_img && !c.bf16 && N > 0 && L > 1 && d.nf == 2;
+        fuse_node_bwd = !c.bf16 && dn == 32 && N <= 4096 && pw <= 384 && kx % 4 == 0 &&
+                        ((((uintptr_t)f.Wnode) | ((uintptr_t)m.node.weight[0])) & 15) == 0 && !getenv("MPNHIP_NO_NODE_FUSION");
+        return MPNHIP_OK;
+    }
+
+    // ---- seeds (caller's stream) -------------------------------------------------------------------------------------------------
+    int seed() {
+        // zeros: dX[0] (unless the caller seeds it) | dX0 | dE0 | gWnode, contiguous in the plan -- and, below, the seed of the gradient
+        // w.r.t. e_L: ONE launch of a plain kernel for both (hipMemsetAsync's fill was preceded by ~18 us of idle queue in every step
+        // of the cfg-D timeline; two of them opened every backward)
+        char* const z0 = reinterpret_cast<char*>(grad_x_out ? p.dX0 : p.dX[0]);
+        const size_t z0_bytes = (size_t)(reinterpret_cast<char*>(p.zero_end) - z0);
+        if (grad_x_out) MPN_HIP(hipMemcpyAsync(p.dX[0], grad_x_out, xs * 4, hipMemcpyDeviceToDevice, s));
+        // the gradient w.r.t. e_s lives in the LAST edge-layer dZ block of step s (it becomes that dZ once masked); bf16 chain: it
+        // travels in p.dEpp[ce].  (L == 0: dE_last aliases p.dE0)
+        float* dE_last = use_b16 ? p.dEpp[0] : (L > 0 ? p.dZed[ne - 1] + (size_t)(L - 1) * es : p.dE0);
+        {
+            bool zero_e = !(grad_e_out && es) && es && L > 0;
+            if (zero_e && ((((uintptr_t)dE_last) & 15) != 0 || (es * 4) % 16 != 0)) {   // (odd E de: a block inside the dZ array is not 16-byte aligned)
+                MPN_HIP(hipMemsetAsync(dE_last, 0, es * 4, s));
+                zero_e = false;
+            }
+            const int64_t n0 = (int64_t)(z0_bytes / 16), n1 = zero_e ? (int64_t)(es * 4 / 16) : 0;   // (arena blocks: 256-byte multiples)
+            if (n0 + n1 > 0) {
+                int64_t blocks = (n0 + n1 + 255) / 256;
+                blocks = blocks > 4096 ? 4096 : blocks;
+                hipLaunchKernelGGL(k_zero_pair, dim3((unsigned)blocks), dim3(256), 0, s, reinterpret_cast<uint4*>(z0), n0, reinterpret_cast<uint4*>(dE_last), n1);
+                MPN_LAUNCH_CHECK();
+            }
+        }
+        if (grad_e_out && es) {
+            hipLaunchKernelGGL(k_gather_rows, dim3((unsigned)((es + 255) / 256)), dim3(256), 0, s, grad_e_out, g.perm, dE_last, E, de);
             MPN_LAUNCH_CHECK();
         }
+        return MPNHIP_OK;
     }
-    if (grad_e_out && es) {
-        hipLaunchKernelGGL(k_gather_rows, dim3((unsigned)((es + 255) / 256)), dim3(256), 0, s, grad_e_out, g.perm, dE_last, E, de);
-        MPN_LAUNCH_CHECK();
-    }
-    const float* x0 = f.x_hist;
-    const float* e0 = f.e_hist;
-    if (use_b16) {
-        const float* f0[2] = {m.flow_out.weight[0], m.flow_in.weight[0]};
-        const float* f1[2] = {m.flow_out.weight[1], m.flow_in.weight[1]};
-        MPN_TRY(pack_chain_bf16_bwd(m.edge.weight[0], m.edge.in_dim, 2 * kx + de, m.edge.weight[1], m.classifier.weight[0], f0, m.flow_out.in_dim, kx, f1,
-                                    he, de, hn, dn, m.classifier.out_dims[0], p.cb16_img, s));
-    }
-    const bool use_chain = chain_shapes_ok(m, d) && E > 0 && L > 0;
-    const bool bwd_split = use_chain && chain_split(m);
-    if (use_chain) {
-        const int HE = pad32(he), DE = pad32(de), HN = pad32(hn), DN = pad32(dn);
-        const int KEp = d.ef * DE;
-        const mpnhip_mlp* fl[2] = {&m.flow_out, &m.flow_in};
-        const int ncol6 = KEp < 64 ? KEp : 64;
-        if (bwd_split) {
-            // the same logical images (rows = contraction index n, columns = k) as split images (edge_chain.hip, split8);
-            // recorded and packed by one launch (pack_split cannot fail once its sizes are valid: nothing returns before the flush)
-            SplitBatch sb;
-            for (int q = 0; q < 2; ++q) {
-                MPN_TRY(pack_split(fl[q]->weight[1], hn, 1, dn, hn, DN, HN, p.wf2p[q], &sb, s));
-                MPN_TRY(pack_split(fl[q]->weight[0] + kx, fl[q]->in_dim, 1, hn, de, HN, DE, p.wfep[q], &sb, s));
-            }
-            MPN_TRY(pack_split(m.classifier.weight[0], de, 1, m.classifier.out_dims[0], de, 32, DE, p.wc1p, &sb, s));
-            MPN_TRY(pack_split(m.edge.weight[1], he, 1, de, he, DE, HE, p.w2p, &sb, s));
-            for (int hlf = 0; hlf < d.ef; ++hlf) {
-                const int col0 = hlf * DE;
-                MPN_TRY(pack_split(m.edge.weight[0] + 2 * kx + hlf * de, m.edge.in_dim, 1, he, de, HE, DE,
-                                   p.w1ep + (int64_t)(col0 / 64) * HE * ncol6 * 3 / 2, &sb, s, ncol6 / 32, (col0 % 64) / 32));
-            }
-            MPN_TRY(split_batch_flush(&sb, s));
-        } else {
-            PackBatch pb;   // (the eight images as one launch)
-            for (int q = 0; q < 2; ++q) {
-                MPN_TRY(pack_padded(fl[q]->weight[1], hn, 0, dn, hn, p.wf2p[q], DN, HN, HN, 0, &pb, s));
-                MPN_TRY(pack_padded(fl[q]->weight[0], fl[q]->in_dim, kx, hn, de, p.wfep[q], HN, DE, DE, 0, &pb, s));
-            }
-            MPN_TRY(pack_padded(m.classifier.weight[0], de, 0, m.classifier.out_dims[0], de, p.wc1p, 32, DE, DE, 0, &pb, s));
-            MPN_TRY(pack_padded(m.edge.weight[1], he, 0, de, he, p.w2p, DE, HE, HE, 0, &pb, s));
-            // e-part columns of edge layer 0 as one image [HE][ncol6] per pass of <= 64 (padded) columns of [e0 | e_{s-1}]
-            // (the kernel streams whole rows of one pass image)
-            for (int hlf = 0; hlf < d.ef; ++hlf) {
-                const int col0 = hlf * DE;
-                MPN_TRY(pack_padded(m.edge.weight[0], m.edge.in_dim, 2 * kx + hlf * de, he, de,
-                                    p.w1ep + (int64_t)(col0 / 64) * HE * ncol6, HE, DE, ncol6, col0 % 64, &pb, s));
-            }
-            MPN_TRY(pack_batch_flush(&pb, s));
+
+    // ---- weight images of the chain kernels (caller's stream): bf16 pair images, the split or padded fp32 images, the node chain's ---
+    int pack_weights() {
+        if (use_b16) {
+            const float* f0[2] = {m.flow_out.weight[0], m.flow_in.weight[0]};
+            const float* f1[2] = {m.flow_out.weight[1], m.flow_in.weight[1]};
+            MPN_TRY(pack_chain_bf16_bwd(m.edge.weight[0], m.edge.in_dim, 2 * kx + de, m.edge.weight[1], m.classifier.weight[0], f0, m.flow_out.in_dim, kx, f1,
+                                        he, de, hn, dn, m.classifier.out_dims[0], p.cb16_img, s));
         }
+        if (use_chain) {
+            const int HE = pad32(he), DE = pad32(de), HN = pad32(hn), DN = pad32(dn);
+            const int KEp = d.ef * DE;
+            const mpnhip_mlp* fl[2] = {&m.flow_out, &m.flow_in};
+            const int ncol6 = KEp < 64 ? KEp : 64;
+            if (bwd_split) {
+                // the same logical images (rows = contraction index n, columns = k) as split images (edge_chain.hip, split8);
+                // recorded and packed by one launch (pack_split cannot fail once its sizes are valid: nothing returns before the flush)
+                SplitBatch sb;
+                for (int q = 0; q < 2; ++q) {
+                    MPN_TRY(pack_split(fl[q]->weight[1], hn, 1, dn, hn, DN, HN, p.wf2p[q], &sb, s));
+                    MPN_TRY(pack_split(fl[q]->weight[0] + kx, fl[q]->in_dim, 1, hn, de, HN, DE, p.wfep[q], &sb, s));
+                }
+                MPN_TRY(pack_split(m.classifier.weight[0], de, 1, m.classifier.out_dims[0], de, 32, DE, p.wc1p, &sb, s));
+                MPN_TRY(pack_split(m.edge.weight[1], he, 1, de, he, DE, HE, p.w2p, &sb, s));
+                for (int hlf = 0; hlf < d.ef; ++hlf) {
+                    const int col0 = hlf * DE;
+                    MPN_TRY(pack_split(m.edge.weight[0] + 2 * kx + hlf * de, m.edge.in_dim, 1, he, de, HE, DE,
+                                       p.w1ep + (int64_t)(col0 / 64) * HE * ncol6 * 3 / 2, &sb, s, ncol6 / 32, (col0 % 64) / 32));
+                }
+                MPN_TRY(split_batch_flush(&sb, s));
+            } else {
+                PackBatch pb;   // (the eight images as one launch)
+                for (int q = 0; q < 2; ++q) {
+                    MPN_TRY(pack_padded(fl[q]->weight[1], hn, 0, dn, hn, p.wf2p[q], DN, HN, HN, 0, &pb, s));
+                    MPN_TRY(pack_padded(fl[q]->weight[0], fl[q]->in_dim, kx, hn, de, p.wfep[q], HN, DE, DE, 0, &pb, s));
+                }
+                MPN_TRY(pack_padded(m.classifier.weight[0], de, 0, m.classifier.out_dims[0], de, p.wc1p, 32, DE, DE, 0, &pb, s));
+                MPN_TRY(pack_padded(m.edge.weight[1], he, 0, de, he, p.w2p, DE, HE, HE, 0, &pb, s));
+                // e-part columns of edge layer 0 as one image [HE][ncol6] per pass of <= 64 (padded) columns of [e0 | e_{s-1}]
+                // (the kernel streams whole rows of one pass image)
+                for (int hlf = 0; hlf < d.ef; ++hlf) {
+                    const int col0 = hlf * DE;
+                    MPN_TRY(pack_padded(m.edge.weight[0], m.edge.in_dim, 2 * kx + hlf * de, he, de,
+                                        p.w1ep + (int64_t)(col0 / 64) * HE * ncol6, HE, DE, ncol6, col0 % 64, &pb, s));
+                }
+                MPN_TRY(pack_batch_flush(&pb, s));
+            }
+        }
+        if (fuse_node_chain_bwd) {
+            node_chain_bwd_image_shorts(dn, pw, &ncb_off_wu);
+            MPN_TRY(pack_node_chain_bwd(m.node.weight[0], f.Wnode, dn, pw, kx, p.ncb_img, s));
+        }
+        return MPNHIP_OK;
+    }
+
+    // ---- the side stream and the groups of steps (host only) ---------------------------------------------------------------------
+    // The steps are finished from L down to 1.  Their weight gradients go in groups: as soon as a group's steps are done
+    // its batched products run on a side stream UNDER the remaining steps' chain kernels (which leave 120 of the 256
+    // CUs idle for the last third of their run at cfg-B); only the last group runs after the loop.  Groups are issued
+    // to ONE side stream in order, so they can share its slab buffer and their "+=" into the gradients stay ordered.
+    int schedule_groups() {
+        const bool want_fork = backward_forks(m) && side_stream_ready(&side) == MPNHIP_OK;
+        if (want_fork) side_lock.lock();
+        join.ss = side;
+        join.caller = s;
+        // Group sizes (in steps, first-finished group first).  The side stream is serial, so the last group should be the
+        // smallest: it starts only when the loop is over and what it has not finished when the encoder's backward ends is
+        // exposed.  Default for L = 12: 5 + 4 + 3; in general three groups with sizes ~ (5 : 4 : 3), two below six steps or when
+        // the products are small.
+        if (want_fork) {
+            if (L >= 6 && (double)E * dn * dn >= 3e8 && !c.wgrad_split) {
+                // (enough work per group to pay for a third round of ~30 launches: cfg-B 8e8; the reference's 32-d widths, 8e7 at
+                // cfg-C, do better with two groups -- measured 2.59 -> 2.48 ms.  The row-panel products of MPNHIP_PREC_FP32_SPLIT are
+                // two launches per group whatever its size, and a larger group needs fewer slabs per row: two groups there,
+                // cfg-B 5.27 -> 5.23 ms)
+                ngroups = 3;
+                gsize[0] = (int)((5 * L + 6) / 12);
+                gsize[2] = (int)(L / 4);
+                gsize[1] = (int)L - gsize[0] - gsize[2];
+            } else {
+                ngroups = 2;
+                gsize[0] = (int)(L - L / 2);
+                gsize[1] = (int)(L / 2);
+            }
+        } else {
+            gsize[0] = (int)L;
+        }
+        return MPNHIP_OK;
+    }
+    // group g (g = 0 is finished first) covers batches [group_lo(g), group_lo(g - 1)); group_lo(-1) = L
+    int group_lo(int g) const {
+        int lo = (int)L;
+        for (int i = 0; i <= g && i < ngroups; ++i) lo -= gsize[i];
+        return g < 0 ? (int)L : lo;
+    }
+    // steps of the last group (the one that runs after the loop): batches [0, last_group_steps())
+    int last_group_steps() const { return group_lo(ngroups - 2 < 0 ? -1 : ngroups - 2); }
+
+    // ---- one step of the loop, step = L .. 1 (caller's stream) -------------------------------------------------------------------
+    int step(int step_no) {
+        StepView v;
+        v.step = step_no;
+        v.b_ = step_no - 1;  // batch (block) index of this step
+        v.b = step_at(f, v.b_);
+        v.x_s = f.x_hist + xs * step_no;
+        v.e_s = f.e_hist + es * step_no;
+        v.dZn = p.dZn + (size_t)v.b_ * xs;
+        v.dP = p.dP + (size_t)v.b_ * N * pw;
+        for (int i = 0; i < nfl; ++i) v.dzfl[i] = p.dZfl[i] + (size_t)v.b_ * E * m.flow_in.out_dims[i];
+        for (int i = 0; i < ne; ++i) v.dzed[i] = p.dZed[i] + (size_t)v.b_ * E * m.edge.out_dims[i];
+        for (int i = 0; i + 1 < nc; ++i) v.dzcl[i] = p.dZcl[i] + (size_t)v.b_ * E * m.classifier.out_dims[i];
+        v.dEc = v.dzed[ne - 1];
+        MPN_TRY(node_update_bwd(v));
+        if (use_b16) MPN_TRY(edge_side_bf16(v));
+        else if (use_chain) MPN_TRY(edge_side_chain(v));
+        else if (E > 0) MPN_TRY(edge_side_unfused(v));
+        else MPN_HIP(hipMemsetAsync(v.dP, 0, (size_t)N * pw * 4, s));
+        MPN_TRY(projection_bwd(v));
+        cx ^= 1;
+        return MPNHIP_OK;
+    }
+
+    // A. node update  x_s = relu(AGG W^T + b)  (mpn.py:97-99)
+    int node_update_bwd(const StepView& v) {
+        if (!node_a_done) {
+            MPN_TRY(relu_mask(p.dX[cx], v.x_s, v.dZn, (int64_t)xs, s, dx_split ? p.dXh : nullptr));
+            const float* Wq[2] = {m.node.weight[0], nullptr};
+            MPN_TRY(act_grad(c, 1, v.dZn, dn, nullptr, Wq, 2 * dn, dn, 2 * dn, p.dAGG, 2 * dn, nullptr, nullptr, 0, 0, nullptr, N, s, 0));
+        }
+        dx_split = false;
+        node_a_done = false;
+        return MPNHIP_OK;
+    }
+
+    // B-E fused, bf16 operands: the mirror of the forward chain kernel (edge_chain_bf16_bwd.hip)
+    int edge_side_bf16(const StepView& v) {
+        const int b_ = v.b_;
+        const int hcw = m.classifier.out_dims[0];
+        EdgeChainBf16BwdArgs a = {};
+        a.E = (int)E; a.N = (int)N; a.agg = m.agg; a.first_step = v.step == 1 ? 1 : 0;
+        a.he = he; a.de = de; a.hn = hn; a.dn = dn; a.hc = hcw;
+        a.header = g.header; a.srow = g.srow; a.perm = g.perm; a.seg_ptr = g.seg_ptr;
+        a.dAGG = p.dAGG; a.mask = reinterpret_cast<const unsigned*>(v.b.MK); a.ARG = v.b.ARG;
+        a.dlog = grad_logits + (size_t)b_ * E;
+        a.dE_in = p.dEpp[ce];
+        a.dZM = w16(p.dZfl[1], (int64_t)b_ * E * dn); a.dZF = w16(p.dZfl[0], (int64_t)b_ * E * hn);
+        a.dZc = w16(p.dZcl[0], (int64_t)b_ * E * hcw); a.dZ2 = w16(p.dZed[1], (int64_t)b_ * E * de);
+        a.dZ1 = w16(p.dZed[0], (int64_t)b_ * E * he);
+        a.dE0 = p.dE0; a.dEprev = p.dEpp[ce ^ 1];
+        a.img_edge = p.cb16_img; a.img_cls = p.cb16_img + p.cb16_off_cls;
+        a.img_flow[0] = p.cb16_img + p.cb16_off_flow[0]; a.img_flow[1] = p.cb16_img + p.cb16_off_flow[1];
+        a.wc2 = m.classifier.weight[1];
+        prof_begin(PROF_CHAIN_BWD, s);
+        MPN_TRY(launch_edge_chain_bf16_bwd(a, s));
+        prof_end(PROF_CHAIN_BWD, s);
+        ce ^= 1;
+        // index_put_(accumulate) of the gathers x[flow_col] (mpn.py:87,93) and x[row], x[col] (mpn.py:69) over the bf16 dZ rows
+        const float* zf = reinterpret_cast<const float*>(a.dZF);
+        const float* z1 = reinterpret_cast<const float*>(a.dZ1);
+        float* const dP = v.dP;
+        unsigned short* const dP16 = node16 ? p.dP16 + (size_t)b_ * N * pw : nullptr;
+        const SegReduce2 c3[3] = {{zf, hn, g.cperm, g.cseg_ptr, 2 * (int)N, hn, dP, pw, (int)N, 2 * he, 2 * he + hn, 0, 0, dP16, pw},
+                                  {z1, he, nullptr, g.seg_ptr, (int)N, he, dP, pw, (int)N, 0, 0, 3, (int)N, dP16, pw},
+                                  {z1, he, g.cperm_all, g.cseg_all, (int)N, he, dP, pw, (int)N, he, he, 0, 0, dP16, pw}};
+        return segment_reduce_csr2_x3_bf16(c3, s);
+    }
+
+    // B-E fused: every activation-gradient product of the per-edge modules in one kernel
+    int edge_side_chain(const StepView& v) {
+        const int b_ = v.b_;
+        float* const dP = v.dP;
+        EdgeChainBwdArgs a = {};
+        a.E = (int)E; a.N = (int)N; a.agg = m.agg; a.first_step = v.step == 1 ? 1 : 0; a.cat_two = d.ef == 2 ? 1 : 0; a.split = bwd_split ? 1 : 0;
+        a.skip_e0 = hoist_e0 ? 1 : 0;
+        a.he = he; a.de = de; a.hn = hn; a.dn = dn; a.hc = m.classifier.out_dims[0];
+        a.header = g.header; a.srow = g.srow; a.perm = g.perm; a.seg_ptr = g.seg_ptr;
+        a.dAGG = p.dAGG; a.mask = reinterpret_cast<const unsigned*>(v.b.MK); a.ARG = v.b.ARG;
+        a.dlog = grad_logits + (size_t)b_ * E;
+        a.dE_io = v.dzed[1]; a.dZM = v.dzfl[1]; a.dZF = v.dzfl[0]; a.dZc = v.dzcl[0]; a.dZ1 = v.dzed[0];
+        a.dE0 = p.dE0; a.dEprev = v.step == 1 ? p.dE0 : p.dZed[ne - 1] + (size_t)(b_ - 1) * es;
+        a.wf2_out = p.wf2p[0]; a.wf2_in = p.wf2p[1]; a.wfe_out = p.wfep[0]; a.wfe_in = p.wfep[1];
+        a.wc1 = p.wc1p; a.wc2 = m.classifier.weight[1]; a.w2 = p.w2p; a.w1e = p.w1ep;
+        prof_begin(PROF_CHAIN_BWD, s);
+        MPN_TRY(launch_edge_chain_bwd(a, s));
+        prof_end(PROF_CHAIN_BWD, s);
+        // index_put_(accumulate) of the gathers x[flow_col] (mpn.py:87,93) and x[row], x[col] (mpn.py:69)
+        if (E >= 48 * N) {
+            // dense graphs (long segments): the three reductions as ONE launch of the block-per-segment kernel
+            const SegReduce2 c3[3] = {{v.dzfl[0], hn, g.cperm, g.cseg_ptr, 2 * (int)N, hn, dP, pw, (int)N, 2 * he, 2 * he + hn, 0, 0},
+                                      {v.dzed[0], he, g.rperm, g.rseg_ptr, (int)N, he, dP, pw, (int)N, 0, 0, 0, 0},
+                                      {v.dzed[0], he, g.cperm_all, g.cseg_all, (int)N, he, dP, pw, (int)N, he, he, 0, 0}};
+            MPN_TRY(segment_reduce_csr2_x3(c3, E, s));
+        } else {
+            // sparse graphs: ONE launch of the short-segment kernel for the three (segment.hip, k_segment_reduce3).
+            // (by row: the sorted order IS (direction, row), so a node's rows are three contiguous runs of the CSR -- no list)
+            const SegReduce2 c3[3] = {{v.dzfl[0], hn, g.cperm, g.cseg_ptr, 2 * (int)N, hn, dP, pw, (int)N, 2 * he, 2 * he + hn, 0, 0},
+                                      {v.dzed[0], he, nullptr, g.seg_ptr, (int)N, he, dP, pw, (int)N, 0, 0, 3, (int)N},
+                                      {v.dzed[0], he, g.cperm_all, g.cseg_all, (int)N, he, dP, pw, (int)N, he, he, 0, 0}};
+            MPN_TRY(segment_reduce_csr2_x3(c3, E, s));
+        }
+        return MPNHIP_OK;
+    }
+
+    // B-E one launch per product (any depth, any width)
+    int edge_side_unfused(const StepView& v) {
+        const int b_ = v.b_;
+        float* const dP = v.dP;
+        // ---- B. aggregation backward + ReLU of the last flow layer ---------------------------
+        {
+            int64_t tot = E * (dn / 4 > 0 && dn % 4 == 0 ? dn / 4 : dn);
+            hipLaunchKernelGGL(k_agg_bwd, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, p.dAGG, v.b.M, v.b.ARG,
+                               g.srow, g.seg_ptr, g.header, (int)N, E, dn, m.agg, dn != 1 ? 1 : 0, v.dzfl[nfl - 1]);
+            MPN_LAUNCH_CHECK();
+        }
+        // ---- C. flow MLPs (both directions grouped) -------------------------------------------
+        MPN_TRY(mlp_chain_backward(c, m.flow_out, &m.flow_in, v.dzfl, v.b.HF, dir_rr, E, s));
+        {
+            // layer 0:  Z = e_s Wfe^T + Pf[col];  dPf[n] = sum over the direction's edges with col == n
+            // (index_put_ of x[flow_col], mpn.py:87,93)
+            MPN_TRY(segment_reduce_csr2(v.dzfl[0], hn, g.cperm, g.cseg_ptr, 2 * (int)N, hn, dP, pw, (int)N, 2 * he, 2 * he + hn, s, E));
+            const float* Wq[2] = {m.flow_out.weight[0] + kx, m.flow_in.weight[0] + kx};
+            MPN_TRY(act_grad(c, 2, v.dzfl[0], hn, nullptr, Wq, m.flow_out.in_dim, hn, de, v.dEc, de, nullptr, nullptr, 0, 1, dir_rr, E, s));
+        }
+        // ---- D. classifier (mpn.py:377 -> :114); also applies the ReLU mask of e_s -------------
+        MPN_TRY(classifier_chain(v.b.HC, v.dzcl, grad_logits + (size_t)b_ * E, v.dEc, de != 1 ? v.e_s : nullptr));
+        // ---- E. edge MLP (EdgeModel, mpn.py:67-69) ----------------------------------------------
+        MPN_TRY(mlp_chain_backward(c, m.edge, nullptr, v.dzed, v.b.HE, nullptr, E, s));
+        {
+            // dPr / dPc: index_put_(accumulate) of x[row], x[col] (mpn.py:69)
+            MPN_TRY(segment_reduce_csr2(v.dzed[0], he, g.rperm, g.rseg_ptr, (int)N, he, dP, pw, (int)N, 0, 0, s, E));
+            MPN_TRY(segment_reduce_csr2(v.dzed[0], he, g.cperm_all, g.cseg_all, (int)N, he, dP, pw, (int)N, he, he, s, E));
+            // gradient w.r.t. [e0 | e_{s-1}]: one product, then split (e_0 IS e0 at step 1)
+            const float* Wa[2] = {m.edge.weight[0] + 2 * kx, nullptr};
+            MPN_TRY(act_grad(c, 1, v.dzed[0], he, nullptr, Wa, m.edge.in_dim, he, ke, p.dCat, ke, nullptr, nullptr, 0, 0, nullptr, E, s));
+            float* dEp = v.step == 1 ? p.dE0 : p.dZed[ne - 1] + (size_t)(b_ - 1) * es;
+            hipLaunchKernelGGL(k_split_cat, dim3((unsigned)((es + 255) / 256)), dim3(256), 0, s, p.dCat, E, de, d.ef == 2 ? 1 : 0,
+                               p.dE0, dEp, v.step == 1 ? 1 : 0);
+            MPN_LAUNCH_CHECK();
+        }
+        return MPNHIP_OK;
     }
 
     // activation-gradient chain of the classifier for one step: dz chain blocks in dzc[], final product
     // accumulated into dEdst and masked by `mask` (ReLU of the edge layer that produced ef)
-    auto classifier_chain = [&](float* const* HC, float* const* dzc, const float* dlog, float* dEdst, const float* mask) -> int {
+    int classifier_chain(float* const* HC, float* const* dzc, const float* dlog, float* dEdst, const float* mask) {
         if (E == 0) return MPNHIP_OK;
+        const mpnhip_mlp& cls = m.classifier;
         for (int i = nc - 1; i >= 0; --i) {
             const int n_out = cls.out_dims[i], k_in = layer_in(cls, i);
             const bool top = i == nc - 1;  // dZ of the last layer is grad_logits, [E, 1] in ORIGINAL order
@@ -847,26 +899,72 @@ extern "C" int mpnhip_backward_flags(const mpnhip_model* model, const void* grap
                                  k_in != 1 ? HC[i - 1] : nullptr, k_in, 0, nullptr, E, s));
         }
         return MPNHIP_OK;
-    };
+    }
 
-    // The re-attached x0 does not change from step to step: its share of dX (and of the packed projection weight's gradient)
-    // comes from the SUM of the steps' dP, once, after the loop
-    const bool hoist_x = d.nf == 2 && L > 1 && N > 0 && pw % 4 == 0 && dn % 4 == 0;
-    // The same for the re-attached e0 on the edge side (fused chain, whole 64-column passes: 32 < de <= 64): the gradient w.r.t. e0
-    // through the edge MLP's first layer and the e0 columns of that layer's weight gradient are ONE product each with
-    // S = sum_s dZ1_s after the loop -- 2 E he de MACs less in every step's backward chain and in every step's weight gradient
-    // (2 x 2.05 of ~31 GFLOP per step at cfg-B), for one pass over the kept dZ1 blocks.
-    // (the bf16 backward chain kernel never contracts the e0 columns: always hoisted there, also at L = 1)
-    const bool hoist_e0 = use_b16 || (use_chain && d.ef == 2 && L > 1 && pad32(de) == 64 && he % 4 == 0 && de % 4 == 0);
-    // bf16-operand training: the per-node projections' weight gradient over bf16 ROWS -- dP_s rounded once by the scatter-add kernel that
-    // produces it, x_{s-1} from the forward's bf16 mirror -- on the LDS-DMA kernel in 256 x 256 output tiles (wgrad_rows16.hip)
-    // (f.xb_hist is filled under the forward's own run-time test: plan.h node_rows16_runtime, the one definition both sides use)
-    const bool node16 = use_b16 && hoist_x && p.dP16 && node_rows16_runtime(f, m, d) && !getenv("MPNHIP_NO_NODE_ROWS16");
-    // bf16 rows: pointer `elems` unsigned shorts into a buffer the plans type as float*
-    auto u16 = [](const float* p0, int64_t elems) { return reinterpret_cast<const float*>(reinterpret_cast<const unsigned short*>(p0) + elems); };
-    // Weight gradients of the message-passing modules for steps b0+1 .. b0+nb: ONE batched split-row product per
-    // weight (batch index = step - 1).  Issued on `st` with the slab buffer `slab`.
-    auto mp_weight_grads = [&](int b0, int nb, hipStream_t st, float* slab) -> int {
+    // F. per-node projections  P = [x0 | x_{s-1}] Wnode^T
+    int projection_bwd(const StepView& v) {
+        const int step = v.step, b_ = v.b_;
+        float* const dP = v.dP;
+        float* dXp = p.dX[cx ^ 1];
+        if (hoist_x && step > 1 && fuse_node_bwd) {
+            // the reference's node width: this product, the previous step's ReLU mask and its node-update activation gradient
+            // in one launch (segment.hip, node_step32_bwd); the next iteration starts at the chain kernel
+            MPN_TRY(node_step32_bwd(dP, (int)N, pw, f.Wnode + dn, kx, f.x_hist + xs * (step - 1), m.node.weight[0],
+                                    p.dZn + (size_t)(b_ - 1) * xs, p.dAGG, s));
+            node_a_done = true;
+        } else if (hoist_x && step > 1 && fuse_node_chain_bwd) {
+            NodeChainBwdArgs a = {(int)N, dn, pw, dP, p.ncb_img, f.x_hist + xs * (step - 1), p.ncb_img + ncb_off_wu,
+                                  p.dZn + (size_t)(b_ - 1) * xs, p.dAGG};
+            MPN_TRY(launch_node_chain_bwd(a, s));
+            node_a_done = true;
+        } else if (hoist_x && step > 1 && pw % 8 == 0 && N * 2 < 2000000000 && !c.bf16) {
+            // [N, pw] x [pw, dn] is 157 tiles of 64 x 64 at cfg-B -- not enough blocks for 256 CUs and 34 K steps each: the two K
+            // halves run as the two groups of ONE grouped launch into dXp / dXh; the next step's ReLU-mask kernel adds them
+            GemmArgs a = {};
+            a.ngroups = 2; a.N = dn; a.K = pw / 2; a.ksplit = pw / 2; a.m_upper = 2 * N; a.small_tiles = 1;
+            for (int q = 0; q < 2; ++q) {
+                GemmGroup& G = a.g[q];
+                init_group(G);
+                G.A = dP + q * (pw / 2); G.lda = pw;
+                G.B = f.Wnode + dn + (size_t)q * (pw / 2) * kx; G.ldb = kx;
+                G.C = q == 0 ? dXp : p.dXh; G.ldc = dn;
+                G.m_static = N;
+            }
+            MPN_TRY(launch_gemm(a, A_KCONTIG, B_NCONTIG, MPNHIP_PREC_FP32, s));
+            dx_split = true;
+        } else if (hoist_x) {
+            // only the x_{s-1} columns here (at step 1 x_0 IS x0); the re-attached x0's columns take the SUM of the steps'
+            // dP after the loop: one product instead of L
+            const float* Wa[2] = {f.Wnode + dn, nullptr};
+            MPN_TRY(act_grad(c, 1, dP, pw, nullptr, Wa, kx, pw, dn, step == 1 ? p.dX0 : dXp, dn, nullptr, nullptr, 0, step == 1 ? 1 : 0,
+                             nullptr, N, s, 1));
+        } else {
+            const float* Wa[2] = {f.Wnode, nullptr};
+            MPN_TRY(act_grad(c, 1, dP, pw, nullptr, Wa, kx, pw, kx, p.dCat, kx, nullptr, nullptr, 0, 0, nullptr, N, s));
+            if (xs) {
+                hipLaunchKernelGGL(k_split_cat, dim3((unsigned)((xs + 255) / 256)), dim3(256), 0, s, p.dCat, N, dn, d.nf == 2 ? 1 : 0,
+                                   p.dX0, step == 1 ? p.dX0 : dXp, step == 1 ? 1 : 0);
+                MPN_LAUNCH_CHECK();
+            }
+        }
+        return MPNHIP_OK;
+    }
+
+    // ---- after step b + 1: a group of steps is complete -> its weight gradients to the side stream ------------------------------
+    int fork_group_if_due(int b) {
+        if (next_group < ngroups - 1 && b == group_lo(next_group)) {
+            MPN_HIP(hipEventRecord(side->ready, s));
+            MPN_HIP(hipStreamWaitEvent(side->stream, side->ready, 0));
+            join.forked = true;
+            MPN_TRY(mp_weight_grads(group_lo(next_group), group_lo(next_group - 1) - group_lo(next_group), side->stream, p.slab_side));
+            ++next_group;
+        }
+        return MPNHIP_OK;
+    }
+
+    // ---- weight gradients of the message-passing modules for steps b0+1 .. b0+nb: ONE batched split-row product per weight ------
+    // (batch index = step - 1).  Issued on `st` with the slab buffer `slab`.
+    int mp_weight_grads(int b0, int nb, hipStream_t st, float* slab) {
         if (nb <= 0) return MPNHIP_OK;
         const int64_t zb = b0;  // first batch
         // MPNHIP_PREC_FP32_SPLIT: the products below are recorded and run as ONE product launch + ONE slab-sum launch at the end
@@ -874,7 +972,6 @@ extern "C" int mpnhip_backward_flags(const mpnhip_model* model, const void* grap
         WpBatch wpb;
         if (c.wgrad_split) wp_batch_init(&wpb, p.slab_wp, p.slab_wp_floats, true, &st);
         WpBatch* const batch = c.wgrad_split ? &wpb : nullptr;
-        auto finish = [&]() -> int { return batch ? wp_batch_flush(batch, st) : MPNHIP_OK; };
         {   // node update Linear
             WgProduct w = {.dZ = {p.dZn + zb * xs, dn, (int64_t)xs}, .H = {f.step0.AGG + zb * sstride, 2 * dn, sstride}, .n_out = dn, .k_in = 2 * dn,
                            .ldw = 2 * dn, .rows = N, .nbatch = nb, .g = {{m.node.grad_weight[0], m.node.grad_bias[0]}}};
@@ -890,367 +987,154 @@ extern "C" int mpnhip_backward_flags(const mpnhip_model* model, const void* grap
             }
             MPN_TRY(weight_grad(c, slab, batch, w, st));
         }
-        if (use_b16) {
-            // every operand of these products is a bf16 row block: the backward chain kernel's dZ outputs, the forward chain kernel's
-            // saved activations and the bf16 mirror of e_hist (WpProduct::src16: loaded as they are, one product per k block)
-            const int hcw = cls.out_dims[0];
-            const int64_t ss16 = 2 * sstride;   // unsigned shorts between two steps' saved activations
-            const float* dZF = u16(p.dZfl[0], zb * E * hn); const float* dZM = u16(p.dZfl[1], zb * E * dn);
-            const float* dZ1 = u16(p.dZed[0], zb * E * he); const float* dZ2 = u16(p.dZed[1], zb * E * de);
-            const float* dZc = u16(p.dZcl[0], zb * E * hcw);
-            const float* H1 = u16(f.step0.HE[0], zb * ss16); const float* HFb = u16(f.step0.HF[0], zb * ss16);
-            const float* HCb = u16(f.step0.HC[0], zb * ss16);
-            const float* eb_new = reinterpret_cast<const float*>(f.eb_hist + es * (zb + 1));
-            const float* eb_prev = reinterpret_cast<const float*>(f.eb_hist + es * zb);
-            // flow layer 1, both directions
-            MPN_TRY(weight_grad(c, slab, batch, {.dZ = {dZM, dn, (int64_t)E * dn}, .H = {HFb, hn, ss16}, .n_out = dn, .k_in = hn, .ldw = hn, .rows = E,
-                                                 .nbatch = nb, .src16 = true,
-                                                 .g = {{m.flow_out.grad_weight[1], m.flow_out.grad_bias[1], dir_rr[0]},
-                                                       {m.flow_in.grad_weight[1], m.flow_in.grad_bias[1], dir_rr[1]}}}, st));
-            // flow layer 0: e' columns [kx, kx + de) and the bias (folded into P in the forward)
-            MPN_TRY(weight_grad(c, slab, batch, {.dZ = {dZF, hn, (int64_t)E * hn}, .H = {eb_new, de, (int64_t)es}, .n_out = hn, .k_in = de,
-                                                 .ldw = m.flow_out.in_dim, .rows = E, .nbatch = nb, .src16 = true,
-                                                 .g = {{m.flow_out.grad_weight[0] + kx, m.flow_out.grad_bias[0], dir_rr[0]},
-                                                       {m.flow_in.grad_weight[0] + kx, m.flow_in.grad_bias[0], dir_rr[1]}}}, st));
-            // classifier output layer [1 x hc]: dZ = grad_logits (fp32, original order -> perm), H = HC rows (bf16)
-            MPN_TRY(weight_grad(c, slab, batch, {.dZ = {grad_logits + zb * E, 1, (int64_t)E}, .dz_idx = g.perm, .H = {HCb, hcw, ss16}, .n_out = 1, .k_in = hcw,
-                                                 .ldw = hcw, .rows = E, .nbatch = nb, .src16 = true, .g = {{cls.grad_weight[1], cls.grad_bias[1]}}}, st));
-            // classifier layer 0
-            MPN_TRY(weight_grad(c, slab, batch, {.dZ = {dZc, hcw, (int64_t)E * hcw}, .H = {eb_new, de, (int64_t)es}, .n_out = hcw, .k_in = de, .ldw = de,
-                                                 .rows = E, .nbatch = nb, .src16 = true, .g = {{cls.grad_weight[0], cls.grad_bias[0]}}}, st));
-            // edge layer 1
-            MPN_TRY(weight_grad(c, slab, batch, {.dZ = {dZ2, de, (int64_t)E * de}, .H = {H1, he, ss16}, .n_out = de, .k_in = he, .ldw = he, .rows = E,
-                                                 .nbatch = nb, .src16 = true, .g = {{m.edge.grad_weight[1], m.edge.grad_bias[1]}}}, st));
-            // edge layer 0: the e_{s-1} columns and the bias (the e0 columns: one product with the summed dZ1 after the loop)
-            MPN_TRY(weight_grad(c, slab, batch, {.dZ = {dZ1, he, (int64_t)E * he}, .H = {eb_prev, de, (int64_t)es}, .n_out = he, .k_in = de,
-                                                 .ldw = m.edge.in_dim, .rows = E, .nbatch = nb, .src16 = true,
-                                                 .g = {{m.edge.grad_weight[0] + 2 * kx + de, m.edge.grad_bias[0]}}}, st));
-        } else if (E > 0) {
-            float* dzfl_b[MPNHIP_MAX_LAYERS];
-            float* dzed_b[MPNHIP_MAX_LAYERS];
-            float* hf_b[MPNHIP_MAX_LAYERS];
-            float* he_b[MPNHIP_MAX_LAYERS];
-            for (int i = 0; i < nfl; ++i) { dzfl_b[i] = p.dZfl[i] + zb * E * m.flow_in.out_dims[i]; hf_b[i] = f.step0.HF[i] ? f.step0.HF[i] + zb * sstride : nullptr; }
-            for (int i = 0; i < ne; ++i) { dzed_b[i] = p.dZed[i] + zb * E * m.edge.out_dims[i]; he_b[i] = f.step0.HE[i] ? f.step0.HE[i] + zb * sstride : nullptr; }
-            MPN_TRY(mlp_weight_grads(c, slab, batch, m.flow_out, &m.flow_in, dzfl_b, hf_b, sstride, dir_rr, E, nb, st));
-            // flow layer 0: e-part columns [kx, kx + de) and the bias (folded into P in the forward)
-            MPN_TRY(weight_grad(c, slab, batch, {.dZ = {dzfl_b[0], hn, (int64_t)E * hn}, .H = {f.e_hist + es * (zb + 1), de, (int64_t)es}, .n_out = hn,
-                                                 .k_in = de, .ldw = m.flow_out.in_dim, .rows = E, .nbatch = nb,
-                                                 .g = {{m.flow_out.grad_weight[0] + kx, m.flow_out.grad_bias[0], dir_rr[0]},
-                                                       {m.flow_in.grad_weight[0] + kx, m.flow_in.grad_bias[0], dir_rr[1]}}}, st));
-            // classifier: dZ of the last layer is grad_logits ([L, E], original order -> perm)
-            for (int i = nc - 1; i >= 0; --i) {
-                const int n_out = cls.out_dims[i], k_in = layer_in(cls, i);
-                const bool top = i == nc - 1;
-                Operand dz = top ? Operand{grad_logits + zb * E, 1, (int64_t)E} : Operand{p.dZcl[i] + zb * E * n_out, n_out, (int64_t)E * n_out};
-                Operand h = i == 0 ? Operand{f.e_hist + es * (zb + 1), de, (int64_t)es} : Operand{f.step0.HC[i - 1] + zb * sstride, k_in, sstride};
-                MPN_TRY(weight_grad(c, slab, batch, {.dZ = dz, .dz_idx = top ? g.perm : nullptr, .H = h, .n_out = n_out, .k_in = k_in, .ldw = k_in, .rows = E,
-                                                     .nbatch = nb, .g = {{cls.grad_weight[i], cls.grad_bias[i]}}}, st));
+        if (use_b16) MPN_TRY(edge_weight_grads_bf16(zb, nb, st, slab, batch));
+        else if (E > 0) MPN_TRY(edge_weight_grads_fp32(zb, nb, st, slab, batch));
+        // per-node projections (packed), accumulated into gWnode
+        if (hoist_x) {
+            // columns [dn, 2 dn) (the current features) here; the x0 columns are one product with the summed dP after the loop
+            WgProduct w = {.dZ = {p.dP + zb * N * pw, pw, (int64_t)N * pw}, .H = {f.x_hist + xs * zb, dn, (int64_t)xs}, .n_out = pw, .k_in = dn,
+                           .ldw = kx, .rows = N, .nbatch = nb, .g = {{p.gWnode + dn, nullptr}}};
+            if (node16) {
+                w.dZ.p = reinterpret_cast<const float*>(p.dP16 + zb * N * pw);
+                w.H.p = reinterpret_cast<const float*>(f.xb_hist + xs * zb);
+                w.src16 = true;
             }
-            MPN_TRY(mlp_weight_grads(c, slab, batch, m.edge, nullptr, dzed_b, he_b, sstride, nullptr, E, nb, st));
-            if (hoist_e0) {
-                // edge layer 0: the e_{s-1} columns [2kx + de, 2kx + 2 de) and the bias; the e0 columns follow after the loop
-                MPN_TRY(weight_grad(c, slab, batch, {.dZ = {dzed_b[0], he, (int64_t)E * he}, .H = {f.e_hist + es * zb, de, (int64_t)es}, .n_out = he,
-                                                     .k_in = de, .ldw = m.edge.in_dim, .rows = E, .nbatch = nb,
-                                                     .g = {{m.edge.grad_weight[0] + 2 * kx + de, m.edge.grad_bias[0]}}}, st));
-            } else {   // edge layer 0: e-part columns [2kx, 2kx + ke) = [e0 | e_{s-1}], and the bias
-                const bool two = d.ef == 2;
-                Operand h1 = two ? Operand{e0, de, 0} : Operand{f.e_hist + es * zb, de, (int64_t)es};
-                Operand h2 = two ? Operand{f.e_hist + es * zb, de, (int64_t)es} : Operand{nullptr, 0, 0};
-                MPN_TRY(weight_grad(c, slab, batch, {.dZ = {dzed_b[0], he, (int64_t)E * he}, .H = h1, .H2 = h2, .csplit = de, .n_out = he, .k_in = ke,
-                                                     .ldw = m.edge.in_dim, .rows = E, .nbatch = nb,
-                                                     .g = {{m.edge.grad_weight[0] + 2 * kx, m.edge.grad_bias[0]}}}, st));
-            }
-        }
-        {   // per-node projections (packed), accumulated into gWnode
-            if (hoist_x) {
-                // columns [dn, 2 dn) (the current features) here; the x0 columns are one product with the summed dP after the loop
-                WgProduct w = {.dZ = {p.dP + zb * N * pw, pw, (int64_t)N * pw}, .H = {f.x_hist + xs * zb, dn, (int64_t)xs}, .n_out = pw, .k_in = dn,
-                               .ldw = kx, .rows = N, .nbatch = nb, .g = {{p.gWnode + dn, nullptr}}};
-                if (node16) {
-                    w.dZ.p = reinterpret_cast<const float*>(p.dP16 + zb * N * pw);
-                    w.H.p = reinterpret_cast<const float*>(f.xb_hist + xs * zb);
-                    w.src16 = true;
-                }
-                MPN_TRY(weight_grad(c, slab, batch, w, st));
-                return finish();
-            }
+            MPN_TRY(weight_grad(c, slab, batch, w, st));
+        } else {
             const bool two = d.nf == 2;
             Operand h1 = two ? Operand{x0, dn, 0} : Operand{f.x_hist + xs * zb, dn, (int64_t)xs};
             Operand h2 = two ? Operand{f.x_hist + xs * zb, dn, (int64_t)xs} : Operand{nullptr, 0, 0};
             MPN_TRY(weight_grad(c, slab, batch, {.dZ = {p.dP + zb * N * pw, pw, (int64_t)N * pw}, .H = h1, .H2 = h2, .csplit = dn, .n_out = pw, .k_in = kx,
                                                  .ldw = kx, .rows = N, .nbatch = nb, .g = {{p.gWnode, nullptr}}}, st));
         }
-        return finish();
-    };
-    // The steps are finished from L down to 1.  Their weight gradients go in groups: as soon as a group's steps are done
-    // its batched products run on a side stream UNDER the remaining steps' chain kernels (which leave 120 of the 256
-    // CUs idle for the last third of their run at cfg-B); only the last group runs after the loop.  Groups are issued
-    // to ONE side stream in order, so they can share its slab buffer and their "+=" into the gradients stay ordered.
-    SideStream* side = nullptr;
-    const bool want_fork = backward_forks(m) && side_stream_ready(&side) == MPNHIP_OK;
-    std::unique_lock<std::mutex> side_lock(g_side_mu, std::defer_lock);
-    if (want_fork) side_lock.lock();
-    SideJoin join;
-    join.ss = side;
-    join.caller = s;
-    // Group sizes (in steps, first-finished group first).  The side stream is serial, so the last group should be the
-    // smallest: it starts only when the loop is over and what it has not finished when the encoder's backward ends is
-    // exposed.  Default for L = 12: 5 + 4 + 3; in general three groups with sizes ~ (5 : 4 : 3), two below six steps or when
-    // the products are small.
-    int gsize[3] = {0};
-    int ngroups = 1;
-    if (want_fork) {
-        if (L >= 6 && (double)E * dn * dn >= 3e8 && !c.wgrad_split) {
-            // (enough work per group to pay for a third round of ~30 launches: cfg-B 8e8; the reference's 32-d widths, 8e7 at
-            // cfg-C, do better with two groups -- measured 2.59 -> 2.48 ms.  The row-panel products of MPNHIP_PREC_FP32_SPLIT are
-            // two launches per group whatever its size, and a larger group needs fewer slabs per row: two groups there,
-            // cfg-B 5.27 -> 5.23 ms)
-            ngroups = 3;
-            gsize[0] = (int)((5 * L + 6) / 12);
-            gsize[2] = (int)(L / 4);
-            gsize[1] = (int)L - gsize[0] - gsize[2];
-        } else {
-            ngroups = 2;
-            gsize[0] = (int)(L - L / 2);
-            gsize[1] = (int)(L / 2);
-        }
-    } else {
-        gsize[0] = (int)L;
+        // the one flush of the recorded batch, whichever form the projection product took
+        return batch ? wp_batch_flush(batch, st) : MPNHIP_OK;
     }
-    // group g (g = 0 is finished first) covers batches [glo(g), glo(g - 1))
-    auto glo = [&](int g) {
-        int lo = (int)L;
-        for (int i = 0; i <= g && i < ngroups; ++i) lo -= gsize[i];
-        return g < 0 ? (int)L : lo;
-    };
-    int next_group = 0;
-    bool& forked = join.forked;
-    bool dx_split = false;   // the gradient w.r.t. x_s arrived as two K halves (p.dX[cx] + p.dXh)
-    bool node_a_done = false;   // dZn / dAGG of the coming step were already produced by node_step32_bwd
-    // (k_node_step32_bwd stages the weights in LDS: 128 pw + 8 KB + ... <= 64 KB, 16-byte aligned rows)
-    // wider models in the split precision: the same three launches as one MFMA kernel (node_chain.hip, node_chain_bwd_kernel)
-    const bool fuse_node_chain_bwd = p.ncb_img && !c.bf16 && N > 0 && L > 1 && d.nf == 2;
-    size_t ncb_off_wu = 0;
-    if (fuse_node_chain_bwd) {
-        node_chain_bwd_image_shorts(dn, pw, &ncb_off_wu);
-        MPN_TRY(pack_node_chain_bwd(m.node.weight[0], f.Wnode, dn, pw, kx, p.ncb_img, s));
+
+    // the per-edge modules' products of mp_weight_grads, bf16 chain: every operand of these products is a bf16 row block -- the backward
+    // chain kernel's dZ outputs, the forward chain kernel's saved activations and the bf16 mirror of e_hist (WpProduct::src16: loaded
+    // as they are, one product per k block)
+    int edge_weight_grads_bf16(int64_t zb, int nb, hipStream_t st, float* slab, WpBatch* batch) {
+        const mpnhip_mlp& cls = m.classifier;
+        const int hcw = cls.out_dims[0];
+        const int64_t ss16 = 2 * sstride;   // unsigned shorts between two steps' saved activations
+        const float* dZF = u16(p.dZfl[0], zb * E * hn); const float* dZM = u16(p.dZfl[1], zb * E * dn);
+        const float* dZ1 = u16(p.dZed[0], zb * E * he); const float* dZ2 = u16(p.dZed[1], zb * E * de);
+        const float* dZc = u16(p.dZcl[0], zb * E * hcw);
+        const float* H1 = u16(f.step0.HE[0], zb * ss16); const float* HFb = u16(f.step0.HF[0], zb * ss16);
+        const float* HCb = u16(f.step0.HC[0], zb * ss16);
+        const float* eb_new = reinterpret_cast<const float*>(f.eb_hist + es * (zb + 1));
+        const float* eb_prev = reinterpret_cast<const float*>(f.eb_hist + es * zb);
+        // flow layer 1, both directions
+        MPN_TRY(weight_grad(c, slab, batch, {.dZ = {dZM, dn, (int64_t)E * dn}, .H = {HFb, hn, ss16}, .n_out = dn, .k_in = hn, .ldw = hn, .rows = E,
+                                             .nbatch = nb, .src16 = true,
+                                             .g = {{m.flow_out.grad_weight[1], m.flow_out.grad_bias[1], dir_rr[0]},
+                                                   {m.flow_in.grad_weight[1], m.flow_in.grad_bias[1], dir_rr[1]}}}, st));
+        // flow layer 0: e' columns [kx, kx + de) and the bias (folded into P in the forward)
+        MPN_TRY(weight_grad(c, slab, batch, {.dZ = {dZF, hn, (int64_t)E * hn}, .H = {eb_new, de, (int64_t)es}, .n_out = hn, .k_in = de,
+                                             .ldw = m.flow_out.in_dim, .rows = E, .nbatch = nb, .src16 = true,
+                                             .g = {{m.flow_out.grad_weight[0] + kx, m.flow_out.grad_bias[0], dir_rr[0]},
+                                                   {m.flow_in.grad_weight[0] + kx, m.flow_in.grad_bias[0], dir_rr[1]}}}, st));
+        // classifier output layer [1 x hc]: dZ = grad_logits (fp32, original order -> perm), H = HC rows (bf16)
+        MPN_TRY(weight_grad(c, slab, batch, {.dZ = {grad_logits + zb * E, 1, (int64_t)E}, .dz_idx = g.perm, .H = {HCb, hcw, ss16}, .n_out = 1, .k_in = hcw,
+                                             .ldw = hcw, .rows = E, .nbatch = nb, .src16 = true, .g = {{cls.grad_weight[1], cls.grad_bias[1]}}}, st));
+        // classifier layer 0
+        MPN_TRY(weight_grad(c, slab, batch, {.dZ = {dZc, hcw, (int64_t)E * hcw}, .H = {eb_new, de, (int64_t)es}, .n_out = hcw, .k_in = de, .ldw = de,
+                                             .rows = E, .nbatch = nb, .src16 = true, .g = {{cls.grad_weight[0], cls.grad_bias[0]}}}, st));
+        // edge layer 1
+        MPN_TRY(weight_grad(c, slab, batch, {.dZ = {dZ2, de, (int64_t)E * de}, .H = {H1, he, ss16}, .n_out = de, .k_in = he, .ldw = he, .rows = E,
+                                             .nbatch = nb, .src16 = true, .g = {{m.edge.grad_weight[1], m.edge.grad_bias[1]}}}, st));
+        // edge layer 0: the e_{s-1} columns and the bias (the e0 columns: one product with the summed dZ1 after the loop)
+        MPN_TRY(weight_grad(c, slab, batch, {.dZ = {dZ1, he, (int64_t)E * he}, .H = {eb_prev, de, (int64_t)es}, .n_out = he, .k_in = de,
+                                             .ldw = m.edge.in_dim, .rows = E, .nbatch = nb, .src16 = true,
+                                             .g = {{m.edge.grad_weight[0] + 2 * kx + de, m.edge.grad_bias[0]}}}, st));
+        return MPNHIP_OK;
     }
-    const bool fuse_node_bwd = !c.bf16 && dn == 32 && N <= 4096 && pw <= 384 && kx % 4 == 0 &&
-                               ((((uintptr_t)f.Wnode) | ((uintptr_t)m.node.weight[0])) & 15) == 0 && !getenv("MPNHIP_NO_NODE_FUSION");
 
-    for (int step = L; step >= 1; --step) {
-        const int b_ = step - 1;  // batch (block) index of this step
-        const StepBufs b = step_at(f, b_);
-        const float* x_s = f.x_hist + xs * step;
-        const float* e_s = f.e_hist + es * step;
-        float* dXc = p.dX[cx];
-        float* dZn = p.dZn + (size_t)b_ * xs;
-        float* dP = p.dP + (size_t)b_ * N * pw;
-        float* dzfl[MPNHIP_MAX_LAYERS];
-        float* dzed[MPNHIP_MAX_LAYERS];
-        float* dzcl[MPNHIP_MAX_LAYERS];
-        for (int i = 0; i < nfl; ++i) dzfl[i] = p.dZfl[i] + (size_t)b_ * E * m.flow_in.out_dims[i];
-        for (int i = 0; i < ne; ++i) dzed[i] = p.dZed[i] + (size_t)b_ * E * m.edge.out_dims[i];
-        for (int i = 0; i + 1 < nc; ++i) dzcl[i] = p.dZcl[i] + (size_t)b_ * E * cls.out_dims[i];
-        float* dEc = dzed[ne - 1];  // gradient w.r.t. e_s (seeded by the later step / the caller)
+    // ... and over fp32 blocks (E > 0)
+    int edge_weight_grads_fp32(int64_t zb, int nb, hipStream_t st, float* slab, WpBatch* batch) {
+        const mpnhip_mlp& cls = m.classifier;
+        float* dzfl_b[MPNHIP_MAX_LAYERS];
+        float* dzed_b[MPNHIP_MAX_LAYERS];
+        float* hf_b[MPNHIP_MAX_LAYERS];
+        float* he_b[MPNHIP_MAX_LAYERS];
+        for (int i = 0; i < nfl; ++i) { dzfl_b[i] = p.dZfl[i] + zb * E * m.flow_in.out_dims[i]; hf_b[i] = f.step0.HF[i] ? f.step0.HF[i] + zb * sstride : nullptr; }
+        for (int i = 0; i < ne; ++i) { dzed_b[i] = p.dZed[i] + zb * E * m.edge.out_dims[i]; he_b[i] = f.step0.HE[i] ? f.step0.HE[i] + zb * sstride : nullptr; }
+        MPN_TRY(mlp_weight_grads(c, slab, batch, m.flow_out, &m.flow_in, dzfl_b, hf_b, sstride, dir_rr, E, nb, st));
+        // flow layer 0: e-part columns [kx, kx + de) and the bias (folded into P in the forward)
+        MPN_TRY(weight_grad(c, slab, batch, {.dZ = {dzfl_b[0], hn, (int64_t)E * hn}, .H = {f.e_hist + es * (zb + 1), de, (int64_t)es}, .n_out = hn,
+                                             .k_in = de, .ldw = m.flow_out.in_dim, .rows = E, .nbatch = nb,
+                                             .g = {{m.flow_out.grad_weight[0] + kx, m.flow_out.grad_bias[0], dir_rr[0]},
+                                                   {m.flow_in.grad_weight[0] + kx, m.flow_in.grad_bias[0], dir_rr[1]}}}, st));
+        // classifier: dZ of the last layer is grad_logits ([L, E], original order -> perm)
+        for (int i = nc - 1; i >= 0; --i) {
+            const int n_out = cls.out_dims[i], k_in = layer_in(cls, i);
+            const bool top = i == nc - 1;
+            Operand dz = top ? Operand{grad_logits + zb * E, 1, (int64_t)E} : Operand{p.dZcl[i] + zb * E * n_out, n_out, (int64_t)E * n_out};
+            Operand h = i == 0 ? Operand{f.e_hist + es * (zb + 1), de, (int64_t)es} : Operand{f.step0.HC[i - 1] + zb * sstride, k_in, sstride};
+            MPN_TRY(weight_grad(c, slab, batch, {.dZ = dz, .dz_idx = top ? g.perm : nullptr, .H = h, .n_out = n_out, .k_in = k_in, .ldw = k_in, .rows = E,
+                                                 .nbatch = nb, .g = {{cls.grad_weight[i], cls.grad_bias[i]}}}, st));
+        }
+        MPN_TRY(mlp_weight_grads(c, slab, batch, m.edge, nullptr, dzed_b, he_b, sstride, nullptr, E, nb, st));
+        if (hoist_e0) {
+            // edge layer 0: the e_{s-1} columns [2kx + de, 2kx + 2 de) and the bias; the e0 columns follow after the loop
+            MPN_TRY(weight_grad(c, slab, batch, {.dZ = {dzed_b[0], he, (int64_t)E * he}, .H = {f.e_hist + es * zb, de, (int64_t)es}, .n_out = he,
+                                                 .k_in = de, .ldw = m.edge.in_dim, .rows = E, .nbatch = nb,
+                                                 .g = {{m.edge.grad_weight[0] + 2 * kx + de, m.edge.grad_bias[0]}}}, st));
+        } else {   // edge layer 0: e-part columns [2kx, 2kx + ke) = [e0 | e_{s-1}], and the bias
+            const bool two = d.ef == 2;
+            Operand h1 = two ? Operand{e0, de, 0} : Operand{f.e_hist + es * zb, de, (int64_t)es};
+            Operand h2 = two ? Operand{f.e_hist + es * zb, de, (int64_t)es} : Operand{nullptr, 0, 0};
+            MPN_TRY(weight_grad(c, slab, batch, {.dZ = {dzed_b[0], he, (int64_t)E * he}, .H = h1, .H2 = h2, .csplit = de, .n_out = he, .k_in = ke,
+                                                 .ldw = m.edge.in_dim, .rows = E, .nbatch = nb,
+                                                 .g = {{m.edge.grad_weight[0] + 2 * kx, m.edge.grad_bias[0]}}}, st));
+        }
+        return MPNHIP_OK;
+    }
 
-        // ---- A. node update  x_s = relu(AGG W^T + b)  (mpn.py:97-99) ---------------------------
-        if (!node_a_done) {
-            MPN_TRY(relu_mask(dXc, x_s, dZn, (int64_t)xs, s, dx_split ? p.dXh : nullptr));
-            const float* Wq[2] = {m.node.weight[0], nullptr};
-            MPN_TRY(act_grad(c, 1, dZn, dn, nullptr, Wq, 2 * dn, dn, 2 * dn, p.dAGG, 2 * dn, nullptr, nullptr, 0, 0, nullptr, N, s, 0));
-        }
-        dx_split = false;
-        node_a_done = false;
-        if (use_b16) {
-            // ---- B-E fused, bf16 operands: the mirror of the forward chain kernel (edge_chain_bf16_bwd.hip) ------------------
-            const int hcw = cls.out_dims[0];
-            auto w16 = [&](float* p0, int64_t elems) { return reinterpret_cast<unsigned short*>(p0) + elems; };
-            EdgeChainBf16BwdArgs a = {};
-            a.E = (int)E; a.N = (int)N; a.agg = m.agg; a.first_step = step == 1 ? 1 : 0;
-            a.he = he; a.de = de; a.hn = hn; a.dn = dn; a.hc = hcw;
-            a.header = g.header; a.srow = g.srow; a.perm = g.perm; a.seg_ptr = g.seg_ptr;
-            a.dAGG = p.dAGG; a.mask = reinterpret_cast<const unsigned*>(b.MK); a.ARG = b.ARG;
-            a.dlog = grad_logits + (size_t)b_ * E;
-            a.dE_in = p.dEpp[ce];
-            a.dZM = w16(p.dZfl[1], (int64_t)b_ * E * dn); a.dZF = w16(p.dZfl[0], (int64_t)b_ * E * hn);
-            a.dZc = w16(p.dZcl[0], (int64_t)b_ * E * hcw); a.dZ2 = w16(p.dZed[1], (int64_t)b_ * E * de);
-            a.dZ1 = w16(p.dZed[0], (int64_t)b_ * E * he);
-            a.dE0 = p.dE0; a.dEprev = p.dEpp[ce ^ 1];
-            a.img_edge = p.cb16_img; a.img_cls = p.cb16_img + p.cb16_off_cls;
-            a.img_flow[0] = p.cb16_img + p.cb16_off_flow[0]; a.img_flow[1] = p.cb16_img + p.cb16_off_flow[1];
-            a.wc2 = cls.weight[1];
-            prof_begin(PROF_CHAIN_BWD, s);
-            MPN_TRY(launch_edge_chain_bf16_bwd(a, s));
-            prof_end(PROF_CHAIN_BWD, s);
-            ce ^= 1;
-            // index_put_(accumulate) of the gathers x[flow_col] (mpn.py:87,93) and x[row], x[col] (mpn.py:69) over the bf16 dZ rows
-            const float* zf = reinterpret_cast<const float*>(a.dZF);
-            const float* z1 = reinterpret_cast<const float*>(a.dZ1);
-            unsigned short* const dP16 = node16 ? p.dP16 + (size_t)b_ * N * pw : nullptr;
-            const SegReduce2 c3[3] = {{zf, hn, g.cperm, g.cseg_ptr, 2 * (int)N, hn, dP, pw, (int)N, 2 * he, 2 * he + hn, 0, 0, dP16, pw},
-                                      {z1, he, nullptr, g.seg_ptr, (int)N, he, dP, pw, (int)N, 0, 0, 3, (int)N, dP16, pw},
-                                      {z1, he, g.cperm_all, g.cseg_all, (int)N, he, dP, pw, (int)N, he, he, 0, 0, dP16, pw}};
-            MPN_TRY(segment_reduce_csr2_x3_bf16(c3, s));
-        } else if (use_chain) {
-            // ---- B-E fused: every activation-gradient product of the per-edge modules in one kernel --------
-            EdgeChainBwdArgs a = {};
-            a.E = (int)E; a.N = (int)N; a.agg = m.agg; a.first_step = step == 1 ? 1 : 0; a.cat_two = d.ef == 2 ? 1 : 0; a.split = bwd_split ? 1 : 0;
-            a.skip_e0 = hoist_e0 ? 1 : 0;
-            a.he = he; a.de = de; a.hn = hn; a.dn = dn; a.hc = cls.out_dims[0];
-            a.header = g.header; a.srow = g.srow; a.perm = g.perm; a.seg_ptr = g.seg_ptr;
-            a.dAGG = p.dAGG; a.mask = reinterpret_cast<const unsigned*>(b.MK); a.ARG = b.ARG;
-            a.dlog = grad_logits + (size_t)b_ * E;
-            a.dE_io = dzed[1]; a.dZM = dzfl[1]; a.dZF = dzfl[0]; a.dZc = dzcl[0]; a.dZ1 = dzed[0];
-            a.dE0 = p.dE0; a.dEprev = step == 1 ? p.dE0 : p.dZed[ne - 1] + (size_t)(b_ - 1) * es;
-            a.wf2_out = p.wf2p[0]; a.wf2_in = p.wf2p[1]; a.wfe_out = p.wfep[0]; a.wfe_in = p.wfep[1];
-            a.wc1 = p.wc1p; a.wc2 = cls.weight[1]; a.w2 = p.w2p; a.w1e = p.w1ep;
-            prof_begin(PROF_CHAIN_BWD, s);
-            MPN_TRY(launch_edge_chain_bwd(a, s));
-            prof_end(PROF_CHAIN_BWD, s);
-            // index_put_(accumulate) of the gathers x[flow_col] (mpn.py:87,93) and x[row], x[col] (mpn.py:69)
-            if (E >= 48 * N) {
-                // dense graphs (long segments): the three reductions as ONE launch of the block-per-segment kernel
-                const SegReduce2 c3[3] = {{dzfl[0], hn, g.cperm, g.cseg_ptr, 2 * (int)N, hn, dP, pw, (int)N, 2 * he, 2 * he + hn, 0, 0},
-                                          {dzed[0], he, g.rperm, g.rseg_ptr, (int)N, he, dP, pw, (int)N, 0, 0, 0, 0},
-                                          {dzed[0], he, g.cperm_all, g.cseg_all, (int)N, he, dP, pw, (int)N, he, he, 0, 0}};
-                MPN_TRY(segment_reduce_csr2_x3(c3, E, s));
-            } else {
-                // sparse graphs: ONE launch of the short-segment kernel for the three (segment.hip, k_segment_reduce3).
-                // (by row: the sorted order IS (direction, row), so a node's rows are three contiguous runs of the CSR -- no list)
-                const SegReduce2 c3[3] = {{dzfl[0], hn, g.cperm, g.cseg_ptr, 2 * (int)N, hn, dP, pw, (int)N, 2 * he, 2 * he + hn, 0, 0},
-                                          {dzed[0], he, nullptr, g.seg_ptr, (int)N, he, dP, pw, (int)N, 0, 0, 3, (int)N},
-                                          {dzed[0], he, g.cperm_all, g.cseg_all, (int)N, he, dP, pw, (int)N, he, he, 0, 0}};
-                MPN_TRY(segment_reduce_csr2_x3(c3, E, s));
-            }
-        } else if (E > 0) {
-            // ---- B. aggregation backward + ReLU of the last flow layer ---------------------------
-            {
-                int64_t tot = E * (dn / 4 > 0 && dn % 4 == 0 ? dn / 4 : dn);
-                hipLaunchKernelGGL(k_agg_bwd, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, p.dAGG, b.M, b.ARG,
-                                   g.srow, g.seg_ptr, g.header, (int)N, E, dn, m.agg, dn != 1 ? 1 : 0, dzfl[nfl - 1]);
-                MPN_LAUNCH_CHECK();
-            }
-            // ---- C. flow MLPs (both directions grouped) -------------------------------------------
-            MPN_TRY(mlp_chain_backward(c, m.flow_out, &m.flow_in, dzfl, b.HF, dir_rr, E, s));
-            {
-                // layer 0:  Z = e_s Wfe^T + Pf[col];  dPf[n] = sum over the direction's edges with col == n
-                // (index_put_ of x[flow_col], mpn.py:87,93)
-                MPN_TRY(segment_reduce_csr2(dzfl[0], hn, g.cperm, g.cseg_ptr, 2 * (int)N, hn, dP, pw, (int)N, 2 * he, 2 * he + hn, s, E));
-                const float* Wq[2] = {m.flow_out.weight[0] + kx, m.flow_in.weight[0] + kx};
-                MPN_TRY(act_grad(c, 2, dzfl[0], hn, nullptr, Wq, m.flow_out.in_dim, hn, de, dEc, de, nullptr, nullptr, 0, 1, dir_rr, E, s));
-            }
-            // ---- D. classifier (mpn.py:377 -> :114); also applies the ReLU mask of e_s -------------
-            MPN_TRY(classifier_chain(b.HC, dzcl, grad_logits + (size_t)b_ * E, dEc, de != 1 ? e_s : nullptr));
-            // ---- E. edge MLP (EdgeModel, mpn.py:67-69) ----------------------------------------------
-            MPN_TRY(mlp_chain_backward(c, m.edge, nullptr, dzed, b.HE, nullptr, E, s));
-            {
-                // dPr / dPc: index_put_(accumulate) of x[row], x[col] (mpn.py:69)
-                MPN_TRY(segment_reduce_csr2(dzed[0], he, g.rperm, g.rseg_ptr, (int)N, he, dP, pw, (int)N, 0, 0, s, E));
-                MPN_TRY(segment_reduce_csr2(dzed[0], he, g.cperm_all, g.cseg_all, (int)N, he, dP, pw, (int)N, he, he, s, E));
-                // gradient w.r.t. [e0 | e_{s-1}]: one product, then split (e_0 IS e0 at step 1)
-                const float* Wa[2] = {m.edge.weight[0] + 2 * kx, nullptr};
-                MPN_TRY(act_grad(c, 1, dzed[0], he, nullptr, Wa, m.edge.in_dim, he, ke, p.dCat, ke, nullptr, nullptr, 0, 0, nullptr, E, s));
-                float* dEp = step == 1 ? p.dE0 : p.dZed[ne - 1] + (size_t)(b_ - 1) * es;
-                hipLaunchKernelGGL(k_split_cat, dim3((unsigned)((es + 255) / 256)), dim3(256), 0, s, p.dCat, E, de, d.ef == 2 ? 1 : 0,
-                                   p.dE0, dEp, step == 1 ? 1 : 0);
-                MPN_LAUNCH_CHECK();
-            }
-        } else {
-            MPN_HIP(hipMemsetAsync(dP, 0, (size_t)N * pw * 4, s));
-        }
-        // ---- F. per-node projections  P = [x0 | x_{s-1}] Wnode^T -----------------------------------
-        {
-            float* dXp = p.dX[cx ^ 1];
-            if (hoist_x && step > 1 && fuse_node_bwd) {
-                // the reference's node width: this product, the previous step's ReLU mask and its node-update activation gradient
-                // in one launch (segment.hip, node_step32_bwd); the next iteration starts at the chain kernel
-                MPN_TRY(node_step32_bwd(dP, (int)N, pw, f.Wnode + dn, kx, f.x_hist + xs * (step - 1), m.node.weight[0],
-                                        p.dZn + (size_t)(b_ - 1) * xs, p.dAGG, s));
-                node_a_done = true;
-            } else if (hoist_x && step > 1 && fuse_node_chain_bwd) {
-                NodeChainBwdArgs a = {(int)N, dn, pw, dP, p.ncb_img, f.x_hist + xs * (step - 1), p.ncb_img + ncb_off_wu,
-                                      p.dZn + (size_t)(b_ - 1) * xs, p.dAGG};
-                MPN_TRY(launch_node_chain_bwd(a, s));
-                node_a_done = true;
-            } else if (hoist_x && step > 1 && pw % 8 == 0 && N * 2 < 2000000000 && !c.bf16) {
-                // [N, pw] x [pw, dn] is 157 tiles of 64 x 64 at cfg-B -- not enough blocks for 256 CUs and 34 K steps each: the two K
-                // halves run as the two groups of ONE grouped launch into dXp / dXh; the next step's ReLU-mask kernel adds them
-                GemmArgs a = {};
-                a.ngroups = 2; a.N = dn; a.K = pw / 2; a.ksplit = pw / 2; a.m_upper = 2 * N; a.small_tiles = 1;
-                for (int q = 0; q < 2; ++q) {
-                    GemmGroup& G = a.g[q];
-                    init_group(G);
-                    G.A = dP + q * (pw / 2); G.lda = pw;
-                    G.B = f.Wnode + dn + (size_t)q * (pw / 2) * kx; G.ldb = kx;
-                    G.C = q == 0 ? dXp : p.dXh; G.ldc = dn;
-                    G.m_static = N;
-                }
-                MPN_TRY(launch_gemm(a, A_KCONTIG, B_NCONTIG, MPNHIP_PREC_FP32, s));
-                dx_split = true;
-            } else if (hoist_x) {
-                // only the x_{s-1} columns here (at step 1 x_0 IS x0); the re-attached x0's columns take the SUM of the steps'
-                // dP after the loop: one product instead of L
-                const float* Wa[2] = {f.Wnode + dn, nullptr};
-                MPN_TRY(act_grad(c, 1, dP, pw, nullptr, Wa, kx, pw, dn, step == 1 ? p.dX0 : dXp, dn, nullptr, nullptr, 0, step == 1 ? 1 : 0,
-                                 nullptr, N, s, 1));
-            } else {
-                const float* Wa[2] = {f.Wnode, nullptr};
-                MPN_TRY(act_grad(c, 1, dP, pw, nullptr, Wa, kx, pw, kx, p.dCat, kx, nullptr, nullptr, 0, 0, nullptr, N, s));
-                if (xs) {
-                    hipLaunchKernelGGL(k_split_cat, dim3((unsigned)((xs + 255) / 256)), dim3(256), 0, s, p.dCat, N, dn, d.nf == 2 ? 1 : 0,
-                                       p.dX0, step == 1 ? p.dX0 : dXp, step == 1 ? 1 : 0);
-                    MPN_LAUNCH_CHECK();
-                }
-            }
-        }
-        cx ^= 1;
-        if (next_group < ngroups - 1 && b_ == glo(next_group)) {
+    // ---- after the loop: the last group of steps goes to the side stream (in order behind the earlier groups), under the sums /
+    // products of the hoisted shares and the encoder's backward that follow on the caller's stream
+    int fork_last_group() {
+        if (L > 0 && join.forked) {
             MPN_HIP(hipEventRecord(side->ready, s));
             MPN_HIP(hipStreamWaitEvent(side->stream, side->ready, 0));
-            forked = true;
-            MPN_TRY(mp_weight_grads(glo(next_group), glo(next_group - 1) - glo(next_group), side->stream, p.slab_side));
-            ++next_group;
+            MPN_TRY(mp_weight_grads(0, last_group_steps(), side->stream, p.slab_side));
         }
+        return MPNHIP_OK;
     }
 
-    // The last group of steps goes to the side stream as soon as the loop is over (in order behind the earlier groups), under the
-    // sums / products of the hoisted shares and the encoder's backward below.
-    const int last_n = glo(ngroups - 2 < 0 ? -1 : ngroups - 2);
-    if (L > 0 && forked) {
-        MPN_HIP(hipEventRecord(side->ready, s));
-        MPN_HIP(hipStreamWaitEvent(side->stream, side->ready, 0));
-        MPN_TRY(mp_weight_grads(0, last_n, side->stream, p.slab_side));
-    }
+    // ---- where the tail's products (hoisted shares, encoder layers) are recorded and where the batch will run (host only) --------
     // MPNHIP_PREC_FP32_SPLIT with a side stream: the weight-gradient products of this tail (hoisted shares, encoder layers) are
     // leaves -- nothing on the caller's stream reads their results -- so they are RECORDED here and run as ONE batch at the end
-    // (flush_tail below), while the caller's stream goes on with the activation-gradient chain (the encoder chains keep every dZ
+    // (flush_tail), while the caller's stream goes on with the activation-gradient chain (the encoder chains keep every dZ
     // block of <= 3 layers: BwdPlan::T / Tn).  With MPNHIP_BWD_DEFER_SIDE_JOIN the encoder's products stay on the caller's stream
     // as separate launches and only the hoisted shares are batched: there the side stream's order must end with the
     // message-passing modules' gradients (a trainer puts their all-reduce behind it while the encoder's backward still runs).
-    WpBatch tailb;
-    const bool defer_tail = c.wgrad_split && L > 0 && forked;
-    const bool defer_encoder = defer_tail && !(flags & MPNHIP_BWD_DEFER_SIDE_JOIN) && m.enc_node.n_layers <= 3 && m.enc_edge.n_layers <= 3;
-    if (defer_tail) wp_batch_init(&tailb, p.slab_tail, p.slab_tail_floats, true, nullptr);   // (no stream yet: a full tail batch is not rolled)
-    // where the tail's products are recorded: the hoisted shares' while the batch exists, the encoder's only when it stays to the end
-    WpBatch* const tail_hoist = defer_tail ? &tailb : nullptr;
-    WpBatch* const tail_enc = defer_encoder ? &tailb : nullptr;
-    // flush_tail runs what was recorded (its "+=" go to gradient columns disjoint from the groups': it may run
-    // beside the last group of steps).  Where it runs.  With the encoder's products deferred to the end anyway (no MPNHIP_BWD_DEFER_SIDE_JOIN) it runs on the
-    // CALLER's stream itself, then the join, the unpacking and whatever the caller enqueues next: no hop ahead of the batch (event
-    // record -> wait: 10 - 18 us each) and one instead of two behind it.  Same-box A-B, three runs each, second side stream / caller's
-    // stream / first side stream: cfg-B 4.94 - 5.00 / 4.90 - 4.93 / 4.92 - 4.97 ms, cfg-C 1.76 - 1.78 / 1.72 - 1.74 / 1.80 - 1.82, cfg-E 33.5 - 33.6 /
-    // 33.6 / 34.0, cfg-D 0.494 / 0.444 / 0.470 -- the second stream was round 4's answer to a tail of ~0.3 ms behind the last group; with
-    // the launches' blocks dispatched longest first it no longer pays.  A trainer's path (MPNHIP_BWD_DEFER_SIDE_JOIN: the hoisted
-    // shares' products run early, the message-passing gradients' collective follows on the first side stream) keeps the second stream
-    // on large graphs -- the first side stream is ordered behind it, so the unpacking and the collective that follow there see both.
-    const bool tail_beside = (flags & MPNHIP_BWD_DEFER_SIDE_JOIN) && (double)E * dn >= 1e6;
-    const bool tail_inline = defer_encoder && !tail_beside;
-    Rows16Later later16;
-    later16.pool = p.enc16;
-    later16.pool_elems = p.enc16_elems;
-    auto flush_tail = [&]() -> int {
+    int plan_tail() {
+        defer_tail = c.wgrad_split && L > 0 && join.forked;
+        defer_encoder = defer_tail && !(flags & MPNHIP_BWD_DEFER_SIDE_JOIN) && m.enc_node.n_layers <= 3 && m.enc_edge.n_layers <= 3;
+        if (defer_tail) wp_batch_init(&tailb, p.slab_tail, p.slab_tail_floats, true, nullptr);   // (no stream yet: a full tail batch is not rolled)
+        // where the tail's products are recorded: the hoisted shares' while the batch exists, the encoder's only when it stays to the end
+        tail_hoist = defer_tail ? &tailb : nullptr;
+        tail_enc = defer_encoder ? &tailb : nullptr;
+        // flush_tail runs what was recorded (its "+=" go to gradient columns disjoint from the groups': it may run
+        // beside the last group of steps).  Where it runs.  With the encoder's products deferred to the end anyway (no MPNHIP_BWD_DEFER_SIDE_JOIN) it runs on the
+        // CALLER's stream itself, then the join, the unpacking and whatever the caller enqueues next: no hop ahead of the batch (event
+        // record -> wait: 10 - 18 us each) and one instead of two behind it.  Same-box A-B, three runs each, second side stream / caller's
+        // stream / first side stream: cfg-B 4.94 - 5.00 / 4.90 - 4.93 / 4.92 - 4.97 ms, cfg-C 1.76 - 1.78 / 1.72 - 1.74 / 1.80 - 1.82, cfg-E 33.5 - 33.6 /
+        // 33.6 / 34.0, cfg-D 0.494 / 0.444 / 0.470 -- the second stream was round 4's answer to a tail of ~0.3 ms behind the last group; with
+        // the launches' blocks dispatched longest first it no longer pays.  A trainer's path (MPNHIP_BWD_DEFER_SIDE_JOIN: the hoisted
+        // shares' products run early, the message-passing gradients' collective follows on the first side stream) keeps the second stream
+        // on large graphs -- the first side stream is ordered behind it, so the unpacking and the collective that follow there see both.
+        tail_beside = (flags & MPNHIP_BWD_DEFER_SIDE_JOIN) && (double)E * dn >= 1e6;
+        tail_inline = defer_encoder && !tail_beside;
+        later16.pool = p.enc16;
+        later16.pool_elems = p.enc16_elems;
+        return MPNHIP_OK;
+    }
+
+    // runs the tail batch: on the caller's stream (tail_inline), on the second side stream (tail_beside) or on the first
+    int flush_tail() {
         if (!defer_tail) return MPNHIP_OK;
         hipStream_t st = tail_inline ? s : tail_beside ? side->stream2 : side->stream;
         if (!tail_inline) {
@@ -1265,45 +1149,52 @@ extern "C" int mpnhip_backward_flags(const mpnhip_model* model, const void* grap
             MPN_HIP(hipStreamWaitEvent(side->stream, side->done2, 0));
         }
         return MPNHIP_OK;
-    };
-    if (hoist_x) {
-        const int64_t n4 = N * pw / 4;
-        hipLaunchKernelGGL(k_sum_blocks, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, p.dP, N * pw, (int)L, n4, p.dPsum);
-        MPN_LAUNCH_CHECK();
-        const float* Wa[2] = {f.Wnode, nullptr};
-        MPN_TRY(act_grad(c, 1, p.dPsum, pw, nullptr, Wa, kx, pw, dn, p.dX0, dn, nullptr, nullptr, 0, 1, nullptr, N, s));
-        // ... and the x0 columns [0, dn) of the packed projection weight's gradient: (sum of dP)^T x0 (disjoint from the columns the
-        // side stream accumulates; main-stream slab buffer)
-        WgProduct w = {.dZ = {p.dPsum, pw, 0}, .H = {x0, dn, 0}, .n_out = pw, .k_in = dn, .ldw = kx, .rows = N, .nbatch = 1, .g = {{p.gWnode, nullptr}}};
-        if (node16) {
-            MPN_TRY(to_bf16_rows(p.dPsum, p.dPsum16, N * pw, s));
-            w.dZ.p = reinterpret_cast<const float*>(p.dPsum16);
-            w.H.p = reinterpret_cast<const float*>(f.xb_hist);
-            w.src16 = true;
+    }
+
+    // ---- the re-attached x0 / e0 shares, once, from the sums over the steps (caller's stream; their weight-gradient products go
+    // to the tail batch when there is one) -----------------------------------------------------------------------------------------
+    int hoisted_shares() {
+        if (hoist_x) {
+            const int64_t n4 = N * pw / 4;
+            hipLaunchKernelGGL(k_sum_blocks, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, p.dP, N * pw, (int)L, n4, p.dPsum);
+            MPN_LAUNCH_CHECK();
+            const float* Wa[2] = {f.Wnode, nullptr};
+            MPN_TRY(act_grad(c, 1, p.dPsum, pw, nullptr, Wa, kx, pw, dn, p.dX0, dn, nullptr, nullptr, 0, 1, nullptr, N, s));
+            // ... and the x0 columns [0, dn) of the packed projection weight's gradient: (sum of dP)^T x0 (disjoint from the columns the
+            // side stream accumulates; main-stream slab buffer)
+            WgProduct w = {.dZ = {p.dPsum, pw, 0}, .H = {x0, dn, 0}, .n_out = pw, .k_in = dn, .ldw = kx, .rows = N, .nbatch = 1, .g = {{p.gWnode, nullptr}}};
+            if (node16) {
+                MPN_TRY(to_bf16_rows(p.dPsum, p.dPsum16, N * pw, s));
+                w.dZ.p = reinterpret_cast<const float*>(p.dPsum16);
+                w.H.p = reinterpret_cast<const float*>(f.xb_hist);
+                w.src16 = true;
+            }
+            MPN_TRY(weight_grad(c, p.slab, tail_hoist, w, s));
         }
-        MPN_TRY(weight_grad(c, p.slab, tail_hoist, w, s));
+        if (hoist_e0) {
+            // S = sum_s dZ1_s (the blocks are all kept for the weight gradients);  dE0 += S W1[:, e0 columns];  dW1[:, e0 columns] += S^T e0
+            const int64_t n4 = E * he / 4;
+            // bf16-operand training: both consumers of S round it to bf16 as they stage it, so S itself is kept as bf16 rows (rounded once,
+            // the same values) and its partner e0 is the forward's bf16 mirror: half the bytes written and read twice, the GEMM reads
+            // bf16 rows, the weight-gradient product runs on the bf16-row kernels
+            const bool s16 = use_b16 && f.eb_hist && he % 8 == 0 && de % 8 == 0;
+            if (s16) hipLaunchKernelGGL(k_sum_blocks_bf16<true>, dim3((unsigned)((n4 / 2 + 255) / 256)), dim3(256), 0, s, reinterpret_cast<const unsigned short*>(p.dZed[0]),
+                                        E * he, (int)L, n4 / 2, p.dZ1sum);
+            else if (use_b16) hipLaunchKernelGGL(k_sum_blocks_bf16<false>, dim3((unsigned)((n4 / 2 + 255) / 256)), dim3(256), 0, s, reinterpret_cast<const unsigned short*>(p.dZed[0]),
+                                                 E * he, (int)L, n4 / 2, p.dZ1sum);   // (he % 8 == 0: chain_bf16_train_ok)
+            else hipLaunchKernelGGL(k_sum_blocks, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, p.dZed[0], E * he, (int)L, n4, p.dZ1sum);
+            MPN_LAUNCH_CHECK();
+            const float* Wa[2] = {m.edge.weight[0] + 2 * kx, nullptr};
+            MPN_TRY(act_grad(c, 1, p.dZ1sum, he, nullptr, Wa, m.edge.in_dim, he, de, p.dE0, de, nullptr, nullptr, 0, 1, nullptr, E, s, -1, s16));
+            MPN_TRY(weight_grad(c, p.slab, tail_hoist, {.dZ = {p.dZ1sum, he, 0}, .H = {s16 ? reinterpret_cast<const float*>(f.eb_hist) : e0, de, 0}, .n_out = he,
+                                                        .k_in = de, .ldw = m.edge.in_dim, .rows = E, .nbatch = 1, .src16 = s16,
+                                                        .g = {{m.edge.grad_weight[0] + 2 * kx, nullptr}}}, s));
+        }
+        return MPNHIP_OK;
     }
-    if (hoist_e0) {
-        // S = sum_s dZ1_s (the blocks are all kept for the weight gradients);  dE0 += S W1[:, e0 columns];  dW1[:, e0 columns] += S^T e0
-        const int64_t n4 = E * he / 4;
-        // bf16-operand training: both consumers of S round it to bf16 as they stage it, so S itself is kept as bf16 rows (rounded once,
-        // the same values) and its partner e0 is the forward's bf16 mirror: half the bytes written and read twice, the GEMM reads
-        // bf16 rows, the weight-gradient product runs on the bf16-row kernels
-        const bool s16 = use_b16 && f.eb_hist && he % 8 == 0 && de % 8 == 0;
-        if (s16) hipLaunchKernelGGL(k_sum_blocks_bf16<true>, dim3((unsigned)((n4 / 2 + 255) / 256)), dim3(256), 0, s, reinterpret_cast<const unsigned short*>(p.dZed[0]),
-                                    E * he, (int)L, n4 / 2, p.dZ1sum);
-        else if (use_b16) hipLaunchKernelGGL(k_sum_blocks_bf16<false>, dim3((unsigned)((n4 / 2 + 255) / 256)), dim3(256), 0, s, reinterpret_cast<const unsigned short*>(p.dZed[0]),
-                                             E * he, (int)L, n4 / 2, p.dZ1sum);   // (he % 8 == 0: chain_bf16_train_ok)
-        else hipLaunchKernelGGL(k_sum_blocks, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, p.dZed[0], E * he, (int)L, n4, p.dZ1sum);
-        MPN_LAUNCH_CHECK();
-        const float* Wa[2] = {m.edge.weight[0] + 2 * kx, nullptr};
-        MPN_TRY(act_grad(c, 1, p.dZ1sum, he, nullptr, Wa, m.edge.in_dim, he, de, p.dE0, de, nullptr, nullptr, 0, 1, nullptr, E, s, -1, s16));
-        MPN_TRY(weight_grad(c, p.slab, tail_hoist, {.dZ = {p.dZ1sum, he, 0}, .H = {s16 ? reinterpret_cast<const float*>(f.eb_hist) : e0, de, 0}, .n_out = he,
-                                                    .k_in = de, .ldw = m.edge.in_dim, .rows = E, .nbatch = 1, .src16 = s16,
-                                                    .g = {{m.edge.grad_weight[0] + 2 * kx, nullptr}}}, s));
-    }
-    auto unpack_node_grads = [&](hipStream_t us) -> int {
-        // the packed node-projection gradient [W1r; W1c; Wfo_x; Wfi_x] back into the layers' grads (their biases were handled above)
+
+    // the packed node-projection gradient [W1r; W1c; Wfo_x; Wfi_x] back into the layers' grads (their biases were handled above)
+    int unpack_node_grads(hipStream_t us) {
         struct { float* dst; int64_t ld; int c0; int r0; int rows; } parts[4] = {
             {m.edge.grad_weight[0], m.edge.in_dim, 0, 0, he},
             {m.edge.grad_weight[0], m.edge.in_dim, kx, he, he},
@@ -1320,10 +1211,12 @@ extern "C" int mpnhip_backward_flags(const mpnhip_model* model, const void* grap
             MPN_LAUNCH_CHECK();
         }
         return MPNHIP_OK;
-    };
-    bool unpack_pending = false;
-    if (L > 0) {
-        if (forked) {
+    }
+
+    // ---- the end of the message-passing modules' gradients: the unpacking -- now, or pending behind the tail batch -----------------
+    int finish_message_passing() {
+        if (L == 0) return classifier_only();
+        if (join.forked) {
             // (the unpacking follows on the side stream as well: with it every gradient of the message-passing modules and of
             // the classifier is final IN SIDE-STREAM ORDER, while the caller's stream still runs the encoder's backward)
             if (defer_encoder) {
@@ -1339,11 +1232,15 @@ extern "C" int mpnhip_backward_flags(const mpnhip_model* model, const void* grap
                 MPN_TRY(unpack_node_grads(side->stream));
             }
         } else {
-            MPN_TRY(mp_weight_grads(0, last_n, s, p.slab));
+            MPN_TRY(mp_weight_grads(0, last_group_steps(), s, p.slab));
             MPN_TRY(unpack_node_grads(s));
         }
-    } else {
-        // mpn.py:387-389: only the classifier sits between the encoder output and the logits
+        return MPNHIP_OK;
+    }
+
+    // L == 0 (mpn.py:387-389): only the classifier sits between the encoder output and the logits
+    int classifier_only() {
+        const mpnhip_mlp& cls = m.classifier;
         StepBufs b = f.step0;
         float* dzc[MPNHIP_MAX_LAYERS];
         for (int i = 0; i + 1 < nc; ++i) dzc[i] = p.dZcl[i];
@@ -1362,13 +1259,12 @@ extern "C" int mpnhip_backward_flags(const mpnhip_model* model, const void* grap
             hipLaunchKernelGGL(k_add_block, dim3((unsigned)((xs + 255) / 256)), dim3(256), 0, s, p.dX[0], dn, p.dX0, dn, 0, (int)N, dn);
             MPN_LAUNCH_CHECK();
         }
-        if (grad_e_out && es) {
-            // dE0 was seeded with the gathered grad_e_out (dE_last aliases dE0 when L == 0): nothing to add
-        }
+        // (grad_e_out: dE0 was seeded with the gathered grad_e_out -- seed()'s dE_last aliases dE0 when L == 0: nothing to add)
+        return MPNHIP_OK;
     }
 
-    // ---- encoder (MLPGraphIndependent, mpn.py:355) -------------------------------------------------
-    {
+    // ---- encoder (MLPGraphIndependent, mpn.py:355), caller's stream; the products go to the tail batch when it stays to the end -----
+    int encoder_node_bwd() {
         float* two[2] = {f.enc_n[0], nullptr};
         float* hid[MPNHIP_MAX_LAYERS];
         hidden_ptrs(m.enc_node, two, N, true, hid);
@@ -1390,8 +1286,10 @@ extern "C" int mpnhip_backward_flags(const mpnhip_model* model, const void* grap
                                  nullptr, nullptr, 0, 0, nullptr, N, s));
             }
         }
+        return MPNHIP_OK;
     }
-    {
+
+    int encoder_edge_bwd() {
         float* two[2] = {f.enc_e[0], nullptr};
         float* hid[MPNHIP_MAX_LAYERS];
         hidden_ptrs(m.enc_edge, two, E, true, hid);
@@ -1433,8 +1331,12 @@ extern "C" int mpnhip_backward_flags(const mpnhip_model* model, const void* grap
                                  ee.in_dim, g.perm, nullptr, 0, 0, nullptr, E, s));
             }
         }
+        return MPNHIP_OK;
     }
-    if (unpack_pending) {
+
+    // ---- the tail batch that stayed to the end, and the unpacking behind it ----------------------------------------------------------
+    int flush_tail_and_unpack() {
+        if (!unpack_pending) return MPNHIP_OK;
         MPN_TRY(flush_tail());
         if (tail_inline) {
             // the groups' "+=" first (side stream), then the unpacking on the caller's stream
@@ -1445,26 +1347,95 @@ extern "C" int mpnhip_backward_flags(const mpnhip_model* model, const void* grap
         } else {
             MPN_TRY(unpack_node_grads(side->stream));
         }
+        return MPNHIP_OK;
     }
-    if ((flags & MPNHIP_BWD_DEFER_SIDE_JOIN) && !forked && side) {
-        // nothing was forked (no side stream work: few steps, or the fork was not possible), but the caller was promised that the
-        // side stream's order ends with the message-passing modules' gradients: order it behind the caller's stream
-        MPN_HIP(hipEventRecord(side->ready, s));
-        MPN_HIP(hipStreamWaitEvent(side->stream, side->ready, 0));
-    }
-    if (L > 0 && forked) {
-        // join: every "+=" of the side stream's groups (and the unpacking) is in.  MPNHIP_BWD_DEFER_SIDE_JOIN leaves it to the
-        // caller (mpnhip_side_stream_join): a data-parallel trainer first puts the all-reduce of the message-passing modules'
-        // gradients on the side stream, where it overlaps the encoder's backward still running on the caller's stream.
-        if (flags & MPNHIP_BWD_DEFER_SIDE_JOIN) {
-            join.joined = true;
-        } else if (!join.joined) {   // (tail_inline: joined ahead of the unpacking)
-            MPN_HIP(hipEventRecord(side->done, side->stream));
-            MPN_HIP(hipStreamWaitEvent(s, side->done, 0));
-            join.joined = true;
+
+    // ---- the caller's stream behind the side stream (or, MPNHIP_BWD_DEFER_SIDE_JOIN, the promise that the caller will do it) -------
+    int join_side() {
+        if ((flags & MPNHIP_BWD_DEFER_SIDE_JOIN) && !join.forked && side) {
+            // nothing was forked (no side stream work: few steps, or the fork was not possible), but the caller was promised that the
+            // side stream's order ends with the message-passing modules' gradients: order it behind the caller's stream
+            MPN_HIP(hipEventRecord(side->ready, s));
+            MPN_HIP(hipStreamWaitEvent(side->stream, side->ready, 0));
         }
+        if (L > 0 && join.forked) {
+            // join: every "+=" of the side stream's groups (and the unpacking) is in.  MPNHIP_BWD_DEFER_SIDE_JOIN leaves it to the
+            // caller (mpnhip_side_stream_join): a data-parallel trainer first puts the all-reduce of the message-passing modules'
+            // gradients on the side stream, where it overlaps the encoder's backward still running on the caller's stream.
+            if (flags & MPNHIP_BWD_DEFER_SIDE_JOIN) {
+                join.joined = true;
+            } else if (!join.joined) {   // (tail_inline: joined ahead of the unpacking)
+                MPN_HIP(hipEventRecord(side->done, side->stream));
+                MPN_HIP(hipStreamWaitEvent(s, side->done, 0));
+                join.joined = true;
+            }
+        }
+        return MPNHIP_OK;
     }
+};
+
+}  // namespace mpnhip
+
+using namespace mpnhip;
+
+extern "C" size_t mpnhip_backward_workspace_bytes(const mpnhip_model* model, int n_nodes, int64_t n_edges) {
+    Dims d;
+    if (!model) return 256;  // non-zero: "the backward pass is built into this library"
+    if (check_full(*model, &d, false) != MPNHIP_OK) return 0;
+    return plan_backward(*model, d, n_nodes, n_edges, nullptr, nullptr);
+}
+
+extern "C" int mpnhip_backward_uses_side_stream(const mpnhip_model* model) { return model && backward_forks(*model) ? 1 : 0; }
+
+extern "C" void* mpnhip_side_stream(void) {
+    SideStream* side = nullptr;
+    std::lock_guard<std::mutex> lock(g_side_mu);
+    return side_stream_ready(&side) == MPNHIP_OK ? static_cast<void*>(side->stream) : nullptr;
+}
+
+extern "C" int mpnhip_side_stream_join(void* stream_) {
+    SideStream* side = nullptr;
+    std::lock_guard<std::mutex> lock(g_side_mu);
+    MPN_TRY(side_stream_ready(&side));
+    MPN_HIP(hipEventRecord(side->done, side->stream));
+    MPN_HIP(hipStreamWaitEvent(static_cast<hipStream_t>(stream_), side->done, 0));
     return MPNHIP_OK;
+}
+
+extern "C" int mpnhip_backward(const mpnhip_model* model, const void* graph_buf, int n_nodes, int64_t n_edges,
+                               const float* x, const float* edge_attr, const float* grad_logits, const float* grad_x_out,
+                               const float* grad_e_out, float* grad_x, float* grad_edge_attr, void* fwd_workspace,
+                               size_t fwd_workspace_bytes, void* bwd_workspace, size_t bwd_workspace_bytes, void* stream_) {
+    return mpnhip_backward_flags(model, graph_buf, n_nodes, n_edges, x, edge_attr, grad_logits, grad_x_out, grad_e_out, grad_x,
+                                 grad_edge_attr, fwd_workspace, fwd_workspace_bytes, bwd_workspace, bwd_workspace_bytes, 0, stream_);
+}
+
+extern "C" int mpnhip_backward_flags(const mpnhip_model* model, const void* graph_buf, int n_nodes, int64_t n_edges,
+                                     const float* x, const float* edge_attr, const float* grad_logits, const float* grad_x_out,
+                                     const float* grad_e_out, float* grad_x, float* grad_edge_attr, void* fwd_workspace,
+                                     size_t fwd_workspace_bytes, void* bwd_workspace, size_t bwd_workspace_bytes, int flags,
+                                     void* stream_) {
+    MPN_CHECK_ARG(model && graph_buf, "backward: null model / graph");
+    BackwardRun run(*model, x, edge_attr, grad_logits, grad_x_out, grad_e_out, grad_x, grad_edge_attr, flags, static_cast<hipStream_t>(stream_));
+    MPN_TRY(run.init(graph_buf, n_nodes, n_edges, fwd_workspace, fwd_workspace_bytes, bwd_workspace, bwd_workspace_bytes));
+    // caller's stream: the seeds and the weight images
+    MPN_TRY(run.seed());
+    MPN_TRY(run.pack_weights());
+    // the step loop on the caller's stream; each complete group of steps forks its weight gradients to the side stream
+    MPN_TRY(run.schedule_groups());
+    for (int step = run.L; step >= 1; --step) {
+        MPN_TRY(run.step(step));
+        MPN_TRY(run.fork_group_if_due(step - 1));
+    }
+    // the last group to the side stream FIRST: it runs under everything the caller's stream does from here on
+    MPN_TRY(run.fork_last_group());
+    MPN_TRY(run.plan_tail());
+    MPN_TRY(run.hoisted_shares());
+    MPN_TRY(run.finish_message_passing());   // (L == 0: classifier_only)
+    MPN_TRY(run.encoder_node_bwd());
+    MPN_TRY(run.encoder_edge_bwd());
+    MPN_TRY(run.flush_tail_and_unpack());
+    return run.join_side();
 }
 
 // Test / diagnosis instrumentation: one block of pre-activation gradients mpnhip_backward left in its workspace (sorted edge

@@ -466,7 +466,7 @@ def test_fp32_two_stage_slab_sum():
 
 # ------------------------------------------------------------------------------------ many jobs in one launch
 def step_group(d, N, E, nb, family):
-    """the products mp_weight_grads (csrc/backward.hip) records for one group of nb steps of the d-wide model in the split form, widths
+    """the products BackwardRun::mp_weight_grads (csrc/backward.hip) records for one group of nb steps of the d-wide model in the split form, widths
     from synth.model_params: node update, flow layers 1 and 0 (two direction groups), classifier output layer and layer 0, edge
     layers 1 and 0 (the e0 share hoisted), per-node projections (the x0 share hoisted; no bias)"""
     p = synth.model_params(d, 2)

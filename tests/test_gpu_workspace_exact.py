@@ -13,7 +13,7 @@ detections, 3 steps, 2 graphs.  The workspace itself is filled with 0xA5 as well
 ``mpnhip_full_masks_workspace_bytes`` is ONE size for three operators (the largest of them plus 256): there the size an
 operator refuses below is read from its own refusal message and must not exceed the advertised one.
 
-The message-passing core (csrc/plan.h, backward.hip: ``mpnhip_forward`` / ``mpnhip_backward``) under the same discipline, at the
+The message-passing core (csrc/plan.h, backward_plan.h: ``mpnhip_forward`` / ``mpnhip_backward``) under the same discipline, at the
 smallest shapes at which each class of region exists -- fp32 / 32-d / max / 3 steps (ARG, the unfused-width slabs), fp32_split / 64-d /
 mean / 4 steps (four steps fork the side stream: slab_side, slab_wp, slab_tail, the node-chain images) and bf16 / 64-d / sum / 4
 steps (the bf16 dZ blocks, dEpp, dP16 / dZn16 / AGG16 / enc16, wt_keep16, the backward pair images).  The layout is a function of

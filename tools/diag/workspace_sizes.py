@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Every ``mpnhip_*_workspace_bytes`` function and ``mpnhip_graph_bytes`` of a given libmpnhip.so over a fixed grid of shapes:
 one line per family with the number of points and a SHA-256 of the values.  Two builds whose workspace layouts are meant to be
-the same (a refactor of the plans in csrc/plan.h, backward.hip, ...) print the same lines; ``--dump`` prints the values.
+the same (a refactor of the plans in csrc/plan.h, backward_plan.h, ...) print the same lines; ``--dump`` prints the values.
 
 Pure host code over ctypes -- the size functions launch nothing, and the model descriptions hold dims only.  The rocprim scratch
 terms of the sort / scan based operators are queried from the runtime: they show with a device present only, so compare two
