@@ -474,7 +474,9 @@ struct BackwardRun {
     const int flags;
     const hipStream_t s;   // the caller's stream: the step loop, the hoisted shares' sums and the encoder chains run here
     // ---- init(): plans, widths, modes
+    const EnvSwitches sw;   // read once by the entry point (tests flip the switches between calls)
     Dims d;
+    FwdRoute fr;            // the route of the forward that left the saves: how to read them
     FwdPlan f;
     BwdPlan p;
     GraphView g;
@@ -488,7 +490,7 @@ struct BackwardRun {
     int64_t sstride = 0;            // floats between two steps' saved activations
     const float* x0 = nullptr;      // the encoder's outputs (x_hist[0], e_hist[0])
     const float* e0 = nullptr;
-    bool use_b16 = false;       // bf16-operand training on the fused kernels (plan.h: chain_bf16_train_ok)
+    bool use_b16 = false;       // bf16-operand training on the fused kernels (plan.h: FwdRoute::b16)
     bool use_chain = false;     // the fused fp32 edge chain (edge_chain.hip)
     bool bwd_split = false;     // ... on split images
     bool hoist_x = false;       // the re-attached x0's share of dX / gWnode: once, from the sum of the steps' dP (hoisted_shares)
@@ -529,9 +531,9 @@ struct BackwardRun {
 
     // (model and the graph buffer are not null: mpnhip_backward_flags checks both before it constructs the object)
     BackwardRun(const mpnhip_model& model, const float* x_, const float* edge_attr_, const float* grad_logits_, const float* grad_x_out_,
-                const float* grad_e_out_, float* grad_x_, float* grad_edge_attr_, int flags_, hipStream_t stream)
+                const float* grad_e_out_, float* grad_x_, float* grad_edge_attr_, int flags_, hipStream_t stream, const EnvSwitches& switches)
         : m(model), x(x_), edge_attr(edge_attr_), grad_logits(grad_logits_), grad_x_out(grad_x_out_), grad_e_out(grad_e_out_),
-          grad_x(grad_x_), grad_edge_attr(grad_edge_attr_), flags(flags_), s(stream) {}
+          grad_x(grad_x_), grad_edge_attr(grad_edge_attr_), flags(flags_), s(stream), sw(switches) {}
     BackwardRun(const BackwardRun&) = delete;
     BackwardRun& operator=(const BackwardRun&) = delete;
 
@@ -550,7 +552,6 @@ struct BackwardRun {
     };
 
     // ---- checks, both plans, the modes (host only: nothing is launched) --------------------------------------------------------
-    // The environment switches are read on every call (tests flip them between calls).
     int init(const void* graph_buf, int n_nodes, int64_t n_edges, void* fwd_workspace, size_t fwd_workspace_bytes, void* bwd_workspace,
              size_t bwd_workspace_bytes) {
         MPN_TRY(check_full(m, &d));
@@ -564,9 +565,10 @@ struct BackwardRun {
                 for (int i = 0; i < q->n_layers; ++i)
                     MPN_CHECK_ARG(q->grad_weight[i] && q->grad_bias[i], "backward: null gradient buffer");
         }
-        const size_t fneed = plan_forward(m, d, N, E, 1, fwd_workspace, &f);
+        fr = fwd_route(m, d, 1, sw);
+        const size_t fneed = plan_forward(m, d, fr, N, E, fwd_workspace, &f);
         MPN_CHECK_WORKSPACE_MSG("backward: forward workspace", " (must be the save_for_backward buffer)", fwd_workspace, fwd_workspace_bytes, fneed);
-        const size_t need = plan_backward(m, d, N, E, bwd_workspace, &p);
+        const size_t need = plan_backward(m, d, fr, N, E, bwd_workspace, &p);
         MPN_CHECK_WORKSPACE("backward", bwd_workspace, bwd_workspace_bytes, need);
         c = {&p, m.precision == MPNHIP_PREC_FP32_SPLIT || m.precision == MPNHIP_PREC_FP32_WGSPLIT || m.precision == MPNHIP_PREC_BF16,
              m.precision == MPNHIP_PREC_BF16, {}};
@@ -583,10 +585,9 @@ struct BackwardRun {
         sstride = (int64_t)(f.step_stride_bytes / sizeof(float));
         x0 = f.x_hist;
         e0 = f.e_hist;
-        if (f.b16 != p.b16) { set_error("backward: the forward workspace was saved in another mode (bf16 fused training %d vs %d)", (int)f.b16, (int)p.b16); return MPNHIP_ERR_ARG; }
-        use_b16 = p.b16 && E > 0 && L > 0;
-        use_chain = chain_shapes_ok(m, d) && E > 0 && L > 0;
-        bwd_split = use_chain && chain_split(m);
+        use_b16 = fr.b16 && E > 0 && L > 0;
+        use_chain = fr.chain && E > 0 && L > 0;
+        bwd_split = use_chain && fr.split;
         // The re-attached x0 does not change from step to step: its share of dX (and of the packed projection weight's gradient)
         // comes from the SUM of the steps' dP, once, after the loop
         hoist_x = d.nf == 2 && L > 1 && N > 0 && pw % 4 == 0 && dn % 4 == 0;
@@ -599,12 +600,12 @@ struct BackwardRun {
         // bf16-operand training: the per-node projections' weight gradient over bf16 ROWS -- dP_s rounded once by the scatter-add kernel that
         // produces it, x_{s-1} from the forward's bf16 mirror -- on the LDS-DMA kernel in 256 x 256 output tiles (wgrad_rows16.hip)
         // (f.xb_hist is filled under the forward's own run-time test: plan.h node_rows16_runtime, the one definition both sides use)
-        node16 = use_b16 && hoist_x && p.dP16 && node_rows16_runtime(f, m, d) && !getenv("MPNHIP_NO_NODE_ROWS16");
+        node16 = use_b16 && hoist_x && p.dP16 && node_rows16_runtime(f, m, d) && !sw.no_node_rows16;
         // (k_node_step32_bwd stages the weights in LDS: 128 pw + 8 KB + ... <= 64 KB, 16-byte aligned rows)
         // wider models in the split precision: the same three launches as one MFMA kernel (node_chain.hip, node_chain_bwd_kernel)
         fuse_node_chain_bwd = p.ncb_img && !c.bf16 && N > 0 && L > 1 && d.nf == 2;
         fuse_node_bwd = !c.bf16 && dn == 32 && N <= 4096 && pw <= 384 && kx % 4 == 0 &&
-                        ((((uintptr_t)f.Wnode) | ((uintptr_t)m.node.weight[0])) & 15) == 0 && !getenv("MPNHIP_NO_NODE_FUSION");
+                        ((((uintptr_t)f.Wnode) | ((uintptr_t)m.node.weight[0])) & 15) == 0 && !sw.no_node_fusion;
         return MPNHIP_OK;
     }
 
@@ -1297,7 +1298,7 @@ struct BackwardRun {
         const float* dz = p.dE0;
         int cur = 0;
         const bool ref_encoder = !c.bf16 && ee.n_layers == 3 && ee.in_dim == 6 && ee.out_dims[0] == 18 && ee.out_dims[1] == 18 && ee.out_dims[2] == 16 &&
-                                 p.t_width >= 52 && !getenv("MPNHIP_NO_ENCODER_FUSION");
+                                 p.t_width >= 52 && !sw.no_encoder_fusion;
         if (E > 0 && ref_encoder) {
             // the reference's edge encoder: all three activation gradients in one launch (dz2 | dz1 | dz0 side by side in T[0]),
             // then the weight-gradient products as before
@@ -1382,7 +1383,7 @@ extern "C" size_t mpnhip_backward_workspace_bytes(const mpnhip_model* model, int
     Dims d;
     if (!model) return 256;  // non-zero: "the backward pass is built into this library"
     if (check_full(*model, &d, false) != MPNHIP_OK) return 0;
-    return plan_backward(*model, d, n_nodes, n_edges, nullptr, nullptr);
+    return plan_backward(*model, d, fwd_route(*model, d, 1, read_switches()), n_nodes, n_edges, nullptr, nullptr);
 }
 
 extern "C" int mpnhip_backward_uses_side_stream(const mpnhip_model* model) { return model && backward_forks(*model) ? 1 : 0; }
@@ -1416,7 +1417,7 @@ extern "C" int mpnhip_backward_flags(const mpnhip_model* model, const void* grap
                                      size_t fwd_workspace_bytes, void* bwd_workspace, size_t bwd_workspace_bytes, int flags,
                                      void* stream_) {
     MPN_CHECK_ARG(model && graph_buf, "backward: null model / graph");
-    BackwardRun run(*model, x, edge_attr, grad_logits, grad_x_out, grad_e_out, grad_x, grad_edge_attr, flags, static_cast<hipStream_t>(stream_));
+    BackwardRun run(*model, x, edge_attr, grad_logits, grad_x_out, grad_e_out, grad_x, grad_edge_attr, flags, static_cast<hipStream_t>(stream_), read_switches());
     MPN_TRY(run.init(graph_buf, n_nodes, n_edges, fwd_workspace, fwd_workspace_bytes, bwd_workspace, bwd_workspace_bytes));
     // caller's stream: the seeds and the weight images
     MPN_TRY(run.seed());
@@ -1450,7 +1451,7 @@ extern "C" int mpnhip_debug_backward_saved(const mpnhip_model* model, int n_node
     MPN_TRY(check_full(m, &d));
     const int64_t N = n_nodes, E = n_edges;
     BwdPlan p;
-    const size_t need = plan_backward(m, d, N, E, const_cast<void*>(bwd_workspace), &p);
+    const size_t need = plan_backward(m, d, fwd_route(m, d, 1, read_switches()), N, E, const_cast<void*>(bwd_workspace), &p);
     // (a null buffer was refused above as a bad argument: only the size test of the macro is live here)
     MPN_CHECK_WORKSPACE("debug_backward_saved", bwd_workspace, bwd_workspace_bytes, need);
     MPN_CHECK_ARG(step >= 1 && step <= (d.L > 0 ? d.L : 1), "debug_backward_saved: step %d", step);

@@ -142,7 +142,8 @@ static inline size_t slab_tail(const mpnhip_model& m, const Dims& d, int64_t N, 
     return t;
 }
 
-static inline size_t plan_backward(const mpnhip_model& m, const Dims& d, int64_t N, int64_t E, void* base, BwdPlan* out) {
+// fr: the route of the training forward whose saves this backward reads (plan.h fwd_route with save = 1)
+static inline size_t plan_backward(const mpnhip_model& m, const Dims& d, const FwdRoute& fr, int64_t N, int64_t E, void* base, BwdPlan* out) {
     Carver a(base);
     BwdPlan p = {};
     const size_t L = d.L > 0 ? d.L : 1;
@@ -164,7 +165,7 @@ static inline size_t plan_backward(const mpnhip_model& m, const Dims& d, int64_t
     }
     p.dZn = a.take<float>(L * N * d.dn);
     p.dP = a.take<float>(L * N * d.pw);
-    p.b16 = chain_bf16_train_ok(m, d);
+    p.b16 = fr.b16;
     p.dP16 = p.dPsum16 = p.dZn16 = p.AGG16 = p.enc16 = nullptr;
     p.enc16_elems = 0;
     const bool node16 = p.b16 && d.pw % 8 == 0 && d.dn % 8 == 0;   // (not `p.dP16 != nullptr`: a size query plans without a base)

@@ -250,14 +250,11 @@ static int pack_node_weights(const mpnhip_model& m, const Dims& d, float* Wnode,
     return MPNHIP_OK;
 }
 
-static int pack_chain_weights(const mpnhip_model& m, const Dims& d, ChainWeights& cw, PackBatch* batch, SplitBatch* split_batch, hipStream_t s) {
-    cw.ok = chain_shapes_ok(m, d);
-    if (!cw.ok) return MPNHIP_OK;
+static int pack_chain_weights(const mpnhip_model& m, const Dims& d, const ChainWeights& cw, bool split, PackBatch* batch, SplitBatch* split_batch, hipStream_t s) {
     const int HE = pad32(d.he), DE = pad32(d.de), HN = pad32(d.hn), DN = pad32(d.dn);
     const int hc = m.classifier.out_dims[0];
     const mpnhip_mlp* fl[2] = {&m.flow_out, &m.flow_in};
-    cw.split = chain_split(m);
-    if (cw.split) {
+    if (split) {
         // the same logical images WT[k][n] = W[n][k0 + k] as below, as split images (3/2 the size, offsets scale alike)
         MPN_TRY(pack_split(m.edge.weight[0] + 2 * d.kx, 1, m.edge.in_dim, d.ke, d.he, d.ke, HE, cw.w1T, split_batch, s));
         MPN_TRY(pack_split(m.edge.weight[1], 1, d.he, d.he, d.de, HE, DE, cw.w2T, split_batch, s));
@@ -289,9 +286,7 @@ static int pack_chain_weights(const mpnhip_model& m, const Dims& d, ChainWeights
     return MPNHIP_OK;
 }
 
-static int pack_chain_bf16_weights(const mpnhip_model& m, const Dims& d, ChainBf16& cb, hipStream_t s) {
-    cb.ok = cb.img && chain_bf16_ok(m, d);
-    if (!cb.ok) return MPNHIP_OK;
+static int pack_chain_bf16_weights(const mpnhip_model& m, const Dims& d, const ChainBf16& cb, hipStream_t s) {
     const float* f0[2] = {m.flow_out.weight[0], m.flow_in.weight[0]};
     const float* f1[2] = {m.flow_out.weight[1], m.flow_in.weight[1]};
     return pack_chain_bf16(m.edge.weight[0], m.edge.in_dim, 2 * d.kx, d.ef, m.edge.weight[1], m.classifier.weight[0], f0, m.flow_out.in_dim,
@@ -321,6 +316,7 @@ __global__ __launch_bounds__(256) void k_proj_hoist32(const float* __restrict__ 
     P[i] = s0 + s1;
 }
 
+// what one MetaLayer step reads and writes (which kernels run it is the route's matter: plan.h FwdRoute)
 struct StepIO {
     // node features as one or two K segments (x0 | x) -- together kx columns
     const float* xa; int64_t ldxa; const float* xb; int64_t ldxb; int kxa;
@@ -330,212 +326,11 @@ struct StepIO {
     const int* e_new_read_idx;            // how the flow MLPs must index e_new (nullptr = sorted order)
     float* x_new;                         // [N, dn]
     float* logits;                        // [E] original order, or nullptr (operator-level call)
-    const float* P0;                      // optional: xa's share of the projections (+ biases), precomputed [N, pw];
-                                          // then only xb is multiplied here (the weights are shared by all steps)
-    const float* Q0;                      // optional (fused chain): ea's share of the edge MLP's first layer, [E, he]
-    int p_ready;                          // the previous step's fused node kernel already wrote this step's projections into b.P
-    int fuse_node;                        // 1: aggregate + node update (+ the NEXT step's projections unless `last`) in one launch
-    int last;                             //    (node_step32: the reference's node width)
-    float* P_next;                        //    where the next step's projections go (its step buffers; inference: the shared ones)
-    const unsigned short* nc_img;         //    non-null: node_chain.hip's kernel (dn = 64 / 128, split precision) instead of node_step32
-    // MPNHIP_PREC_BF16 with bf16 rows (gemm_bf16.hip): images of the packed projection / node-update weights, mirrors of xa / xb,
-    // and where the mirror of x_new goes
-    const unsigned short* Wnode16; const unsigned short* Wu16; const unsigned short* xa16; const unsigned short* xb16;
-    unsigned short* x_new16;
+    // FwdRoute::rows16 (gemm_bf16.hip reads bf16 rows): mirrors of xa / xb, and where the mirror of x_new goes
+    const unsigned short* xa16; const unsigned short* xb16; unsigned short* x_new16;
+    // FwdRoute::e16_on (FwdPlan::eb_hist): mirrors of ea / eb, and where the mirror of e_new goes
+    const unsigned short* ea16; const unsigned short* eb16; unsigned short* e_new16;
 };
-
-// One MetaLayer.forward (mpn.py:33-54) (+ classifier, mpn.py:114) on prepared weights.
-// e16: bf16 mirror of the edge features of this step (FwdPlan::eb_hist): [0] the re-attached initial ones, [1] the current ones,
-// [2] where the new ones go; write_e32: the fp32 features of this step are needed (the last step's are returned / kept)
-struct StepE16 { const unsigned short* e0; const unsigned short* cur; unsigned short* out; bool write_e32; };
-
-static int run_step(const mpnhip_model& m, const Dims& d, const GraphView& g, const float* Wnode, const float* bnode,
-                    const StepIO& io, const StepBufs& b, bool save_arg, int prec, hipStream_t s, const ChainWeights* cw = nullptr,
-                    bool save_acts = false, const ChainBf16* cb = nullptr, const StepE16* e16 = nullptr) {
-    unsigned short* const save_eb = e16 ? e16->out : nullptr;
-    const int64_t N = g.N, E = g.E;
-    const int he = d.he, hn = d.hn;
-    // (1) per-node projections P = [xa | xb] Wnode^T + bnode
-    if (!io.p_ready) {
-        GemmArgs a = {};
-        a.ngroups = 1; a.N = d.pw; a.relu = 0; a.m_upper = N;
-        GemmGroup& G = a.g[0];
-        init_group(G);
-        if (io.Wnode16 && io.xa16) {
-            // bf16 rows in memory, the whole K (both segments), biases in the epilogue: the LDS-DMA ring kernel
-            a.K = d.kx; a.ksplit = io.xb16 ? io.kxa : d.kx;
-            G.A = reinterpret_cast<const float*>(io.xa16); G.lda = io.ldxa; G.a16 = 1;
-            G.A2 = reinterpret_cast<const float*>(io.xb16); G.lda2 = io.ldxb;
-            G.B = reinterpret_cast<const float*>(io.Wnode16); G.ldb = d.kx; G.b16 = 1; G.bias = bnode;
-        } else if (io.P0 && io.xb) {
-            // xa (the re-attached initial features) does not change from step to step: its product is P0
-            a.K = d.kx - io.kxa; a.ksplit = a.K;
-            G.A = io.xb; G.lda = io.ldxb;
-            G.B = Wnode + io.kxa; G.ldb = d.kx;
-            G.G1 = io.P0; G.ldg1 = d.pw;
-        } else {
-            a.K = d.kx; a.ksplit = io.xb ? io.kxa : d.kx;
-            G.A = io.xa; G.lda = io.ldxa; G.A2 = io.xb; G.lda2 = io.ldxb;
-            G.B = Wnode; G.ldb = d.kx; G.bias = bnode;
-        }
-        G.C = b.P; G.ldc = d.pw; G.m_static = N;
-        MPN_TRY(launch_gemm(a, A_KCONTIG, B_KCONTIG, prec, s));
-    }
-    const bool chain = cw && cw->ok && E > 0 && io.logits && !io.e_idx && !io.e_new_idx && !io.e_new_read_idx;
-    bool agg_done = false;   // the chain kernel aggregated the messages itself
-    // (training: only with the bf16 save buffers of FwdPlan::b16 -- save_eb is given exactly then)
-    const bool chain_bf16 = !chain && cb && cb->ok && (!save_acts || save_eb) && E > 0 && io.logits && io.eb && !io.e_idx && !io.e_new_idx &&
-                            !io.e_new_read_idx;
-    if (e16 && !chain_bf16) { set_error("forward: the bf16 mirror of the edge features needs the bf16 chain kernel"); return MPNHIP_ERR_ARG; }
-    if (chain_bf16) {
-        // (2)-(4) fused, bf16 operands / fp32 accumulation (edge_chain_bf16.hip)
-        EdgeChainBf16Args a = {};
-        a.E = (int)E; a.N = (int)N; a.header = g.header; a.srow = g.srow; a.scol = g.scol; a.perm = g.perm;
-        a.he = d.he; a.de = d.de; a.hn = d.hn; a.dn = d.dn; a.hc = m.classifier.out_dims[0];
-        a.xa = io.ea; a.ldxa = io.ldea; a.xb = io.eb; a.ldxb = io.ldeb;
-        a.P = b.P; a.pw = d.pw;
-        a.img_edge = cb->img; a.img_cls = cb->img + cb->off_cls; a.img_flow[0] = cb->img + cb->off_flow[0]; a.img_flow[1] = cb->img + cb->off_flow[1];
-        a.b2 = m.edge.bias[1]; a.bc1 = m.classifier.bias[0]; a.wc2 = m.classifier.weight[1]; a.bc2 = m.classifier.bias[1];
-        a.bf2_out = m.flow_out.bias[1]; a.bf2_in = m.flow_in.bias[1];
-        a.e_new = io.e_new; a.msg = b.M; a.logits = io.logits;
-        // the aggregation of the messages inside the kernel (they never reach HBM); MPNHIP_NO_AGG_FUSION=1: k_aggregate as before
-        // (training with max keeps the separate kernel: it records the arg max the backward needs)
-        agg_done = cb->piece && !io.fuse_node && !save_arg && !getenv("MPNHIP_NO_AGG_FUSION");
-        if (e16) {
-            a.xa16 = e16->e0; a.xb16 = e16->cur; a.e16_out = e16->out;
-            if (!e16->write_e32) a.e_new = nullptr;
-        }
-        if (save_acts) {
-            a.save_h1 = reinterpret_cast<unsigned short*>(b.HE[0]);
-            a.save_hc = reinterpret_cast<unsigned short*>(b.HC[0]);
-            a.save_hf = reinterpret_cast<unsigned short*>(b.HF[0]);
-            a.save_eb = save_eb;
-            a.save_mask = reinterpret_cast<unsigned*>(b.MK);
-        }
-        if (agg_done) {
-            a.seg_ptr = g.seg_ptr; a.agg_out = b.AGG; a.piece = cb->piece; a.start_row = cb->start_row; a.agg = m.agg;
-            MPN_HIP(hipMemsetAsync(b.AGG, 0, (size_t)N * 2 * d.dn * sizeof(float), s));   // (empty segments)
-        }
-        prof_begin(PROF_GEMM, s);
-        MPN_TRY(launch_edge_chain_bf16(a, s));
-        prof_end(PROF_GEMM, s);
-    } else if (chain) {
-        // (2)-(4) fused: edge MLP, classifier and both flow MLPs in one kernel (edge_chain.hip)
-        EdgeChainArgs a = {};
-        a.E = (int)E; a.N = (int)N; a.header = g.header; a.srow = g.srow; a.scol = g.scol; a.perm = g.perm; a.split = cw->split ? 1 : 0;
-        a.he = d.he; a.de = d.de; a.hn = d.hn; a.dn = d.dn; a.hc = m.classifier.out_dims[0];
-        a.xa = io.ea; a.ldxa = io.ldea; a.k1a = io.eb ? io.kea : d.ke;
-        a.xb = io.eb; a.ldxb = io.ldeb; a.k1b = io.eb ? d.ke - io.kea : 0;
-        a.P = b.P; a.pw = d.pw;
-        a.w1T = cw->w1T; a.w2T = cw->w2T; a.b2 = m.edge.bias[1];
-        if (io.Q0 && io.eb) {
-            // ea = the re-attached initial edge features: their product with W1's e0 columns is Q0 (once per forward);
-            // the kernel multiplies the current features only (rows kea.. of the [k][n] weight image)
-            a.Q0 = io.Q0;
-            a.xa = io.eb; a.ldxa = io.ldeb; a.k1a = d.ke - io.kea;
-            a.xb = nullptr; a.ldxb = 0; a.k1b = 0;
-            a.w1T = cw->w1T + (size_t)io.kea * pad32(d.he) * (cw->split ? 3 : 2) / 2;
-        }
-        a.wc1T = cw->wc1T; a.bc1 = m.classifier.bias[0]; a.wc2 = m.classifier.weight[1]; a.bc2 = m.classifier.bias[1];
-        a.wf1T_out = cw->wf1T[0]; a.wf1T_in = cw->wf1T[1]; a.wf2T_out = cw->wf2T[0]; a.wf2T_in = cw->wf2T[1];
-        a.bf2_out = m.flow_out.bias[1]; a.bf2_in = m.flow_in.bias[1];
-        a.e_new = io.e_new; a.msg = b.M; a.logits = io.logits;
-        a.save_h1 = save_acts ? b.HE[0] : nullptr;
-        a.save_hc = save_acts ? b.HC[0] : nullptr;
-        a.save_hf = save_acts ? b.HF[0] : nullptr;
-        a.save_mask = save_acts ? reinterpret_cast<unsigned*>(b.MK) : nullptr;
-        prof_begin(PROF_GEMM, s);
-        MPN_TRY(launch_edge_chain(a, s));
-        prof_end(PROF_GEMM, s);
-    } else if (E > 0) {
-        // (2) edge MLP layer 0: relu([ea | eb] W1e^T + P_r[row] + P_c[col])      (EdgeModel, mpn.py:67-69)
-        {
-            GemmArgs a = {};
-            a.ngroups = 1; a.N = he; a.K = d.ke; a.ksplit = io.eb ? io.kea : d.ke; a.m_upper = E;
-            a.relu = he != 1;
-            GemmGroup& G = a.g[0];
-            init_group(G);
-            G.A = io.ea; G.lda = io.ldea; G.A2 = io.eb; G.lda2 = io.ldeb; G.a_idx = io.e_idx;
-            G.B = m.edge.weight[0] + 2 * d.kx; G.ldb = m.edge.in_dim;
-            G.G1 = b.P; G.g1_idx = g.srow; G.ldg1 = d.pw;
-            G.G2 = b.P + he; G.g2_idx = g.scol; G.ldg2 = d.pw;
-            bool last = m.edge.n_layers == 1;
-            G.C = last ? io.e_new : b.HE[0]; G.ldc = last ? d.de : he; G.c_idx = last ? io.e_new_idx : nullptr;
-            G.m_static = E;
-            prof_begin(PROF_GEMM, s);
-            MPN_TRY(launch_gemm(a, A_KCONTIG, B_KCONTIG, prec, s));
-            prof_end(PROF_GEMM, s);
-        }
-        MPN_TRY(mlp_tail(m.edge, nullptr, nullptr, b.HE, io.e_new, d.de, io.e_new_idx, E, prec, s));
-        // (3) classifier on the NEW edge features (mpn.py:377 -> :114)
-        if (io.logits) {
-            const mpnhip_mlp& c = m.classifier;
-            GemmArgs a = {};
-            a.ngroups = 1; a.N = c.out_dims[0]; a.K = d.de; a.ksplit = d.de; a.relu = c.out_dims[0] != 1; a.m_upper = E;
-            GemmGroup& G = a.g[0];
-            init_group(G);
-            G.A = io.e_new; G.lda = d.de; G.a_idx = io.e_new_read_idx; G.B = c.weight[0]; G.ldb = d.de; G.bias = c.bias[0];
-            bool last = c.n_layers == 1;
-            G.C = last ? io.logits : b.HC[0]; G.ldc = last ? 1 : a.N; G.c_idx = last ? g.perm : nullptr; G.m_static = E;
-            MPN_TRY(launch_gemm(a, A_KCONTIG, B_KCONTIG, prec, s));
-            MPN_TRY(mlp_tail(c, nullptr, nullptr, b.HC, io.logits, 1, g.perm, E, prec, s));
-        }
-        // (4) flow MLP layer 0, both directions in one grouped launch (TimeAwareNodeModel, mpn.py:85-94)
-        {
-            GemmArgs a = {};
-            a.ngroups = 2; a.N = hn; a.K = d.de; a.ksplit = d.de; a.relu = hn != 1; a.m_upper = E;
-            bool last = m.flow_in.n_layers == 1;
-            for (int q = 0; q < 2; ++q) {
-                const mpnhip_mlp& f = q == 0 ? m.flow_out : m.flow_in;
-                GemmGroup& G = a.g[q];
-                init_group(G);
-                G.A = io.e_new; G.lda = d.de; G.a_idx = io.e_new_read_idx;
-                G.B = f.weight[0] + d.kx; G.ldb = f.in_dim;
-                G.G1 = b.P + 2 * he + q * hn; G.g1_idx = g.scol; G.ldg1 = d.pw;
-                G.C = last ? b.M : b.HF[0]; G.ldc = last ? d.dn : hn;
-                G.m_static = E;
-                G.row_begin = q == 0 ? nullptr : g.header + 4;
-                G.row_end = q == 0 ? g.header + 4 : g.header + 5;
-            }
-            MPN_TRY(launch_gemm(a, A_KCONTIG, B_KCONTIG, prec, s));
-        }
-        MPN_TRY(mlp_tail(m.flow_out, &m.flow_in, &g, b.HF, b.M, d.dn, nullptr, E, prec, s));
-    }
-    // (5) aggregation (node_agg_fn, mpn.py:89,96) and node update (mpn.py:97-99)
-    if (io.fuse_node && io.nc_img) {
-        size_t off_wx = 0;
-        node_chain_image_shorts(d.dn, d.pw, &off_wx);
-        NodeChainArgs a = {(int)N, d.dn, d.pw, m.agg, g.seg_ptr, b.M, io.nc_img, m.node.bias[0], io.nc_img + off_wx, io.P0,
-                           io.last ? nullptr : io.P_next, io.x_new, save_acts ? b.AGG : nullptr};
-        // (profiled under the aggregation's kind: node_agg_fn runs inside this launch)
-        prof_begin(PROF_AGG, s);
-        const int st_nc = launch_node_chain(a, s);
-        prof_end(PROF_AGG, s);
-        return st_nc;
-    }
-    if (io.fuse_node) {
-        MPN_TRY(node_step32(g, b.M, m.agg, m.node.weight[0], m.node.bias[0], io.x_new, save_acts ? b.AGG : nullptr, Wnode + io.kxa, d.kx,
-                            io.P0, io.last ? nullptr : io.P_next, d.pw, s));
-        return MPNHIP_OK;
-    }
-    if (!agg_done) {
-        prof_begin(PROF_AGG, s);
-        MPN_TRY(aggregate(g, b.M, d.dn, m.agg, b.AGG, save_arg ? b.ARG : nullptr, s));
-        prof_end(PROF_AGG, s);
-    }
-    if (io.Wu16 && N > 0) {
-        // bf16 weight image; the bf16 mirror of the new node features (the next step's projections read it) leaves with the result
-        GemmArgs a = {};
-        a.ngroups = 1; a.N = d.dn; a.K = 2 * d.dn; a.ksplit = a.K; a.relu = 1; a.m_upper = N;
-        GemmGroup& G = a.g[0];
-        init_group(G);
-        G.A = b.AGG; G.lda = 2 * d.dn; G.B = reinterpret_cast<const float*>(io.Wu16); G.ldb = 2 * d.dn; G.b16 = 1;
-        G.bias = m.node.bias[0]; G.C = io.x_new; G.ldc = d.dn; G.C16 = io.x_new16; G.ldc16 = d.dn; G.m_static = N;
-        return launch_gemm(a, A_KCONTIG, B_KCONTIG, prec, s);
-    }
-    MPN_TRY(linear(b.AGG, 2 * d.dn, m.node.weight[0], m.node.bias[0], io.x_new, d.dn, N, d.dn, 2 * d.dn, 1, prec, s));
-    return MPNHIP_OK;
-}
 
 // ---- the reference's edge encoder (6 -> 18 -> 18 -> 16, ReLU after every layer; tracking_cfg.yaml:136-139) in one launch ----
 // Three Linear layers this narrow are three launches of the any-shape GEMM kernel (one thread per OUTPUT element, ~25 us each at
@@ -590,11 +385,10 @@ __global__ __launch_bounds__(256) void k_edge_encoder(const float* __restrict__ 
     }
 }
 
-// true (and launched) when `m` is exactly that encoder; hidden[0..1] = where the backward wants the activations, or nullptr
+// (tried where FwdRoute::enc_fused holds)  true (and launched) when `m` is exactly that encoder; hidden[0..1] = where the backward wants the activations, or nullptr
 static bool edge_encoder_fused(const mpnhip_mlp& m, const float* x, const int* idx, float* const* hidden, bool keep_hidden, float* y,
                                int64_t rows, hipStream_t s, int* status) {
     *status = MPNHIP_OK;
-    if (getenv("MPNHIP_NO_ENCODER_FUSION")) return false;
     if (m.n_layers == 3 && rows > 0 && !(m.in_dim == 6 && m.out_dims[0] == 18 && m.out_dims[1] == 18 && m.out_dims[2] == 16)) {
         // the wider models' encoder (e.g. 6 -> 72 -> 72 -> 64 at d = 128): the MFMA form (edge_chain.hip, k_edge_encoder_mfma)
         const float* w[3] = {m.weight[0], m.weight[1], m.weight[2]};
@@ -656,6 +450,400 @@ static int mlp_forward(const mpnhip_mlp& m, const float* x, int64_t ldx, const i
     return MPNHIP_OK;
 }
 
+// One mpnhip_forward call: the object lives in that call's frame (no allocation), the route (plan.h FwdRoute) is decided once in
+// init(), and the phases are the methods below in the order mpnhip_forward calls them.  mpnhip_meta_layer_forward runs the same
+// step code on the all-off route with the caller's row indirections.
+struct ForwardRun {
+    const mpnhip_model& m;
+    const EnvSwitches sw;
+    const hipStream_t s;
+    Dims d;
+    FwdPlan p;
+    GraphView g;
+    FwdRoute r = {};
+    int prec = MPNHIP_PREC_FP32;
+    int64_t N = 0, E = 0;
+    float *x0 = nullptr, *e0 = nullptr;   // the encoder's outputs (x_hist[0], e_hist[0])
+    size_t xs = 0, es = 0;                // floats of one [N, dn] / [E, de] block
+    int prev = 0, cur = 0;   // history slots of the step's inputs / outputs: advanced by step()
+
+    ForwardRun(const mpnhip_model& model, const EnvSwitches& switches, hipStream_t stream) : m(model), sw(switches), s(stream) {}
+    ForwardRun(const ForwardRun&) = delete;
+    ForwardRun& operator=(const ForwardRun&) = delete;
+
+    // ---- checks, the plan, the route (host only: nothing is launched) -----------------------------------------------------------
+    int init(const void* graph_buf, int n_nodes, int64_t n_edges, const float* x, const float* edge_attr, const float* logits, void* workspace,
+             size_t workspace_bytes, int save) {
+        MPN_TRY(check_full(m, &d));
+        N = n_nodes; E = n_edges;
+        MPN_CHECK_ARG(N >= 0 && E >= 0, "forward: negative sizes");
+        MPN_CHECK_ARG((x || N == 0) && (edge_attr || E == 0) && (logits || E == 0), "forward: null tensor");
+        r = fwd_route(m, d, save, sw);
+        const size_t need = plan_forward(m, d, r, N, E, workspace, &p);
+        MPN_CHECK_WORKSPACE("forward", workspace, workspace_bytes, need);
+        graph_layout(n_nodes, n_edges, &g, const_cast<void*>(graph_buf));
+        MPN_CHECK_ARG(m.precision == MPNHIP_PREC_FP32 || m.precision == MPNHIP_PREC_BF16 || m.precision == MPNHIP_PREC_FP32_SPLIT ||
+                      m.precision == MPNHIP_PREC_FP32_WGSPLIT, "forward: unknown precision %d", m.precision);
+        // every product of this call rounds its operands as the model asks (FP32_SPLIT: the fused chain kernels, and the larger
+        // K-contiguous GEMMs -- gemm.hip; FP32_WGSPLIT differs from FP32 in the backward's weight gradients only)
+        prec = m.precision == MPNHIP_PREC_FP32_WGSPLIT ? MPNHIP_PREC_FP32 : m.precision;
+        x0 = p.x_hist; e0 = p.e_hist;
+        xs = (size_t)N * d.dn; es = (size_t)E * d.de;
+        decide();
+        return MPNHIP_OK;
+    }
+
+    // the run part of the route: what needs N, E and the carved pointers
+    void decide() {
+        auto al = [](const void* a, const void* b = nullptr) { return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 15) == 0; };
+        // the node side runs over bf16 rows (plan.h: the backward applies the same test before it reads xb_hist)
+        r.rows16 = node_rows16_runtime(p, m, d);
+        // P0 = x0 Wnode[:, :dn]^T + bnode, once per forward, is the re-attached x0's share of every step's projections
+        // (bf16 rows: the projections multiply [x0 | x] whole -- twice the MFMAs, which this product has to spare, instead of streaming
+        // the [N, pw] fp32 table P0 back in every step)
+        r.hoist = d.nf == 2 && d.L > 1 && !r.rows16;
+        // the same for the edge side of the fused chain: Q0 = e0 W1[:, e0 columns]^T, [E, he] (64 MB at cfg-B), saves a
+        // quarter of the chain's first-layer MFMAs in every step
+        // (measured: pays from de = 32 up; at the reference's de = 16 the extra C-in loads cost more than the one chunk saved)
+        // (FP32_SPLIT: the chain kernel is bound by its row traffic, not by MFMA cycles -- re-reading 4 he bytes per edge and step
+        // costs more than the k blocks it saves: measured 1.59 -> 1.55 ms per cfg-B forward without the hoist)
+        r.hoist_e = r.chain && !r.split && d.ef == 2 && d.L > 1 && E > 0 && d.de >= 32 && (d.ke - d.de) % 16 == 0 && d.de % 16 == 0;
+        // The reference's node width, few nodes: ONE gate for k_proj_hoist32 and node_step32 (segment.hip: the three node-side kernels
+        // of a step in one launch); both need the hoisted P0 form and 16-byte aligned images.  (Every 2-node block re-reads the 43 KB of
+        // node-side weights from L2: beyond a few thousand nodes the GEMMs win again.)
+        const bool node32 = r.hoist && d.dn == 32 && N > 0 && N <= 4096 && m.precision != MPNHIP_PREC_BF16 && al(p.Wnode, p.P0) && !sw.no_node_fusion;
+        // each adds what its own kernel reads: k_proj_hoist32 loads x0 as float4 (kx == 2 dn follows from hoist); node_step32 loads the
+        // node update's weight as float4, needs edges, and does not record the arg max a training forward with max keeps
+        r.proj_small = node32 && al(x0);   // P0 AND the first step's projections in one launch
+        r.fuse_node32 = node32 && !r.save_arg && d.pw % 4 == 0 && E > 0 && al(m.node.weight[0]);
+        // wider models in the split precision: the same three launches as one (node_chain.hip)
+        r.fuse_node_chain = !r.save_arg && r.hoist && p.nc_img && m.precision == MPNHIP_PREC_FP32_SPLIT && E > 0 && N > 0 && m.node.n_layers == 1 &&
+                            al(m.node.bias[0]);
+        // (training on the bf16 chain kernel: only with the bf16 saves of FwdRoute::b16; without edges no chain kernel runs, nothing mirrors)
+        r.edge_bf16 = r.chain_bf16 && (!r.save || r.b16) && E > 0;   // the edge side of a step: the bf16 chain kernel,
+        r.edge_chain = r.chain && E > 0;                             // the fp32 one, or (neither) one launch per product
+        // the edge features travel between the steps as bf16 rows (eb_hist is planned only where edge_bf16 can hold: fwd_route)
+        r.e16_on = r.eb_hist && E > 0;
+        // the bf16 chain kernel aggregates the messages itself: they never reach HBM (MPNHIP_NO_AGG_FUSION=1: k_aggregate); training with
+        // max keeps k_aggregate, which records the arg max.  (No fused node kernel stands beside this arm: they refuse MPNHIP_PREC_BF16.)
+        r.agg_in_kernel = r.edge_bf16 && !r.save_arg && !sw.no_agg_fusion;
+        // the edge encoder may run as one fused launch (bf16-operand mode: every Linear product rounds its operands -- the GEMM path
+        // does that, the fused encoder is fp32)
+        r.enc_fused = m.precision != MPNHIP_PREC_BF16 && !sw.no_encoder_fusion;
+    }
+
+    // ---- weight images at the head of the workspace ------------------------------------------------------------------------------
+    int pack_weights() {
+        if (m.weights_prepacked && !r.save) return MPNHIP_OK;   // the caller kept them from an earlier call
+        count_path(PC_WEIGHT_PACK);
+        PackBatch pb;   // (the fp32 images' copies / transposes are recorded and run as one launch,
+        SplitBatch sb;  //  the split images as another)
+        int rc = pack_node_weights(m, d, p.Wnode, p.bnode, &pb, s);
+        if (rc == MPNHIP_OK && r.chain) rc = pack_chain_weights(m, d, p.cw, r.split, &pb, &sb, s);
+        if (rc == MPNHIP_OK && r.chain_bf16) rc = pack_chain_bf16_weights(m, d, p.cb, s);
+        const int rf = pack_batch_flush(&pb, s);
+        const int rs = split_batch_flush(&sb, s);
+        MPN_TRY(rc);
+        MPN_TRY(rf);
+        MPN_TRY(rs);
+        // (after the flush: the unit images of the fused node-side kernel read the packed projection weights)
+        if (p.nc_img && m.precision == MPNHIP_PREC_FP32_SPLIT)
+            MPN_TRY(pack_node_chain(m.node.weight[0], p.Wnode, d.dn, d.pw, d.kx, p.nc_img, s));
+        // ... and so do the bf16 images of the node-side weights (what to_bf16_rows needs; FwdRoute::rows16 adds the GEMM's conditions)
+        if (p.Wnode16 && ((size_t)d.pw * d.kx) % 4 == 0 && ((size_t)d.dn * 2 * d.dn) % 4 == 0 && (((uintptr_t)m.node.weight[0]) & 15) == 0) {
+            MPN_TRY(to_bf16_rows(p.Wnode, p.Wnode16, (int64_t)d.pw * d.kx, s));
+            MPN_TRY(to_bf16_rows(m.node.weight[0], p.Wu16, (int64_t)d.dn * 2 * d.dn, s));
+        }
+        return MPNHIP_OK;
+    }
+
+    // ---- encoder (mpn.py:355 -> :164-178); the edge encoder reads edge_attr through the sort permutation: per-edge tensors are sorted
+    int encode(const float* x, const float* edge_attr) {
+        float* hid[MPNHIP_MAX_LAYERS];
+        hidden_ptrs(m.enc_node, p.enc_n, N, r.save, hid);
+        MPN_TRY(mlp_forward(m.enc_node, x, m.enc_node.in_dim, nullptr, hid, x0, N, prec, s, p.splitk, p.splitk_floats));
+        hidden_ptrs(m.enc_edge, p.enc_e, E, r.save, hid);
+        int st = MPNHIP_OK;
+        if (!r.enc_fused || !edge_encoder_fused(m.enc_edge, edge_attr, g.perm, hid, r.save, e0, E, s, &st))
+            return mlp_forward(m.enc_edge, edge_attr, m.enc_edge.in_dim, g.perm, hid, e0, E, prec, s);
+        return st;
+    }
+
+    // ---- the encoder outputs as slot 0 of the bf16 mirrors ---------------------------------------------------------------------------
+    int mirror_encoder_outputs() {
+        if (r.e16_on && d.L > 0) MPN_TRY(to_bf16_rows(e0, p.eb_hist, (int64_t)es, s));
+        if (r.rows16 && xs && d.L > 0) MPN_TRY(to_bf16_rows(x0, p.xb_hist, (int64_t)xs, s));
+        return MPNHIP_OK;
+    }
+
+    // ---- P0 = x0 Wnode[:, :dn]^T + bnode, once per forward (the GEMM form; the small form: hoist_projections32) -----------------------
+    int hoist_projections() {
+        if (!r.hoist || r.proj_small) return MPNHIP_OK;
+        GemmArgs a = {};
+        a.ngroups = 1; a.N = d.pw; a.K = d.dn; a.ksplit = d.dn; a.m_upper = N;
+        GemmGroup& G = a.g[0];
+        init_group(G);
+        G.A = x0; G.lda = d.dn; G.B = p.Wnode; G.ldb = d.kx; G.bias = p.bnode; G.C = p.P0; G.ldc = d.pw; G.m_static = N;
+        return launch_gemm(a, A_KCONTIG, B_KCONTIG, prec, s);
+    }
+
+    // ---- Q0 = e0 W1[:, e0 columns]^T ---------------------------------------------------------------------------------------------------
+    int hoist_edge_share() {
+        if (!r.hoist_e) return MPNHIP_OK;
+        GemmArgs a = {};
+        a.ngroups = 1; a.N = d.he; a.K = d.de; a.ksplit = d.de; a.m_upper = E;
+        GemmGroup& G = a.g[0];
+        init_group(G);
+        G.A = e0; G.lda = d.de; G.B = m.edge.weight[0] + 2 * d.kx; G.ldb = m.edge.in_dim; G.C = p.Q0; G.ldc = d.he; G.m_static = E;
+        return launch_gemm(a, A_KCONTIG, B_KCONTIG, prec, s);
+    }
+
+    // ---- P0 AND the first step's projections by k_proj_hoist32 (its place in the launch order: behind Q0) ------------------------------
+    int hoist_projections32() {
+        if (!r.proj_small) return MPNHIP_OK;
+        const int64_t total = N * d.pw;
+        hipLaunchKernelGGL(k_proj_hoist32, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, x0, p.Wnode, p.bnode, p.P0, step_at(p, 0).P,
+                           total, d.pw, d.dn);
+        MPN_LAUNCH_CHECK();
+        return MPNHIP_OK;
+    }
+
+    // ---- message-passing step i (0-based) between the history slots -------------------------------------------------------------------
+    int step(int i, float* logits) {
+        cur = r.save ? i + 1 : 1 + (i & 1);
+        StepIO io = {};
+        const float* xp = p.x_hist + xs * prev;
+        const float* ep = p.e_hist + es * prev;
+        if (d.nf == 2) { io.xa = x0; io.ldxa = d.dn; io.xb = xp; io.ldxb = d.dn; io.kxa = d.dn; }
+        else { io.xa = xp; io.ldxa = d.dn; }
+        if (d.ef == 2) { io.ea = e0; io.ldea = d.de; io.eb = ep; io.ldeb = d.de; io.kea = d.de; }
+        else { io.ea = ep; io.ldea = d.de; }
+        io.e_new = p.e_hist + es * cur;
+        io.x_new = p.x_hist + xs * cur;
+        io.logits = logits + (size_t)i * E;
+        if (r.rows16) {
+            io.xa16 = d.nf == 2 ? p.xb_hist : p.xb_hist + xs * prev;
+            io.xb16 = d.nf == 2 ? p.xb_hist + xs * prev : nullptr;
+            io.x_new16 = p.xb_hist + xs * cur;
+        }
+        // (bf16-operand chain: the edge features travel between the steps as bf16 rows; the fp32 ones only where they are returned)
+        if (r.e16_on) { io.ea16 = p.eb_hist; io.eb16 = p.eb_hist + es * prev; io.e_new16 = p.eb_hist + es * cur; }
+        MPN_TRY(meta_layer(io, step_at(p, i), i));
+        prev = cur;
+        return MPNHIP_OK;
+    }
+
+    // One MetaLayer.forward (mpn.py:33-54) (+ classifier, mpn.py:114) on prepared weights
+    int meta_layer(const StepIO& io, const StepBufs& b, int i) {
+        MPN_TRY(projections(io, b, i));
+        if (r.edge_bf16) MPN_TRY(edge_side_bf16(io, b, i));
+        else if (r.edge_chain) MPN_TRY(edge_side_chain(io, b));
+        else if (E > 0) MPN_TRY(edge_side_unfused(io, b));
+        return node_side(io, b, i);
+    }
+
+    // (1) per-node projections P = [xa | xb] Wnode^T + bnode
+    int projections(const StepIO& io, const StepBufs& b, int i) {
+        // (the previous step's fused node kernel, or k_proj_hoist32 ahead of the first step, already wrote them into b.P)
+        if (((r.fuse_node32 || r.fuse_node_chain) && i > 0) || (r.proj_small && i == 0)) return MPNHIP_OK;
+        GemmArgs a = {};
+        a.ngroups = 1; a.N = d.pw; a.relu = 0; a.m_upper = N;
+        GemmGroup& G = a.g[0];
+        init_group(G);
+        if (r.rows16) {
+            // bf16 rows in memory, the whole K (both segments), biases in the epilogue: the LDS-DMA ring kernel
+            a.K = d.kx; a.ksplit = io.xb16 ? io.kxa : d.kx;
+            G.A = reinterpret_cast<const float*>(io.xa16); G.lda = io.ldxa; G.a16 = 1;
+            G.A2 = reinterpret_cast<const float*>(io.xb16); G.lda2 = io.ldxb;
+            G.B = reinterpret_cast<const float*>(p.Wnode16); G.ldb = d.kx; G.b16 = 1; G.bias = p.bnode;
+        } else if (r.hoist) {
+            // xa (the re-attached initial features) does not change from step to step: its product is P0
+            a.K = d.kx - io.kxa; a.ksplit = a.K;
+            G.A = io.xb; G.lda = io.ldxb;
+            G.B = p.Wnode + io.kxa; G.ldb = d.kx;
+            G.G1 = p.P0; G.ldg1 = d.pw;
+        } else {
+            a.K = d.kx; a.ksplit = io.xb ? io.kxa : d.kx;
+            G.A = io.xa; G.lda = io.ldxa; G.A2 = io.xb; G.lda2 = io.ldxb;
+            G.B = p.Wnode; G.ldb = d.kx; G.bias = p.bnode;
+        }
+        G.C = b.P; G.ldc = d.pw; G.m_static = N;
+        return launch_gemm(a, A_KCONTIG, B_KCONTIG, prec, s);
+    }
+
+    // (2)-(4) fused, bf16 operands / fp32 accumulation (edge_chain_bf16.hip)
+    int edge_side_bf16(const StepIO& io, const StepBufs& b, int i) {
+        EdgeChainBf16Args a = {};
+        a.E = (int)E; a.N = (int)N; a.header = g.header; a.srow = g.srow; a.scol = g.scol; a.perm = g.perm;
+        a.he = d.he; a.de = d.de; a.hn = d.hn; a.dn = d.dn; a.hc = m.classifier.out_dims[0];
+        a.xa = io.ea; a.ldxa = io.ldea; a.xb = io.eb; a.ldxb = io.ldeb;
+        a.P = b.P; a.pw = d.pw;
+        a.img_edge = p.cb.img; a.img_cls = p.cb.img + p.cb.off_cls; a.img_flow[0] = p.cb.img + p.cb.off_flow[0]; a.img_flow[1] = p.cb.img + p.cb.off_flow[1];
+        a.b2 = m.edge.bias[1]; a.bc1 = m.classifier.bias[0]; a.wc2 = m.classifier.weight[1]; a.bc2 = m.classifier.bias[1];
+        a.bf2_out = m.flow_out.bias[1]; a.bf2_in = m.flow_in.bias[1];
+        a.e_new = io.e_new; a.msg = b.M; a.logits = io.logits;
+        if (r.e16_on) {
+            a.xa16 = io.ea16; a.xb16 = io.eb16; a.e16_out = io.e_new16;
+            if (i + 1 != d.L) a.e_new = nullptr;   // (the fp32 features of the last step only: they are returned / kept)
+        }
+        if (r.save) {
+            a.save_h1 = reinterpret_cast<unsigned short*>(b.HE[0]); a.save_hc = reinterpret_cast<unsigned short*>(b.HC[0]);
+            a.save_hf = reinterpret_cast<unsigned short*>(b.HF[0]); a.save_eb = io.e_new16; a.save_mask = reinterpret_cast<unsigned*>(b.MK);
+        }
+        if (r.agg_in_kernel) {
+            a.seg_ptr = g.seg_ptr; a.agg_out = b.AGG; a.piece = p.cb.piece; a.start_row = p.cb.start_row; a.agg = m.agg;
+            MPN_HIP(hipMemsetAsync(b.AGG, 0, (size_t)N * 2 * d.dn * sizeof(float), s));   // (empty segments)
+        }
+        prof_begin(PROF_GEMM, s);
+        MPN_TRY(launch_edge_chain_bf16(a, s));
+        prof_end(PROF_GEMM, s);
+        return MPNHIP_OK;
+    }
+
+    // (2)-(4) fused: edge MLP, classifier and both flow MLPs in one kernel (edge_chain.hip)
+    int edge_side_chain(const StepIO& io, const StepBufs& b) {
+        EdgeChainArgs a = {};
+        a.E = (int)E; a.N = (int)N; a.header = g.header; a.srow = g.srow; a.scol = g.scol; a.perm = g.perm; a.split = r.split ? 1 : 0;
+        a.he = d.he; a.de = d.de; a.hn = d.hn; a.dn = d.dn; a.hc = m.classifier.out_dims[0];
+        a.xa = io.ea; a.ldxa = io.ldea; a.k1a = io.eb ? io.kea : d.ke;
+        a.xb = io.eb; a.ldxb = io.ldeb; a.k1b = io.eb ? d.ke - io.kea : 0;
+        a.P = b.P; a.pw = d.pw;
+        a.w1T = p.cw.w1T; a.w2T = p.cw.w2T; a.b2 = m.edge.bias[1];
+        if (r.hoist_e) {
+            // ea = the re-attached initial edge features: their product with W1's e0 columns is Q0 (once per forward);
+            // the kernel multiplies the current features only (rows kea.. of the [k][n] weight image)
+            a.Q0 = p.Q0;
+            a.xa = io.eb; a.ldxa = io.ldeb; a.k1a = d.ke - io.kea;
+            a.xb = nullptr; a.ldxb = 0; a.k1b = 0;
+            a.w1T = p.cw.w1T + (size_t)io.kea * pad32(d.he) * (r.split ? 3 : 2) / 2;
+        }
+        a.wc1T = p.cw.wc1T; a.bc1 = m.classifier.bias[0]; a.wc2 = m.classifier.weight[1]; a.bc2 = m.classifier.bias[1];
+        a.wf1T_out = p.cw.wf1T[0]; a.wf1T_in = p.cw.wf1T[1]; a.wf2T_out = p.cw.wf2T[0]; a.wf2T_in = p.cw.wf2T[1];
+        a.bf2_out = m.flow_out.bias[1]; a.bf2_in = m.flow_in.bias[1];
+        a.e_new = io.e_new; a.msg = b.M; a.logits = io.logits;
+        if (r.save) { a.save_h1 = b.HE[0]; a.save_hc = b.HC[0]; a.save_hf = b.HF[0]; a.save_mask = reinterpret_cast<unsigned*>(b.MK); }
+        prof_begin(PROF_GEMM, s);
+        MPN_TRY(launch_edge_chain(a, s));
+        prof_end(PROF_GEMM, s);
+        return MPNHIP_OK;
+    }
+
+    // (2)-(4) one launch per product
+    int edge_side_unfused(const StepIO& io, const StepBufs& b) {
+        const int he = d.he, hn = d.hn;
+        // (2) edge MLP layer 0: relu([ea | eb] W1e^T + P_r[row] + P_c[col])      (EdgeModel, mpn.py:67-69)
+        {
+            GemmArgs a = {};
+            a.ngroups = 1; a.N = he; a.K = d.ke; a.ksplit = io.eb ? io.kea : d.ke; a.m_upper = E;
+            a.relu = he != 1;
+            GemmGroup& G = a.g[0];
+            init_group(G);
+            G.A = io.ea; G.lda = io.ldea; G.A2 = io.eb; G.lda2 = io.ldeb; G.a_idx = io.e_idx;
+            G.B = m.edge.weight[0] + 2 * d.kx; G.ldb = m.edge.in_dim;
+            G.G1 = b.P; G.g1_idx = g.srow; G.ldg1 = d.pw;
+            G.G2 = b.P + he; G.g2_idx = g.scol; G.ldg2 = d.pw;
+            bool last = m.edge.n_layers == 1;
+            G.C = last ? io.e_new : b.HE[0]; G.ldc = last ? d.de : he; G.c_idx = last ? io.e_new_idx : nullptr;
+            G.m_static = E;
+            prof_begin(PROF_GEMM, s);
+            MPN_TRY(launch_gemm(a, A_KCONTIG, B_KCONTIG, prec, s));
+            prof_end(PROF_GEMM, s);
+        }
+        MPN_TRY(mlp_tail(m.edge, nullptr, nullptr, b.HE, io.e_new, d.de, io.e_new_idx, E, prec, s));
+        // (3) classifier on the NEW edge features (mpn.py:377 -> :114)
+        if (io.logits) {
+            const mpnhip_mlp& c = m.classifier;
+            GemmArgs a = {};
+            a.ngroups = 1; a.N = c.out_dims[0]; a.K = d.de; a.ksplit = d.de; a.relu = c.out_dims[0] != 1; a.m_upper = E;
+            GemmGroup& G = a.g[0];
+            init_group(G);
+            G.A = io.e_new; G.lda = d.de; G.a_idx = io.e_new_read_idx; G.B = c.weight[0]; G.ldb = d.de; G.bias = c.bias[0];
+            bool last = c.n_layers == 1;
+            G.C = last ? io.logits : b.HC[0]; G.ldc = last ? 1 : a.N; G.c_idx = last ? g.perm : nullptr; G.m_static = E;
+            MPN_TRY(launch_gemm(a, A_KCONTIG, B_KCONTIG, prec, s));
+            MPN_TRY(mlp_tail(c, nullptr, nullptr, b.HC, io.logits, 1, g.perm, E, prec, s));
+        }
+        // (4) flow MLP layer 0, both directions in one grouped launch (TimeAwareNodeModel, mpn.py:85-94)
+        {
+            GemmArgs a = {};
+            a.ngroups = 2; a.N = hn; a.K = d.de; a.ksplit = d.de; a.relu = hn != 1; a.m_upper = E;
+            bool last = m.flow_in.n_layers == 1;
+            for (int q = 0; q < 2; ++q) {
+                const mpnhip_mlp& f = q == 0 ? m.flow_out : m.flow_in;
+                GemmGroup& G = a.g[q];
+                init_group(G);
+                G.A = io.e_new; G.lda = d.de; G.a_idx = io.e_new_read_idx;
+                G.B = f.weight[0] + d.kx; G.ldb = f.in_dim;
+                G.G1 = b.P + 2 * he + q * hn; G.g1_idx = g.scol; G.ldg1 = d.pw;
+                G.C = last ? b.M : b.HF[0]; G.ldc = last ? d.dn : hn;
+                G.m_static = E;
+                G.row_begin = q == 0 ? nullptr : g.header + 4;
+                G.row_end = q == 0 ? g.header + 4 : g.header + 5;
+            }
+            MPN_TRY(launch_gemm(a, A_KCONTIG, B_KCONTIG, prec, s));
+        }
+        return mlp_tail(m.flow_out, &m.flow_in, &g, b.HF, b.M, d.dn, nullptr, E, prec, s);
+    }
+
+    // (5) aggregation (mpn.py:89,96) and node update (mpn.py:97-99); the fused kernels also write the NEXT step's projections
+    int node_side(const StepIO& io, const StepBufs& b, int i) {
+        float* const P_next = i + 1 == d.L ? nullptr : step_at(p, i + 1).P;
+        if (r.fuse_node_chain) {
+            size_t off_wx = 0;
+            node_chain_image_shorts(d.dn, d.pw, &off_wx);
+            NodeChainArgs a = {(int)N, d.dn, d.pw, m.agg, g.seg_ptr, b.M, p.nc_img, m.node.bias[0], p.nc_img + off_wx, p.P0,
+                               P_next, io.x_new, r.save ? b.AGG : nullptr};
+            // (profiled under the aggregation's kind: node_agg_fn runs inside this launch)
+            prof_begin(PROF_AGG, s);
+            const int st_nc = launch_node_chain(a, s);
+            prof_end(PROF_AGG, s);
+            return st_nc;
+        }
+        if (r.fuse_node32)
+            return node_step32(g, b.M, m.agg, m.node.weight[0], m.node.bias[0], io.x_new, r.save ? b.AGG : nullptr, p.Wnode + io.kxa, d.kx,
+                               p.P0, P_next, d.pw, s);
+        if (!r.agg_in_kernel) {
+            prof_begin(PROF_AGG, s);
+            MPN_TRY(aggregate(g, b.M, d.dn, m.agg, b.AGG, r.save_arg ? b.ARG : nullptr, s));
+            prof_end(PROF_AGG, s);
+        }
+        if (r.rows16 && N > 0) {
+            // bf16 weight image; the bf16 mirror of the new node features (the next step's projections read it) leaves with the result
+            GemmArgs a = {};
+            a.ngroups = 1; a.N = d.dn; a.K = 2 * d.dn; a.ksplit = a.K; a.relu = 1; a.m_upper = N;
+            GemmGroup& G = a.g[0];
+            init_group(G);
+            G.A = b.AGG; G.lda = 2 * d.dn; G.B = reinterpret_cast<const float*>(p.Wu16); G.ldb = 2 * d.dn; G.b16 = 1;
+            G.bias = m.node.bias[0]; G.C = io.x_new; G.ldc = d.dn; G.C16 = io.x_new16; G.ldc16 = d.dn; G.m_static = N;
+            return launch_gemm(a, A_KCONTIG, B_KCONTIG, prec, s);
+        }
+        return linear(b.AGG, 2 * d.dn, m.node.weight[0], m.node.bias[0], io.x_new, d.dn, N, d.dn, 2 * d.dn, 1, prec, s);
+    }
+
+    // ---- mpn.py:387-389: no message-passing step -- classify the encoder output once ---------------------------------------------------
+    int classify_encoder_output(float* logits) {
+        if (d.L != 0 || E <= 0) return MPNHIP_OK;
+        const mpnhip_mlp& c = m.classifier;
+        if (c.n_layers == 1) {
+            GemmArgs a = {};
+            a.ngroups = 1; a.N = 1; a.K = d.de; a.ksplit = d.de; a.relu = 0; a.m_upper = E;
+            GemmGroup& G = a.g[0];
+            init_group(G);
+            G.A = e0; G.lda = d.de; G.B = c.weight[0]; G.ldb = d.de; G.bias = c.bias[0];
+            G.C = logits; G.ldc = 1; G.c_idx = g.perm; G.m_static = E;
+            return launch_gemm(a, A_KCONTIG, B_KCONTIG, prec, s);
+        }
+        MPN_TRY(linear(e0, d.de, c.weight[0], c.bias[0], p.step0.HC[0], c.out_dims[0], E, c.out_dims[0], d.de, c.out_dims[0] != 1, prec, s));
+        return mlp_tail(c, nullptr, nullptr, p.step0.HC, logits, 1, g.perm, E, prec, s);
+    }
+
+    // ---- the final features, edges back in original order ----------------------------------------------------------------------------
+    int write_outputs(float* x_out, float* e_out) {
+        if (x_out && N > 0) MPN_HIP(hipMemcpyAsync(x_out, p.x_hist + xs * prev, xs * sizeof(float), hipMemcpyDeviceToDevice, s));
+        if (e_out) MPN_TRY(scatter_rows(p.e_hist + es * prev, g.perm, e_out, E, d.de, s));
+        return MPNHIP_OK;
+    }
+};
 
 }  // namespace mpnhip
 
@@ -676,225 +864,67 @@ extern "C" const char* mpnhip_debug_counter_name(int index) { return index >= 0 
 extern "C" size_t mpnhip_forward_workspace_bytes(const mpnhip_model* model, int n_nodes, int64_t n_edges, int save) {
     Dims d;
     if (!model || check_full(*model, &d, false) != MPNHIP_OK) return 0;
-    return plan_forward(*model, d, n_nodes, n_edges, save, nullptr, nullptr);
+    return plan_forward(*model, d, fwd_route(*model, d, save, read_switches()), n_nodes, n_edges, nullptr, nullptr);
 }
 
 extern "C" int mpnhip_forward(const mpnhip_model* model, const void* graph_buf, int n_nodes, int64_t n_edges,
                               const float* x, const float* edge_attr, float* logits, float* x_out, float* e_out,
                               void* workspace, size_t workspace_bytes, int save, void* stream_) {
-    hipStream_t s = static_cast<hipStream_t>(stream_);
     MPN_CHECK_ARG(model && graph_buf, "forward: null model / graph");
-    const mpnhip_model& m = *model;
-    Dims d;
-    MPN_TRY(check_full(m, &d));
-    const int64_t N = n_nodes, E = n_edges;
-    MPN_CHECK_ARG(N >= 0 && E >= 0, "forward: negative sizes");
-    MPN_CHECK_ARG((x || N == 0) && (edge_attr || E == 0) && (logits || E == 0), "forward: null tensor");
-    FwdPlan p;
-    const size_t need = plan_forward(m, d, N, E, save, workspace, &p);
-    MPN_CHECK_WORKSPACE("forward", workspace, workspace_bytes, need);
-    GraphView g;
-    graph_layout(n_nodes, n_edges, &g, const_cast<void*>(graph_buf));
-    MPN_CHECK_ARG(m.precision == MPNHIP_PREC_FP32 || m.precision == MPNHIP_PREC_BF16 || m.precision == MPNHIP_PREC_FP32_SPLIT ||
-                  m.precision == MPNHIP_PREC_FP32_WGSPLIT, "forward: unknown precision %d", m.precision);
-    // every product of this call rounds its operands as the model asks (FP32_SPLIT: the fused chain kernels, and the larger
-    // K-contiguous GEMMs -- gemm.hip; FP32_WGSPLIT differs from FP32 in the backward's weight gradients only)
-    const int prec = m.precision == MPNHIP_PREC_FP32_WGSPLIT ? MPNHIP_PREC_FP32 : m.precision;
-
-    if (m.weights_prepacked && !save) {
-        p.cw.ok = chain_shapes_ok(m, d);  // the images are already at the head of the workspace
-        p.cw.split = chain_split(m);
-        p.cb.ok = p.cb.img && chain_bf16_ok(m, d);
-    } else {
-        count_path(PC_WEIGHT_PACK);
-        PackBatch pb;   // (the fp32 images' copies / transposes are recorded and run as one launch,
-        SplitBatch sb;  //  the split images as another)
-        int rc = pack_node_weights(m, d, p.Wnode, p.bnode, &pb, s);
-        if (rc == MPNHIP_OK) rc = pack_chain_weights(m, d, p.cw, &pb, &sb, s);
-        if (rc == MPNHIP_OK) rc = pack_chain_bf16_weights(m, d, p.cb, s);
-        const int rf = pack_batch_flush(&pb, s);
-        const int rs = split_batch_flush(&sb, s);
-        MPN_TRY(rc);
-        MPN_TRY(rf);
-        MPN_TRY(rs);
-        // (after the flush: the unit images of the fused node-side kernel read the packed projection weights)
-        if (p.nc_img && m.precision == MPNHIP_PREC_FP32_SPLIT)
-            MPN_TRY(pack_node_chain(m.node.weight[0], p.Wnode, d.dn, d.pw, d.kx, p.nc_img, s));
-        // ... and so do the bf16 images of the node-side weights (gemm_bf16.hip reads bf16 rows)
-        if (p.Wnode16 && ((size_t)d.pw * d.kx) % 4 == 0 && ((size_t)d.dn * 2 * d.dn) % 4 == 0 && (((uintptr_t)m.node.weight[0]) & 15) == 0) {
-            MPN_TRY(to_bf16_rows(p.Wnode, p.Wnode16, (int64_t)d.pw * d.kx, s));
-            MPN_TRY(to_bf16_rows(m.node.weight[0], p.Wu16, (int64_t)d.dn * 2 * d.dn, s));
-        }
-    }
-    // bf16 rows for the node-side products of this call (weights at the head of the workspace: kept with the other images)
-    const bool rows16 = node_rows16_runtime(p, m, d);   // (plan.h: the backward applies the same test)
-    // encoder (MLPGraphIndependent, mpn.py:355 -> :164-178); the edge encoder reads edge_attr through
-    // the sort permutation so that every per-edge tensor downstream lives in sorted order
-    float* hid[MPNHIP_MAX_LAYERS];
-    float* x0 = p.x_hist;
-    float* e0 = p.e_hist;
-    hidden_ptrs(m.enc_node, p.enc_n, N, save != 0, hid);
-    MPN_TRY(mlp_forward(m.enc_node, x, m.enc_node.in_dim, nullptr, hid, x0, N, prec, s, p.splitk, p.splitk_floats));
-    hidden_ptrs(m.enc_edge, p.enc_e, E, save != 0, hid);
-    {
-        int st = MPNHIP_OK;
-        // (bf16-operand mode: every Linear product rounds its operands -- the GEMM path does that, the fused kernel is fp32)
-        if (m.precision == MPNHIP_PREC_BF16 || !edge_encoder_fused(m.enc_edge, edge_attr, g.perm, hid, save != 0, e0, E, s, &st))
-            MPN_TRY(mlp_forward(m.enc_edge, edge_attr, m.enc_edge.in_dim, g.perm, hid, e0, E, prec, s));
-        else if (st != MPNHIP_OK) return st;
-    }
-
-    const size_t xs = (size_t)N * d.dn, es = (size_t)E * d.de;
-    if (p.eb_hist && p.cb.ok && (!save || p.b16) && es && d.L > 0) MPN_TRY(to_bf16_rows(e0, p.eb_hist, (int64_t)es, s));   // the encoder output as slot 0 of the bf16 mirror
-    if (rows16 && xs && d.L > 0) MPN_TRY(to_bf16_rows(x0, p.xb_hist, (int64_t)xs, s));   // the encoder output as slot 0 of the node mirror
-    // (bf16 rows: the projections multiply [x0 | x] whole -- twice the MFMAs, which this product has to spare, instead of streaming
-    // the [N, pw] fp32 table P0 back in every step)
-    const bool hoist = d.nf == 2 && d.L > 1 && !rows16;
-    // few nodes at the reference's width: P0 and the first step's projections by one small kernel (decided with fuse_node below)
-    const bool proj_small = hoist && d.dn == 32 && N > 0 && N <= 4096 && d.kx == 2 * d.dn && m.precision != MPNHIP_PREC_BF16 &&
-                            ((((uintptr_t)p.Wnode) | ((uintptr_t)p.P0) | ((uintptr_t)x0)) & 15) == 0 && !getenv("MPNHIP_NO_NODE_FUSION");
-    if (hoist && !proj_small) {  // P0 = x0 Wnode[:, :dn]^T + bnode, once per forward
-        GemmArgs a = {};
-        a.ngroups = 1; a.N = d.pw; a.K = d.dn; a.ksplit = d.dn; a.m_upper = N;
-        GemmGroup& G = a.g[0];
-        init_group(G);
-        G.A = x0; G.lda = d.dn; G.B = p.Wnode; G.ldb = d.kx; G.bias = p.bnode; G.C = p.P0; G.ldc = d.pw; G.m_static = N;
-        MPN_TRY(launch_gemm(a, A_KCONTIG, B_KCONTIG, prec, s));
-    }
-    // the same for the edge side of the fused chain: Q0 = e0 W1[:, e0 columns]^T, [E, he] (64 MB at cfg-B), saves a
-    // quarter of the chain's first-layer MFMAs in every step
-    // (measured: pays from de = 32 up; at the reference's de = 16 the extra C-in loads cost more than the one chunk saved)
-    // (FP32_SPLIT: the chain kernel is bound by its row traffic, not by MFMA cycles -- re-reading 4 he bytes per edge and step
-    // costs more than the k blocks it saves: measured 1.59 -> 1.55 ms per cfg-B forward without the hoist)
-    const bool hoist_e = p.cw.ok && !p.cw.split && d.ef == 2 && d.L > 1 && E > 0 && d.de >= 32 && (d.ke - d.de) % 16 == 0 &&
-                         d.de % 16 == 0;
-    if (hoist_e) {
-        GemmArgs a = {};
-        a.ngroups = 1; a.N = d.he; a.K = d.de; a.ksplit = d.de; a.m_upper = E;
-        GemmGroup& G = a.g[0];
-        init_group(G);
-        G.A = e0; G.lda = d.de; G.B = m.edge.weight[0] + 2 * d.kx; G.ldb = m.edge.in_dim; G.C = p.Q0; G.ldc = d.he; G.m_static = E;
-        MPN_TRY(launch_gemm(a, A_KCONTIG, B_KCONTIG, prec, s));
-    }
-    // the reference's node width: the three node-side kernels of a step in one launch (segment.hip, node_step32); needs the
-    // hoisted P0 form of the projections and 16-byte aligned weights; training with max aggregation keeps the separate
-    // kernels (the fused one does not record the arg max)
-    // (every 2-node block re-reads the 43 KB of node-side weights from L2: beyond a few thousand nodes the GEMMs win again)
-    const bool fuse_node32 = (!save || m.agg != MPNHIP_AGG_MAX) && hoist && d.dn == 32 && d.pw % 4 == 0 && E > 0 && N > 0 && N <= 4096 && m.precision != MPNHIP_PREC_BF16 &&
-                             ((((uintptr_t)m.node.weight[0]) | ((uintptr_t)p.P0) | ((uintptr_t)p.Wnode)) & 15) == 0 &&
-                             !getenv("MPNHIP_NO_NODE_FUSION");
-    // wider models in the split precision: the same three launches as one (node_chain.hip)
-    const bool fuse_node_chain = (!save || m.agg != MPNHIP_AGG_MAX) && hoist && p.nc_img && m.precision == MPNHIP_PREC_FP32_SPLIT && E > 0 && N > 0 &&
-                                 m.node.n_layers == 1 && (((uintptr_t)m.node.bias[0]) & 15) == 0;
-    const bool fuse_node = fuse_node32 || fuse_node_chain;
-    if (proj_small) {
-        const int64_t total = N * d.pw;
-        hipLaunchKernelGGL(k_proj_hoist32, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, x0, p.Wnode, p.bnode, p.P0, step_at(p, 0).P,
-                           total, d.pw, d.dn);
-        MPN_LAUNCH_CHECK();
-    }
-    int prev = 0;
-    for (int step = 0; step < d.L; ++step) {
-        int cur = save ? step + 1 : 1 + (step & 1);
-        StepBufs b = step_at(p, step);
-        StepIO io = {};
-        const float* xp = p.x_hist + xs * prev;
-        const float* ep = p.e_hist + es * prev;
-        if (d.nf == 2) { io.xa = x0; io.ldxa = d.dn; io.xb = xp; io.ldxb = d.dn; io.kxa = d.dn; }
-        else { io.xa = xp; io.ldxa = d.dn; }
-        if (d.ef == 2) { io.ea = e0; io.ldea = d.de; io.eb = ep; io.ldeb = d.de; io.kea = d.de; }
-        else { io.ea = ep; io.ldea = d.de; }
-        io.e_new = p.e_hist + es * cur;
-        io.x_new = p.x_hist + xs * cur;
-        io.logits = logits + (size_t)step * E;
-        io.P0 = hoist ? p.P0 : nullptr;
-        if (rows16) {
-            io.Wnode16 = p.Wnode16; io.Wu16 = p.Wu16;
-            io.xa16 = d.nf == 2 ? p.xb_hist : p.xb_hist + xs * prev;
-            io.xb16 = d.nf == 2 ? p.xb_hist + xs * prev : nullptr;
-            io.x_new16 = p.xb_hist + xs * cur;
-        }
-        io.Q0 = hoist_e ? p.Q0 : nullptr;
-        io.fuse_node = fuse_node ? 1 : 0;
-        io.nc_img = fuse_node_chain ? p.nc_img : nullptr;
-        io.p_ready = (fuse_node && step > 0) || (proj_small && step == 0) ? 1 : 0;
-        io.last = step + 1 == d.L ? 1 : 0;
-        io.P_next = io.last ? nullptr : step_at(p, step + 1).P;
-        // (bf16-operand chain: the edge features travel between the steps as bf16 rows; the fp32 ones only where they are returned)
-        // (a graph with nodes and no edges launches no chain kernel: nothing mirrors, run_step takes its E == 0 path)
-        const bool e16_on = p.eb_hist && p.cb.ok && (!save || p.b16) && E > 0;
-        const StepE16 e16 = {p.eb_hist, p.eb_hist ? p.eb_hist + es * prev : nullptr, p.eb_hist ? p.eb_hist + es * cur : nullptr,
-                             step + 1 == d.L};
-        MPN_TRY(run_step(m, d, g, p.Wnode, p.bnode, io, b, save && m.agg == MPNHIP_AGG_MAX, prec, s, &p.cw, save != 0, &p.cb, e16_on ? &e16 : nullptr));
-        prev = cur;
-    }
-    if (d.L == 0 && E > 0) {
-        // mpn.py:387-389: classify the encoder output once
-        StepBufs b = p.step0;
-        const mpnhip_mlp& c = m.classifier;
-        float* hidc[MPNHIP_MAX_LAYERS];
-        for (int i = 0; i < MPNHIP_MAX_LAYERS; ++i) hidc[i] = b.HC[i];
-        if (c.n_layers == 1) {
-            GemmArgs a = {};
-            a.ngroups = 1; a.N = 1; a.K = d.de; a.ksplit = d.de; a.relu = 0; a.m_upper = E;
-            GemmGroup& G = a.g[0];
-            init_group(G);
-            G.A = e0; G.lda = d.de; G.B = c.weight[0]; G.ldb = d.de; G.bias = c.bias[0];
-            G.C = logits; G.ldc = 1; G.c_idx = g.perm; G.m_static = E;
-            MPN_TRY(launch_gemm(a, A_KCONTIG, B_KCONTIG, prec, s));
-        } else {
-            MPN_TRY(linear(e0, d.de, c.weight[0], c.bias[0], hidc[0], c.out_dims[0], E, c.out_dims[0], d.de,
-                           c.out_dims[0] != 1, prec, s));
-            MPN_TRY(mlp_tail(c, nullptr, nullptr, hidc, logits, 1, g.perm, E, prec, s));
-        }
-    }
-    if (x_out && N > 0) MPN_HIP(hipMemcpyAsync(x_out, p.x_hist + xs * prev, xs * sizeof(float), hipMemcpyDeviceToDevice, s));
-    if (e_out) MPN_TRY(scatter_rows(p.e_hist + es * prev, g.perm, e_out, E, d.de, s));
-    return MPNHIP_OK;
+    ForwardRun run(*model, read_switches(), static_cast<hipStream_t>(stream_));
+    MPN_TRY(run.init(graph_buf, n_nodes, n_edges, x, edge_attr, logits, workspace, workspace_bytes, save));
+    MPN_TRY(run.pack_weights());
+    MPN_TRY(run.encode(x, edge_attr));
+    MPN_TRY(run.mirror_encoder_outputs());
+    MPN_TRY(run.hoist_projections());
+    MPN_TRY(run.hoist_edge_share());
+    MPN_TRY(run.hoist_projections32());
+    for (int i = 0; i < run.d.L; ++i) MPN_TRY(run.step(i, logits));
+    MPN_TRY(run.classify_encoder_output(logits));   // (L == 0)
+    return run.write_outputs(x_out, e_out);
 }
 
 // ------------------------------------------------------------------------------------ MetaLayer op
-static size_t plan_meta(const mpnhip_model& m, const Dims& d, int64_t N, int64_t E, void* base, float** Wnode,
-                        float** bnode, StepBufs* sb) {
+// (the part of a FwdPlan one step reads on the all-off route: the packed node weights and one block of step buffers)
+static size_t plan_meta(const mpnhip_model& m, const Dims& d, int64_t N, int64_t E, void* base, FwdPlan* out) {
     Carver a(base);
-    float* w = a.take<float>((size_t)d.pw * d.kx);
-    float* b = a.take<float>((size_t)d.pw);
-    carve_step(a, m, d, N, E, false, false, sb);
-    if (Wnode) *Wnode = w;
-    if (bnode) *bnode = b;
+    FwdPlan p = {};
+    p.Wnode = a.take<float>((size_t)d.pw * d.kx);
+    p.bnode = a.take<float>((size_t)d.pw);
+    carve_step(a, m, d, N, E, false, false, &p.step0);
+    if (out) *out = p;
     return a.bytes();
 }
 
 extern "C" size_t mpnhip_meta_layer_workspace_bytes(const mpnhip_model* model, int n_nodes, int64_t n_edges) {
     Dims d;
     if (!model || check_core(*model, &d, false) != MPNHIP_OK) return 0;
-    return plan_meta(*model, d, n_nodes, n_edges, nullptr, nullptr, nullptr, nullptr);
+    return plan_meta(*model, d, n_nodes, n_edges, nullptr, nullptr);
 }
 
 extern "C" int mpnhip_meta_layer_forward(const mpnhip_model* model, const void* graph_buf, int n_nodes, int64_t n_edges,
                                          const float* x, const float* e, float* x_new, float* e_new, void* workspace,
                                          size_t workspace_bytes, void* stream_) {
-    hipStream_t s = static_cast<hipStream_t>(stream_);
     MPN_CHECK_ARG(model && graph_buf, "meta_layer: null model / graph");
-    Dims d;
-    MPN_TRY(check_core(*model, &d));
-    const int64_t N = n_nodes, E = n_edges;
-    MPN_CHECK_ARG((x && x_new) || N == 0, "meta_layer: null node tensors");
-    MPN_CHECK_ARG((e && e_new) || E == 0, "meta_layer: null edge tensors");
-    float *Wnode, *bnode;
-    StepBufs b;
-    const size_t need = plan_meta(*model, d, N, E, workspace, &Wnode, &bnode, &b);
+    // the full forward's step code on the all-off route (fp32, one launch per product): the operator takes [initial | current] features
+    // whole, in original edge order, so the edge side goes through row indirections no fused kernel reads
+    ForwardRun run(*model, read_switches(), static_cast<hipStream_t>(stream_));
+    const Dims& d = run.d;
+    MPN_TRY(check_core(*model, &run.d));
+    run.N = n_nodes; run.E = n_edges;
+    MPN_CHECK_ARG((x && x_new) || run.N == 0, "meta_layer: null node tensors");
+    MPN_CHECK_ARG((e && e_new) || run.E == 0, "meta_layer: null edge tensors");
+    const size_t need = plan_meta(*model, d, run.N, run.E, workspace, &run.p);
     MPN_CHECK_WORKSPACE("meta_layer", workspace, workspace_bytes, need);
-    GraphView g;
-    graph_layout(n_nodes, n_edges, &g, const_cast<void*>(graph_buf));
-    MPN_TRY(pack_node_weights(*model, d, Wnode, bnode, nullptr, s));
+    graph_layout(n_nodes, n_edges, &run.g, const_cast<void*>(graph_buf));
+    MPN_TRY(pack_node_weights(*model, d, run.p.Wnode, run.p.bnode, nullptr, run.s));
     StepIO io = {};
     io.xa = x; io.ldxa = d.kx;
-    io.ea = e; io.ldea = d.ke; io.e_idx = g.perm;
-    io.e_new = e_new; io.e_new_idx = g.perm; io.e_new_read_idx = g.perm;
+    io.ea = e; io.ldea = d.ke; io.e_idx = run.g.perm;
+    io.e_new = e_new; io.e_new_idx = run.g.perm; io.e_new_read_idx = run.g.perm;
     io.x_new = x_new;
     io.logits = nullptr;
-    return run_step(*model, d, g, Wnode, bnode, io, b, false, MPNHIP_PREC_FP32, s);
+    return run.meta_layer(io, run.p.step0, 0);
 }
 
 // ------------------------------------------------------------------------------------ Linear / MLP ops
@@ -964,8 +994,9 @@ extern "C" int mpnhip_debug_saved(const mpnhip_model* model, const void* graph_b
     Dims d;
     MPN_TRY(check_full(m, &d));
     const int64_t N = n_nodes, E = n_edges;
+    const FwdRoute r = fwd_route(m, d, 1, read_switches());   // (what was saved, and in which form, is the route's to say)
     FwdPlan p;
-    const size_t need = plan_forward(m, d, N, E, 1, const_cast<void*>(fwd_workspace), &p);
+    const size_t need = plan_forward(m, d, r, N, E, const_cast<void*>(fwd_workspace), &p);
     // (a null buffer was refused above as a bad argument: only the size test of the macro is live here)
     MPN_CHECK_WORKSPACE_MSG("debug_saved: workspace", " (must be a save_for_backward buffer)", fwd_workspace, fwd_workspace_bytes, need);
     GraphView g;
@@ -1010,7 +1041,7 @@ extern "C" int mpnhip_debug_saved(const mpnhip_model* model, const void* graph_b
     if (rows_out) *rows_out = rows;
     if (width_out) *width_out = width;
     if (!out || rows * width == 0) return MPNHIP_OK;
-    if (p.b16 && step_ok && E > 0) {
+    if (r.b16 && step_ok && E > 0) {
         // bf16-operand training on the fused kernels: the hidden activations are bf16 rows (returned as floats), and for sum / mean
         // the messages themselves are never stored -- their ReLU decisions are (returned as 1.0 / 0.0: what a test reads them for)
         if (what == MPNHIP_SAVED_EDGE_HIDDEN || what == MPNHIP_SAVED_CLS_HIDDEN || what == MPNHIP_SAVED_FLOW_HIDDEN)
@@ -1035,7 +1066,8 @@ extern "C" int mpnhip_debug_saved(const mpnhip_model* model, const void* graph_b
 extern "C" int mpnhip_edge_chain_active(const mpnhip_model* model) {
     Dims d;
     if (!model || check_full(*model, &d, false) != MPNHIP_OK) return 0;
-    return chain_shapes_ok(*model, d) ? 1 : (chain_bf16_ok(*model, d) ? 2 : 0);
+    const FwdRoute r = fwd_route(*model, d, 0, read_switches());
+    return r.chain ? 1 : (r.chain_bf16 ? 2 : 0);
 }
 
 extern "C" int mpnhip_profile_enable(int on) {

@@ -3,6 +3,7 @@
 #pragma once
 #include <cstdlib>
 #include <cstring>
+#include <unistd.h>   // environ
 
 #include "common.h"
 #include "edge_chain.h"
@@ -82,20 +83,84 @@ static inline int64_t sum_hidden(const mpnhip_mlp& m) {
     return s;
 }
 
+// ------------------------------------------------------------------------------------ the forward's route
+// The orchestration switches of the environment (A-B / tuning; the launchers' own switches stay with the launchers).  Every C
+// entry point that plans or runs reads them ONCE, here, and hands them down -- never cached: tests flip them between calls.
+struct EnvSwitches {
+    bool no_chain, no_chain_bf16, no_chain_bf16_train, no_chain_bf16_e16, no_agg_fusion, no_encoder_fusion, no_node_fusion, no_node_rows16;
+    int chain_split;   // MPNHIP_CHAIN_SPLIT=0/1 overrides the model's precision (-1: not set)
+};
+static inline EnvSwitches read_switches() {
+    // (no MPNHIP_* variable at all -- every run but a test's or a measurement's: ONE pass over the environment instead of nine.  A
+    // training step enters four times, two size queries among them, and 36 getenv calls were 2 us of cfg-D's 0.41 ms)
+    bool any = false;
+    for (char** e = environ; !any && e && *e; ++e) any = (*e)[0] == 'M' && strncmp(*e, "MPNHIP_", 7) == 0;
+    if (!any) return {false, false, false, false, false, false, false, false, -1};
+    const char* const cs = getenv("MPNHIP_CHAIN_SPLIT");
+    return {getenv("MPNHIP_NO_CHAIN") != nullptr, getenv("MPNHIP_NO_CHAIN_BF16") != nullptr, getenv("MPNHIP_NO_CHAIN_BF16_TRAIN") != nullptr,
+            getenv("MPNHIP_NO_CHAIN_BF16_E16") != nullptr, getenv("MPNHIP_NO_AGG_FUSION") != nullptr, getenv("MPNHIP_NO_ENCODER_FUSION") != nullptr,
+            getenv("MPNHIP_NO_NODE_FUSION") != nullptr, getenv("MPNHIP_NO_NODE_ROWS16") != nullptr, cs ? (cs[0] == '1' ? 1 : 0) : -1};
+}
+
+// the fused edge-chain kernels (edge_chain.hip) cover this model's per-edge modules
+static inline bool chain_shapes_ok(const mpnhip_model& m, const Dims& d, const EnvSwitches& sw) {
+    if (sw.no_chain) return false;  // tuning / A-B switch
+    if (m.precision == MPNHIP_PREC_BF16) return false;  // the fused chain kernels compute fp32 results (FP32 / FP32_SPLIT)
+    return m.edge.n_layers == 2 && m.flow_in.n_layers == 2 && m.classifier.n_layers == 2 && m.classifier.out_dims[1] == 1 &&
+           edge_chain_supported(d.he, d.de, d.hn, d.dn, m.classifier.out_dims[0], d.de, d.ef == 2 ? d.de : 0);
+}
+// split (three-piece bf16) weight images and six-product MFMAs in the fused chain kernels: mpnhip_model.precision ==
+// MPNHIP_PREC_FP32_SPLIT (MPNHIP_CHAIN_SPLIT=0/1 in the environment overrides it: A-B switch for measurements)
+static inline bool chain_split(const mpnhip_model& m, const EnvSwitches& sw) {
+    return sw.chain_split >= 0 ? sw.chain_split == 1 : m.precision == MPNHIP_PREC_FP32_SPLIT;
+}
 // the bf16-operand chain kernels (edge_chain_bf16.hip, edge_chain_bf16_bwd.hip) cover this model's per-edge modules
-static inline bool chain_bf16_ok(const mpnhip_model& m, const Dims& d) {
-    if (getenv("MPNHIP_NO_CHAIN") || getenv("MPNHIP_NO_CHAIN_BF16")) return false;
+static inline bool chain_bf16_ok(const mpnhip_model& m, const Dims& d, const EnvSwitches& sw) {
+    if (sw.no_chain || sw.no_chain_bf16) return false;
     return m.precision == MPNHIP_PREC_BF16 && m.edge.n_layers == 2 && m.flow_in.n_layers == 2 && m.classifier.n_layers == 2 &&
            m.classifier.out_dims[1] == 1 && edge_chain_bf16_supported(d.he, d.de, d.hn, d.dn, m.classifier.out_dims[0], d.ef);
 }
 // TRAINING in that mode on the fused kernels (round 4): the forward chain kernel saves the hidden activations as bf16 rows and
 // the ReLU decisions as bits, the backward is one fused chain kernel per step writing bf16 dZ blocks, the weight-gradient and
-// scatter-add kernels read bf16 sources.  One predicate for the forward's and the backward's plans (MPNHIP_NO_CHAIN_BF16_TRAIN=1:
-// round 3's unfused training path, A-B switch).
-static inline bool chain_bf16_train_ok(const mpnhip_model& m, const Dims& d) {
-    return chain_bf16_ok(m, d) && d.L >= 1 && d.he % 8 == 0 && d.de % 8 == 0 && d.hn % 8 == 0 && d.dn % 8 == 0 &&
+// scatter-add kernels read bf16 sources (MPNHIP_NO_CHAIN_BF16_TRAIN=1: round 3's unfused training path, A-B switch).
+static inline bool chain_bf16_train_ok(const mpnhip_model& m, const Dims& d, const EnvSwitches& sw) {
+    return chain_bf16_ok(m, d, sw) && d.L >= 1 && d.he % 8 == 0 && d.de % 8 == 0 && d.hn % 8 == 0 && d.dn % 8 == 0 &&
            m.classifier.out_dims[0] % 8 == 0 && edge_chain_bf16_bwd_supported(d.he, d.de, d.hn, d.dn, m.classifier.out_dims[0]) &&
-           !getenv("MPNHIP_NO_CHAIN_BF16_TRAIN");
+           !sw.no_chain_bf16_train;
+}
+
+// Which way one forward goes: ONE value per call, read by the workspace layout (plan_forward, plan_backward), the orchestration
+// (mpn.hip ForwardRun), the readers of the saves (mpnhip_debug_saved, backward.hip BackwardRun) and mpnhip_edge_chain_active.
+struct FwdRoute {
+    // ---- shape part: fwd_route(), a pure function of (model dims and precision, save, switches) -- the size queries have no more
+    bool save, save_arg;       // training forward: every activation is kept; ... and the arg max of the aggregation (max)
+    bool chain, split;         // the fp32 chain kernel covers the per-edge modules (edge_chain.hip); ... on three-piece bf16 split images
+    bool cb_img, chain_bf16;   // the dims fit the bf16 chain kernel: its pair images are carved whatever the precision; ... and it runs (MPNHIP_PREC_BF16)
+    bool b16;                  // training in that mode on the fused kernels: bf16 saves (implies chain_bf16)
+    bool eb_hist;              // the bf16 mirror of the edge features is carved: b16 training, and bf16 inference where de % 8 == 0
+    bool rows16_planned;       // bf16 images of the node-side weights and mirrors of the node features are carved
+    bool nc_img;               // the unit images of the fused node-side kernel (node_chain.hip) are carved
+    // ---- run part: needs N, E and the carved pointers' alignment; decided and explained in ONE place, mpn.hip ForwardRun::decide
+    bool rows16, hoist, hoist_e, proj_small, fuse_node32, fuse_node_chain, edge_bf16, edge_chain, e16_on, agg_in_kernel, enc_fused;
+};
+
+static inline FwdRoute fwd_route(const mpnhip_model& m, const Dims& d, int save, const EnvSwitches& sw) {
+    FwdRoute r = {};
+    r.save = save != 0;
+    r.save_arg = r.save && m.agg == MPNHIP_AGG_MAX;
+    r.chain = chain_shapes_ok(m, d, sw);
+    r.split = r.chain && chain_split(m, sw);
+    r.cb_img = edge_chain_bf16_supported(d.he, d.de, d.hn, d.dn, m.classifier.n_layers >= 1 ? m.classifier.out_dims[0] : 0, d.ef);
+    r.chain_bf16 = r.cb_img && chain_bf16_ok(m, d, sw);
+    r.b16 = r.save && r.cb_img && chain_bf16_train_ok(m, d, sw);
+    // (inference in the bf16-operand mode keeps the same mirror over its three history slots: the chain kernel reads its first-layer
+    // input as bf16 rows -- the values it rounds to anyway -- and writes the new features as bf16 for the next step)
+    r.eb_hist = r.b16 || (!r.save && r.chain_bf16 && d.L >= 1 && d.de % 8 == 0 && !sw.no_chain_bf16_e16);
+    // (bf16 rows for the tiled / ring GEMM kernels: 16-byte pieces of 8 elements)
+    // (d.pw % 4: launch_gemm's bf16-row path stores 16-byte result vectors -- N = pw of the projections, N = dn of the node update)
+    r.rows16_planned = m.precision == MPNHIP_PREC_BF16 && d.kx % 8 == 0 && d.dn % 8 == 0 && d.pw % 4 == 0 && m.node.n_layers == 1;
+    r.nc_img = node_chain_supported(d.dn, d.pw, d.kx) && m.node.n_layers == 1;
+    return r;
 }
 
 // ------------------------------------------------------------------------------------ workspace
@@ -114,7 +179,7 @@ struct StepBufs {
     float* AGG;                        // [N, 2dn]  [flow_in | flow_out]
     int* ARG;                          // [N, 2dn]  argmax (max aggregation, training only)
     int* MK;                           // ReLU masks of the fused chain kernels as bits (edge_chain.h: chain_mask_ints / chain_bf16_mask_ints)
-    // (FwdPlan::b16 -- bf16-operand training on the fused kernels: HE[0] / HC[0] / HF[0] hold bf16 [E, width] rows, not floats)
+    // (FwdRoute::b16 -- bf16-operand training on the fused kernels: HE[0] / HC[0] / HF[0] hold bf16 [E, width] rows, not floats)
 };
 
 static inline int pad32(int v) { return (v + 31) / 32 * 32; }
@@ -126,15 +191,13 @@ struct ChainWeights {
     float* wc1T;      // [P(de)][32]
     float* wf1T[2];   // [P(de)][P(hn)]  (0: flow_out, 1: flow_in)
     float* wf2T[2];   // [P(hn)][P(dn)]
-    bool ok;          // the model's shapes are covered by the fused kernel
-    bool split;       // the images are three-piece bf16 split images (edge_chain.hip), 3/2 the size, same logical layout
+    // (FwdRoute::split: three-piece bf16 split images (edge_chain.hip), 3/2 the size, same logical layout)
 };
 
 // pair images of the bf16-operand chain kernel (edge_chain_bf16.hip)
 struct ChainBf16 {
     char* img;        // [edge | classifier | flow_out | flow_in]
     size_t off_cls, off_flow[2];
-    bool ok;          // the model's shapes are covered and mpnhip_model.precision == MPNHIP_PREC_BF16
     float* piece;     // scratch of the kernel's fused aggregation (depends on E: carved at the END of the plan)
     int* start_row;
 };
@@ -162,7 +225,6 @@ struct FwdPlan {
     size_t step_stride_bytes;  // 0 when the step buffers are reused (inference)
     float* splitk;             // scratch of the split-K form of the node encoder's layers (few rows, long K), or nullptr
     size_t splitk_floats;
-    bool b16;                  // training in the bf16-operand mode on the fused kernels (chain_bf16_train_ok): bf16 saves
     unsigned short* eb_hist;   // [hist_slots][E, de] bf16 copies of e_hist: the chain kernel's first-layer input (b16 training and
                                // bf16 inference) and, in training, operands of the weight-gradient products; or nullptr
     size_t total;
@@ -205,7 +267,7 @@ static inline StepBufs step_at(const FwdPlan& p, int s) {
 }
 
 // ONE definition, for the forward (mpn.hip) and the backward (backward.hip), of "the node side of this call runs over bf16 rows": the
-// plan carved the images (dims + environment: `rows16` in plan_forward) AND the run-time alignments launch_gemm's bf16-row path insists
+// plan carved the images (dims: FwdRoute::rows16_planned) AND the run-time alignments launch_gemm's bf16-row path insists
 // on hold (16-byte weight / bias bases, whole 16-byte result vectors).  The forward fills xb_hist only under this test; the backward
 // reads it only under the same one.
 static inline bool node_rows16_runtime(const FwdPlan& p, const mpnhip_model& m, const Dims& d) {
@@ -214,7 +276,8 @@ static inline bool node_rows16_runtime(const FwdPlan& p, const mpnhip_model& m, 
            al(m.node.weight[0]) && (!m.node.bias[0] || al(m.node.bias[0]));
 }
 
-static inline size_t plan_forward(const mpnhip_model& m, const Dims& d, int64_t N, int64_t E, int save, void* base, FwdPlan* out) {
+static inline size_t plan_forward(const mpnhip_model& m, const Dims& d, const FwdRoute& r, int64_t N, int64_t E, void* base, FwdPlan* out) {
+    const bool save = r.save;
     Carver a(base);
     FwdPlan p = {};
     // weight images first: their offsets depend on the model's dims only, never on N / E, so a caller that keeps the
@@ -223,7 +286,7 @@ static inline size_t plan_forward(const mpnhip_model& m, const Dims& d, int64_t 
     p.bnode = a.take<float>((size_t)d.pw);
     {
         const size_t HE = pad32(d.he), DE = pad32(d.de), HN = pad32(d.hn), DN = pad32(d.dn);
-        // (sized for the split images, 3/2 of the fp32 ones: ChainWeights.split)
+        // (sized for the split images, 3/2 of the fp32 ones: FwdRoute::split)
         const size_t KE = (size_t)(d.ke + 15) / 16 * 16;
         p.cw.w1T = a.take<float>(KE * HE * 3 / 2);
         p.cw.w2T = a.take<float>(HE * DE * 3 / 2);
@@ -232,24 +295,12 @@ static inline size_t plan_forward(const mpnhip_model& m, const Dims& d, int64_t 
             p.cw.wf1T[q] = a.take<float>(DE * HN * 3 / 2);
             p.cw.wf2T[q] = a.take<float>(HN * DN * 3 / 2);
         }
-        p.cw.ok = false;
     }
-    bool cb_shapes = false;   // (not p.cb.img: the sizing pass runs without a base pointer)
-    {
-        const int hc = m.classifier.n_layers >= 1 ? m.classifier.out_dims[0] : 0;
-        p.cb = {};
-        cb_shapes = edge_chain_bf16_supported(d.he, d.de, d.hn, d.dn, hc, d.ef);
-        if (cb_shapes)
-            p.cb.img = a.take<char>(chain_bf16_image_bytes(d.he, d.de, d.hn, d.dn, hc, d.ef, &p.cb.off_cls, &p.cb.off_flow[0], &p.cb.off_flow[1]));
-    }
-    p.nc_img = nullptr;
-    if (node_chain_supported(d.dn, d.pw, d.kx) && m.node.n_layers == 1)
-        p.nc_img = a.take<unsigned short>(node_chain_image_shorts(d.dn, d.pw, nullptr));
-    // (bf16 rows for the tiled / ring GEMM kernels: 16-byte pieces of 8 elements)
-    // (d.pw % 4: launch_gemm's bf16-row path stores 16-byte result vectors -- N = pw of the projections, N = dn of the node update)
-    const bool rows16 = m.precision == MPNHIP_PREC_BF16 && d.kx % 8 == 0 && d.dn % 8 == 0 && d.pw % 4 == 0 && m.node.n_layers == 1;
-    p.Wnode16 = rows16 ? a.take<unsigned short>((size_t)d.pw * d.kx) : nullptr;
-    p.Wu16 = rows16 ? a.take<unsigned short>((size_t)d.dn * 2 * d.dn) : nullptr;
+    if (r.cb_img)   // (the route, not p.cb.img: the sizing pass runs without a base pointer)
+        p.cb.img = a.take<char>(chain_bf16_image_bytes(d.he, d.de, d.hn, d.dn, m.classifier.out_dims[0], d.ef, &p.cb.off_cls, &p.cb.off_flow[0], &p.cb.off_flow[1]));
+    if (r.nc_img) p.nc_img = a.take<unsigned short>(node_chain_image_shorts(d.dn, d.pw, nullptr));
+    p.Wnode16 = r.rows16_planned ? a.take<unsigned short>((size_t)d.pw * d.kx) : nullptr;
+    p.Wu16 = r.rows16_planned ? a.take<unsigned short>((size_t)d.dn * 2 * d.dn) : nullptr;
     p.P0 = a.take<float>((size_t)N * d.pw);
     p.Q0 = a.take<float>((size_t)E * d.he);
     int hn_ = max_hidden(m.enc_node), he_ = max_hidden(m.enc_edge);
@@ -267,14 +318,10 @@ static inline size_t plan_forward(const mpnhip_model& m, const Dims& d, int64_t 
     p.hist_slots = save ? d.L + 1 : 3;
     p.x_hist = a.take<float>((size_t)p.hist_slots * N * d.dn);
     p.e_hist = a.take<float>((size_t)p.hist_slots * E * d.de);
-    p.xb_hist = rows16 ? a.take<unsigned short>((size_t)p.hist_slots * N * d.dn) : nullptr;
-    p.b16 = save && cb_shapes && chain_bf16_train_ok(m, d);
-    // (inference in the bf16-operand mode keeps the same mirror over its three history slots: the chain kernel reads its first-layer
-    // input as bf16 rows -- the values it rounds to anyway -- and writes the new features as bf16 for the next step)
-    const bool eb_inf = !save && cb_shapes && chain_bf16_ok(m, d) && d.L >= 1 && d.de % 8 == 0 && !getenv("MPNHIP_NO_CHAIN_BF16_E16");
-    p.eb_hist = (p.b16 || eb_inf) ? a.take<unsigned short>((size_t)p.hist_slots * E * d.de) : nullptr;
+    p.xb_hist = r.rows16_planned ? a.take<unsigned short>((size_t)p.hist_slots * N * d.dn) : nullptr;
+    p.eb_hist = r.eb_hist ? a.take<unsigned short>((size_t)p.hist_slots * E * d.de) : nullptr;
     const size_t step0 = a.bytes();
-    carve_step(a, m, d, N, E, true, save && m.agg == MPNHIP_AGG_MAX, &p.step0, p.b16);
+    carve_step(a, m, d, N, E, true, r.save_arg, &p.step0, r.b16);
     p.step_stride_bytes = save && d.L > 1 ? a.repeat(step0, (size_t)d.L) : 0;   // (training: one block per step; inference reuses one)
     {
         size_t sk = 0;
@@ -285,7 +332,7 @@ static inline size_t plan_forward(const mpnhip_model& m, const Dims& d, int64_t 
         p.splitk_floats = sk;
         p.splitk = sk ? a.take<float>(sk) : nullptr;
     }
-    if (cb_shapes && (!save || p.b16)) {
+    if (r.cb_img && (!save || r.b16)) {
         // (the pieces are whole 2 KiB units, so the start rows follow them directly: one scratch of chain_bf16_agg_scratch_floats())
         size_t pieces = 0;
         const size_t fl = chain_bf16_agg_scratch_floats(E, d.dn, &pieces);
@@ -307,21 +354,6 @@ static inline void hidden_ptrs(const mpnhip_mlp& m, float* const two[2], int64_t
             out[i] = two[i & 1];
         }
     }
-}
-
-// the fused edge-chain kernels (edge_chain.hip) cover this model's per-edge modules
-static inline bool chain_shapes_ok(const mpnhip_model& m, const Dims& d) {
-    if (getenv("MPNHIP_NO_CHAIN")) return false;  // tuning / A-B switch
-    if (m.precision == MPNHIP_PREC_BF16) return false;  // the fused chain kernels compute fp32 results (FP32 / FP32_SPLIT)
-    return m.edge.n_layers == 2 && m.flow_in.n_layers == 2 && m.classifier.n_layers == 2 && m.classifier.out_dims[1] == 1 &&
-           edge_chain_supported(d.he, d.de, d.hn, d.dn, m.classifier.out_dims[0], d.de, d.ef == 2 ? d.de : 0);
-}
-
-// split (three-piece bf16) weight images and six-product MFMAs in the fused chain kernels: mpnhip_model.precision ==
-// MPNHIP_PREC_FP32_SPLIT (MPNHIP_CHAIN_SPLIT=0/1 in the environment overrides it: A-B switch for measurements)
-static inline bool chain_split(const mpnhip_model& m) {
-    if (const char* e = getenv("MPNHIP_CHAIN_SPLIT")) return e[0] == '1';
-    return m.precision == MPNHIP_PREC_FP32_SPLIT;
 }
 
 static inline void init_group(GemmGroup& g) { memset(&g, 0, sizeof(g)); }
