@@ -257,6 +257,176 @@ size_t mpnhip_debug_weight_grad_batch_workspace_bytes(const mpnhip_wgrad_product
 int mpnhip_debug_weight_grad_batch(const mpnhip_wgrad_product* products, int n_products, int precision, int batched, int one_launch,
                                    int64_t batch_slab_floats, void* workspace, size_t workspace_bytes, int32_t* chosen, void* stream);
 
+/* Test instrumentation: ONE launch of the fused per-edge chain kernel of a message-passing step (csrc/edge_chain.hip:
+ * edge_chain_kernel, what mpnhip_forward runs per step in MPNHIP_PREC_FP32 and MPNHIP_PREC_FP32_SPLIT) on caller-given tensors, through
+ * the forward's own packer and launcher (pack_chain_weights, launch_edge_chain; with hoist_e0 the forward's Q0 product as well).
+ * Of the model only edge, flow_in, flow_out, classifier (two Linear layers each, with weights and biases), dn, de, agg,
+ * reattach_edges and precision are read; kx, the node columns in front of the edge columns of edge.weight[0] (twice) and of
+ * flow_*.weight[0] (once), is (edge.in_dim - ke) / 2 with ke = (reattach_edges ? 2 : 1) de.  Widths: he = edge.out_dims[0],
+ * hn = flow_*.out_dims[0], hc = classifier.out_dims[0], pw = 2 he + 2 hn.  The entries take flags for what the forward's route would
+ * decide and read none of its MPNHIP_* switches; two switches that the shared LAUNCHERS read themselves still act:
+ * MPNHIP_CHAIN_BF16_PLAIN_BARRIERS (launch_edge_chain_bf16 / _bwd: overrides the plain_barriers flag) and MPNHIP_NO_NODE_CHAIN_BWD
+ * (node_chain_bwd_supported: mpnhip_debug_node_chain_backward then returns MPNHIP_ERR_UNSUPPORTED).
+ * Per-edge tensors cross the ABI in SORTED edge order (position i holds edge perm[i] of the prepared graph: the edges with
+ * row < col first -- group 0, flow_out --, then row > col -- group 1, flow_in --, then the self loops, each group by row); logits is in
+ * ORIGINAL order.  With W1 = edge.weight[0], W2 = edge.weight[1], Wc* = classifier.weight[*], Wf* = the weights of flow_out (group
+ * 0) or flow_in (group 1), r = srow[i], c = scol[i], for every sorted position i < n_edges:
+ *   H1[i]  = relu( [e0[i] | e_prev[i]] W1[:, 2 kx :]^T + P[r][0 .. he) + P[c][he .. 2 he) )       (without re-attachment: e_prev alone)
+ *   e_new[i] = relu( H1[i] W2^T + edge.bias[1] )
+ *   HC[i]  = relu( e_new[i] Wc0^T + classifier.bias[0] );   logits[perm[i]] = HC[i] . Wc1[0] + classifier.bias[1][0]
+ *   and for the edges of groups 0 and 1 only (q = the group):
+ *   HF[i]  = relu( e_new[i] Wf0[:, kx :]^T + P[c][2 he + q hn .. 2 he + (q + 1) hn) )
+ *   msg[i] = relu( HF[i] Wf1^T + flow.bias[1] )
+ * (the first layers' biases and node columns are inside P: the per-node projections, P [N, pw] = [Pr | Pc | Pf_out | Pf_in]).  The rows
+ * of msg and hf at self loops are never written.  Every value that is stored is the fp32 value the next product consumes; nothing
+ * is rounded between the stages.  MPNHIP_PREC_FP32: fp32 MFMAs; _FP32_SPLIT: three bf16 pieces per operand, six products.
+ * save != 0 (training): h1 [E, he], hc [E, hc], hf [E, hn] receive H1, HC, HF as fp32 rows and mask receives the ReLU decisions
+ * of H1 | e_new | HC | HF | msg as bits in the kernels' private layout, mpnhip_debug_edge_chain_mask_ints(model, n_edges) words of
+ * which none past that count is written: the buffer mpnhip_debug_edge_chain_backward reads.  save == 0: the four are ignored.
+ * hoist_e0 != 0 (MPNHIP_PREC_FP32 with re-attachment, de >= 32 and de % 16 == 0 only -- where mpnhip_forward takes this form): Q0 = e0 W1[:, 2 kx : 2 kx + de]^T is computed first
+ * (one GEMM launch, counted as such) and the kernel starts H1 from P[r] + Q0[i] and multiplies e_prev only -- the same H1.
+ * workspace: mpnhip_debug_edge_chain_forward_workspace_bytes(model, n_edges) (weight images and Q0).
+ * Checked on the host before any launch: a null model / graph / io, inconsistent model dims, negative sizes, hoist_e0 where it
+ * does not apply (MPNHIP_ERR_ARG); MLP depths other than two, MPNHIP_PREC_BF16, widths edge_chain_supported refuses -- tiles of
+ * 32 other than (he, de, hn, dn) = (10, 2, 7, 4), (5, 1, 4, 2), (3, 1, 2, 1), hc > 32, a width that is no multiple of 4, de no multiple
+ * of 16 -- (MPNHIP_ERR_UNSUPPORTED; the size queries then return 0); then, with edges (n_edges == 0 is a successful no-op): null
+ * tensors, save without its four buffers, a matrix or workspace that is not 16-byte aligned (MPNHIP_ERR_ARG), a short workspace
+ * (MPNHIP_ERR_WORKSPACE).  A successful call with edges adds 1 to "edge_chain_fwd" (FP32) or "edge_chain_fwd_split". */
+typedef struct mpnhip_debug_edge_chain_fwd {
+    const float* P; const float* e0; const float* e_prev;      /* e0: NULL without re-attachment */
+    float* e_new; float* msg; float* logits;                   /* [E, de], [E, dn], [E] */
+    float* h1; float* hc; float* hf; uint32_t* mask;           /* save != 0 */
+    int save; int hoist_e0;
+} mpnhip_debug_edge_chain_fwd;
+size_t mpnhip_debug_edge_chain_mask_ints(const mpnhip_model* model, int64_t n_edges);
+size_t mpnhip_debug_edge_chain_forward_workspace_bytes(const mpnhip_model* model, int64_t n_edges);
+int mpnhip_debug_edge_chain_forward(const mpnhip_model* model, const void* graph_buf, int n_nodes, int64_t n_edges,
+                                    const mpnhip_debug_edge_chain_fwd* io, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Test instrumentation: ONE launch of the backward of the same chain (csrc/edge_chain.hip: edge_chain_bwd_kernel, steps B1 - B6),
+ * through the backward's packer and launcher (pack_chain_bwd_weights, launch_edge_chain_bwd), on the mask buffer a call of
+ * mpnhip_debug_edge_chain_forward (save != 0, same model and graph) left.  Model, orders and names as above; [X > 0] are the
+ * decisions in the mask buffer.  For every sorted position i, with r = srow[i]:
+ *   B1 (groups 0, 1)  g = dAGG[r][dn .. 2 dn) (group 0) or dAGG[r][0 .. dn) (group 1);
+ *                     MEAN: g /= max(count of r's segment in the group, 1);  MAX: g[k] = ARG[r][that column] == i ? g[k] : 0
+ *                     dZM[i] = g (.) [msg[i] > 0]
+ *   B2                dZF[i] = (dZM[i] Wf1) (.) [HF[i] > 0]
+ *   B3                dE' = dE_io[i] + dZF[i] Wf0[:, kx :]                            (self loops: dE' = dE_io[i])
+ *   B4                dZc[i] = dlog[perm[i]] Wc1[0] (.) [HC[i] > 0];  dE' += dZc[i] Wc0;  dZ2[i] = dE' (.) [e_new[i] > 0]
+ *   B5                dZ1[i] = (dZ2[i] W2) (.) [H1[i] > 0]
+ *   B6                [d0 | dp] = dZ1[i] W1[:, 2 kx :]     (without re-attachment: dp alone)
+ *                     dE0[i] += d0  (not with skip_e0);   first_step ? dE0[i] += dp : dEprev[i] = dp
+ * dAGG [N, 2 dn] = [flow_in | flow_out]; ARG (MAX only) [N, 2 dn] int32: the SORTED position the forward's maximum took, -1 for none;
+ * dlog [E] in ORIGINAL order; dE_io [E, de]: in, the gradient with respect to e_new arriving from the later step; out, dZ2 (written
+ * in place).  Outputs dZM [E, dn], dZF [E, hn] (rows of self loops are never written), dZc [E, hc], dZ1 [E, he]; dE0 [E, de] is
+ * accumulated into what the caller put there; dEprev [E, de] (may be NULL with first_step).  skip_e0 != 0 (re-attachment and
+ * 32 < de <= 64 only): the e0 half of B6 is left to the caller (mpnhip_backward takes it as one product over the sum of the steps'
+ * dZ1), dE0 then receives only the first step's dp.  Every stage consumes the fp32 value it stores.
+ * workspace: mpnhip_debug_edge_chain_backward_workspace_bytes(model) (the weight images).
+ * Host-side refusals as for the forward (skip_e0 where it does not apply: MPNHIP_ERR_ARG; ARG is required for MAX).  A successful
+ * call with edges adds 1 to "edge_chain_bwd" (FP32), "edge_chain_bwd_split" or "edge_chain_bwd_bf16" and to no other counter.
+ * MPNHIP_PREC_BF16 (csrc/edge_chain_bf16_bwd.hip: edge_chain_bf16_bwd_kernel through pack_chain_bf16_bwd_weights and
+ * launch_edge_chain_bf16_bwd; re-attached edge features and widths that are multiples of 8 which edge_chain_bf16_bwd_supported
+ * takes, else MPNHIP_ERR_UNSUPPORTED), on the mask buffer mpnhip_debug_edge_chain_bf16_forward (save != 0) left.  The same steps
+ * with bf(.) = nearest-even bfloat16 on BOTH operands of every product, fp32 sums:
+ *   dZM = bf(g (.) [msg > 0]);  dZF = bf((dZM bf(Wf1)) (.) [HF > 0]);  dZc = bf(dlog[perm[i]] bf(Wc1[0]) (.) [HC > 0])   (dlog unrounded)
+ *   dZ2 = bf((dE_io[i] + dZF bf(Wf0e) + dZc bf(Wc0)) (.) [e_new > 0]);  dZ1 = bf((dZ2 bf(W2)) (.) [H1 > 0])
+ *   dp = dZ1 bf(W1[:, 2 kx + de :])  (fp32);  first_step ? dE0[i] += dp : dEprev[i] = dp
+ * Every dZ is rounded once and the rounded value is both stored and fed.  The five dZ blocks are bf16 ROWS (uint16 [E, width] behind the
+ * void pointers, dZ2 a buffer of its own); dE_io is read only; the e0 half of B6 is never computed (skip_e0 is ignored: mpnhip_backward
+ * always takes it as one product after the step loop), so dE0 is touched at the first step only and dEprev at the others only.
+ * plain_barriers: passed to the launcher (the fp32 kernels ignore it). */
+typedef struct mpnhip_debug_edge_chain_bwd {
+    const float* dAGG; const int32_t* ARG; const float* dlog; const uint32_t* mask;
+    float* dE_io; void* dZM; void* dZF; void* dZc; void* dZ1; float* dE0; float* dEprev;
+    void* dZ2;                                                  /* MPNHIP_PREC_BF16 only */
+    int first_step; int skip_e0; int plain_barriers;
+} mpnhip_debug_edge_chain_bwd;
+size_t mpnhip_debug_edge_chain_backward_workspace_bytes(const mpnhip_model* model);
+int mpnhip_debug_edge_chain_backward(const mpnhip_model* model, const void* graph_buf, int n_nodes, int64_t n_edges,
+                                     const mpnhip_debug_edge_chain_bwd* io, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Test instrumentation: ONE launch of the bf16-operand forward chain kernel (csrc/edge_chain_bf16.hip: edge_chain_bf16_kernel, what
+ * mpnhip_forward runs per step in MPNHIP_PREC_BF16), through pack_chain_bf16_weights and launch_edge_chain_bf16.  Model, orders and
+ * formulas as for mpnhip_debug_edge_chain_forward (re-attached edge features are required), with bf(.) = round to nearest-even
+ * bfloat16 applied to BOTH operands of every product and everything else in fp32:
+ *   H1 = relu(bf([e0 | e_prev]) bf(W1e)^T + P[r] + P[c]);  the kernel keeps and feeds bf(H1)
+ *   e_new = relu(bf(H1) bf(W2)^T + b2)  (fp32, stored);     e16 = bf(e_new) is what the classifier and the flow MLPs consume
+ *   HC = relu(e16 bf(Wc0)^T + bc0);  logits[perm[i]] = sum_k bf(Wc1[0][k]) bf(HC[k]) + bc1   (an fp32 fma chain)
+ *   HF = relu(e16 bf(Wf0e)^T + Pf[c]);  msg = relu(bf(HF) bf(Wf1)^T + bf2)  (fp32)                 (groups 0 and 1 only)
+ * The ReLU decisions are taken on the ROUNDED values (bf(H1) > 0, e16 > 0, bf(HC) > 0, bf(HF) > 0) and on the fp32 msg.
+ * Flags: save (the SAVE variant: widths multiples of 8 that edge_chain_bf16_bwd_supported takes); rows16 (de % 8 == 0: the entry rounds
+ * e0 / e_prev to bf16 rows with the forward's own to_bf16_rows and the kernel reads those -- the same values -- and writes e16);
+ * fused_agg (the kernel aggregates: agg_out [N, 2 dn] = [flow_in | flow_out] of msg by model.agg, zero-filled first, msg is not written);
+ * plain_barriers (__syncthreads at the weight-chunk ends instead of the counted waits).
+ * Outputs: e_new [E, de], msg [E, dn] (or agg_out), in SORTED order; logits [E] in ORIGINAL order.  With save or rows16: e16 [E, de], the
+ * bf16 mirror decoded to floats; with save also h1 [E, he], hc [E, hc], hf [E, hn] (the bf16 rows the kernel keeps, decoded) and the five
+ * decision sections dec_h1 | dec_e | dec_hc | dec_hf | dec_m as 1.0 / 0.0 floats (self loops: 0 in dec_hf / dec_m) -- ALL decoded
+ * tensors come back in ORIGINAL edge order, as mpnhip_debug_saved gives them (chain_bf16_debug_rows / chain_bf16_debug_mask); the raw
+ * bits stay in mask, mpnhip_debug_edge_chain_bf16_mask_ints(model, n_edges) words of which none past that count is written.
+ * mpnhip_debug_edge_chain_bf16_geometry reports the edges and waves per block of the launch (0: widths the kernel does not take).
+ * workspace: mpnhip_debug_edge_chain_bf16_forward_workspace_bytes(model, n_edges).  Host-side refusals as for the fp32 entry; any other
+ * precision, widths edge_chain_bf16_supported refuses, save / rows16 at widths they do not take: MPNHIP_ERR_UNSUPPORTED.  A successful
+ * call with edges adds 1 to "edge_chain_fwd_bf16" and to no other counter. */
+typedef struct mpnhip_debug_edge_chain_bf16_fwd {
+    const float* P; const float* e0; const float* e_prev;
+    float* e_new; float* msg; float* agg_out; float* logits;
+    float* e16; float* h1; float* hc; float* hf;
+    float* dec_h1; float* dec_e; float* dec_hc; float* dec_hf; float* dec_m;
+    uint32_t* mask;
+    int save; int rows16; int fused_agg; int plain_barriers;
+} mpnhip_debug_edge_chain_bf16_fwd;
+size_t mpnhip_debug_edge_chain_bf16_mask_ints(const mpnhip_model* model, int64_t n_edges);
+size_t mpnhip_debug_edge_chain_bf16_forward_workspace_bytes(const mpnhip_model* model, int64_t n_edges);
+void mpnhip_debug_edge_chain_bf16_geometry(const mpnhip_model* model, int32_t* edges_per_block, int32_t* waves_per_block);
+int mpnhip_debug_edge_chain_bf16_forward(const mpnhip_model* model, const void* graph_buf, int n_nodes, int64_t n_edges,
+                                         const mpnhip_debug_edge_chain_bf16_fwd* io, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Test instrumentation: ONE launch of the fused node-side kernel of a message-passing step (csrc/node_chain.hip:
+ * node_chain_kernel, what mpnhip_forward runs per step in MPNHIP_PREC_FP32_SPLIT at dn = 64 / 128), on caller-given tensors, through
+ * the forward's own packer and launcher (pack_node_chain, launch_node_chain).  On a prepared graph (mpnhip_graph_prep) with
+ * seg_ptr the CSR over the keys dir * N + row of the SORTED edge order (dir 0: row < col, flow_out; 1: row > col, flow_in; self
+ * loops are in neither), for every node n < n_nodes:
+ *   AGG[n][0 .. dn)      = agg over j in [seg_ptr[N + n], seg_ptr[N + n + 1]) of M[j][:]          (flow_in)
+ *   AGG[n][dn .. 2 dn)   = agg over j in [seg_ptr[n], seg_ptr[n + 1]) of M[j][:]                  (flow_out)
+ *       agg = MPNHIP_AGG_SUM: the sum in ascending j; _MEAN: that sum times 1 / max(count, 1); _MAX: the maximum; an empty segment
+ *       gives 0 with all three
+ *   x_new[n][o]          = max(sum_{k < 2 dn} Wu[o][k] AGG[n][k] + bu[o], 0)                       o < dn
+ *   P_next[n][p]         = P0[n][p] + sum_{k < dn} Wnode[p][dn + k] x_new[n][k]                    p < pw
+ * M [E, dn] in SORTED edge order; Wu [dn, 2 dn], bu [dn]; Wnode [pw, 2 dn]: the packed projection weights, of which only the
+ * current-feature columns [dn, 2 dn) are read; P0, P_next [N, pw]; x_new [N, dn]; agg_out [N, 2 dn] receives AGG.  P_next (the last
+ * step has none; P0 may then be NULL too) and agg_out (inference) may each be NULL.  Both products take their fp32 operands as three
+ * bf16 pieces (MPNHIP_PREC_FP32_SPLIT): nothing is rounded to bf16; AGG is stored as the fp32 value that is multiplied, and
+ * P_next is computed from the fp32 x_new that is stored.  Nothing but rows [0, N) of the three outputs is written.
+ * workspace: mpnhip_debug_node_chain_workspace_bytes(dn, pw) bytes (the weight images; 0: widths the kernel does not take).
+ * Checked on the host before any launch: negative sizes, an unknown agg, a null graph (MPNHIP_ERR_ARG); widths other than
+ * dn in {64, 128} with pw a positive multiple of 32 (MPNHIP_ERR_UNSUPPORTED); then, with n_nodes > 0 (n_nodes == 0 is a successful
+ * no-op): null Wu / bu / Wnode / x_new, null M with edges, P_next without P0, a pointer among M, bu, P0, x_new, P_next, agg_out or
+ * the workspace that is not 16-byte aligned (MPNHIP_ERR_ARG); a null or short workspace (MPNHIP_ERR_WORKSPACE).  A successful call
+ * with nodes adds 1 to the path counter "node_chain" and to no other. */
+size_t mpnhip_debug_node_chain_workspace_bytes(int dn, int pw);
+int mpnhip_debug_node_chain(const void* graph_buf, int n_nodes, int64_t n_edges, const float* M, int dn, int pw, int agg,
+                            const float* Wu, const float* bu, const float* Wnode, const float* P0, float* x_new, float* P_next,
+                            float* agg_out, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Test instrumentation: ONE launch of the node side of a backward step (csrc/node_chain.hip: node_chain_bwd_kernel; what
+ * mpnhip_backward runs between two steps in MPNHIP_PREC_FP32_SPLIT at dn = 64 / 128), through pack_node_chain_bwd and
+ * launch_node_chain_bwd.  For every node n < n_nodes:
+ *   dX[n][k]    = sum_{p < pw} dP[n][p] Wnode[p][dn + k]                                           k < dn
+ *   dZn[n][k]   = x_prev[n][k] > 0 ? dX[n][k] : 0
+ *   dAGG[n][c]  = sum_{k < dn} dZn[n][k] Wu[k][c]                                                  c < 2 dn
+ * dP [N, pw]: the gradient of a step's projections; x_prev [N, dn]: the output of the previous step's node update, read only for
+ * its sign (a NaN counts as not positive); Wnode [pw, 2 dn] and Wu [dn, 2 dn] as above; outputs dZn [N, dn] and dAGG [N, 2 dn], rows
+ * [0, N) only.  Three-piece operands as above; dAGG is computed from the fp32 dZn that is stored.
+ * workspace: mpnhip_debug_node_chain_backward_workspace_bytes(dn, pw) bytes (0: widths the kernel does not take).
+ * Checked on the host before any launch: negative sizes (MPNHIP_ERR_ARG); widths other than dn in {64, 128} with pw >= 64 a multiple
+ * of 16 (MPNHIP_ERR_UNSUPPORTED); then, with n_nodes > 0: a null pointer, a pointer among dP, x_prev, dZn, dAGG or the workspace
+ * that is not 16-byte aligned (MPNHIP_ERR_ARG); a null or short workspace (MPNHIP_ERR_WORKSPACE).  A successful call with nodes adds
+ * 1 to the path counter "node_chain_bwd" and to no other. */
+size_t mpnhip_debug_node_chain_backward_workspace_bytes(int dn, int pw);
+int mpnhip_debug_node_chain_backward(int n_nodes, const float* dP, int dn, int pw, const float* x_prev, const float* Wnode,
+                                     const float* Wu, float* dZn, float* dAGG, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Graph preparation -- replaces the six boolean-mask indexings per step of
  * TimeAwareNodeModel.forward (models/mpn.py:85-87,91-93) and the implicit index structures behind

@@ -111,6 +111,25 @@ class ConvArgs(C.Structure):
     ]
 
 
+class DebugEdgeChainFwd(C.Structure):
+    """``mpnhip_debug_edge_chain_fwd`` (include/mpnhip.h)."""
+    _fields_ = [(n, C.c_void_p) for n in ("P", "e0", "e_prev", "e_new", "msg", "logits", "h1", "hc", "hf", "mask")] + \
+               [("save", C.c_int), ("hoist_e0", C.c_int)]
+
+
+class DebugEdgeChainBf16Fwd(C.Structure):
+    """``mpnhip_debug_edge_chain_bf16_fwd`` (include/mpnhip.h)."""
+    _fields_ = [(n, C.c_void_p) for n in ("P", "e0", "e_prev", "e_new", "msg", "agg_out", "logits", "e16", "h1", "hc", "hf", "dec_h1", "dec_e",
+                                          "dec_hc", "dec_hf", "dec_m", "mask")] + \
+               [(n, C.c_int) for n in ("save", "rows16", "fused_agg", "plain_barriers")]
+
+
+class DebugEdgeChainBwd(C.Structure):
+    """``mpnhip_debug_edge_chain_bwd`` (include/mpnhip.h)."""
+    _fields_ = [(n, C.c_void_p) for n in ("dAGG", "ARG", "dlog", "mask", "dE_io", "dZM", "dZF", "dZc", "dZ1", "dE0", "dEprev", "dZ2")] + \
+               [("first_step", C.c_int), ("skip_e0", C.c_int), ("plain_barriers", C.c_int)]
+
+
 # name -> (restype, argtypes); mirrors include/mpnhip.h one to one (tests/test_capi_symbols.py
 # checks that every function the header declares is listed here and exported by the library)
 _P, _I, _L, _Z = C.c_void_p, C.c_int, C.c_int64, C.c_size_t
@@ -129,6 +148,19 @@ SIGNATURES = {
                                         _P]),
     "mpnhip_debug_weight_grad_batch_workspace_bytes": (_Z, [C.POINTER(WgradProduct), _I, _I, _I, _L]),
     "mpnhip_debug_weight_grad_batch": (_I, [C.POINTER(WgradProduct), _I, _I, _I, _I, _L, _P, _Z, C.POINTER(C.c_int32), _P]),
+    "mpnhip_debug_edge_chain_mask_ints": (_Z, [C.POINTER(Model), _L]),
+    "mpnhip_debug_edge_chain_forward_workspace_bytes": (_Z, [C.POINTER(Model), _L]),
+    "mpnhip_debug_edge_chain_forward": (_I, [C.POINTER(Model), _P, _I, _L, C.POINTER(DebugEdgeChainFwd), _P, _Z, _P]),
+    "mpnhip_debug_edge_chain_backward_workspace_bytes": (_Z, [C.POINTER(Model)]),
+    "mpnhip_debug_edge_chain_backward": (_I, [C.POINTER(Model), _P, _I, _L, C.POINTER(DebugEdgeChainBwd), _P, _Z, _P]),
+    "mpnhip_debug_edge_chain_bf16_mask_ints": (_Z, [C.POINTER(Model), _L]),
+    "mpnhip_debug_edge_chain_bf16_forward_workspace_bytes": (_Z, [C.POINTER(Model), _L]),
+    "mpnhip_debug_edge_chain_bf16_geometry": (None, [C.POINTER(Model), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "mpnhip_debug_edge_chain_bf16_forward": (_I, [C.POINTER(Model), _P, _I, _L, C.POINTER(DebugEdgeChainBf16Fwd), _P, _Z, _P]),
+    "mpnhip_debug_node_chain_workspace_bytes": (_Z, [_I, _I]),
+    "mpnhip_debug_node_chain": (_I, [_P, _I, _L, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _P]),
+    "mpnhip_debug_node_chain_backward_workspace_bytes": (_Z, [_I, _I]),
+    "mpnhip_debug_node_chain_backward": (_I, [_I, _P, _I, _I, _P, _P, _P, _P, _P, _P, _Z, _P]),
     "mpnhip_graph_bytes": (_Z, [_I, _L]),
     "mpnhip_graph_prep_workspace_bytes": (_Z, [_I, _L]),
     "mpnhip_graph_prep": (_I, [_P, _I, _L, _P, _Z, _P, _Z, _P]),

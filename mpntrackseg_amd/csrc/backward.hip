@@ -458,6 +458,95 @@ static inline unsigned short* w16(float* p0, int64_t elems) { return reinterpret
 
 static bool backward_forks(const mpnhip_model& m) { return m.num_enc_steps >= 4; }
 
+// The weight images of edge_chain_bwd_kernel (caller's stream): one launch for the eight of them
+int pack_chain_bwd_weights(const mpnhip_model& m, const Dims& d, const ChainBwdImages& p, bool bwd_split, hipStream_t s) {
+    const int he = d.he, de = d.de, hn = d.hn, dn = d.dn, kx = d.kx;
+    const int HE = pad32(he), DE = pad32(de), HN = pad32(hn), DN = pad32(dn);
+    const int KEp = d.ef * DE;
+    const mpnhip_mlp* fl[2] = {&m.flow_out, &m.flow_in};
+    const int ncol6 = KEp < 64 ? KEp : 64;
+    if (bwd_split) {
+        // the same logical images (rows = contraction index n, columns = k) as split images (edge_chain.hip, split8);
+        // recorded and packed by one launch (pack_split cannot fail once its sizes are valid: nothing returns before the flush)
+        SplitBatch sb;
+        for (int q = 0; q < 2; ++q) {
+            MPN_TRY(pack_split(fl[q]->weight[1], hn, 1, dn, hn, DN, HN, p.wf2p[q], &sb, s));
+            MPN_TRY(pack_split(fl[q]->weight[0] + kx, fl[q]->in_dim, 1, hn, de, HN, DE, p.wfep[q], &sb, s));
+        }
+        MPN_TRY(pack_split(m.classifier.weight[0], de, 1, m.classifier.out_dims[0], de, 32, DE, p.wc1p, &sb, s));
+        MPN_TRY(pack_split(m.edge.weight[1], he, 1, de, he, DE, HE, p.w2p, &sb, s));
+        for (int hlf = 0; hlf < d.ef; ++hlf) {
+            const int col0 = hlf * DE;
+            MPN_TRY(pack_split(m.edge.weight[0] + 2 * kx + hlf * de, m.edge.in_dim, 1, he, de, HE, DE,
+                               p.w1ep + (int64_t)(col0 / 64) * HE * ncol6 * 3 / 2, &sb, s, ncol6 / 32, (col0 % 64) / 32));
+        }
+        return split_batch_flush(&sb, s);
+    }
+    PackBatch pb;   // (the eight images as one launch)
+    for (int q = 0; q < 2; ++q) {
+        MPN_TRY(pack_padded(fl[q]->weight[1], hn, 0, dn, hn, p.wf2p[q], DN, HN, HN, 0, &pb, s));
+        MPN_TRY(pack_padded(fl[q]->weight[0], fl[q]->in_dim, kx, hn, de, p.wfep[q], HN, DE, DE, 0, &pb, s));
+    }
+    MPN_TRY(pack_padded(m.classifier.weight[0], de, 0, m.classifier.out_dims[0], de, p.wc1p, 32, DE, DE, 0, &pb, s));
+    MPN_TRY(pack_padded(m.edge.weight[1], he, 0, de, he, p.w2p, DE, HE, HE, 0, &pb, s));
+    // e-part columns of edge layer 0 as one image [HE][ncol6] per pass of <= 64 (padded) columns of [e0 | e_{s-1}]
+    // (the kernel streams whole rows of one pass image)
+    for (int hlf = 0; hlf < d.ef; ++hlf) {
+        const int col0 = hlf * DE;
+        MPN_TRY(pack_padded(m.edge.weight[0], m.edge.in_dim, 2 * kx + hlf * de, he, de,
+                            p.w1ep + (int64_t)(col0 / 64) * HE * ncol6, HE, DE, ncol6, col0 % 64, &pb, s));
+    }
+    return pack_batch_flush(&pb, s);
+}
+
+// The pair images of edge_chain_bf16_bwd_kernel (caller's stream)
+int pack_chain_bf16_bwd_weights(const mpnhip_model& m, const Dims& d, const ChainBf16BwdImages& im, hipStream_t s) {
+    const float* f0[2] = {m.flow_out.weight[0], m.flow_in.weight[0]};
+    const float* f1[2] = {m.flow_out.weight[1], m.flow_in.weight[1]};
+    return pack_chain_bf16_bwd(m.edge.weight[0], m.edge.in_dim, 2 * d.kx + d.de, m.edge.weight[1], m.classifier.weight[0], f0, m.flow_out.in_dim,
+                               d.kx, f1, d.he, d.de, d.hn, d.dn, m.classifier.out_dims[0], im.img, s);
+}
+
+// What one launch of a backward chain kernel reads and writes besides the model, the graph and the weight images (fp32 / split:
+// dE_io in and out, dZ2 unused; bf16: dE_io is read only, the five dZ blocks are bf16 rows behind the float pointers)
+struct ChainBwdIO {
+    const float* dAGG; const unsigned* mask; const int* ARG; const float* dlog;
+    float* dE_io; float* dZM; float* dZF; float* dZc; float* dZ2; float* dZ1; float* dE0; float* dEprev;
+    int first_step, skip_e0, plain_barriers;
+};
+// The arguments of edge_chain_bwd_kernel for one step (BackwardRun::edge_side_chain; mpnhip_debug_edge_chain_backward)
+static EdgeChainBwdArgs chain_bwd_args(const mpnhip_model& m, const Dims& d, const GraphView& g, int64_t N, int64_t E, const ChainBwdImages& im,
+                                       bool split, const ChainBwdIO& io) {
+    EdgeChainBwdArgs a = {};
+    a.E = (int)E; a.N = (int)N; a.agg = m.agg; a.first_step = io.first_step ? 1 : 0; a.cat_two = d.ef == 2 ? 1 : 0; a.split = split ? 1 : 0;
+    a.skip_e0 = io.skip_e0 ? 1 : 0;
+    a.he = d.he; a.de = d.de; a.hn = d.hn; a.dn = d.dn; a.hc = m.classifier.out_dims[0];
+    a.header = g.header; a.srow = g.srow; a.perm = g.perm; a.seg_ptr = g.seg_ptr;
+    a.dAGG = io.dAGG; a.mask = io.mask; a.ARG = io.ARG; a.dlog = io.dlog;
+    a.dE_io = io.dE_io; a.dZM = io.dZM; a.dZF = io.dZF; a.dZc = io.dZc; a.dZ1 = io.dZ1;
+    a.dE0 = io.dE0; a.dEprev = io.first_step ? io.dE0 : io.dEprev;   // (the first step's e_{s-1} IS the re-attached e0)
+    a.wf2_out = im.wf2p[0]; a.wf2_in = im.wf2p[1]; a.wfe_out = im.wfep[0]; a.wfe_in = im.wfep[1];
+    a.wc1 = im.wc1p; a.wc2 = m.classifier.weight[1]; a.w2 = im.w2p; a.w1e = im.w1ep;
+    return a;
+}
+// ... and of edge_chain_bf16_bwd_kernel (BackwardRun::edge_side_bf16; mpnhip_debug_edge_chain_backward in MPNHIP_PREC_BF16)
+static EdgeChainBf16BwdArgs chain_bf16_bwd_args(const mpnhip_model& m, const Dims& d, const GraphView& g, int64_t N, int64_t E,
+                                                const ChainBf16BwdImages& im, const ChainBwdIO& io) {
+    auto r16 = [](float* q) { return reinterpret_cast<unsigned short*>(q); };
+    EdgeChainBf16BwdArgs a = {};
+    a.E = (int)E; a.N = (int)N; a.agg = m.agg; a.first_step = io.first_step ? 1 : 0;
+    a.he = d.he; a.de = d.de; a.hn = d.hn; a.dn = d.dn; a.hc = m.classifier.out_dims[0];
+    a.plain_barriers = io.plain_barriers ? 1 : 0;
+    a.header = g.header; a.srow = g.srow; a.perm = g.perm; a.seg_ptr = g.seg_ptr;
+    a.dAGG = io.dAGG; a.mask = io.mask; a.ARG = io.ARG; a.dlog = io.dlog;
+    a.dE_in = io.dE_io;
+    a.dZM = r16(io.dZM); a.dZF = r16(io.dZF); a.dZc = r16(io.dZc); a.dZ2 = r16(io.dZ2); a.dZ1 = r16(io.dZ1);
+    a.dE0 = io.dE0; a.dEprev = io.dEprev;
+    a.img_edge = im.img; a.img_cls = im.img + im.off_cls; a.img_flow[0] = im.img + im.off_flow[0]; a.img_flow[1] = im.img + im.off_flow[1];
+    a.wc2 = m.classifier.weight[1];
+    return a;
+}
+
 // One call of mpnhip_backward_flags: constructed in that call's frame, its methods are the phases of the backward in the order
 // mpnhip_backward_flags calls them.  Every method returns an MPNHIP_* status; after a failure the object is only destroyed (which
 // orders the caller's stream behind whatever was forked: SideJoin).
@@ -644,49 +733,12 @@ struct BackwardRun {
     // ---- weight images of the chain kernels (caller's stream): bf16 pair images, the split or padded fp32 images, the node chain's ---
     int pack_weights() {
         if (use_b16) {
-            const float* f0[2] = {m.flow_out.weight[0], m.flow_in.weight[0]};
-            const float* f1[2] = {m.flow_out.weight[1], m.flow_in.weight[1]};
-            MPN_TRY(pack_chain_bf16_bwd(m.edge.weight[0], m.edge.in_dim, 2 * kx + de, m.edge.weight[1], m.classifier.weight[0], f0, m.flow_out.in_dim, kx, f1,
-                                        he, de, hn, dn, m.classifier.out_dims[0], p.cb16_img, s));
+            const ChainBf16BwdImages im = {p.cb16_img, p.cb16_off_cls, {p.cb16_off_flow[0], p.cb16_off_flow[1]}};
+            MPN_TRY(pack_chain_bf16_bwd_weights(m, d, im, s));
         }
         if (use_chain) {
-            const int HE = pad32(he), DE = pad32(de), HN = pad32(hn), DN = pad32(dn);
-            const int KEp = d.ef * DE;
-            const mpnhip_mlp* fl[2] = {&m.flow_out, &m.flow_in};
-            const int ncol6 = KEp < 64 ? KEp : 64;
-            if (bwd_split) {
-                // the same logical images (rows = contraction index n, columns = k) as split images (edge_chain.hip, split8);
-                // recorded and packed by one launch (pack_split cannot fail once its sizes are valid: nothing returns before the flush)
-                SplitBatch sb;
-                for (int q = 0; q < 2; ++q) {
-                    MPN_TRY(pack_split(fl[q]->weight[1], hn, 1, dn, hn, DN, HN, p.wf2p[q], &sb, s));
-                    MPN_TRY(pack_split(fl[q]->weight[0] + kx, fl[q]->in_dim, 1, hn, de, HN, DE, p.wfep[q], &sb, s));
-                }
-                MPN_TRY(pack_split(m.classifier.weight[0], de, 1, m.classifier.out_dims[0], de, 32, DE, p.wc1p, &sb, s));
-                MPN_TRY(pack_split(m.edge.weight[1], he, 1, de, he, DE, HE, p.w2p, &sb, s));
-                for (int hlf = 0; hlf < d.ef; ++hlf) {
-                    const int col0 = hlf * DE;
-                    MPN_TRY(pack_split(m.edge.weight[0] + 2 * kx + hlf * de, m.edge.in_dim, 1, he, de, HE, DE,
-                                       p.w1ep + (int64_t)(col0 / 64) * HE * ncol6 * 3 / 2, &sb, s, ncol6 / 32, (col0 % 64) / 32));
-                }
-                MPN_TRY(split_batch_flush(&sb, s));
-            } else {
-                PackBatch pb;   // (the eight images as one launch)
-                for (int q = 0; q < 2; ++q) {
-                    MPN_TRY(pack_padded(fl[q]->weight[1], hn, 0, dn, hn, p.wf2p[q], DN, HN, HN, 0, &pb, s));
-                    MPN_TRY(pack_padded(fl[q]->weight[0], fl[q]->in_dim, kx, hn, de, p.wfep[q], HN, DE, DE, 0, &pb, s));
-                }
-                MPN_TRY(pack_padded(m.classifier.weight[0], de, 0, m.classifier.out_dims[0], de, p.wc1p, 32, DE, DE, 0, &pb, s));
-                MPN_TRY(pack_padded(m.edge.weight[1], he, 0, de, he, p.w2p, DE, HE, HE, 0, &pb, s));
-                // e-part columns of edge layer 0 as one image [HE][ncol6] per pass of <= 64 (padded) columns of [e0 | e_{s-1}]
-                // (the kernel streams whole rows of one pass image)
-                for (int hlf = 0; hlf < d.ef; ++hlf) {
-                    const int col0 = hlf * DE;
-                    MPN_TRY(pack_padded(m.edge.weight[0], m.edge.in_dim, 2 * kx + hlf * de, he, de,
-                                        p.w1ep + (int64_t)(col0 / 64) * HE * ncol6, HE, DE, ncol6, col0 % 64, &pb, s));
-                }
-                MPN_TRY(pack_batch_flush(&pb, s));
-            }
+            const ChainBwdImages im = {{p.wf2p[0], p.wf2p[1]}, {p.wfep[0], p.wfep[1]}, p.wc1p, p.w2p, p.w1ep};
+            MPN_TRY(pack_chain_bwd_weights(m, d, im, bwd_split, s));
         }
         if (fuse_node_chain_bwd) {
             node_chain_bwd_image_shorts(dn, pw, &ncb_off_wu);
@@ -778,20 +830,17 @@ struct BackwardRun {
     int edge_side_bf16(const StepView& v) {
         const int b_ = v.b_;
         const int hcw = m.classifier.out_dims[0];
-        EdgeChainBf16BwdArgs a = {};
-        a.E = (int)E; a.N = (int)N; a.agg = m.agg; a.first_step = v.step == 1 ? 1 : 0;
-        a.he = he; a.de = de; a.hn = hn; a.dn = dn; a.hc = hcw;
-        a.header = g.header; a.srow = g.srow; a.perm = g.perm; a.seg_ptr = g.seg_ptr;
-        a.dAGG = p.dAGG; a.mask = reinterpret_cast<const unsigned*>(v.b.MK); a.ARG = v.b.ARG;
-        a.dlog = grad_logits + (size_t)b_ * E;
-        a.dE_in = p.dEpp[ce];
-        a.dZM = w16(p.dZfl[1], (int64_t)b_ * E * dn); a.dZF = w16(p.dZfl[0], (int64_t)b_ * E * hn);
-        a.dZc = w16(p.dZcl[0], (int64_t)b_ * E * hcw); a.dZ2 = w16(p.dZed[1], (int64_t)b_ * E * de);
-        a.dZ1 = w16(p.dZed[0], (int64_t)b_ * E * he);
-        a.dE0 = p.dE0; a.dEprev = p.dEpp[ce ^ 1];
-        a.img_edge = p.cb16_img; a.img_cls = p.cb16_img + p.cb16_off_cls;
-        a.img_flow[0] = p.cb16_img + p.cb16_off_flow[0]; a.img_flow[1] = p.cb16_img + p.cb16_off_flow[1];
-        a.wc2 = m.classifier.weight[1];
+        auto f16 = [](unsigned short* q) { return reinterpret_cast<float*>(q); };
+        ChainBwdIO c = {};
+        c.dAGG = p.dAGG; c.mask = reinterpret_cast<const unsigned*>(v.b.MK); c.ARG = v.b.ARG; c.dlog = grad_logits + (size_t)b_ * E;
+        c.dE_io = p.dEpp[ce];
+        c.dZM = f16(w16(p.dZfl[1], (int64_t)b_ * E * dn)); c.dZF = f16(w16(p.dZfl[0], (int64_t)b_ * E * hn));
+        c.dZc = f16(w16(p.dZcl[0], (int64_t)b_ * E * hcw)); c.dZ2 = f16(w16(p.dZed[1], (int64_t)b_ * E * de));
+        c.dZ1 = f16(w16(p.dZed[0], (int64_t)b_ * E * he));
+        c.dE0 = p.dE0; c.dEprev = p.dEpp[ce ^ 1];
+        c.first_step = v.step == 1 ? 1 : 0;
+        const ChainBf16BwdImages im = {p.cb16_img, p.cb16_off_cls, {p.cb16_off_flow[0], p.cb16_off_flow[1]}};
+        const EdgeChainBf16BwdArgs a = chain_bf16_bwd_args(m, d, g, N, E, im, c);
         prof_begin(PROF_CHAIN_BWD, s);
         MPN_TRY(launch_edge_chain_bf16_bwd(a, s));
         prof_end(PROF_CHAIN_BWD, s);
@@ -811,17 +860,13 @@ struct BackwardRun {
     int edge_side_chain(const StepView& v) {
         const int b_ = v.b_;
         float* const dP = v.dP;
-        EdgeChainBwdArgs a = {};
-        a.E = (int)E; a.N = (int)N; a.agg = m.agg; a.first_step = v.step == 1 ? 1 : 0; a.cat_two = d.ef == 2 ? 1 : 0; a.split = bwd_split ? 1 : 0;
-        a.skip_e0 = hoist_e0 ? 1 : 0;
-        a.he = he; a.de = de; a.hn = hn; a.dn = dn; a.hc = m.classifier.out_dims[0];
-        a.header = g.header; a.srow = g.srow; a.perm = g.perm; a.seg_ptr = g.seg_ptr;
-        a.dAGG = p.dAGG; a.mask = reinterpret_cast<const unsigned*>(v.b.MK); a.ARG = v.b.ARG;
-        a.dlog = grad_logits + (size_t)b_ * E;
-        a.dE_io = v.dzed[1]; a.dZM = v.dzfl[1]; a.dZF = v.dzfl[0]; a.dZc = v.dzcl[0]; a.dZ1 = v.dzed[0];
-        a.dE0 = p.dE0; a.dEprev = v.step == 1 ? p.dE0 : p.dZed[ne - 1] + (size_t)(b_ - 1) * es;
-        a.wf2_out = p.wf2p[0]; a.wf2_in = p.wf2p[1]; a.wfe_out = p.wfep[0]; a.wfe_in = p.wfep[1];
-        a.wc1 = p.wc1p; a.wc2 = m.classifier.weight[1]; a.w2 = p.w2p; a.w1e = p.w1ep;
+        ChainBwdIO c = {};
+        c.dAGG = p.dAGG; c.mask = reinterpret_cast<const unsigned*>(v.b.MK); c.ARG = v.b.ARG; c.dlog = grad_logits + (size_t)b_ * E;
+        c.dE_io = v.dzed[1]; c.dZM = v.dzfl[1]; c.dZF = v.dzfl[0]; c.dZc = v.dzcl[0]; c.dZ1 = v.dzed[0];
+        c.dE0 = p.dE0; c.dEprev = v.step == 1 ? p.dE0 : p.dZed[ne - 1] + (size_t)(b_ - 1) * es;
+        c.first_step = v.step == 1 ? 1 : 0; c.skip_e0 = hoist_e0 ? 1 : 0;
+        const ChainBwdImages im = {{p.wf2p[0], p.wf2p[1]}, {p.wfep[0], p.wfep[1]}, p.wc1p, p.w2p, p.w1ep};
+        const EdgeChainBwdArgs a = chain_bwd_args(m, d, g, N, E, im, bwd_split, c);
         prof_begin(PROF_CHAIN_BWD, s);
         MPN_TRY(launch_edge_chain_bwd(a, s));
         prof_end(PROF_CHAIN_BWD, s);
@@ -1437,6 +1482,86 @@ extern "C" int mpnhip_backward_flags(const mpnhip_model* model, const void* grap
     MPN_TRY(run.encoder_edge_bwd());
     MPN_TRY(run.flush_tail_and_unpack());
     return run.join_side();
+}
+
+// ---- test instrumentation: ONE launch of a backward chain kernel (include/mpnhip.h) ----------------------------------------------
+static int debug_chain_bwd_model(const mpnhip_model* model, Dims* d) {
+    MPN_CHECK_ARG(model, "debug_edge_chain_backward: null model");
+    MPN_TRY(check_chain_model(*model, d));
+    const int hc = model->classifier.out_dims[0];
+    bool ok;
+    if (model->precision == MPNHIP_PREC_BF16)   // (what the forward's plan asks before it saves in the bf16-row form: chain_bf16_train_ok)
+        ok = edge_chain_bf16_supported(d->he, d->de, d->hn, d->dn, hc, d->ef) && d->he % 8 == 0 && d->de % 8 == 0 && d->hn % 8 == 0 &&
+             d->dn % 8 == 0 && hc % 8 == 0 && edge_chain_bf16_bwd_supported(d->he, d->de, d->hn, d->dn, hc);
+    else if (model->precision == MPNHIP_PREC_FP32 || model->precision == MPNHIP_PREC_FP32_SPLIT)
+        ok = edge_chain_supported(d->he, d->de, d->hn, d->dn, hc, d->de, d->ef == 2 ? d->de : 0);
+    else {
+        set_error("debug_edge_chain_backward: precision %d (MPNHIP_PREC_FP32 / _FP32_SPLIT / _BF16)", model->precision);
+        return MPNHIP_ERR_UNSUPPORTED;
+    }
+    if (!ok) {
+        set_error("debug_edge_chain_backward: widths he %d de %d hn %d dn %d hc %d (re-attached edges: %d) are not the kernel's", d->he, d->de,
+                  d->hn, d->dn, hc, d->ef - 1);
+        return MPNHIP_ERR_UNSUPPORTED;
+    }
+    return MPNHIP_OK;
+}
+
+extern "C" size_t mpnhip_debug_edge_chain_backward_workspace_bytes(const mpnhip_model* model) {
+    Dims d;
+    if (debug_chain_bwd_model(model, &d) != MPNHIP_OK) return 0;
+    Carver a(nullptr);
+    if (model->precision == MPNHIP_PREC_BF16) {
+        ChainBf16BwdImages im;
+        carve_chain_bf16_bwd_images(a, *model, d, &im);
+    } else {
+        ChainBwdImages im;
+        carve_chain_bwd_images(a, d, &im);
+    }
+    return a.bytes();
+}
+
+extern "C" int mpnhip_debug_edge_chain_backward(const mpnhip_model* model, const void* graph_buf, int n_nodes, int64_t n_edges,
+                                                const mpnhip_debug_edge_chain_bwd* io, void* workspace, size_t workspace_bytes,
+                                                void* stream_) {
+    hipStream_t s = static_cast<hipStream_t>(stream_);
+    Dims d;
+    MPN_TRY(debug_chain_bwd_model(model, &d));
+    const mpnhip_model& m = *model;
+    const bool bf16 = m.precision == MPNHIP_PREC_BF16;
+    MPN_CHECK_ARG(graph_buf && io, "debug_edge_chain_backward: null graph / io");
+    MPN_CHECK_ARG(n_nodes >= 0 && n_edges >= 0 && n_edges <= INT32_MAX, "debug_edge_chain_backward: bad sizes");
+    MPN_CHECK_ARG(!io->skip_e0 || bf16 || (d.ef == 2 && pad32(d.de) == 64),
+                  "debug_edge_chain_backward: skip_e0 needs re-attached edge features and 32 < de <= 64 (whole column passes)");
+    if (n_edges == 0) return MPNHIP_OK;
+    MPN_CHECK_ARG(n_nodes > 0, "debug_edge_chain_backward: edges without nodes");
+    MPN_CHECK_ARG(io->dAGG && io->dlog && io->mask && io->dE_io && io->dZM && io->dZF && io->dZc && io->dZ1 && io->dE0 && (io->dZ2 || !bf16) &&
+                  (io->dEprev || io->first_step) && (io->ARG || m.agg != MPNHIP_AGG_MAX), "debug_edge_chain_backward: null tensor");
+    MPN_CHECK_ARG(aligned16(io->dAGG) && aligned16(io->ARG) && aligned16(io->dE_io) && aligned16(io->dZM) && aligned16(io->dZF) &&
+                  aligned16(io->dZc) && aligned16(io->dZ2) && aligned16(io->dZ1) && aligned16(io->dE0) && aligned16(io->dEprev) &&
+                  aligned16(io->mask) && aligned16(workspace),
+                  "debug_edge_chain_backward: the matrices and the workspace must be 16-byte aligned");
+    MPN_CHECK_WORKSPACE("debug_edge_chain_backward", workspace, workspace_bytes, mpnhip_debug_edge_chain_backward_workspace_bytes(model));
+    GraphView g;
+    graph_layout(n_nodes, n_edges, &g, const_cast<void*>(graph_buf));
+    Carver c(workspace);
+    auto fp = [](void* q) { return static_cast<float*>(q); };
+    ChainBwdIO b = {};
+    b.dAGG = io->dAGG; b.mask = io->mask; b.ARG = io->ARG; b.dlog = io->dlog;
+    b.dE_io = io->dE_io; b.dZM = fp(io->dZM); b.dZF = fp(io->dZF); b.dZc = fp(io->dZc); b.dZ2 = fp(io->dZ2); b.dZ1 = fp(io->dZ1);
+    b.dE0 = io->dE0; b.dEprev = io->dEprev;
+    b.first_step = io->first_step; b.skip_e0 = io->skip_e0; b.plain_barriers = io->plain_barriers;
+    if (bf16) {
+        ChainBf16BwdImages im;
+        carve_chain_bf16_bwd_images(c, m, d, &im);
+        MPN_TRY(pack_chain_bf16_bwd_weights(m, d, im, s));
+        return launch_edge_chain_bf16_bwd(chain_bf16_bwd_args(m, d, g, n_nodes, n_edges, im, b), s);
+    }
+    ChainBwdImages im;
+    carve_chain_bwd_images(c, d, &im);
+    const bool split = m.precision == MPNHIP_PREC_FP32_SPLIT;
+    MPN_TRY(pack_chain_bwd_weights(m, d, im, split, s));
+    return launch_edge_chain_bwd(chain_bwd_args(m, d, g, n_nodes, n_edges, im, split, b), s);
 }
 
 // Test / diagnosis instrumentation: one block of pre-activation gradients mpnhip_backward left in its workspace (sorted edge

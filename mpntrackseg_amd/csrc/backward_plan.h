@@ -7,6 +7,28 @@
 
 namespace mpnhip {
 
+// zero-padded copies of the per-edge weights for the fused backward chain kernel (edge_chain.hip: native [n][k] orientation, or the
+// same logical images as three-piece split images): ONE layout and ONE packer for the backward's plan and for
+// mpnhip_debug_edge_chain_backward
+struct ChainBwdImages { float* wf2p[2]; float* wfep[2]; float* wc1p; float* w2p; float* w1ep; };
+static inline void carve_chain_bwd_images(Carver& a, const Dims& d, ChainBwdImages* im) {
+    const size_t HE = pad32(d.he), DE = pad32(d.de), HN = pad32(d.hn), DN = pad32(d.dn);
+    // (sized for the split images, 3/2 of the fp32 ones)
+    for (int q = 0; q < 2; ++q) { im->wf2p[q] = a.take<float>(DN * HN * 3 / 2); im->wfep[q] = a.take<float>(HN * DE * 3 / 2); }
+    im->wc1p = a.take<float>(32 * DE * 3 / 2);
+    im->w2p = a.take<float>(DE * HE * 3 / 2);
+    im->w1ep = a.take<float>(HE * 2 * DE * 3 / 2);
+}
+// ... and the pair images of the bf16-operand backward chain kernel (edge_chain_bf16_bwd.hip): edge | classifier | flow_out | flow_in
+struct ChainBf16BwdImages { char* img; size_t off_cls, off_flow[2]; };
+static inline void carve_chain_bf16_bwd_images(Carver& a, const mpnhip_model& m, const Dims& d, ChainBf16BwdImages* im) {
+    im->img = a.take<char>(chain_bf16_bwd_image_bytes(d.he, d.de, d.hn, d.dn, m.classifier.out_dims[0], &im->off_cls, &im->off_flow[0],
+                                                      &im->off_flow[1]));
+}
+// (backward.hip)
+int pack_chain_bwd_weights(const mpnhip_model& m, const Dims& d, const ChainBwdImages& im, bool split, hipStream_t s);
+int pack_chain_bf16_bwd_weights(const mpnhip_model& m, const Dims& d, const ChainBf16BwdImages& im, hipStream_t s);
+
 // ------------------------------------------------------------------------------------ plan
 // Pre-activation gradients (dZ) of EVERY step are kept ([L][rows][width] blocks): the activation-gradient
 // chain of a step reads its predecessor's block, and after the step loop each weight's gradient is ONE
@@ -188,8 +210,9 @@ static inline size_t plan_backward(const mpnhip_model& m, const Dims& d, const F
     p.cb16_img = nullptr;
     if (p.b16) {
         for (int i = 0; i < 2; ++i) p.dEpp[i] = a.take<float>((size_t)E * d.de);
-        p.cb16_img = a.take<char>(chain_bf16_bwd_image_bytes(d.he, d.de, d.hn, d.dn, m.classifier.out_dims[0], &p.cb16_off_cls, &p.cb16_off_flow[0],
-                                                             &p.cb16_off_flow[1]));
+        ChainBf16BwdImages im;
+        carve_chain_bf16_bwd_images(a, m, d, &im);
+        p.cb16_img = im.img; p.cb16_off_cls = im.off_cls; p.cb16_off_flow[0] = im.off_flow[0]; p.cb16_off_flow[1] = im.off_flow[1];
     }
     int mw = enc_maxw(m, d);
     if (mw < 52) mw = 52;   // (the fused reference edge encoder keeps dz2 | dz1 | dz0 side by side in T[0])
@@ -197,12 +220,10 @@ static inline size_t plan_backward(const mpnhip_model& m, const Dims& d, const F
     for (int i = 0; i < 3; ++i) p.Tn[i] = a.take<float>((size_t)N * mw);
     p.t_width = (int)mw;
     {
-        const size_t HE = pad32(d.he), DE = pad32(d.de), HN = pad32(d.hn), DN = pad32(d.dn);
-        // (sized for the split images, 3/2 of the fp32 ones)
-        for (int q = 0; q < 2; ++q) { p.wf2p[q] = a.take<float>(DN * HN * 3 / 2); p.wfep[q] = a.take<float>(HN * DE * 3 / 2); }
-        p.wc1p = a.take<float>(32 * DE * 3 / 2);
-        p.w2p = a.take<float>(DE * HE * 3 / 2);
-        p.w1ep = a.take<float>(HE * 2 * DE * 3 / 2);
+        ChainBwdImages im;
+        carve_chain_bwd_images(a, d, &im);
+        for (int q = 0; q < 2; ++q) { p.wf2p[q] = im.wf2p[q]; p.wfep[q] = im.wfep[q]; }
+        p.wc1p = im.wc1p; p.w2p = im.w2p; p.w1ep = im.w1ep;
     }
     p.ncb_img = nullptr;
     if (node_chain_bwd_supported(d.dn, d.pw, d.kx) && m.node.n_layers == 1 && m.precision == MPNHIP_PREC_FP32_SPLIT)

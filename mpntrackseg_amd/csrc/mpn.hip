@@ -286,11 +286,86 @@ static int pack_chain_weights(const mpnhip_model& m, const Dims& d, const ChainW
     return MPNHIP_OK;
 }
 
+// Q0 = e0 W1[:, e0 columns]^T, [E, he]: the re-attached initial edge features' share of the edge MLP's first layer, the same in every
+// step (ForwardRun::hoist_edge_share; mpnhip_debug_edge_chain_forward)
+static int edge_share_q0(const mpnhip_model& m, const Dims& d, const float* e0, float* Q0, int64_t E, int prec, hipStream_t s) {
+    GemmArgs a = {};
+    a.ngroups = 1; a.N = d.he; a.K = d.de; a.ksplit = d.de; a.m_upper = E;
+    GemmGroup& G = a.g[0];
+    init_group(G);
+    G.A = e0; G.lda = d.de; G.B = m.edge.weight[0] + 2 * d.kx; G.ldb = m.edge.in_dim; G.C = Q0; G.ldc = d.he; G.m_static = E;
+    return launch_gemm(a, A_KCONTIG, B_KCONTIG, prec, s);
+}
+
+// What one launch of the fp32 / split forward chain kernel reads and writes besides the model and the graph: [ea | eb] the first
+// layer's input segments (eb == nullptr: ea alone, all ke columns), the saves all four or none
+struct ChainFwdIO {
+    const float* ea; int64_t ldea; int kea; const float* eb; int64_t ldeb;
+    const float* P;
+    float* e_new; float* msg; float* logits;
+    float* save_h1; float* save_hc; float* save_hf; unsigned* save_mask;
+};
+// The kernel's arguments for one step (ForwardRun::edge_side_chain; mpnhip_debug_edge_chain_forward).  Q0 (or nullptr): ea = the
+// re-attached initial edge features, whose product with W1's e0 columns is Q0 -- the kernel multiplies the current features only
+// (rows kea .. of the [k][n] weight image)
+static EdgeChainArgs chain_fwd_args(const mpnhip_model& m, const Dims& d, const GraphView& g, int64_t N, int64_t E, const ChainWeights& cw,
+                                    bool split, const float* Q0, const ChainFwdIO& io) {
+    EdgeChainArgs a = {};
+    a.E = (int)E; a.N = (int)N; a.header = g.header; a.srow = g.srow; a.scol = g.scol; a.perm = g.perm; a.split = split ? 1 : 0;
+    a.he = d.he; a.de = d.de; a.hn = d.hn; a.dn = d.dn; a.hc = m.classifier.out_dims[0];
+    a.xa = io.ea; a.ldxa = io.ldea; a.k1a = io.eb ? io.kea : d.ke;
+    a.xb = io.eb; a.ldxb = io.ldeb; a.k1b = io.eb ? d.ke - io.kea : 0;
+    a.P = io.P; a.pw = d.pw;
+    a.w1T = cw.w1T; a.w2T = cw.w2T; a.b2 = m.edge.bias[1];
+    if (Q0) {
+        a.Q0 = Q0;
+        a.xa = io.eb; a.ldxa = io.ldeb; a.k1a = d.ke - io.kea;
+        a.xb = nullptr; a.ldxb = 0; a.k1b = 0;
+        a.w1T = cw.w1T + (size_t)io.kea * pad32(d.he) * (split ? 3 : 2) / 2;
+    }
+    a.wc1T = cw.wc1T; a.bc1 = m.classifier.bias[0]; a.wc2 = m.classifier.weight[1]; a.bc2 = m.classifier.bias[1];
+    a.wf1T_out = cw.wf1T[0]; a.wf1T_in = cw.wf1T[1]; a.wf2T_out = cw.wf2T[0]; a.wf2T_in = cw.wf2T[1];
+    a.bf2_out = m.flow_out.bias[1]; a.bf2_in = m.flow_in.bias[1];
+    a.e_new = io.e_new; a.msg = io.msg; a.logits = io.logits;
+    a.save_h1 = io.save_h1; a.save_hc = io.save_hc; a.save_hf = io.save_hf; a.save_mask = io.save_mask;
+    return a;
+}
+
 static int pack_chain_bf16_weights(const mpnhip_model& m, const Dims& d, const ChainBf16& cb, hipStream_t s) {
     const float* f0[2] = {m.flow_out.weight[0], m.flow_in.weight[0]};
     const float* f1[2] = {m.flow_out.weight[1], m.flow_in.weight[1]};
     return pack_chain_bf16(m.edge.weight[0], m.edge.in_dim, 2 * d.kx, d.ef, m.edge.weight[1], m.classifier.weight[0], f0, m.flow_out.in_dim,
                            d.kx, f1, d.he, d.de, d.hn, d.dn, m.classifier.out_dims[0], cb.img, s);
+}
+
+// What one launch of the bf16-operand forward chain kernel reads and writes besides the model and the graph: the first-layer input
+// [ea | eb] as fp32 rows or (ea16 / eb16) as bf16 rows; the saves all four or none; agg_out: the kernel aggregates (msg is not written)
+struct ChainBf16FwdIO {
+    const float* ea; int64_t ldea; const float* eb; int64_t ldeb;
+    const unsigned short* ea16; const unsigned short* eb16;
+    const float* P;
+    float* e_new; unsigned short* e16_out; float* msg; float* logits;
+    unsigned short* save_h1; unsigned short* save_hc; unsigned short* save_hf; unsigned* save_mask;
+    float* agg_out; float* piece; int* start_row;
+    int plain_barriers;
+};
+// The kernel's arguments for one step (ForwardRun::edge_side_bf16; mpnhip_debug_edge_chain_bf16_forward)
+static EdgeChainBf16Args chain_bf16_fwd_args(const mpnhip_model& m, const Dims& d, const GraphView& g, int64_t N, int64_t E, const ChainBf16& cb,
+                                             const ChainBf16FwdIO& io) {
+    EdgeChainBf16Args a = {};
+    a.E = (int)E; a.N = (int)N; a.header = g.header; a.srow = g.srow; a.scol = g.scol; a.perm = g.perm;
+    a.he = d.he; a.de = d.de; a.hn = d.hn; a.dn = d.dn; a.hc = m.classifier.out_dims[0];
+    a.xa = io.ea; a.ldxa = io.ldea; a.xb = io.eb; a.ldxb = io.ldeb;
+    a.P = io.P; a.pw = d.pw;
+    a.img_edge = cb.img; a.img_cls = cb.img + cb.off_cls; a.img_flow[0] = cb.img + cb.off_flow[0]; a.img_flow[1] = cb.img + cb.off_flow[1];
+    a.b2 = m.edge.bias[1]; a.bc1 = m.classifier.bias[0]; a.wc2 = m.classifier.weight[1]; a.bc2 = m.classifier.bias[1];
+    a.bf2_out = m.flow_out.bias[1]; a.bf2_in = m.flow_in.bias[1];
+    a.e_new = io.e_new; a.msg = io.msg; a.logits = io.logits;
+    a.xa16 = io.ea16; a.xb16 = io.eb16; a.e16_out = io.e16_out;
+    if (io.save_mask) { a.save_h1 = io.save_h1; a.save_hc = io.save_hc; a.save_hf = io.save_hf; a.save_eb = io.e16_out; a.save_mask = io.save_mask; }
+    if (io.agg_out) { a.seg_ptr = g.seg_ptr; a.agg_out = io.agg_out; a.piece = io.piece; a.start_row = io.start_row; a.agg = m.agg; }
+    a.plain_barriers = io.plain_barriers;
+    return a;
 }
 
 // Reference widths, few nodes: the hoisted projections P0 = x0 Wnode[:, :dn]^T + bnode AND the first step's P = P0 + x0 Wnode[:, dn:]^T
@@ -590,12 +665,7 @@ struct ForwardRun {
     // ---- Q0 = e0 W1[:, e0 columns]^T ---------------------------------------------------------------------------------------------------
     int hoist_edge_share() {
         if (!r.hoist_e) return MPNHIP_OK;
-        GemmArgs a = {};
-        a.ngroups = 1; a.N = d.he; a.K = d.de; a.ksplit = d.de; a.m_upper = E;
-        GemmGroup& G = a.g[0];
-        init_group(G);
-        G.A = e0; G.lda = d.de; G.B = m.edge.weight[0] + 2 * d.kx; G.ldb = m.edge.in_dim; G.C = p.Q0; G.ldc = d.he; G.m_static = E;
-        return launch_gemm(a, A_KCONTIG, B_KCONTIG, prec, s);
+        return edge_share_q0(m, d, e0, p.Q0, E, prec, s);
     }
 
     // ---- P0 AND the first step's projections by k_proj_hoist32 (its place in the launch order: behind Q0) ------------------------------
@@ -673,27 +743,22 @@ struct ForwardRun {
 
     // (2)-(4) fused, bf16 operands / fp32 accumulation (edge_chain_bf16.hip)
     int edge_side_bf16(const StepIO& io, const StepBufs& b, int i) {
-        EdgeChainBf16Args a = {};
-        a.E = (int)E; a.N = (int)N; a.header = g.header; a.srow = g.srow; a.scol = g.scol; a.perm = g.perm;
-        a.he = d.he; a.de = d.de; a.hn = d.hn; a.dn = d.dn; a.hc = m.classifier.out_dims[0];
-        a.xa = io.ea; a.ldxa = io.ldea; a.xb = io.eb; a.ldxb = io.ldeb;
-        a.P = b.P; a.pw = d.pw;
-        a.img_edge = p.cb.img; a.img_cls = p.cb.img + p.cb.off_cls; a.img_flow[0] = p.cb.img + p.cb.off_flow[0]; a.img_flow[1] = p.cb.img + p.cb.off_flow[1];
-        a.b2 = m.edge.bias[1]; a.bc1 = m.classifier.bias[0]; a.wc2 = m.classifier.weight[1]; a.bc2 = m.classifier.bias[1];
-        a.bf2_out = m.flow_out.bias[1]; a.bf2_in = m.flow_in.bias[1];
-        a.e_new = io.e_new; a.msg = b.M; a.logits = io.logits;
+        ChainBf16FwdIO c = {};
+        c.ea = io.ea; c.ldea = io.ldea; c.eb = io.eb; c.ldeb = io.ldeb; c.P = b.P;
+        c.e_new = io.e_new; c.msg = b.M; c.logits = io.logits;
         if (r.e16_on) {
-            a.xa16 = io.ea16; a.xb16 = io.eb16; a.e16_out = io.e_new16;
-            if (i + 1 != d.L) a.e_new = nullptr;   // (the fp32 features of the last step only: they are returned / kept)
+            c.ea16 = io.ea16; c.eb16 = io.eb16; c.e16_out = io.e_new16;
+            if (i + 1 != d.L) c.e_new = nullptr;   // (the fp32 features of the last step only: they are returned / kept)
         }
         if (r.save) {
-            a.save_h1 = reinterpret_cast<unsigned short*>(b.HE[0]); a.save_hc = reinterpret_cast<unsigned short*>(b.HC[0]);
-            a.save_hf = reinterpret_cast<unsigned short*>(b.HF[0]); a.save_eb = io.e_new16; a.save_mask = reinterpret_cast<unsigned*>(b.MK);
+            c.save_h1 = reinterpret_cast<unsigned short*>(b.HE[0]); c.save_hc = reinterpret_cast<unsigned short*>(b.HC[0]);
+            c.save_hf = reinterpret_cast<unsigned short*>(b.HF[0]); c.e16_out = io.e_new16; c.save_mask = reinterpret_cast<unsigned*>(b.MK);
         }
         if (r.agg_in_kernel) {
-            a.seg_ptr = g.seg_ptr; a.agg_out = b.AGG; a.piece = p.cb.piece; a.start_row = p.cb.start_row; a.agg = m.agg;
+            c.agg_out = b.AGG; c.piece = p.cb.piece; c.start_row = p.cb.start_row;
             MPN_HIP(hipMemsetAsync(b.AGG, 0, (size_t)N * 2 * d.dn * sizeof(float), s));   // (empty segments)
         }
+        const EdgeChainBf16Args a = chain_bf16_fwd_args(m, d, g, N, E, p.cb, c);
         prof_begin(PROF_GEMM, s);
         MPN_TRY(launch_edge_chain_bf16(a, s));
         prof_end(PROF_GEMM, s);
@@ -702,26 +767,11 @@ struct ForwardRun {
 
     // (2)-(4) fused: edge MLP, classifier and both flow MLPs in one kernel (edge_chain.hip)
     int edge_side_chain(const StepIO& io, const StepBufs& b) {
-        EdgeChainArgs a = {};
-        a.E = (int)E; a.N = (int)N; a.header = g.header; a.srow = g.srow; a.scol = g.scol; a.perm = g.perm; a.split = r.split ? 1 : 0;
-        a.he = d.he; a.de = d.de; a.hn = d.hn; a.dn = d.dn; a.hc = m.classifier.out_dims[0];
-        a.xa = io.ea; a.ldxa = io.ldea; a.k1a = io.eb ? io.kea : d.ke;
-        a.xb = io.eb; a.ldxb = io.ldeb; a.k1b = io.eb ? d.ke - io.kea : 0;
-        a.P = b.P; a.pw = d.pw;
-        a.w1T = p.cw.w1T; a.w2T = p.cw.w2T; a.b2 = m.edge.bias[1];
-        if (r.hoist_e) {
-            // ea = the re-attached initial edge features: their product with W1's e0 columns is Q0 (once per forward);
-            // the kernel multiplies the current features only (rows kea.. of the [k][n] weight image)
-            a.Q0 = p.Q0;
-            a.xa = io.eb; a.ldxa = io.ldeb; a.k1a = d.ke - io.kea;
-            a.xb = nullptr; a.ldxb = 0; a.k1b = 0;
-            a.w1T = p.cw.w1T + (size_t)io.kea * pad32(d.he) * (r.split ? 3 : 2) / 2;
-        }
-        a.wc1T = p.cw.wc1T; a.bc1 = m.classifier.bias[0]; a.wc2 = m.classifier.weight[1]; a.bc2 = m.classifier.bias[1];
-        a.wf1T_out = p.cw.wf1T[0]; a.wf1T_in = p.cw.wf1T[1]; a.wf2T_out = p.cw.wf2T[0]; a.wf2T_in = p.cw.wf2T[1];
-        a.bf2_out = m.flow_out.bias[1]; a.bf2_in = m.flow_in.bias[1];
-        a.e_new = io.e_new; a.msg = b.M; a.logits = io.logits;
-        if (r.save) { a.save_h1 = b.HE[0]; a.save_hc = b.HC[0]; a.save_hf = b.HF[0]; a.save_mask = reinterpret_cast<unsigned*>(b.MK); }
+        ChainFwdIO c = {};
+        c.ea = io.ea; c.ldea = io.ldea; c.kea = io.kea; c.eb = io.eb; c.ldeb = io.ldeb; c.P = b.P;
+        c.e_new = io.e_new; c.msg = b.M; c.logits = io.logits;
+        if (r.save) { c.save_h1 = b.HE[0]; c.save_hc = b.HC[0]; c.save_hf = b.HF[0]; c.save_mask = reinterpret_cast<unsigned*>(b.MK); }
+        const EdgeChainArgs a = chain_fwd_args(m, d, g, N, E, p.cw, r.split, r.hoist_e ? p.Q0 : nullptr, c);
         prof_begin(PROF_GEMM, s);
         MPN_TRY(launch_edge_chain(a, s));
         prof_end(PROF_GEMM, s);
@@ -882,6 +932,212 @@ extern "C" int mpnhip_forward(const mpnhip_model* model, const void* graph_buf, 
     for (int i = 0; i < run.d.L; ++i) MPN_TRY(run.step(i, logits));
     MPN_TRY(run.classify_encoder_output(logits));   // (L == 0)
     return run.write_outputs(x_out, e_out);
+}
+
+// ------------------------------------------------------------------------------------ test instrumentation: the forward chain kernel
+// (workspace of mpnhip_debug_edge_chain_forward: the weight images, then Q0)
+static size_t plan_debug_chain_fwd(const Dims& d, int64_t E, void* base, ChainWeights* cw, float** Q0) {
+    Carver a(base);
+    ChainWeights w;
+    carve_chain_weights(a, d, &w);
+    float* q = a.take<float>((size_t)E * d.he);
+    if (cw) *cw = w;
+    if (Q0) *Q0 = q;
+    return a.bytes();
+}
+// model and precision checks shared by the size queries and the entry: MPNHIP_OK with *d filled, or the refusal
+static int debug_chain_fwd_model(const mpnhip_model* model, Dims* d) {
+    MPN_CHECK_ARG(model, "debug_edge_chain_forward: null model");
+    MPN_TRY(check_chain_model(*model, d));
+    if (model->precision != MPNHIP_PREC_FP32 && model->precision != MPNHIP_PREC_FP32_SPLIT) {
+        set_error("debug_edge_chain_forward: precision %d (the entry runs edge_chain_kernel: MPNHIP_PREC_FP32 / _FP32_SPLIT)", model->precision);
+        return MPNHIP_ERR_UNSUPPORTED;
+    }
+    if (!edge_chain_supported(d->he, d->de, d->hn, d->dn, model->classifier.out_dims[0], d->de, d->ef == 2 ? d->de : 0)) {
+        set_error("debug_edge_chain_forward: widths he %d de %d hn %d dn %d hc %d are not the kernel's", d->he, d->de, d->hn, d->dn,
+                  model->classifier.out_dims[0]);
+        return MPNHIP_ERR_UNSUPPORTED;
+    }
+    return MPNHIP_OK;
+}
+
+extern "C" size_t mpnhip_debug_edge_chain_mask_ints(const mpnhip_model* model, int64_t n_edges) {
+    Dims d;
+    if (n_edges < 0 || debug_chain_fwd_model(model, &d) != MPNHIP_OK) return 0;
+    return chain_mask_ints(n_edges, d.he, d.de, d.hn, d.dn);
+}
+
+extern "C" size_t mpnhip_debug_edge_chain_forward_workspace_bytes(const mpnhip_model* model, int64_t n_edges) {
+    Dims d;
+    if (n_edges < 0 || debug_chain_fwd_model(model, &d) != MPNHIP_OK) return 0;
+    return plan_debug_chain_fwd(d, n_edges, nullptr, nullptr, nullptr);
+}
+
+extern "C" int mpnhip_debug_edge_chain_forward(const mpnhip_model* model, const void* graph_buf, int n_nodes, int64_t n_edges,
+                                               const mpnhip_debug_edge_chain_fwd* io, void* workspace, size_t workspace_bytes, void* stream_) {
+    hipStream_t s = static_cast<hipStream_t>(stream_);
+    Dims d;
+    MPN_TRY(debug_chain_fwd_model(model, &d));
+    const mpnhip_model& m = *model;
+    MPN_CHECK_ARG(graph_buf && io, "debug_edge_chain_forward: null graph / io");
+    MPN_CHECK_ARG(n_nodes >= 0 && n_edges >= 0 && n_edges <= INT32_MAX, "debug_edge_chain_forward: bad sizes");
+    const bool split = m.precision == MPNHIP_PREC_FP32_SPLIT;
+    // (the conditions of the forward's own route, ForwardRun::decide, but for its L > 1)
+    MPN_CHECK_ARG(!io->hoist_e0 || (d.ef == 2 && !split && d.de >= 32 && d.de % 16 == 0),
+                  "debug_edge_chain_forward: hoist_e0 needs re-attached edge features, MPNHIP_PREC_FP32 and de >= 32, a multiple of 16");
+    if (n_edges == 0) return MPNHIP_OK;
+    MPN_CHECK_ARG(n_nodes > 0, "debug_edge_chain_forward: edges without nodes");
+    MPN_CHECK_ARG(io->P && io->e_prev && (io->e0 || d.ef == 1) && io->e_new && io->msg && io->logits, "debug_edge_chain_forward: null tensor");
+    MPN_CHECK_ARG(!io->save || (io->h1 && io->hc && io->hf && io->mask), "debug_edge_chain_forward: save without h1 / hc / hf / mask");
+    MPN_CHECK_ARG(aligned16(io->P) && aligned16(io->e0) && aligned16(io->e_prev) && aligned16(io->e_new) && aligned16(io->msg) &&
+                  aligned16(io->h1) && aligned16(io->hc) && aligned16(io->hf) && aligned16(workspace),
+                  "debug_edge_chain_forward: the feature matrices and the workspace must be 16-byte aligned");
+    MPN_CHECK_WORKSPACE("debug_edge_chain_forward", workspace, workspace_bytes, plan_debug_chain_fwd(d, n_edges, nullptr, nullptr, nullptr));
+    GraphView g;
+    graph_layout(n_nodes, n_edges, &g, const_cast<void*>(graph_buf));
+    ChainWeights cw;
+    float* Q0 = nullptr;
+    plan_debug_chain_fwd(d, n_edges, workspace, &cw, &Q0);
+    {
+        PackBatch pb;
+        SplitBatch sb;
+        const int rc = pack_chain_weights(m, d, cw, split, &pb, &sb, s);
+        const int rf = pack_batch_flush(&pb, s);
+        const int rs = split_batch_flush(&sb, s);
+        MPN_TRY(rc);
+        MPN_TRY(rf);
+        MPN_TRY(rs);
+    }
+    if (io->hoist_e0) MPN_TRY(edge_share_q0(m, d, io->e0, Q0, n_edges, MPNHIP_PREC_FP32, s));
+    ChainFwdIO c = {};
+    if (d.ef == 2) { c.ea = io->e0; c.ldea = d.de; c.kea = d.de; c.eb = io->e_prev; c.ldeb = d.de; }
+    else { c.ea = io->e_prev; c.ldea = d.de; }
+    c.P = io->P; c.e_new = io->e_new; c.msg = io->msg; c.logits = io->logits;
+    if (io->save) { c.save_h1 = io->h1; c.save_hc = io->hc; c.save_hf = io->hf; c.save_mask = io->mask; }
+    const EdgeChainArgs a = chain_fwd_args(m, d, g, n_nodes, n_edges, cw, split, io->hoist_e0 ? Q0 : nullptr, c);
+    return launch_edge_chain(a, s);
+}
+
+// ---- ... and the bf16-operand forward chain kernel -----------------------------------------------------------------------------------
+struct DebugChainBf16Plan {
+    ChainBf16 cb;
+    unsigned short* x16[2];                      // rows16: the first-layer input as bf16 rows
+    unsigned short* e16; unsigned short* h1; unsigned short* hc; unsigned short* hf;   // raw bf16 rows the kernel writes
+};
+static size_t plan_debug_chain_bf16(const mpnhip_model& m, const Dims& d, int64_t E, void* base, DebugChainBf16Plan* out) {
+    Carver a(base);
+    DebugChainBf16Plan p = {};
+    const int hc = m.classifier.out_dims[0];
+    p.cb.img = a.take<char>(chain_bf16_image_bytes(d.he, d.de, d.hn, d.dn, hc, d.ef, &p.cb.off_cls, &p.cb.off_flow[0], &p.cb.off_flow[1]));
+    size_t pieces = 0;
+    const size_t fl = chain_bf16_agg_scratch_floats(E, d.dn, &pieces);
+    p.cb.piece = a.take<float>(pieces);
+    p.cb.start_row = a.take<int>(fl - pieces);
+    for (int i = 0; i < 2; ++i) p.x16[i] = a.take<unsigned short>((size_t)E * d.de);
+    p.e16 = a.take<unsigned short>((size_t)E * d.de);
+    p.h1 = a.take<unsigned short>((size_t)E * d.he);
+    p.hc = a.take<unsigned short>((size_t)E * hc);
+    p.hf = a.take<unsigned short>((size_t)E * d.hn);
+    if (out) *out = p;
+    return a.bytes();
+}
+static int debug_chain_bf16_model(const mpnhip_model* model, Dims* d) {
+    MPN_CHECK_ARG(model, "debug_edge_chain_bf16_forward: null model");
+    MPN_TRY(check_chain_model(*model, d));
+    if (model->precision != MPNHIP_PREC_BF16) {
+        set_error("debug_edge_chain_bf16_forward: precision %d (the entry runs edge_chain_bf16_kernel: MPNHIP_PREC_BF16)", model->precision);
+        return MPNHIP_ERR_UNSUPPORTED;
+    }
+    if (!edge_chain_bf16_supported(d->he, d->de, d->hn, d->dn, model->classifier.out_dims[0], d->ef)) {
+        set_error("debug_edge_chain_bf16_forward: widths he %d de %d hn %d dn %d hc %d (re-attached edges: %d) are not the kernel's", d->he, d->de,
+                  d->hn, d->dn, model->classifier.out_dims[0], d->ef - 1);
+        return MPNHIP_ERR_UNSUPPORTED;
+    }
+    return MPNHIP_OK;
+}
+
+extern "C" size_t mpnhip_debug_edge_chain_bf16_mask_ints(const mpnhip_model* model, int64_t n_edges) {
+    Dims d;
+    if (n_edges < 0 || debug_chain_bf16_model(model, &d) != MPNHIP_OK) return 0;
+    return chain_bf16_mask_ints(n_edges, d.he, d.de, d.hn, d.dn, model->classifier.out_dims[0]);
+}
+
+extern "C" size_t mpnhip_debug_edge_chain_bf16_forward_workspace_bytes(const mpnhip_model* model, int64_t n_edges) {
+    Dims d;
+    if (n_edges < 0 || debug_chain_bf16_model(model, &d) != MPNHIP_OK) return 0;
+    return plan_debug_chain_bf16(*model, d, n_edges, nullptr, nullptr);
+}
+
+extern "C" void mpnhip_debug_edge_chain_bf16_geometry(const mpnhip_model* model, int32_t* edges_per_block, int32_t* waves_per_block) {
+    Dims d;
+    int epb = 0, nw = 0;
+    if (debug_chain_bf16_model(model, &d) == MPNHIP_OK) chain_bf16_geometry(d.he, d.de, d.hn, d.dn, model->classifier.out_dims[0], &epb, &nw);
+    if (edges_per_block) *edges_per_block = epb;
+    if (waves_per_block) *waves_per_block = nw;
+}
+
+extern "C" int mpnhip_debug_edge_chain_bf16_forward(const mpnhip_model* model, const void* graph_buf, int n_nodes, int64_t n_edges,
+                                                    const mpnhip_debug_edge_chain_bf16_fwd* io, void* workspace, size_t workspace_bytes,
+                                                    void* stream_) {
+    hipStream_t s = static_cast<hipStream_t>(stream_);
+    Dims d;
+    MPN_TRY(debug_chain_bf16_model(model, &d));
+    const mpnhip_model& m = *model;
+    const int hc = m.classifier.out_dims[0];
+    MPN_CHECK_ARG(graph_buf && io, "debug_edge_chain_bf16_forward: null graph / io");
+    MPN_CHECK_ARG(n_nodes >= 0 && n_edges >= 0 && n_edges <= INT32_MAX, "debug_edge_chain_bf16_forward: bad sizes");
+    if (io->save && !(d.he % 8 == 0 && d.de % 8 == 0 && d.hn % 8 == 0 && d.dn % 8 == 0 && hc % 8 == 0 &&
+                      edge_chain_bf16_bwd_supported(d.he, d.de, d.hn, d.dn, hc))) {
+        set_error("debug_edge_chain_bf16_forward: the SAVE variant needs widths that are multiples of 8 and that the backward kernel takes");
+        return MPNHIP_ERR_UNSUPPORTED;
+    }
+    if (io->rows16 && d.de % 8 != 0) {
+        set_error("debug_edge_chain_bf16_forward: rows16 needs de a multiple of 8");
+        return MPNHIP_ERR_UNSUPPORTED;
+    }
+    if (n_edges == 0) return MPNHIP_OK;
+    MPN_CHECK_ARG(n_nodes > 0, "debug_edge_chain_bf16_forward: edges without nodes");
+    MPN_CHECK_ARG(io->P && io->e0 && io->e_prev && io->e_new && io->logits && (io->fused_agg ? io->agg_out != nullptr : io->msg != nullptr),
+                  "debug_edge_chain_bf16_forward: null tensor");
+    MPN_CHECK_ARG(!io->save || (io->h1 && io->hc && io->hf && io->e16 && io->mask && io->dec_h1 && io->dec_e && io->dec_hc && io->dec_hf && io->dec_m),
+                  "debug_edge_chain_bf16_forward: save without its buffers");
+    MPN_CHECK_ARG(!io->rows16 || io->e16, "debug_edge_chain_bf16_forward: rows16 without e16");
+    MPN_CHECK_ARG(aligned16(io->P) && aligned16(io->e0) && aligned16(io->e_prev) && aligned16(io->e_new) && aligned16(io->msg) &&
+                  aligned16(io->agg_out) && aligned16(io->mask) && aligned16(workspace),
+                  "debug_edge_chain_bf16_forward: the matrices and the workspace must be 16-byte aligned");
+    MPN_CHECK_WORKSPACE("debug_edge_chain_bf16_forward", workspace, workspace_bytes, plan_debug_chain_bf16(m, d, n_edges, nullptr, nullptr));
+    GraphView g;
+    graph_layout(n_nodes, n_edges, &g, const_cast<void*>(graph_buf));
+    DebugChainBf16Plan p;
+    plan_debug_chain_bf16(m, d, n_edges, workspace, &p);
+    MPN_TRY(pack_chain_bf16_weights(m, d, p.cb, s));
+    ChainBf16FwdIO c = {};
+    c.ea = io->e0; c.ldea = d.de; c.eb = io->e_prev; c.ldeb = d.de; c.P = io->P;
+    c.e_new = io->e_new; c.msg = io->fused_agg ? nullptr : io->msg; c.logits = io->logits;
+    if (io->rows16) {
+        MPN_TRY(to_bf16_rows(io->e0, p.x16[0], n_edges * d.de, s));
+        MPN_TRY(to_bf16_rows(io->e_prev, p.x16[1], n_edges * d.de, s));
+        c.ea16 = p.x16[0]; c.eb16 = p.x16[1]; c.e16_out = p.e16;
+    }
+    if (io->save) { c.save_h1 = p.h1; c.save_hc = p.hc; c.save_hf = p.hf; c.e16_out = p.e16; c.save_mask = io->mask; }
+    if (io->fused_agg) {
+        c.agg_out = io->agg_out; c.piece = p.cb.piece; c.start_row = p.cb.start_row;
+        MPN_HIP(hipMemsetAsync(io->agg_out, 0, (size_t)n_nodes * 2 * d.dn * sizeof(float), s));   // (empty segments, as the forward does)
+    }
+    c.plain_barriers = io->plain_barriers ? 1 : 0;
+    const EdgeChainBf16Args a = chain_bf16_fwd_args(m, d, g, n_nodes, n_edges, p.cb, c);
+    MPN_TRY(launch_edge_chain_bf16(a, s));
+    // the bf16 rows and the decision bits, decoded with the readers of mpnhip_debug_saved (ORIGINAL edge order)
+    if (c.e16_out && io->e16) MPN_TRY(chain_bf16_debug_rows(p.e16, g.perm, n_edges, d.de, io->e16, s));
+    if (io->save) {
+        MPN_TRY(chain_bf16_debug_rows(p.h1, g.perm, n_edges, d.he, io->h1, s));
+        MPN_TRY(chain_bf16_debug_rows(p.hc, g.perm, n_edges, hc, io->hc, s));
+        MPN_TRY(chain_bf16_debug_rows(p.hf, g.perm, n_edges, d.hn, io->hf, s));
+        float* const dec[5] = {io->dec_h1, io->dec_e, io->dec_hc, io->dec_hf, io->dec_m};
+        for (int sec = 0; sec < 5; ++sec)
+            MPN_TRY(chain_bf16_debug_mask(io->mask, sec, g.header, g.perm, n_edges, d.he, d.de, d.hn, d.dn, hc, dec[sec], s));
+    }
+    return MPNHIP_OK;
 }
 
 // ------------------------------------------------------------------------------------ MetaLayer op

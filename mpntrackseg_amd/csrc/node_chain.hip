@@ -634,3 +634,71 @@ int launch_node_chain_bwd(const NodeChainBwdArgs& a_in, hipStream_t s) {
 }
 
 }  // namespace mpnhip
+
+// ---- test instrumentation: ONE launch of each kernel above on caller-given tensors, through the packers and launchers the forward
+// and the backward use (include/mpnhip.h) ----------------------------------------------------------------------------------------------
+using namespace mpnhip;
+
+extern "C" size_t mpnhip_debug_node_chain_workspace_bytes(int dn, int pw) {
+    if (!node_chain_supported(dn, pw, 2 * dn)) return 0;
+    Carver a(nullptr);
+    a.take<unsigned short>(node_chain_image_shorts(dn, pw, nullptr));
+    return a.bytes();
+}
+
+extern "C" int mpnhip_debug_node_chain(const void* graph_buf, int n_nodes, int64_t n_edges, const float* M, int dn, int pw, int agg,
+                                       const float* Wu, const float* bu, const float* Wnode, const float* P0, float* x_new,
+                                       float* P_next, float* agg_out, void* workspace, size_t workspace_bytes, void* stream_) {
+    hipStream_t s = static_cast<hipStream_t>(stream_);
+    MPN_CHECK_ARG(n_nodes >= 0 && n_edges >= 0 && n_edges <= INT32_MAX && dn >= 1 && pw >= 1, "debug_node_chain: bad sizes");
+    MPN_CHECK_ARG(agg >= MPNHIP_AGG_SUM && agg <= MPNHIP_AGG_MAX, "debug_node_chain: unknown aggregation %d", agg);
+    MPN_CHECK_ARG(graph_buf, "debug_node_chain: null graph");
+    if (!node_chain_supported(dn, pw, 2 * dn)) {
+        set_error("debug_node_chain: widths dn %d, pw %d are not the kernel's", dn, pw);
+        return MPNHIP_ERR_UNSUPPORTED;
+    }
+    if (n_nodes == 0) return MPNHIP_OK;
+    MPN_CHECK_ARG(Wu && bu && Wnode && x_new && (M || n_edges == 0) && (P0 || !P_next), "debug_node_chain: null pointer");
+    MPN_CHECK_ARG(aligned16(M) && aligned16(bu) && aligned16(P0) && aligned16(x_new) && aligned16(P_next) && aligned16(agg_out),
+                  "debug_node_chain: M, bu, P0, x_new, P_next and agg_out must be 16-byte aligned");
+    MPN_CHECK_WORKSPACE("debug_node_chain", workspace, workspace_bytes, mpnhip_debug_node_chain_workspace_bytes(dn, pw));
+    MPN_CHECK_ARG(aligned16(workspace), "debug_node_chain: the workspace must be 16-byte aligned");
+    GraphView g;
+    graph_layout(n_nodes, n_edges, &g, const_cast<void*>(graph_buf));
+    Carver c(workspace);
+    size_t off_wx = 0;
+    unsigned short* img = c.take<unsigned short>(node_chain_image_shorts(dn, pw, &off_wx));
+    MPN_TRY(pack_node_chain(Wu, Wnode, dn, pw, 2 * dn, img, s));
+    NodeChainArgs a = {n_nodes, dn, pw, agg, g.seg_ptr, M, img, bu, img + off_wx, P0, P_next, x_new, agg_out};
+    return launch_node_chain(a, s);
+}
+
+extern "C" size_t mpnhip_debug_node_chain_backward_workspace_bytes(int dn, int pw) {
+    if (!node_chain_bwd_supported(dn, pw, 2 * dn)) return 0;
+    Carver a(nullptr);
+    a.take<unsigned short>(node_chain_bwd_image_shorts(dn, pw, nullptr));
+    return a.bytes();
+}
+
+extern "C" int mpnhip_debug_node_chain_backward(int n_nodes, const float* dP, int dn, int pw, const float* x_prev, const float* Wnode,
+                                                const float* Wu, float* dZn, float* dAGG, void* workspace, size_t workspace_bytes,
+                                                void* stream_) {
+    hipStream_t s = static_cast<hipStream_t>(stream_);
+    MPN_CHECK_ARG(n_nodes >= 0 && dn >= 1 && pw >= 1, "debug_node_chain_backward: bad sizes");
+    if (!node_chain_bwd_supported(dn, pw, 2 * dn)) {
+        set_error("debug_node_chain_backward: widths dn %d, pw %d are not the kernel's", dn, pw);
+        return MPNHIP_ERR_UNSUPPORTED;
+    }
+    if (n_nodes == 0) return MPNHIP_OK;
+    MPN_CHECK_ARG(dP && x_prev && Wnode && Wu && dZn && dAGG, "debug_node_chain_backward: null pointer");
+    MPN_CHECK_ARG(aligned16(dP) && aligned16(x_prev) && aligned16(dZn) && aligned16(dAGG),
+                  "debug_node_chain_backward: dP, x_prev, dZn and dAGG must be 16-byte aligned");
+    MPN_CHECK_WORKSPACE("debug_node_chain_backward", workspace, workspace_bytes, mpnhip_debug_node_chain_backward_workspace_bytes(dn, pw));
+    MPN_CHECK_ARG(aligned16(workspace), "debug_node_chain_backward: the workspace must be 16-byte aligned");
+    Carver c(workspace);
+    size_t off_wu = 0;
+    unsigned short* img = c.take<unsigned short>(node_chain_bwd_image_shorts(dn, pw, &off_wu));
+    MPN_TRY(pack_node_chain_bwd(Wu, Wnode, dn, pw, 2 * dn, img, s));
+    NodeChainBwdArgs a = {n_nodes, dn, pw, dP, img, x_prev, img + off_wu, dZn, dAGG};
+    return launch_node_chain_bwd(a, s);
+}

@@ -72,6 +72,39 @@ static inline int check_full(const mpnhip_model& m, Dims* d, bool ptrs = true) {
     return MPNHIP_OK;
 }
 
+// The per-edge modules alone, as the operator-level entries of the fused chain kernels take them (mpnhip_debug_edge_chain_forward /
+// _backward): edge, flow_in, flow_out and classifier with their weights, dn, de, agg, reattach_edges.  The node width of the first
+// layers' inputs (kx) is read off the edge MLP's in_dim; L = 0.  MPNHIP_ERR_UNSUPPORTED: depths other than the chain kernels' two layers.
+static inline int check_chain_model(const mpnhip_model& m, Dims* d) {
+    MPN_CHECK_ARG(m.dn >= 1 && m.de >= 1, "model: dn/de");
+    MPN_CHECK_ARG(m.agg >= 0 && m.agg <= 2, "model: node_agg_fn code %d", m.agg);
+    MPN_TRY(mlp_ok(m.edge, "edge_model", true));
+    MPN_TRY(mlp_ok(m.flow_in, "flow_in_model", true));
+    MPN_TRY(mlp_ok(m.flow_out, "flow_out_model", true));
+    MPN_TRY(mlp_ok(m.classifier, "classifier.edge_model", true));
+    if (m.edge.n_layers != 2 || m.flow_in.n_layers != 2 || m.flow_out.n_layers != 2 || m.classifier.n_layers != 2) {
+        set_error("edge chain: the fused kernels take two-layer edge, flow and classifier MLPs");
+        return MPNHIP_ERR_UNSUPPORTED;
+    }
+    d->dn = m.dn;
+    d->de = m.de;
+    d->ef = m.reattach_edges ? 2 : 1;
+    d->ke = d->ef * d->de;
+    d->kx = (m.edge.in_dim - d->ke) / 2;
+    d->nf = d->kx == 2 * d->dn ? 2 : 1;
+    d->L = 0;
+    MPN_CHECK_ARG(d->kx >= 1 && m.edge.in_dim == 2 * d->kx + d->ke, "edge_model in_dim %d is not 2 kx + %d", m.edge.in_dim, d->ke);
+    MPN_CHECK_ARG(m.edge.out_dims[1] == d->de, "edge_model must end at edge_out_dim");
+    MPN_CHECK_ARG(m.flow_in.in_dim == d->kx + d->de && m.flow_out.in_dim == d->kx + d->de, "flow model in_dim != %d", d->kx + d->de);
+    MPN_CHECK_ARG(m.flow_in.out_dims[0] == m.flow_out.out_dims[0], "flow_in / flow_out dims differ");
+    MPN_CHECK_ARG(m.flow_in.out_dims[1] == d->dn && m.flow_out.out_dims[1] == d->dn, "flow models must end at node_out_dim");
+    MPN_CHECK_ARG(m.classifier.in_dim == d->de && m.classifier.out_dims[1] == 1, "classifier must map edge_out_dim to 1");
+    d->he = m.edge.out_dims[0];
+    d->hn = m.flow_in.out_dims[0];
+    d->pw = 2 * d->he + 2 * d->hn;
+    return MPNHIP_OK;
+}
+
 static inline int max_hidden(const mpnhip_mlp& m) {
     int mx = 0;
     for (int i = 0; i + 1 < m.n_layers; ++i) mx = m.out_dims[i] > mx ? m.out_dims[i] : mx;
@@ -194,6 +227,20 @@ struct ChainWeights {
     // (FwdRoute::split: three-piece bf16 split images (edge_chain.hip), 3/2 the size, same logical layout)
 };
 
+// (one layout for the forward's plan and for mpnhip_debug_edge_chain_forward)
+static inline void carve_chain_weights(Carver& a, const Dims& d, ChainWeights* cw) {
+    const size_t HE = pad32(d.he), DE = pad32(d.de), HN = pad32(d.hn), DN = pad32(d.dn);
+    // (sized for the split images, 3/2 of the fp32 ones: FwdRoute::split)
+    const size_t KE = (size_t)(d.ke + 15) / 16 * 16;
+    cw->w1T = a.take<float>(KE * HE * 3 / 2);
+    cw->w2T = a.take<float>(HE * DE * 3 / 2);
+    cw->wc1T = a.take<float>(DE * 32 * 3 / 2);
+    for (int q = 0; q < 2; ++q) {
+        cw->wf1T[q] = a.take<float>(DE * HN * 3 / 2);
+        cw->wf2T[q] = a.take<float>(HN * DN * 3 / 2);
+    }
+}
+
 // pair images of the bf16-operand chain kernel (edge_chain_bf16.hip)
 struct ChainBf16 {
     char* img;        // [edge | classifier | flow_out | flow_in]
@@ -284,18 +331,7 @@ static inline size_t plan_forward(const mpnhip_model& m, const Dims& d, const Fw
     // workspace can keep them across calls (mpnhip_model.weights_prepacked)
     p.Wnode = a.take<float>((size_t)d.pw * d.kx);
     p.bnode = a.take<float>((size_t)d.pw);
-    {
-        const size_t HE = pad32(d.he), DE = pad32(d.de), HN = pad32(d.hn), DN = pad32(d.dn);
-        // (sized for the split images, 3/2 of the fp32 ones: FwdRoute::split)
-        const size_t KE = (size_t)(d.ke + 15) / 16 * 16;
-        p.cw.w1T = a.take<float>(KE * HE * 3 / 2);
-        p.cw.w2T = a.take<float>(HE * DE * 3 / 2);
-        p.cw.wc1T = a.take<float>(DE * 32 * 3 / 2);
-        for (int q = 0; q < 2; ++q) {
-            p.cw.wf1T[q] = a.take<float>(DE * HN * 3 / 2);
-            p.cw.wf2T[q] = a.take<float>(HN * DN * 3 / 2);
-        }
-    }
+    carve_chain_weights(a, d, &p.cw);
     if (r.cb_img)   // (the route, not p.cb.img: the sizing pass runs without a base pointer)
         p.cb.img = a.take<char>(chain_bf16_image_bytes(d.he, d.de, d.hn, d.dn, m.classifier.out_dims[0], d.ef, &p.cb.off_cls, &p.cb.off_flow[0], &p.cb.off_flow[1]));
     if (r.nc_img) p.nc_img = a.take<unsigned short>(node_chain_image_shorts(d.dn, d.pw, nullptr));

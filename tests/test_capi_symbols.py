@@ -355,3 +355,163 @@ def test_weight_grad_batch_debug_entry_argument_checks_without_gpu():
     for prec in (0, 1, 2):
         assert call([prod(rows=0)], prec=prec, chosen=chosen) == 0
         assert list(chosen)[:10] == [-1] + [0] * 9
+
+
+def test_chain_debug_entries_argument_checks_without_gpu():
+    """mpnhip_debug_edge_chain_forward / _backward and mpnhip_debug_node_chain / _backward check their arguments on the host:
+    everything below returns before a kernel is launched (the non-null pointers are host dummies that are never dereferenced)."""
+    from mpntrackseg_amd import synth
+    l = capi.load()
+    dummy = ctypes.create_string_buffer(512)
+    addr = (ctypes.addressof(dummy) + 255) & ~255
+    p = ctypes.c_void_p(addr)
+    capi.path_counters(reset=True)
+
+    def model(d=128, prec="fp32", **change):
+        params = synth.model_params(d, 2)
+        for k, v in change.items():
+            params[k] = v
+        return capi.dims_model(params, prec, addr)
+
+    def fwd_io(**kw):
+        io = capi.DebugEdgeChainFwd()
+        for n in ("P", "e0", "e_prev", "e_new", "msg", "logits", "h1", "hc", "hf", "mask"):
+            setattr(io, n, addr)
+        for k, v in kw.items():
+            setattr(io, k, v)
+        return io
+
+    def bwd_io(**kw):
+        io = capi.DebugEdgeChainBwd()
+        for n in ("dAGG", "ARG", "dlog", "mask", "dE_io", "dZM", "dZF", "dZc", "dZ1", "dE0", "dEprev", "dZ2"):
+            setattr(io, n, addr)
+        for k, v in kw.items():
+            setattr(io, k, v)
+        return io
+
+    fwd = lambda m, io, n=3, e=5, ws=p, nbytes=1 << 40, graph=p: l.mpnhip_debug_edge_chain_forward(
+        ctypes.byref(m) if m is not None else None, graph, n, e, ctypes.byref(io) if io is not None else None, ws, nbytes, None)
+    bwd = lambda m, io, n=3, e=5, ws=p, nbytes=1 << 40, graph=p: l.mpnhip_debug_edge_chain_backward(
+        ctypes.byref(m) if m is not None else None, graph, n, e, ctypes.byref(io) if io is not None else None, ws, nbytes, None)
+    m = model()
+    # sizes grow with the edge count; the mask buffer is the chain's own formula: ((E + 127) / 128 + 3) blocks x 4 waves x 64 lanes x 14 words
+    assert l.mpnhip_debug_edge_chain_mask_ints(ctypes.byref(m), 161) == (2 + 3) * 4 * 64 * (5 + 1 + 1 + 4 + 2)
+    assert 0 < l.mpnhip_debug_edge_chain_forward_workspace_bytes(ctypes.byref(m), 10) < l.mpnhip_debug_edge_chain_forward_workspace_bytes(ctypes.byref(m), 1000)
+    assert l.mpnhip_debug_edge_chain_backward_workspace_bytes(ctypes.byref(m)) > 0
+    for call, io in ((fwd, fwd_io()), (bwd, bwd_io())):
+        assert call(None, io) == -1 and call(m, None) == -1 and call(m, io, graph=None) == -1
+        assert b"debug_edge_chain" in l.mpnhip_last_error()
+        assert call(m, io, n=-1) == -1 and call(m, io, e=-1) == -1
+        assert call(m, io, n=0, e=5) == -1                       # edges without nodes
+        assert call(m, io, e=0) == 0                             # no edges: a successful no-op
+        assert call(m, io, ws=None) == -3 and call(m, io, nbytes=16) == -3
+        assert call(m, io, ws=ctypes.c_void_p(addr + 4)) == -1   # misaligned workspace
+        # refused widths and modes: MPNHIP_ERR_UNSUPPORTED, and the size queries say 0
+        for bad in (model(96), model(256), model(128, "fp32_wgsplit")):
+            assert call(bad, io) == -4
+            assert l.mpnhip_debug_edge_chain_forward_workspace_bytes(ctypes.byref(bad), 10) == 0
+            assert l.mpnhip_debug_edge_chain_mask_ints(ctypes.byref(bad), 10) == 0
+            assert l.mpnhip_debug_edge_chain_backward_workspace_bytes(ctypes.byref(bad)) == 0
+        deep = model()
+        deep.classifier.n_layers, deep.classifier.out_dims[1], deep.classifier.out_dims[2] = 3, 8, 1
+        deep.classifier.weight[2] = deep.classifier.bias[2] = addr
+        assert call(deep, io) == -4
+        wrong = model()
+        wrong.flow_in.in_dim += 4
+        assert call(wrong, io) == -1
+    for name in ("P", "e_prev", "e0", "e_new", "msg", "logits"):
+        assert fwd(m, fwd_io(**{name: None})) == -1, name
+    assert fwd(m, fwd_io(save=1, mask=None)) == -1 and fwd(m, fwd_io(save=1, h1=None)) == -1
+    assert fwd(m, fwd_io(P=addr + 4)) == -1
+    # hoist_e0: MPNHIP_PREC_FP32 with re-attached edge features only
+    assert fwd(model(128, "fp32_split"), fwd_io(hoist_e0=1)) == -1
+    assert fwd(model(128, reattach_initial_edges=False), fwd_io(hoist_e0=1, e0=None)) == -1
+    assert fwd(model(128, reattach_initial_edges=False), fwd_io(e0=None), e=0) == 0
+    for name in ("dAGG", "dlog", "mask", "dE_io", "dZM", "dZF", "dZc", "dZ1", "dE0", "dEprev"):
+        assert bwd(m, bwd_io(**{name: None})) == -1, name
+    assert bwd(m, bwd_io(dEprev=None, first_step=1), e=0) == 0
+    mx = model()
+    mx.agg = capi.AGG_CODE["max"]
+    assert bwd(mx, bwd_io(ARG=None)) == -1
+    # the fp32 forward entry does not take MPNHIP_PREC_BF16 (mpnhip_debug_edge_chain_bf16_forward does); the backward entry does, at the
+    # widths the bf16 backward kernel takes: multiples of 8, re-attached edge features -- with dZ2 a buffer of its own
+    assert fwd(model(128, "bf16"), fwd_io()) == -4 and l.mpnhip_debug_edge_chain_mask_ints(ctypes.byref(model(128, "bf16")), 10) == 0
+    mb16 = model(128, "bf16")
+    assert l.mpnhip_debug_edge_chain_backward_workspace_bytes(ctypes.byref(mb16)) > 0
+    assert l.mpnhip_debug_edge_chain_backward_workspace_bytes(ctypes.byref(model(256, "bf16"))) > \
+        l.mpnhip_debug_edge_chain_backward_workspace_bytes(ctypes.byref(mb16))
+    assert bwd(mb16, bwd_io(), e=0) == 0 and bwd(mb16, bwd_io(), ws=None) == -3 and bwd(mb16, bwd_io(skip_e0=1), ws=None) == -3
+    assert bwd(mb16, bwd_io(dZ2=None)) == -1 and bwd(m, bwd_io(dZ2=None), ws=None) == -3
+    assert bwd(model(128, "bf16", reattach_initial_edges=False), bwd_io()) == -4 and bwd(model(96, "bf16"), bwd_io()) == -4
+    odd16 = model(128, "bf16")
+    odd16.classifier.out_dims[0] = 28
+    assert bwd(odd16, bwd_io()) == -4 and l.mpnhip_debug_edge_chain_backward_workspace_bytes(ctypes.byref(odd16)) == 0
+    # hoist_e0 only where the forward takes that form: de >= 32
+    assert fwd(model(32), fwd_io(hoist_e0=1)) == -1 and fwd(model(64), fwd_io(hoist_e0=1), ws=None) == -3
+    # skip_e0: two column passes only (re-attachment, 32 < de <= 64)
+    assert bwd(model(64), bwd_io(skip_e0=1)) == -1 and bwd(model(128, reattach_initial_edges=False), bwd_io(skip_e0=1)) == -1
+
+    # the bf16-operand forward chain: its own precision, re-attached edge features, save / rows16 only at widths they take
+    def bf_io(**kw):
+        io = capi.DebugEdgeChainBf16Fwd()
+        for n, t in io._fields_:
+            if t is ctypes.c_void_p:
+                setattr(io, n, addr)
+        for k, v in kw.items():
+            setattr(io, k, v)
+        return io
+
+    bf = lambda m, io, n=3, e=5, ws=p, nbytes=1 << 40, graph=p: l.mpnhip_debug_edge_chain_bf16_forward(
+        ctypes.byref(m) if m is not None else None, graph, n, e, ctypes.byref(io) if io is not None else None, ws, nbytes, None)
+    mb = model(128, "bf16")
+    epb, nw = ctypes.c_int32(-1), ctypes.c_int32(-1)
+    l.mpnhip_debug_edge_chain_bf16_geometry(ctypes.byref(mb), ctypes.byref(epb), ctypes.byref(nw))
+    assert (epb.value, nw.value) == (256, 8)
+    l.mpnhip_debug_edge_chain_bf16_geometry(ctypes.byref(model(256, "bf16")), ctypes.byref(epb), ctypes.byref(nw))
+    assert (epb.value, nw.value) == (128, 4)
+    l.mpnhip_debug_edge_chain_bf16_geometry(ctypes.byref(model(96, "bf16")), ctypes.byref(epb), ctypes.byref(nw))
+    assert (epb.value, nw.value) == (0, 0)
+    # ((E + 255) / 256 + 4) blocks x 8 waves x 64 lanes x (5 + 1 + 1 + 4 + 2) words
+    assert l.mpnhip_debug_edge_chain_bf16_mask_ints(ctypes.byref(mb), 300) == (2 + 4) * 8 * 64 * 13
+    assert 0 < l.mpnhip_debug_edge_chain_bf16_forward_workspace_bytes(ctypes.byref(mb), 10) < \
+        l.mpnhip_debug_edge_chain_bf16_forward_workspace_bytes(ctypes.byref(mb), 5000)
+    assert bf(None, bf_io()) == -1 and bf(mb, None) == -1 and bf(mb, bf_io(), graph=None) == -1 and bf(mb, bf_io(), e=-1) == -1
+    assert bf(mb, bf_io(), e=0) == 0 and bf(mb, bf_io(), n=0) == -1
+    for bad in (model(128, "fp32"), model(128, "fp32_split"), model(96, "bf16"), model(128, "bf16", reattach_initial_edges=False)):
+        assert bf(bad, bf_io()) == -4
+        assert l.mpnhip_debug_edge_chain_bf16_mask_ints(ctypes.byref(bad), 10) == 0
+        assert l.mpnhip_debug_edge_chain_bf16_forward_workspace_bytes(ctypes.byref(bad), 10) == 0
+    odd = model(128, "bf16")               # hc = 28: the inference variant takes it, the SAVE variant (hc % 8) does not
+    odd.classifier.out_dims[0] = 28
+    assert bf(odd, bf_io(save=1)) == -4 and bf(odd, bf_io(), ws=None) == -3
+    d44 = model(128, "bf16")               # de = 44: two tiles like 64, but no bf16 rows of 8
+    d44.de = d44.edge.out_dims[1] = d44.classifier.in_dim = 44
+    d44.edge.in_dim, d44.flow_in.in_dim, d44.flow_out.in_dim = 4 * 128 + 2 * 44, 2 * 128 + 44, 2 * 128 + 44
+    assert l.mpnhip_debug_edge_chain_bf16_forward_workspace_bytes(ctypes.byref(d44), 10) > 0
+    assert bf(d44, bf_io(rows16=1)) == -4 and bf(d44, bf_io(save=1)) == -4 and bf(d44, bf_io(), ws=None) == -3
+    for name in ("P", "e0", "e_prev", "e_new", "msg", "logits"):
+        assert bf(mb, bf_io(**{name: None})) == -1, name
+    assert bf(mb, bf_io(fused_agg=1, agg_out=None)) == -1 and bf(mb, bf_io(fused_agg=1, msg=None), ws=None) == -3
+    assert bf(mb, bf_io(save=1, dec_m=None)) == -1 and bf(mb, bf_io(rows16=1, e16=None)) == -1
+    assert bf(mb, bf_io(), ws=None) == -3 and bf(mb, bf_io(), nbytes=64) == -3 and bf(mb, bf_io(P=addr + 4)) == -1
+
+    # node chain: widths, then pointers
+    nc = lambda dn=64, pw=544, n=4, e=9, agg=0, graph=p, M=p, Wu=p, bu=p, Wn=p, P0=p, x=p, Pn=p, ao=p, ws=p, nbytes=1 << 40: \
+        l.mpnhip_debug_node_chain(graph, n, e, M, dn, pw, agg, Wu, bu, Wn, P0, x, Pn, ao, ws, nbytes, None)
+    ncb = lambda dn=64, pw=544, n=4, dP=p, xp=p, Wn=p, Wu=p, dZ=p, dA=p, ws=p, nbytes=1 << 40: \
+        l.mpnhip_debug_node_chain_backward(n, dP, dn, pw, xp, Wn, Wu, dZ, dA, ws, nbytes, None)
+    assert l.mpnhip_debug_node_chain_workspace_bytes(64, 544) > 0 and l.mpnhip_debug_node_chain_backward_workspace_bytes(128, 1088) > 0
+    for dn, pw in ((32, 272), (96, 816), (64, 540), (256, 2176)):
+        assert l.mpnhip_debug_node_chain_workspace_bytes(dn, pw) == 0 and l.mpnhip_debug_node_chain_backward_workspace_bytes(dn, pw) == 0
+        assert nc(dn=dn, pw=pw) == -4 and ncb(dn=dn, pw=pw) == -4
+        assert b"debug_node_chain" in l.mpnhip_last_error()
+    assert nc(n=-1) == -1 and nc(e=-1) == -1 and nc(agg=3) == -1 and nc(graph=None) == -1 and nc(dn=0) == -1
+    assert nc(n=0) == 0 and ncb(n=0) == 0
+    for bad in (dict(M=None), dict(Wu=None), dict(bu=None), dict(Wn=None), dict(x=None), dict(P0=None), dict(x=ctypes.c_void_p(addr + 4))):
+        assert nc(**bad) == -1, bad
+    assert nc(P0=None, Pn=None, ws=None) == -3                    # (no P_next: P0 is not needed -- reaches the workspace check)
+    assert nc(ws=None) == -3 and nc(nbytes=8) == -3 and ncb(ws=None) == -3 and ncb(nbytes=8) == -3
+    assert ncb(n=-1) == -1
+    for bad in (dict(dP=None), dict(xp=None), dict(Wn=None), dict(Wu=None), dict(dZ=None), dict(dA=None), dict(dP=ctypes.c_void_p(addr + 4))):
+        assert ncb(**bad) == -1, bad
+    assert not any(capi.path_counters(reset=True).values()), "an argument check let a launch through"
