@@ -21,7 +21,7 @@ $(TORCH_LIB): $(CSRC)/torch_ops.cpp include/mpnhip.h $(LIB)
 	    -I$(TORCH_DIR)/include -I$(TORCH_DIR)/include/torch/csrc/api/include -I/opt/rocm/include \
 	    $< -o $@ -L$(CSRC) -lmpnhip -L$(TORCH_DIR)/lib -lc10 -lc10_hip -ltorch_cpu -ltorch_hip -ltorch -Wl,-rpath,'$$ORIGIN' -Wl,-rpath,$(TORCH_DIR)/lib
 
-$(CSRC)/%.o: $(CSRC)/%.hip $(CSRC)/common.h $(CSRC)/device_prims.h $(CSRC)/label_tables.h $(CSRC)/plan.h $(CSRC)/backward_plan.h $(CSRC)/projection_common.h $(CSRC)/edge_chain.h $(CSRC)/edge_chain_bf16_common.h $(CSRC)/row_stage.h include/mpnhip.h
+$(CSRC)/%.o: $(CSRC)/%.hip $(CSRC)/common.h $(CSRC)/device_prims.h $(CSRC)/label_tables.h $(CSRC)/plan.h $(CSRC)/backward_plan.h $(CSRC)/projection_common.h $(CSRC)/edge_chain.h $(CSRC)/chain_layout.h $(CSRC)/chain_device.h $(CSRC)/edge_chain_bf16_common.h $(CSRC)/row_stage.h include/mpnhip.h
 	$(HIPCC) $(CXXFLAGS) -c $< -o $@
 
 $(LIB): $(OBJS)

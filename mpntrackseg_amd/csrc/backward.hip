@@ -460,43 +460,10 @@ static bool backward_forks(const mpnhip_model& m) { return m.num_enc_steps >= 4;
 
 // The weight images of edge_chain_bwd_kernel (caller's stream): one launch for the eight of them
 int pack_chain_bwd_weights(const mpnhip_model& m, const Dims& d, const ChainBwdImages& p, bool bwd_split, hipStream_t s) {
-    const int he = d.he, de = d.de, hn = d.hn, dn = d.dn, kx = d.kx;
-    const int HE = pad32(he), DE = pad32(de), HN = pad32(hn), DN = pad32(dn);
-    const int KEp = d.ef * DE;
-    const mpnhip_mlp* fl[2] = {&m.flow_out, &m.flow_in};
-    const int ncol6 = KEp < 64 ? KEp : 64;
-    if (bwd_split) {
-        // the same logical images (rows = contraction index n, columns = k) as split images (edge_chain.hip, split8);
-        // recorded and packed by one launch (pack_split cannot fail once its sizes are valid: nothing returns before the flush)
-        SplitBatch sb;
-        for (int q = 0; q < 2; ++q) {
-            MPN_TRY(pack_split(fl[q]->weight[1], hn, 1, dn, hn, DN, HN, p.wf2p[q], &sb, s));
-            MPN_TRY(pack_split(fl[q]->weight[0] + kx, fl[q]->in_dim, 1, hn, de, HN, DE, p.wfep[q], &sb, s));
-        }
-        MPN_TRY(pack_split(m.classifier.weight[0], de, 1, m.classifier.out_dims[0], de, 32, DE, p.wc1p, &sb, s));
-        MPN_TRY(pack_split(m.edge.weight[1], he, 1, de, he, DE, HE, p.w2p, &sb, s));
-        for (int hlf = 0; hlf < d.ef; ++hlf) {
-            const int col0 = hlf * DE;
-            MPN_TRY(pack_split(m.edge.weight[0] + 2 * kx + hlf * de, m.edge.in_dim, 1, he, de, HE, DE,
-                               p.w1ep + (int64_t)(col0 / 64) * HE * ncol6 * 3 / 2, &sb, s, ncol6 / 32, (col0 % 64) / 32));
-        }
-        return split_batch_flush(&sb, s);
-    }
-    PackBatch pb;   // (the eight images as one launch)
-    for (int q = 0; q < 2; ++q) {
-        MPN_TRY(pack_padded(fl[q]->weight[1], hn, 0, dn, hn, p.wf2p[q], DN, HN, HN, 0, &pb, s));
-        MPN_TRY(pack_padded(fl[q]->weight[0], fl[q]->in_dim, kx, hn, de, p.wfep[q], HN, DE, DE, 0, &pb, s));
-    }
-    MPN_TRY(pack_padded(m.classifier.weight[0], de, 0, m.classifier.out_dims[0], de, p.wc1p, 32, DE, DE, 0, &pb, s));
-    MPN_TRY(pack_padded(m.edge.weight[1], he, 0, de, he, p.w2p, DE, HE, HE, 0, &pb, s));
-    // e-part columns of edge layer 0 as one image [HE][ncol6] per pass of <= 64 (padded) columns of [e0 | e_{s-1}]
-    // (the kernel streams whole rows of one pass image)
-    for (int hlf = 0; hlf < d.ef; ++hlf) {
-        const int col0 = hlf * DE;
-        MPN_TRY(pack_padded(m.edge.weight[0], m.edge.in_dim, 2 * kx + hlf * de, he, de,
-                            p.w1ep + (int64_t)(col0 / 64) * HE * ncol6, HE, DE, ncol6, col0 % 64, &pb, s));
-    }
-    return pack_batch_flush(&pb, s);
+    const float* f0[2] = {m.flow_out.weight[0], m.flow_in.weight[0]};
+    const float* f1[2] = {m.flow_out.weight[1], m.flow_in.weight[1]};
+    return pack_edge_chain_bwd(m.edge.weight[0], m.edge.in_dim, 2 * d.kx, d.ef, m.edge.weight[1], m.classifier.weight[0], f0, m.flow_out.in_dim,
+                               d.kx, f1, d.he, d.de, d.hn, d.dn, m.classifier.out_dims[0], p, bwd_split, s);
 }
 
 // The pair images of edge_chain_bf16_bwd_kernel (caller's stream)
@@ -685,7 +652,7 @@ struct BackwardRun {
         // S = sum_s dZ1_s after the loop -- 2 E he de MACs less in every step's backward chain and in every step's weight gradient
         // (2 x 2.05 of ~31 GFLOP per step at cfg-B), for one pass over the kept dZ1 blocks.
         // (the bf16 backward chain kernel never contracts the e0 columns: always hoisted there, also at L = 1)
-        hoist_e0 = use_b16 || (use_chain && d.ef == 2 && L > 1 && pad32(de) == 64 && he % 4 == 0 && de % 4 == 0);
+        hoist_e0 = use_b16 || (use_chain && d.ef == 2 && L > 1 && chain_e0_half_is_one_pass(pad32(de)) && he % 4 == 0 && de % 4 == 0);
         // bf16-operand training: the per-node projections' weight gradient over bf16 ROWS -- dP_s rounded once by the scatter-add kernel that
         // produces it, x_{s-1} from the forward's bf16 mirror -- on the LDS-DMA kernel in 256 x 256 output tiles (wgrad_rows16.hip)
         // (f.xb_hist is filled under the forward's own run-time test: plan.h node_rows16_runtime, the one definition both sides use)
@@ -1531,7 +1498,7 @@ extern "C" int mpnhip_debug_edge_chain_backward(const mpnhip_model* model, const
     const bool bf16 = m.precision == MPNHIP_PREC_BF16;
     MPN_CHECK_ARG(graph_buf && io, "debug_edge_chain_backward: null graph / io");
     MPN_CHECK_ARG(n_nodes >= 0 && n_edges >= 0 && n_edges <= INT32_MAX, "debug_edge_chain_backward: bad sizes");
-    MPN_CHECK_ARG(!io->skip_e0 || bf16 || (d.ef == 2 && pad32(d.de) == 64),
+    MPN_CHECK_ARG(!io->skip_e0 || bf16 || (d.ef == 2 && chain_e0_half_is_one_pass(pad32(d.de))),
                   "debug_edge_chain_backward: skip_e0 needs re-attached edge features and 32 < de <= 64 (whole column passes)");
     if (n_edges == 0) return MPNHIP_OK;
     MPN_CHECK_ARG(n_nodes > 0, "debug_edge_chain_backward: edges without nodes");

@@ -9,15 +9,13 @@ namespace mpnhip {
 
 // zero-padded copies of the per-edge weights for the fused backward chain kernel (edge_chain.hip: native [n][k] orientation, or the
 // same logical images as three-piece split images): ONE layout and ONE packer for the backward's plan and for
-// mpnhip_debug_edge_chain_backward
-struct ChainBwdImages { float* wf2p[2]; float* wfep[2]; float* wc1p; float* w2p; float* w1ep; };
+// mpnhip_debug_edge_chain_backward (edge_chain.h: ChainBwdImages; each sized for either operand form)
 static inline void carve_chain_bwd_images(Carver& a, const Dims& d, ChainBwdImages* im) {
     const size_t HE = pad32(d.he), DE = pad32(d.de), HN = pad32(d.hn), DN = pad32(d.dn);
-    // (sized for the split images, 3/2 of the fp32 ones)
-    for (int q = 0; q < 2; ++q) { im->wf2p[q] = a.take<float>(DN * HN * 3 / 2); im->wfep[q] = a.take<float>(HN * DE * 3 / 2); }
-    im->wc1p = a.take<float>(32 * DE * 3 / 2);
-    im->w2p = a.take<float>(DE * HE * 3 / 2);
-    im->w1ep = a.take<float>(HE * 2 * DE * 3 / 2);
+    for (int q = 0; q < 2; ++q) { im->wf2p[q] = a.take<float>(chain_image_capacity(DN * HN)); im->wfep[q] = a.take<float>(chain_image_capacity(HN * DE)); }
+    im->wc1p = a.take<float>(chain_image_capacity(CHAIN_HC * DE));
+    im->w2p = a.take<float>(chain_image_capacity(DE * HE));
+    im->w1ep = a.take<float>(chain_image_capacity(HE * 2 * DE));
 }
 // ... and the pair images of the bf16-operand backward chain kernel (edge_chain_bf16_bwd.hip): edge | classifier | flow_out | flow_in
 struct ChainBf16BwdImages { char* img; size_t off_cls, off_flow[2]; };

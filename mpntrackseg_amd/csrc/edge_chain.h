@@ -1,5 +1,6 @@
 // Fused per-edge chain kernel of one message-passing step (see edge_chain.hip).
 #pragma once
+#include "chain_layout.h"
 #include "common.h"
 
 namespace mpnhip {
@@ -84,16 +85,7 @@ struct EdgeChainBwdArgs {
 };
 int launch_edge_chain_bwd(const EdgeChainBwdArgs& a, hipStream_t s);
 
-// ReLU-mask words per lane (two 32-feature tiles per 32-bit word, one word range per section H1 | e' | HC | HF | M) and
-// the size of one step's mask buffer: every wave tile (4 per block of 128 edges, + the launchers' 3 spare blocks)
-// holds NW x 64 words
-static inline int chain_mask_words(int he, int de, int hn, int dn) {
-    auto w = [](int v) { return ((v + 31) / 32 + 1) / 2; };
-    return w(he) + w(de) + 1 + w(hn) + w(dn);
-}
-static inline size_t chain_mask_ints(int64_t E, int he, int de, int hn, int dn) {
-    return (size_t)((E + 127) / 128 + 3) * 4 * 64 * (size_t)chain_mask_words(he, de, hn, dn);
-}
+// (ReLU-mask words and the size of one step's mask buffer: chain_layout.h, chain_mask_words / chain_mask_ints)
 bool edge_chain_supported(int he, int de, int hn, int dn, int hc, int k1a, int k1b);
 int launch_edge_chain(const EdgeChainArgs& a, hipStream_t s);
 // the three-layer edge encoder at the wider models' dims in one launch (edge_chain.hip: k_edge_encoder_mfma); 1 launched / 0 not its shape / < 0 error
@@ -113,9 +105,27 @@ int split_batch_flush(const SplitBatch* b, hipStream_t s);
 // batch (common.h: PackBatch): recorded there; nullptr (or a full one): launched now
 int transpose_padded(const float* W, int64_t ldw, int k0, int n_rows, int k_cols, float* WT, int n_pad, int k_pad, PackBatch* batch,
                      hipStream_t s);
-int pack_padded(const float* src, int64_t lds, int c0, int rows, int cols, float* dst, int rows_pad, int cols_pad, int ldd,
-                int dst_c0, PackBatch* batch, hipStream_t s);
 
+// The weight images of the two kernels (layout: chain_layout.h; every buffer holds chain_image_capacity() floats of its padded
+// size: plan.h carve_chain_weights, backward_plan.h carve_chain_bwd_images).  P(.) = pad32
+struct ChainWeights {     // edge_chain_kernel: pre-transposed [k][n]
+    float* w1T;       // [ke][P(he)]
+    float* w2T;       // [P(he)][P(de)]
+    float* wc1T;      // [P(de)][32]
+    float* wf1T[2];   // [P(de)][P(hn)] as block images  (0: flow_out, 1: flow_in)
+    float* wf2T[2];   // [P(hn)][P(dn)]
+};
+struct ChainBwdImages { float* wf2p[2]; float* wfep[2]; float* wc1p; float* w2p; float* w1ep; };   // edge_chain_bwd_kernel: native [n][k]
+// w_edge0: edge MLP layer 0 [he][ld_edge0], its ke = ef * de e columns start at col0_edge; w_edge1 [de][he]; w_cls0 [hc][de];
+// w_flow0[q] [hn][ld_flow0], e' columns from col0_flow; w_flow1[q] [dn][hn].
+// Forward: the fp32 transposes are recorded into `batch`, the split images into `split_batch` (nullptr / full: launched now).
+int pack_edge_chain(const float* w_edge0, int ld_edge0, int col0_edge, int ke, const float* w_edge1, const float* w_cls0,
+                    const float* const w_flow0[2], int ld_flow0, int col0_flow, const float* const w_flow1[2], int he, int de, int hn, int dn,
+                    int hc, const ChainWeights& img, bool split, PackBatch* batch, SplitBatch* split_batch, hipStream_t s);
+// Backward: the eight images as ONE launch on s (its own batch, flushed here)
+int pack_edge_chain_bwd(const float* w_edge0, int ld_edge0, int col0_edge, int ef, const float* w_edge1, const float* w_cls0,
+                        const float* const w_flow0[2], int ld_flow0, int col0_flow, const float* const w_flow1[2], int he, int de, int hn,
+                        int dn, int hc, const ChainBwdImages& img, bool split, hipStream_t s);
 
 // ---- bf16-operand forward chain (edge_chain_bf16.hip): N-tiled hidden layers, widths up to BASELINE.json configs[4] (256-d)
 struct EdgeChainBf16Args {
@@ -168,17 +178,7 @@ struct EdgeChainBf16Args {
     long long* ts;                // debug build: 48 cycle stamps per wave
 #endif
 };
-// mask words per lane of one 32-edge wave tile (two 32-feature tiles per word; sections H1 | e' | HC | HF | M) and the size of one
-// step's mask buffer (every wave tile of the launch incl. its 3 spare blocks; `epb`-independent: 32-edge tiles)
-static inline int chain_bf16_mask_words(int he, int de, int hn, int dn, int hc) {
-    auto w = [](int v) { return ((v + 31) / 32 + 1) / 2; };
-    return w(he) + w(de) + w(hc) + w(hn) + w(dn);
-}
-static inline size_t chain_bf16_mask_ints(int64_t E, int he, int de, int hn, int dn, int hc) {
-    return (size_t)((E + 255) / 256 + 4) * 8 * 64 * (size_t)chain_bf16_mask_words(he, de, hn, dn, hc);
-}
-// bit of element r (0..15) of a tile with parity p inside its mask word
-__host__ __device__ static inline int chain_bf16_mask_bit(int p, int r) { return 8 * p + (r >> 1) + 16 * (r & 1); }
+// (mask words, mask buffer size, chain_bf16_mask_bit, supported widths and launch geometry: chain_layout.h)
 // floats of the fused aggregation's scratch: piece [tiles][2][pad32(dn)] followed by start_row [tiles] (ints)
 size_t chain_bf16_agg_scratch_floats(int64_t E, int dn, size_t* off_start_row);
 bool edge_chain_bf16_supported(int he, int de, int hn, int dn, int hc, int ef);
@@ -204,15 +204,6 @@ int pack_pair_bf16_general(const float* Wa, int64_t sa_n, int64_t sa_k, int a_co
                            int a_natural = 0);
 
 // ---- backward of the bf16-operand chain (edge_chain_bf16_bwd.hip) ----
-// the tile counts / exactness launch_edge_chain_bf16_bwd has an instantiation for (its dispatch table, stated once: the forward's
-// plan asks this before it saves in the bf16-row form, so that a width the backward cannot take trains on the unfused path)
-static inline bool edge_chain_bf16_bwd_supported(int he, int de, int hn, int dn, int hc) {
-    const bool exact = he % 32 == 0 && de % 32 == 0 && hn % 32 == 0 && dn % 32 == 0 && hc % 32 == 0;
-    const int t1 = (he + 31) / 32, t2 = (de + 31) / 32, tf = (hn + 31) / 32, td = (dn + 31) / 32, tc = (hc + 31) / 32;
-    if (t1 == 20 && t2 == 4 && tf == 14 && td == 8 && tc == 2) return exact;
-    return (t1 == 10 && t2 == 2 && tf == 7 && td == 4 && tc == 1) || (t1 == 5 && t2 == 1 && tf == 4 && td == 2 && tc == 1) ||
-           (t1 == 3 && t2 == 1 && tf == 2 && td == 1 && tc == 1);
-}
 struct EdgeChainBf16BwdArgs {
     int E, N, agg, first_step;
     int he, de, hn, dn, hc;   // real widths
@@ -245,7 +236,5 @@ int pack_chain_bf16_bwd(const float* w_edge0, int ld_edge0, int col_e, const flo
                         const float* const w_flow0[2], int ld_flow0, int col0_flow, const float* const w_flow1[2],
                         int he, int de, int hn, int dn, int hc, void* image, hipStream_t s);
 int launch_edge_chain_bf16_bwd(const EdgeChainBf16BwdArgs& a, hipStream_t s);
-// edges per block / waves per block of the launch for these widths (forward and backward kernels share the mapping)
-void chain_bf16_geometry(int he, int de, int hn, int dn, int hc, int* epb, int* nw);
 
 }  // namespace mpnhip

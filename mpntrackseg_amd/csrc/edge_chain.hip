@@ -23,6 +23,7 @@
 // (80/16/56/32/8 -> 3/1/2/1) and 64-d (5/1/4/2); anything else uses the unfused GEMM path.
 #include <type_traits>
 
+#include "chain_device.h"
 #include "common.h"
 #include "edge_chain.h"
 #include "row_stage.h"
@@ -34,14 +35,12 @@
 
 namespace mpnhip {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 namespace {
 
 // Debug build (make EXTRA=-DMPNHIP_CHAIN_TS): lane 0 of every wave stamps s_memtime at the phase boundaries; with
 // MPNHIP_CHAIN_TS=<file prefix> in the environment the 40th launch of each kernel dumps its stamps as text.
 #ifdef MPNHIP_CHAIN_TS
-#define TS_INIT() long long* tsp = A.ts ? A.ts + ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 16 : nullptr
+#define TS_INIT() long long* tsp = A.ts ? A.ts + ((int64_t)blockIdx.x * ChainGeom::WAVES + (threadIdx.x >> 6)) * 16 : nullptr
 #define TS(i) do { if (tsp && (threadIdx.x & 63) == 0) tsp[i] = clock64(); } while (0)
 // slot 15: where the wave ran -- HW_ID (wave / simd / cu / sh / se fields) | XCC_ID << 32
 #define TS_WHERE() do { if (tsp && (threadIdx.x & 63) == 0) { unsigned hw, xcc; \
@@ -54,8 +53,6 @@ namespace {
 #endif
 
 constexpr int CH_FLOATS = 7680;  // floats per weight chunk buffer (20 KB fp32 images, 30 KB split images)
-
-__device__ __forceinline__ float4 ldg4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 
 // Weight chunks are CONTIGUOUS runs of floats in the packed images (the images are laid out so that every chunk is:
 // whole rows of a [k][n] image, or one column block stored as its own image).  They are copied with the gfx950
@@ -85,53 +82,15 @@ __device__ __forceinline__ void chunk_fetch(const float* src, int n4, int tid, f
     }
 }
 
-constexpr int cmax(int a, int b) { return a > b ? a : b; }
-constexpr int cmin(int a, int b) { return a < b ? a : b; }
 constexpr int chunk_q(int n4) { return (n4 + 255) / 256; }
 
-// 16-byte piece of a feature row at column n (n % 4 == 0, dim % 4 == 0): zero beyond the real width
-template <bool EXACT>
-__device__ __forceinline__ float4 ldrow(const float* row, int n, int dim) {
-    if (EXACT) return ldg4(row + n);  // widths are multiples of 32: nothing to mask
-    const bool ok = n < dim;
-    float4 v = ldg4(row + (ok ? n : 0));
-    v.x = ok ? v.x : 0.f; v.y = ok ? v.y : 0.f; v.z = ok ? v.z : 0.f; v.w = ok ? v.w : 0.f;
-    return v;
-}
-template <bool EXACT>
-__device__ __forceinline__ void strow(float* row, int n, int dim, float4 v, bool ok) {
-    if (ok && (EXACT || n < dim)) *reinterpret_cast<float4*>(row + n) = v;
-}
-
-// the same through a (scalar) base pointer and a 32-bit element offset: one address register per row instead of two
-template <bool EXACT>
-__device__ __forceinline__ float4 ldrow(const float* base, unsigned off, int n, int dim) {
-    // (base + zext(off)) + n: scalar base, 32-bit register offset, n in the instruction's immediate field
-    if (EXACT) return ldg4(base + (size_t)off + n);
-    const bool ok = n < dim;
-    float4 v = ldg4(base + (size_t)off + (ok ? n : 0));
-    v.x = ok ? v.x : 0.f; v.y = ok ? v.y : 0.f; v.z = ok ? v.z : 0.f; v.w = ok ? v.w : 0.f;
-    return v;
-}
-template <bool EXACT>
-__device__ __forceinline__ void strow(float* base, unsigned off, int n, int dim, float4 v, bool ok) {
-    if (ok && (EXACT || n < dim)) *reinterpret_cast<float4*>(base + (size_t)off + n) = v;
-}
-
-__device__ __forceinline__ void relu16(f32x16& a) {
-#pragma unroll
-    for (int r = 0; r < 16; ++r) a[r] = fmaxf(a[r], 0.f);
-}
-
+// (ldg4, ldrow, strow, get4, relu16: chain_device.h)
 // D tile rows of register group g (registers 4g..4g+3): n = 8g + 4h + (0..3)
 __device__ __forceinline__ void set4(f32x16& a, int g, float4 v) {
     a[4 * g + 0] = v.x; a[4 * g + 1] = v.y; a[4 * g + 2] = v.z; a[4 * g + 3] = v.w;
 }
 __device__ __forceinline__ void add4(f32x16& a, int g, float4 v) {
     a[4 * g + 0] += v.x; a[4 * g + 1] += v.y; a[4 * g + 2] += v.z; a[4 * g + 3] += v.w;
-}
-__device__ __forceinline__ float4 get4(const f32x16& a, int g) {
-    return make_float4(a[4 * g + 0], a[4 * g + 1], a[4 * g + 2], a[4 * g + 3]);
 }
 // sign flips by XOR (sx = 0x80000000 or 0): the split backward kernel keeps the gradients of every other edge NEGATED in its
 // registers (see edge_chain_bwd_kernel)
@@ -173,7 +132,6 @@ __device__ __forceinline__ void apply_mask(f32x16& a, unsigned word, int shift) 
 // of lane (m, g) holds W[n0 + m][k0 + (i & 3) + 8 (i >> 2) + 4 g] -- the contraction order of the accumulator layout, so
 // that registers 8c .. 8c+7 of an activation tile ARE the B operand of k block c.  A [K][N] image takes K N 6 bytes,
 // 3/2 of the fp32 image: the chunk schedule is the fp32 one with every offset and size scaled by 3/2.
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 struct Split8 { bf16x8 p[3]; };
 
 __device__ __forceinline__ Split8 split8(float x0, float x1, float x2, float x3, float x4, float x5, float x6, float x7) {
@@ -318,34 +276,32 @@ constexpr int chain_waves(int t1) { return t1 <= 3 ? 3 : 2; }  // waves per SIMD
 
 template <int T1, int T2, int TF, int TD, bool EXACT, bool SP>
 __global__ __launch_bounds__(256, chain_waves(T1)) void edge_chain_kernel(EdgeChainArgs A) {
-    constexpr int HE = 32 * T1, DE = 32 * T2, HN = 32 * TF, DN = 32 * TD, HC = 32;
-    constexpr int KC1 = 16;                       // phase-1 chunk: [16 k][HE]
-    constexpr int KC2 = 64;                       // phase-2 chunk: [<=64 k][DE]
-    constexpr int NC4 = 64;                       // phase-4 chunk: [DE k][<=64 n]
-    constexpr int KC5 = 32;                       // phase-5 chunk: [32 k][DN]
+    constexpr int HE = 32 * T1, DE = 32 * T2, HN = 32 * TF, DN = 32 * TD, HC = CHAIN_HC;
+    // chunk sizes (chain_layout.h: the packers lay the images out for exactly this schedule)
+    constexpr int KC1 = ChainFwd::KC1, KC2 = ChainFwd::KC2, NC4 = ChainFwd::NC4, KC5 = ChainFwd::KC5;
+    constexpr int EPB = ChainGeom::EPB;
 
     // ---- chunk schedule (float4 counts; every chunk is a contiguous run of its image) -----------------------
-    constexpr int NCH2 = (HE + KC2 - 1) / KC2;
-    constexpr int NCH4 = (HN + NC4 - 1) / NC4;
+    constexpr int NCH2 = chain_nchunks(HE, KC2);
+    constexpr int NCH4 = chain_wf1_blocks(HN);
     constexpr int NCH5 = HN / KC5;
     constexpr bool P2PIPE = T1 < 10;                         // phase 2 of the widest variant has no registers for a second operand set
-    constexpr int SCN = SP ? 3 : 2;                          // image size in halves of the fp32 image's (split images: 3/2)
-    constexpr int N4_1 = KC1 * HE / 4 * SCN / 2;             // phase 1: 16 rows of W1T
-    constexpr int N4_2_0 = cmin(KC2, HE) * DE / 4 * SCN / 2; // phase 2, first chunk
-    constexpr int N4_3 = DE * HC / 4 * SCN / 2;              // classifier layer 0, whole
-    constexpr int N4_4_0 = DE * cmin(NC4, HN) / 4 * SCN / 2; // phase 4, first column block
-    constexpr int N4_5 = KC5 * DN / 4 * SCN / 2;             // phase 5: 32 rows of Wf2T
+    constexpr int N4_1 = chain_f4(KC1 * HE, SP);                           // phase 1: 16 rows of W1T
+    constexpr int N4_2_0 = chain_f4(chain_chunk_len(HE, KC2, 0) * DE, SP); // phase 2, first chunk
+    constexpr int N4_3 = chain_f4(DE * HC, SP);                            // classifier layer 0, whole
+    constexpr int N4_4_0 = chain_f4(DE * chain_wf1_block_cols(HN, 0), SP); // phase 4, first column block
+    constexpr int N4_5 = chain_f4(KC5 * DN, SP);                           // phase 5: 32 rows of Wf2T
     constexpr int N4_MAX = cmax(cmax(N4_1, N4_2_0), cmax(cmax(N4_3, N4_4_0), N4_5));
     // chunk buffer: whole 1 KiB DMA pieces of the largest chunk (split images: exactly the largest chunk)
-    constexpr int CHF = SP ? 4 * N4_MAX : 1024 * chunk_q(N4_MAX);
+    constexpr int CHF = chain_chunk_buffer_floats(N4_MAX, SP);
     static_assert(CHF <= CH_FLOATS, "chunk too large");
-    // ReLU-mask words per lane for the backward kernel (edge_chain.h: chain_mask_words)
-    constexpr int W_H1 = 0, W_E = W_H1 + (T1 + 1) / 2, W_HC = W_E + (T2 + 1) / 2, W_HF = W_HC + 1, W_M = W_HF + (TF + 1) / 2,
-                  NW = W_M + (TD + 1) / 2;
+    // ReLU-mask words per lane for the backward kernel (chain_layout.h: ChainMaskWords)
+    using MW = ChainMaskWords<T1, T2, chain_tiles(HC), TF, TD>;
+    constexpr int W_H1 = MW::H1, W_E = MW::E, W_HC = MW::HC, W_HF = MW::HF, W_M = MW::M, NW = MW::NW;
     // ONE LDS object (a second one beside the LDS-DMA target makes hipcc drain vmcnt before unrelated ds_reads):
     // two weight-chunk buffers, two phase-1 input staging buffers, then the biases [b2 (DE) | bc1 (32) | wc2 (32) | bf2 (DN)], zero-padded
     constexpr int XS_FLOATS = 4 * 2 * 64 * 4;  // phase-1 input staging per buffer: 4 waves x 2 pieces x 64 lanes x 16 B
-    __shared__ __attribute__((aligned(16))) float smem[2 * CHF + 2 * XS_FLOATS + DE + 64 + DN];
+    __shared__ __attribute__((aligned(16))) float smem[2 * CHF + 2 * XS_FLOATS + DE + 2 * HC + DN];
     float* const wbuf0 = smem;
     float* const xs0 = smem + 2 * CHF;
     float* const sbias = xs0 + 2 * XS_FLOATS;
@@ -360,12 +316,12 @@ __global__ __launch_bounds__(256, chain_waves(T1)) void edge_chain_kernel(EdgeCh
     const int E = A.E;
     int grp, beg, end, blk = blockIdx.x;
     {
-        const int nb0 = (e_out + 127) >> 7, nb1 = (e_in + 127) >> 7;
+        const int nb0 = chain_group_blocks(e_out), nb1 = chain_group_blocks(e_in);
         if (blk < nb0) { grp = 0; beg = 0; end = e_out; }
         else if (blk < nb0 + nb1) { grp = 1; blk -= nb0; beg = e_out; end = e_out + e_in; }
         else { grp = 2; blk -= nb0 + nb1; beg = e_out + e_in; end = E; }
     }
-    const int tile0 = beg + blk * 128;
+    const int tile0 = beg + blk * EPB;
     if (tile0 >= end) return;
     const int edge_raw = tile0 + wave * 32 + lj;
     const bool edge_ok = edge_raw < end;
@@ -378,10 +334,10 @@ __global__ __launch_bounds__(256, chain_waves(T1)) void edge_chain_kernel(EdgeCh
     // 88.7 us per training launch (30 registers spilled at the phase-2 peak), HC / HF / M only 83.0 us: the forward is not bound
     // by its stores.)
     // (wave-uniform base + lane: no address registers; rows of P / Q0 / save_h1 are addressed as base + 32-bit offset)
-    unsigned* const mkb = A.save_mask ? A.save_mask + (int64_t)__builtin_amdgcn_readfirstlane(blockIdx.x * 4 + wave) * NW * 64 : nullptr;
+    unsigned* const mkb = A.save_mask ? A.save_mask + (int64_t)__builtin_amdgcn_readfirstlane(blockIdx.x * ChainGeom::WAVES + wave) * NW * 64 : nullptr;
 #define MKP(w) mkb[(w) * 64 + lane]
 
-    const float* wf1 = grp == 1 ? A.wf1T_in : A.wf1T_out;   // NCH4 column-block images [DE][<=64], block i at DE * 64 * i
+    const float* wf1 = grp == 1 ? A.wf1T_in : A.wf1T_out;   // NCH4 column-block images [DE][<= NC4], block i at chain_wf1_block_off(DE, i)
     const float* wf2 = grp == 1 ? A.wf2T_in : A.wf2T_out;
 
     int c = 0;  // chunk being computed (buffer parity)
@@ -394,10 +350,10 @@ __global__ __launch_bounds__(256, chain_waves(T1)) void edge_chain_kernel(EdgeCh
         const float* bf2 = grp == 1 ? A.bf2_in : A.bf2_out;
         float v = 0.f;
         if (tid < DE) v = tid < de ? A.b2[tid] : 0.f;
-        else if (tid < DE + 32) v = tid - DE < hc ? A.bc1[tid - DE] : 0.f;
-        else if (tid < DE + 64) v = tid - DE - 32 < hc ? A.wc2[tid - DE - 32] : 0.f;
-        else if (tid < DE + 64 + DN) v = tid - DE - 64 < dn ? bf2[tid - DE - 64] : 0.f;
-        if (tid < DE + 64 + DN) sbias[tid] = v;
+        else if (tid < DE + HC) v = tid - DE < hc ? A.bc1[tid - DE] : 0.f;
+        else if (tid < DE + 2 * HC) v = tid - DE - HC < hc ? A.wc2[tid - DE - HC] : 0.f;
+        else if (tid < DE + 2 * HC + DN) v = tid - DE - 2 * HC < dn ? bf2[tid - DE - 2 * HC] : 0.f;
+        if (tid < DE + 2 * HC + DN) sbias[tid] = v;
     }
 
     // ---- phase 1: H1^T = W1e [e0|e]^T, C-in = Pr[row] (+ Pc[col] after the MFMAs) ---------------------------
@@ -474,7 +430,7 @@ __global__ __launch_bounds__(256, chain_waves(T1)) void edge_chain_kernel(EdgeCh
         // One phase-1 chunk (16 contraction rows).  `last`: the chunk also carries the first Pc gather round.
         auto p1_chunk = [&](int i, bool last1) {
             // next chunk: the following 16 rows of W1T, or the first chunk of phase 2
-            const float* nsrc = last1 ? A.w2T : A.w1T + (int64_t)(i + 1) * (KC1 * HE * SCN / 2);
+            const float* nsrc = last1 ? A.w2T : A.w1T + (int64_t)(i + 1) * chain_row_off(KC1, HE, SP);
             const int nn4 = last1 ? N4_2_0 : N4_1;
             // (read this chunk's inputs BEFORE the DMAs go out: hipcc drains vmcnt in front of a plain ds_read_b128 that
             // follows an LDS-DMA into the same object)
@@ -553,9 +509,9 @@ __global__ __launch_bounds__(256, chain_waves(T1)) void edge_chain_kernel(EdgeCh
         pc_finish(i);
         // next: rows 64 (i + 1) .. of W2T, or the classifier image
         const bool more = i + 1 < NCH2;
-        const int rows_n = more ? (HE - (i + 1) * KC2 < KC2 ? HE - (i + 1) * KC2 : KC2) : 0;  // folds: i is unrolled
-        const float* nsrc = more ? A.w2T + (i + 1) * (KC2 * DE * SCN / 2) : A.wc1T;
-        const int nn4 = more ? rows_n * DE / 4 * SCN / 2 : N4_3;
+        const int rows_n = more ? chain_chunk_len(HE, KC2, i + 1) : 0;  // folds: i is unrolled
+        const float* nsrc = more ? A.w2T + chain_row_off((i + 1) * KC2, DE, SP) : A.wc1T;
+        const int nn4 = more ? chain_f4(rows_n * DE, SP) : N4_3;
         __builtin_amdgcn_sched_barrier(0);
         chunk_fetch<chunk_q(cmax(N4_2_0, N4_3)), SP>(nsrc, nn4, tid, wbuf_at(c + 1));
         if (more) pc_issue(i + 1);
@@ -619,7 +575,7 @@ __global__ __launch_bounds__(256, chain_waves(T1)) void edge_chain_kernel(EdgeCh
         float part = 0.f;
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
-            const float4 w = *reinterpret_cast<const float4*>(sbias + DE + 32 + 8 * g + 4 * lh);
+            const float4 w = *reinterpret_cast<const float4*>(sbias + DE + HC + 8 * g + 4 * lh);
             part = fmaf(w.x, hcv[4 * g + 0], part);
             part = fmaf(w.y, hcv[4 * g + 1], part);
             part = fmaf(w.z, hcv[4 * g + 2], part);
@@ -637,13 +593,13 @@ __global__ __launch_bounds__(256, chain_waves(T1)) void edge_chain_kernel(EdgeCh
 #pragma unroll
     for (int i = 0; i < NCH4; ++i) {
         const bool more = i + 1 < NCH4;
-        const int ncw_n = more ? ((HN - (i + 1) * NC4) < NC4 ? (HN - (i + 1) * NC4) : NC4) : 0;
-        const float* nsrc = more ? wf1 + (DE * NC4 * SCN / 2) * (i + 1) : wf2;
-        const int nn4 = more ? DE * ncw_n / 4 * SCN / 2 : N4_5;
+        const int ncw_n = more ? chain_wf1_block_cols(HN, i + 1) : 0;
+        const float* nsrc = more ? wf1 + chain_wf1_block_off(DE, i + 1, SP) : wf2;
+        const int nn4 = more ? chain_f4(DE * ncw_n, SP) : N4_5;
         chunk_fetch<chunk_q(cmax(N4_4_0, N4_5)), SP>(nsrc, nn4, tid, wbuf_at(c + 1));
         const float* ws = wbuf_at(c);
         constexpr int full = NC4 / 32;
-        const int ncw = (HN - i * NC4) < NC4 ? (HN - i * NC4) : NC4;  // compile-time per unrolled i
+        const int ncw = (HN - i * NC4) < NC4 ? (HN - i * NC4) : NC4;  // = chain_wf1_block_cols(HN, i), written out (see B6); compile-time per unrolled i
 #pragma unroll
         for (int t = 0; t < T2; ++t) {
             if constexpr (SP) {
@@ -679,10 +635,10 @@ __global__ __launch_bounds__(256, chain_waves(T1)) void edge_chain_kernel(EdgeCh
 #pragma unroll
     for (int t = 0; t < TD; ++t)
 #pragma unroll
-        for (int g = 0; g < 4; ++g) set4(mm[t], g, *reinterpret_cast<const float4*>(sbias + DE + 64 + 32 * t + 8 * g + 4 * lh));
+        for (int g = 0; g < 4; ++g) set4(mm[t], g, *reinterpret_cast<const float4*>(sbias + DE + 2 * HC + 32 * t + 8 * g + 4 * lh));
 #pragma unroll
     for (int i = 0; i < NCH5; ++i) {
-        if (i + 1 < NCH5) chunk_fetch<chunk_q(N4_5), SP>(wf2 + (i + 1) * (KC5 * DN * SCN / 2), N4_5, tid, wbuf_at(c + 1));  // static: i is unrolled
+        if (i + 1 < NCH5) chunk_fetch<chunk_q(N4_5), SP>(wf2 + chain_row_off((i + 1) * KC5, DN, SP), N4_5, tid, wbuf_at(c + 1));  // static: i is unrolled
         const float* ws = wbuf_at(c);
         if constexpr (SP) chain_units<TD, 2>(hf[i], 0, mm, lds_addr(ws) + lane * 16, TD, 0, 0);
         else chain_tile<TD>(hf[i], mm, ws, DN, 0, 0, 4 * lh * DN + lj);
@@ -721,25 +677,23 @@ __global__ __launch_bounds__(256, chain_waves(T1)) void edge_chain_kernel(EdgeCh
 //   B6  d[e0 | e_{s-1}] = W1e^T dZ1  ->  dE0 += ..., dEprev = ...
 template <int T1, int T2, int TF, int TD, bool EXACT, bool SP>
 __global__ __launch_bounds__(256, chain_waves(T1)) void edge_chain_bwd_kernel(EdgeChainBwdArgs A) {
-    constexpr int HE = 32 * T1, DE = 32 * T2, HN = 32 * TF, DN = 32 * TD, HC = 32;
-    constexpr int NR2 = 16;   // B2 chunk: [16 n][HN]
-    constexpr int NR3 = 64;   // B3 chunk: [<=64 n][DE]
-    constexpr int NR5 = 16;   // B5 chunk: [16 n][HE]
-    constexpr int NR6 = 64;   // B6 chunk: [<=64 n][64 k]
+    constexpr int HE = 32 * T1, DE = 32 * T2, HN = 32 * TF, DN = 32 * TD, HC = CHAIN_HC;
+    // chunk sizes (chain_layout.h: the packers lay the images out for exactly this schedule)
+    constexpr int NR2 = ChainBwd::NR2, NR3 = ChainBwd::NR3, NR5 = ChainBwd::NR5, NR6 = ChainBwd::NR6, NC6 = ChainBwd::NC6;
+    constexpr int EPB = ChainGeom::EPB;
     // ---- chunk schedule: [B2 | B3] (flow groups only) B4 B5 B6; float4 counts of the contiguous chunks ------------
-    constexpr int NCH2 = DN / NR2, NCH3 = (HN + NR3 - 1) / NR3, NCH5 = DE / NR5, NCH6 = (HE + NR6 - 1) / NR6;
-    constexpr int SCN = SP ? 3 : 2;                                // split images: 3/2 the size (edge_chain.hip, split8)
-    constexpr int N4_2 = NR2 * HN / 4 * SCN / 2;                   // 16 rows of Wf2
-    constexpr int N4_3_0 = cmin(NR3, HN) * DE / 4 * SCN / 2;       // first 64 rows of Wfe
-    constexpr int N4_4 = HC * DE / 4 * SCN / 2;                    // Wc1, whole
-    constexpr int N4_5 = NR5 * HE / 4 * SCN / 2;                   // 16 rows of W2
-    constexpr int N4_6MAX = cmin(NR6, HE) * 64 / 4 * SCN / 2;      // <= 64 rows of one W1e column-pass image [HE][ncol6]
+    constexpr int NCH2 = DN / NR2, NCH3 = chain_nchunks(HN, NR3), NCH5 = DE / NR5, NCH6 = chain_nchunks(HE, NR6);
+    constexpr int N4_2 = chain_f4(NR2 * HN, SP);                             // 16 rows of Wf2
+    constexpr int N4_3_0 = chain_f4(chain_chunk_len(HN, NR3, 0) * DE, SP);   // first 64 rows of Wfe
+    constexpr int N4_4 = chain_f4(HC * DE, SP);                              // Wc1, whole
+    constexpr int N4_5 = chain_f4(NR5 * HE, SP);                             // 16 rows of W2
+    constexpr int N4_6MAX = chain_f4(chain_chunk_len(HE, NR6, 0) * NC6, SP); // <= 64 rows of one W1e column-pass image [HE][ncol6]
     constexpr int N4_MAX = cmax(cmax(N4_2, N4_3_0), cmax(cmax(N4_4, N4_5), N4_6MAX));
-    constexpr int CHF = SP ? 4 * N4_MAX : 1024 * chunk_q(N4_MAX);
+    constexpr int CHF = chain_chunk_buffer_floats(N4_MAX, SP);
     static_assert(CHF <= CH_FLOATS, "chunk too large");
-    // mask words per lane (edge_chain.h: chain_mask_words)
-    constexpr int W_H1 = 0, W_E = W_H1 + (T1 + 1) / 2, W_HC = W_E + (T2 + 1) / 2, W_HF = W_HC + 1, W_M = W_HF + (TF + 1) / 2,
-                  NW = W_M + (TD + 1) / 2;
+    // mask words per lane (chain_layout.h: ChainMaskWords)
+    using MW = ChainMaskWords<T1, T2, chain_tiles(HC), TF, TD>;
+    constexpr int W_H1 = MW::H1, W_E = MW::E, W_HC = MW::HC, W_HF = MW::HF, W_M = MW::M, NW = MW::NW;
 
     // one LDS object: two weight-chunk buffers, then wc2 (zero-padded to 32)
     __shared__ __attribute__((aligned(16))) float smem[2 * CHF + 32];
@@ -753,12 +707,12 @@ __global__ __launch_bounds__(256, chain_waves(T1)) void edge_chain_bwd_kernel(Ed
     const int e_out = A.header[1], e_in = A.header[2];
     int grp, beg, end, blk = blockIdx.x;
     {
-        const int nb0 = (e_out + 127) >> 7, nb1 = (e_in + 127) >> 7;
+        const int nb0 = chain_group_blocks(e_out), nb1 = chain_group_blocks(e_in);
         if (blk < nb0) { grp = 0; beg = 0; end = e_out; }
         else if (blk < nb0 + nb1) { grp = 1; blk -= nb0; beg = e_out; end = e_out + e_in; }
         else { grp = 2; blk -= nb0 + nb1; beg = e_out + e_in; end = A.E; }
     }
-    const int tile0 = beg + blk * 128;
+    const int tile0 = beg + blk * EPB;
     if (tile0 >= end) return;
     const int edge_raw = tile0 + wave * 32 + lj;
     const bool edge_ok = edge_raw < end;
@@ -793,8 +747,16 @@ __global__ __launch_bounds__(256, chain_waves(T1)) void edge_chain_bwd_kernel(Ed
     };
     auto flipped = [&](const f32x16& a) { f32x16 v = a; flip16(v, sx); return v; };
     const int KEp = A.cat_two ? 2 * DE : DE;  // padded columns of [e0 | e_{s-1}] (each half padded to DE)
-    const int npass6 = KEp / 64 > 0 ? KEp / 64 : 1;
-    const int ncol6 = KEp < 64 ? KEp : 64;    // columns per B6 pass
+    // (chain_w1e_passes / chain_w1e_cols / chain_w1e_off written out with the header's constants wherever the value is a RUN-TIME one:
+    // through a call -- force-inlined or not -- the same arithmetic reaches the optimiser in another order and the kernel's schedule
+    // moves; the static_asserts tie the two forms together)
+    constexpr int SCN = ChainScale::num(SP), SCD = ChainScale::DEN;
+    static_assert(chain_w1e_off(1, HE, NR6, NC6, SP) == ((int64_t)1 * HE + NR6) * NC6 * SCN / SCD && chain_w1e_passes(2 * NC6) == 2 &&
+                      chain_w1e_passes(32) == (32 / NC6 > 0 ? 32 / NC6 : 1) && chain_w1e_cols(32) == (32 < NC6 ? 32 : NC6) &&
+                      chain_chunk_len(HE, NR6, NCH6 - 1) == (HE - (NCH6 - 1) * NR6 < NR6 ? HE - (NCH6 - 1) * NR6 : NR6),
+                  "B6's written-out offsets follow chain_layout.h");
+    const int npass6 = KEp / NC6 > 0 ? KEp / NC6 : 1;
+    const int ncol6 = KEp < NC6 ? KEp : NC6;    // columns per B6 pass
 
     const float* wf2 = grp == 1 ? A.wf2_in : A.wf2_out;
     const float* wfe = grp == 1 ? A.wfe_in : A.wfe_out;
@@ -812,7 +774,7 @@ __global__ __launch_bounds__(256, chain_waves(T1)) void edge_chain_bwd_kernel(Ed
     // the ReLU masks (a few words), the gathered aggregate gradient, the incoming edge gradient, the logit gradient.
     unsigned mk[NW];
     {
-        const unsigned* mp = A.mask + ((int64_t)(blockIdx.x * 4 + wave) * NW) * 64 + lane;
+        const unsigned* mp = A.mask + ((int64_t)(blockIdx.x * ChainGeom::WAVES + wave) * NW) * 64 + lane;
 #pragma unroll
         for (int w = 0; w < NW; ++w) mk[w] = mp[w * 64];
     }
@@ -883,7 +845,7 @@ __global__ __launch_bounds__(256, chain_waves(T1)) void edge_chain_bwd_kernel(Ed
 #pragma unroll
         for (int i = 0; i < NCH2; ++i) {
             const bool more = i + 1 < NCH2;  // folds: i is unrolled
-            const float* nsrc = more ? wf2 + (i + 1) * (NR2 * HN * SCN / 2) : wfe;
+            const float* nsrc = more ? wf2 + chain_row_off((i + 1) * NR2, HN, SP) : wfe;
             const int nn4 = more ? N4_2 : N4_3_0;
             chunk_fetch<chunk_q(cmax(N4_2, N4_3_0)), SP>(nsrc, nn4, tid, wbuf_at(c + 1));
             if (i == NCH2 - 1) load_dE();
@@ -910,9 +872,9 @@ __global__ __launch_bounds__(256, chain_waves(T1)) void edge_chain_bwd_kernel(Ed
 #pragma unroll
         for (int i = 0; i < NCH3; ++i) {
             const bool more = i + 1 < NCH3;
-            const int rows_n = more ? (HN - (i + 1) * NR3 < NR3 ? HN - (i + 1) * NR3 : NR3) : 0;
-            const float* nsrc = more ? wfe + (i + 1) * (NR3 * DE * SCN / 2) : A.wc1;
-            const int nn4 = more ? rows_n * DE / 4 * SCN / 2 : N4_4;
+            const int rows_n = more ? chain_chunk_len(HN, NR3, i + 1) : 0;
+            const float* nsrc = more ? wfe + chain_row_off((i + 1) * NR3, DE, SP) : A.wc1;
+            const int nn4 = more ? chain_f4(rows_n * DE, SP) : N4_4;
             chunk_fetch<chunk_q(cmax(N4_3_0, N4_4)), SP>(nsrc, nn4, tid, wbuf_at(c + 1));
             const float* ws = wbuf_at(c);
             if constexpr (SP) {
@@ -965,14 +927,14 @@ __global__ __launch_bounds__(256, chain_waves(T1)) void edge_chain_bwd_kernel(Ed
     for (int t = 0; t < T1; ++t)
 #pragma unroll
         for (int r = 0; r < 16; ++r) dz1[t][r] = 0.f;
-    const int rows6_0 = HE < NR6 ? HE : NR6;
+    const int rows6_0 = chain_chunk_len(HE, NR6, 0);
     // (skip_e0: the passes of the e0 half -- the first KEp / 128 of them -- are not computed here)
     const int pass6_0 = A.skip_e0 ? npass6 / 2 : 0;
 #pragma unroll
     for (int i = 0; i < NCH5; ++i) {
         const bool more = i + 1 < NCH5;
-        const float* nsrc = more ? A.w2 + (i + 1) * (NR5 * HE * SCN / 2) : A.w1e + (int64_t)pass6_0 * HE * ncol6 * SCN / 2;
-        const int nn4 = more ? N4_5 : rows6_0 * ncol6 / 4 * SCN / 2;
+        const float* nsrc = more ? A.w2 + chain_row_off((i + 1) * NR5, HE, SP) : A.w1e + chain_w1e_off(pass6_0, HE, 0, ncol6, SP);
+        const int nn4 = more ? N4_5 : chain_f4(rows6_0 * ncol6, SP);
         chunk_fetch<chunk_q(cmax(N4_5, N4_6MAX)), SP>(nsrc, nn4, tid, wbuf_at(c + 1));
         // two sweeps over the same chunk keep the weight staging registers at about T1 / 2 per step
         constexpr int TA = (T1 + 1) / 2, TB = T1 - TA;
@@ -1030,8 +992,8 @@ __global__ __launch_bounds__(256, chain_waves(T1)) void edge_chain_bwd_kernel(Ed
             const int in = more ? i + 1 : (more_pass ? 0 : i);
             const int pn = more ? pass : (more_pass ? pass + 1 : pass);
             const int rows_n = HE - in * NR6 < NR6 ? HE - in * NR6 : NR6;
-            const float* nsrc = A.w1e + ((int64_t)pn * HE + in * NR6) * ncol6 * SCN / 2;
-            const int nn4 = rows_n * ncol6 / 4 * SCN / 2;
+            const float* nsrc = A.w1e + ((int64_t)pn * HE + in * NR6) * ncol6 * SCN / SCD;
+            const int nn4 = chain_f4(rows_n * ncol6, SP);
             chunk_fetch<chunk_q(N4_6MAX), SP>(nsrc, nn4, tid, wbuf_at(c + 1));
             const float* ws = wbuf_at(c);
             if constexpr (SP) {
@@ -1040,16 +1002,16 @@ __global__ __launch_bounds__(256, chain_waves(T1)) void edge_chain_bwd_kernel(Ed
                 // ahead of the pass loop and spills them)
                 asm volatile("" : "+v"(dz1[2 * i]));
                 if (2 * i + 1 < T1) asm volatile("" : "+v"(dz1[2 * i + 1 < T1 ? 2 * i + 1 : 0]));
-                if (ncol6 == 64) {
+                if (ncol6 == NC6) {
                     chain_units<2, 2>(dz1[2 * i], 0, dc, wa, 2, 0, 0);
                     if (2 * i + 1 < T1) chain_units<2, 2>(dz1[2 * i + 1], 0, dc, wa, 2, 2, 0);
                 } else {
                     chain_units<1, 2>(dz1[2 * i], 0, dc, wa, 1, 0, 0);
                     if (2 * i + 1 < T1) chain_units<1, 2>(dz1[2 * i + 1], 0, dc, wa, 1, 2, 0);
                 }
-            } else if (ncol6 == 64) {
-                chain_tile<2>(dz1[2 * i], dc, ws, 64, 0, 0, 4 * lh * 64 + lj);
-                if (2 * i + 1 < T1) chain_tile<2>(dz1[2 * i + 1], dc, ws, 64, 32, 0, 4 * lh * 64 + lj);
+            } else if (ncol6 == NC6) {
+                chain_tile<2>(dz1[2 * i], dc, ws, NC6, 0, 0, 4 * lh * NC6 + lj);
+                if (2 * i + 1 < T1) chain_tile<2>(dz1[2 * i + 1], dc, ws, NC6, 32, 0, 4 * lh * NC6 + lj);
             } else {
                 chain_tile<1>(dz1[2 * i], dc, ws, 32, 0, 0, 4 * lh * 32 + lj);
                 if (2 * i + 1 < T1) chain_tile<1>(dz1[2 * i + 1], dc, ws, 32, 32, 0, 4 * lh * 32 + lj);
@@ -1161,8 +1123,8 @@ int transpose_padded(const float* W, int64_t ldw, int k0, int n_rows, int k_cols
     return MPNHIP_OK;
 }
 
-int pack_padded(const float* src, int64_t lds, int c0, int rows, int cols, float* dst, int rows_pad, int cols_pad, int ldd,
-                int dst_c0, PackBatch* batch, hipStream_t s) {
+static int pack_padded(const float* src, int64_t lds, int c0, int rows, int cols, float* dst, int rows_pad, int cols_pad, int ldd,
+                       int dst_c0, PackBatch* batch, hipStream_t s) {
     const int64_t n = (int64_t)rows_pad * cols_pad;
     if (n <= 0) return MPNHIP_OK;
     if (pack_batch_add(batch, {src, dst, lds, c0, rows, cols, rows_pad, cols_pad, ldd, dst_c0, 0})) return MPNHIP_OK;
@@ -1170,6 +1132,61 @@ int pack_padded(const float* src, int64_t lds, int c0, int rows, int cols, float
                        cols_pad, ldd, dst_c0);
     MPN_LAUNCH_CHECK();
     return MPNHIP_OK;
+}
+
+// The images of edge_chain_kernel: logical WT[k][n] = W[n][k0 + k], zero-padded, as fp32 transposes or as split images (layout and
+// offsets: chain_layout.h -- the kernel's chunk schedule reads the same functions)
+int pack_edge_chain(const float* w_edge0, int ld_edge0, int col0_edge, int ke, const float* w_edge1, const float* w_cls0,
+                    const float* const w_flow0[2], int ld_flow0, int col0_flow, const float* const w_flow1[2], int he, int de, int hn, int dn,
+                    int hc, const ChainWeights& img, bool split, PackBatch* batch, SplitBatch* split_batch, hipStream_t s) {
+    const int HE = pad32(he), DE = pad32(de), HN = pad32(hn), DN = pad32(dn);
+    // one image: K x N real, Kp x Np padded, W's row stride ldw, its first contraction column k0
+    auto image = [&](const float* W, int ldw, int k0, int K, int N, int Kp, int Np, float* dst) {
+        return split ? pack_split(W + k0, 1, ldw, K, N, Kp, Np, dst, split_batch, s) : transpose_padded(W, ldw, k0, N, K, dst, Np, Kp, batch, s);
+    };
+    MPN_TRY(image(w_edge0, ld_edge0, col0_edge, ke, he, ke, HE, img.w1T));
+    MPN_TRY(image(w_edge1, he, 0, he, de, HE, DE, img.w2T));
+    MPN_TRY(image(w_cls0, de, 0, de, hc, DE, CHAIN_HC, img.wc1T));
+    for (int q = 0; q < 2; ++q) {
+        // flow layer 0, e'-part: one image [DE][<= NC4] per block of output features (the kernel streams whole blocks)
+        for (int i = 0; i < chain_wf1_blocks(HN); ++i) {
+            const int n0 = i * ChainFwd::NC4, ncw = chain_wf1_block_cols(HN, i);
+            const int rows = hn - n0 < 0 ? 0 : (hn - n0 < ncw ? hn - n0 : ncw);
+            MPN_TRY(image(w_flow0[q] + (int64_t)n0 * ld_flow0, ld_flow0, col0_flow, de, rows, DE, ncw, img.wf1T[q] + chain_wf1_block_off(DE, i, split)));
+        }
+        MPN_TRY(image(w_flow1[q], hn, 0, hn, dn, HN, DN, img.wf2T[q]));
+    }
+    return MPNHIP_OK;
+}
+
+// The images of edge_chain_bwd_kernel: the same weights in their native orientation (rows = contraction index n, columns = k),
+// recorded and packed by one launch (pack_split / pack_padded cannot fail once their sizes are valid: nothing returns before the flush)
+int pack_edge_chain_bwd(const float* w_edge0, int ld_edge0, int col0_edge, int ef, const float* w_edge1, const float* w_cls0,
+                        const float* const w_flow0[2], int ld_flow0, int col0_flow, const float* const w_flow1[2], int he, int de, int hn,
+                        int dn, int hc, const ChainBwdImages& img, bool split, hipStream_t s) {
+    const int HE = pad32(he), DE = pad32(de), HN = pad32(hn), DN = pad32(dn);
+    const int ncol6 = chain_w1e_cols(ef * DE);
+    SplitBatch sb;
+    PackBatch pb;
+    // rows x cols real (W's row stride ldw, first column c0), padded to Rp x Cp, at column dst_c0 of an image with ldd columns
+    auto image = [&](const float* W, int ldw, int c0, int rows, int cols, int Rp, int Cp, float* dst, int ldd, int dst_c0) {
+        return split ? pack_split(W + c0, ldw, 1, rows, cols, Rp, Cp, dst, &sb, s, ldd / 32, dst_c0 / 32)
+                     : pack_padded(W, ldw, c0, rows, cols, dst, Rp, Cp, ldd, dst_c0, &pb, s);
+    };
+    for (int q = 0; q < 2; ++q) {
+        MPN_TRY(image(w_flow1[q], hn, 0, dn, hn, DN, HN, img.wf2p[q], HN, 0));
+        MPN_TRY(image(w_flow0[q], ld_flow0, col0_flow, hn, de, HN, DE, img.wfep[q], DE, 0));
+    }
+    MPN_TRY(image(w_cls0, de, 0, hc, de, CHAIN_HC, DE, img.wc1p, DE, 0));
+    MPN_TRY(image(w_edge1, he, 0, de, he, DE, HE, img.w2p, HE, 0));
+    // e-part columns of edge layer 0 as one image [HE][ncol6] per pass of <= NC6 (padded) columns of [e0 | e_{s-1}]
+    // (the kernel streams whole rows of one pass image)
+    for (int hlf = 0; hlf < ef; ++hlf) {
+        const int col0 = hlf * DE;
+        MPN_TRY(image(w_edge0, ld_edge0, col0_edge + hlf * de, he, de, HE, DE, img.w1ep + chain_w1e_off(chain_w1e_pass_of(col0), HE, 0, ncol6, split),
+                      ncol6, chain_w1e_col_in_pass(col0)));
+    }
+    return split ? split_batch_flush(&sb, s) : pack_batch_flush(&pb, s);
 }
 
 #ifdef MPNHIP_CHAIN_TS
@@ -1180,7 +1197,7 @@ struct StampDump {
     int launches = 0;
     long long* prepare(unsigned blocks, hipStream_t s) {
         if (!getenv("MPNHIP_CHAIN_TS")) return nullptr;
-        const size_t need = (size_t)blocks * 4 * 16 * sizeof(long long);
+        const size_t need = (size_t)blocks * ChainGeom::WAVES * 16 * sizeof(long long);
         if (need > cap) { if (buf) (void)hipFree(buf); if (hipMalloc(&buf, need) != hipSuccess) return nullptr; cap = need; }
         (void)hipMemsetAsync(buf, 0, need, s);
         return buf;
@@ -1188,11 +1205,11 @@ struct StampDump {
     void finish(const char* name, unsigned blocks, hipStream_t s) {
         if (!buf || !getenv("MPNHIP_CHAIN_TS") || ++launches != 40) return;
         (void)hipStreamSynchronize(s);
-        std::vector<long long> h((size_t)blocks * 64);
+        std::vector<long long> h((size_t)blocks * ChainGeom::WAVES * 16);
         (void)hipMemcpy(h.data(), buf, h.size() * sizeof(long long), hipMemcpyDeviceToHost);
         std::string path = std::string(getenv("MPNHIP_CHAIN_TS")) + "_" + name + ".txt";
         if (FILE* f = fopen(path.c_str(), "w")) {
-            for (unsigned w = 0; w < blocks * 4; ++w) {
+            for (unsigned w = 0; w < blocks * ChainGeom::WAVES; ++w) {
                 for (int i = 0; i < 16; ++i) fprintf(f, "%lld ", h[(size_t)w * 16 + i]);
                 fprintf(f, "\n");
             }
@@ -1308,17 +1325,9 @@ int launch_edge_encoder_mfma(const float* x, const int* idx, int64_t rows, int i
     return 1;
 }
 
-static int chain_variant(int he, int de, int hn, int dn) {
-    const int t1 = (he + 31) / 32, t2 = (de + 31) / 32, tf = (hn + 31) / 32, td = (dn + 31) / 32;
-    if (t1 == 10 && t2 == 2 && tf == 7 && td == 4) return 128;
-    if (t1 == 5 && t2 == 1 && tf == 4 && td == 2) return 64;
-    if (t1 == 3 && t2 == 1 && tf == 2 && td == 1) return 32;
-    return 0;
-}
-
 bool edge_chain_supported(int he, int de, int hn, int dn, int hc, int k1a, int k1b) {
-    return chain_variant(he, de, hn, dn) != 0 && hc >= 4 && hc <= 32 && he % 4 == 0 && de % 4 == 0 && hn % 4 == 0 && dn % 4 == 0 &&
-           hc % 4 == 0 && (k1a % 16 == 0) && (k1b % 16 == 0) && (k1a + k1b) >= 16;
+    return chain_variant(he, de, hn, dn) >= 0 && hc >= 4 && hc <= CHAIN_HC && he % 4 == 0 && de % 4 == 0 && hn % 4 == 0 && dn % 4 == 0 &&
+           hc % 4 == 0 && (k1a % ChainFwd::KC1 == 0) && (k1b % ChainFwd::KC1 == 0) && (k1a + k1b) >= ChainFwd::KC1;
 }
 
 int launch_edge_chain(const EdgeChainArgs& a_in, hipStream_t s) {
@@ -1329,33 +1338,16 @@ int launch_edge_chain(const EdgeChainArgs& a_in, hipStream_t s) {
         set_error("edge_chain: graph too large for 32-bit row offsets (E * he or N * pw >= 2^32)");
         return MPNHIP_ERR_UNSUPPORTED;
     }
-    const unsigned blocks = (unsigned)((a.E + 127) / 128 + 3);
+    const unsigned blocks = chain_blocks(a.E);
     count_path(a.split ? PC_CHAIN_FWD_SPLIT : PC_CHAIN_FWD);
 #ifdef MPNHIP_CHAIN_TS
     a.ts = g_stamp_fwd.prepare(blocks, s);
 #endif
-    const bool exact = a.he % 32 == 0 && a.de % 32 == 0 && a.hn % 32 == 0 && a.dn % 32 == 0 && a.hc == 32;
-    switch (chain_variant(a.he, a.de, a.hn, a.dn)) {
-        case 128:
-            if (a.split && exact)
-                MPN_LAUNCH_PROFILED((edge_chain_kernel<10, 2, 7, 4, true, true>), dim3(blocks), dim3(256), s, a);
-            else if (a.split)
-                MPN_LAUNCH_PROFILED((edge_chain_kernel<10, 2, 7, 4, false, true>), dim3(blocks), dim3(256), s, a);
-            else if (exact)
-                MPN_LAUNCH_PROFILED((edge_chain_kernel<10, 2, 7, 4, true, false>), dim3(blocks), dim3(256), s, a);
-            else
-                MPN_LAUNCH_PROFILED((edge_chain_kernel<10, 2, 7, 4, false, false>), dim3(blocks), dim3(256), s, a);
-            break;
-        case 64:
-            if (a.split) MPN_LAUNCH_PROFILED((edge_chain_kernel<5, 1, 4, 2, false, true>), dim3(blocks), dim3(256), s, a);
-            else MPN_LAUNCH_PROFILED((edge_chain_kernel<5, 1, 4, 2, false, false>), dim3(blocks), dim3(256), s, a);
-            break;
-        case 32:
-            if (a.split) MPN_LAUNCH_PROFILED((edge_chain_kernel<3, 1, 2, 1, false, true>), dim3(blocks), dim3(256), s, a);
-            else MPN_LAUNCH_PROFILED((edge_chain_kernel<3, 1, 2, 1, false, false>), dim3(blocks), dim3(256), s, a);
-            break;
-        default: set_error("edge_chain: unsupported widths"); return MPNHIP_ERR_UNSUPPORTED;
-    }
+    const bool found = chain_dispatch(chain_variant(a.he, a.de, a.hn, a.dn), chain_widths_exact(a.he, a.de, a.hn, a.dn, a.hc), a.split != 0, [&](auto v) {
+        using V = decltype(v);
+        MPN_LAUNCH_PROFILED((edge_chain_kernel<V::T1, V::T2, V::TF, V::TD, V::EXACT, V::SP>), dim3(blocks), dim3(ChainGeom::THREADS), s, a);
+    });
+    if (!found) { set_error("edge_chain: unsupported widths"); return MPNHIP_ERR_UNSUPPORTED; }
 #ifdef MPNHIP_CHAIN_TS
     g_stamp_fwd.finish("fwd", blocks, s);
 #endif
@@ -1366,33 +1358,16 @@ int launch_edge_chain(const EdgeChainArgs& a_in, hipStream_t s) {
 int launch_edge_chain_bwd(const EdgeChainBwdArgs& a_in, hipStream_t s) {
     if (a_in.E <= 0) return MPNHIP_OK;
     EdgeChainBwdArgs a = a_in;
-    const unsigned blocks = (unsigned)((a.E + 127) / 128 + 3);
+    const unsigned blocks = chain_blocks(a.E);
     count_path(a.split ? PC_CHAIN_BWD_SPLIT : PC_CHAIN_BWD);
 #ifdef MPNHIP_CHAIN_TS
     a.ts = g_stamp_bwd.prepare(blocks, s);
 #endif
-    const bool exact = a.he % 32 == 0 && a.de % 32 == 0 && a.hn % 32 == 0 && a.dn % 32 == 0 && a.hc == 32;
-    switch (chain_variant(a.he, a.de, a.hn, a.dn)) {
-        case 128:
-            if (a.split && exact)
-                MPN_LAUNCH_PROFILED((edge_chain_bwd_kernel<10, 2, 7, 4, true, true>), dim3(blocks), dim3(256), s, a);
-            else if (a.split)
-                MPN_LAUNCH_PROFILED((edge_chain_bwd_kernel<10, 2, 7, 4, false, true>), dim3(blocks), dim3(256), s, a);
-            else if (exact)
-                MPN_LAUNCH_PROFILED((edge_chain_bwd_kernel<10, 2, 7, 4, true, false>), dim3(blocks), dim3(256), s, a);
-            else
-                MPN_LAUNCH_PROFILED((edge_chain_bwd_kernel<10, 2, 7, 4, false, false>), dim3(blocks), dim3(256), s, a);
-            break;
-        case 64:
-            if (a.split) MPN_LAUNCH_PROFILED((edge_chain_bwd_kernel<5, 1, 4, 2, false, true>), dim3(blocks), dim3(256), s, a);
-            else MPN_LAUNCH_PROFILED((edge_chain_bwd_kernel<5, 1, 4, 2, false, false>), dim3(blocks), dim3(256), s, a);
-            break;
-        case 32:
-            if (a.split) MPN_LAUNCH_PROFILED((edge_chain_bwd_kernel<3, 1, 2, 1, false, true>), dim3(blocks), dim3(256), s, a);
-            else MPN_LAUNCH_PROFILED((edge_chain_bwd_kernel<3, 1, 2, 1, false, false>), dim3(blocks), dim3(256), s, a);
-            break;
-        default: set_error("edge_chain_bwd: unsupported widths"); return MPNHIP_ERR_UNSUPPORTED;
-    }
+    const bool found = chain_dispatch(chain_variant(a.he, a.de, a.hn, a.dn), chain_widths_exact(a.he, a.de, a.hn, a.dn, a.hc), a.split != 0, [&](auto v) {
+        using V = decltype(v);
+        MPN_LAUNCH_PROFILED((edge_chain_bwd_kernel<V::T1, V::T2, V::TF, V::TD, V::EXACT, V::SP>), dim3(blocks), dim3(ChainGeom::THREADS), s, a);
+    });
+    if (!found) { set_error("edge_chain_bwd: unsupported widths"); return MPNHIP_ERR_UNSUPPORTED; }
 #ifdef MPNHIP_CHAIN_TS
     g_stamp_bwd.finish("bwd", blocks, s);
 #endif

@@ -67,11 +67,11 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void edge_chain_bf16_kern
     constexpr int SECC = KBE;              // per HC tile section (classifier layer 0 only; its layer 1 is a dot product)
     constexpr int CT = CTI;                // hidden tiles per chunk
     constexpr int NCH1 = (T1 + CT - 1) / CT, NCHF = (TF + CT - 1) / CT;
-    constexpr int CHU = bmax(bmax(CT * SEC1, CT * SECF), TC * SECC);   // KiB per chunk buffer
+    constexpr int CHU = cmax(cmax(CT * SEC1, CT * SECF), TC * SECC);   // KiB per chunk buffer
     // one LDS object: two chunk buffers, then the biases [b2 (DE) | bc1 (HC) | wc2 (HC) | bf2 (DN)], zero-padded
     // (the fused aggregation's per-wave slabs reuse the chunk buffers after the last chunk: 8 x [32 edges][32 RT + 1] floats)
     constexpr int AGG_RT = TD >= 2 ? 2 : 1, AGG_BYTES = NW * (32 * AGG_RT) * 36 * 4;
-    constexpr int WB_BYTES = bmax(2 * CHU * 1024, (AGG_BYTES + 15) / 16 * 16);
+    constexpr int WB_BYTES = cmax(2 * CHU * 1024, (AGG_BYTES + 15) / 16 * 16);
     static_assert(!GD || (EXACT && !SAVE && ROW_SLAB_BYTES >= 4096), "the DMA gathers fetch whole 128-byte pieces into the row slabs");
     __shared__ __attribute__((aligned(16))) char smem[WB_BYTES + (DE + 2 * HC + DN) * 4];
     // per-wave slabs of the full-line row stores (RowStage): a separate object, never the target of an LDS-DMA
@@ -104,7 +104,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void edge_chain_bf16_kern
 
     TS16_INIT();
     TS16(0);
-    chunk_fetch<bmin(CT, T1) * SEC1, NW>(img1, WBUF(0), wave, lane);
+    chunk_fetch<cmin(CT, T1) * SEC1, NW>(img1, WBUF(0), wave, lane);
     {
         const float* bf2 = grp == 1 ? A.bf2_in : A.bf2_out;
         for (int i = tid; i < DE + 2 * HC + DN; i += 64 * NW) {
@@ -163,8 +163,8 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void edge_chain_bf16_kern
                                              (__attribute__((address_space(3))) void*)(gp_ptr + q * 1024), 16, 0, 0);
     };
     // training saves: mask words of this wave tile (sections H1 | e' | HC | HF | M, two tiles per word)
-    constexpr int WB_E = (T1 + 1) / 2, WB_C = WB_E + (T2 + 1) / 2, WB_F = WB_C + (TC + 1) / 2, WB_M = WB_F + (TF + 1) / 2;
-    constexpr int NWORDS = WB_M + (TD + 1) / 2;
+    using MW = ChainMaskWords<T1, T2, TC, TF, TD>;   // (chain_layout.h)
+    constexpr int WB_E = MW::E, WB_C = MW::HC, WB_F = MW::HF, WB_M = MW::M, NWORDS = MW::NW;
     unsigned mw = 0;
     const unsigned ones = 0x00010001u;
     unsigned* const mask_wt = SAVE ? A.save_mask + ((size_t)(blockIdx.x * NW + wave) * NWORDS) * 64 + lane : nullptr;
@@ -259,7 +259,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void edge_chain_bf16_kern
     int c = 0;
 #pragma unroll
     for (int ch = 0; ch < NCH1; ++ch) {
-        const int nt = bmin(CT, T1 - ch * CT);
+        const int nt = cmin(CT, T1 - ch * CT);
         // the next chunk's DMA goes out AFTER the first tile has taken its gathered C-in (the compiler's wait for those loads is
         // vmcnt(0): issued earlier, the DMA would be waited for right there, its whole L2 latency exposed once per chunk)
         auto fetch_next = [&]() {
@@ -330,7 +330,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void edge_chain_bf16_kern
     if constexpr (GD) { if (flow) pf_issue(0); }   // (after the e' rows left through the slab the patch shares)
     TS16(22);
     // ---- phase 3: classifier (its image is in the current buffer) -------------------------------------------------------
-    if (flow) chunk_fetch<bmin(CT, TF) * SECF, NW>(imgf, WBUF(c + 1), wave, lane);
+    if (flow) chunk_fetch<cmin(CT, TF) * SECF, NW>(imgf, WBUF(c + 1), wave, lane);
     {
         float part = 0.f;
 #pragma unroll
@@ -382,7 +382,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void edge_chain_bf16_kern
         for (int r = 0; r < 16; ++r) mm[o][r] = 0.f;
 #pragma unroll
     for (int ch = 0; ch < NCHF; ++ch) {
-        const int nt = bmin(CT, TF - ch * CT);
+        const int nt = cmin(CT, TF - ch * CT);
         auto fetch_next = [&]() {
             if (ch + 1 < NCHF) {
                 if (TF - (ch + 1) * CT >= CT) chunk_fetch<CT * SECF, NW>(imgf + (size_t)(ch + 1) * CT * SECF * 1024, WBUF(c + 1), wave, lane);
@@ -606,19 +606,8 @@ int pack_pair_bf16_general(const float* Wa, int64_t sa_n, int64_t sa_k, int a_co
     return MPNHIP_OK;
 }
 
-static int chain_bf16_variant(int he, int de, int hn, int dn, int hc) {
-    const int t1 = (he + 31) / 32, t2 = (de + 31) / 32, tf = (hn + 31) / 32, td = (dn + 31) / 32, tc = (hc + 31) / 32;
-    if (t1 == 20 && t2 == 4 && tf == 14 && td == 8 && tc == 2) return 256;
-    if (t1 == 10 && t2 == 2 && tf == 7 && td == 4 && tc == 1) return 128;
-    if (t1 == 5 && t2 == 1 && tf == 4 && td == 2 && tc == 1) return 64;
-    if (t1 == 3 && t2 == 1 && tf == 2 && td == 1 && tc == 1) return 32;
-    return 0;
-}
-
 bool edge_chain_bf16_supported(int he, int de, int hn, int dn, int hc, int ef) {
-    const int v = chain_bf16_variant(he, de, hn, dn, hc);
-    if (v == 256 && !(he % 32 == 0 && de % 32 == 0 && hn % 32 == 0 && dn % 32 == 0)) return false;
-    return v != 0 && ef == 2 && he % 4 == 0 && de % 4 == 0 && hn % 4 == 0 && dn % 4 == 0 && hc >= 1;
+    return chain_bf16_fwd_widths_ok(he, de, hn, dn, hc) && ef == 2 && he % 4 == 0 && de % 4 == 0 && hn % 4 == 0 && dn % 4 == 0 && hc >= 1;
 }
 
 size_t chain_bf16_image_bytes(int he, int de, int hn, int dn, int hc, int ef, size_t* off_cls, size_t* off_flow0, size_t* off_flow1) {
@@ -650,16 +639,14 @@ int launch_edge_chain_bf16(const EdgeChainBf16Args& a_in, hipStream_t s) {
     if (a_in.E <= 0) return MPNHIP_OK;
     EdgeChainBf16Args a = a_in;
     if (const char* e = getenv("MPNHIP_CHAIN_BF16_PLAIN_BARRIERS")) a.plain_barriers = e[0] == '1' ? 1 : 0;
-    if ((int64_t)a.E * bmax(bmax(a.he, a.dn), a.de) >= ((int64_t)1 << 32) || (int64_t)a.N * a.pw >= ((int64_t)1 << 32)) {
+    if ((int64_t)a.E * cmax(cmax(a.he, a.dn), a.de) >= ((int64_t)1 << 32) || (int64_t)a.N * a.pw >= ((int64_t)1 << 32)) {
         set_error("edge_chain_bf16: graph too large for 32-bit row offsets");
         return MPNHIP_ERR_UNSUPPORTED;
     }
     // 256-d: 4-wave blocks, two per CU (cfg-E: 643 -> 581 us per launch against one 8-wave block)
-    const int variant = chain_bf16_variant(a.he, a.de, a.hn, a.dn, a.hc);
     int epb, nwv;
     chain_bf16_geometry(a.he, a.de, a.hn, a.dn, a.hc, &epb, &nwv);
-    const bool four = nwv == 4;
-    const unsigned blocks = (unsigned)((a.E + epb - 1) / epb + 3);
+    const unsigned blocks = chain_bf16_blocks(a.E, epb);
     count_path(PC_CHAIN_FWD_BF16);
     const bool exact = a.he % 32 == 0 && a.de % 32 == 0 && a.hn % 32 == 0 && a.dn % 32 == 0;
 #ifdef MPNHIP_CHAIN_TS
@@ -677,28 +664,24 @@ int launch_edge_chain_bf16(const EdgeChainBf16Args& a_in, hipStream_t s) {
     if (save && !(a.save_h1 && a.save_hc && a.save_hf && a.save_eb)) { set_error("edge_chain_bf16: incomplete save buffers"); return MPNHIP_ERR_ARG; }
     if (save) a.e16_out = a.save_eb;
     if (!a.e_new && !a.e16_out) { set_error("edge_chain_bf16: no output for the edge features"); return MPNHIP_ERR_ARG; }
-#define MPN_CB16(SV, ...) do { if (SV) MPN_LAUNCH_PROFILED((edge_chain_bf16_kernel<__VA_ARGS__, true>), dim3(blocks), dim3(512), s, a); \
-                              else MPN_LAUNCH_PROFILED((edge_chain_bf16_kernel<__VA_ARGS__, false>), dim3(blocks), dim3(512), s, a); } while (0)
-    switch (variant) {
-        case 256:
-            // (widths that are multiples of 32 only: the masked form of this variant does not fit the register budget)
-            if (save) MPN_LAUNCH_PROFILED((edge_chain_bf16_kernel<20, 4, 14, 8, 2, 2, true, 4, 1, true>), dim3(blocks), dim3(256), s, a);
-            else MPN_LAUNCH_PROFILED((edge_chain_bf16_kernel<20, 4, 14, 8, 2, 2, true, 4, 1, false, DEPTH, true>), dim3(blocks), dim3(256), s, a);
-            break;
-        case 128:
-            if (exact) MPN_CB16(save, 10, 2, 7, 4, 1, 2, true, 8, 2);
-            else MPN_CB16(save, 10, 2, 7, 4, 1, 2, false, 8, 2);
-            break;
-        case 64: MPN_CB16(save, 5, 1, 4, 2, 1, 2, false, 8, 2); break;
-        case 32: MPN_CB16(save, 3, 1, 2, 1, 1, 2, false, 8, 2); break;
-        default: set_error("edge_chain_bf16: unsupported widths"); return MPNHIP_ERR_UNSUPPORTED;
-    }
-#undef MPN_CB16
+    // (256-d, widths that are multiples of 32 only: the masked form of this variant does not fit the register budget; its inference
+    // form gathers by LDS-DMA)
+    const bool found = chain_bf16_dispatch(chain_bf16_variant(a.he, a.de, a.hn, a.dn, a.hc), exact, [&](auto v) {
+        using V = decltype(v);
+        constexpr bool GD = V::NW == 4;
+        if (save)
+            MPN_LAUNCH_PROFILED((edge_chain_bf16_kernel<V::T1, V::T2, V::TF, V::TD, V::TC, 2, V::EXACT, V::NW, V::CT, true>), dim3(blocks),
+                                dim3(64 * V::NW), s, a);
+        else
+            MPN_LAUNCH_PROFILED((edge_chain_bf16_kernel<V::T1, V::T2, V::TF, V::TD, V::TC, 2, V::EXACT, V::NW, V::CT, false, DEPTH, GD>), dim3(blocks),
+                                dim3(64 * V::NW), s, a);
+    });
+    if (!found) { set_error("edge_chain_bf16: unsupported widths"); return MPNHIP_ERR_UNSUPPORTED; }
     MPN_LAUNCH_CHECK();
 #ifdef MPNHIP_CHAIN_TS
     if (a.ts && ++ts_launches == 20) {
         (void)hipStreamSynchronize(s);
-        const size_t n = (size_t)blocks * (four ? 4 : 8) * 48;
+        const size_t n = (size_t)blocks * nwv * 48;
         long long* h = (long long*)malloc(n * sizeof(long long));
         (void)hipMemcpy(h, a.ts, n * sizeof(long long), hipMemcpyDeviceToHost);
         char path[512];
@@ -711,17 +694,11 @@ int launch_edge_chain_bf16(const EdgeChainBf16Args& a_in, hipStream_t s) {
     }
 #endif
     if (a.agg_out) {
-        hipLaunchKernelGGL(k_agg_fixup, dim3(blocks * (four ? 4 : 8)), dim3(64), 0, s, a.header, a.seg_ptr, a.start_row, a.piece, a.agg_out,
-                           a.N, a.dn, (a.dn + 31) / 32 * 32, a.agg, four ? 4 : 8);
+        hipLaunchKernelGGL(k_agg_fixup, dim3(blocks * nwv), dim3(64), 0, s, a.header, a.seg_ptr, a.start_row, a.piece, a.agg_out,
+                           a.N, a.dn, pad32(a.dn), a.agg, nwv);
         MPN_LAUNCH_CHECK();
     }
     return MPNHIP_OK;
-}
-
-void chain_bf16_geometry(int he, int de, int hn, int dn, int hc, int* epb, int* nw) {
-    const bool four = chain_bf16_variant(he, de, hn, dn, hc) == 256;
-    *epb = four ? 128 : 256;
-    *nw = four ? 4 : 8;
 }
 
 __global__ __launch_bounds__(256) void k_to_bf16(const float* __restrict__ src, unsigned short* __restrict__ dst, int64_t n4) {
@@ -783,15 +760,14 @@ int chain_bf16_debug_mask(const unsigned* mask, int section, const int* header, 
     if (E <= 0) return MPNHIP_OK;
     const int widths[5] = {he, de, hc, hn, dn};
     MPN_CHECK_ARG(section >= 0 && section < 5, "chain_bf16_debug_mask: section %d", section);
-    int wbase = 0;
-    for (int i = 0; i < section; ++i) wbase += ((widths[i] + 31) / 32 + 1) / 2;
+    const int wbase = chain_mask_section_word(chain_mask_sections(chain_tiles(he), chain_tiles(de), chain_tiles(hc), chain_tiles(hn), chain_tiles(dn)), section);
     int epb, nw;
     chain_bf16_geometry(he, de, hn, dn, hc, &epb, &nw);
-    const unsigned blocks = (unsigned)((E + epb - 1) / epb + 3);
+    const unsigned blocks = chain_bf16_blocks(E, epb);
     // (self-loop edges take no part in the flow MLPs: their HF / M words are never written -- zero the output first)
     MPN_HIP(hipMemsetAsync(out, 0, (size_t)E * widths[section] * sizeof(float), s));
     hipLaunchKernelGGL(k_bf16_debug_mask, dim3(blocks * nw), dim3(64), 0, s, mask, wbase, chain_bf16_mask_words(he, de, hn, dn, hc),
-                       (widths[section] + 31) / 32, widths[section], section >= 3 ? 1 : 0, header, perm, (int)E, epb, nw, out);
+                       chain_tiles(widths[section]), widths[section], section >= 3 ? 1 : 0, header, perm, (int)E, epb, nw, out);
     MPN_LAUNCH_CHECK();
     return MPNHIP_OK;
 }
@@ -801,7 +777,7 @@ size_t chain_bf16_agg_scratch_floats(int64_t E, int dn, size_t* off_start_row) {
     // directly: the pieces are whole 256-byte units whatever E and dn are
     constexpr size_t TILE_GROUP = 8, DN_PAD = 32;
     static_assert(TILE_GROUP * 2 * DN_PAD * sizeof(float) % 256 == 0, "the piece part must end on a region boundary of the Carver");
-    const size_t tiles = (size_t)((E + 255) / 256 + 3) * TILE_GROUP, DN = (size_t)(dn + DN_PAD - 1) / DN_PAD * DN_PAD;
+    const size_t tiles = (size_t)chain_bf16_blocks(E, 32 * (int)TILE_GROUP) * TILE_GROUP, DN = (size_t)(dn + DN_PAD - 1) / DN_PAD * DN_PAD;
     if (off_start_row) *off_start_row = tiles * 2 * DN;
     return tiles * 2 * DN + tiles;
 }

@@ -33,9 +33,9 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void edge_chain_bf16_bwd_
     constexpr int SECC = 2 * T2;            // per HC tile: Wc1^T (2 k blocks x T2 output tiles)
     constexpr int SEC1 = KBE + 2 * T2;      // per H1 tile: W2^T (k blocks of de) | W1e^T (2 k blocks x T2 output tiles)
     constexpr int NCHF = (TF + CT - 1) / CT, NCH1 = (T1 + CT - 1) / CT;
-    constexpr int CHU = bmax(bmax(CT * SECF, CT * SEC1), TC * SECC);
-    constexpr int WB_E = (T1 + 1) / 2, WB_C = WB_E + (T2 + 1) / 2, WB_F = WB_C + (TC + 1) / 2, WB_M = WB_F + (TF + 1) / 2;
-    constexpr int NWORDS = WB_M + (TD + 1) / 2;
+    constexpr int CHU = cmax(cmax(CT * SECF, CT * SEC1), TC * SECC);
+    using MW = ChainMaskWords<T1, T2, TC, TF, TD>;   // (chain_layout.h)
+    constexpr int WB_E = MW::E, WB_C = MW::HC, WB_F = MW::HF, WB_M = MW::M, NWORDS = MW::NW;
     __shared__ __attribute__((aligned(16))) char smem[2 * CHU * 1024 + HC * 4];
     __shared__ __attribute__((aligned(16))) char rowslab[NW * ROW_SLAB_BYTES];   // full-line row stores (RowStage)
     float* const swc2 = reinterpret_cast<float*>(smem + 2 * CHU * 1024);
@@ -63,7 +63,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void edge_chain_bf16_bwd_
     const char* const imgf = static_cast<const char*>(grp == 1 ? A.img_flow[1] : A.img_flow[0]);
     const char* const img1 = static_cast<const char*>(A.img_edge);
 
-    if (flow) chunk_fetch<bmin(CT, TF) * SECF, NW>(imgf, WBUF(0), wave, lane);
+    if (flow) chunk_fetch<cmin(CT, TF) * SECF, NW>(imgf, WBUF(0), wave, lane);
     else chunk_fetch<TC * SECC, NW>(static_cast<const char*>(A.img_cls), WBUF(0), wave, lane);
     for (int i = tid; i < HC; i += 64 * NW) swc2[i] = i < hc ? A.wc2[i] : 0.f;
 
@@ -98,7 +98,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void edge_chain_bf16_bwd_
     if (flow) {
         // ---- B1: dZM = gather(dAGG)[row] (.) [M > 0]  (node_agg_fn backward, mpn.py:89,96) ---------------------------------
         bf16x8 X[KBM];
-        unsigned mwf[(TF + 1) / 2];
+        unsigned mwf[chain_pair_words(TF)];
         {
             const int row = A.srow[edge];
             const unsigned ro = (unsigned)row * (unsigned)(2 * dn) + (unsigned)(grp == 0 ? dn : 0);
@@ -109,7 +109,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void edge_chain_bf16_bwd_
                 scale = (float)(cnt > 0 ? cnt : 1);
             }
 #pragma unroll
-            for (int w = 0; w < (TF + 1) / 2; ++w) mwf[w] = mask_wt[(size_t)(WB_F + w) * 64];
+            for (int w = 0; w < chain_pair_words(TF); ++w) mwf[w] = mask_wt[(size_t)(WB_F + w) * 64];
 #pragma unroll
             for (int t = 0; t < TD; ++t) {
                 f32x16 v;
@@ -137,7 +137,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void edge_chain_bf16_bwd_
         // ---- B2 + B3: per HF tile  dZF_t = (Wf2[:, t]^T dZM) (.) [HF_t > 0]  ->  dE' += Wfe[t, :]^T dZF_t ---------------------
 #pragma unroll
         for (int ch = 0; ch < NCHF; ++ch) {
-            const int nt = bmin(CT, TF - ch * CT);
+            const int nt = cmin(CT, TF - ch * CT);
             if (ch + 1 < NCHF) {
                 if (TF - (ch + 1) * CT >= CT) chunk_fetch<CT * SECF, NW>(imgf + (size_t)(ch + 1) * CT * SECF * 1024, WBUF(c + 1), wave, lane);
                 else chunk_fetch<(TF % CT ? TF % CT : CT) * SECF, NW>(imgf + (size_t)(ch + 1) * CT * SECF * 1024, WBUF(c + 1), wave, lane);
@@ -168,7 +168,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void edge_chain_bf16_bwd_
 
     // ---- B4: classifier (its image is in the current buffer): dZc = (dlog wc2) (.) [HC > 0];  dE' += Wc1^T dZc ----------------
     // the gradient arriving from the later step joins here (fetched under the classifier's products)
-    chunk_fetch<bmin(CT, T1) * SEC1, NW>(img1, WBUF(c + 1), wave, lane);
+    chunk_fetch<cmin(CT, T1) * SEC1, NW>(img1, WBUF(c + 1), wave, lane);
     pin_order();
     float4 din[4 * T2];
     {
@@ -178,9 +178,9 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void edge_chain_bf16_bwd_
 #pragma unroll
             for (int g = 0; g < 4; ++g) din[4 * o + g] = ldrow<EXACT>(A.dE_in, eo, 32 * o + 8 * g + 4 * lh, de);
     }
-    unsigned mw1[(T1 + 1) / 2];
+    unsigned mw1[chain_pair_words(T1)];
 #pragma unroll
-    for (int w = 0; w < (T1 + 1) / 2; ++w) mw1[w] = mask_wt[(size_t)w * 64];
+    for (int w = 0; w < chain_pair_words(T1); ++w) mw1[w] = mask_wt[(size_t)w * 64];
     {
         const unsigned mwc = mask_wt[(size_t)WB_C * 64];
         static_assert(TC <= 2, "classifier hidden width up to 64");
@@ -245,7 +245,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void edge_chain_bf16_bwd_
     // ---- B5 + B6: per H1 tile  dZ1_t = (W2[:, t]^T dZ2) (.) [H1_t > 0]  ->  dE_prev += W1e[t, e columns]^T dZ1_t ---------------
 #pragma unroll
     for (int ch = 0; ch < NCH1; ++ch) {
-        const int nt = bmin(CT, T1 - ch * CT);
+        const int nt = cmin(CT, T1 - ch * CT);
         if (ch + 1 < NCH1) {
             if (T1 - (ch + 1) * CT >= CT) chunk_fetch<CT * SEC1, NW>(img1 + (size_t)(ch + 1) * CT * SEC1 * 1024, WBUF(c + 1), wave, lane);
             else chunk_fetch<(T1 % CT ? T1 % CT : CT) * SEC1, NW>(img1 + (size_t)(ch + 1) * CT * SEC1 * 1024, WBUF(c + 1), wave, lane);
@@ -318,29 +318,16 @@ int launch_edge_chain_bf16_bwd(const EdgeChainBf16BwdArgs& a_in, hipStream_t s) 
     }
     int epb, nw;
     chain_bf16_geometry(a.he, a.de, a.hn, a.dn, a.hc, &epb, &nw);
-    const unsigned blocks = (unsigned)((a.E + epb - 1) / epb + 3);
-    const bool exact = a.he % 32 == 0 && a.de % 32 == 0 && a.hn % 32 == 0 && a.dn % 32 == 0 && a.hc % 32 == 0;
-    const int t1 = (a.he + 31) / 32, t2 = (a.de + 31) / 32, tf = (a.hn + 31) / 32, td = (a.dn + 31) / 32, tc = (a.hc + 31) / 32;
+    const unsigned blocks = chain_bf16_blocks(a.E, epb);
     if (!edge_chain_bf16_bwd_supported(a.he, a.de, a.hn, a.dn, a.hc)) {
         set_error("edge_chain_bf16_bwd: unsupported widths");
         return MPNHIP_ERR_UNSUPPORTED;
     }
     count_path(PC_CHAIN_BWD_BF16);
-#define MPN_CBB(...) MPN_LAUNCH_PROFILED((edge_chain_bf16_bwd_kernel<__VA_ARGS__>), dim3(blocks), dim3(64 * nw), s, a)
-    if (t1 == 20 && t2 == 4 && tf == 14 && td == 8 && tc == 2 && exact) {
-        MPN_CBB(20, 4, 14, 8, 2, true, 4, 1);
-    } else if (t1 == 10 && t2 == 2 && tf == 7 && td == 4 && tc == 1) {
-        if (exact) MPN_CBB(10, 2, 7, 4, 1, true, 8, 2);
-        else MPN_CBB(10, 2, 7, 4, 1, false, 8, 2);
-    } else if (t1 == 5 && t2 == 1 && tf == 4 && td == 2 && tc == 1) {
-        MPN_CBB(5, 1, 4, 2, 1, false, 8, 2);
-    } else if (t1 == 3 && t2 == 1 && tf == 2 && td == 1 && tc == 1) {
-        MPN_CBB(3, 1, 2, 1, 1, false, 8, 2);
-    } else {
-        set_error("edge_chain_bf16_bwd: unsupported widths");
-        return MPNHIP_ERR_UNSUPPORTED;
-    }
-#undef MPN_CBB
+    (void)chain_bf16_dispatch(chain_bf16_variant(a.he, a.de, a.hn, a.dn, a.hc), chain_bf16_bwd_widths_exact(a.he, a.de, a.hn, a.dn, a.hc), [&](auto v) {
+        using V = decltype(v);
+        MPN_LAUNCH_PROFILED((edge_chain_bf16_bwd_kernel<V::T1, V::T2, V::TF, V::TD, V::TC, V::EXACT, V::NW, V::CT>), dim3(blocks), dim3(64 * V::NW), s, a);
+    });
     MPN_LAUNCH_CHECK();
     return MPNHIP_OK;
 }

@@ -2,6 +2,7 @@
 // backward): 1 KiB weight units streamed L2 -> LDS by LDS-DMA, A operands read back by hand-placed ds_read_b128, the N-tiled
 // "hidden tile" step (first-layer units -> activation -> the finished tile IS the next layer's B operand), training saves.
 #pragma once
+#include "chain_device.h"
 #include "common.h"
 #include "edge_chain.h"
 #include "row_stage.h"
@@ -9,36 +10,8 @@
 
 namespace mpnhip {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 namespace {
 
-constexpr int bmax(int a, int b) { return a > b ? a : b; }
-constexpr int bmin(int a, int b) { return a < b ? a : b; }
-
-__device__ __forceinline__ float4 ldg4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-template <bool EXACT>
-__device__ __forceinline__ float4 ldrow(const float* base, unsigned off, int n, int dim) {
-    if (EXACT) return ldg4(base + (size_t)off + n);
-    const bool ok = n < dim;
-    float4 v = ldg4(base + (size_t)off + (ok ? n : 0));
-    v.x = ok ? v.x : 0.f; v.y = ok ? v.y : 0.f; v.z = ok ? v.z : 0.f; v.w = ok ? v.w : 0.f;
-    return v;
-}
-template <bool EXACT>
-__device__ __forceinline__ void strow(float* base, unsigned off, int n, int dim, float4 v, bool ok) {
-    // (plain stores: a row's 128-byte lines are completed by several wave instructions and L2 merges the pieces; non-temporal
-    // stores / loads here took the kernel from 0.63 to 0.92 ms at cfg-E)
-    if (ok && (EXACT || n < dim)) *reinterpret_cast<float4*>(base + (size_t)off + n) = v;
-}
-__device__ __forceinline__ float4 get4(const f32x16& a, int g) {
-    return make_float4(a[4 * g + 0], a[4 * g + 1], a[4 * g + 2], a[4 * g + 3]);
-}
-__device__ __forceinline__ void relu16(f32x16& a) {
-#pragma unroll
-    for (int r = 0; r < 16; ++r) a[r] = fmaxf(a[r], 0.f);
-}
 __device__ __forceinline__ bf16x8 pack8(float4 u, float4 v) {
     return bf16x8{(__bf16)u.x, (__bf16)u.y, (__bf16)u.z, (__bf16)u.w, (__bf16)v.x, (__bf16)v.y, (__bf16)v.z, (__bf16)v.w};
 }

@@ -251,39 +251,10 @@ static int pack_node_weights(const mpnhip_model& m, const Dims& d, float* Wnode,
 }
 
 static int pack_chain_weights(const mpnhip_model& m, const Dims& d, const ChainWeights& cw, bool split, PackBatch* batch, SplitBatch* split_batch, hipStream_t s) {
-    const int HE = pad32(d.he), DE = pad32(d.de), HN = pad32(d.hn), DN = pad32(d.dn);
-    const int hc = m.classifier.out_dims[0];
-    const mpnhip_mlp* fl[2] = {&m.flow_out, &m.flow_in};
-    if (split) {
-        // the same logical images WT[k][n] = W[n][k0 + k] as below, as split images (3/2 the size, offsets scale alike)
-        MPN_TRY(pack_split(m.edge.weight[0] + 2 * d.kx, 1, m.edge.in_dim, d.ke, d.he, d.ke, HE, cw.w1T, split_batch, s));
-        MPN_TRY(pack_split(m.edge.weight[1], 1, d.he, d.he, d.de, HE, DE, cw.w2T, split_batch, s));
-        MPN_TRY(pack_split(m.classifier.weight[0], 1, d.de, d.de, hc, DE, 32, cw.wc1T, split_batch, s));
-        for (int q = 0; q < 2; ++q) {
-            for (int n0 = 0; n0 < HN; n0 += 64) {
-                const int ncw = HN - n0 < 64 ? HN - n0 : 64;
-                const int rows = d.hn - n0 < 0 ? 0 : (d.hn - n0 < ncw ? d.hn - n0 : ncw);
-                MPN_TRY(pack_split(fl[q]->weight[0] + (int64_t)n0 * fl[q]->in_dim + d.kx, 1, fl[q]->in_dim, d.de, rows, DE, ncw,
-                                   cw.wf1T[q] + (int64_t)DE * n0 * 3 / 2, split_batch, s));
-            }
-            MPN_TRY(pack_split(fl[q]->weight[1], 1, d.hn, d.hn, d.dn, HN, DN, cw.wf2T[q], split_batch, s));
-        }
-        return MPNHIP_OK;
-    }
-    MPN_TRY(transpose_padded(m.edge.weight[0], m.edge.in_dim, 2 * d.kx, d.he, d.ke, cw.w1T, HE, d.ke, batch, s));
-    MPN_TRY(transpose_padded(m.edge.weight[1], d.he, 0, d.de, d.he, cw.w2T, DE, HE, batch, s));
-    MPN_TRY(transpose_padded(m.classifier.weight[0], d.de, 0, hc, d.de, cw.wc1T, 32, DE, batch, s));
-    for (int q = 0; q < 2; ++q) {
-        // flow layer 0, e'-part: one image [DE][<= 64] per block of 64 output features (the kernel streams whole blocks)
-        for (int n0 = 0; n0 < HN; n0 += 64) {
-            const int ncw = HN - n0 < 64 ? HN - n0 : 64;
-            const int rows = d.hn - n0 < 0 ? 0 : (d.hn - n0 < ncw ? d.hn - n0 : ncw);
-            MPN_TRY(transpose_padded(fl[q]->weight[0] + (int64_t)n0 * fl[q]->in_dim, fl[q]->in_dim, d.kx, rows, d.de,
-                                     cw.wf1T[q] + (int64_t)DE * n0, ncw, DE, batch, s));
-        }
-        MPN_TRY(transpose_padded(fl[q]->weight[1], d.hn, 0, d.dn, d.hn, cw.wf2T[q], DN, HN, batch, s));
-    }
-    return MPNHIP_OK;
+    const float* f0[2] = {m.flow_out.weight[0], m.flow_in.weight[0]};
+    const float* f1[2] = {m.flow_out.weight[1], m.flow_in.weight[1]};
+    return pack_edge_chain(m.edge.weight[0], m.edge.in_dim, 2 * d.kx, d.ke, m.edge.weight[1], m.classifier.weight[0], f0, m.flow_out.in_dim, d.kx,
+                           f1, d.he, d.de, d.hn, d.dn, m.classifier.out_dims[0], cw, split, batch, split_batch, s);
 }
 
 // Q0 = e0 W1[:, e0 columns]^T, [E, he]: the re-attached initial edge features' share of the edge MLP's first layer, the same in every
@@ -321,7 +292,7 @@ static EdgeChainArgs chain_fwd_args(const mpnhip_model& m, const Dims& d, const 
         a.Q0 = Q0;
         a.xa = io.eb; a.ldxa = io.ldeb; a.k1a = d.ke - io.kea;
         a.xb = nullptr; a.ldxb = 0; a.k1b = 0;
-        a.w1T = cw.w1T + (size_t)io.kea * pad32(d.he) * (split ? 3 : 2) / 2;
+        a.w1T = cw.w1T + chain_row_off(io.kea, pad32(d.he), split);
     }
     a.wc1T = cw.wc1T; a.bc1 = m.classifier.bias[0]; a.wc2 = m.classifier.weight[1]; a.bc2 = m.classifier.bias[1];
     a.wf1T_out = cw.wf1T[0]; a.wf1T_in = cw.wf1T[1]; a.wf2T_out = cw.wf2T[0]; a.wf2T_in = cw.wf2T[1];

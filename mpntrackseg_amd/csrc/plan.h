@@ -211,33 +211,21 @@ struct StepBufs {
     float* M;                          // [E, dn]   messages (post-ReLU), sorted order
     float* AGG;                        // [N, 2dn]  [flow_in | flow_out]
     int* ARG;                          // [N, 2dn]  argmax (max aggregation, training only)
-    int* MK;                           // ReLU masks of the fused chain kernels as bits (edge_chain.h: chain_mask_ints / chain_bf16_mask_ints)
+    int* MK;                           // ReLU masks of the fused chain kernels as bits (chain_layout.h: chain_mask_ints / chain_bf16_mask_ints)
     // (FwdRoute::b16 -- bf16-operand training on the fused kernels: HE[0] / HC[0] / HF[0] hold bf16 [E, width] rows, not floats)
 };
 
-static inline int pad32(int v) { return (v + 31) / 32 * 32; }
-
-// pre-transposed, zero-padded weight images of the fused edge-chain kernel (edge_chain.hip); P(.) = pad32
-struct ChainWeights {
-    float* w1T;       // [ke][P(he)]
-    float* w2T;       // [P(he)][P(de)]
-    float* wc1T;      // [P(de)][32]
-    float* wf1T[2];   // [P(de)][P(hn)]  (0: flow_out, 1: flow_in)
-    float* wf2T[2];   // [P(hn)][P(dn)]
-    // (FwdRoute::split: three-piece bf16 split images (edge_chain.hip), 3/2 the size, same logical layout)
-};
-
-// (one layout for the forward's plan and for mpnhip_debug_edge_chain_forward)
+// pre-transposed, zero-padded weight images of the fused edge-chain kernel (edge_chain.h: ChainWeights), each sized for either
+// operand form (FwdRoute::split); one layout for the forward's plan and for mpnhip_debug_edge_chain_forward
 static inline void carve_chain_weights(Carver& a, const Dims& d, ChainWeights* cw) {
     const size_t HE = pad32(d.he), DE = pad32(d.de), HN = pad32(d.hn), DN = pad32(d.dn);
-    // (sized for the split images, 3/2 of the fp32 ones: FwdRoute::split)
-    const size_t KE = (size_t)(d.ke + 15) / 16 * 16;
-    cw->w1T = a.take<float>(KE * HE * 3 / 2);
-    cw->w2T = a.take<float>(HE * DE * 3 / 2);
-    cw->wc1T = a.take<float>(DE * 32 * 3 / 2);
+    const size_t KE = (size_t)(d.ke + ChainFwd::KC1 - 1) / ChainFwd::KC1 * ChainFwd::KC1;
+    cw->w1T = a.take<float>(chain_image_capacity(KE * HE));
+    cw->w2T = a.take<float>(chain_image_capacity(HE * DE));
+    cw->wc1T = a.take<float>(chain_image_capacity(DE * CHAIN_HC));
     for (int q = 0; q < 2; ++q) {
-        cw->wf1T[q] = a.take<float>(DE * HN * 3 / 2);
-        cw->wf2T[q] = a.take<float>(HN * DN * 3 / 2);
+        cw->wf1T[q] = a.take<float>(chain_image_capacity(DE * HN));
+        cw->wf2T[q] = a.take<float>(chain_image_capacity(HN * DN));
     }
 }
 

@@ -1,10 +1,8 @@
 // Full-line row stores for the chain kernels (edge_chain.hip, edge_chain_bf16.hip, edge_chain_bf16_bwd.hip): see RowStage.
 #pragma once
-#include <hip/hip_runtime.h>
+#include "chain_device.h"
 
 namespace mpnhip {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 namespace {
 
