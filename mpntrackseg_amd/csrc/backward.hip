@@ -272,7 +272,9 @@ struct BwdCtx {
 // batch: where the product is recorded (all products of a group of steps: one product launch + one slab-sum launch); nullptr: run now,
 // as a batch of its own on slab_base
 static int weight_grad(const BwdCtx& c, float* slab_base, WpBatch* batch, const WgProduct& w, hipStream_t s) {
-    return weight_grad_route({c.wgrad_split, c.bf16, c.p->slab_floats_per_group}, slab_base, batch, w, s);
+    const int rc = weight_grad_route({c.wgrad_split, c.bf16}, wg_two_group_slabs(slab_base, c.p->slab_floats_per_group), batch, w, s);
+    if (rc == MPNHIP_ERR_UNSUPPORTED) set_error("backward (bf16): a product over bf16 rows [%d x %d] is not covered by the row-panel kernel", w.n_out, w.k_in);
+    return rc;
 }
 
 // C = mask( A B (+ C) ) with B given as weight rows: B[k][n] = W[k * ldw + n]  (dH = dZ W)
@@ -1025,7 +1027,7 @@ struct BackwardRun {
     }
 
     // the per-edge modules' products of mp_weight_grads, bf16 chain: every operand of these products is a bf16 row block -- the backward
-    // chain kernel's dZ outputs, the forward chain kernel's saved activations and the bf16 mirror of e_hist (WpProduct::src16: loaded
+    // chain kernel's dZ outputs, the forward chain kernel's saved activations and the bf16 mirror of e_hist (WgProduct::src16: loaded
     // as they are, one product per k block)
     int edge_weight_grads_bf16(int64_t zb, int nb, hipStream_t st, float* slab, WpBatch* batch) {
         const mpnhip_mlp& cls = m.classifier;

@@ -123,8 +123,8 @@ static inline size_t slab_per_group(const mpnhip_model& m, const Dims& d, int64_
     upd(mlp_slab(m.classifier, d.de, E, L));
     upd(tn_slab_floats(d.dn, 2 * d.dn, N, L));
     upd(tn_slab_floats(d.pw, d.kx, N, L));
-    // the same products in the row-panel form (MPNHIP_PREC_FP32_SPLIT); a group's share of the slab is half of it
-    auto updw = [&](int n_out, int k_in, int64_t rows, bool rows16) { if (rows > 0) upd((wp_slab_floats(n_out, k_in, rows, 1, false, false, rows16) + 1) / 2); };
+    // the same products in the row-panel form (MPNHIP_PREC_FP32_SPLIT), each a batch of its own over both groups' shares (common.h)
+    auto updw = [&](int n_out, int k_in, int64_t rows, bool rows16) { if (rows > 0) upd(wg_group_share(wp_slab_floats(n_out, k_in, rows, 1, false, false, rows16))); };
     for (int i = 0; i < m.enc_node.n_layers; ++i) updw(m.enc_node.out_dims[i], layer_in(m.enc_node, i), N, false);
     for (int i = 0; i < m.enc_edge.n_layers; ++i) updw(m.enc_edge.out_dims[i], layer_in(m.enc_edge, i), E, false);
     updw(d.he, d.de, E, false);

@@ -186,28 +186,19 @@ struct WpJob {             // one product (one direction group of it), as the ke
 };
 constexpr int WP_MAX_JOBS = 16;
 struct WpTable { WpJob job[WP_MAX_JOBS]; int njobs; int debug; };   // debug: MPNHIP_WP_DEBUG, read only by a -DMPNHIP_WP_ABLATE build (results wrong)
-struct WpProduct {         // host-side description of one product
-    const float* dZ; int64_t ldz, z_bstride;
-    const float* H; int64_t ldh, h_bstride;
-    const int* row_begin; const int* row_end;   // device-side row range (a direction group) or nullptr
-    int64_t rows;          // rows of one batch (upper bound when ranged)
-    int nbatch, n_out, k_in;
-    float* grad_w; int64_t ldw; float* grad_b;
-    const int* dz_idx;     // optional row gathers (narrow products and the [1 x k] form only)
-    const int* h_idx;
-    const float* H2; int64_t ldh2, h2_bstride; int csplit;   // second column segment of H (nullptr: none)
-    int pieces;            // 3 (fp32 from three bf16 pieces) or 1 (bf16-rounded operands); 0 = 3
-    int src16;             // bf16 source rows (WpJob::src16); needs pieces == 1
-};
 // (nblocks2 / bytes2: the jobs of wgrad_rows16.hip's kernel -- variant >= 16, their block0 counts inside that launch)
 struct WpBatch { WpTable tab; float* slab; size_t slab_floats, used; double flops, bytes, bytes2; int nblocks, nblocks2, nred; bool batched;
                  hipStream_t stream; bool has_stream;      // has_stream: every flush of this batch goes to `stream` (wp_batch_roll)
                  WgChosen* chosen[WP_MAX_JOBS]; };         // per job, or null: filled by the flush (the tiling is final only there)
-bool wp_eligible(const WpProduct& p);
 // wgrad_rows16.hip: the one-pass LDS-DMA kernel for bf16 rows at the 256-d widths
 int r16_variant(int n_out, int k_in, int* tiles_o, int* tiles_c);
 int launch_wgrad_rows16(const WpTable& tab, int nblocks, hipStream_t s);
-// (batched: the job shares its launch with the other products of a group of steps -- fewer row chunks per job)
+// The plan of one job (one direction group of a product): block variant, output tiles, row chunks, the slab floats it takes in its batch.
+// ranged: a device-side row range (the group is expected to hold half of `rows`); batched: the job shares its launch with the other
+// products of a group of steps -- fewer row chunks per job; rows16: bf16 rows that meet the LDS-DMA kernel's alignment.  Over bf16 rows
+// slab_floats is the larger of the two kernels' needs: which takes the product depends on the operands' alignment, unknown to a size query.
+struct WpJobPlan { int variant, tiles_o, tiles_c, chunk, nsplit; size_t slab_floats; };
+WpJobPlan wp_job_plan(int n_out, int k_in, int64_t rows, int nbatch, bool ranged, bool batched, bool src16, bool rows16);
 size_t wp_slab_floats(int n_out, int k_in, int64_t rows, int nbatch, bool ranged, bool batched, bool src16 = false);
 // A WpBatch is an object its caller holds (on its stack) and passes to whatever records into it; nothing else refers to it.
 // init: empty, over `slab`.  stream (or nullptr): the one stream every flush of this batch will go to, which allows wp_batch_roll
@@ -215,12 +206,9 @@ void wp_batch_init(WpBatch* b, float* slab, size_t slab_floats, bool batched, co
 // b is full (job table or slab space) for these eligible products: run what it holds on its stream and empty it -- launches on
 // one stream are serial, so the slab region is reused; false: not possible (no stream given at init / nothing recorded)
 bool wp_batch_roll(WpBatch* b, int* status);
-// true: recorded -- all n (the direction groups of one product) or none: every product eligible, table and slab space suffice
-// chosen (optional): n entries, written when the batch is flushed -- they must live until then
-bool wp_batch_add(WpBatch* b, const WpProduct* ps, int n, WgChosen* chosen = nullptr);
 int wp_batch_flush(WpBatch* b, hipStream_t stream);   // product launch + slab-sum launch of what was recorded
 
-// ---- one weight-gradient product as the backward describes it, and the routing every such product goes through (gemm_tn.hip) ----
+// ---- one weight-gradient product as its caller describes it, and the routing every such product goes through (wgrad.hip) ----
 struct RowRange {
     const int* begin;
     const int* end;
@@ -231,26 +219,42 @@ struct Operand {        // one side of a (batched) weight-gradient product
     int64_t bstride;    // floats between consecutive batches (0: same block every batch)
 };
 // dW += dZ^T [H | H2] (+ bias)  for one or two direction groups, over nbatch row blocks: the shared part, then grad_w / grad_b / the
-// device-side row range of each group (g[1].grad_w == nullptr: one group)
+// device-side row range of each group (g[1].grad_w == nullptr: one group).  The ONE host-side description: the backward, the public
+// mpnhip_weight_grad* entries and the test entry fill it, the fp32 kernels' TnArgs and the row-panel WpJobs are filled from it.
 struct WgGroup { float* grad_w; float* grad_b; RowRange rr; };
 struct WgProduct {
     Operand dZ;
-    const int* dz_idx;  // optional row gather
+    const int* dz_idx;  // optional row gather (row-panel kernels: narrow products and the [1 x k] form only)
     Operand H, H2;      // H2: the columns >= csplit of the layer input (H2.p == nullptr: none, csplit unused)
     int csplit;
     const int* h_idx;   // optional row gather
     int n_out, k_in;
-    int64_t ldw, rows;
+    int64_t ldw, rows;  // rows of one batch (upper bound with device-side row ranges)
     int nbatch;
-    bool src16;         // the operands are bf16 rows (WpProduct::src16): the dZ blocks / saved activations of the fused bf16 chain
+    bool src16;         // the operands are bf16 rows (WpJob::src16): the dZ blocks / saved activations of the fused bf16 chain
     WgGroup g[2];
 };
-// what the routing needs to know of its caller: wgrad_split -- the row-panel kernels (three-piece operands, or one piece with bf16);
-// slab_floats_per_group: a group's share of slab_base (which holds two), for a product that runs on its own
-struct WgRouting { bool wgrad_split, bf16; size_t slab_floats_per_group; };
+static inline int wg_ngroups(const WgProduct& w) { return w.g[1].grad_w ? 2 : 1; }
+// the row-panel kernels (wgrad_panel.hip) take this product; pieces: 3 (fp32 from three bf16 pieces) or 1 (bf16-rounded operands)
+bool wp_eligible(const WgProduct& w, int pieces);
+// true: recorded -- every direction group of the product as a job of its own, or none: eligible, table and slab space suffice
+// chosen (optional): one entry per group, written when the batch is flushed -- they must live until then
+bool wp_batch_add(WpBatch* b, const WgProduct& w, int pieces, WgChosen* chosen = nullptr);
+
+// The slab region a routed product may use: the fp32 kernels put group q's slab at base + q * group_stride; a product that runs
+// on the row-panel kernels as a batch of its own has own_floats from base.
+struct WgSlabs { float* base; size_t own_floats, group_stride; };
+// A region of two groups' fp32 slabs, `per_group` floats each (BwdPlan::slab / slab_side): a batch of its own has BOTH groups' shares
+// -- so a row-panel product that needs `own_floats` alone asks for half of that per group.
+static inline WgSlabs wg_two_group_slabs(float* base, size_t per_group) { return {base, 2 * per_group, per_group}; }
+static inline size_t wg_group_share(size_t own_floats) { return (own_floats + 1) / 2; }
+// what the routing needs to know of its caller: wgrad_split -- the row-panel kernels (three-piece operands, or one piece with bf16)
+struct WgRouting { bool wgrad_split, bf16; };
 // batch: where the product is recorded (all products of a group of steps: one product launch + one slab-sum launch); nullptr: run now,
-// as a batch of its own on slab_base.  chosen (optional): two entries; those of a recorded product are written when its batch is flushed
-int weight_grad_route(const WgRouting& r, float* slab_base, WpBatch* batch, const WgProduct& w, hipStream_t s, WgChosen* chosen = nullptr);
+// as a batch of its own.  chosen (optional): two entries; those of a recorded product are written when its batch is flushed.
+// A split / bf16 product that is no row-panel shape is counted (wgrad_panel_fallback) and runs on the fp32 kernels; over bf16 rows
+// there is none: MPNHIP_ERR_UNSUPPORTED with nothing launched and no error text -- the caller words its own.
+int weight_grad_route(const WgRouting& r, const WgSlabs& slabs, WpBatch* batch, const WgProduct& w, hipStream_t s, WgChosen* chosen = nullptr);
 
 // few rows, long K (node encoder at the reference's graph sizes): split-K into `scratch`, then a fixed-order sum (gemm.hip)
 // `next` (optional): the Linear layer that follows ([next->n x n] weights, output next->y): evaluated in the summing launch when it is

@@ -10,8 +10,8 @@
 // straight into k-major LDS images (the row index IS the MFMA k index, so nothing is transposed).
 // H may come as two column segments (the reference's torch.cat([initial, current]) input), rows of
 // either operand may be gathered through an index (edge_attr / dlogits live in original edge order).
+// This file: the fp32 kernels, their chunk plan (tn_plan) and launch_gemm_tn.  Which products come here is decided in wgrad.hip.
 #include <cstdlib>
-#include <cstring>
 
 #include "common.h"
 
@@ -577,278 +577,4 @@ int launch_gemm_tn(const TnArgs& a_in, hipStream_t s, WgChosen* chosen) {
     return MPNHIP_OK;
 }
 
-int weight_grad_route(const WgRouting& c, float* slab_base, WpBatch* batch, const WgProduct& w, hipStream_t s, WgChosen* chosen) {
-    const int ngroups = w.g[1].grad_w ? 2 : 1;
-    if (chosen)
-        for (int q = 0; q < 2; ++q) chosen[q] = {WG_PATH_NONE, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    if (c.wgrad_split && w.rows > 0) {
-        // MPNHIP_PREC_FP32_SPLIT: the row-panel kernel (wgrad_panel.hip)
-        WpProduct wp[2];
-        for (int q = 0; q < ngroups; ++q)
-            wp[q] = {w.dZ.p, w.dZ.ld, w.dZ.bstride, w.H.p, w.H.ld, w.H.bstride, w.g[q].rr.begin, w.g[q].rr.end, w.rows, w.nbatch,
-                     w.n_out, w.k_in, w.g[q].grad_w, w.ldw, w.g[q].grad_b, w.dz_idx, w.h_idx, w.H2.p, w.H2.ld, w.H2.bstride, w.csplit,
-                     c.bf16 ? 1 : 3, w.src16 ? 1 : 0};
-        if (batch) {
-            if (wp_batch_add(batch, wp, ngroups, chosen)) return MPNHIP_OK;
-            bool eligible = true;
-            for (int q = 0; q < ngroups; ++q) eligible = eligible && wp_eligible(wp[q]);
-            if (eligible) {
-                // the batch is full (more than WP_MAX_JOBS jobs in a group of steps: deeper MLPs; or its slab region): run it
-                // and go on in a fresh one rather than switch kernels in the middle of a group
-                int st = MPNHIP_OK;
-                if (wp_batch_roll(batch, &st) && wp_batch_add(batch, wp, ngroups, chosen)) {
-                    if (chosen)
-                        for (int q = 0; q < ngroups; ++q) chosen[q].rolled = 1;
-                    return MPNHIP_OK;
-                }
-                MPN_TRY(st);
-            }
-        } else {
-            WpBatch own;
-            wp_batch_init(&own, slab_base, 2 * c.slab_floats_per_group, false, nullptr);
-            if (wp_batch_add(&own, wp, ngroups, chosen)) return wp_batch_flush(&own, s);
-        }
-        // not a shape / alignment of the row-panel kernel (or the batch cannot be rolled): the fp32 kernel below, counted
-        count_path(PC_TN_PANEL_FALLBACK);
-        if (w.src16) { set_error("backward (bf16): a product over bf16 rows [%d x %d] is not covered by the row-panel kernel", w.n_out, w.k_in); return MPNHIP_ERR_UNSUPPORTED; }
-    }
-    const bool ranged = w.g[0].rr.begin || w.g[0].rr.end;
-    TnArgs a = {};
-    a.ngroups = ngroups;
-    a.n_out = w.n_out;
-    a.k_in = w.k_in;
-    a.csplit = w.H2.p ? w.csplit : w.k_in;
-    a.m_upper = w.rows;
-    a.nbatch = w.nbatch;
-    // (with device-side row ranges the groups partition the `rows` rows between them; without, each group covers all of them)
-    a.flops = 2.0 * (double)w.rows * (ranged ? 1 : ngroups) * w.nbatch * w.n_out * w.k_in;
-    for (int q = 0; q < ngroups; ++q) {
-        TnGroup& g = a.g[q];
-        g.dZ = w.dZ.p;
-        g.ldz = w.dZ.ld;
-        g.z_bstride = w.dZ.bstride;
-        g.dz_idx = w.dz_idx;
-        g.H = w.H.p;
-        g.ldh = w.H.ld;
-        g.h_bstride = w.H.bstride;
-        g.H2 = w.H2.p;
-        g.ldh2 = w.H2.ld;
-        g.h2_bstride = w.H2.bstride;
-        g.h_idx = w.h_idx;
-        g.row_begin = w.g[q].rr.begin;
-        g.row_end = w.g[q].rr.end;
-        g.m_static = w.rows;
-        g.slab = slab_base + q * c.slab_floats_per_group;
-        g.grad_w = w.g[q].grad_w;
-        g.ldw = w.ldw;
-        g.grad_b = w.g[q].grad_b;
-    }
-    return launch_gemm_tn(a, s, chosen);
-}
-
 }  // namespace mpnhip
-
-using namespace mpnhip;
-
-// One slab -- the larger of the split-row and the row-panel form's (MPNHIP_PREC_FP32_SPLIT / _BF16); rows16: the row-panel form over
-// bf16 rows only -- behind a base the operator rounds up to 256 itself (callers may pass unaligned buffers): 256 bytes to spare.
-static size_t weight_grad_layout(int n_out, int k_in, int64_t rows, int nbatch, bool rows16, void* workspace, float** slab) {
-    const int nb = nbatch < 1 ? 1 : nbatch;
-    const size_t tn = rows16 ? 0 : tn_slab_floats(n_out, k_in, rows, nb), wp = rows > 0 ? wp_slab_floats(n_out, k_in, rows, nb, false, false, rows16) : 0;
-    const uintptr_t w = reinterpret_cast<uintptr_t>(workspace);
-    Carver c(workspace ? static_cast<char*>(workspace) + (align_up(w, 256) - w) : nullptr);
-    *slab = c.take<float>(tn > wp ? tn : wp);
-    return c.bytes() + 256;
-}
-
-extern "C" size_t mpnhip_weight_grad_workspace_bytes(int n_out, int k_in, int64_t rows, int nbatch) {
-    float* slab;
-    return n_out < 1 || k_in < 1 || rows < 0 ? 0 : weight_grad_layout(n_out, k_in, rows, nbatch, false, nullptr, &slab);
-}
-
-static int weight_grad_args(const float* dZ, const float* H, int64_t rows, int n_out, int k_in, int nbatch, float* grad_w, float* grad_b,
-                            void* workspace, size_t workspace_bytes, TnArgs* out) {
-    MPN_CHECK_ARG(n_out >= 1 && k_in >= 1 && rows >= 0 && nbatch >= 1, "weight_grad: bad sizes");
-    MPN_CHECK_ARG((dZ && H && grad_w) || rows == 0, "weight_grad: null pointer");
-    TnArgs a = {};
-    const size_t need = weight_grad_layout(n_out, k_in, rows, nbatch, false, workspace, &a.g[0].slab);
-    if (rows > 0) MPN_CHECK_WORKSPACE("weight_grad", workspace, workspace_bytes, need);
-    a.ngroups = 1; a.n_out = n_out; a.k_in = k_in; a.csplit = k_in; a.m_upper = rows; a.nbatch = nbatch;
-    TnGroup& g = a.g[0];
-    g.dZ = dZ; g.ldz = n_out; g.z_bstride = rows * n_out;
-    g.H = H; g.ldh = k_in; g.h_bstride = rows * k_in;
-    g.m_static = rows;
-    g.grad_w = grad_w; g.ldw = k_in; g.grad_b = grad_b;
-    a.flops = 2.0 * (double)rows * nbatch * n_out * k_in;
-    *out = a;
-    return MPNHIP_OK;
-}
-
-// precision MPNHIP_PREC_FP32_SPLIT: the row-panel kernel with three-piece bf16 operands (wgrad_panel.hip) where the shape allows it
-static int weight_grad_run(const TnArgs& a, int precision, void* workspace, size_t workspace_bytes, hipStream_t s) {
-    if (precision == MPNHIP_PREC_FP32_SPLIT || precision == MPNHIP_PREC_BF16) {
-        const TnGroup& g = a.g[0];
-        WpProduct p = {g.dZ, g.ldz, g.z_bstride, g.H, g.ldh, g.h_bstride, nullptr, nullptr, a.m_upper, a.nbatch, a.n_out, a.k_in,
-                       g.grad_w, g.ldw, g.grad_b, nullptr, nullptr, nullptr, 0, 0, 0, precision == MPNHIP_PREC_BF16 ? 1 : 3};
-        WpBatch b;
-        wp_batch_init(&b, g.slab, (workspace_bytes - 256) / sizeof(float), false, nullptr);
-        if (wp_batch_add(&b, &p, 1)) return wp_batch_flush(&b, s);
-    }
-    return launch_gemm_tn(a, s);
-}
-
-extern "C" int mpnhip_weight_grad_prec(const float* dZ, const float* H, int64_t rows, int n_out, int k_in, int nbatch, int precision,
-                                       float* grad_w, float* grad_b, void* workspace, size_t workspace_bytes, void* stream) {
-    MPN_CHECK_ARG(precision == MPNHIP_PREC_FP32 || precision == MPNHIP_PREC_FP32_SPLIT || precision == MPNHIP_PREC_BF16, "weight_grad: precision %d", precision);
-    TnArgs a;
-    MPN_TRY(weight_grad_args(dZ, H, rows, n_out, k_in, nbatch, grad_w, grad_b, workspace, workspace_bytes, &a));
-    if (rows == 0) return MPNHIP_OK;
-    return weight_grad_run(a, precision, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
-}
-
-extern "C" int mpnhip_weight_grad_bf16_rows(const uint16_t* dZ, const uint16_t* H, int64_t rows, int n_out, int k_in, int nbatch,
-                                            float* grad_w, float* grad_b, void* workspace, size_t workspace_bytes, void* stream) {
-    MPN_CHECK_ARG(n_out >= 1 && k_in >= 1 && rows >= 0 && nbatch >= 1, "weight_grad_bf16_rows: bad sizes");
-    if (rows == 0) return MPNHIP_OK;
-    MPN_CHECK_ARG(dZ && H && grad_w, "weight_grad_bf16_rows: null pointer");
-    float* slab;
-    const size_t need = weight_grad_layout(n_out, k_in, rows, nbatch, true, workspace, &slab);
-    MPN_CHECK_WORKSPACE("weight_grad_bf16_rows", workspace, workspace_bytes, need);
-    WpProduct p = {reinterpret_cast<const float*>(dZ), n_out, rows * n_out, reinterpret_cast<const float*>(H), k_in, rows * k_in, nullptr, nullptr,
-                   rows, nbatch, n_out, k_in, grad_w, k_in, grad_b, nullptr, nullptr, nullptr, 0, 0, 0, 1, 1};
-    WpBatch b;
-    wp_batch_init(&b, slab, (workspace_bytes - 256) / sizeof(float), false, nullptr);
-    if (wp_batch_add(&b, &p, 1)) return wp_batch_flush(&b, static_cast<hipStream_t>(stream));
-    set_error("weight_grad_bf16_rows: [%d x %d] over bf16 rows is not a shape of the row-panel kernel (multiples of 4, 8-byte aligned rows)", n_out, k_in);
-    return MPNHIP_ERR_UNSUPPORTED;
-}
-
-extern "C" size_t mpnhip_weight_grad_bf16_rows_workspace_bytes(int n_out, int k_in, int64_t rows, int nbatch) {
-    float* slab;
-    return n_out < 1 || k_in < 1 || rows < 0 ? 0 : weight_grad_layout(n_out, k_in, rows, nbatch, true, nullptr, &slab);
-}
-
-extern "C" int mpnhip_weight_grad(const float* dZ, const float* H, int64_t rows, int n_out, int k_in, int nbatch, float* grad_w,
-                                  float* grad_b, void* workspace, size_t workspace_bytes, void* stream) {
-    return mpnhip_weight_grad_prec(dZ, H, rows, n_out, k_in, nbatch, MPNHIP_PREC_FP32, grad_w, grad_b, workspace, workspace_bytes, stream);
-}
-
-extern "C" int mpnhip_time_weight_grad_prec(const float* dZ, const float* H, int64_t rows, int n_out, int k_in, int nbatch, int precision,
-                                            float* grad_w, float* grad_b, void* workspace, size_t workspace_bytes, int iters, float* avg_us,
-                                            void* stream_) {
-    hipStream_t s = static_cast<hipStream_t>(stream_);
-    MPN_CHECK_ARG(avg_us && iters > 0 && rows > 0, "time_weight_grad: bad argument");
-    MPN_CHECK_ARG(precision == MPNHIP_PREC_FP32 || precision == MPNHIP_PREC_FP32_SPLIT || precision == MPNHIP_PREC_BF16, "time_weight_grad: precision %d", precision);
-    TnArgs a;
-    MPN_TRY(weight_grad_args(dZ, H, rows, n_out, k_in, nbatch, grad_w, grad_b, workspace, workspace_bytes, &a));
-    hipEvent_t t0, t1;
-    MPN_HIP(hipEventCreate(&t0));
-    MPN_HIP(hipEventCreate(&t1));
-    MPN_TRY(weight_grad_run(a, precision, workspace, workspace_bytes, s));
-    MPN_HIP(hipEventRecord(t0, s));
-    for (int i = 0; i < iters; ++i) MPN_TRY(weight_grad_run(a, precision, workspace, workspace_bytes, s));
-    MPN_HIP(hipEventRecord(t1, s));
-    MPN_HIP(hipEventSynchronize(t1));
-    float ms = 0.f;
-    MPN_HIP(hipEventElapsedTime(&ms, t0, t1));
-    *avg_us = ms * 1000.f / iters;
-    (void)hipEventDestroy(t0);
-    (void)hipEventDestroy(t1);
-    return MPNHIP_OK;
-}
-
-extern "C" int mpnhip_time_weight_grad(const float* dZ, const float* H, int64_t rows, int n_out, int k_in, int nbatch, float* grad_w,
-                                       float* grad_b, void* workspace, size_t workspace_bytes, int iters, float* avg_us, void* stream_) {
-    return mpnhip_time_weight_grad_prec(dZ, H, rows, n_out, k_in, nbatch, MPNHIP_PREC_FP32, grad_w, grad_b, workspace, workspace_bytes, iters,
-                                        avg_us, stream_);
-}
-
-// ---- test instrumentation: the backward's weight-gradient routing (weight_grad_route) behind the C ABI ---------------------------
-// Workspace: [ two groups' slabs for a product that runs on its own (and the fp32 kernels) | the slab region of the batch ]
-namespace {
-struct WgDebugLayout { float* own; size_t per_group; float* batch; size_t batch_floats; };
-bool wg_ranged(const mpnhip_wgrad_product& p) { return p.g[0].row_begin || p.g[0].row_end; }
-size_t wg_debug_layout(const mpnhip_wgrad_product* ps, int n, int precision, int batched, int64_t batch_slab_floats, void* workspace,
-                       WgDebugLayout* out) {
-    size_t per_group = 0, sum = 0;
-    for (int i = 0; i < n; ++i) {
-        const mpnhip_wgrad_product& p = ps[i];
-        if (p.rows <= 0 || p.n_out < 1 || p.k_in < 1 || p.nbatch < 1) continue;
-        const size_t tn = p.src16 ? 0 : tn_slab_floats(p.n_out, p.k_in, p.rows, p.nbatch);
-        const size_t own = wp_slab_floats(p.n_out, p.k_in, p.rows, p.nbatch, wg_ranged(p), false, p.src16 != 0);
-        per_group = std::max(per_group, std::max(tn, own));
-        sum += (p.g[1].grad_w ? 2 : 1) * wp_slab_floats(p.n_out, p.k_in, p.rows, p.nbatch, wg_ranged(p), batched != 0, p.src16 != 0);
-    }
-    per_group = (per_group + 63) / 64 * 64;
-    const uintptr_t w = reinterpret_cast<uintptr_t>(workspace);
-    Carver c(workspace ? static_cast<char*>(workspace) + (align_up(w, 256) - w) : nullptr);
-    out->per_group = per_group;
-    out->own = c.take<float>(2 * per_group);
-    out->batch_floats = precision == MPNHIP_PREC_FP32 ? 0 : (batch_slab_floats > 0 ? (size_t)batch_slab_floats : sum);
-    out->batch = c.take<float>(out->batch_floats);
-    return c.bytes() + 256;
-}
-int wg_debug_check(const mpnhip_wgrad_product* ps, int n, int precision) {
-    MPN_CHECK_ARG(ps, "debug_weight_grad_batch: null products");
-    MPN_CHECK_ARG(n >= 1 && n <= WP_MAX_JOBS, "debug_weight_grad_batch: %d products (1 .. %d)", n, WP_MAX_JOBS);
-    MPN_CHECK_ARG(precision == MPNHIP_PREC_FP32 || precision == MPNHIP_PREC_FP32_SPLIT || precision == MPNHIP_PREC_BF16,
-                  "debug_weight_grad_batch: unknown precision %d", precision);
-    for (int i = 0; i < n; ++i) {
-        const mpnhip_wgrad_product& p = ps[i];
-        MPN_CHECK_ARG(p.n_out >= 1 && p.k_in >= 1 && p.rows >= 0 && p.nbatch >= 1 && p.ldw >= p.k_in, "debug_weight_grad_batch: product %d: bad sizes", i);
-        MPN_CHECK_ARG(p.rows == 0 || (p.dZ && p.H && p.g[0].grad_w), "debug_weight_grad_batch: product %d: null dZ / H / grad_w", i);
-        MPN_CHECK_ARG(!p.src16 || precision == MPNHIP_PREC_BF16, "debug_weight_grad_batch: product %d: src16 needs the bf16 precision", i);
-        MPN_CHECK_ARG(!p.H2 || (p.csplit > 0 && p.csplit < p.k_in), "debug_weight_grad_batch: product %d: csplit %d outside (0, %d)", i, p.csplit,
-                      p.k_in);
-    }
-    return MPNHIP_OK;
-}
-}  // namespace
-
-extern "C" size_t mpnhip_debug_weight_grad_batch_workspace_bytes(const mpnhip_wgrad_product* products, int n_products, int precision,
-                                                                 int batched, int64_t batch_slab_floats) {
-    if (wg_debug_check(products, n_products, precision) != MPNHIP_OK) return 0;
-    WgDebugLayout L;
-    return wg_debug_layout(products, n_products, precision, batched, batch_slab_floats, nullptr, &L);
-}
-
-extern "C" int mpnhip_debug_weight_grad_batch(const mpnhip_wgrad_product* products, int n_products, int precision, int batched, int one_launch,
-                                              int64_t batch_slab_floats, void* workspace, size_t workspace_bytes, int32_t* chosen,
-                                              void* stream_) {
-    MPN_TRY(wg_debug_check(products, n_products, precision));
-    WgDebugLayout L;
-    const size_t need = wg_debug_layout(products, n_products, precision, batched, batch_slab_floats, workspace, &L);
-    MPN_CHECK_WORKSPACE("debug_weight_grad_batch", workspace, workspace_bytes, need);
-    hipStream_t s = static_cast<hipStream_t>(stream_);
-    const WgRouting r = {precision != MPNHIP_PREC_FP32, precision == MPNHIP_PREC_BF16, L.per_group};
-    static_assert(sizeof(WgChosen) == 10 * sizeof(int32_t), "the chosen report is ten ints per group");
-    WgChosen ch[WP_MAX_JOBS][2];
-    for (int i = 0; i < n_products; ++i)
-        for (int q = 0; q < 2; ++q) ch[i][q] = {WG_PATH_NONE, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    // one_launch: one batch for all products; else batched: a batch per product (a job with the batched chunk plan, alone in its
-    // launch); else: no batch -- the routing runs the product now, on a batch of its own
-    WpBatch wpb;
-    const bool use_batch = r.wgrad_split && (one_launch || batched);
-    if (use_batch) wp_batch_init(&wpb, L.batch, L.batch_floats, batched != 0, &s);
-    int rc = MPNHIP_OK;
-    for (int i = 0; i < n_products && rc == MPNHIP_OK; ++i) {
-        const mpnhip_wgrad_product& p = products[i];
-        WgProduct w = {};
-        w.dZ = {static_cast<const float*>(p.dZ), p.ldz, p.z_bstride};
-        w.dz_idx = p.dz_idx;
-        w.H = {static_cast<const float*>(p.H), p.ldh, p.h_bstride};
-        w.H2 = {static_cast<const float*>(p.H2), p.ldh2, p.h2_bstride};
-        w.csplit = p.csplit;
-        w.h_idx = p.h_idx;
-        w.n_out = p.n_out; w.k_in = p.k_in; w.ldw = p.ldw; w.rows = p.rows; w.nbatch = p.nbatch; w.src16 = p.src16 != 0;
-        for (int q = 0; q < 2; ++q) w.g[q] = {p.g[q].grad_w, p.g[q].grad_b, {p.g[q].row_begin, p.g[q].row_end}};
-        rc = weight_grad_route(r, L.own, use_batch ? &wpb : nullptr, w, s, ch[i]);
-        if (rc == MPNHIP_OK && use_batch && !one_launch) {
-            rc = wp_batch_flush(&wpb, s);
-            wp_batch_init(&wpb, L.batch, L.batch_floats, batched != 0, &s);
-        }
-    }
-    if (rc == MPNHIP_OK && use_batch && one_launch) rc = wp_batch_flush(&wpb, s);
-    if (chosen) memcpy(chosen, ch, sizeof(WgChosen) * 2 * (size_t)n_products);
-    return rc;
-}

@@ -16,6 +16,7 @@
 //     are summed by ONE launch (fixed order: deterministic, no float atomics).  Chunks with an odd index carry NEGATED dZ and
 //     are subtracted: the bf16 MFMA's accumulate is biased toward -inf, and the alternation cancels the
 //     bias across neighbouring chunks instead of adding it up over all rows.
+#include <algorithm>
 #include <cstdlib>
 #include <type_traits>
 #include <utility>
@@ -816,54 +817,59 @@ size_t wp_lds_bytes() {
 
 }  // namespace
 
-bool wp_eligible(const WpProduct& p) {
+bool wp_eligible(const WgProduct& w, int pieces) {
     auto al16 = [](const void* q) { return (((uintptr_t)q) & 15) == 0; };
-    if (p.rows <= 0 || p.rows >= (int64_t)1 << 31 || p.nbatch < 1 || !p.dZ || !p.H || p.n_out < 1 || p.k_in < 1) return false;
-    if (p.src16) {
+    const Operand &dZ = w.dZ, &H = w.H, &H2 = w.H2;
+    if (w.rows <= 0 || w.rows >= (int64_t)1 << 31 || w.nbatch < 1 || !dZ.p || !H.p || w.n_out < 1 || w.k_in < 1) return false;
+    if (w.src16) {
         // bf16 source rows: H (and, except for the [1 x k] form whose dZ is the fp32 logit gradient, dZ) are unsigned shorts
         auto al8 = [](const void* q) { return (((uintptr_t)q) & 7) == 0; };
-        if (p.pieces != 1 || p.H2 || p.h_idx) return false;
-        if (p.n_out == 1 && p.k_in % 4 == 0 && p.k_in <= 64) return al8(p.H) && p.ldh % 4 == 0 && p.h_bstride % 4 == 0;
-        if (p.dz_idx) return false;
-        if (wp_is_small(p.n_out, p.k_in)) return p.n_out * (p.k_in + 1) <= 5 * WP_NT;
-        return p.n_out % 4 == 0 && p.k_in % 4 == 0 && al8(p.dZ) && al8(p.H) && p.ldz % 4 == 0 && p.ldh % 4 == 0 && p.z_bstride % 4 == 0 &&
-               p.h_bstride % 4 == 0;
+        if (pieces != 1 || H2.p || w.h_idx) return false;
+        if (w.n_out == 1 && w.k_in % 4 == 0 && w.k_in <= 64) return al8(H.p) && H.ld % 4 == 0 && H.bstride % 4 == 0;
+        if (w.dz_idx) return false;
+        if (wp_is_small(w.n_out, w.k_in)) return w.n_out * (w.k_in + 1) <= 5 * WP_NT;
+        return w.n_out % 4 == 0 && w.k_in % 4 == 0 && al8(dZ.p) && al8(H.p) && dZ.ld % 4 == 0 && H.ld % 4 == 0 && dZ.bstride % 4 == 0 &&
+               H.bstride % 4 == 0;
     }
-    if (p.n_out == 1 && p.k_in % 4 == 0 && p.k_in <= 64 && !p.h_idx && !p.H2 && al16(p.H) && p.ldh % 4 == 0 && p.h_bstride % 4 == 0)
+    if (w.n_out == 1 && w.k_in % 4 == 0 && w.k_in <= 64 && !w.h_idx && !H2.p && al16(H.p) && H.ld % 4 == 0 && H.bstride % 4 == 0)
         return true;   // wp_block_vec: gathered dZ allowed
-    if (wp_is_small(p.n_out, p.k_in))   // wp_block_small: any alignment, gathers allowed
-        return !p.H2 && p.n_out * (p.k_in + 1) <= 5 * WP_NT;
-    return !p.dz_idx && !p.h_idx && p.n_out % 4 == 0 && p.k_in % 4 == 0 &&
-           al16(p.dZ) && al16(p.H) && p.ldz % 4 == 0 && p.ldh % 4 == 0 && p.z_bstride % 4 == 0 && p.h_bstride % 4 == 0 &&
-           (!p.H2 || (al16(p.H2) && p.ldh2 % 4 == 0 && p.h2_bstride % 4 == 0 && p.csplit % 4 == 0 && p.csplit > 0 && p.csplit < p.k_in));
+    if (wp_is_small(w.n_out, w.k_in))   // wp_block_small: any alignment, gathers allowed
+        return !H2.p && w.n_out * (w.k_in + 1) <= 5 * WP_NT;
+    return !w.dz_idx && !w.h_idx && w.n_out % 4 == 0 && w.k_in % 4 == 0 &&
+           al16(dZ.p) && al16(H.p) && dZ.ld % 4 == 0 && H.ld % 4 == 0 && dZ.bstride % 4 == 0 && H.bstride % 4 == 0 &&
+           (!H2.p || (al16(H2.p) && H2.ld % 4 == 0 && H2.bstride % 4 == 0 && w.csplit % 4 == 0 && w.csplit > 0 && w.csplit < w.k_in));
 }
 
+// The rows a group with a device-side row range is expected to hold, in two roundings that stay apart: whole rows for the chunk
+// plan, the exact half for the flops / bytes figures and the block weights.
+static int64_t wp_rows_expected(int64_t rows, bool ranged) { return ranged ? (rows + 1) / 2 : rows; }
+static double wp_rows_work(int64_t rows, bool ranged) { return ranged ? rows / 2.0 : (double)rows; }
+static bool wp_ranged(const WpJob& J) { return J.row_begin || J.row_end; }
+static int wp_job_blocks(const WpJob& J) { return J.tiles_o * J.tiles_c * J.nsplit * J.nbatch; }
+
+static WpJobPlan wp_plan_kernel(int n_out, int k_in, int64_t rows, int nbatch, bool ranged, bool batched, bool src16, bool rows16) {
+    WpJobPlan p;
+    wp_choose(n_out, k_in, &p.variant, &p.tiles_o, &p.tiles_c, src16, rows16);
+    wp_plan(wp_rows_expected(rows, ranged), rows, nbatch, p.tiles_o * p.tiles_c, batched, &p.chunk, &p.nsplit, 256, wp_light(p.variant, n_out, k_in));
+    p.slab_floats = ((size_t)p.nsplit * nbatch * n_out * tn_kpad(k_in) + 63) / 64 * 64;
+    return p;
+}
+WpJobPlan wp_job_plan(int n_out, int k_in, int64_t rows, int nbatch, bool ranged, bool batched, bool src16, bool rows16) {
+    WpJobPlan p = wp_plan_kernel(n_out, k_in, rows, nbatch, ranged, batched, src16, rows16);
+    // (bf16 rows: reserve for whichever of the two kernels cuts more row chunks)
+    if (src16) p.slab_floats = std::max(p.slab_floats, wp_plan_kernel(n_out, k_in, rows, nbatch, ranged, batched, true, !rows16).slab_floats);
+    return p;
+}
 size_t wp_slab_floats(int n_out, int k_in, int64_t rows, int nbatch, bool ranged, bool batched, bool src16) {
-    int v, to, tc, chunk, nsplit;
-    size_t need = 0;
-    // (bf16 rows: which of the two kernels takes the product depends on the operands' alignment, known only when it is added --
-    // reserve for the one that cuts more row chunks)
-    for (int pass = 0; pass < (src16 ? 2 : 1); ++pass) {
-        wp_choose(n_out, k_in, &v, &to, &tc, src16, pass == 1);
-        wp_plan(ranged ? (rows + 1) / 2 : rows, rows, nbatch, to * tc, batched, &chunk, &nsplit, 256, wp_light(v, n_out, k_in));
-        const size_t f = ((size_t)nsplit * nbatch * n_out * tn_kpad(k_in) + 63) / 64 * 64;
-        need = f > need ? f : need;
-    }
-    return need;
+    return wp_job_plan(n_out, k_in, rows, nbatch, ranged, batched, src16, false).slab_floats;
 }
 
 void wp_batch_init(WpBatch* b, float* slab, size_t slab_floats, bool batched, const hipStream_t* stream) {
     b->batched = batched;
     b->tab.njobs = 0;
-    b->slab = slab;
-    b->slab_floats = slab_floats;
-    b->used = 0;
-    b->flops = 0.0;
-    b->bytes = 0.0;
-    b->nblocks = 0;
-    b->nblocks2 = 0;
-    b->bytes2 = 0.0;
-    b->nred = 0;
+    b->slab = slab; b->slab_floats = slab_floats; b->used = 0;
+    b->flops = b->bytes = b->bytes2 = 0.0;
+    b->nblocks = b->nblocks2 = b->nred = 0;
     b->stream = stream ? *stream : nullptr;
     b->has_stream = stream != nullptr;
     for (int i = 0; i < WP_MAX_JOBS; ++i) b->chosen[i] = nullptr;
@@ -877,51 +883,56 @@ bool wp_batch_roll(WpBatch* b, int* status) {
     return *status == MPNHIP_OK;
 }
 
-static bool ranged_gather(const WpProduct& p) { return p.dz_idx || p.h_idx || p.H2; }
+// group q of the product as the kernels see it: everything but the plan, the slab and the block indices
+static WpJob wp_job_of(const WgProduct& w, int q, int pieces) {
+    WpJob J = {};
+    J.dZ = w.dZ.p; J.ldz = w.dZ.ld; J.z_bstride = w.dZ.bstride; J.dz_idx = w.dz_idx;
+    J.H = w.H.p; J.ldh = w.H.ld; J.h_bstride = w.H.bstride; J.h_idx = w.h_idx;
+    J.H2 = w.H2.p; J.ldh2 = w.H2.ld; J.h2_bstride = w.H2.bstride; J.csplit = w.H2.p ? w.csplit : w.k_in;
+    J.row_begin = w.g[q].rr.begin; J.row_end = w.g[q].rr.end; J.m_static = w.rows;
+    J.grad_w = w.g[q].grad_w; J.ldw = w.ldw; J.grad_b = w.g[q].grad_b;
+    J.n_out = w.n_out; J.k_in = w.k_in; J.nbatch = w.nbatch;
+    J.pieces = pieces == 1 ? 1 : 3;
+    J.src16 = w.src16 ? 1 : 0;
+    return J;
+}
 
-// records the n (1 or 2: the direction groups of one product) jobs, or none of them
-bool wp_batch_add(WpBatch* b, const WpProduct* ps, int n, WgChosen* chosen) {
-    if (b->tab.njobs + n > WP_MAX_JOBS) return false;
+bool wp_batch_add(WpBatch* b, const WgProduct& w, int pieces, WgChosen* chosen) {
+    const int n = wg_ngroups(w);
+    if (b->tab.njobs + n > WP_MAX_JOBS || !wp_eligible(w, pieces)) return false;
+    auto al16 = [](const void* q) { return (((uintptr_t)q) & 15) == 0; };
+    const bool rows16 = w.src16 && !w.dz_idx && !w.h_idx && !w.H2.p && al16(w.dZ.p) && al16(w.H.p) && w.dZ.ld % 8 == 0 && w.H.ld % 8 == 0 &&
+                        w.dZ.bstride % 8 == 0 && w.H.bstride % 8 == 0 && w.dZ.ld < ((int64_t)1 << 28) && w.H.ld < ((int64_t)1 << 28);
+    WpJob job[2];
+    WpJobPlan plan[2];
     size_t need = 0;
-    for (int i = 0; i < n; ++i) {
-        if (!wp_eligible(ps[i])) return false;
-        need += wp_slab_floats(ps[i].n_out, ps[i].k_in, ps[i].rows, ps[i].nbatch, ps[i].row_begin || ps[i].row_end, b->batched, ps[i].src16 != 0);
+    for (int q = 0; q < n; ++q) {
+        job[q] = wp_job_of(w, q, pieces);
+        plan[q] = wp_job_plan(w.n_out, w.k_in, w.rows, w.nbatch, wp_ranged(job[q]), b->batched, w.src16, rows16);
+        need += plan[q].slab_floats;
     }
     if (b->used + need > b->slab_floats) return false;
-    for (int i = 0; i < n; ++i) {
-        const WpProduct& p = ps[i];
-        const bool ranged = p.row_begin || p.row_end;
+    for (int q = 0; q < n; ++q) {
         WpJob& J = b->tab.job[b->tab.njobs];
-        J = WpJob{};
-        auto al16 = [](const void* q) { return (((uintptr_t)q) & 15) == 0; };
-        const bool rows16 = p.src16 && !ranged_gather(p) && al16(p.dZ) && al16(p.H) && p.ldz % 8 == 0 && p.ldh % 8 == 0 && p.z_bstride % 8 == 0 &&
-                            p.h_bstride % 8 == 0 && p.ldz < ((int64_t)1 << 28) && p.ldh < ((int64_t)1 << 28);
-        wp_choose(p.n_out, p.k_in, &J.variant, &J.tiles_o, &J.tiles_c, p.src16 != 0, rows16);
-        J.src16 = p.src16 ? 1 : 0;
-        wp_plan(ranged ? (p.rows + 1) / 2 : p.rows, p.rows, p.nbatch, J.tiles_o * J.tiles_c, b->batched, &J.chunk, &J.nsplit, 256,
-                wp_light(J.variant, p.n_out, p.k_in));
-        J.dZ = p.dZ; J.H = p.H; J.ldz = p.ldz; J.ldh = p.ldh; J.z_bstride = p.z_bstride; J.h_bstride = p.h_bstride;
-        J.H2 = p.H2; J.ldh2 = p.ldh2; J.h2_bstride = p.h2_bstride; J.csplit = p.H2 ? p.csplit : p.k_in;
-        J.pieces = p.pieces == 1 ? 1 : 3;
-        J.row_begin = p.row_begin; J.row_end = p.row_end; J.m_static = p.rows; J.dz_idx = p.dz_idx; J.h_idx = p.h_idx;
+        J = job[q];
+        J.variant = plan[q].variant; J.tiles_o = plan[q].tiles_o; J.tiles_c = plan[q].tiles_c; J.chunk = plan[q].chunk; J.nsplit = plan[q].nsplit;
         J.slab = b->slab + b->used;
-        J.grad_w = p.grad_w; J.ldw = p.ldw; J.grad_b = p.grad_b;
-        J.n_out = p.n_out; J.k_in = p.k_in; J.nbatch = p.nbatch;
+        b->used += plan[q].slab_floats;
+        const double rows = wp_rows_work(w.rows, wp_ranged(J)) * w.nbatch;
         if (J.variant >= 16) {   // wgrad_rows16.hip's launch
             J.block0 = b->nblocks2;
-            b->nblocks2 += J.tiles_o * J.tiles_c * J.nsplit * J.nbatch;
-            b->bytes2 += 2.0 * (ranged ? p.rows / 2.0 : (double)p.rows) * p.nbatch * (p.n_out + p.k_in);
+            b->nblocks2 += wp_job_blocks(J);
+            b->bytes2 += 2.0 * rows * (w.n_out + w.k_in);
             count_path(PC_TN_ROWS16);
         } else {
             J.block0 = b->nblocks;
-            b->nblocks += J.tiles_o * J.tiles_c * J.nsplit * J.nbatch;
+            b->nblocks += wp_job_blocks(J);
         }
         J.red_block0 = b->nred;
-        b->nred += (int)(((int64_t)p.n_out * tn_kpad(p.k_in) / 4 + 31) / 32);
-        b->used += wp_slab_floats(p.n_out, p.k_in, p.rows, p.nbatch, ranged, b->batched, p.src16 != 0);
-        b->chosen[b->tab.njobs] = chosen ? chosen + i : nullptr;
-        b->flops += 2.0 * (ranged ? p.rows / 2.0 : (double)p.rows) * p.nbatch * p.n_out * p.k_in;
-        b->bytes += (p.src16 ? 2.0 : 4.0) * (ranged ? p.rows / 2.0 : (double)p.rows) * p.nbatch * (p.n_out + p.k_in);
+        b->nred += (int)(((int64_t)w.n_out * tn_kpad(w.k_in) / 4 + 31) / 32);
+        b->chosen[b->tab.njobs] = chosen ? chosen + q : nullptr;
+        b->flops += 2.0 * rows * w.n_out * w.k_in;
+        b->bytes += (w.src16 ? 2.0 : 4.0) * rows * (w.n_out + w.k_in);
         ++b->tab.njobs;
         count_path(PC_TN_PANEL);
     }
@@ -944,14 +955,13 @@ int wp_batch_flush(WpBatch* b, hipStream_t s) {
     // chunks are untouched by the tiling -- and run by the four-blocks-per-CU instantiation.  Taken when the re-tiling re-reads
     // at most 15 % more operand columns over the whole launch (a [80 x 32] product as 2 x 1 tiles reads its 32 H columns twice).
     bool narrow = b->nblocks > 0;
-    const int narrow_lds = WP_NARROW_LDS;
     {
         double cols = 0.0, extra = 0.0;
         for (int i = 0; i < b->tab.njobs && narrow; ++i) {
             const WpJob& J = b->tab.job[i];
             if (J.variant >= 16) continue;
             if (J.src16 || J.variant > 7 || J.variant == 4) { narrow = false; break; }
-            const double rows = (double)J.m_static * J.nbatch * ((J.row_begin || J.row_end) ? 0.5 : 1.0);
+            const double rows = wp_rows_work(J.m_static, wp_ranged(J)) * J.nbatch;
             if (J.variant == 6 || J.variant == 7) { cols += rows * (J.n_out + J.k_in); continue; }
             const int to = (J.n_out + 63) / 64, tc = (J.k_in + 63) / 64;
             cols += rows * ((double)J.n_out * J.tiles_c + (double)J.k_in * J.tiles_o);
@@ -976,24 +986,14 @@ int wp_batch_flush(WpBatch* b, hipStream_t s) {
             c->variant = J.variant; c->tiles_o = J.tiles_o; c->tiles_c = J.tiles_c; c->chunk = J.chunk; c->nsplit = J.nsplit;
             c->narrow = narrow && J.variant < 16 ? 1 : 0;
         }
-    {   // (block counts follow the tiling: recomputed here, then re-indexed below)
-        int n1 = 0, n2 = 0;
-        for (int i = 0; i < b->tab.njobs; ++i) {
-            const WpJob& J = b->tab.job[i];
-            const int nb = J.tiles_o * J.tiles_c * J.nsplit * J.nbatch;
-            if (J.variant >= 16) n2 += nb; else n1 += nb;
-        }
-        b->nblocks = n1;
-        b->nblocks2 = n2;
-    }
-    for (int pass = 0; pass < 2; ++pass) {   // the row-panel kernel's jobs, then wgrad_rows16.hip's: each launch has its own indices
+    // the row-panel kernel's jobs, then wgrad_rows16.hip's: each launch has its own block indices, and its block count follows the tiling
+    for (int pass = 0; pass < 2; ++pass) {
         int idx[WP_MAX_JOBS], n = 0;
         double w[WP_MAX_JOBS];
         for (int i = 0; i < b->tab.njobs; ++i) {
             const WpJob& J = b->tab.job[i];
             if ((J.variant >= 16) != (pass == 1)) continue;
-            const double rows = (J.row_begin || J.row_end) ? 0.5 * J.chunk : (double)J.chunk;
-            w[n] = rows * ((double)J.n_out / J.tiles_o + (double)J.k_in / J.tiles_c);
+            w[n] = wp_rows_work(J.chunk, wp_ranged(J)) * ((double)J.n_out / J.tiles_o + (double)J.k_in / J.tiles_c);
             idx[n++] = i;
         }
         for (int a = 1; a < n; ++a)   // (insertion sort, stable: equal weights keep the recording order)
@@ -1002,9 +1002,18 @@ int wp_batch_flush(WpBatch* b, hipStream_t s) {
         for (int a = 0; a < n; ++a) {
             WpJob& J = b->tab.job[idx[a]];
             J.block0 = next;
-            next += J.tiles_o * J.tiles_c * J.nsplit * J.nbatch;
+            next += wp_job_blocks(J);
         }
+        (pass == 1 ? b->nblocks2 : b->nblocks) = next;
     }
+    // the row-panel launch: the narrow or the wide instantiation, with the open profile bracket's events where `profiled` and there are any
+    auto launch_panel = [&](bool profiled) {
+        void (*const kernel)(WpTable) = narrow ? wgrad_panel_narrow_kernel : wgrad_panel_kernel;
+        const size_t lds = narrow ? (size_t)WP_NARROW_LDS : wp_lds_bytes();
+        hipEvent_t e0, e1;
+        if (profiled && prof_launch_events(&e0, &e1)) hipExtLaunchKernelGGL(kernel, dim3((unsigned)b->nblocks), dim3(WP_NT), lds, s, e0, e1, 0, b->tab);
+        else hipLaunchKernelGGL(kernel, dim3((unsigned)b->nblocks), dim3(WP_NT), lds, s, b->tab);
+    };
     if (b->nblocks2 > 0) {
         // the bf16-row jobs of the LDS-DMA kernel (wgrad_rows16.hip): the profiled launch of a batch that has them (their bytes)
         count_path(PC_TN_ROWS16_LAUNCH);
@@ -1012,21 +1021,11 @@ int wp_batch_flush(WpBatch* b, hipStream_t s) {
         const int r2 = launch_wgrad_rows16(b->tab, b->nblocks2, s);
         prof_end(PROF_TN, s);
         MPN_TRY(r2);
-        if (b->nblocks > 0) {
-            if (narrow) hipLaunchKernelGGL(wgrad_panel_narrow_kernel, dim3((unsigned)b->nblocks), dim3(WP_NT), narrow_lds, s, b->tab);
-            else hipLaunchKernelGGL(wgrad_panel_kernel, dim3((unsigned)b->nblocks), dim3(WP_NT), wp_lds_bytes(), s, b->tab);
-        }
+        if (b->nblocks > 0) launch_panel(false);
         MPN_LAUNCH_CHECK();
     } else if (b->nblocks > 0) {
         prof_begin(PROF_TN, s, b->bytes);   // (HBM-bound by design: the hook's work figure is the launch's operand bytes)
-        {
-            hipEvent_t e0, e1;
-            const bool ev = prof_launch_events(&e0, &e1);
-            if (narrow && ev) hipExtLaunchKernelGGL(wgrad_panel_narrow_kernel, dim3((unsigned)b->nblocks), dim3(WP_NT), narrow_lds, s, e0, e1, 0, b->tab);
-            else if (narrow) hipLaunchKernelGGL(wgrad_panel_narrow_kernel, dim3((unsigned)b->nblocks), dim3(WP_NT), narrow_lds, s, b->tab);
-            else if (ev) hipExtLaunchKernelGGL(wgrad_panel_kernel, dim3((unsigned)b->nblocks), dim3(WP_NT), wp_lds_bytes(), s, e0, e1, 0, b->tab);
-            else hipLaunchKernelGGL(wgrad_panel_kernel, dim3((unsigned)b->nblocks), dim3(WP_NT), wp_lds_bytes(), s, b->tab);
-        }
+        launch_panel(true);
         prof_end(PROF_TN, s);
         MPN_LAUNCH_CHECK();
     }

@@ -84,3 +84,57 @@ def test_weight_grad_over_bf16_rows_matches_float64(n_out, k_in):
             err = float((gw.double() - 0.25 - ref).abs().max()) / (float(ref.abs().max()) + 1e-30)
             errb = float((gb.double() + 0.5 - refb).abs().max()) / (float(refb.abs().max()) + 1e-30)
             assert err < 3e-6 and errb < 3e-6, (rows, nb, err, errb)
+
+
+WG_COUNTERS = ("gemm_tn_mfma", "gemm_tn_small", "gemm_tn_generic", "gemm_tn_panel", "wgrad_panel_launches", "wgrad_panel_narrow_launches",
+               "wgrad_panel_fallback", "wgrad_rows16", "wgrad_rows16_launches")
+
+
+def test_public_entries_take_the_routes_decisions():
+    """The public entries go through the backward's routing (csrc/wgrad.hip: weight_grad_route): the path counters after one call
+    are those of the same product routed on its own -- fp32 kernels for fp32, a row-panel job for a split / bf16 product of those
+    kernels' shapes (the small block for [18 x 18], alone in a narrow launch), the counted fallback to the fp32 kernels for one that
+    is none ([160 x 7]: k_in no multiple of 4, n_out > 96), the LDS-DMA kernel over aligned bf16 rows, and over bf16 rows a refusal
+    worded by the entry where no kernel covers the shape."""
+    lib = capi.load()
+    dev = torch.device("cuda:0")
+    rows, nb = 300, 1
+
+    def call(n_out, k_in, precision):   # precision None: mpnhip_weight_grad_bf16_rows
+        dz = torch.from_numpy(synth.normal(3 + rows, (nb, rows, n_out))).to(dev)
+        h = torch.from_numpy(synth.normal(5 + rows, (nb, rows, k_in))).to(dev)
+        gw = torch.full((n_out, k_in), 0.25, device=dev)
+        gb = torch.full((n_out,), -0.5, device=dev)
+        capi.path_counters(reset=True)
+        if precision is None:
+            dz, h = dz.bfloat16(), h.bfloat16()
+            ws = torch.empty(lib.mpnhip_weight_grad_bf16_rows_workspace_bytes(n_out, k_in, rows, nb), dtype=torch.uint8, device=dev)
+            rc = lib.mpnhip_weight_grad_bf16_rows(capi.ptr(dz), capi.ptr(h), rows, n_out, k_in, nb, capi.ptr(gw), capi.ptr(gb), capi.ptr(ws),
+                                                  ws.numel(), capi.stream_ptr())
+        else:
+            ws = torch.empty(lib.mpnhip_weight_grad_workspace_bytes(n_out, k_in, rows, nb), dtype=torch.uint8, device=dev)
+            rc = lib.mpnhip_weight_grad_prec(capi.ptr(dz), capi.ptr(h), rows, n_out, k_in, nb, capi.PRECISIONS[precision], capi.ptr(gw),
+                                             capi.ptr(gb), capi.ptr(ws), ws.numel(), capi.stream_ptr())
+        torch.cuda.synchronize()
+        got = capi.path_counters()
+        ref = torch.einsum("bmo,bmc->oc", dz.double(), h.double())
+        err = float((gw.double() - 0.25 - ref).abs().max()) / (float(ref.abs().max()) + 1e-30)
+        return rc, {k: got[k] for k in WG_COUNTERS}, err, gw
+
+    def counts(**kw):
+        return {**dict.fromkeys(WG_COUNTERS, 0), **kw}
+
+    rc, got, err, _ = call(320, 64, "fp32")
+    assert rc == 0 and got == counts(gemm_tn_mfma=1) and err < 3e-6, (rc, got, err)
+    rc, got, err, _ = call(320, 64, "fp32_split")
+    assert rc == 0 and got == counts(gemm_tn_panel=1, wgrad_panel_launches=1) and err < 3e-6, (rc, got, err)
+    rc, got, err, _ = call(160, 7, "fp32_split")
+    assert rc == 0 and got == counts(wgrad_panel_fallback=1, gemm_tn_generic=1) and err < 3e-6, (rc, got, err)
+    rc, got, err, _ = call(18, 18, "bf16")
+    assert rc == 0 and got == counts(gemm_tn_panel=1, wgrad_panel_launches=1, wgrad_panel_narrow_launches=1) and err < 1.5e-2, (rc, got, err)
+    rc, got, err, _ = call(640, 128, None)
+    assert rc == 0 and got == counts(gemm_tn_panel=1, wgrad_panel_launches=1, wgrad_rows16=1, wgrad_rows16_launches=1) and err < 3e-6, (rc, got, err)
+    rc, got, _, gw = call(160, 7, None)
+    assert rc == -4 and got == counts(wgrad_panel_fallback=1), (rc, got)   # MPNHIP_ERR_UNSUPPORTED, nothing launched
+    assert b"weight_grad_bf16_rows: [160 x 7] over bf16 rows is not a shape of the row-panel kernel" in lib.mpnhip_last_error()
+    assert bool((gw == 0.25).all())

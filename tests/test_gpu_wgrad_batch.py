@@ -1,5 +1,5 @@
 """Operator-level parity of the weight-gradient products as mpnhip_backward issues them: mpnhip_debug_weight_grad_batch runs the
-backward's own routing (csrc/gemm_tn.hip: weight_grad_route) over the row-panel kernels (csrc/wgrad_panel.hip), the LDS-DMA kernel
+backward's own routing (csrc/wgrad.hip: weight_grad_route) over the row-panel kernels (csrc/wgrad_panel.hip), the LDS-DMA kernel
 over bf16 rows (csrc/wgrad_rows16.hip) and the four fp32 kernels behind launch_gemm_tn, against ONE float64 CPU reference of the
 documented formula (tests/wgrad_ref.py, pinned by tests/test_wgrad_reference_cpu.py).
 
