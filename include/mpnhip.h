@@ -1069,6 +1069,58 @@ int mpnhip_hota_association(const int32_t* matches_count, const int32_t* gt_coun
                             int64_t n_tr_ids, double* out, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * TrackEval's Identity and CLEAR metrics of a KITTI-MOTS sequence (metrics/identity.py:32-89, metrics/clear.py:37-128) for one
+ * class, from what mpnhip_hota_frame_similarity left on the device for a launch: sim, sim_ptr, the lists, b_removed and the
+ * trajectory indices, all as in the HOTA calls above (an entry is KEPT in the same way).  The accumulators and the scan's state
+ * belong to the caller, who initialises them before the first launch of a sequence; the launches are issued in frame order and
+ * the result does not depend on how the frames are split into launches.  Integer atomics only; the one float64 sum (MOTP_sum)
+ * is one thread adding in the kit's order: the same bits on every call (tests/clear_identity_ref.py restates the operators in
+ * numpy).  Every index read from a caller's array is clamped or checked before it is used.  MPNHIP_ERR_UNSUPPORTED from the
+ * two Identity calls for n_gt_ids * n_tr_ids >= 2^31 (the table is one problem of mpnhip_lsa_batched).
+ * ------------------------------------------------------------------------------------------- */
+/* Bytes that any of the calls below needs for these sizes.  0 for sizes the calls refuse. */
+size_t mpnhip_clear_identity_workspace_bytes(int64_t n_a, int64_t n_b, int64_t n_frames, int64_t n_gt_ids, int64_t n_tr_ids);
+/* identity.py:55-57 for one launch: potential_count [n_gt_ids, n_tr_ids] (int32) += 1 at the ids of every kept pair with
+ * sim >= 0.5 (the kit's np.greater_equal on the double of mpnhip_hota_frame_similarity).  gt_id_count / tracker_id_count of
+ * :60-61 are gt_count / tr_count of mpnhip_hota_accumulate_alignment. */
+int mpnhip_identity_accumulate(const double* sim, int64_t sim_cells, const int64_t* sim_ptr, const int32_t* a_ptr, int64_t n_a,
+                               const int32_t* b_ptr, int64_t n_b, int64_t n_frames, const int32_t* a_traj, const int32_t* b_traj,
+                               const unsigned char* b_removed, int64_t n_gt_ids, int64_t n_tr_ids, int32_t* potential_count, void* stream);
+/* idtp [1] (int64, written by the call) = the sum of potential_count[g, match_b[g]] over the ids g with match_b[g] (int32
+ * [n_gt_ids]) in [0, n_tr_ids): IDTP for the complete assignment of min(n_gt_ids, n_tr_ids) pairs that maximises that sum, which
+ * is what identity.py:63-85 computes (IDFN = sum(gt_count) - IDTP, IDFP = sum(tr_count) - IDTP).  match_b is that of
+ * mpnhip_lsa_batched for the one problem a_ptr = {0, n_gt_ids}, b_ptr = {0, n_tr_ids}. */
+int mpnhip_identity_sums(const int32_t* potential_count, const int32_t* match_b, int64_t n_gt_ids, int64_t n_tr_ids, int64_t* idtp,
+                         void* stream);
+/* clear.py:81 for one launch, all frames in parallel.  A cell is eligible iff sim >= 0.5 - eps (compared as doubles; for a mask:
+ * 2 i >= u).  a_cand [n_a, 2] / b_cand [n_b, 2] (int32): the first two kept entries of the other list (indices into it, list
+ * order) a kept entry is eligible with, -1 for none and for an entry that is not kept.  status [1] (int32, written by the
+ * call): bit 0 an entry has three or more, bit 1 an a-entry with two has one that itself has two -- among the disjoint masks
+ * of label images neither can happen, and a component of eligible cells is a single pair or a star of three entries. */
+int mpnhip_clear_frame_candidates(const double* sim, int64_t sim_cells, const int64_t* sim_ptr, const int32_t* a_ptr, int64_t n_a,
+                                  const int32_t* b_ptr, int64_t n_b, int64_t n_frames, const int32_t* a_traj, const int32_t* b_traj,
+                                  const unsigned char* b_removed, int64_t n_gt_ids, int64_t n_tr_ids, int32_t* a_cand, int32_t* b_cand,
+                                  int32_t* status, void* stream);
+/* clear.py:67-114 for one launch, its frames in ascending order (one wavefront).  State of the sequence, all [n_gt_ids] int32:
+ * prev_tracker_id and prev_timestep_tracker_id (trajectory indices; the caller starts them at -1, the kit's NaN), gt_id_count,
+ * gt_matched_count, gt_frag_count (from 0); counters [4] (int64, from 0): CLR_TP, CLR_FN, CLR_FP, IDSW; motp_sum [1] (float64).
+ * A frame without kept a-entries only adds its kept b-entries to CLR_FP; one without kept b-entries adds to CLR_FN and
+ * gt_id_count; both leave prev_timestep_tracker_id alone.  Otherwise a single pair of candidates is a match; in a star the arm
+ * whose tracker id equals prev_timestep_tracker_id of its object wins, without one the entry earlier in the list (the kit:
+ * scipy's tie order).  match_b [n_a] (int32, written by the call): the b-entry matched with every a-entry, or -1. */
+int mpnhip_clear_sequence_scan(const double* sim, int64_t sim_cells, const int64_t* sim_ptr, const int32_t* a_ptr, int64_t n_a,
+                               const int32_t* b_ptr, int64_t n_b, int64_t n_frames, const int32_t* a_traj, const int32_t* b_traj,
+                               const unsigned char* b_removed, const int32_t* a_cand, const int32_t* b_cand, int64_t n_gt_ids,
+                               int64_t n_tr_ids, int32_t* prev_tracker_id, int32_t* prev_timestep_tracker_id, int32_t* gt_id_count,
+                               int32_t* gt_matched_count, int32_t* gt_frag_count, int64_t* counters, double* motp_sum, int32_t* match_b,
+                               void* workspace, size_t workspace_bytes, void* stream);
+/* clear.py:117-121: out [4] (int64, written by the call) = MT, PT, ML, Frag from the three per-id counts: over the ids with
+ * gt_id_count > 0, matched / count > 0.8 is MT and >= 0.2 is MT + PT (decided in integers: 5 m > 4 c, 5 m >= c);
+ * ML = n_gt_ids - MT - PT; Frag = the sum of gt_frag_count - 1 over the ids where it is positive. */
+int mpnhip_clear_track_summary(const int32_t* gt_id_count, const int32_t* gt_matched_count, const int32_t* gt_frag_count, int64_t n_gt_ids,
+                               int64_t* out, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Batched rectangular linear sum assignment: scipy.optimize.linear_sum_assignment(cost, maximize) for n_problems problems in
  * one launch, in the layout of the HOTA calls above (a score block goes in as it is).  Problem f owns the a-entries a_ptr[f] ..
  * a_ptr[f + 1] and the b-entries b_ptr[f] .. b_ptr[f + 1] of two lists (device int32 [n_problems + 1]) and na_f x nb_f float64

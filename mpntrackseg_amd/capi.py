@@ -264,6 +264,13 @@ SIGNATURES = {
     "mpnhip_hota_frame_scores": (_I, [_P, _L, _P, _P, _L, _P, _L, _L, _P, _P, _P, _L, _L, _P, _P, _P, _P, _P]),
     "mpnhip_hota_alpha_accumulate": (_I, [_P, _L, _P, _P, _L, _P, _L, _L, _P, _P, _P, _P, _P, _L, _L, _P, _P, _P, _P, _Z, _P]),
     "mpnhip_hota_association": (_I, [_P, _P, _P, _L, _L, _P, _P, _Z, _P]),
+    "mpnhip_clear_identity_workspace_bytes": (_Z, [_L, _L, _L, _L, _L]),
+    "mpnhip_identity_accumulate": (_I, [_P, _L, _P, _P, _L, _P, _L, _L, _P, _P, _P, _L, _L, _P, _P]),
+    "mpnhip_identity_sums": (_I, [_P, _P, _L, _L, _P, _P]),
+    "mpnhip_clear_frame_candidates": (_I, [_P, _L, _P, _P, _L, _P, _L, _L, _P, _P, _P, _L, _L, _P, _P, _P, _P]),
+    "mpnhip_clear_sequence_scan": (_I, [_P, _L, _P, _P, _L, _P, _L, _L, _P, _P, _P, _P, _P, _L, _L, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                                        _Z, _P]),
+    "mpnhip_clear_track_summary": (_I, [_P, _P, _P, _L, _P, _P]),
     "mpnhip_lsa_workspace_bytes": (_Z, [_L, _L, _L]),
     "mpnhip_lsa_batched": (_I, [_P, _L, _P, _P, _L, _P, _L, _L, _P, _P, _I, _P, _P, _P, _P, _Z, _P]),
     "mpnhip_profile_enable": (_I, [_I]),

@@ -12,40 +12,17 @@
 #include <cfloat>
 #include <climits>
 
-#include "label_tables.h"
+#include "sim_lists.h"
 
 namespace mpnhip {
 namespace {
 
 constexpr int N_ALPHA = MPNHIP_HOTA_ALPHAS;
-constexpr int HT_THREADS = 256, HT_WAVES = HT_THREADS / 64;
+constexpr int HT_THREADS = MT_THREADS, HT_WAVES = HT_THREADS / 64;
 constexpr int AS_CELLS_PER_BLOCK = 1024, AS_MAX_BLOCKS = 256;   // association: blocks per alpha = f(G * T) alone
 constexpr double EPS = DBL_EPSILON;                            // np.finfo('float').eps
 
-// one launch's lists and the layout of its similarity block: frame f owns na_f x nb_f doubles at sim_ptr[f]
-struct Lists {
-    const int* a_ptr; const int* b_ptr; const int64_t* sim_ptr;
-    int n_a, n_b, n_frames;
-    int64_t sim_cells;
-};
-struct FrameSim { int a0, na, b0, nb; int64_t base; bool ok; };
-__device__ __forceinline__ FrameSim frame_sim(const Lists& L, int f) {
-    FrameSim s;
-    clamp_range(L.a_ptr, f, L.n_a, s.a0, s.na);
-    clamp_range(L.b_ptr, f, L.n_b, s.b0, s.nb);
-    s.base = L.sim_ptr[f];
-    const int64_t cells = (int64_t)s.na * s.nb;
-    s.ok = s.base >= 0 && s.base <= L.sim_cells && cells <= L.sim_cells - s.base;
-    return s;
-}
 struct Alphas { double v[N_ALPHA]; };
-
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-__device__ __forceinline__ bool in_range(int v, int n) { return (unsigned)v < (unsigned)n; }
 
 // ------------------------------------------------------------------------------------------------ similarity
 // One wavefront per a-entry: its row of the similarity block (0 in the row of an ignore entry and in the column of a
@@ -323,9 +300,6 @@ static AssView ass_view(void* workspace, int64_t cells) {
     return v;
 }
 
-static bool hota_sizes_ok(int64_t n_a, int64_t n_b, int64_t n_frames, int64_t n_gt, int64_t n_tr) {
-    return list_sizes_ok(n_a, n_frames, 0) && list_sizes_ok(n_b, n_frames, 0) && n_gt >= 0 && n_tr >= 0 && n_gt < (1LL << 31) && n_tr < (1LL << 31);
-}
 // the int32 matches_count [N_ALPHA, G, T] and the per-frame maps [n_frames, G] / [n_frames, T] are indexed below 2^31
 static bool hota_supported(int64_t n_frames, int64_t n_gt, int64_t n_tr) {
     return n_gt * n_tr * N_ALPHA < (1LL << 31) && n_frames * (n_gt + n_tr) < (1LL << 31);
@@ -336,17 +310,7 @@ static int refuse_unsupported(const char* name, int64_t n_frames, int64_t n_gt, 
     return MPNHIP_ERR_UNSUPPORTED;
 }
 
-static Lists make_lists(const int32_t* a_ptr, int64_t n_a, const int32_t* b_ptr, int64_t n_b, const int64_t* sim_ptr, int64_t sim_cells,
-                        int64_t n_frames) {
-    Lists L = {a_ptr, b_ptr, sim_ptr, (int)n_a, (int)n_b, (int)n_frames, sim_cells};
-    return L;
-}
 static unsigned wave_blocks(int64_t n) { return (unsigned)((n + HT_WAVES - 1) / HT_WAVES); }
-// blocks of a frame for a stride loop over its cells: sized for the average frame, at most 64
-static unsigned frame_blocks(int64_t sim_cells, int64_t n_frames) {
-    const int64_t b = (sim_cells / n_frames + HT_THREADS - 1) / HT_THREADS;
-    return (unsigned)(b < 1 ? 1 : (b > 64 ? 64 : b));
-}
 
 }  // namespace
 }  // namespace mpnhip
@@ -354,7 +318,7 @@ static unsigned frame_blocks(int64_t sim_cells, int64_t n_frames) {
 using namespace mpnhip;
 
 extern "C" size_t mpnhip_hota_workspace_bytes(int64_t n_a, int64_t n_b, int64_t n_frames, int64_t n_gt_ids, int64_t n_tr_ids) {
-    if (!hota_sizes_ok(n_a, n_b, n_frames, n_gt_ids, n_tr_ids) || !hota_supported(n_frames, n_gt_ids, n_tr_ids)) return 0;
+    if (!sim_sizes_ok(n_a, n_b, n_frames, n_gt_ids, n_tr_ids) || !hota_supported(n_frames, n_gt_ids, n_tr_ids)) return 0;
     size_t need = sim_view(nullptr, n_a, n_b).bytes;
     const size_t others[3] = {map_view(nullptr, n_frames, n_gt_ids, n_tr_ids).bytes, alpha_view(nullptr, n_frames).bytes,
                               ass_view(nullptr, n_gt_ids * n_tr_ids).bytes};
@@ -368,7 +332,7 @@ extern "C" int mpnhip_hota_frame_similarity(const int32_t* table, int64_t table_
                                             int64_t sim_cells, double* sim, unsigned char* b_removed, double* row_sum, double* col_sum,
                                             void* workspace, size_t workspace_bytes, void* stream_) {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    MPN_CHECK_ARG(hota_sizes_ok(n_a, n_b, n_frames, 0, 0) && table_cells >= 0 && sim_cells >= 0, "hota_frame_similarity: bad sizes");
+    MPN_CHECK_ARG(sim_sizes_ok(n_a, n_b, n_frames, 0, 0) && table_cells >= 0 && sim_cells >= 0, "hota_frame_similarity: bad sizes");
     if (table_cells >= (1LL << 31) || sim_cells >= (1LL << 31)) {
         set_error("hota_frame_similarity: a table of %lld cells (2^31 or more) is not supported: fewer frames per call", (long long)table_cells);
         return MPNHIP_ERR_UNSUPPORTED;
@@ -419,7 +383,7 @@ extern "C" int mpnhip_hota_accumulate_alignment(const double* sim, int64_t sim_c
                                                 int32_t* gt_count, int32_t* tr_count, void* workspace, size_t workspace_bytes,
                                                 void* stream_) {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    MPN_CHECK_ARG(hota_sizes_ok(n_a, n_b, n_frames, n_gt_ids, n_tr_ids) && sim_cells >= 0 && sim_cells < (1LL << 31),
+    MPN_CHECK_ARG(sim_sizes_ok(n_a, n_b, n_frames, n_gt_ids, n_tr_ids) && sim_cells >= 0 && sim_cells < (1LL << 31),
                   "hota_accumulate_alignment: bad sizes");
     if (!hota_supported(n_frames, n_gt_ids, n_tr_ids)) return refuse_unsupported("hota_accumulate_alignment", n_frames, n_gt_ids, n_tr_ids);
     if (n_a == 0 && n_b == 0) return MPNHIP_OK;
@@ -450,7 +414,7 @@ extern "C" int mpnhip_hota_frame_scores(const double* sim, int64_t sim_cells, co
                                         const unsigned char* b_removed, int64_t n_gt_ids, int64_t n_tr_ids, const double* potential,
                                         const int32_t* gt_count, const int32_t* tr_count, double* score, void* stream_) {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    MPN_CHECK_ARG(hota_sizes_ok(n_a, n_b, n_frames, n_gt_ids, n_tr_ids) && sim_cells >= 0 && sim_cells < (1LL << 31),
+    MPN_CHECK_ARG(sim_sizes_ok(n_a, n_b, n_frames, n_gt_ids, n_tr_ids) && sim_cells >= 0 && sim_cells < (1LL << 31),
                   "hota_frame_scores: bad sizes");
     if (!hota_supported(n_frames, n_gt_ids, n_tr_ids)) return refuse_unsupported("hota_frame_scores", n_frames, n_gt_ids, n_tr_ids);
     if (sim_cells == 0) return MPNHIP_OK;
@@ -472,7 +436,7 @@ extern "C" int mpnhip_hota_alpha_accumulate(const double* sim, int64_t sim_cells
                                             const double* alphas, int64_t n_gt_ids, int64_t n_tr_ids, int64_t* tp, double* loca,
                                             int32_t* matches_count, void* workspace, size_t workspace_bytes, void* stream_) {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    MPN_CHECK_ARG(hota_sizes_ok(n_a, n_b, n_frames, n_gt_ids, n_tr_ids) && sim_cells >= 0 && sim_cells < (1LL << 31),
+    MPN_CHECK_ARG(sim_sizes_ok(n_a, n_b, n_frames, n_gt_ids, n_tr_ids) && sim_cells >= 0 && sim_cells < (1LL << 31),
                   "hota_alpha_accumulate: bad sizes");
     if (!hota_supported(n_frames, n_gt_ids, n_tr_ids)) return refuse_unsupported("hota_alpha_accumulate", n_frames, n_gt_ids, n_tr_ids);
     MPN_CHECK_ARG(alphas && tp && loca, "hota_alpha_accumulate: null alphas, tp or loca");
@@ -495,7 +459,7 @@ extern "C" int mpnhip_hota_alpha_accumulate(const double* sim, int64_t sim_cells
 extern "C" int mpnhip_hota_association(const int32_t* matches_count, const int32_t* gt_count, const int32_t* tr_count, int64_t n_gt_ids,
                                        int64_t n_tr_ids, double* out, void* workspace, size_t workspace_bytes, void* stream_) {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    MPN_CHECK_ARG(hota_sizes_ok(0, 0, 0, n_gt_ids, n_tr_ids), "hota_association: bad sizes");
+    MPN_CHECK_ARG(sim_sizes_ok(0, 0, 0, n_gt_ids, n_tr_ids), "hota_association: bad sizes");
     if (!hota_supported(0, n_gt_ids, n_tr_ids)) return refuse_unsupported("hota_association", 0, n_gt_ids, n_tr_ids);
     MPN_CHECK_ARG(out, "hota_association: null out");
     const int64_t cells = n_gt_ids * n_tr_ids;

@@ -277,16 +277,11 @@ def _check_frames(frames, num_timesteps, what):
         raise ValueError("%s data contains the following invalid timesteps: %s" % (what, ", ".join(str(int(v)) for v in bad)))
 
 
-def _evaluate(gt_rows, num_timesteps, class_id, ignore_class, frames_per_launch, device, b_frame, b_traj, b_ids, b_labels,
-              img_shape, details=False, ops=None, assignment="host"):
-    """The two passes over the launches of a sequence.  The b-side as in ``mots_eval._evaluate``: its frames' entries
-    (``b_frame`` ascending, ``b_traj``; -1: an entry that only occupies pixels) and ``b_labels(frames, b_ptr, b_entries, hw)``
-    -> the label images of ascending ``frames``.  ``ops``: the operators (this module's and ``mots_eval``'s two; the tests' numpy
-    restatements have no device to run on).  ``assignment``: ``'host'`` (``assign_frames``) or ``'device'``
-    (``ops.assign_frames_device``)."""
-    ops = ops or sys.modules[__name__]
-    if assignment not in ("host", "device"):
-        raise ValueError("assignment is 'host' or 'device' (%r)" % (assignment,))
+def _pass1(gt_rows, num_timesteps, class_id, ignore_class, frames_per_launch, device, b_frame, b_traj, b_ids, b_labels, img_shape, ops):
+    """The first pass over the launches of a sequence for one class: the pixel work, the removals and the global alignment.
+    Returns what every metric of the class consumes (``kitti_mots_eval`` shares it between HOTA, CLEAR and Identity): ``acc``
+    (the accumulators), ``launches`` ([(S, a_traj, b_traj)], the similarity blocks on the device), ``counts`` (the kit's
+    num_gt_dets, num_tracker_dets, num_gt_ids, num_tracker_ids after the preprocessing), ``b_traj`` and ``b_kept`` per b-entry."""
     _check_frames(gt_rows["frame"], num_timesteps, "Ground-truth")
     _check_frames(b_frame, num_timesteps, "Tracking")
     b_traj = np.asarray(b_traj, np.int64)
@@ -302,7 +297,7 @@ def _evaluate(gt_rows, num_timesteps, class_id, ignore_class, frames_per_launch,
     frames = np.union1d(a.frame, b_frame)
     step = max(int(frames_per_launch), 1)
     launches = []
-    for g0 in range(0, frames.size if hw else 0, step):   # pass 1: the pixel work, the removals and the global alignment
+    for g0 in range(0, frames.size if hw else 0, step):
         fl = frames[g0:g0 + step]
         a_ptr, a_entries, (re_, rb, ren) = a.launch(fl)
         b_lo, b_hi = np.searchsorted(b_frame, fl, "left"), np.searchsorted(b_frame, fl, "right")
@@ -318,22 +313,45 @@ def _evaluate(gt_rows, num_timesteps, class_id, ignore_class, frames_per_launch,
         launches.append((S, at, bt))
     b_kept = (b_traj >= 0) & ~b_removed
     counts = (int((a.traj >= 0).sum()), int(b_kept.sum()), int(a.ids.size), int(np.unique(b_traj[b_kept]).size))
+    return {"acc": acc, "launches": launches, "counts": counts, "b_traj": b_traj, "b_kept": b_kept}
+
+
+def _pass2(P, ops, assignment):
+    """The second pass over the launches of ``_pass1``: the assignments and the counts per alpha; HOTA's fields."""
+    acc, launches, counts = P["acc"], P["launches"], P["counts"]
     if counts[0] == 0 or counts[1] == 0:
-        res = hota_from_accumulators(None, None, None, *counts)
-    else:
-        for S, at, bt in launches:                        # pass 2: the assignments and the counts per alpha
-            if assignment == "device":
-                match_b = ops.assign_frames_device(S, at, bt, ops.frame_scores(S, at, bt, acc, host=False))
-            else:
-                match_b = assign_frames(S, at, bt, ops.frame_scores(S, at, bt, acc))
-            ops.alpha_accumulate(S, at, bt, match_b, ALPHAS, acc)
+        return hota_from_accumulators(None, None, None, *counts)
+    for S, at, bt in launches:
         if assignment == "device":
-            check_assignment_status([S for S, _, _ in launches])   # (before the sums are read: no silent fallback)
-        out = ops.association(acc)
-        res = hota_from_accumulators(out["tp"], out["loca"], out["ass"], *counts)
+            match_b = ops.assign_frames_device(S, at, bt, ops.frame_scores(S, at, bt, acc, host=False))
+        else:
+            match_b = assign_frames(S, at, bt, ops.frame_scores(S, at, bt, acc))
+        ops.alpha_accumulate(S, at, bt, match_b, ALPHAS, acc)
+    if assignment == "device":
+        check_assignment_status([S for S, _, _ in launches])   # (before the sums are read: no silent fallback)
+    out = ops.association(acc)
+    return hota_from_accumulators(out["tp"], out["loca"], out["ass"], *counts)
+
+
+def _check_assignment(assignment):
+    if assignment not in ("host", "device"):
+        raise ValueError("assignment is 'host' or 'device' (%r)" % (assignment,))
+
+
+def _evaluate(gt_rows, num_timesteps, class_id, ignore_class, frames_per_launch, device, b_frame, b_traj, b_ids, b_labels,
+              img_shape, details=False, ops=None, assignment="host"):
+    """The two passes over the launches of a sequence.  The b-side as in ``mots_eval._evaluate``: its frames' entries
+    (``b_frame`` ascending, ``b_traj``; -1: an entry that only occupies pixels) and ``b_labels(frames, b_ptr, b_entries, hw)``
+    -> the label images of ascending ``frames``.  ``ops``: the operators (this module's and ``mots_eval``'s two; the tests' numpy
+    restatements have no device to run on).  ``assignment``: ``'host'`` (``assign_frames``) or ``'device'``
+    (``ops.assign_frames_device``)."""
+    ops = ops or sys.modules[__name__]
+    _check_assignment(assignment)
+    P = _pass1(gt_rows, num_timesteps, class_id, ignore_class, frames_per_launch, device, b_frame, b_traj, b_ids, b_labels, img_shape, ops)
+    res = _pass2(P, ops, assignment)
     if details:   # {frame: the prediction ids the preprocessing keeps, ascending}
         ids = np.asarray(b_ids, np.int64)
-        res["kept_tracker_ids"] = {int(f): sorted(int(v) for v in ids[b_traj[(b_frame == f) & b_kept]]) for f in np.unique(b_frame)}
+        res["kept_tracker_ids"] = {int(f): sorted(int(v) for v in ids[P["b_traj"][(b_frame == f) & P["b_kept"]]]) for f in np.unique(b_frame)}
     return res
 
 

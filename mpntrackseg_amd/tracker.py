@@ -410,18 +410,10 @@ def evaluate_mots_sequence(node_preds, boxes, frame_num_per_node, ped_ids, label
                         traj_ids, b_labels, img_shape, details)
 
 
-@capi.on_tensor_device
-def evaluate_hota_sequence(node_preds, boxes, frame_num_per_node, ped_ids, label, keep, img_shape, gt, num_timesteps, mask_threshold=0.5,
-                           frames_per_launch=8, class_id=2, ignore_class=10, details=False, assignment="host"):
-    """HOTA (``eval_kitti_mots``, utils/evaluation.py:127-135) of a tracked KITTI-MOTS sequence against the ground truth ``gt``
-    (a MOTS text file, or what ``mots_eval.load_mots_txt`` returns) over the frames ``0 .. num_timesteps - 1``: what
-    ``hota_eval.evaluate_hota_files`` gives for the rows ``save_results_to_file`` writes for the same arguments, without the
-    run-length strings and the text file -- the twin of ``evaluate_mots_sequence``, with the prediction's label images straight
-    from ``masks.paste_unique_masks`` (every kept detection pastes; only those with ``label == class_id`` are scored).
-
-    The arguments as ``evaluate_mots_sequence``, but ``num_timesteps`` frames instead of its ``seq_length + 1``; ``assignment``
-    ('host' or 'device') as ``hota_eval.evaluate_hota_files``.  Returns the dict of ``hota_eval.evaluate_hota_files``."""
-    from . import hota_eval as HE, masks as M
+def _pasted_b_side(node_preds, boxes, frame_num_per_node, ped_ids, label, keep, img_shape, mask_threshold):
+    """The prediction side of ``hota_eval._pass1`` from a tracked sequence's pasted label images: ``b_side(class_id)`` ->
+    (b_frame, b_traj, b_ids, b_labels, img_shape).  Every kept detection pastes; those with ``label == class_id`` are scored."""
+    from . import masks as M
     capi.require_device(node_preds)
     N = int(node_preds.shape[0])
     as_np = lambda v: np.asarray(v.detach().cpu() if isinstance(v, torch.Tensor) else v)
@@ -435,11 +427,46 @@ def evaluate_hota_sequence(node_preds, boxes, frame_num_per_node, ped_ids, label
     ids = ped[kept] + lab[kept] * 1000 + 1
     if np.unique(np.stack((frame_h[kept], ids)), axis=1).shape[1] != kept.size:
         raise ValueError("Multiple objects with one track id in a frame")
-    scored = lab[kept] == class_id
-    traj_ids = np.unique(ids[scored])
-    b_traj = np.where(scored, np.searchsorted(traj_ids, ids), -1).astype(np.int64)
 
-    def b_labels(frames, b_ptr, b_entries, hw):
-        return M.paste_unique_masks(node_preds, boxes, b_ptr, img_shape, mask_threshold, det_ids=kept[b_entries])
-    return HE._evaluate(HE._as_loaded(gt), num_timesteps, class_id, ignore_class, frames_per_launch, node_preds.device, frame_h[kept],
+    def b_side(class_id):
+        scored = lab[kept] == class_id
+        traj_ids = np.unique(ids[scored])
+        b_traj = np.where(scored, np.searchsorted(traj_ids, ids), -1).astype(np.int64)
+
+        def b_labels(frames, b_ptr, b_entries, hw):
+            return M.paste_unique_masks(node_preds, boxes, b_ptr, img_shape, mask_threshold, det_ids=kept[b_entries])
+        return frame_h[kept], b_traj, traj_ids, b_labels, img_shape
+    return b_side
+
+
+@capi.on_tensor_device
+def evaluate_hota_sequence(node_preds, boxes, frame_num_per_node, ped_ids, label, keep, img_shape, gt, num_timesteps, mask_threshold=0.5,
+                           frames_per_launch=8, class_id=2, ignore_class=10, details=False, assignment="host"):
+    """HOTA (``eval_kitti_mots``, utils/evaluation.py:127-135) of a tracked KITTI-MOTS sequence against the ground truth ``gt``
+    (a MOTS text file, or what ``mots_eval.load_mots_txt`` returns) over the frames ``0 .. num_timesteps - 1``: what
+    ``hota_eval.evaluate_hota_files`` gives for the rows ``save_results_to_file`` writes for the same arguments, without the
+    run-length strings and the text file -- the twin of ``evaluate_mots_sequence``, with the prediction's label images straight
+    from ``masks.paste_unique_masks`` (every kept detection pastes; only those with ``label == class_id`` are scored).
+
+    The arguments as ``evaluate_mots_sequence``, but ``num_timesteps`` frames instead of its ``seq_length + 1``; ``assignment``
+    ('host' or 'device') as ``hota_eval.evaluate_hota_files``.  Returns the dict of ``hota_eval.evaluate_hota_files``."""
+    from . import hota_eval as HE
+    b_frame, b_traj, traj_ids, b_labels, _ = _pasted_b_side(node_preds, boxes, frame_num_per_node, ped_ids, label, keep, img_shape,
+                                                            mask_threshold)(class_id)
+    return HE._evaluate(HE._as_loaded(gt), num_timesteps, class_id, ignore_class, frames_per_launch, node_preds.device, b_frame,
                         b_traj, traj_ids, b_labels, img_shape, details, assignment=assignment)
+
+
+@capi.on_tensor_device
+def evaluate_kitti_mots_sequence(node_preds, boxes, frame_num_per_node, ped_ids, label, keep, img_shape, gt, num_timesteps, mask_threshold=0.5,
+                                 frames_per_launch=8, classes=("car", "pedestrian"), metrics=("HOTA", "CLEAR", "Identity"),
+                                 assignment="host"):
+    """HOTA, CLEAR, Identity and Count (``TrackEval/scripts/run_kitti_mots.py``'s defaults) of a tracked KITTI-MOTS sequence
+    against the ground truth ``gt`` for every class of ``classes``: what ``kitti_mots_eval.evaluate_sequence_files`` gives for the
+    rows ``save_results_to_file`` writes for the same arguments, without the run-length strings and the text file -- next to
+    ``evaluate_hota_sequence``, whose arguments it takes; a prediction's class is its ``label`` (1 car, 2 pedestrian).  Returns
+    ``{cls: {metric: fields}}``."""
+    from . import hota_eval as HE, kitti_mots_eval as KE
+    b_side = _pasted_b_side(node_preds, boxes, frame_num_per_node, ped_ids, label, keep, img_shape, mask_threshold)
+    return KE._evaluate_classes(HE._as_loaded(gt), num_timesteps, classes, metrics, frames_per_launch, node_preds.device, b_side, None,
+                                assignment)

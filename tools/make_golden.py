@@ -57,6 +57,12 @@ Fixtures:
                                every twentieth, removals by the ignore region), and HOTA.combine_sequences over the three: every result
                                field, the four counts and per frame the kept prediction ids.  Only with --only g23.
 
+  g24_clear_identity.npz       TrackEval's CLEAR, Identity, Count and HOTA .eval_sequence for the classes car and pedestrian on g22's and
+                               g23's scenes (not stored again) and on "clear" (12 frames of 30 x 40: a row star and a column star decided by
+                               continuity, a frame without predictions, a frame without ground truth, objects matched in exactly 4 of 5
+                               and 1 of 5 frames, a car with an absence, an id switch and a removed prediction), and the three combine
+                               methods of every metric: every field per scene and class, the COMBINED_SEQ rows.  Only with --only g24.
+
 Usage:  python tools/make_golden.py [--only g1,g2,...]
 """
 import sys
@@ -1672,6 +1678,171 @@ def gen_g23():
     print("g23 bytes", os.path.getsize(path))
 
 
+# ------------------------------------------------------------------ g24: TrackEval's CLEAR, Identity and Count on KITTI-MOTS
+def _g24_clear():
+    """12 frames of 30 x 40, both classes; the asserts of gen_g24 check that the cases are there.  Lists are in ascending id order,
+    so of two entries the one with the higher id is the LATER one."""
+    F, H, W = 12, 30, 40
+    gt, pr = np.zeros((F, H, W), np.uint16), np.zeros((F, H, W), np.uint16)
+    for f in range(5):
+        _g22_rect(gt, f, 2001, 0, 8, 0, 4)                            # 2001: found by 2012 throughout (5 of 5) ...
+        if f == 2:                                                    # ... and once split into two exact halves: a row star, the
+            _g22_rect(pr, f, 2011, 0, 4, 0, 4)                        # later prediction continues the previous frame's match
+            _g22_rect(pr, f, 2012, 4, 8, 0, 4)
+        else:
+            _g22_rect(pr, f, 2012, 0, 8, 0, 4)
+        _g22_rect(gt, f, 2002, 10, 14, 0, 4)                          # 2002 / 2003: two equal objects; 2013 finds the later one
+        _g22_rect(gt, f, 2003, 14, 18, 0, 4)                          # (5 of 5) ...
+        _g22_rect(pr, f, 2013, 10 if f == 2 else 14, 18, 0, 4)        # ... and is once exactly their union: a column star
+        if f == 4:
+            _g22_rect(pr, f, 2014, 10, 14, 0, 4)                      # 2002 is matched in exactly 1 of 5 frames,
+        _g22_rect(gt, f, 2004, 20, 26, 0, 4)                          # 2004 in exactly 4 of 5 (a fragment)
+        if f != 3:
+            _g22_rect(pr, f, 2015, 21, 27, 0, 4)
+    for f in (5, 6, 7, 8, 9, 11):
+        _g22_rect(gt, f, 2005, 0, 8, 10, 14)                          # 2005: found by 2016; frame 7 has no prediction at all, and in
+    for f in (5, 6, 9):                                               # frame 8 the later half continues the match of frame 6
+        _g22_rect(pr, f, 2016, 0, 8, 10, 14)
+    _g22_rect(pr, 8, 2010, 0, 4, 10, 14)
+    _g22_rect(pr, 8, 2016, 4, 8, 10, 14)
+    _g22_rect(pr, 10, 2016, 0, 8, 10, 14)                             # frame 10 has predictions and no ground truth
+    _g22_rect(pr, 10, 1002, 20, 28, 21, 29)
+    _g22_rect(pr, 11, 2017, 0, 8, 10, 14)                             # an id switch against the match of frame 9
+    for f in range(6):
+        _g22_rect(gt, f, 10000, 0, H, 34, W)                          # the ignore region
+    for f in range(10):                                               # the car: its prediction is absent in frame 4 (and 7) and
+        _g22_rect(gt, f, 1001, 20, 28, 20, 28)                        # comes back under another id
+        if f not in (4, 7):
+            _g22_rect(pr, f, 1001 if f < 4 else 1002, 20, 28, 21, 29)
+    _g22_rect(pr, 1, 1009, 2, 8, 32, 38)                              # a car, four of six columns inside the ignore region: removed
+    return gt, pr, F
+
+
+def gen_g24():
+    """TrackEval's OWN KittiMOTS.get_raw_seq_data / get_preprocessed_seq_data, then CLEAR, Identity, Count and HOTA
+    .eval_sequence and their combine_sequences / combine_classes_class_averaged / combine_classes_det_averaged, for the classes car
+    and pedestrian, on g22's and g23's scenes and one new scene.  The stand-ins are gen_g23's.  Every assignment the metrics
+    solve is also repeated with its cost matrix times 1 + 1e-9 * noise: no recorded field may move, so no result rests on
+    scipy's tie order."""
+    import tempfile
+    for name, t in (("float", float), ("bool", bool), ("int", int)):
+        if not hasattr(np, name):
+            setattr(np, name, t)
+    _install_pycocotools_standin()
+    standin_iou = sys.modules["pycocotools.mask"].iou   # (a frame without ignore rows: see gen_g23)
+    sys.modules["pycocotools.mask"].iou = lambda dt, gt, iscrowd: np.maximum(standin_iou(dt, gt, iscrowd), 0.0)
+    sys.path.insert(0, "/root/reference/TrackEval")
+    import trackeval
+    from trackeval.metrics import clear as clear_module, hota as hota_module, identity as identity_module
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    import mots_metrics_ref as R
+    from scipy.optimize import linear_sum_assignment as real_lsa
+    CLASSES, METRICS = ("car", "pedestrian"), ("HOTA", "CLEAR", "Identity", "Count")
+    metric_objs = {"HOTA": trackeval.metrics.HOTA(), "CLEAR": trackeval.metrics.CLEAR({"PRINT_CONFIG": False}),
+                   "Identity": trackeval.metrics.Identity({"PRINT_CONFIG": False}), "Count": trackeval.metrics.Count()}
+
+    def run(gt, pr, num_timesteps, noise_seed=None):
+        rng = np.random.default_rng(noise_seed)
+        stars = []   # of CLEAR's assignments: (class, 'row' | 'column', the arm with continuity is the later one)
+
+        def lsa(cost):
+            if noise_seed is not None:
+                cost = cost * (1 + 1e-9 * rng.standard_normal(cost.shape))
+            return real_lsa(cost)
+
+        def clear_lsa(cost):   # cost = -score_mat (clear.py:84): every star has exactly one arm with continuity
+            for kind, m in (("row", cost), ("column", cost.T)):
+                for line in m:
+                    arms = np.flatnonzero(line)
+                    if arms.size > 1:
+                        cont = np.flatnonzero(line[arms] < -999)
+                        assert arms.size == 2 and cont.size == 1, (kind, line[arms])
+                        stars.append((cls_now[0], kind, bool(cont[0] == 1)))
+            return lsa(cost)
+        cls_now = [None]
+        hota_module.linear_sum_assignment = identity_module.linear_sum_assignment = lsa
+        clear_module.linear_sum_assignment = clear_lsa
+        ds = trackeval.datasets.KittiMOTS.__new__(trackeval.datasets.KittiMOTS)
+        res = {}
+        try:
+            with tempfile.TemporaryDirectory() as d:
+                os.makedirs(os.path.join(d, "label_02"))
+                os.makedirs(os.path.join(d, "trk", "data"))
+                R.write_txt(os.path.join(d, "label_02", "0000.txt"), R.id_image_rows(gt))
+                R.write_txt(os.path.join(d, "trk", "data", "0000.txt"), R.id_image_rows(pr))
+                ds.config = {"GT_LOC_FORMAT": "{gt_folder}/label_02/{seq}.txt"}
+                ds.gt_fol, ds.tracker_fol, ds.tracker_sub_fol, ds.data_is_zipped = d, d, "data", False
+                ds.seq_lengths = {"0000": num_timesteps}
+                ds.class_name_to_class_id = {"car": "1", "pedestrian": "2", "ignore": "10"}
+                raw = ds.get_raw_seq_data("trk", "0000")
+                for cls in CLASSES:
+                    cls_now[0] = cls
+                    data = ds.get_preprocessed_seq_data(raw, cls)
+                    res[cls] = {m: metric_objs[m].eval_sequence(data) for m in METRICS}
+        finally:
+            hota_module.linear_sum_assignment = identity_module.linear_sum_assignment = clear_module.linear_sum_assignment = real_lsa
+        return res, stars
+
+    def combined(all_res):   # eval.py:93-112
+        comb = {cls: {m: metric_objs[m].combine_sequences({s: r[cls][m] for s, r in all_res.items()}) for m in METRICS} for cls in CLASSES}
+        per_class = dict(comb)
+        comb["cls_comb_cls_av"] = {m: metric_objs[m].combine_classes_class_averaged({c: per_class[c][m] for c in CLASSES}) for m in METRICS}
+        comb["cls_comb_det_av"] = {m: metric_objs[m].combine_classes_det_averaged({c: per_class[c][m] for c in CLASSES}) for m in METRICS}
+        return comb
+
+    def same(x, y, what):
+        for k in x:
+            if isinstance(x[k], dict):
+                same(x[k], y[k], what + (k,))
+            else:
+                assert np.allclose(np.asarray(y[k], np.float64), np.asarray(x[k], np.float64), rtol=1e-9, atol=1e-9), (what, k, x[k], y[k])
+
+    g22, g23 = np.load(os.path.join(GOLD, "g22_mots_metrics.npz")), np.load(os.path.join(GOLD, "g23_hota.npz"))
+    scenes = [(name, g22[name + ":gt"], g22[name + ":pred"], int(g22[name + ":seq_length"]) + 1) for name in ("cases", "crowded")]
+    scenes.append(("association", g23["association:gt"], g23["association:pred"], int(g23["association:num_timesteps"])))
+    scenes.append(("clear",) + _g24_clear())
+    rec, all_res = {}, {}
+    noisy_res = {seed: {} for seed in range(1, 9)}
+    for name, gt, pr, num_timesteps in scenes:
+        res, stars = run(gt, pr, num_timesteps)
+        for seed in noisy_res:
+            noisy_res[seed][name], _ = run(gt, pr, num_timesteps, noise_seed=seed)
+            same(res, noisy_res[seed][name], (name, seed))
+        all_res[name] = res
+        rec[f"{name}:num_timesteps"] = np.int64(num_timesteps)
+        print("g24", name, "stars", stars)
+        for cls in CLASSES:
+            c, i = res[cls]["CLEAR"], res[cls]["Identity"]
+            print("   ", cls, {k: int(c[k]) for k in ("CLR_TP", "CLR_FN", "CLR_FP", "IDSW", "MT", "PT", "ML", "Frag")}, "MOTP_sum %.6f" % c["MOTP_sum"],
+                  {k: int(i[k]) for k in ("IDTP", "IDFN", "IDFP")}, res[cls]["Count"])
+        if name == "clear":
+            rec[f"{name}:gt"], rec[f"{name}:pred"] = gt, pr
+            assert gt.shape == (12, 30, 40)
+            ped = [s[1:] for s in stars if s[0] == "pedestrian"]
+            assert ped.count(("row", True)) == 2 and ped.count(("column", True)) == 1 and len(ped) == 3   # continuity on the later arm
+            c = res["pedestrian"]["CLEAR"]
+            # continuity survives the empty tracker frame 7 (else 2010, the earlier half, would win frame 8: two more IDSW); the one
+            # IDSW is frame 11's, the one Frag 2004's missing frame 3
+            assert (c["CLR_TP"], c["CLR_FN"], c["CLR_FP"], c["IDSW"], c["Frag"]) == (20, 6, 3, 1, 1)
+            assert not pr[7].any() and gt[7].any() and not gt[10].any() and pr[10].any()
+            # 2001, 2003 (5 of 5) and 2005 (5 of 6) are mostly tracked; 2004 (exactly 4 of 5) and 2002 (exactly 1 of 5) partly
+            assert (c["MT"], c["PT"], c["ML"]) == (3, 2, 0)
+            c, n = res["car"]["CLEAR"], res["car"]["Count"]
+            # the car: frames 4 and 7 have no car prediction, so they keep the continuity state (no Frag); 1009 is removed
+            assert (c["CLR_TP"], c["IDSW"], c["Frag"], c["CLR_FP"], c["CLR_FN"]) == (8, 1, 0, 1, 2) and n["Dets"] == 9 and n["IDs"] == 2
+    comb = combined(all_res)
+    for seed, noisy in noisy_res.items():
+        same(comb, combined(noisy), ("combined", seed))
+    for prefix, per_cls in list(all_res.items()) + [("COMBINED_SEQ", comb)]:
+        for cls, per_metric in per_cls.items():
+            for m, fields in per_metric.items():
+                for k, v in fields.items():
+                    rec[f"{prefix}:{cls}:{m}:{k}"] = np.asarray(v, np.float64)
+    path = os.path.join(GOLD, "g24_clear_identity.npz")
+    np.savez_compressed(path, **rec)
+    print("g24 bytes", os.path.getsize(path), "keys", len(rec))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", default="g0,g1,g4,g5,g6,g7,g8,g2,g3,g11,g12,g10,g9")
@@ -1704,6 +1875,7 @@ def main():
     if "g21" in only: gen_g21()
     if "g22" in only: gen_g22()
     if "g23" in only: gen_g23()
+    if "g24" in only: gen_g24()
 
 
 if __name__ == "__main__":
