@@ -1155,6 +1155,67 @@ int mpnhip_lsa_batched(const double* cost, int64_t cells, const int64_t* cell_pt
                        void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Training inputs from a detections file and a ground-truth file: MOTSeqProcessor._assign_gt and _store_gt_masks
+ * (data/seq_processing/seq_processor.py:203-237, :289-393).  Side a = the detections, side b = the ground-truth rows, both lists
+ * grouped by frame (a_ptr / b_ptr [n_frames + 1], device int32, ascending, at most 65535 frames per call); a launch's pairs are
+ * one block of cells in the layout of mpnhip_lsa_batched: frame f owns na_f x nb_f cells at cell_ptr[f] (device int64
+ * [n_frames + 1]), cell [ia * nb_f + ib]; cells is their number (< 2^31).  Per cell the two cost calls write
+ *   iou     (float64) the pair's intersection over union;
+ *   allowed (uint8)   !(iou < min_iou): the pairs the reference does not overwrite with NaN (:223);
+ *   cost    (float64) allowed ? 1 - iou : min(na_f, nb_f) + 1.
+ * Solved with mpnhip_lsa_batched (minimising), a forbidden cell costs more than any complete assignment of allowed ones, so the
+ * allowed pairs of the solution are: among the matchings of allowed pairs one with the most pairs, and among those one of the
+ * smallest total 1 - iou -- what solve_dense(1 - iou) with NaN for the forbidden pairs is taken to return.  A cell that belongs
+ * to no frame (cell_ptr not ascending, a frame whose cells leave the block) gets 0, 0, 0.  Float64 arithmetic, one rounded
+ * operation at a time, no atomics: the same bits on every call (tests/gt_assign_ref.py restates the operators in numpy).  Every
+ * index read from a caller's array is clamped or checked before it is used.  MPNHIP_ERR_UNSUPPORTED for cells >= 2^31.
+ * ------------------------------------------------------------------------------------------- */
+/* a_boxes [n_a, 4] / b_boxes [n_b, 4] (float64: top, left, bottom, right).  iou = utils/iou.py:4-31: the extents of the
+ * intersection and of both boxes with + 1, inter / (area_a + area_b - inter); NaN where numpy's is (allowed, cost NaN: the
+ * solver then reports status 1 for the frame). */
+int mpnhip_box_iou_costs(const double* a_boxes, int64_t n_a, const double* b_boxes, int64_t n_b, const int32_t* a_ptr,
+                         const int32_t* b_ptr, const int64_t* cell_ptr, int64_t n_frames, int64_t cells, double min_iou, double* iou,
+                         unsigned char* allowed, double* cost, void* stream);
+/* The same from the table of mpnhip_label_overlap(labels of the detections, labels of the ground truth) -- masks that are
+ * disjoint within a side of a frame: with i = cell, A = row sum, B = column sum, u = A + B - i, iou = double(i) / double(u)
+ * (pycocotools' iou with iscrowd = False, utils/iou.py:62-76).  A pair with u = 0 has iou 0 and is not allowed. */
+int mpnhip_overlap_iou_costs(const int32_t* table, int64_t table_cells, const int64_t* table_ptr, const int32_t* a_ptr, int64_t n_a,
+                             const int32_t* b_ptr, int64_t n_b, const int64_t* cell_ptr, int64_t n_frames, int64_t cells,
+                             double min_iou, double* iou, unsigned char* allowed, double* cost, void* stream);
+/* seq_processor.py:226-234 from the solver's match_b [n_a] (the b-entry of every a-entry, or -1): a pair counts when both are
+ * entries of one frame and its cell is allowed.  gt_ids [n_b] (int64): the id column; gt_row [n_b] / det_row [n_a] (int32; NULL =
+ * identity): the row of either file an entry stands for.  Per a-entry, at row o = det_row[a] of the two results [n_out] (skipped
+ * when o is outside): det_gt_entry (int32) = gt_row of its b-entry or -1, det_id (int64) = that entry's id or -1 (a false
+ * positive). */
+int mpnhip_gt_assign_finish(const int32_t* match_b, const unsigned char* allowed, int64_t cells, const int64_t* cell_ptr,
+                            const int32_t* a_ptr, int64_t n_a, const int32_t* b_ptr, int64_t n_b, int64_t n_frames,
+                            const int64_t* gt_ids, const int32_t* gt_row, const int32_t* det_row, int64_t n_out, int32_t* det_gt_entry,
+                            int64_t* det_id, void* stream);
+/* largest number of samples per output pixel and axis mpnhip_roi_align_labels takes: a box of up to 256 * ph x 256 * pw pixels */
+#define MPNHIP_ROI_MAX_GRID 256
+/* torchvision 0.6.0's roi_align(input [K, 1, H, W], rois, (ph, pw), spatial_scale = 1, sampling_ratio = -1, aligned = False) on
+ * the CPU in float32 (seq_processor.py:344-355), where input[k] = "the pixel belongs to the ground-truth mask detection k was
+ * assigned" is never materialised: labels [n_frames, img_w, img_h] (int32, position x * img_h + y) is the ground truth's label
+ * image of mpnhip_paint_label_runs, one per frame for all its detections.  The n_dets detections of the launch are a list
+ * grouped by frame (det_ptr [n_frames + 1]) with boxes [n_dets, 4] (float32: left, top, right, bottom) and det_row [n_dets]
+ * (int32; NULL = identity), their row o of det_gt_entry (int32), masks ([n_out, ph, pw] float32) and valid ([n_out] uint8); a
+ * row outside [0, n_out) is skipped.  e = det_gt_entry[o] is a row of the ground-truth file (n_gt rows): gt_ids [n_gt] (int64)
+ * its id, gt_label [n_gt] (int32) the label its pixels have in this launch, which must be an entry of the detection's frame in
+ * gt_ptr [n_frames + 1].
+ *   valid = e in [0, n_gt), the label in the frame's range, and the id none of ignore_ids [n_ignore] (int64; :329).  Where it is
+ *   0 the row of masks is 0, and so it is for a box that is not finite or needs more than MPNHIP_ROI_MAX_GRID samples per axis.
+ *   Else, in float32 and unfused: roi = max(x2 - x1, 1), bin = roi / p, grid = ceil(roi / p) per axis; sample (iy, ix) of pixel
+ *   (py, px) lies at start + p * bin + (i + 0.5) * bin / grid; outside [-1, size] it adds 0, else it is clamped at 0, low =
+ *   int(v), at low >= size - 1: low = high = size - 1 and v = low; l = v - low, h = 1 - l; it adds hy hx t(ylow, xlow) +
+ *   hy lx t(ylow, xhigh) + ly hx t(yhigh, xlow) + ly lx t(yhigh, xhigh), t = 1 where the label is the detection's.  Samples are
+ *   added in (iy, ix) order and the sum is divided by max(grid_h * grid_w, 1).
+ * One block per detection, no atomics: the same bits on every call, and those of tests/gt_assign_ref.py in float32. */
+int mpnhip_roi_align_labels(const int32_t* labels, int64_t n_frames, int img_h, int img_w, const int32_t* det_ptr, const int32_t* gt_ptr,
+                            const float* boxes, int64_t n_dets, const int32_t* det_row, const int32_t* det_gt_entry, int64_t n_out,
+                            const int32_t* gt_label, const int64_t* gt_ids, int64_t n_gt, const int64_t* ignore_ids, int n_ignore,
+                            int ph, int pw, float* masks, unsigned char* valid, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Measurement helpers used by bench.py (HIP events on the launch stream; these synchronise).
  * ------------------------------------------------------------------------------------------- */
 /* In-stream kernel timing of the real hot path: while enabled, mpnhip_forward brackets (a) the first-layer

@@ -273,6 +273,10 @@ SIGNATURES = {
     "mpnhip_clear_track_summary": (_I, [_P, _P, _P, _L, _P, _P]),
     "mpnhip_lsa_workspace_bytes": (_Z, [_L, _L, _L]),
     "mpnhip_lsa_batched": (_I, [_P, _L, _P, _P, _L, _P, _L, _L, _P, _P, _I, _P, _P, _P, _P, _Z, _P]),
+    "mpnhip_box_iou_costs": (_I, [_P, _L, _P, _L, _P, _P, _P, _L, _L, C.c_double, _P, _P, _P, _P]),
+    "mpnhip_overlap_iou_costs": (_I, [_P, _L, _P, _P, _L, _P, _L, _P, _L, _L, C.c_double, _P, _P, _P, _P]),
+    "mpnhip_gt_assign_finish": (_I, [_P, _P, _L, _P, _P, _L, _P, _L, _L, _P, _P, _P, _L, _P, _P, _P]),
+    "mpnhip_roi_align_labels": (_I, [_P, _L, _I, _I, _P, _P, _P, _L, _P, _P, _L, _P, _P, _L, _P, _I, _I, _I, _P, _P, _P]),
     "mpnhip_profile_enable": (_I, [_I]),
     "mpnhip_edge_chain_active": (_I, [C.POINTER(Model)]),
     "mpnhip_profile_read": (_I, [C.POINTER(C.c_float), C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(C.c_int),

@@ -51,25 +51,36 @@ def load_mots_txt(path):
                 raise ValueError("Unknown object class %d" % ci)
             if h < 0 or w < 0 or (counts.size and counts.min() < 0) or int(counts.sum()) != h * w:
                 raise ValueError("the counts of track id %d in frame %d do not describe a %d x %d mask" % (ti, fr, h, w))
-            edges = np.cumsum(counts)
-            b, e = edges[0::2][:edges.size // 2], edges[1::2]
-            keep = e > b
-            rr.append(np.full(int(keep.sum()), len(frame), np.int64))
-            rb.append(b[keep])
-            re_.append(e[keep])
+            b, e = counts_to_runs(counts)
+            rr.append(np.full(b.size, len(frame), np.int64))
+            rb.append(b)
+            re_.append(e)
             frame.append(fr); tid.append(ti); cls.append(ci); hs.append(h); ws.append(w)
     cat = lambda parts: np.concatenate(parts).astype(np.int64) if parts else np.zeros(0, np.int64)
     out = {"frame": np.asarray(frame, np.int64), "track_id": np.asarray(tid, np.int64), "class_id": np.asarray(cls, np.int64),
            "h": np.asarray(hs, np.int64), "w": np.asarray(ws, np.int64), "run_row": cat(rr), "run_begin": cat(rb), "run_end": cat(re_)}
     out["area"] = np.bincount(out["run_row"], weights=out["run_end"] - out["run_begin"], minlength=len(frame)).astype(np.int64)
-    # overlapping masks: sort the frame's runs by their begin; two neighbours overlap iff the later begins before the earlier ends
-    run_frame = out["frame"][out["run_row"]]
-    order = np.lexsort((out["run_begin"], run_frame))
-    f_s, b_s, e_s = run_frame[order], out["run_begin"][order], out["run_end"][order]
+    refuse_overlapping_masks(out["frame"], out["run_row"], out["run_begin"], out["run_end"])
+    return out
+
+
+def counts_to_runs(counts):
+    """``(begin, end)`` of the runs of set pixels of COCO's ``counts`` (positions ``x * h + y``), empty runs left out"""
+    edges = np.cumsum(counts)
+    b, e = edges[0::2][:edges.size // 2], edges[1::2]
+    keep = e > b
+    return b[keep], e[keep]
+
+
+def refuse_overlapping_masks(frame, run_row, run_begin, run_end):
+    """``ValueError`` where two masks of one frame share a pixel: sort the frame's runs by their begin; two neighbours overlap iff
+    the later begins before the earlier ends"""
+    run_frame = frame[run_row]
+    order = np.lexsort((run_begin, run_frame))
+    f_s, b_s, e_s = run_frame[order], run_begin[order], run_end[order]
     bad = np.flatnonzero((f_s[1:] == f_s[:-1]) & (b_s[1:] < e_s[:-1]))
     if bad.size:
         raise ValueError("Objects with overlapping masks in frame %d" % int(f_s[bad[0]]))
-    return out
 
 
 # ------------------------------------------------------------------------------------------------ operators (device)
