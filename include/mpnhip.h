@@ -1216,6 +1216,71 @@ int mpnhip_roi_align_labels(const int32_t* labels, int64_t n_frames, int img_h, 
                             int ph, int pw, float* masks, unsigned char* valid, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The inputs of the two embedding CNNs: MOTSeqProcessor._store_embeddings (data/seq_processing/seq_processor.py:395-562) around
+ * its stock modules.  No atomics, no sums in a tree: the same bits on every call, and those of tests/embed_inputs_ref.py.  Every
+ * index read from a caller's array is checked before it is used.
+ * ------------------------------------------------------------------------------------------- */
+/* largest side of a padded crop and of the output of mpnhip_reid_crops */
+#define MPNHIP_CROP_MAX_SIDE 8192
+/* Bytes mpnhip_reid_crops needs for n boxes whose padded crops are at most max_ph x max_pw (both passes' coefficients and the
+ * pad's means, per box).  0 for sizes the call refuses. */
+size_t mpnhip_reid_crops_workspace_bytes(int64_t n, int max_ph, int max_pw, int oh, int ow);
+/* BoundingBoxDataset.__getitem__ (utils/rgb.py:40-69) for n boxes in one launch sequence: the crop, np.pad(mode='mean'),
+ * PIL.Image.resize((ow, oh), BILINEAR), ToTensor, Normalize.
+ *   frames [n_frames, H, W, 3] (uint8, as imread returns them); box_frame [n] (int32) the frame of every box;
+ *   geom [n, 8] (int32) what the reference's expressions give for the box: y0, y1, x0, x1 -- the crop is rows [y0, y1) and
+ *   columns [x0, x1) of the frame -- and pt, pb, pl, pr, the pads above, below, left and right of it; the padded crop has
+ *   ph = pt + (y1 - y0) + pb rows and pw = pl + (x1 - x0) + pr columns, at most max_ph and max_pw (<= MPNHIP_CROP_MAX_SIDE);
+ *   mean_std (HOST, 6 floats): Normalize's mean and std per channel;
+ *   out [n, 3, oh, ow] (float32); out_u8 [n, oh, ow, 3] (uint8; may be NULL): the resized patch before ToTensor.
+ * A box whose frame, crop or pads do not fit (frame outside [0, n_frames), an empty crop or one outside the frame, a negative
+ * pad, a padded side above max_ph / max_pw) gets zeros.
+ *   The pad, never materialised: a padded row above or below the crop holds per column and channel m(sum of that column over
+ *   the crop's rows, rows), m(s, c) = s / c rounded half to even in integer arithmetic (numpy's mean of uint8 and its round());
+ *   then every row, the padded ones included, is continued left and right by m(sum of the row over the crop's columns, columns).
+ *   The resize is Pillow's ImagingResample for 8-bit images, the horizontal pass first, a pass skipped when its size does not
+ *   change.  Per output index xx of an axis in -> out, in float64 and unfused: scale = in / out, filterscale = support =
+ *   max(scale, 1), center = (xx + 0.5) * scale, xmin = max(int(center - support + 0.5), 0), xmax = min(int(center + support +
+ *   0.5), in); tap x of xmax - xmin has w = max(0, 1 - |(x + xmin - center + 0.5) * (1 / filterscale)|), the weights are divided
+ *   by their sum (added in tap order) and each becomes int(0.5 + w * 2^22).  A pixel of a pass is
+ *   clip8((2^21 + sum coef * pixel) >> 22) in int32, stored as uint8 between the passes.
+ *   out = (float(v) / 255f - mean[c]) / std[c] in float32, one rounded operation at a time.
+ * A block takes a box and a band of output rows: the horizontal pass of the input rows the band's vertical taps reach goes to
+ * LDS, the vertical pass reads it there.  MPNHIP_ERR_UNSUPPORTED when not even one output row's input rows fit (60 KiB);
+ * n == 0: a successful no-op. */
+int mpnhip_reid_crops(const unsigned char* frames, int64_t n_frames, int H, int W, const int32_t* geom, const int32_t* box_frame,
+                      int64_t n, int max_ph, int max_pw, int oh, int ow, const float* mean_std, float* out, unsigned char* out_u8,
+                      void* workspace, size_t workspace_bytes, void* stream);
+
+#define MPNHIP_FPN_LEVELS 4
+/* largest output_size * sampling_ratio of mpnhip_fpn_roi_align: the samples of one axis, kept in LDS */
+#define MPNHIP_FPN_MAX_SAMPLES 1024
+/* the four levels of one feature pyramid (a HOST struct): data[l] [n_frames, channels, h[l], w[l]] (float32, device), scale[l]
+ * the level's cells per pixel of the network's image */
+typedef struct mpnhip_fpn_levels {
+    const float* data[MPNHIP_FPN_LEVELS];
+    int h[MPNHIP_FPN_LEVELS];
+    int w[MPNHIP_FPN_LEVELS];
+    float scale[MPNHIP_FPN_LEVELS];
+} mpnhip_fpn_levels;
+/* MultiScaleRoIAlign(['0', '1', '2', '3'], output_size, sampling_ratio) of torchvision 0.6.0 (maskrcnn_fpn.py:108-115,
+ * seq_processor.py:493-495) with the level of every box chosen by the caller: box k = boxes [k, 4] (float32: left, top, right,
+ * bottom in the network's image) is pooled from frame box_frame[k] (int32) of level box_level[k] (int32) into
+ * out [n, channels (+ 1), S, S] (float32), S = output_size; a box whose frame or level is outside gets zeros.
+ *   Per axis, in float32 and unfused, with scale and size the level's: roi_start = v1 * scale, extent = max(v2 * scale -
+ *   roi_start, 1), bin = extent / S, grid = sampling_ratio; sample i of output p lies at (roi_start + p * bin) + ((i + 0.5) * bin)
+ *   / grid; outside [-1, size] it adds 0, else it is clamped at 0, low = int(v), at low >= size - 1: low = high = size - 1 and
+ *   v = low; l = v - low, h = float(1 - double(l)).  A sample adds ((hy hx t(ylow, xlow) + hy lx t(ylow, xhigh)) + ly hx
+ *   t(yhigh, xlow)) + ly lx t(yhigh, xhigh), t the channel's plane; samples are added in (iy, ix) order and the sum is divided
+ *   by float(grid * grid).  The same for every channel.
+ *   detection_id [n] (int32, values in [0, 2^24); may be NULL): when given, channel 0 of out holds float(detection_id[k]) and
+ *   the features follow from channel 1 -- the stored format of seq_processor.py:545-548 without the torch.cat.
+ * n == 0: a successful no-op. */
+int mpnhip_fpn_roi_align(const mpnhip_fpn_levels* levels, int64_t n_frames, int channels, const float* boxes, const int32_t* box_frame,
+                         const int32_t* box_level, int64_t n, int output_size, int sampling_ratio, const int32_t* detection_id,
+                         float* out, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Measurement helpers used by bench.py (HIP events on the launch stream; these synchronise).
  * ------------------------------------------------------------------------------------------- */
 /* In-stream kernel timing of the real hot path: while enabled, mpnhip_forward brackets (a) the first-layer

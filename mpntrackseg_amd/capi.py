@@ -111,6 +111,14 @@ class ConvArgs(C.Structure):
     ]
 
 
+FPN_LEVELS = 4
+
+
+class FpnLevels(C.Structure):
+    """``mpnhip_fpn_levels`` (include/mpnhip.h): the four levels of one feature pyramid."""
+    _fields_ = [("data", C.c_void_p * FPN_LEVELS), ("h", C.c_int * FPN_LEVELS), ("w", C.c_int * FPN_LEVELS), ("scale", C.c_float * FPN_LEVELS)]
+
+
 class DebugEdgeChainFwd(C.Structure):
     """``mpnhip_debug_edge_chain_fwd`` (include/mpnhip.h)."""
     _fields_ = [(n, C.c_void_p) for n in ("P", "e0", "e_prev", "e_new", "msg", "logits", "h1", "hc", "hf", "mask")] + \
@@ -277,6 +285,9 @@ SIGNATURES = {
     "mpnhip_overlap_iou_costs": (_I, [_P, _L, _P, _P, _L, _P, _L, _P, _L, _L, C.c_double, _P, _P, _P, _P]),
     "mpnhip_gt_assign_finish": (_I, [_P, _P, _L, _P, _P, _L, _P, _L, _L, _P, _P, _P, _L, _P, _P, _P]),
     "mpnhip_roi_align_labels": (_I, [_P, _L, _I, _I, _P, _P, _P, _L, _P, _P, _L, _P, _P, _L, _P, _I, _I, _I, _P, _P, _P]),
+    "mpnhip_reid_crops_workspace_bytes": (_Z, [_L, _I, _I, _I, _I]),
+    "mpnhip_reid_crops": (_I, [_P, _L, _I, _I, _P, _P, _L, _I, _I, _I, _I, C.POINTER(C.c_float), _P, _P, _P, _Z, _P]),
+    "mpnhip_fpn_roi_align": (_I, [C.POINTER(FpnLevels), _L, _I, _P, _P, _P, _L, _I, _I, _P, _P, _P]),
     "mpnhip_profile_enable": (_I, [_I]),
     "mpnhip_edge_chain_active": (_I, [C.POINTER(Model)]),
     "mpnhip_profile_read": (_I, [C.POINTER(C.c_float), C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(C.c_int),
