@@ -1281,6 +1281,68 @@ int mpnhip_fpn_roi_align(const mpnhip_fpn_levels* levels, int64_t n_frames, int 
                          float* out, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Training batches: MOTGraphDataset.get_from_frame_and_seq (data/mot_graph_dataset.py:185-234) and the DataLoader's collation
+ * for all graphs of a batch at once.  A batch is n_nodes nodes in graph order (graph g owns the nodes graph_ptr[g] ..
+ * graph_ptr[g + 1]), every node a row of a sequence table that stays on the device.  Which rows, and the random shifts, come
+ * from the host (mpntrackseg_amd/dataset.py).  Node indices are batch-global everywhere.  No float atomics and no sums in a
+ * tree: the same bits on every call -- those of numpy in float64, and in float32 those of mpnhip_edge_features /
+ * mpnhip_pairwise_distance on each graph alone.  kNN pruning, edge labels and the row gathers of x / x_ext / the mask
+ * targets are the existing mpnhip_knn_mask (it ranks per node, so the batch graph is the same problem), mpnhip_edge_labels
+ * and mpnhip_gather_rows over the batch.
+ * ------------------------------------------------------------------------------------------- */
+/* columns of a box table, float64: bb_left, bb_top, bb_right, bb_bot, bb_width, bb_height, feet_x, feet_y */
+#define MPNHIP_BOX_COLS 8
+/* columns an edge attribute can be made of: the five of mpnhip_edge_features, then the embedding distance */
+#define MPNHIP_EDGE_ATTR_COLS 6
+size_t mpnhip_augment_boxes_workspace_bytes(void);
+/* Gather and MOTGraphAugmentor._wiggle_boxes (data/augmentation.py:41-86).
+ *   boxes [n_rows, MPNHIP_BOX_COLS] (float64), frame [n_rows], ids [n_rows] (int64): the table; node_src [n_nodes] (int32) the
+ *   row of every node; graph_ptr_host [n_graphs + 1] (int32, HOST): must start at 0, never descend and end at n_nodes -- it is
+ *   checked here and copied to graph_ptr [n_graphs + 1] (device), which the later calls take; eps [n_nodes, 4] (float64; NULL
+ *   = no augmentation, the rows are copied) the relative shift of the top, bottom, left and right side.
+ *   In float64 and unfused, in the reference's order (:71-80): top += h * e0, bot += h * e1, left += w * e2, right += w * e3 with
+ *   the table's h and w, then h = bot - top, w = right - left.  feet_x / feet_y are NOT touched (the reference's code, against
+ *   its docstring).
+ *   out_boxes [n_nodes, MPNHIP_BOX_COLS] (float64); out_cols [n_nodes, 4] (float32) = bb_height, bb_width, feet_x, feet_y cast
+ *   as .float() casts; out_frame, out_id [n_nodes] (int64); node_graph [n_nodes] (int32).
+ *   min_iou (device double) = min over the nodes of iou_pairs(new box, old box) (utils/iou.py:33-59, the + 1 convention), NaN if
+ *   any is NaN, + inf without eps or without nodes: the caller compares it with min_iou_bb_wiggling (:86).
+ *   bad_rows (device int32) = the nodes whose row lies outside [0, n_rows); they get zeros and id -1.
+ * n_graphs == 0 (then n_nodes must be 0): a successful no-op. */
+int mpnhip_augment_boxes(const double* boxes, const int64_t* frame, const int64_t* ids, int64_t n_rows, const int32_t* node_src,
+                         const int32_t* graph_ptr_host, int64_t n_graphs, const double* eps, int64_t n_nodes, double* out_boxes,
+                         float* out_cols, int64_t* out_frame, int64_t* out_id, int32_t* node_graph, int32_t* graph_ptr,
+                         double* min_iou, int32_t* bad_rows, void* workspace, size_t workspace_bytes, void* stream);
+/* get_time_valid_conn_ixs (utils/graph.py:6-37) inside every graph of the batch: the pairs (i, j), i < j, of ONE graph whose
+ * frames differ and are at most max_frame_dist apart (< 0 = 'max'), by ascending i, then j -- the concatenation of the graphs'
+ * own lists with their node offsets added.  frame_num [n_nodes] (int64); node_graph, graph_ptr: device, as mpnhip_augment_boxes
+ * wrote them.  count / fill as mpnhip_time_valid_conn_count / _fill: two launches and a scan, however many graphs.
+ * n_nodes == 0: a successful no-op that writes nothing. */
+size_t mpnhip_batch_pairs_workspace_bytes(int64_t n_nodes);
+int mpnhip_batch_pairs_count(const int64_t* frame_num, const int32_t* node_graph, const int32_t* graph_ptr, int64_t n_graphs,
+                             int64_t n_nodes, int64_t max_frame_dist, int64_t* offsets, void* workspace, size_t workspace_bytes,
+                             void* stream);
+int mpnhip_batch_pairs_fill(const int64_t* frame_num, const int32_t* node_graph, const int32_t* graph_ptr, int64_t n_graphs,
+                            int64_t n_nodes, int64_t max_frame_dist, const int64_t* offsets, int64_t n_pairs, int64_t* edge_ixs,
+                            void* stream);
+/* compute_edge_feats_dict (utils/graph.py:90-124) with fps [n_graphs] (float32, device) -- float32(frame) / fps is formed per
+ * node with the fps of the node's graph, then subtracted -- and F.pairwise_distance of emb [n_nodes, dim] (row stride ld).
+ * node_cols [n_nodes, 4] = out_cols of mpnhip_augment_boxes.  edge_feats [n_edges, 5], emb_dist [n_edges]. */
+int mpnhip_batch_edge_features(const int64_t* edge_ixs, int64_t n_edges, int64_t n_nodes, const int64_t* frame_num,
+                               const int32_t* node_graph, const float* fps, int64_t n_graphs, const float* node_cols,
+                               const float* emb, int64_t ld, int dim, float eps, float* edge_feats, float* emb_dist, void* stream);
+/* From the kept pairs to the layout of a PyG Batch of reference graphs (data/mot_graph.py:311-312): kept [n_kept] (int32,
+ * ascending; NULL = all, n_kept == n_pairs) selects of pairs [2, n_pairs]; a graph with m kept pairs, the first of them kept
+ * pair number s, owns the edges 2 s .. 2 s + 2 m: its pairs, then its flipped pairs.  attr_cols [n_attr_cols] (HOST, each in
+ * 0 .. MPNHIP_EDGE_ATTR_COLS - 1) names the columns of edge_attr [2 n_kept, n_attr_cols]: 0 .. 4 of edge_feats, 5 = emb_dist;
+ * values are duplicated, not sign-flipped.  edge_index [2, 2 n_kept] (int64), edge_graph [2 n_kept] (int32). */
+size_t mpnhip_batch_edge_layout_workspace_bytes(int64_t n_graphs);
+int mpnhip_batch_edge_layout(const int64_t* pairs, int64_t n_pairs, const int32_t* kept, int64_t n_kept, const int32_t* node_graph,
+                             int64_t n_nodes, int64_t n_graphs, const float* edge_feats, const float* emb_dist,
+                             const int32_t* attr_cols, int n_attr_cols, int64_t* edge_index, float* edge_attr, int32_t* edge_graph,
+                             void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Measurement helpers used by bench.py (HIP events on the launch stream; these synchronise).
  * ------------------------------------------------------------------------------------------- */
 /* In-stream kernel timing of the real hot path: while enabled, mpnhip_forward brackets (a) the first-layer

@@ -288,6 +288,14 @@ SIGNATURES = {
     "mpnhip_reid_crops_workspace_bytes": (_Z, [_L, _I, _I, _I, _I]),
     "mpnhip_reid_crops": (_I, [_P, _L, _I, _I, _P, _P, _L, _I, _I, _I, _I, C.POINTER(C.c_float), _P, _P, _P, _Z, _P]),
     "mpnhip_fpn_roi_align": (_I, [C.POINTER(FpnLevels), _L, _I, _P, _P, _P, _L, _I, _I, _P, _P, _P]),
+    "mpnhip_augment_boxes_workspace_bytes": (_Z, []),
+    "mpnhip_augment_boxes": (_I, [_P, _P, _P, _L, _P, _P, _L, _P, _L, _P, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _P]),
+    "mpnhip_batch_pairs_workspace_bytes": (_Z, [_L]),
+    "mpnhip_batch_pairs_count": (_I, [_P, _P, _P, _L, _L, _L, _P, _P, _Z, _P]),
+    "mpnhip_batch_pairs_fill": (_I, [_P, _P, _P, _L, _L, _L, _P, _L, _P, _P]),
+    "mpnhip_batch_edge_features": (_I, [_P, _L, _L, _P, _P, _P, _L, _P, _P, _L, _I, C.c_float, _P, _P, _P]),
+    "mpnhip_batch_edge_layout_workspace_bytes": (_Z, [_L]),
+    "mpnhip_batch_edge_layout": (_I, [_P, _L, _P, _L, _P, _L, _L, _P, _P, _P, _I, _P, _P, _P, _P, _Z, _P]),
     "mpnhip_profile_enable": (_I, [_I]),
     "mpnhip_edge_chain_active": (_I, [C.POINTER(Model)]),
     "mpnhip_profile_read": (_I, [C.POINTER(C.c_float), C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(C.c_int),
