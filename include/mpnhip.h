@@ -960,6 +960,48 @@ int mpnhip_mask_run_events(const int32_t* labels, int64_t n_frames, int64_t hw, 
                            void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * COCO's compressed run-length strings for a batch of masks: rleToString / rleFrString of the COCO API (common/maskApi.c), as
+ * masks.rle_string, masks.rle_counts and mots_eval.counts_to_runs restate them on the host.  A string holds a mask's counts
+ * (alternating run lengths, zeros first, summing to hw); count i >= 3 is stored as its difference to count i - 2; a value is
+ * written in 5-bit groups, low bits first, as the characters 48 + group + 32 * more.  Integers only (int64, wrapping as numpy's):
+ * the bytes and numbers of the host codec on every call.
+ * ------------------------------------------------------------------------------------------- */
+/* Bytes mpnhip_rle_encode needs for these sizes (no device needed).  0 for sizes the call refuses, and when nothing is needed. */
+size_t mpnhip_rle_encode_workspace_bytes(int64_t n_dets, int64_t n_events);
+/* The strings of n_dets masks from what mpnhip_mask_run_events_count / mpnhip_mask_run_events leave on the device: det_counts
+ * [n_dets] and event_pos [n_events] (int32, sorted by (entry, position); n_events and hw < 2^31).  The counts of entry d are the
+ * differences of (0, its positions ..., hw): det_counts[d] + 1 of them -- the one count hw for an entry without events, a leading 0
+ * for a first position of 0.  bytes [bytes_capacity] (uint8): the strings one behind the other in entry order, no separator;
+ * str_ptr [n_dets + 1] (int64): string d is bytes[str_ptr[d] .. str_ptr[d + 1]).  No host read sizes the output: a value takes at
+ * most 7 characters, and a bytes_capacity below 7 * (n_events + n_dets) is refused before any launch.  Lists that are not those
+ * two calls' own (unsorted positions, counts that do not sum to n_events) give strings of no meaning and no access outside the
+ * buffers. */
+int mpnhip_rle_encode(const int32_t* event_pos, const int32_t* det_counts, int64_t n_dets, int64_t n_events, int64_t hw,
+                      unsigned char* bytes, int64_t bytes_capacity, int64_t* str_ptr, void* workspace, size_t workspace_bytes,
+                      void* stream);
+/* Bytes mpnhip_rle_decode_runs needs for n strings (mpnhip_rle_decode_scan needs none). */
+size_t mpnhip_rle_decode_workspace_bytes(int64_t n);
+/* The runs of set pixels of n strings in two calls, because the caller allocates the result.  bytes [n_bytes] (uint8, n_bytes <
+ * 2^31) and str_ptr [n + 1] (int64) as above (offsets are clamped into the buffer); hw_per_string [n] (int64): the pixels every
+ * string must describe.
+ *   scan: per string n_counts (int32), n_runs (int32: the non-empty runs of set pixels, i.e. the odd counts > 0), area (int64:
+ *         their total length) and status (int32), the refusals of the host path as bits: 1 = a character outside '0' .. 'o',
+ *         2 = truncated (the last character announces another group), 4 = a count of more than 12 groups, 8 = a negative
+ *         count, 16 = the counts do not sum to hw_per_string, or a position leaves [0, 2^31).  With one of 1 / 2 / 4 there are
+ *         no counts to judge and 8 / 16 stay clear.  A string with a status has n_runs = area = 0.  The empty string has no
+ *         counts: status 0 for hw = 0, else 16.
+ *   runs: run_ptr [n + 1] (int64) = exclusive scan of n_runs (the scan's, with status; total_runs = their sum, read by the
+ *         caller); run_row, run_begin, run_end [total_runs] (int32): string, first position and position behind the run, ordered
+ *         by string, then position.  Empty runs are left out, adjacent runs are not merged ([3, 2, 0, 4] gives [3, 5) and
+ *         [5, 9)).  A string with a status writes nothing.
+ * Malformed input of any kind ends in a status, never in an access outside the buffers. */
+int mpnhip_rle_decode_scan(const unsigned char* bytes, int64_t n_bytes, const int64_t* str_ptr, const int64_t* hw_per_string, int64_t n,
+                           int32_t* n_counts, int32_t* n_runs, int64_t* area, int32_t* status, void* stream);
+int mpnhip_rle_decode_runs(const unsigned char* bytes, int64_t n_bytes, const int64_t* str_ptr, const int64_t* hw_per_string, int64_t n,
+                           const int32_t* n_runs, const int32_t* status, int64_t total_runs, int64_t* run_ptr, int32_t* run_row,
+                           int32_t* run_begin, int32_t* run_end, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * The pixel work of the MOTS metrics (sMOTSA, IDF1, ...): compute_mots_metrics (utils/evaluation.py:87-102) =
  * MOTChallengeEvalKit/MOTS/MOTS_metrics.py.  Masks of one MOTS frame are disjoint (mots_common/io.py:57-62), so a frame is one
  * label image per side, as above: [n_frames, img_w, img_h] int32, position p = x * img_h + y, hw = img_h * img_w < 2^31, at most

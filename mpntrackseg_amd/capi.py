@@ -262,6 +262,11 @@ SIGNATURES = {
     "mpnhip_paste_unique_masks": (_I, [_P, _L, _I, _I, _P, _P, _L, _P, _L, _I, _I, C.c_float, _P, _P, _P, _Z, _P]),
     "mpnhip_mask_run_events_count": (_I, [_P, _L, _L, _L, _P, _P, _P, _Z, _P]),
     "mpnhip_mask_run_events": (_I, [_P, _L, _L, _L, _L, _P, _P, _Z, _P]),
+    "mpnhip_rle_encode_workspace_bytes": (_Z, [_L, _L]),
+    "mpnhip_rle_encode": (_I, [_P, _P, _L, _L, _L, _P, _L, _P, _P, _Z, _P]),
+    "mpnhip_rle_decode_workspace_bytes": (_Z, [_L]),
+    "mpnhip_rle_decode_scan": (_I, [_P, _L, _P, _P, _L, _P, _P, _P, _P, _P]),
+    "mpnhip_rle_decode_runs": (_I, [_P, _L, _P, _P, _L, _P, _P, _L, _P, _P, _P, _P, _P, _Z, _P]),
     "mpnhip_mots_workspace_bytes": (_Z, [_L, _L, _L, _L, _L]),
     "mpnhip_paint_label_runs": (_I, [_P, _P, _P, _L, _P, _L, _L, _L, _P, _P, _Z, _P]),
     "mpnhip_label_overlap": (_I, [_P, _P, _P, _L, _P, _L, _P, _P, _L, _L, _P, _L, _P]),

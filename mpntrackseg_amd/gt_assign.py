@@ -65,12 +65,15 @@ class _Rows:
         return np.concatenate(([0], np.cumsum(hi - lo))).astype(np.int64), entries
 
 
-def mask_rows(rows):
+def mask_rows(rows, device=None):
     """The masks of ``rows`` (``frame``, ``img_height``, ``img_width``, ``rle``: COCO's compressed strings) as ``load_mots_txt``
     returns them -- runs of set pixels at positions ``x * h + y`` -- refusing what it refuses: counts that do not describe the
-    image, and overlapping masks in a frame."""
+    image, and overlapping masks in a frame.  ``device``: decode the strings there, all rows in two launches
+    (``masks.rle_decode_batch``), instead of one numpy decode per row: the same dict, the same refusals."""
     frame, hs, ws = _col(rows, "frame", np.int64), _col(rows, "img_height", np.int64), _col(rows, "img_width", np.int64)
     rle = _col(rows, "rle")
+    if device is not None:
+        return _mask_rows_device(frame, hs, ws, rle, device)
     rr, rb, re_ = [], [], []
     for k in range(frame.size):
         s = rle[k]
@@ -88,9 +91,39 @@ def mask_rows(rows):
     return out
 
 
-def _mask_side(rows):
+def _mask_rows_device(frame, hs, ws, rle, device):
+    """``mask_rows`` with the strings decoded on the device.  A string that is not ASCII is the host codec's to refuse: the rows
+    before it are decoded first, since an earlier bad row decides."""
+    strings, foreign = [], None
+    for k in range(frame.size):
+        s = rle[k]
+        if (isinstance(s, bytes) and not s.isascii()) or (not isinstance(s, bytes) and not str(s).isascii()):
+            foreign = k
+            break
+        strings.append(s.decode("ascii") if isinstance(s, bytes) else str(s))
+    n = len(strings)
+    dec = M.rle_decode_batch(strings, hs[:n], ws[:n], device)
+    status = dec["status"]
+    bad = np.flatnonzero((status != 0) | (hs[:n] < 0) | (ws[:n] < 0))
+    if bad.size:
+        k = int(bad[0])
+        text = M.rle_status_error(int(status[k]))
+        if text is not None:
+            raise ValueError(text)
+        raise ValueError("the counts of row %d in frame %d do not describe a %d x %d mask" % (k, frame[k], hs[k], ws[k]))
+    if foreign is not None:
+        s = rle[foreign]
+        M.rle_counts(s.decode("ascii") if isinstance(s, bytes) else str(s))   # raises what the host path raises
+    runs = torch.stack((dec["run_row"], dec["run_begin"], dec["run_end"])).cpu().numpy().astype(np.int64)
+    out = {"frame": frame, "h": hs, "w": ws, "run_row": runs[0], "run_begin": runs[1], "run_end": runs[2],
+           "class_id": np.zeros(frame.size, np.int64), "track_id": np.arange(frame.size, dtype=np.int64)}
+    ME.refuse_overlapping_masks(frame, out["run_row"], out["run_begin"], out["run_end"])
+    return out
+
+
+def _mask_side(rows, strings_device=None):
     """``mots_eval._Side`` over all rows: the same order as ``_Rows`` (a stable sort by frame), plus the runs by entry"""
-    loaded = mask_rows(rows)
+    loaded = mask_rows(rows, strings_device)
     return ME._Side(loaded, np.ones(loaded["frame"].size, bool), ())
 
 
@@ -147,7 +180,13 @@ def overlap_iou_costs(table, table_ptr, a_ptr, b_ptr, min_iou=0.5):
 
 
 # ------------------------------------------------------------------------------------------------ the reference's two steps
-def assign_gt(det, gt, min_iou=0.5, mask_priority=False, frames_per_launch=8, device=None, details=False):
+def _strings_device(strings, dev):
+    if strings not in ("host", "device"):
+        raise MpnhipError("strings must be 'host' or 'device' (%r)" % (strings,))
+    return dev if strings == "device" else None
+
+
+def assign_gt(det, gt, min_iou=0.5, mask_priority=False, frames_per_launch=8, device=None, details=False, strings="host"):
     """``MOTSeqProcessor._assign_gt``.  ``det`` / ``gt``: dict-likes or DataFrames with ``frame`` and the box columns ``bb_top``,
     ``bb_left``, ``bb_bot``, ``bb_right``; ``gt`` also ``id``; with ``mask_priority`` both instead of the boxes ``img_height``,
     ``img_width`` and ``rle`` (masks disjoint within a side of a frame, see the module docstring).  ``min_iou``:
@@ -157,11 +196,14 @@ def assign_gt(det, gt, min_iou=0.5, mask_priority=False, frames_per_launch=8, de
     A frame without ground truth leaves its detections false positives; ground truth in a frame without detections takes no
     part.  ``frames_per_launch`` frames share the launches; the result does not depend on it.  A frame whose problem the solver
     does not take (NaN costs, more than ``assignment.MAX_SIDE`` rows on a side) raises ``MpnhipError`` once all frames are
-    enqueued.  ``details``: also a list with one dict per launch: ``frames``, ``a_ptr``, ``b_ptr``, ``cell_ptr`` (host),
-    ``det_row``, ``gt_row`` (host: the row of every entry) and ``iou``, ``allowed`` (device cells)."""
+    enqueued.  ``strings`` (with ``mask_priority``): 'host' decodes the run-length strings row by row in numpy, 'device' all at once
+    on the device (``mask_rows``); the result is the same.  ``details``: also a list with one dict per launch: ``frames``,
+    ``a_ptr``, ``b_ptr``, ``cell_ptr`` (host), ``det_row``, ``gt_row`` (host: the row of every entry) and ``iou``, ``allowed``
+    (device cells)."""
     lib, dev = capi.load(), _device(device)
     if mask_priority:
-        a_masks, b_masks = _mask_side(det), _mask_side(gt)
+        sdev = _strings_device(strings, dev)
+        a_masks, b_masks = _mask_side(det, sdev), _mask_side(gt, sdev)
         size = ME._image_size(a_masks, b_masks)
         hw = size[0] * size[1] if size else 0
     d_frame, g_frame = _col(det, "frame", np.int64), _col(gt, "frame", np.int64)
@@ -206,13 +248,14 @@ def assign_gt(det, gt, min_iou=0.5, mask_priority=False, frames_per_launch=8, de
     return (det_id, det_gt_entry, launches) if details else (det_id, det_gt_entry)
 
 
-def gt_roi_masks(det, gt, det_gt_entry, size=(56, 56), ignore_ids=IGNORE_IDS, frames_per_launch=8):
+def gt_roi_masks(det, gt, det_gt_entry, size=(56, 56), ignore_ids=IGNORE_IDS, frames_per_launch=8, strings="host"):
     """``MOTSeqProcessor._store_gt_masks`` up to its files.  ``det``: ``frame`` and the box columns ``bb_left``, ``bb_top``,
     ``bb_right``, ``bb_bot`` (used as float32, like the reference's ``.float()``); ``gt``: ``frame``, ``id``, ``img_height``,
     ``img_width``, ``rle`` (masks disjoint within a frame); ``det_gt_entry``: ``assign_gt``'s, on the device.  ``size``:
     ``dataset_params['gt_mask_spatial_size']``.  Returns ``(masks [n_det, 1, size[0], size[1]] float32, valid [n_det] uint8)`` on
     that device: ``roi_align`` of the assigned ground-truth mask over the detection's box, and whether there is one -- a
-    detection without a match, or matched to an id of ``ignore_ids``, has a zero mask and ``valid`` 0."""
+    detection without a match, or matched to an id of ``ignore_ids``, has a zero mask and ``valid`` 0.  ``strings``: as in
+    ``assign_gt``."""
     lib = capi.load()
     capi.require_device(det_gt_entry)
     dev = det_gt_entry.device
@@ -231,7 +274,7 @@ def gt_roi_masks(det, gt, det_gt_entry, size=(56, 56), ignore_ids=IGNORE_IDS, fr
     if too_large.any():
         raise ValueError("the box of detection %d needs more than %d samples per output pixel and axis" % (int(np.flatnonzero(too_large)[0]), MAX_GRID))
     g_id = _col(gt, "id", np.int64)
-    b = _mask_side(gt)
+    b = _mask_side(gt, _strings_device(strings, dev))
     n_gt = b.frame.size
     b_order = np.argsort(_col(gt, "frame", np.int64), kind="stable")   # (the order of b's entries)
     img = ME._image_size(b)

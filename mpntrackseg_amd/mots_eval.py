@@ -25,12 +25,17 @@ CLASS_ID, IGNORE_CLASS = 2, 10   # MOTS_metrics.py:12-13: pedestrians only
 
 
 # ------------------------------------------------------------------------------------------------ text files (host)
-def load_mots_txt(path):
+def load_mots_txt(path, device=None):
     """The rows ``frame id class img_height img_width rle`` of a MOTS text file as arrays, refusing what the kit's ``load_txt``
     (``mots_common/io.py:31-69``) refuses: two rows of one id in a frame, a class other than 1 / 2 / 10, overlapping masks in a
     frame.  Returns a dict: ``frame``, ``track_id``, ``class_id``, ``h``, ``w`` (int64 [n], file order) and the masks as runs of
     set pixels -- ``run_row``, ``run_begin``, ``run_end`` (row of the file and positions ``x * h + y`` in COCO's column-major
-    order; sorted by row, then position) -- and ``area`` [n]."""
+    order; sorted by row, then position) -- and ``area`` [n].
+
+    ``device``: decode the strings there, all rows in two launches (``masks.rle_decode_batch``), instead of one numpy decode per
+    row; the host still splits the lines.  The same dict and the same refusals, with the same text."""
+    if device is not None:
+        return _load_mots_txt_device(path, device)
     frame, tid, cls, hs, ws, rr, rb, re_ = [], [], [], [], [], [], [], []
     seen = set()
     with open(path, "r") as fh:
@@ -60,6 +65,78 @@ def load_mots_txt(path):
     out = {"frame": np.asarray(frame, np.int64), "track_id": np.asarray(tid, np.int64), "class_id": np.asarray(cls, np.int64),
            "h": np.asarray(hs, np.int64), "w": np.asarray(ws, np.int64), "run_row": cat(rr), "run_begin": cat(rb), "run_end": cat(re_)}
     out["area"] = np.bincount(out["run_row"], weights=out["run_end"] - out["run_begin"], minlength=len(frame)).astype(np.int64)
+    refuse_overlapping_masks(out["frame"], out["run_row"], out["run_begin"], out["run_end"])
+    return out
+
+
+def first_refused_row(frame, track_id, class_id, h, w, status):
+    """Which row of a file ``load_mots_txt`` refuses, and why, from the rows' integers and the decoder's status words
+    (``masks.RLE_*``): ``(row, reason)`` of the first bad row in file order, or None.  Inside a row the loader's order: ``'parse'``
+    (a string ``rle_counts`` does not read), ``'duplicate'`` (the id occurred in the frame before), ``'class'`` (not 1 / 2 / 10),
+    ``'counts'`` (a negative size or count, or counts that do not sum to ``h * w``).  Pure host arithmetic."""
+    frame, track_id, class_id, h, w, status = (np.asarray(v, np.int64).reshape(-1) for v in (frame, track_id, class_id, h, w, status))
+    n = frame.size
+    if n == 0:
+        return None
+    parse = (status & M.RLE_UNREADABLE) != 0
+    order = np.lexsort((np.arange(n), track_id, frame))   # the rows of one (frame, id) side by side, in file order
+    same = (frame[order][1:] == frame[order][:-1]) & (track_id[order][1:] == track_id[order][:-1])
+    duplicate = np.zeros(n, bool)
+    duplicate[order[1:][same]] = True
+    unknown = ~np.isin(class_id, (1, 2, 10))
+    counts = (h < 0) | (w < 0) | ((status & (M.RLE_NEGATIVE | M.RLE_BAD_SUM)) != 0)
+    bad = np.flatnonzero(parse | duplicate | unknown | counts)
+    if bad.size == 0:
+        return None
+    r = int(bad[0])
+    return r, ("parse" if parse[r] else "duplicate" if duplicate[r] else "class" if unknown[r] else "counts")
+
+
+def _split_mots_rows(path):
+    """The host's share of the device ``load_mots_txt``: ``(ints [n, 5], strings, lines, unreadable)`` of the rows up to the first
+    one the host alone refuses (fewer than six fields, an integer or a string that is none) -- ``unreadable``: that line, or None"""
+    ints, strings, lines = [], [], []
+    unreadable = None
+    with open(path, "r") as fh:
+        for line in fh:
+            line = line.strip()
+            if not line:
+                continue
+            fields = line.split(" ")
+            try:
+                row = [int(v) for v in fields[:5]]
+                if len(row) < 5 or not fields[5].isascii():
+                    raise ValueError
+            except (ValueError, IndexError):
+                unreadable = line
+                break
+            ints.append(row)
+            strings.append(fields[5])
+            lines.append(line)
+    return np.asarray(ints, np.int64).reshape(-1, 5), strings, lines, unreadable
+
+
+def _load_mots_txt_device(path, device):
+    """``load_mots_txt`` with the strings decoded on the device.  The rows behind a line the host cannot split are not looked
+    at: they cannot be refused before it."""
+    cols, strings, lines, unreadable = _split_mots_rows(path)
+    frame, tid, cls, hs, ws = (np.ascontiguousarray(cols[:, k]) for k in range(5))
+    dec = M.rle_decode_batch(strings, hs, ws, device)
+    refused = first_refused_row(frame, tid, cls, hs, ws, dec["status"])
+    if refused is not None:
+        r, why = refused
+        if why == "parse":
+            raise ValueError("Error in %s in line: %s" % (str(path).split("/")[-1], lines[r]))
+        if why == "duplicate":
+            raise ValueError("Multiple objects with track id %d in frame %d" % (tid[r], frame[r]))
+        if why == "class":
+            raise ValueError("Unknown object class %d" % cls[r])
+        raise ValueError("the counts of track id %d in frame %d do not describe a %d x %d mask" % (tid[r], frame[r], hs[r], ws[r]))
+    if unreadable is not None:
+        raise ValueError("Error in %s in line: %s" % (str(path).split("/")[-1], unreadable))
+    runs = torch.stack((dec["run_row"], dec["run_begin"], dec["run_end"])).cpu().numpy().astype(np.int64)
+    out = {"frame": frame, "track_id": tid, "class_id": cls, "h": hs, "w": ws, "run_row": runs[0], "run_begin": runs[1], "run_end": runs[2],
+           "area": dec["area"].astype(np.int64)}
     refuse_overlapping_masks(out["frame"], out["run_row"], out["run_begin"], out["run_end"])
     return out
 

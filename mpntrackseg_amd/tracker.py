@@ -25,8 +25,8 @@ detections in, track ids out.
 ``to_full_masks`` and ``save_results_to_file`` are the last two steps (``_to_full_masks``, ``:267-298``, and ``save_results_to_file``,
 ``:398-417``): the RoI masks of the surviving detections are pasted into their frames, made disjoint and thresholded on the device
 (``masks.py``, ``csrc/full_masks.hip``: one label per pixel instead of one image per detection), leave it as run boundaries and
-become COCO run-length strings on the host; the text file has the MOTS challenge's rows.  ``mots_sequence`` is ``track_sequence``
-followed by ``to_full_masks``: detections in, MOTS rows out.  What stays in the reference needs a second network or files of its
+become COCO run-length strings on the host (or, with ``strings='device'``, on the device: ``csrc/rle_codec.hip``); the text file
+has the MOTS challenge's rows.  ``mots_sequence`` is ``track_sequence`` followed by ``to_full_masks``: detections in, MOTS rows out.  What stays in the reference needs a second network or files of its
 detector (``_predict_nan_masks``, ``_add_tracktor_detects``), or is commented out there (the trajectory interpolation)."""
 import collections
 import types
@@ -301,7 +301,7 @@ def track_sequence(model, x, edge_index, edge_attr, reid_emb_dists, frame_num_pe
 
 
 @capi.on_tensor_device
-def to_full_masks(node_preds, boxes, frame_num_per_node, keep, img_shape, mask_threshold=0.5, frames_per_launch=8):
+def to_full_masks(node_preds, boxes, frame_num_per_node, keep, img_shape, mask_threshold=0.5, frames_per_launch=8, strings='host'):
     """``MPNTracker._to_full_masks`` (mpn_tracker.py:267-298): an object array [N] with the COCO run-length string of every kept
     detection's full-frame mask (``None`` for the dropped ones).  Per frame: ``paste_masks_in_image`` of the kept detections' RoI
     masks in node order, ``ensure_unique_masks``, ``>= mask_threshold``, ``rletools.encode`` -- see ``masks.py``.
@@ -309,8 +309,14 @@ def to_full_masks(node_preds, boxes, frame_num_per_node, keep, img_shape, mask_t
     ``node_preds`` [N, 1, mh, mw] (device), ``boxes`` [N, 4] (left, top, right, bottom), ``frame_num_per_node`` [N], ``keep`` [N]
     bool, ``img_shape`` = (H, W).  The kept detections are grouped by frame with a stable sort (the identity for frame-ordered
     nodes) and ``frames_per_launch`` frames share a launch: the label workspace is 4 B x H x W x frames_per_launch, and the result
-    does not depend on it.  Host reads: ``keep`` once, then per launch the number of run boundaries and the boundaries."""
+    does not depend on it.  Host reads: ``keep`` once, then per launch the number of run boundaries and the boundaries.
+
+    ``strings``: 'host' turns the boundaries into strings one detection at a time in numpy (``masks.rle_string``); 'device' encodes
+    all strings of a launch on the device (``masks.mask_run_strings``) and reads the finished bytes instead of the boundaries.
+    The strings are the same."""
     from . import masks as M
+    if strings not in ('host', 'device'):
+        raise MpnhipError("strings must be 'host' or 'device' (%r)" % (strings,))
     capi.require_device(node_preds)
     N = int(node_preds.shape[0])
     H, W = int(img_shape[0]), int(img_shape[1])
@@ -330,6 +336,10 @@ def to_full_masks(node_preds, boxes, frame_num_per_node, keep, img_shape, mask_t
         ids = kept[first[g0]:first[g0] + int(cnt.sum())]
         frame_ptr = np.concatenate(([0], np.cumsum(cnt)))
         labels = M.paste_unique_masks(node_preds, boxes, frame_ptr, (H, W), mask_threshold, det_ids=ids)
+        if strings == 'device':
+            for node, s in zip(ids, M.rle_strings(*M.mask_run_strings(labels, ids.size))):
+                out[node] = s
+            continue
         pos, counts = M.mask_run_events(labels, ids.size)
         ends = np.cumsum(counts)
         for j, node in enumerate(ids):
@@ -362,14 +372,15 @@ def save_results_to_file(path, frame, ped_ids, label, img_shape, rles, keep):
 
 @capi.on_tensor_device
 def mots_sequence(model, x, edge_index, edge_attr, reid_emb_dists, frame_num_per_node, frames_per_graph, top_k_nns, x_ext, boxes,
-                  img_shape, mask_threshold=0.5, frames_per_launch=8, **track_args):
-    """``track_sequence`` (``track_args``: its remaining keyword arguments), then ``to_full_masks``: ``(TrackResult, rles)``."""
+                  img_shape, mask_threshold=0.5, frames_per_launch=8, strings='host', **track_args):
+    """``track_sequence`` (``track_args``: its remaining keyword arguments), then ``to_full_masks`` (``strings``: its argument):
+    ``(TrackResult, rles)``."""
     res = track_sequence(model, x, edge_index, edge_attr, reid_emb_dists, frame_num_per_node, frames_per_graph, top_k_nns, x_ext=x_ext,
                          **track_args)
     if res.node_preds is None:
         raise MpnhipError("mots_sequence needs the mask branch: a model with one and the RoI features x_ext")
     rles = to_full_masks(res.node_preds, boxes, frame_num_per_node, res.keep, img_shape, mask_threshold=mask_threshold,
-                         frames_per_launch=frames_per_launch)
+                         frames_per_launch=frames_per_launch, strings=strings)
     return res, rles
 
 
