@@ -628,6 +628,16 @@ int mpnhip_tracking_loss_graphs(const float* logits, const float* labels, const 
 int mpnhip_step_metrics(const void* graph_buf, int n_nodes, int64_t n_edges, const float* logits, const float* labels,
                         int32_t* counts, void* stream);
 
+/* The same eight counts for each graph of ONE block-diagonal batch (a batch is n_graphs reference steps executed in space, so
+ * validation_epoch_end's means need them graph by graph): counts [n_graphs, 8] int32, row g = {TP, FP, TN, FN, viol_out, viol_in,
+ * constr_out, constr_in} as above, over the edges with edge_graph[e] == g and the nodes with node_graph[n] == g (int32, edge_index /
+ * node order).  n_graphs in [1, 1024]; with n_graphs == 1 both id arrays may be NULL (every edge and node is graph 0).  An id outside
+ * [0, n_graphs) is counted nowhere and writes nowhere; labels other than 0 / 1 fall in no confusion cell.  Integer counts: exact and
+ * independent of the order.  No workspace, nothing read back. */
+int mpnhip_step_metrics_graphs(const void* graph_buf, int n_nodes, int64_t n_edges, const float* logits, const float* labels,
+                               const int32_t* edge_graph, const int32_t* node_graph, int n_graphs, int32_t* counts /* [n_graphs, 8] */,
+                               void* stream);
+
 /* MOTGraph.assign_edge_labels (data/mot_graph.py:223-262): labels [E] float32 in {0, 1} from edge_index (int64 [2, E]) and the
  * track id of every node (ids, int64 [N]; -1 = no track).  same_id = ids[row] == ids[col] && ids[row] != -1.
  *   MPNHIP_LABELS_ALL:      label = same_id;

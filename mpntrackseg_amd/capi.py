@@ -209,6 +209,7 @@ SIGNATURES = {
     "mpnhip_tracking_loss_graphs_workspace_bytes": (_Z, [_I, _L, _I]),
     "mpnhip_tracking_loss_graphs": (_I, [_P, _P, _P, _I, _I, _L, _I, C.c_float, _P, _P, _P, _Z, _P]),
     "mpnhip_step_metrics": (_I, [_P, _I, _L, _P, _P, _P, _P]),
+    "mpnhip_step_metrics_graphs": (_I, [_P, _I, _L, _P, _P, _P, _P, _I, _P, _P]),
     "mpnhip_edge_labels_workspace_bytes": (_Z, [_L]),
     "mpnhip_edge_labels": (_I, [_P, _L, _P, _L, _I, _P, _P, _P, _Z, _P]),
     "mpnhip_mask_loss_workspace_bytes": (_Z, [_I, _L, _L, _I]),

@@ -185,6 +185,74 @@ __global__ void k_flow_constraints(GraphView g, const float* __restrict__ logits
     if (c_in > 0) atomicAdd(out + 7, 1);
 }
 
+// ---- the same eight counts per graph of a block-diagonal batch: counts [K][8], K <= 1024 ------------------------------------------
+// Each block keeps a table of K x 4 ints in LDS (16 KB at K = 1024: four blocks of 256 threads still fit a CU's LDS), adds into it
+// with LDS atomics, and flushes its non-zero cells with one global atomic each: the edges (nodes) of one graph are neighbours in a
+// block-diagonal batch, so a block touches a handful of graphs -- one global atomic per edge would queue every edge of a graph on
+// the same four addresses.  Integer counts: exact, independent of the order.  `ids` == nullptr (K = 1): everything is graph 0.
+// An id outside [0, K) is counted nowhere and indexes nothing.
+__device__ __forceinline__ void graph_cells_zero(int* sc, int K) {
+    for (int i = threadIdx.x; i < 4 * K; i += 256) sc[i] = 0;
+    __syncthreads();
+}
+// cell c of graph g goes to counts[8 g + col0 + c]
+__device__ __forceinline__ void graph_cells_flush(const int* sc, int K, int col0, int* __restrict__ counts) {
+    __syncthreads();
+    for (int j = threadIdx.x; j < 4 * K; j += 256)
+        if (sc[j]) atomicAdd(&counts[8 * (j >> 2) + col0 + (j & 3)], sc[j]);
+}
+
+__global__ __launch_bounds__(256) void k_confusion_graphs(const float* __restrict__ logits, const float* __restrict__ labels,
+                                                          const int* __restrict__ edge_graph, int64_t E, int K, int* __restrict__ counts) {
+    extern __shared__ int sc[];   // [K][4]: TP, FP, TN, FN
+    graph_cells_zero(sc, K);
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < E) {
+        const int g = edge_graph ? edge_graph[i] : 0;
+        if (g >= 0 && g < K) {
+            const int pred = logits[i] > 0.f, y = labels[i] == 1.f, y0 = labels[i] == 0.f;
+            if (y && pred) atomicAdd(&sc[4 * g + 0], 1);
+            else if (y0 && pred) atomicAdd(&sc[4 * g + 1], 1);
+            else if (y0 && !pred) atomicAdd(&sc[4 * g + 2], 1);
+            else if (y && !pred) atomicAdd(&sc[4 * g + 3], 1);
+        }
+    }
+    graph_cells_flush(sc, K, 0, counts);
+}
+
+// k_flow_constraints' node terms, booked on the node's graph
+__global__ __launch_bounds__(256) void k_flow_constraints_graphs(GraphView g, const float* __restrict__ logits, const int* __restrict__ node_graph,
+                                                                 int K, int* __restrict__ counts) {
+    extern __shared__ int sc[];   // [K][4]: viol_out, viol_in, constr_out, constr_in
+    graph_cells_zero(sc, K);
+    const int n = blockIdx.x * 256 + threadIdx.x;
+    const int N = g.N;
+    const int gr = n < N ? (node_graph ? node_graph[n] : 0) : -1;
+    if (gr >= 0 && gr < K) {
+        auto seg_sum = [&](const int* ptr, const int* list, int key, int& cnt) {
+            float s = 0.f;
+            const int b = ptr[key], e = ptr[key + 1];
+            for (int j = b; j < e; ++j) {
+                const int pos = list ? list[j] : j;
+                s += logits[g.perm[pos]] > 0.f ? 1.f : 0.f;
+            }
+            cnt += e - b;
+            return s;
+        };
+        int c_out = 0, c_in = 0, c_self = 0;
+        const float self_cnt = seg_sum(g.seg_ptr, nullptr, 2 * N + n, c_self);
+        const float f_out = (seg_sum(g.seg_ptr, nullptr, n, c_out) + seg_sum(g.cseg_ptr, g.cperm, N + n, c_out) + self_cnt) * 0.5f;
+        const float f_in = (seg_sum(g.seg_ptr, nullptr, N + n, c_in) + seg_sum(g.cseg_ptr, g.cperm, n, c_in) + self_cnt) * 0.5f;
+        c_out += c_self;
+        c_in += c_self;
+        if (f_out > 1.f) atomicAdd(&sc[4 * gr + 0], 1);
+        if (f_in > 1.f) atomicAdd(&sc[4 * gr + 1], 1);
+        if (c_out > 0) atomicAdd(&sc[4 * gr + 2], 1);
+        if (c_in > 0) atomicAdd(&sc[4 * gr + 3], 1);
+    }
+    graph_cells_flush(sc, K, 4, counts);
+}
+
 // the tracking loss' workspace: a 256-byte head (the positive count), the blocks' partial sums [steps][blocks], and for the
 // per-graph form (per_graph) the graphs' {edges, positives} counts behind them
 struct LossView { float* pos; float* partial; int* counts; size_t bytes; };
@@ -271,6 +339,28 @@ extern "C" int mpnhip_step_metrics(const void* graph_buf, int n_nodes, int64_t n
     MPN_LAUNCH_CHECK();
     hipLaunchKernelGGL(k_flow_constraints, dim3((n_nodes + 255) / 256), dim3(256), 0, s, g, logits, counts);
     MPN_LAUNCH_CHECK();
+    return MPNHIP_OK;
+}
+
+extern "C" int mpnhip_step_metrics_graphs(const void* graph_buf, int n_nodes, int64_t n_edges, const float* logits, const float* labels,
+                                          const int32_t* edge_graph, const int32_t* node_graph, int n_graphs, int32_t* counts,
+                                          void* stream_) {
+    hipStream_t s = static_cast<hipStream_t>(stream_);
+    MPN_CHECK_ARG(n_graphs >= 1 && n_graphs <= 1024 && n_nodes >= 0 && n_edges >= 0, "step_metrics_graphs: bad sizes");
+    MPN_CHECK_ARG(graph_buf && counts, "step_metrics_graphs: null pointer");
+    MPN_CHECK_ARG(n_graphs == 1 || (edge_graph && node_graph), "step_metrics_graphs: more than one graph needs edge_graph and node_graph");
+    MPN_HIP(hipMemsetAsync(counts, 0, (size_t)8 * n_graphs * sizeof(int32_t), s));
+    if (n_edges == 0) return MPNHIP_OK;
+    MPN_CHECK_ARG(logits && labels, "step_metrics_graphs: null tensor");
+    GraphView g;
+    graph_layout(n_nodes, n_edges, &g, const_cast<void*>(graph_buf));
+    const size_t lds = (size_t)4 * n_graphs * sizeof(int);
+    hipLaunchKernelGGL(k_confusion_graphs, dim3(blocks_for(n_edges)), dim3(256), lds, s, logits, labels, edge_graph, n_edges, n_graphs, counts);
+    MPN_LAUNCH_CHECK();
+    if (n_nodes > 0) {
+        hipLaunchKernelGGL(k_flow_constraints_graphs, dim3((n_nodes + 255) / 256), dim3(256), lds, s, g, logits, node_graph, n_graphs, counts);
+        MPN_LAUNCH_CHECK();
+    }
     return MPNHIP_OK;
 }
 

@@ -187,3 +187,56 @@ def compute_perform_metrics(graph_out, graph_obj):
             "recall": tp / (tp + fn) if tp + fn > 0 else 0.0,
             "precision": tp / (tp + fp) if tp + fp > 0 else 0.0,
             "constr_sr": 1.0 - (vo + vi) / (co + ci) if co + ci > 0 else float("nan")}
+
+
+METRIC_COUNT_NAMES = ("tp", "fp", "tn", "fn", "viol_out", "viol_in", "constr_out", "constr_in")
+
+
+def step_metric_counts(logits_last, edge_labels, edge_index, num_nodes, edge_graph=None, node_graph=None, n_graphs=1, holder=None,
+                       out=None):
+    """The eight counts of ``compute_perform_metrics`` for each graph of a block-diagonal batch (``mpnhip_step_metrics_graphs``):
+    device int32 [n_graphs, 8], rows ``METRIC_COUNT_NAMES``, no host read.  ``logits_last`` [E] is the last step's logits;
+    ``edge_graph`` [E] / ``node_graph`` [N] (int32) may be left out for one graph.  ``out``: an int32 [n_graphs, 8] device buffer to
+    fill (a row block of ``train.EpochLog``).  ``metrics_from_counts`` turns the counts into the ratios, on the host."""
+    from .mpn import _prepared
+    capi.require_device(logits_last, edge_labels, edge_index, edge_graph, node_graph)
+    lib = capi.load()
+    lg = capi.f32c(logits_last.detach()).view(-1)
+    y = capi.f32c(edge_labels).view(-1)
+    k = int(n_graphs)
+    g = _prepared(edge_index, int(num_nodes), holder)
+    if lg.numel() != g.E or y.numel() != g.E:
+        raise capi.MpnhipError("step_metric_counts: %d logits and %d labels for %d edges" % (lg.numel(), y.numel(), g.E))
+    eg = ng = None
+    if edge_graph is not None:
+        eg = edge_graph.to(torch.int32).contiguous().view(-1)
+        if eg.numel() != g.E:
+            raise capi.MpnhipError("edge_graph must name the graph of each of the %d edges" % g.E)
+    if node_graph is not None:
+        ng = node_graph.to(torch.int32).contiguous().view(-1)
+        if ng.numel() != g.N:
+            raise capi.MpnhipError("node_graph must name the graph of each of the %d nodes" % g.N)
+    if out is None:
+        out = torch.empty((max(k, 1), 8), dtype=torch.int32, device=lg.device)
+    elif out.dtype != torch.int32 or not out.is_contiguous() or out.numel() != 8 * k or out.device != lg.device:
+        raise capi.MpnhipError("step_metric_counts: out must be a contiguous int32 [%d, 8] tensor on %s" % (k, lg.device))
+    with torch.cuda.device(lg.device):
+        capi.check(lib.mpnhip_step_metrics_graphs(capi.ptr(g.buf), g.N, g.E, capi.ptr(lg), capi.ptr(y), capi.ptr(eg), capi.ptr(ng), k,
+                                                  capi.ptr(out), capi.stream_ptr()), "mpnhip_step_metrics_graphs")
+    return out
+
+
+def metrics_from_counts(counts):
+    """Per-graph ``{'accuracy', 'recall', 'precision', 'constr_sr'}`` (float64 arrays [n_graphs]) from ``step_metric_counts``' table
+    with ``compute_perform_metrics``' formulas: accuracy and constr_sr are NaN without edges / constraints, recall and precision
+    0.0 without positives.  Runs on the host (a device tensor is read here, once)."""
+    import numpy as np
+    c = counts.detach().cpu().numpy() if isinstance(counts, torch.Tensor) else np.asarray(counts)
+    c = c.reshape(-1, 8).astype(np.float64)
+    tp, fp, tn, fn, vo, vi, co, ci = (c[:, i] for i in range(8))
+    tot = tp + fp + tn + fn
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return {"accuracy": np.where(tot > 0, (tp + tn) / tot, np.nan),
+                "recall": np.where(tp + fn > 0, tp / (tp + fn), 0.0),
+                "precision": np.where(tp + fp > 0, tp / (tp + fp), 0.0),
+                "constr_sr": np.where(co + ci > 0, 1.0 - (vo + vi) / (co + ci), np.nan)}
