@@ -714,6 +714,41 @@ typedef struct mpnhip_conv_args {
 } mpnhip_conv_args;
 int mpnhip_conv2d_forward(const mpnhip_conv_args* args, void* stream);
 
+/* Mask branch, training: the backward of ONE nn.Conv2d(cin, cout, ksize, stride 1, padding ksize / 2), ksize 1 or 3, with the
+ * ReLU that mpnhip_conv2d_forward fuses behind it (relu != 0).  Exact fp32 products, fp32 accumulation, no float atomics: every
+ * sum has a fixed order that depends on the layer and on n_images alone, so two calls on the same inputs agree bit for bit.
+ *
+ * Inputs: the segment list of the forward (the layer's input), weight [cout][cin][ksize][ksize], the layer's output y (image i at
+ * y + i * y_stride, dense [cout][H][W]; read only when relu != 0) and grad_out (image i at grad_out + i * grad_out_stride,
+ * dense [cout][H][W]).  Outputs, each may be NULL ("not needed") and each is OVERWRITTEN, never accumulated into:
+ *   grad_in     [n_images][cin][H][W], dense: the gradient of the channel concatenation; segment s owns the channel slice behind
+ *               the channels of segments 0 .. s - 1.
+ *   grad_weight [cout][cin][ksize][ksize]
+ *   grad_bias   [cout]
+ *
+ *   g = grad_out * [y > 0] (relu; torch's ReLU backward: nothing at y == 0), else g = grad_out.  A pre-pass writes g once into the
+ *       workspace and sums it per (block of 8 images, channel); grad_bias adds those partial sums in block order.
+ *   grad_in = conv2d(g, W') with W'[c][m][ky][kx] = W[m][c][k-1-ky][k-1-kx], built in the workspace, through
+ *       mpnhip_conv2d_forward itself (its small-cout kernel when cin <= 8): an image's bits do not depend on the batch.
+ *       Skipped when grad_in is NULL.
+ *   grad_weight[m][c][tap] = sum over images and pixels of g[m][n][p] * x[c][n][p + tap offset]: one block per (<= 128 rows of
+ *       cout, 32 input channels, 8 images) on v_mfma_f32_32x32x2_f32 with the pixel as k, partial sums [split][cout][cin * taps]
+ *       in the workspace, added in split order by a second kernel.  cout <= 8: a plain kernel, the same two stages.
+ *
+ * MPNHIP_ERR_ARG before any launch: everything mpnhip_conv2d_forward refuses (with grad_in's image in the place of out),
+ * transposed != 0, relu with a null y, a null grad_out, all three outputs NULL, y_stride / grad_out_stride outside the 32-bit
+ * range, a null workspace or one smaller than mpnhip_conv2d_backward_workspace_bytes(args), more images than one launch holds.
+ * n_images == 0 (checked like any other call) zero-fills grad_weight / grad_bias where given and touches nothing else.
+ * mpnhip_conv2d_backward_workspace_bytes: 0 for arguments the operator refuses. */
+typedef struct mpnhip_conv_bwd_args {
+    const float* seg_data[4]; int64_t seg_stride[4]; int seg_channels[4]; int n_segments;
+    int H; int W; int cout; int ksize; int transposed; int relu;
+    int64_t n_images; const float* weight; const float* y; int64_t y_stride; const float* grad_out; int64_t grad_out_stride;
+    float* grad_in; float* grad_weight; float* grad_bias;
+} mpnhip_conv_bwd_args;
+size_t mpnhip_conv2d_backward_workspace_bytes(const mpnhip_conv_bwd_args* args);
+int mpnhip_conv2d_backward(const mpnhip_conv_bwd_args* args, void* workspace, size_t workspace_bytes, void* stream);
+
 /* nn.LayerNorm over the trailing [C][H][W] of every image (MaskModel.layer_norm), elementwise affine of that same shape:
  * out = (x - mean) / sqrt(var + eps) * weight + bias with the biased variance of the centred values (two passes: the mean first).
  * The input is a segment list as above (C = the sum of seg_channels, hw = H * W), weight / bias [C * hw] (both or neither may

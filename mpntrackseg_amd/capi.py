@@ -140,6 +140,17 @@ class DebugEdgeChainBwd(C.Structure):
 
 # name -> (restype, argtypes); mirrors include/mpnhip.h one to one (tests/test_capi_symbols.py
 # checks that every function the header declares is listed here and exported by the library)
+class ConvBwdArgs(C.Structure):
+    """``mpnhip_conv_bwd_args`` (include/mpnhip.h): the backward of one Conv2d (+ fused ReLU) of ``mpnhip_conv2d_backward``."""
+    _fields_ = [
+        ("seg_data", C.c_void_p * CONV_MAX_SEGMENTS), ("seg_stride", C.c_int64 * CONV_MAX_SEGMENTS),
+        ("seg_channels", C.c_int * CONV_MAX_SEGMENTS), ("n_segments", C.c_int), ("H", C.c_int), ("W", C.c_int), ("cout", C.c_int),
+        ("ksize", C.c_int), ("transposed", C.c_int), ("relu", C.c_int), ("n_images", C.c_int64), ("weight", C.c_void_p),
+        ("y", C.c_void_p), ("y_stride", C.c_int64), ("grad_out", C.c_void_p), ("grad_out_stride", C.c_int64),
+        ("grad_in", C.c_void_p), ("grad_weight", C.c_void_p), ("grad_bias", C.c_void_p),
+    ]
+
+
 _P, _I, _L, _Z = C.c_void_p, C.c_int, C.c_int64, C.c_size_t
 SIGNATURES = {
     "mpnhip_version": (C.c_char_p, []),
@@ -218,6 +229,8 @@ SIGNATURES = {
     "mpnhip_attention_aggregate_backward": (_I, [_P, _I, _L, _P, _L, _P, _P, _P, _P, _I, _P, _P, _P]),
     "mpnhip_avgpool": (_I, [_P, _L, _I, _P, _P]),
     "mpnhip_conv2d_forward": (_I, [C.POINTER(ConvArgs), _P]),
+    "mpnhip_conv2d_backward_workspace_bytes": (_Z, [C.POINTER(ConvBwdArgs)]),
+    "mpnhip_conv2d_backward": (_I, [C.POINTER(ConvBwdArgs), _P, _Z, _P]),
     "mpnhip_layer_norm_forward": (_I, [C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int), _I, _L, _L, _P, _P, C.c_float,
                                        _P, _L, _P]),
     "mpnhip_adam_step": (_I, [_P, _P, _P, _P, _L, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _I, _P]),

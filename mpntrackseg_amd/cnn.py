@@ -2,7 +2,9 @@
 (``/root/reference/src/mot_neural_solver/models/cnn.py``): same constructor arguments and the same
 ``layers`` Sequential indices, so the reference's ``state_dict`` keys load.
 
-``forward`` runs the stock PyTorch-ROCm (MIOpen) modules: training and everything that records gradients goes there.
+``forward`` runs the stock PyTorch-ROCm (MIOpen) modules: training and everything that records gradients goes there by default.
+``forward_native_autograd`` is the opt-in training route: the same native forward per Conv2d, recorded by autograd, its backward
+one ``mpnhip_conv2d_backward`` call (csrc/conv_backward.hip); a ConvTranspose2d stays the stock module there.
 ``forward_native`` is the no-grad inference forward through ``mpnhip_conv2d_forward`` (csrc/conv.hip): one native call per
 (transposed) convolution with its bias and ReLU fused, the input given as a list of channel segments so that a ``torch.cat`` in
 front of the stack is never materialised.  ``native_supported()`` says whether the stack is one the kernels cover."""
@@ -73,6 +75,81 @@ def conv2d_native(segments, weight, bias, relu=False, transposed=False, out=None
     return y
 
 
+def conv2d_native_backward(segments, weight, y, grad_out, relu=False, need_input=True, need_weight=True, need_bias=True):
+    """``mpnhip_conv2d_backward`` (csrc/conv_backward.hip) for Conv2d(k = 1 | 3, stride 1, padding k // 2) with its fused ReLU:
+    ``(grad_in, grad_weight, grad_bias)``, None where ``need_*`` is false.  ``grad_in`` is ONE dense [N, cin, H, W] tensor over the
+    channel concatenation of ``segments``; ``y``: the layer's output (read only with ``relu``, else it may be None)."""
+    segs = _segments(list(segments))
+    w = capi.f32c(weight.detach())
+    capi.require_device(w, y, grad_out)
+    n, _, h, wd = segs[0].shape
+    cin = sum(int(s.shape[1]) for s in segs)
+    cout = int(w.shape[0])
+    if w.dim() != 4 or int(w.shape[1]) != cin or w.shape[2] != w.shape[3]:
+        raise capi.MpnhipError("weight %s does not fit %d input channels" % (tuple(w.shape), cin))
+    if tuple(grad_out.shape) != (n, cout, h, wd) or (relu and (y is None or tuple(y.shape) != (n, cout, h, wd))):
+        raise capi.MpnhipError("grad_out (and y, with relu) must be [%d, %d, %d, %d]" % (n, cout, h, wd))
+    go = grad_out if _image_dense(grad_out) else capi.f32c(grad_out)     # (an expanded scalar, as .sum().backward() hands over, is copied)
+    yy = None if not relu else (y if _image_dense(y) else capi.f32c(y))
+    dev = segs[0].device
+    gi = torch.empty((n, cin, h, wd), dtype=torch.float32, device=dev) if need_input else None
+    gw = torch.empty_like(w) if need_weight else None
+    gb = torch.empty((cout,), dtype=torch.float32, device=dev) if need_bias else None
+    a = capi.ConvBwdArgs()
+    for i, s in enumerate(segs):
+        a.seg_data[i], a.seg_stride[i], a.seg_channels[i] = s.data_ptr(), s.stride(0), int(s.shape[1])
+    a.n_segments, a.H, a.W, a.cout, a.ksize, a.transposed, a.relu = len(segs), int(h), int(wd), cout, int(w.shape[2]), 0, int(relu)
+    a.n_images, a.weight = int(n), w.data_ptr()
+    a.y, a.y_stride = (yy.data_ptr(), yy.stride(0)) if yy is not None else (None, 0)
+    a.grad_out, a.grad_out_stride = go.data_ptr(), go.stride(0)
+    a.grad_in, a.grad_weight, a.grad_bias = (t.data_ptr() if t is not None else None for t in (gi, gw, gb))
+    lib = capi.load()
+    with torch.cuda.device(dev):
+        ws = capi.workspace(lib.mpnhip_conv2d_backward_workspace_bytes(C.byref(a)), dev, "conv_bwd")
+        capi.check(lib.mpnhip_conv2d_backward(C.byref(a), capi.ptr(ws), ws.numel(), capi.stream_ptr()), "mpnhip_conv2d_backward")
+    return gi, gw, gb
+
+
+class _Conv2dNative(torch.autograd.Function):
+    """One Conv2d (+ fused ReLU) of the mask branch: ``conv2d_native`` forward, one ``mpnhip_conv2d_backward`` call backward."""
+
+    @staticmethod
+    def forward(ctx, weight, bias, relu, *segments):
+        y = conv2d_native(segments, weight, bias, relu=relu)
+        ctx.relu, ctx.has_bias, ctx.channels = bool(relu), bias is not None, [int(s.shape[1]) for s in segments]
+        # the segments as the caller holds them (channel slices stay views of their tensors), the weight, and with relu the
+        # output: y is this call's own allocation, never a view of a buffer a later step overwrites
+        ctx.save_for_backward(weight, *(segments + ((y,) if relu else ())))
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        saved = ctx.saved_tensors
+        weight, k = saved[0], len(ctx.channels)
+        segments, y = saved[1:1 + k], (saved[1 + k] if ctx.relu else None)
+        need = ctx.needs_input_grad
+        need_input = any(need[3:])
+        gi, gw, gb = conv2d_native_backward(segments, weight, y, grad_out, relu=ctx.relu, need_input=need_input, need_weight=need[0],
+                                            need_bias=ctx.has_bias and need[1])
+        grads, c0 = [], 0
+        for i, c in enumerate(ctx.channels):
+            grads.append(gi[:, c0:c0 + c] if need_input and need[3 + i] else None)
+            c0 += c
+        return (gw, gb, None) + tuple(grads)
+
+
+def conv2d_native_autograd(segments, weight, bias, relu=False):
+    """``conv2d_native`` (Conv2d only) as a ``torch.autograd.Function``: the gradients of the segments (channel slices of one
+    dense ``grad_in``), of ``weight`` and of ``bias`` come from one ``mpnhip_conv2d_backward`` call that skips whatever
+    ``needs_input_grad`` does not want.  It takes no ``out=``: a saved tensor must not alias a buffer that is written again."""
+    segments = tuple(segments)
+    capi.require_device(weight, bias, *segments)
+    if not 1 <= len(segments) <= capi.CONV_MAX_SEGMENTS:
+        raise capi.MpnhipError("a native convolution takes 1 .. %d channel segments, not %d" % (capi.CONV_MAX_SEGMENTS, len(segments)))
+    return _Conv2dNative.apply(weight, bias, bool(relu), *segments)
+
+
 def layer_norm_native(segments, weight, bias, eps, out=None):
     """``mpnhip_layer_norm_forward``: nn.LayerNorm over the trailing [C, H, W] of the channel concatenation of ``segments``."""
     segs = _segments(list(segments))
@@ -137,6 +214,25 @@ def _layers_forward_native(layers, segments, out):
     return x[0]
 
 
+def _layers_forward_native_autograd(layers, segments):
+    """``_layers_forward_native`` with gradients: every Conv2d through ``conv2d_native_autograd`` with its ReLU fused, a
+    ConvTranspose2d (and the ReLU behind it) as the stock modules on the materialised tensor."""
+    mods = list(layers)
+    if not any(isinstance(m, (nn.Conv2d, nn.ConvTranspose2d)) for m in mods):
+        raise capi.MpnhipError("forward_native_autograd: the stack has no convolution")
+    x = list(segments)
+    for i, m in enumerate(mods):
+        if not isinstance(m, (nn.Conv2d, nn.ConvTranspose2d)):
+            continue
+        relu = i + 1 < len(mods) and isinstance(mods[i + 1], nn.ReLU)
+        if isinstance(m, nn.ConvTranspose2d):                # the stock modules, the ReLU behind it included
+            y = m(x[0] if len(x) == 1 else torch.cat(x, dim=1))
+            x = [mods[i + 1](y) if relu else y]
+        else:
+            x = [conv2d_native_autograd(x, m.weight, m.bias, relu=relu)]
+    return x[0]
+
+
 class CNN(nn.Module):
     """cnn.py:4-44: Conv2d (+BatchNorm2d) + ReLU (+Dropout2d) per entry of ``dims``."""
 
@@ -171,6 +267,13 @@ class CNN(nn.Module):
             raise capi.MpnhipError("this CNN is not covered by the native convolutions (see native_supported)")
         return _layers_forward_native(self.layers, segments, out)
 
+    def forward_native_autograd(self, segments):
+        """``forward_native`` for training: the same native forward, recorded by autograd, the backward of every Conv2d one
+        ``mpnhip_conv2d_backward`` call (``conv2d_native_autograd``).  No ``out=``: the outputs are saved for the backward."""
+        if not self.native_supported():
+            raise capi.MpnhipError("this CNN is not covered by the native convolutions (see native_supported)")
+        return _layers_forward_native_autograd(self.layers, segments)
+
 
 class MaskRCNNPredictor(nn.Module):
     """cnn.py:47-84: (transposed) convolutions with a ReLU after every layer but the last."""
@@ -201,3 +304,9 @@ class MaskRCNNPredictor(nn.Module):
         if not self.native_supported():
             raise capi.MpnhipError("this MaskRCNNPredictor is not covered by the native convolutions (see native_supported)")
         return _layers_forward_native(self.layers, segments, out)
+
+    def forward_native_autograd(self, segments):
+        """As ``CNN.forward_native_autograd``; a transposed convolution runs as the stock module."""
+        if not self.native_supported():
+            raise capi.MpnhipError("this MaskRCNNPredictor is not covered by the native convolutions (see native_supported)")
+        return _layers_forward_native_autograd(self.layers, segments)

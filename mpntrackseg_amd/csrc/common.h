@@ -442,13 +442,28 @@ inline unsigned stream_blocks(int64_t items) {
     return (unsigned)(need < 1 ? 1 : (need < cap ? need : cap));
 }
 
+// ------------------------------------------------------------------------------------ mask-branch convolutions
+// Geometry and segment list shared by the forward (conv.hip) and the backward (conv_backward.hip).
+constexpr int CONV_TILE = 14;                 // output tile edge
+constexpr int CONV_PATCH = 16;                // input patch edge (tile + halo of a 3 x 3)
+constexpr int CONV_PATCH_CELLS = CONV_PATCH * CONV_PATCH;
+constexpr int CONV_SMALL_COUT = 8;            // at most this many output channels: the plain kernels
+struct ConvSegs {
+    const float* p[MPNHIP_CONV_MAX_SEGMENTS];
+    int64_t stride[MPNHIP_CONV_MAX_SEGMENTS];
+    int ch[MPNHIP_CONV_MAX_SEGMENTS];
+    int n;
+};
+int check_segments(const char* name, const float* const* data, const int64_t* stride, const int* channels, int n_segments,
+                   int64_t hw, ConvSegs* segs, int64_t* cin);
+
 // Host-side counters of the kernel variants launched (mpnhip_debug_counters): test instrumentation that lets a parity test
 // assert WHICH code path produced the result it checked.  One relaxed atomic add per launch site.
 enum PathCounter {
     PC_CHAIN_FWD = 0, PC_CHAIN_FWD_SPLIT, PC_CHAIN_BWD, PC_CHAIN_BWD_SPLIT, PC_AGGREGATE, PC_AGGREGATE_BLOCK, PC_NODE_STEP32,
     PC_NODE_STEP32_BWD, PC_SEG_SHORT, PC_SEG_BLOCK, PC_SEG_BLOCK3, PC_EDGE_ENCODER, PC_EDGE_ENCODER_BWD, PC_TN_MFMA, PC_TN_SMALL,
     PC_TN_GENERIC, PC_GEMM_FP32, PC_GEMM_SPLIT, PC_GEMM_BF16, PC_WEIGHT_PACK, PC_SEG_SHORT3, PC_GEMM_SPLITK, PC_CHAIN_FWD_BF16, PC_TN_PANEL, PC_TN_PANEL_LAUNCH, PC_NODE_CHAIN, PC_TN_PANEL_FALLBACK, PC_CHAIN_BWD_BF16, PC_NODE_CHAIN_BWD, PC_GEMM_BF16_TILED, PC_GEMM_BF16_RING, PC_TN_ROWS16, PC_TN_ROWS16_LAUNCH, PC_TN_PANEL_NARROW, PC_LABEL_OVERLAP_LDS, PC_LABEL_OVERLAP_GLOBAL, PC_CONV_TILE, PC_CONV_SMALL_COUT,
-    PC_CONV_TRANSPOSE, PC_LAYER_NORM, PC_COUNT
+    PC_CONV_TRANSPOSE, PC_LAYER_NORM, PC_CONV_BWD_GATE, PC_CONV_WGRAD, PC_CONV_WGRAD_PLAIN, PC_COUNT
 };
 void count_path(int id);
 

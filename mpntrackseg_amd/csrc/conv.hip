@@ -19,19 +19,8 @@
 namespace mpnhip {
 namespace {
 
-constexpr int CONV_TILE = 14;                 // output tile edge
-constexpr int CONV_PATCH = 16;                // input patch edge (tile + halo of a 3 x 3)
-constexpr int CONV_PATCH_CELLS = CONV_PATCH * CONV_PATCH;
 constexpr int CONV_NT = 7;                    // 32-pixel column tiles per block: 7 * 32 >= 196
 constexpr int CONV_THREADS = 256;
-constexpr int CONV_SMALL_COUT = 8;            // at most this many output channels: the plain kernel
-
-struct ConvSegs {
-    const float* p[MPNHIP_CONV_MAX_SEGMENTS];
-    int64_t stride[MPNHIP_CONV_MAX_SEGMENTS];
-    int ch[MPNHIP_CONV_MAX_SEGMENTS];
-    int n;
-};
 
 using f32x16 = __attribute__((ext_vector_type(16))) float;
 
@@ -291,7 +280,9 @@ __global__ __launch_bounds__(LN_THREADS) void layer_norm_kernel(ConvSegs segs, i
     }
 }
 
-// the checks the two entry points share; *cin: the channel total.  name: the entry point, for the message
+}  // namespace
+
+// the checks the entry points share (common.h); *cin: the channel total.  name: the entry point, for the message
 int check_segments(const char* name, const float* const* data, const int64_t* stride, const int* channels, int n_segments,
                    int64_t hw, ConvSegs* segs, int64_t* cin) {
     MPN_CHECK_ARG(n_segments >= 1 && n_segments <= MPNHIP_CONV_MAX_SEGMENTS, "%s: n_segments %d outside 1 .. %d", name, n_segments,
@@ -318,6 +309,8 @@ int check_segments(const char* name, const float* const* data, const int64_t* st
     *cin = c;
     return MPNHIP_OK;
 }
+
+namespace {
 
 template <int KS, bool TRANSPOSED>
 void launch_conv_tile(const ConvSegs& segs, int cin, const mpnhip_conv_args& a, int M, hipStream_t stream) {

@@ -306,6 +306,14 @@ class TimeAwareAttentionModel(nn.Module):
         flow_in, flow_out = _AttentionAggregate.apply(g, x, dec_edge_feats)
         return self.node_model.forward_native([x, flow_in.view_as(x), flow_out.view_as(x)], out=out)
 
+    def aggregate_native_autograd(self, x, edge_index, dec_edge_feats, holder=None):
+        """``aggregate`` for training through the native convolutions with their native backward (``CNN.forward_native_autograd``):
+        ``node_model`` reads the segments (x, flow_in, flow_out) -- no ``torch.cat``."""
+        capi.require_device(x, edge_index, dec_edge_feats)
+        g = _prepared(edge_index, x.shape[0], holder)
+        flow_in, flow_out = _AttentionAggregate.apply(g, x, dec_edge_feats)
+        return self.node_model.forward_native_autograd([x, flow_in.view_as(x), flow_out.view_as(x)])
+
     def forward(self, x, edge_index, edge_attr, cls_net):
         dec_edge_feats, _ = cls_net(edge_attr)                    # mpn.py:114
         return self.aggregate(x, edge_index, dec_edge_feats), dec_edge_feats
@@ -341,6 +349,14 @@ class MaskModel(nn.Module):
         x = layer_norm_native([feats, node_embeds], ln.weight, ln.bias, ln.eps)
         return self.mask_predictor.forward_native([self.mask_head.forward_native([x])])
 
+    def forward_native_autograd(self, feature_embeds, node_embeds):
+        """``forward`` for training with the Conv2d layers native in both directions (``forward_native_autograd`` of the two CNNs
+        and of ``mask_predictor``, whose last 1 x 1 layer is the native one); the concatenation, the LayerNorm and the transposed
+        convolution are the stock modules."""
+        feats = self.feature_encoder.forward_native_autograd([feature_embeds])
+        x = self.layer_norm(torch.cat((feats, node_embeds), dim=1))
+        return self.mask_predictor.forward_native_autograd([self.mask_head.forward_native_autograd([x])])
+
 
 class MOTMPNet(nn.Module):
     """mpn.py:209-394.  ``MOTMPNet(model_params, bb_encoder=None)``; ``forward(data)`` returns
@@ -353,7 +369,10 @@ class MOTMPNet(nn.Module):
     stock PyTorch-ROCm modules by default (``mask_convs = 'stock'``: training, autograd); with ``mask_convs = 'native'`` a
     no-grad call of ``mask_predictions`` runs all of them through ``mpnhip_conv2d_forward`` / ``mpnhip_layer_norm_forward``
     (csrc/conv.hip) and falls back to the stock modules, silently, whenever gradients are being recorded, a tensor is not
-    on the device or a module is outside what the kernels cover (``native_supported``).
+    on the device or a module is outside what the kernels cover (``native_supported``).  ``mask_conv_grads = 'native'`` is the
+    training-side selector: while gradients are recorded, every Conv2d of the branch runs the native forward under autograd with
+    ``mpnhip_conv2d_backward`` (csrc/conv_backward.hip) as its backward; ConvTranspose2d, LayerNorm and the ``torch.cat`` in front
+    of it stay stock, and the same conditions and silent fall-back apply.
     It is built only when ``model_params`` carries the mask-branch dicts (as configs/tracking_cfg.yaml does) and
     evaluated only when ``data.x_ext`` is present; otherwise ``mask_predictions`` is an empty list.
     """
@@ -382,6 +401,12 @@ class MOTMPNet(nn.Module):
         self.keep_packed_weights = False
         # 'stock' | 'native': how mask_predictions runs the mask branch's convolutions and LayerNorm (see the class docstring)
         self.mask_convs = 'stock'
+        # 'stock' | 'native': the route of mask_predictions WHILE GRADIENTS ARE RECORDED.  'native': every Conv2d of the mask branch
+        # runs mpnhip_conv2d_forward under autograd with mpnhip_conv2d_backward as its backward (csrc/conv_backward.hip): one
+        # arithmetic per layer, no algorithm search, gradients that repeat bit for bit.  ConvTranspose2d, LayerNorm and the
+        # torch.cat in front of it stay stock modules.  Same conditions as mask_convs (device tensors, covered stacks), same
+        # silent fall-back to the stock route.
+        self.mask_conv_grads = 'stock'
 
     def _build_core_MPNet(self, model_params, encoder_feats_dict):
         """mpn.py:254-317."""
@@ -636,8 +661,12 @@ class MOTMPNet(nn.Module):
         L, k = int(self.num_enc_steps), int(self.num_class_steps)
         if self.mask_convs not in ('stock', 'native'):
             raise capi.MpnhipError("mask_convs must be 'stock' or 'native', not %r" % (self.mask_convs,))
+        if self.mask_conv_grads not in ('stock', 'native'):
+            raise capi.MpnhipError("mask_conv_grads must be 'stock' or 'native', not %r" % (self.mask_conv_grads,))
         if self.mask_convs == 'native' and self._mask_native_ok(x_ext, edge_index, logits):
             return self._mask_predictions_native(x_ext, edge_index, logits, holder, last_only)
+        if self.mask_conv_grads == 'native' and self._mask_native_grad_ok(x_ext, edge_index, logits):
+            return self._mask_predictions_native_grad(x_ext, edge_index, logits, holder, last_only)
         latent_node_ext_feats = self.node_ext_encoder(x_ext)                           # mpn.py:356
         initial_node_ext_feats = latent_node_ext_feats
         first_class_step = L - k + 1
@@ -656,15 +685,44 @@ class MOTMPNet(nn.Module):
     def _mask_modules(self):
         return (self.node_ext_encoder, self.MPAttentionNet.node_model, self.mask_predictor)
 
-    def _mask_native_ok(self, x_ext, edge_index, logits):
-        """The conditions of the native mask branch: device tensors, modules the kernels cover, no gradient being recorded."""
+    def _mask_native_covered(self, x_ext, edge_index, logits):
+        """Device tensors and modules the kernels cover: what both native routes need."""
         tensors = (x_ext, edge_index, logits)
         if not all(isinstance(t, torch.Tensor) and t.is_cuda for t in tensors) or x_ext.dim() != 4 or x_ext.dtype != torch.float32:
             return False
         params = [p for m in self._mask_modules() for p in m.parameters()]
-        if not all(p.is_cuda for p in params) or not all(m.native_supported() for m in self._mask_modules()):
-            return False
-        return not (torch.is_grad_enabled() and any(t.requires_grad for t in (x_ext, logits) + tuple(params)))
+        return all(p.is_cuda for p in params) and all(m.native_supported() for m in self._mask_modules())
+
+    def _mask_grads_recorded(self, x_ext, logits):
+        params = [p for m in self._mask_modules() for p in m.parameters()]
+        return torch.is_grad_enabled() and any(t.requires_grad for t in (x_ext, logits) + tuple(params))
+
+    def _mask_native_ok(self, x_ext, edge_index, logits):
+        """The conditions of the native mask branch: device tensors, modules the kernels cover, no gradient being recorded."""
+        return self._mask_native_covered(x_ext, edge_index, logits) and not self._mask_grads_recorded(x_ext, logits)
+
+    def _mask_native_grad_ok(self, x_ext, edge_index, logits):
+        """The conditions of ``mask_conv_grads = 'native'``: the same tensors and modules, and a gradient being recorded."""
+        return self._mask_native_covered(x_ext, edge_index, logits) and self._mask_grads_recorded(x_ext, logits)
+
+    def _mask_predictions_native_grad(self, x_ext, edge_index, logits, holder, last_only):
+        """``mask_predictions`` under autograd with every Conv2d native in both directions.  The steps are those of the stock route
+        (the ``initial || latent`` concatenation is a ``torch.cat``: the saved tensors of a step must outlive the next one, so
+        the buffer reuse of the inference route does not apply)."""
+        L, k = int(self.num_enc_steps), int(self.num_class_steps)
+        first_class_step = L - k + 1
+        latent = self.node_ext_encoder.forward_native_autograd([x_ext])                 # mpn.py:356
+        initial = latent
+        preds = []
+        for step in range(1, L + 1):
+            if self.reattach_initial_nodes:                                             # mpn.py:373
+                latent = torch.cat((initial, latent), dim=1)
+            latent = self.MPAttentionNet.aggregate_native_autograd(latent, edge_index, logits[step - 1], holder=holder)   # mpn.py:377
+            if step >= first_class_step and (step == L or not last_only):
+                preds.append(self.mask_predictor.forward_native_autograd(x_ext, latent))
+        if L == 0:
+            preds.append(self.mask_predictor.forward_native_autograd(x_ext, latent))
+        return preds
 
     def _mask_predictions_native(self, x_ext, edge_index, logits, holder, last_only):
         """``mask_predictions`` through the native convolutions.  With ``reattach_initial_nodes`` one [N, 2 c, H, W] buffer holds

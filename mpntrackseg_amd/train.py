@@ -393,7 +393,8 @@ class TrainStep:
     def state_dict(self):
         """Everything a resumed run needs, keyed by parameter NAME (not by flat offset, so a checkpoint does not depend on the bucket
         layout): the model's ``state_dict``, Adam's ``exp_avg`` / ``exp_avg_sq`` per parameter, the call count ``t``, the device-side
-        count of skipped calls, the optimizer's hyper-parameters and ``train_mask_branch``.  Tensors are copies on their device."""
+        count of skipped calls, the optimizer's hyper-parameters, ``train_mask_branch`` and the model's ``mask_conv_grads`` selector
+        (which backward the mask branch's convolutions took).  Tensors are copies on their device."""
         b, o = self.bucket, self.opt
         names = self._param_names()
 
@@ -402,13 +403,13 @@ class TrainStep:
         return {'model': dict((k, v.detach().clone()) for k, v in self.model.state_dict().items()),
                 'exp_avg': slices(o.exp_avg), 'exp_avg_sq': slices(o.exp_avg_sq), 't': int(o.t), 'skipped': o.skipped.clone(),
                 'lr': o.lr, 'betas': tuple(o.betas), 'eps': o.eps, 'weight_decay': o.weight_decay,
-                'train_mask_branch': self.train_mask_branch}
+                'train_mask_branch': self.train_mask_branch, 'mask_conv_grads': getattr(self.model, 'mask_conv_grads', 'stock')}
 
     def load_state_dict(self, state):
         """Restore ``state_dict()`` into this step (built on a fresh model): weights are written THROUGH the flat views, the moments
         into the flat moment buffers by parameter name.  A hot-path-only checkpoint loads into a joint step (mask moments zero; mask
         weights from the checkpoint's model when it has them), a joint checkpoint into a hot-path-only step (its mask moments are
-        ignored).  A hot-path key that is missing or has another shape raises ``MpnhipError`` naming it, before anything is written."""
+        ignored).  ``mask_conv_grads`` goes back onto the model.  A hot-path key that is missing or has another shape raises ``MpnhipError`` naming it, before anything is written."""
         b, o = self.bucket, self.opt
         names = self._param_names()
         hot = set(id(p) for p in self._hot_params)
@@ -444,6 +445,8 @@ class TrainStep:
             o.skipped.copy_(state['skipped'])
         o.t = int(state['t'])
         o.lr, o.betas, o.eps, o.weight_decay = state['lr'], tuple(state['betas']), state['eps'], state['weight_decay']
+        if 'mask_conv_grads' in state:    # (a checkpoint from before the selector leaves the model's as it is)
+            self.model.mask_conv_grads = state['mask_conv_grads']
         capi._weights_epoch[0] += 1   # raw writes into flat_params: packed weight images are stale
         self._cmodels = {}
 

@@ -65,6 +65,8 @@ def main():
     ap.add_argument("--runs", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--graphs", type=int, default=2)
+    ap.add_argument("--mask-conv-grads", choices=("stock", "native"), default="stock",
+                    help="MOTMPNet.mask_conv_grads of BOTH routes: the backward of the mask branch's Conv2d layers")
     ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "joint_step",
                                                   "timing.json"))
     a = ap.parse_args()
@@ -75,6 +77,7 @@ def main():
     lw = {"tracking": 1, "segmentation": 1}
     step = TrainStep(fresh(), lr=1e-3, train_mask_branch=True, loss_weights=lw)
     twin = fresh()
+    step.model.mask_conv_grads = twin.mask_conv_grads = a.mask_conv_grads
     opt = torch.optim.Adam(twin.parameters(), lr=1e-3)
     data = _Obj()
     data.x, data.x_ext, data.edge_index, data.edge_attr = b["x"], b["x_ext"], b["edge_index"], b["edge_attr"]
@@ -115,7 +118,7 @@ def main():
             losses[name].append(float(last[name]))
     res = {"problem": {"graphs": a.graphs, "nodes": int(b["x"].shape[0]), "edges": int(b["edge_index"].shape[1]), "L": L,
                        "x_ext": list(b["x_ext"].shape), "flat_bucket_floats": int(step.bucket.n), "mask_floats": int(step.mask_elems)},
-           "runs": len(times["joint"]), "warmup": a.warmup, "timing": "host clock around the step + device synchronise, ms"}
+           "mask_conv_grads": a.mask_conv_grads, "runs": len(times["joint"]), "warmup": a.warmup, "timing": "host clock around the step + device synchronise, ms"}
     for name, ts in times.items():
         res[name] = {"median_ms": statistics.median(ts), "min_ms": min(ts), "max_ms": max(ts), "first_call_ms": first[name],
                      "loss_first": losses[name][0], "loss_last": losses[name][-1]}
