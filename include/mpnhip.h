@@ -749,6 +749,37 @@ typedef struct mpnhip_conv_bwd_args {
 size_t mpnhip_conv2d_backward_workspace_bytes(const mpnhip_conv_bwd_args* args);
 int mpnhip_conv2d_backward(const mpnhip_conv_bwd_args* args, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Mask branch, training: the backward of ONE nn.ConvTranspose2d(cin, cout, 2, stride 2, padding 0) with the ReLU that
+ * mpnhip_conv2d_forward (transposed != 0) fuses behind it.  The same args struct as mpnhip_conv2d_backward, read as follows:
+ * transposed must be non-zero and ksize 2; H, W are the INPUT size; the segment list is the layer's input ([channels][H][W] per
+ * image); weight and grad_weight are [cin][cout][2][2]; y and grad_out are dense [cout][2 H][2 W] per image at y_stride /
+ * grad_out_stride; grad_in is dense [n_images][cin][H][W] over the channel concatenation of the segments; grad_bias [cout].
+ * Outputs may be NULL and are overwritten, never accumulated into.  Exact fp32 products, fp32 accumulation, no float atomics:
+ * every sum has an order fixed by the layer's shape and n_images alone.
+ *
+ * Stride equals kernel size, so no two taps meet in one output pixel and the layer is a 1 x 1 product in a space-to-depth layout:
+ *   pre-pass    g = grad_out * [y > 0] (relu) or grad_out, written once into the workspace as g'[n][4 m + 2 dy + dx][h][w] =
+ *               g[n][m][2 h + dy][2 w + dx]: 4 cout channels at H x W.  The same kernel sums g per (block of 8 images, channel m);
+ *               grad_bias adds those partial sums in block order.
+ *   grad_in     [n][c][h][w] = sum over (m, dy, dx) of g'[n][(m, dy, dx)][h][w] * W[c][m][dy][dx]: the weight as stored is the
+ *               weight [cin][4 cout] of a 1 x 1 Conv2d from g' to the input, so this is mpnhip_conv2d_forward (ksize 1) on g'
+ *               with the weight pointer itself -- an image's bits do not depend on the batch.  Skipped when grad_in is NULL.
+ *   grad_weight [c][(m, dy, dx)] = sum over images and pixels of x[n][c][p] * g'[n][(m, dy, dx)][p]: a 1 x 1 weight-gradient
+ *               product with its rows from the layer's input and its columns from g', so its output layout is this weight's: one
+ *               block per (32 rows, 64 columns, 8 images) on v_mfma_f32_32x32x2_f32 with the pixel as k (cin <= 8: the plain
+ *               kernel of mpnhip_conv2d_backward with the roles swapped); partial sums added in split order.  The row operand is
+ *               one dense tensor: more than one input segment is first gathered into the workspace.
+ *
+ * Workspace (floats, every region padded to 256 bytes), with splits = ceil(n_images / 8):
+ *   g' [n_images][4 cout][H W] | the gathered input [n_images][cin][H W] (only when n_segments > 1) |
+ *   weight partial sums [splits][cin][4 cout] | bias partial sums [splits][cout]
+ *
+ * MPNHIP_ERR_ARG before any launch, the message starting with the entry point's name: what mpnhip_conv2d_backward refuses, with
+ * transposed == 0 and ksize != 2 in the place of its kernel-size rules.  n_images == 0 zero-fills grad_weight / grad_bias where
+ * given and touches nothing else.  mpnhip_conv_transpose2d_backward_workspace_bytes: 0 for arguments the operator refuses. */
+size_t mpnhip_conv_transpose2d_backward_workspace_bytes(const mpnhip_conv_bwd_args* args);
+int mpnhip_conv_transpose2d_backward(const mpnhip_conv_bwd_args* args, void* workspace, size_t workspace_bytes, void* stream);
+
 /* nn.LayerNorm over the trailing [C][H][W] of every image (MaskModel.layer_norm), elementwise affine of that same shape:
  * out = (x - mean) / sqrt(var + eps) * weight + bias with the biased variance of the centred values (two passes: the mean first).
  * The input is a segment list as above (C = the sum of seg_channels, hw = H * W), weight / bias [C * hw] (both or neither may
@@ -758,6 +789,34 @@ int mpnhip_conv2d_backward(const mpnhip_conv_bwd_args* args, void* workspace, si
 int mpnhip_layer_norm_forward(const float* const* seg_data, const int64_t* seg_stride, const int* seg_channels, int n_segments,
                               int64_t n_images, int64_t hw, const float* weight, const float* bias, float eps, float* out,
                               int64_t out_stride, void* stream);
+
+/* The backward of mpnhip_layer_norm_forward over the same segment list.  weight [C * hw] or NULL (no affine: gamma = 1; the call
+ * computes grad_in only, and a grad_weight or grad_bias handed to it is refused); grad_out image i at grad_out + i *
+ * grad_out_stride, dense [C * hw].  Outputs, each may be NULL (all three NULL is refused), each overwritten:
+ *   grad_in     [n_images][C * hw], dense: segment s owns the channel slice behind the channels of segments 0 .. s - 1
+ *   grad_weight [C * hw], grad_bias [C * hw]
+ * Per image (one block, like the forward): mean and rstd are recomputed with the forward's own two passes and block sums -- the
+ * same order, hence the same bits --, then a = sum g_i gamma_i and b = sum g_i gamma_i xhat_i as fixed-order block sums and
+ * grad_in_i = rstd * (g_i gamma_i - a / F - xhat_i * b / F), F = C * hw: an image's grad_in does not depend on the batch.
+ * Per element: grad_weight_i = sum_n g[n][i] * xhat[n][i], grad_bias_i = sum_n g[n][i] as partial sums over blocks of 8 images
+ * (threads along i), added in block order by a second kernel: a function of the inputs and n_images alone.  No float atomics.
+ *
+ * Workspace (floats, every region padded to 256 bytes), with splits = ceil(n_images / 8):
+ *   (mean, rstd) [n_images][2] | with a weight: grad_weight partial sums [splits][C * hw] | grad_bias partial sums [splits][C * hw]
+ *
+ * MPNHIP_ERR_ARG before any launch, the message starting with the entry point's name: what the forward refuses (null lists,
+ * n_segments outside 1 .. 4, null / empty segments, hw < 1, eps < 0 or not finite, sizes or strides beyond INT32_MAX), a null
+ * grad_out, no output wanted, grad_weight / grad_bias with a NULL weight, a null workspace or one smaller than
+ * mpnhip_layer_norm_backward_workspace_bytes (which is 0 for arguments the operator refuses).  n_images == 0 zero-fills
+ * grad_weight / grad_bias where given and touches nothing else. */
+size_t mpnhip_layer_norm_backward_workspace_bytes(const float* const* seg_data, const int64_t* seg_stride, const int* seg_channels,
+                                                  int n_segments, int64_t n_images, int64_t hw, const float* weight, float eps,
+                                                  const float* grad_out, int64_t grad_out_stride, float* grad_in, float* grad_weight,
+                                                  float* grad_bias);
+int mpnhip_layer_norm_backward(const float* const* seg_data, const int64_t* seg_stride, const int* seg_channels, int n_segments,
+                               int64_t n_images, int64_t hw, const float* weight, float eps, const float* grad_out,
+                               int64_t grad_out_stride, float* grad_in, float* grad_weight, float* grad_bias, void* workspace,
+                               size_t workspace_bytes, void* stream);
 
 /* torch.optim.Adam(lr, betas, eps, weight_decay).step() (the optimizer of pl_module.py:76-77, configs/tracking_cfg.yaml:6-10)
  * over FLAT fp32 buffers of n elements: parameters, gradients (as the backward / all-reduce left them) and the two

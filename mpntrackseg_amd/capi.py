@@ -233,6 +233,12 @@ SIGNATURES = {
     "mpnhip_conv2d_backward": (_I, [C.POINTER(ConvBwdArgs), _P, _Z, _P]),
     "mpnhip_layer_norm_forward": (_I, [C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int), _I, _L, _L, _P, _P, C.c_float,
                                        _P, _L, _P]),
+    "mpnhip_conv_transpose2d_backward_workspace_bytes": (_Z, [C.POINTER(ConvBwdArgs)]),
+    "mpnhip_conv_transpose2d_backward": (_I, [C.POINTER(ConvBwdArgs), _P, _Z, _P]),
+    "mpnhip_layer_norm_backward_workspace_bytes": (_Z, [C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int), _I, _L, _L, _P,
+                                                        C.c_float, _P, _L, _P, _P, _P]),
+    "mpnhip_layer_norm_backward": (_I, [C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int), _I, _L, _L, _P, C.c_float, _P,
+                                        _L, _P, _P, _P, _P, _Z, _P]),
     "mpnhip_adam_step": (_I, [_P, _P, _P, _P, _L, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _I, _P]),
     "mpnhip_adam_step_guarded": (_I, [_P, _P, _P, _P, _L, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _I, _P, _P]),
     "mpnhip_adam_step_counted": (_I, [_P, _P, _P, _P, _L, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _I, _P, _P, _P]),

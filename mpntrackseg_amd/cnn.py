@@ -4,7 +4,9 @@
 
 ``forward`` runs the stock PyTorch-ROCm (MIOpen) modules: training and everything that records gradients goes there by default.
 ``forward_native_autograd`` is the opt-in training route: the same native forward per Conv2d, recorded by autograd, its backward
-one ``mpnhip_conv2d_backward`` call (csrc/conv_backward.hip); a ConvTranspose2d stays the stock module there.
+one ``mpnhip_conv2d_backward`` call (csrc/conv_backward.hip); a ConvTranspose2d stays the stock module there unless
+``transposed_native`` sends it through ``conv_transpose2d_native_autograd`` (``mpnhip_conv_transpose2d_backward``).
+``layer_norm_native_autograd`` is the LayerNorm of MaskModel the same way (``mpnhip_layer_norm_backward``, csrc/conv.hip).
 ``forward_native`` is the no-grad inference forward through ``mpnhip_conv2d_forward`` (csrc/conv.hip): one native call per
 (transposed) convolution with its bias and ReLU fused, the input given as a list of channel segments so that a ``torch.cat`` in
 front of the stack is never materialised.  ``native_supported()`` says whether the stack is one the kernels cover."""
@@ -150,6 +152,156 @@ def conv2d_native_autograd(segments, weight, bias, relu=False):
     return _Conv2dNative.apply(weight, bias, bool(relu), *segments)
 
 
+def conv_transpose2d_native_backward(segments, weight, y, grad_out, relu=False, need_input=True, need_weight=True, need_bias=True):
+    """``mpnhip_conv_transpose2d_backward`` (csrc/conv_backward.hip) for ConvTranspose2d(2, stride 2, padding 0) with its fused
+    ReLU: ``(grad_in, grad_weight, grad_bias)``, None where ``need_*`` is false.  ``segments`` are [N, C_s, H, W], ``weight``
+    [cin, cout, 2, 2], ``y`` (read only with ``relu``) and ``grad_out`` [N, cout, 2 H, 2 W]; ``grad_in`` is ONE dense
+    [N, cin, H, W] tensor over the channel concatenation of ``segments``."""
+    segs = _segments(list(segments))
+    w = capi.f32c(weight.detach())
+    capi.require_device(w, y, grad_out)
+    n, _, h, wd = segs[0].shape
+    cin = sum(int(s.shape[1]) for s in segs)
+    if w.dim() != 4 or int(w.shape[0]) != cin or w.shape[2] != w.shape[3]:
+        raise capi.MpnhipError("weight %s does not fit %d input channels" % (tuple(w.shape), cin))
+    cout = int(w.shape[1])
+    if tuple(grad_out.shape) != (n, cout, 2 * h, 2 * wd) or (relu and (y is None or tuple(y.shape) != (n, cout, 2 * h, 2 * wd))):
+        raise capi.MpnhipError("grad_out (and y, with relu) must be [%d, %d, %d, %d]" % (n, cout, 2 * h, 2 * wd))
+    go = grad_out if _image_dense(grad_out) else capi.f32c(grad_out)     # (an expanded scalar, as .sum().backward() hands over, is copied)
+    yy = None if not relu else (y if _image_dense(y) else capi.f32c(y))
+    dev = segs[0].device
+    gi = torch.empty((n, cin, h, wd), dtype=torch.float32, device=dev) if need_input else None
+    gw = torch.empty_like(w) if need_weight else None
+    gb = torch.empty((cout,), dtype=torch.float32, device=dev) if need_bias else None
+    a = capi.ConvBwdArgs()
+    for i, s in enumerate(segs):
+        a.seg_data[i], a.seg_stride[i], a.seg_channels[i] = s.data_ptr(), s.stride(0), int(s.shape[1])
+    a.n_segments, a.H, a.W, a.cout, a.ksize, a.transposed, a.relu = len(segs), int(h), int(wd), cout, int(w.shape[2]), 1, int(relu)
+    a.n_images, a.weight = int(n), w.data_ptr()
+    a.y, a.y_stride = (yy.data_ptr(), yy.stride(0)) if yy is not None else (None, 0)
+    a.grad_out, a.grad_out_stride = go.data_ptr(), go.stride(0)
+    a.grad_in, a.grad_weight, a.grad_bias = (t.data_ptr() if t is not None else None for t in (gi, gw, gb))
+    lib = capi.load()
+    with torch.cuda.device(dev):
+        ws = capi.workspace(lib.mpnhip_conv_transpose2d_backward_workspace_bytes(C.byref(a)), dev, "conv_bwd")
+        capi.check(lib.mpnhip_conv_transpose2d_backward(C.byref(a), capi.ptr(ws), ws.numel(), capi.stream_ptr()),
+                   "mpnhip_conv_transpose2d_backward")
+    return gi, gw, gb
+
+
+class _ConvTranspose2dNative(torch.autograd.Function):
+    """One ConvTranspose2d(2, stride 2) (+ fused ReLU) of the mask branch: ``conv2d_native(transposed=True)`` forward, one
+    ``mpnhip_conv_transpose2d_backward`` call backward."""
+
+    @staticmethod
+    def forward(ctx, weight, bias, relu, *segments):
+        y = conv2d_native(segments, weight, bias, relu=relu, transposed=True)
+        ctx.relu, ctx.has_bias, ctx.channels = bool(relu), bias is not None, [int(s.shape[1]) for s in segments]
+        ctx.save_for_backward(weight, *(segments + ((y,) if relu else ())))     # (as _Conv2dNative)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        saved = ctx.saved_tensors
+        weight, k = saved[0], len(ctx.channels)
+        segments, y = saved[1:1 + k], (saved[1 + k] if ctx.relu else None)
+        need = ctx.needs_input_grad
+        need_input = any(need[3:])
+        gi, gw, gb = conv_transpose2d_native_backward(segments, weight, y, grad_out, relu=ctx.relu, need_input=need_input,
+                                                      need_weight=need[0], need_bias=ctx.has_bias and need[1])
+        grads, c0 = [], 0
+        for i, c in enumerate(ctx.channels):
+            grads.append(gi[:, c0:c0 + c] if need_input and need[3 + i] else None)
+            c0 += c
+        return (gw, gb, None) + tuple(grads)
+
+
+def conv_transpose2d_native_autograd(segments, weight, bias, relu=False):
+    """``conv2d_native(..., transposed=True)`` as a ``torch.autograd.Function``: the gradients of the segments (channel slices of
+    one dense ``grad_in``), of ``weight`` and of ``bias`` come from one ``mpnhip_conv_transpose2d_backward`` call that skips
+    whatever ``needs_input_grad`` does not want.  No ``out=``, as ``conv2d_native_autograd``."""
+    segments = tuple(segments)
+    capi.require_device(weight, bias, *segments)
+    if not 1 <= len(segments) <= capi.CONV_MAX_SEGMENTS:
+        raise capi.MpnhipError("a native convolution takes 1 .. %d channel segments, not %d" % (capi.CONV_MAX_SEGMENTS, len(segments)))
+    return _ConvTranspose2dNative.apply(weight, bias, bool(relu), *segments)
+
+
+def layer_norm_native_backward(segments, weight, eps, grad_out, need_input=True, need_weight=True, need_bias=True):
+    """``mpnhip_layer_norm_backward`` (csrc/conv.hip): ``(grad_in, grad_weight, grad_bias)`` of ``layer_norm_native`` on the same
+    ``segments``, None where ``need_*`` is false.  ``grad_in`` is ONE dense [N, C, H, W] tensor over the channel concatenation;
+    ``weight`` None: no affine, ``grad_in`` only."""
+    segs = _segments(list(segments))
+    n, _, h, wd = segs[0].shape
+    c = sum(int(s.shape[1]) for s in segs)
+    w = capi.f32c(weight.detach()) if weight is not None else None
+    capi.require_device(w, grad_out)
+    if w is not None and w.numel() != c * h * wd:
+        raise capi.MpnhipError("the LayerNorm affine must have the input's [%d, %d, %d] elements" % (c, h, wd))
+    if w is None and (need_weight or need_bias):
+        raise capi.MpnhipError("a LayerNorm without an affine has no weight or bias gradient")
+    if tuple(grad_out.shape) != (n, c, h, wd):
+        raise capi.MpnhipError("grad_out must be [%d, %d, %d, %d]" % (n, c, h, wd))
+    go = grad_out if _image_dense(grad_out) else capi.f32c(grad_out)
+    dev = segs[0].device
+    gi = torch.empty((n, c, h, wd), dtype=torch.float32, device=dev) if need_input else None
+    gw = torch.empty((c, h, wd), dtype=torch.float32, device=dev) if need_weight else None
+    gb = torch.empty((c, h, wd), dtype=torch.float32, device=dev) if need_bias else None
+    k = len(segs)
+    data = (C.c_void_p * k)(*[s.data_ptr() for s in segs])
+    stride = (C.c_int64 * k)(*[s.stride(0) for s in segs])
+    chans = (C.c_int * k)(*[int(s.shape[1]) for s in segs])
+    head = (data, stride, chans, k, int(n), int(h * wd), capi.ptr(w), float(eps), capi.ptr(go), go.stride(0), capi.ptr(gi), capi.ptr(gw),
+            capi.ptr(gb))
+    lib = capi.load()
+    with torch.cuda.device(dev):
+        ws = capi.workspace(lib.mpnhip_layer_norm_backward_workspace_bytes(*head), dev, "conv_bwd")
+        capi.check(lib.mpnhip_layer_norm_backward(*(head + (capi.ptr(ws), ws.numel(), capi.stream_ptr()))), "mpnhip_layer_norm_backward")
+    return gi, gw, gb
+
+
+class _LayerNormNative(torch.autograd.Function):
+    """``layer_norm_native`` forward on the segments as the caller holds them, one ``mpnhip_layer_norm_backward`` call backward."""
+
+    @staticmethod
+    def forward(ctx, weight, bias, eps, *segments):
+        y = layer_norm_native(segments, weight, bias, eps)
+        ctx.eps, ctx.affine, ctx.channels = float(eps), weight is not None, [int(s.shape[1]) for s in segments]
+        ctx.save_for_backward(*(((weight,) if weight is not None else ()) + segments))
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        saved = ctx.saved_tensors
+        weight, segments = (saved[0], saved[1:]) if ctx.affine else (None, saved)
+        need = ctx.needs_input_grad
+        need_input = any(need[3:])
+        if not (need_input or (ctx.affine and (need[0] or need[1]))):
+            return (None,) * (3 + len(ctx.channels))
+        gi, gw, gb = layer_norm_native_backward(segments, weight, ctx.eps, grad_out, need_input=need_input,
+                                                need_weight=ctx.affine and need[0], need_bias=ctx.affine and need[1])
+        grads, c0 = [], 0
+        for i, c in enumerate(ctx.channels):
+            grads.append(gi[:, c0:c0 + c] if need_input and need[3 + i] else None)
+            c0 += c
+        shape = weight.shape if ctx.affine else None
+        return (gw.view(shape) if gw is not None else None, gb.view(shape) if gb is not None else None, None) + tuple(grads)
+
+
+def layer_norm_native_autograd(segments, weight, bias, eps):
+    """``layer_norm_native`` as a ``torch.autograd.Function``.  The segments are read where they are (no ``torch.cat``); their
+    gradients are channel slices of one dense ``grad_in``, those of ``weight`` / ``bias`` (both or neither) have their shape."""
+    segments = tuple(segments)
+    capi.require_device(weight, bias, *segments)
+    if not 1 <= len(segments) <= capi.CONV_MAX_SEGMENTS:
+        raise capi.MpnhipError("a native LayerNorm takes 1 .. %d channel segments, not %d" % (capi.CONV_MAX_SEGMENTS, len(segments)))
+    if (weight is None) != (bias is None):
+        raise capi.MpnhipError("the LayerNorm affine needs weight and bias, or neither")
+    return _LayerNormNative.apply(weight, bias, float(eps), *segments)
+
+
 def layer_norm_native(segments, weight, bias, eps, out=None):
     """``mpnhip_layer_norm_forward``: nn.LayerNorm over the trailing [C, H, W] of the channel concatenation of ``segments``."""
     segs = _segments(list(segments))
@@ -214,9 +366,10 @@ def _layers_forward_native(layers, segments, out):
     return x[0]
 
 
-def _layers_forward_native_autograd(layers, segments):
-    """``_layers_forward_native`` with gradients: every Conv2d through ``conv2d_native_autograd`` with its ReLU fused, a
-    ConvTranspose2d (and the ReLU behind it) as the stock modules on the materialised tensor."""
+def _layers_forward_native_autograd(layers, segments, transposed_native=False):
+    """``_layers_forward_native`` with gradients: every Conv2d through ``conv2d_native_autograd`` with its ReLU fused.  A
+    ConvTranspose2d (and the ReLU behind it) runs as the stock modules on the materialised tensor, or, with ``transposed_native``,
+    through ``conv_transpose2d_native_autograd`` with that ReLU fused."""
     mods = list(layers)
     if not any(isinstance(m, (nn.Conv2d, nn.ConvTranspose2d)) for m in mods):
         raise capi.MpnhipError("forward_native_autograd: the stack has no convolution")
@@ -225,7 +378,9 @@ def _layers_forward_native_autograd(layers, segments):
         if not isinstance(m, (nn.Conv2d, nn.ConvTranspose2d)):
             continue
         relu = i + 1 < len(mods) and isinstance(mods[i + 1], nn.ReLU)
-        if isinstance(m, nn.ConvTranspose2d):                # the stock modules, the ReLU behind it included
+        if isinstance(m, nn.ConvTranspose2d) and transposed_native:
+            x = [conv_transpose2d_native_autograd(x, m.weight, m.bias, relu=relu)]
+        elif isinstance(m, nn.ConvTranspose2d):              # the stock modules, the ReLU behind it included
             y = m(x[0] if len(x) == 1 else torch.cat(x, dim=1))
             x = [mods[i + 1](y) if relu else y]
         else:
@@ -305,8 +460,9 @@ class MaskRCNNPredictor(nn.Module):
             raise capi.MpnhipError("this MaskRCNNPredictor is not covered by the native convolutions (see native_supported)")
         return _layers_forward_native(self.layers, segments, out)
 
-    def forward_native_autograd(self, segments):
-        """As ``CNN.forward_native_autograd``; a transposed convolution runs as the stock module."""
+    def forward_native_autograd(self, segments, transposed_native=False):
+        """As ``CNN.forward_native_autograd``; a transposed convolution runs as the stock module, or with ``transposed_native``
+        through ``conv_transpose2d_native_autograd`` (backward: ``mpnhip_conv_transpose2d_backward``)."""
         if not self.native_supported():
             raise capi.MpnhipError("this MaskRCNNPredictor is not covered by the native convolutions (see native_supported)")
-        return _layers_forward_native_autograd(self.layers, segments)
+        return _layers_forward_native_autograd(self.layers, segments, transposed_native=transposed_native)

@@ -280,6 +280,116 @@ __global__ __launch_bounds__(LN_THREADS) void layer_norm_kernel(ConvSegs segs, i
     }
 }
 
+// ---- backward (mpnhip_layer_norm_backward)
+constexpr int LNB_IMAGES = 8;                 // images per block of the affine gradients: the split is a function of n_images alone
+constexpr int LNB_THREADS = 256;
+
+// One block per image.  mean / rstd: layer_norm_kernel's own two passes and block sums (same order, same bits), written to
+// stats[img] = (mean, rstd); then (grad_in given) a = sum g gamma, b = sum g gamma xhat and grad_in = rstd (g gamma - a / F - xhat b / F).
+__global__ __launch_bounds__(LN_THREADS) void layer_norm_bwd_image_kernel(ConvSegs segs, int hw, int feat,
+                                                                          const float* __restrict__ weight, float eps,
+                                                                          const float* __restrict__ grad_out, int64_t go_stride,
+                                                                          float* __restrict__ grad_in, float* __restrict__ stats) {
+    __shared__ float red[LN_THREADS / 64];
+    const int64_t img = blockIdx.x;
+    const int t = threadIdx.x;
+    float s = 0.f;
+    for (int sg = 0; sg < segs.n; ++sg) {
+        const float* __restrict__ x = segs.p[sg] + img * segs.stride[sg];
+        const int n = segs.ch[sg] * hw;
+        for (int i = t; i < n; i += LN_THREADS) s += x[i];
+    }
+    const float mean = ln_block_sum(s, red) / (float)feat;
+    float q = 0.f;
+    for (int sg = 0; sg < segs.n; ++sg) {
+        const float* __restrict__ x = segs.p[sg] + img * segs.stride[sg];
+        const int n = segs.ch[sg] * hw;
+        for (int i = t; i < n; i += LN_THREADS) {
+            const float d = x[i] - mean;
+            q = fmaf(d, d, q);
+        }
+    }
+    const float rstd = 1.f / sqrtf(ln_block_sum(q, red) / (float)feat + eps);
+    if (t == 0) {
+        stats[2 * img] = mean;
+        stats[2 * img + 1] = rstd;
+    }
+    if (!grad_in) return;
+    const float* __restrict__ go = grad_out + img * go_stride;
+    float a = 0.f, b = 0.f;
+    int base = 0;
+    for (int sg = 0; sg < segs.n; ++sg) {
+        const float* __restrict__ x = segs.p[sg] + img * segs.stride[sg];
+        const int n = segs.ch[sg] * hw;
+        for (int i = t; i < n; i += LN_THREADS) {
+            const float gg = weight ? go[base + i] * weight[base + i] : go[base + i];
+            a += gg;
+            b = fmaf(gg, (x[i] - mean) * rstd, b);
+        }
+        base += n;
+    }
+    a = ln_block_sum(a, red) / (float)feat;
+    b = ln_block_sum(b, red) / (float)feat;
+    float* __restrict__ gi = grad_in + img * (int64_t)feat;
+    base = 0;
+    for (int sg = 0; sg < segs.n; ++sg) {
+        const float* __restrict__ x = segs.p[sg] + img * segs.stride[sg];
+        const int n = segs.ch[sg] * hw;
+        for (int i = t; i < n; i += LN_THREADS) {
+            const float gg = weight ? go[base + i] * weight[base + i] : go[base + i];
+            gi[base + i] = rstd * (gg - a - (x[i] - mean) * rstd * b);
+        }
+        base += n;
+    }
+}
+
+// grid (blocks along i, splits): one thread per element i, the block's LNB_IMAGES images one after the other.
+// w_partial / b_partial: [splits][feat], either may be nullptr
+__global__ __launch_bounds__(LNB_THREADS) void layer_norm_bwd_affine_kernel(ConvSegs segs, int hw, int feat,
+                                                                            const float* __restrict__ grad_out, int64_t go_stride,
+                                                                            const float* __restrict__ stats, int64_t n_images,
+                                                                            float* __restrict__ w_partial,
+                                                                            float* __restrict__ b_partial) {
+    const int i = blockIdx.x * LNB_THREADS + threadIdx.x;
+    if (i >= feat) return;
+    int sg = 0, base = 0;
+    while (i >= base + segs.ch[sg] * hw) {
+        base += segs.ch[sg] * hw;
+        ++sg;
+    }
+    const float* __restrict__ x = segs.p[sg] + (i - base);
+    const int64_t xs = segs.stride[sg];
+    const int64_t img0 = (int64_t)blockIdx.y * LNB_IMAGES;
+    const int64_t img1 = img0 + LNB_IMAGES < n_images ? img0 + LNB_IMAGES : n_images;
+    float sw = 0.f, sb = 0.f;
+    for (int64_t img = img0; img < img1; ++img) {
+        const float g = grad_out[img * go_stride + i];
+        sb += g;
+        if (w_partial) sw = fmaf(g, (x[img * xs] - stats[2 * img]) * stats[2 * img + 1], sw);
+    }
+    if (w_partial) w_partial[(int64_t)blockIdx.y * feat + i] = sw;
+    if (b_partial) b_partial[(int64_t)blockIdx.y * feat + i] = sb;
+}
+
+// out[i] = partial[0][i] + partial[1][i] + ... in that order, for the weight and the bias gradient (either may be nullptr)
+__global__ __launch_bounds__(LNB_THREADS) void layer_norm_bwd_sum_kernel(const float* __restrict__ w_partial,
+                                                                         const float* __restrict__ b_partial, int splits, int feat,
+                                                                         float* __restrict__ grad_weight,
+                                                                         float* __restrict__ grad_bias) {
+    const int i = blockIdx.x * LNB_THREADS + threadIdx.x;
+    if (i >= feat) return;
+    if (grad_weight) {
+        float s = 0.f;
+        for (int sp = 0; sp < splits; ++sp) s += w_partial[(int64_t)sp * feat + i];
+        grad_weight[i] = s;
+    }
+    if (grad_bias) {
+        float s = 0.f;
+        for (int sp = 0; sp < splits; ++sp) s += b_partial[(int64_t)sp * feat + i];
+        grad_bias[i] = s;
+    }
+}
+
 }  // namespace
 
 // the checks the entry points share (common.h); *cin: the channel total.  name: the entry point, for the message
@@ -400,6 +510,104 @@ extern "C" int mpnhip_layer_norm_forward(const float* const* seg_data, const int
     MPN_CHECK_ARG(n_images <= INT32_MAX, "%s: %lld images are more than one launch holds", name, (long long)n_images);
     layer_norm_kernel<<<(unsigned)n_images, LN_THREADS, 0, stream>>>(segs, (int)hw, (int)(c * hw), weight, bias, eps, out, out_stride);
     count_path(PC_LAYER_NORM);
+    MPN_LAUNCH_CHECK();
+    return MPNHIP_OK;
+}
+
+namespace mpnhip {
+namespace {
+
+int64_t ln_bwd_splits(int64_t n_images) { return (n_images + LNB_IMAGES - 1) / LNB_IMAGES; }
+
+// The regions of the backward's workspace; sized by the shape and by whether there is an affine
+struct LnBwdWs {
+    float* stats;         // [n_images][2]: mean, rstd
+    float* w_partial;     // [splits][feat]
+    float* b_partial;     // [splits][feat]
+};
+size_t ln_bwd_layout(int64_t n_images, int64_t feat, bool affine, void* workspace, LnBwdWs* ws) {
+    Carver c(workspace);
+    const size_t splits = (size_t)ln_bwd_splits(n_images);
+    ws->stats = c.take<float>((size_t)n_images * 2);
+    ws->w_partial = c.take<float>(affine ? splits * feat : 0);
+    ws->b_partial = c.take<float>(affine ? splits * feat : 0);
+    return c.bytes();
+}
+
+// every refusal that does not concern the workspace
+int ln_bwd_check(const char* name, const float* const* seg_data, const int64_t* seg_stride, const int* seg_channels, int n_segments,
+                 int64_t n_images, int64_t hw, const float* weight, float eps, const float* grad_out, int64_t grad_out_stride,
+                 const float* grad_in, const float* grad_weight, const float* grad_bias, ConvSegs* segs, int64_t* feat) {
+    MPN_CHECK_ARG(n_images >= 0, "%s: negative n_images", name);
+    MPN_CHECK_ARG(seg_data != nullptr && seg_stride != nullptr && seg_channels != nullptr, "%s: null segment lists", name);
+    MPN_CHECK_ARG(hw >= 1 && hw <= INT32_MAX, "%s: hw %lld must be positive and within 32 bits", name, (long long)hw);
+    MPN_CHECK_ARG(eps >= 0.f && isfinite(eps), "%s: eps %g", name, (double)eps);
+    int64_t c = 0;
+    MPN_TRY(check_segments(name, seg_data, seg_stride, seg_channels, n_segments, hw, segs, &c));
+    MPN_CHECK_ARG(grad_out != nullptr, "%s: null grad_out", name);
+    MPN_CHECK_ARG(grad_in != nullptr || grad_weight != nullptr || grad_bias != nullptr, "%s: no output wanted (all three are null)", name);
+    MPN_CHECK_ARG(weight != nullptr || (grad_weight == nullptr && grad_bias == nullptr),
+                  "%s: grad_weight / grad_bias without a weight (no affine: grad_in only)", name);
+    MPN_CHECK_ARG(grad_out_stride >= 0 && grad_out_stride <= INT32_MAX, "%s: grad_out_stride %lld outside the 32-bit range", name,
+                  (long long)grad_out_stride);
+    MPN_CHECK_ARG(n_images <= INT32_MAX && ln_bwd_splits(n_images) <= 65535, "%s: %lld images are more than one launch holds", name,
+                  (long long)n_images);
+    *feat = c * hw;
+    return MPNHIP_OK;
+}
+
+}  // namespace
+}  // namespace mpnhip
+
+extern "C" size_t mpnhip_layer_norm_backward_workspace_bytes(const float* const* seg_data, const int64_t* seg_stride,
+                                                             const int* seg_channels, int n_segments, int64_t n_images, int64_t hw,
+                                                             const float* weight, float eps, const float* grad_out,
+                                                             int64_t grad_out_stride, float* grad_in, float* grad_weight,
+                                                             float* grad_bias) {
+    ConvSegs segs;
+    int64_t feat = 0;
+    if (ln_bwd_check("mpnhip_layer_norm_backward_workspace_bytes", seg_data, seg_stride, seg_channels, n_segments, n_images, hw, weight, eps,
+                     grad_out, grad_out_stride, grad_in, grad_weight, grad_bias, &segs, &feat) != MPNHIP_OK)
+        return 0;
+    if (n_images == 0) return 0;
+    LnBwdWs ws;
+    return ln_bwd_layout(n_images, feat, weight != nullptr, nullptr, &ws);
+}
+
+extern "C" int mpnhip_layer_norm_backward(const float* const* seg_data, const int64_t* seg_stride, const int* seg_channels,
+                                          int n_segments, int64_t n_images, int64_t hw, const float* weight, float eps,
+                                          const float* grad_out, int64_t grad_out_stride, float* grad_in, float* grad_weight,
+                                          float* grad_bias, void* workspace, size_t workspace_bytes, void* stream_) {
+    static const char* const name = "mpnhip_layer_norm_backward";
+    hipStream_t stream = (hipStream_t)stream_;
+    ConvSegs segs;
+    int64_t feat64 = 0;
+    MPN_TRY(ln_bwd_check(name, seg_data, seg_stride, seg_channels, n_segments, n_images, hw, weight, eps, grad_out, grad_out_stride, grad_in,
+                         grad_weight, grad_bias, &segs, &feat64));
+    const int feat = (int)feat64;
+    if (n_images == 0) {
+        if (grad_weight) MPN_HIP(hipMemsetAsync(grad_weight, 0, sizeof(float) * feat, stream));
+        if (grad_bias) MPN_HIP(hipMemsetAsync(grad_bias, 0, sizeof(float) * feat, stream));
+        return MPNHIP_OK;
+    }
+    LnBwdWs ws;
+    const size_t need = ln_bwd_layout(n_images, feat, weight != nullptr, nullptr, &ws);
+    MPN_CHECK_ARG(workspace != nullptr && workspace_bytes >= need, "%s: workspace %zu < %zu", name, workspace ? workspace_bytes : (size_t)0,
+                  need);
+    ln_bwd_layout(n_images, feat, weight != nullptr, workspace, &ws);
+    count_path(PC_LAYER_NORM_BWD);
+
+    if (grad_in || grad_weight)     // (the bias gradient alone needs no statistics)
+        layer_norm_bwd_image_kernel<<<(unsigned)n_images, LN_THREADS, 0, stream>>>(segs, (int)hw, feat, weight, eps, grad_out,
+                                                                                   grad_out_stride, grad_in, ws.stats);
+    if (grad_weight || grad_bias) {
+        const int splits = (int)ln_bwd_splits(n_images);
+        const unsigned bx = (unsigned)((feat + LNB_THREADS - 1) / LNB_THREADS);
+        layer_norm_bwd_affine_kernel<<<dim3(bx, (unsigned)splits), LNB_THREADS, 0, stream>>>(
+            segs, (int)hw, feat, grad_out, grad_out_stride, ws.stats, n_images, grad_weight ? ws.w_partial : nullptr,
+            grad_bias ? ws.b_partial : nullptr);
+        layer_norm_bwd_sum_kernel<<<bx, LNB_THREADS, 0, stream>>>(ws.w_partial, ws.b_partial, splits, feat, grad_weight, grad_bias);
+    }
     MPN_LAUNCH_CHECK();
     return MPNHIP_OK;
 }

@@ -13,7 +13,7 @@ import torch
 from torch import nn
 
 from . import capi
-from .cnn import CNN, MaskRCNNPredictor, layer_norm_native
+from .cnn import CNN, MaskRCNNPredictor, layer_norm_native, layer_norm_native_autograd
 from .mlp import MLP
 
 
@@ -349,13 +349,22 @@ class MaskModel(nn.Module):
         x = layer_norm_native([feats, node_embeds], ln.weight, ln.bias, ln.eps)
         return self.mask_predictor.forward_native([self.mask_head.forward_native([x])])
 
-    def forward_native_autograd(self, feature_embeds, node_embeds):
+    def forward_native_autograd(self, feature_embeds, node_embeds, all_layers=False):
         """``forward`` for training with the Conv2d layers native in both directions (``forward_native_autograd`` of the two CNNs
         and of ``mask_predictor``, whose last 1 x 1 layer is the native one); the concatenation, the LayerNorm and the transposed
-        convolution are the stock modules."""
+        convolution are the stock modules.  ``all_layers``: those too are native -- the LayerNorm reads (feats, node_embeds) as two
+        segments (``layer_norm_native_autograd``: no ``torch.cat``) and the transposed convolutions go through
+        ``conv_transpose2d_native_autograd``, so no stock module of the branch runs."""
         feats = self.feature_encoder.forward_native_autograd([feature_embeds])
-        x = self.layer_norm(torch.cat((feats, node_embeds), dim=1))
-        return self.mask_predictor.forward_native_autograd([self.mask_head.forward_native_autograd([x])])
+        if all_layers:
+            ln = self.layer_norm
+            shape = (feats.shape[1] + node_embeds.shape[1],) + tuple(feats.shape[2:])
+            if shape != tuple(ln.normalized_shape):
+                raise capi.MpnhipError("LayerNorm(%s) does not fit the %s features" % (tuple(ln.normalized_shape), shape))
+            x = layer_norm_native_autograd([feats, node_embeds], ln.weight, ln.bias, ln.eps)
+        else:
+            x = self.layer_norm(torch.cat((feats, node_embeds), dim=1))
+        return self.mask_predictor.forward_native_autograd([self.mask_head.forward_native_autograd([x])], transposed_native=all_layers)
 
 
 class MOTMPNet(nn.Module):
@@ -372,7 +381,10 @@ class MOTMPNet(nn.Module):
     on the device or a module is outside what the kernels cover (``native_supported``).  ``mask_conv_grads = 'native'`` is the
     training-side selector: while gradients are recorded, every Conv2d of the branch runs the native forward under autograd with
     ``mpnhip_conv2d_backward`` (csrc/conv_backward.hip) as its backward; ConvTranspose2d, LayerNorm and the ``torch.cat`` in front
-    of it stay stock, and the same conditions and silent fall-back apply.
+    of it stay stock, and the same conditions and silent fall-back apply.  ``mask_conv_grads = 'native_all'`` is that route with
+    the two ConvTranspose2d layers (``mpnhip_conv_transpose2d_backward``) and the LayerNorm (``mpnhip_layer_norm_backward``, its
+    input read as two segments) native as well: no MIOpen or aten module of the branch runs, and every gradient of the branch
+    repeats bit for bit.
     It is built only when ``model_params`` carries the mask-branch dicts (as configs/tracking_cfg.yaml does) and
     evaluated only when ``data.x_ext`` is present; otherwise ``mask_predictions`` is an empty list.
     """
@@ -401,11 +413,12 @@ class MOTMPNet(nn.Module):
         self.keep_packed_weights = False
         # 'stock' | 'native': how mask_predictions runs the mask branch's convolutions and LayerNorm (see the class docstring)
         self.mask_convs = 'stock'
-        # 'stock' | 'native': the route of mask_predictions WHILE GRADIENTS ARE RECORDED.  'native': every Conv2d of the mask branch
+        # 'stock' | 'native' | 'native_all': the route of mask_predictions WHILE GRADIENTS ARE RECORDED.  'native': every Conv2d of the mask branch
         # runs mpnhip_conv2d_forward under autograd with mpnhip_conv2d_backward as its backward (csrc/conv_backward.hip): one
         # arithmetic per layer, no algorithm search, gradients that repeat bit for bit.  ConvTranspose2d, LayerNorm and the
-        # torch.cat in front of it stay stock modules.  Same conditions as mask_convs (device tensors, covered stacks), same
-        # silent fall-back to the stock route.
+        # torch.cat in front of it stay stock modules.  'native_all': those too (mpnhip_conv_transpose2d_backward,
+        # mpnhip_layer_norm_backward).  Same conditions as mask_convs (device tensors, covered stacks), same silent fall-back to the
+        # stock route.
         self.mask_conv_grads = 'stock'
 
     def _build_core_MPNet(self, model_params, encoder_feats_dict):
@@ -661,12 +674,13 @@ class MOTMPNet(nn.Module):
         L, k = int(self.num_enc_steps), int(self.num_class_steps)
         if self.mask_convs not in ('stock', 'native'):
             raise capi.MpnhipError("mask_convs must be 'stock' or 'native', not %r" % (self.mask_convs,))
-        if self.mask_conv_grads not in ('stock', 'native'):
-            raise capi.MpnhipError("mask_conv_grads must be 'stock' or 'native', not %r" % (self.mask_conv_grads,))
+        if self.mask_conv_grads not in ('stock', 'native', 'native_all'):
+            raise capi.MpnhipError("mask_conv_grads must be 'stock', 'native' or 'native_all', not %r" % (self.mask_conv_grads,))
         if self.mask_convs == 'native' and self._mask_native_ok(x_ext, edge_index, logits):
             return self._mask_predictions_native(x_ext, edge_index, logits, holder, last_only)
-        if self.mask_conv_grads == 'native' and self._mask_native_grad_ok(x_ext, edge_index, logits):
-            return self._mask_predictions_native_grad(x_ext, edge_index, logits, holder, last_only)
+        if self.mask_conv_grads in ('native', 'native_all') and self._mask_native_grad_ok(x_ext, edge_index, logits):
+            return self._mask_predictions_native_grad(x_ext, edge_index, logits, holder, last_only,
+                                                      all_layers=self.mask_conv_grads == 'native_all')
         latent_node_ext_feats = self.node_ext_encoder(x_ext)                           # mpn.py:356
         initial_node_ext_feats = latent_node_ext_feats
         first_class_step = L - k + 1
@@ -705,8 +719,9 @@ class MOTMPNet(nn.Module):
         """The conditions of ``mask_conv_grads = 'native'``: the same tensors and modules, and a gradient being recorded."""
         return self._mask_native_covered(x_ext, edge_index, logits) and self._mask_grads_recorded(x_ext, logits)
 
-    def _mask_predictions_native_grad(self, x_ext, edge_index, logits, holder, last_only):
-        """``mask_predictions`` under autograd with every Conv2d native in both directions.  The steps are those of the stock route
+    def _mask_predictions_native_grad(self, x_ext, edge_index, logits, holder, last_only, all_layers=False):
+        """``mask_predictions`` under autograd with every Conv2d native in both directions; ``all_layers``: the LayerNorm and the
+        transposed convolutions of ``mask_predictor`` too.  The steps are those of the stock route
         (the ``initial || latent`` concatenation is a ``torch.cat``: the saved tensors of a step must outlive the next one, so
         the buffer reuse of the inference route does not apply)."""
         L, k = int(self.num_enc_steps), int(self.num_class_steps)
@@ -719,9 +734,9 @@ class MOTMPNet(nn.Module):
                 latent = torch.cat((initial, latent), dim=1)
             latent = self.MPAttentionNet.aggregate_native_autograd(latent, edge_index, logits[step - 1], holder=holder)   # mpn.py:377
             if step >= first_class_step and (step == L or not last_only):
-                preds.append(self.mask_predictor.forward_native_autograd(x_ext, latent))
+                preds.append(self.mask_predictor.forward_native_autograd(x_ext, latent, all_layers=all_layers))
         if L == 0:
-            preds.append(self.mask_predictor.forward_native_autograd(x_ext, latent))
+            preds.append(self.mask_predictor.forward_native_autograd(x_ext, latent, all_layers=all_layers))
         return preds
 
     def _mask_predictions_native(self, x_ext, edge_index, logits, holder, last_only):

@@ -394,7 +394,8 @@ class TrainStep:
         """Everything a resumed run needs, keyed by parameter NAME (not by flat offset, so a checkpoint does not depend on the bucket
         layout): the model's ``state_dict``, Adam's ``exp_avg`` / ``exp_avg_sq`` per parameter, the call count ``t``, the device-side
         count of skipped calls, the optimizer's hyper-parameters, ``train_mask_branch`` and the model's ``mask_conv_grads`` selector
-        (which backward the mask branch's convolutions took).  Tensors are copies on their device."""
+        ('stock', 'native' or 'native_all': which backward the mask branch's convolutions, transposed convolutions and LayerNorm
+        took).  Tensors are copies on their device."""
         b, o = self.bucket, self.opt
         names = self._param_names()
 

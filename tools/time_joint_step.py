@@ -65,8 +65,9 @@ def main():
     ap.add_argument("--runs", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--graphs", type=int, default=2)
-    ap.add_argument("--mask-conv-grads", choices=("stock", "native"), default="stock",
-                    help="MOTMPNet.mask_conv_grads of BOTH routes: the backward of the mask branch's Conv2d layers")
+    ap.add_argument("--mask-conv-grads", choices=("stock", "native", "native_all"), default="stock",
+                    help="MOTMPNet.mask_conv_grads of BOTH routes: the backward of the mask branch's Conv2d layers (native_all: of its "
+                         "transposed convolutions and LayerNorm too)")
     ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "joint_step",
                                                   "timing.json"))
     a = ap.parse_args()

@@ -1,12 +1,13 @@
 #!/usr/bin/env python3
 """Time of the mask branch in TRAINING: MOTMPNet.mask_predictions forward + backward with the stock convolution backward (MIOpen
-under autograd) and with the native one (mask_conv_grads = 'stock' | 'native': mpnhip_conv2d_forward under autograd,
-mpnhip_conv2d_backward), on the batch of tools/time_joint_step.py: 2 graphs of synth.make_knn_graph(frames=20, dets=7, top_k=100)
+under autograd), with the native Conv2d one (mask_conv_grads = 'native': mpnhip_conv2d_forward under autograd,
+mpnhip_conv2d_backward) and with every layer native ('native_all': mpnhip_conv_transpose2d_backward and
+mpnhip_layer_norm_backward as well), on the batch of tools/time_joint_step.py: 2 graphs of synth.make_knn_graph(frames=20, dets=7, top_k=100)
 (280 nodes, 28,748 edges), synth.MASK_PARAMS, L = 4 with 2 classified steps, x_ext [280, 256, 14, 14].  The loss is sum(pred * r)
 with fixed r; the logits are a leaf that takes a gradient, x_ext takes none -- what the joint training step asks of the branch.
 
-Both selectors are timed in the same process with device events, alternating, after 5 warm-up calls each; reported are the median
-and the min .. max of at least 20 calls, and the largest difference between the two routes' parameter gradients.  The first call of
+The selectors are timed in the same process with device events, alternating, after 5 warm-up calls each; reported are the median
+and the min .. max of at least 20 calls, and the largest difference between each native route's parameter gradients and the stock route's.  The first call of
 each selector (code-object load, the library's algorithm search) is timed in a fresh child process of its own.
 
 Writes profiles/mask_convs/train_timing.json (or --out).  Needs a GPU: there is no CPU fall-back."""
@@ -25,7 +26,7 @@ from mpntrackseg_amd import synth
 from mpntrackseg_amd.mpn import MOTMPNet
 
 L = 4
-SELECTORS = ("stock", "native")
+SELECTORS = ("stock", "native", "native_all")
 
 
 def problem(dev):
@@ -101,20 +102,21 @@ def main():
     torch.cuda.synchronize()
     times = {sel: [] for sel in SELECTORS}
     for _ in range(runs):
-        for sel in SELECTORS:              # alternating: both routes see the same neighbours on the machine
+        for sel in SELECTORS:              # alternating: the routes see the same neighbours on the machine
             t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             t0.record()
             run(model, x_ext, ei, logits, r, holder, sel)
             t1.record()
             t1.synchronize()
             times[sel].append(t0.elapsed_time(t1))
-    diff = max(float((n_ - s_).abs().max() / s_.abs().max().clamp_min(1e-30)) for n_, s_ in zip(grads["native"], grads["stock"]))
+    rel = lambda sel: max(float((n_ - s_).abs().max() / s_.abs().max().clamp_min(1e-30)) for n_, s_ in zip(grads[sel], grads["stock"]))
     res = {"problem": {"graphs": 2, "nodes": int(x_ext.shape[0]), "edges": int(ei.shape[1]), "L": L, "x_ext": list(x_ext.shape)},
            "what": "mask_predictions forward + backward, device events, ms", "runs": runs, "warmup": a.warmup,
-           "native_vs_stock_max_rel_grad_diff": diff}
+           "native_vs_stock_max_rel_grad_diff": rel("native"), "native_all_vs_stock_max_rel_grad_diff": rel("native_all")}
     for sel, ts in times.items():
         res[sel] = {"median_ms": statistics.median(ts), "min_ms": min(ts), "max_ms": max(ts)}
     res["native_over_stock_median"] = res["native"]["median_ms"] / res["stock"]["median_ms"]
+    res["native_all_over_stock_median"] = res["native_all"]["median_ms"] / res["stock"]["median_ms"]
     for sel in SELECTORS:                  # a fresh process per selector: nothing loaded, nothing tuned
         p = subprocess.run([sys.executable, os.path.abspath(__file__), "--first-call", sel], capture_output=True, text=True, timeout=600)
         line = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
