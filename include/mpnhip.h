@@ -818,6 +818,49 @@ int mpnhip_layer_norm_backward(const float* const* seg_data, const int64_t* seg_
                                int64_t grad_out_stride, float* grad_in, float* grad_weight, float* grad_bias, void* workspace,
                                size_t workspace_bytes, void* stream);
 
+/* ReID ResNet50 (models/resnet.py), inference: ONE nn.Conv2d(cin, cout, ksize, stride, padding ksize / 2, bias=False) with the
+ * eval-mode BatchNorm, the residual add and the ReLU behind it.  ksize 1, 3 or 7; stride 1 or 2; Hout = (H - 1) / stride + 1,
+ * Wout likewise.  Everything is NCHW fp32.
+ *   x         image i at x + i * x_stride (floats), dense [cin][H][W]
+ *   weight    [cout][cin][ksize][ksize], as the module stores it
+ *   scale, shift   [cout] each or NULL (1 and 0 stand in): the folded BatchNorm, gamma / sqrt(var + eps) and beta - mean * scale
+ *   residual  NULL, or image i at residual + i * residual_stride, dense [cout][Hout][Wout]
+ *   out       image i at out + i * out_stride, dense [cout][Hout][Wout]: a stride wider than that writes a channel slice of a
+ *             wider tensor and leaves the rest alone.  out must not overlap x or residual (not checked).
+ * Result, in this float32 order: v = fmaf(acc, scale[m], shift[m]); v += residual; relu != 0: v = max(v, 0).
+ *
+ * acc is an implicit GEMM on v_mfma_f32_32x32x2_f32 (exact fp32 products, fp32 accumulation): M = cout, N = n_images * Hout * Wout
+ * -- the output pixels of ALL images packed into one column index, so a small map fills the 32-column tiles --, K = cin * ksize^2
+ * walked in (channel, then tap) order, one chain per output, no split of K across blocks, no float atomics: an output's bits are
+ * a function of the layer and of its image alone, not of n_images and not of the image's position in the batch.  No workspace.
+ * K > 2048 (the 3 x 3 layers of 256 and 512 channels): the chain is cut into groups of four K chunks (a chunk: 32 channels of a
+ * 1 x 1, 4 channels of a 3 x 3) -- every group is summed from zero and added to the running total, groups in order; one chain of
+ * K = 4608 measured 2.5e-6 of the largest output against float64, above the 2e-6 the shorter chains are held to.  The grouping is
+ * a function of the layer alone as well.  The block shape (128 x 128; 64 rows x 256 columns for cout <= 64; 64 x 64 when fewer than
+ * 512 of the large blocks would be launched) does depend on n_images, and does not show in the bits: the chain is the same in all
+ * three.  Path counters: conv_affine_tile (every launch), conv_affine_grouped (K > 2048), conv_affine_small_grid (64 x 64 blocks),
+ * conv_affine_wide (64 x 256 blocks); a launch counted by neither of the last two ran 128 x 128 blocks.
+ *
+ * MPNHIP_ERR_ARG before any launch, the message starting with the entry point's name: null args; n_images < 0; (n_images == 0 is
+ * a successful no-op, nothing else is looked at;) null x, weight or out; a ksize other than 1, 3, 7; a stride other than 1, 2;
+ * H, W, cin or cout < 1; and any stride, image size (cin * H * W, cout * Hout * Wout) or weight count beyond INT32_MAX,
+ * n_images * Hout * Wout beyond INT32_MAX - 256 (a block's column indices run past the last column), or more blocks than a
+ * launch holds. */
+typedef struct mpnhip_conv_affine_args {
+    const float* x; int64_t x_stride; const float* weight; const float* scale; const float* shift;
+    const float* residual; int64_t residual_stride; int relu; float* out; int64_t out_stride;
+    int64_t n_images; int cin; int cout; int H; int W; int ksize; int stride;
+} mpnhip_conv_affine_args;
+int mpnhip_conv2d_affine_forward(const mpnhip_conv_affine_args* args, void* stream);
+
+/* nn.MaxPool2d(3, stride 2, padding 1) (the ReID ResNet50's stem): image i at x + i * x_stride, dense [C][H][W], to out + i *
+ * out_stride, dense [C][Hout][Wout] with Hout = (H - 1) / 2 + 1, Wout likewise.  Padded cells do not take part: a window of
+ * negative values yields the largest of them, never 0.  One thread per output element.  MPNHIP_ERR_ARG before any launch:
+ * n_images < 0 (0 is a successful no-op), null x or out, C, H or W < 1, a stride or an input image beyond INT32_MAX, more
+ * elements than a launch holds. */
+int mpnhip_maxpool2d_forward(const float* x, int64_t x_stride, int64_t n_images, int C, int H, int W, float* out, int64_t out_stride,
+                             void* stream);
+
 /* torch.optim.Adam(lr, betas, eps, weight_decay).step() (the optimizer of pl_module.py:76-77, configs/tracking_cfg.yaml:6-10)
  * over FLAT fp32 buffers of n elements: parameters, gradients (as the backward / all-reduce left them) and the two
  * moment buffers (zero before step 1); step = 1, 2, ... counts the calls. */

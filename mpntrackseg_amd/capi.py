@@ -151,6 +151,17 @@ class ConvBwdArgs(C.Structure):
     ]
 
 
+class ConvAffineArgs(C.Structure):
+    """``mpnhip_conv_affine_args`` (include/mpnhip.h): one Conv2d + folded BatchNorm + residual + ReLU of
+    ``mpnhip_conv2d_affine_forward``."""
+    _fields_ = [
+        ("x", C.c_void_p), ("x_stride", C.c_int64), ("weight", C.c_void_p), ("scale", C.c_void_p), ("shift", C.c_void_p),
+        ("residual", C.c_void_p), ("residual_stride", C.c_int64), ("relu", C.c_int), ("out", C.c_void_p), ("out_stride", C.c_int64),
+        ("n_images", C.c_int64), ("cin", C.c_int), ("cout", C.c_int), ("H", C.c_int), ("W", C.c_int), ("ksize", C.c_int),
+        ("stride", C.c_int),
+    ]
+
+
 _P, _I, _L, _Z = C.c_void_p, C.c_int, C.c_int64, C.c_size_t
 SIGNATURES = {
     "mpnhip_version": (C.c_char_p, []),
@@ -239,6 +250,8 @@ SIGNATURES = {
                                                         C.c_float, _P, _L, _P, _P, _P]),
     "mpnhip_layer_norm_backward": (_I, [C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int), _I, _L, _L, _P, C.c_float, _P,
                                         _L, _P, _P, _P, _P, _Z, _P]),
+    "mpnhip_conv2d_affine_forward": (_I, [C.POINTER(ConvAffineArgs), _P]),
+    "mpnhip_maxpool2d_forward": (_I, [_P, _L, _L, _I, _I, _I, _P, _L, _P]),
     "mpnhip_adam_step": (_I, [_P, _P, _P, _P, _L, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _I, _P]),
     "mpnhip_adam_step_guarded": (_I, [_P, _P, _P, _P, _L, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _I, _P, _P]),
     "mpnhip_adam_step_counted": (_I, [_P, _P, _P, _P, _L, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _I, _P, _P, _P]),

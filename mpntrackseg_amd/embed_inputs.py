@@ -1,6 +1,10 @@
 """The inputs of the two embedding CNNs of the reference's ``MOTSeqProcessor._store_embeddings``
-(``data/seq_processing/seq_processor.py:395-562``), on the device and without ``torchvision`` or ``PIL``.  The CNNs themselves --
-the torchreid ResNet50 and the Mask R-CNN FPN backbone -- stay stock modules; what surrounds them is here:
+(``data/seq_processing/seq_processor.py:395-562``), on the device and without ``torchvision`` or ``PIL``.  The Mask R-CNN FPN
+backbone stays a stock module; the torchreid ResNet50 is ``reid_net.ResNet`` (stock modules by default, native kernels on
+request); what surrounds them is here:
+
+``reid_embeddings``           crops -> the ReID CNN (``convs='stock' | 'native'``) -> node-core maps and ReID vectors;
+``store_reid_embeddings``     their per-frame files (``seq_processor.py:443-475``);
 
 ``reid_crops``                ``BoundingBoxDataset.__getitem__`` (``utils/rgb.py:40-69``) for all boxes at once: crop,
                               ``np.pad(mode='mean')``, ``PIL.Image.resize`` (bilinear, bit for bit), ``ToTensor``, ``Normalize``;
@@ -127,6 +131,51 @@ def reid_crops(frames, boxes, box_frame, output_size=(128, 64), pad=True, mean=I
             check(lib.mpnhip_reid_crops(ptr(frames), B, H, W, ptr(gd), ptr(fd), m, max_ph, max_pw, oh, ow, mean_std, ptr(out[k0:k0 + m]),
                                         ptr(u8[k0:k0 + m]) if return_uint8 else None, ptr(ws), ws.numel(), stream_ptr()), "mpnhip_reid_crops")
     return (out, u8) if return_uint8 else out
+
+
+def reid_embeddings(net, frames, det, box_frame, convs='stock', batch_size=1000):
+    """The ReID CNN over the detections ``det`` (``seq_processor.py:411-441``): ``reid_crops`` -> ``net`` (a
+    ``reid_net.ResNet`` in eval mode on the device of ``frames``) -> ``(node_core [n, 2048, 8, 4], reid [n, 256])`` on the device.
+    ``convs='stock'`` (the default) runs ``net.forward`` -- the stock modules -- under ``no_grad`` in batches of ``batch_size``
+    (the reference's ``img_batch_size``); ``convs='native'`` runs ``net.forward_native`` (csrc/conv_strided.hip) in slices of
+    ``batch_size``.  ``frames``, ``det`` (boxes or a table with the ``bb_*`` columns) and ``box_frame`` as for ``reid_crops``.
+    No detections give empty tensors of the right shapes on both routes."""
+    if convs not in ('stock', 'native'):
+        raise ValueError("convs must be 'stock' or 'native', not %r" % (convs,))
+    crops = reid_crops(frames, det, box_frame)
+    step = max(int(batch_size), 1)
+    if crops.shape[0] == 0:                 # no detections: empty results on either route, the network is not run
+        fshape, width = net.output_shapes(int(crops.shape[2]), int(crops.shape[3]))
+        return crops.new_empty((0,) + tuple(fshape)), crops.new_empty((0, width))
+    if convs == 'native':
+        return net.forward_native(crops, max_images=step)
+    with torch.no_grad():
+        parts = [net(crops[k0:k0 + step]) for k0 in range(0, crops.shape[0], step)]
+    return torch.cat([p[0] for p in parts], dim=0), torch.cat([p[1] for p in parts], dim=0)
+
+
+def store_reid_embeddings(seq_path, det_file_name, reid_dir, node_core_dir, frame, detection_id, node_core, reid):
+    """The files of ``seq_processor.py:443-475``: ``<seq_path>/processed_data/embeddings/<det_file_name>/<reid_dir>/<frame>.pt``
+    ([n_f, 1 + 256], the detection id in column 0) and ``.../<node_core_dir>/<frame>.pt`` ([n_f, 1 + 2048, 8, 4], the id
+    broadcast into channel 0), through ``embeddings.write_frame_embeddings``.  A directory that exists is removed first, as the
+    reference does.  Returns the two directories relative to ``processed_data``: the ``embeddings_dir`` arguments of
+    ``embeddings.load_precomputed_embeddings(..., '1D')`` and ``(..., '3D')``."""
+    import shutil
+    from .embeddings import write_frame_embeddings
+    frame = np.asarray(frame).reshape(-1)
+    ids = np.asarray(detection_id).reshape(-1)
+    reid, node_core = torch.as_tensor(reid).detach(), torch.as_tensor(node_core).detach()
+    if reid.dim() != 2 or node_core.dim() != 4 or not (reid.shape[0] == node_core.shape[0] == frame.size == ids.size):
+        raise MpnhipError("reid [n, D] and node_core [n, C, H, W] need one row per entry of frame and detection_id")
+    rels = []
+    for sub, emb in ((reid_dir, reid), (node_core_dir, node_core)):
+        rel = osp.join("embeddings", det_file_name, sub)
+        d = osp.join(seq_path, "processed_data", rel)
+        if osp.exists(d):
+            shutil.rmtree(d)
+        write_frame_embeddings(seq_path, rel, frame, ids, emb.float().cpu())
+        rels.append(rel)
+    return tuple(rels)
 
 
 # ------------------------------------------------------------------------------------------------ FPN RoIAlign

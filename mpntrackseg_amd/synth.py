@@ -186,6 +186,40 @@ def make_mask_weights(seed=17, bias_std=0.05):
     return out
 
 
+REID_INPUT_STREAM = 100000   # the stream of the ReID test crops: synth.normal(seed, (3, 3, 128, 64), stream=REID_INPUT_STREAM)
+
+
+def make_reid_weights(net, seed):
+    """Fills every ``state_dict`` entry of a ReID ResNet (``reid_net.ResNet`` or the reference's), in ``state_dict`` order, from
+    stream i = its index (``num_batches_tracked`` is skipped, its index is not reused): Conv2d weights He-scaled
+    (std = sqrt(2 / (cin k k))), Linear weights std = sqrt(2 / in_features), Linear biases std 0.05, BatchNorm weight and
+    ``running_var`` 0.75 + 0.5 uniform01, BatchNorm bias and ``running_mean`` N(0, 0.1^2).  Loads them into ``net`` and returns
+    {key: float32 ndarray}."""
+    import torch
+    sd = net.state_dict()
+    out = {}
+    for i, (k, t) in enumerate(sd.items()):
+        shp = tuple(t.shape)
+        prefix, leaf = k.rsplit(".", 1)
+        if leaf == "num_batches_tracked":
+            continue
+        if leaf == "weight" and len(shp) == 4:
+            v = normal(seed, shp, stream=i, std=math.sqrt(2.0 / (shp[1] * shp[2] * shp[3])))
+        elif leaf == "weight" and len(shp) == 2:
+            v = normal(seed, shp, stream=i, std=math.sqrt(2.0 / shp[1]))
+        elif leaf in ("weight", "running_var"):
+            v = (0.75 + 0.5 * uniform01(seed, shp[0], stream=i)).astype(np.float32)
+        elif leaf == "bias" and sd[prefix + ".weight"].dim() == 2:
+            v = normal(seed, shp, stream=i, std=0.05)
+        else:                                   # BatchNorm bias, running_mean
+            v = normal(seed, shp, stream=i, std=0.1)
+        out[k] = v
+    full = dict(sd)
+    full.update({k: torch.from_numpy(v).to(sd[k].dtype) for k, v in out.items()})
+    net.load_state_dict(full)
+    return out
+
+
 def make_weights(p, seed=7, bias_std=0.1, gain=1.0):
     """He-normal weights (std = gain*sqrt(2/fan_in)), biases N(0, bias_std^2); one RNG stream per
     tensor in ``hot_path_param_shapes`` order. Returns {key: float32 ndarray}."""
