@@ -663,7 +663,8 @@ int mpnhip_edge_labels(const int64_t* edge_index, int64_t n_edges, const int64_t
  * graph its own mean over its own valid rows, a graph without one contributes nothing, the n_graphs losses averaged (as
  * mpnhip_tracking_loss_graphs).  Without it n_graphs must be 1.
  * All steps run in ONE launch; 16-byte accesses when every base pointer and row_floats allow them, 4-byte ones otherwise.
- * Per-block partial sums are added in double in a fixed order: the loss is bitwise reproducible.  No host read. */
+ * Per-block partial sums are added in double in a fixed order, and which elements a thread sums depends on row_floats alone:
+ * the loss is bitwise reproducible, also between differently aligned copies of the same tensors.  No host read. */
 size_t mpnhip_mask_loss_workspace_bytes(int n_steps, int64_t n_nodes, int64_t row_floats, int n_graphs);
 int mpnhip_mask_loss(const float* const* preds, int n_steps, const float* labels, const uint8_t* valid, const int32_t* node_graph,
                      int n_graphs, int64_t n_nodes, int64_t row_floats, float weight, float* loss_out, float* const* grads,

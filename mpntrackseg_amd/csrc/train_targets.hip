@@ -90,10 +90,30 @@ __device__ __forceinline__ float lane(const float& v, int) { return v; }
 __device__ __forceinline__ void set_lane(float4& v, int i, float x) { if (i == 0) v.x = x; else if (i == 1) v.y = x; else if (i == 2) v.z = x; else v.w = x; }
 __device__ __forceinline__ void set_lane(float& v, int, float x) { v = x; }
 
-// One block = one chunk of one node's row ([N, P] rows; V floats per access: 4 when every base and P allow 16-byte accesses).
+// a unit of V floats at unit index i of `base`: one 16-byte access (WIDE: V == 4 and the base on a 16-byte boundary) or V 4-byte ones
+template <int V, bool WIDE>
+__device__ __forceinline__ typename Pack<V>::T load_unit(const float* __restrict__ base, int64_t i) {
+    using T = typename Pack<V>::T;
+    if constexpr (WIDE || V == 1) return reinterpret_cast<const T*>(base)[i];
+    T v;
+#pragma unroll
+    for (int j = 0; j < V; ++j) set_lane(v, j, base[i * V + j]);
+    return v;
+}
+template <int V, bool WIDE>
+__device__ __forceinline__ void store_unit(float* __restrict__ base, int64_t i, const typename Pack<V>::T& v) {
+    using T = typename Pack<V>::T;
+    if constexpr (WIDE || V == 1) { reinterpret_cast<T*>(base)[i] = v; return; }
+#pragma unroll
+    for (int j = 0; j < V; ++j) base[i * V + j] = lane(v, j);
+}
+
+// One block = one chunk of one node's row ([N, P] rows in units of V floats: 4 when P is a multiple of 4, else 1; WIDE: every base
+// allows 16-byte accesses.  Which element a thread takes and the order of every sum depend on V alone, so the loss of a row shape
+// does not depend on where the allocator put the tensors: bit-equal results with and without WIDE).
 // block b: node b / cpr, units [(b % cpr) * chunk, ...) of the row's P / V units.  partial[s][b] = the block's sum of the BCE terms
 // of step s divided by the valid rows of the node's graph (0 for a row that is not valid).
-template <int V>
+template <int V, bool WIDE>
 __global__ __launch_bounds__(256) void k_mask_bce(MaskPtrs p, int k, const float* __restrict__ labels, const unsigned char* __restrict__ valid,
                                                   const int* __restrict__ node_graph, int K, const int* __restrict__ counts, int64_t P,
                                                   int cpr, int chunk, float weight, float* __restrict__ partial) {
@@ -112,7 +132,7 @@ __global__ __launch_bounds__(256) void k_mask_bce(MaskPtrs p, int k, const float
         for (int64_t u = u0 + threadIdx.x; u < u1; u += 256) {
 #pragma unroll
             for (int s = 0; s < MASK_MAX_STEPS; ++s)
-                if (s < k) reinterpret_cast<T*>(p.grad[s])[row + u] = zero;
+                if (s < k) store_unit<V, WIDE>(p.grad[s], row + u, zero);
         }
         if ((int)threadIdx.x < k) partial[(int64_t)threadIdx.x * gridDim.x + blockIdx.x] = 0.f;
         return;
@@ -123,11 +143,11 @@ __global__ __launch_bounds__(256) void k_mask_bce(MaskPtrs p, int k, const float
 #pragma unroll
     for (int s = 0; s < MASK_MAX_STEPS; ++s) acc[s] = 0.f;
     for (int64_t u = u0 + threadIdx.x; u < u1; u += 256) {
-        const T y = reinterpret_cast<const T*>(labels)[row + u];
+        const T y = load_unit<V, WIDE>(labels, row + u);
 #pragma unroll
         for (int s = 0; s < MASK_MAX_STEPS; ++s) {
             if (s < k) {
-                const T z = reinterpret_cast<const T*>(p.pred[s])[row + u];
+                const T z = load_unit<V, WIDE>(p.pred[s], row + u);
                 T gr;
                 float t = 0.f;
 #pragma unroll
@@ -139,7 +159,7 @@ __global__ __launch_bounds__(256) void k_mask_bce(MaskPtrs p, int k, const float
                     set_lane(gr, j, (sg - yj) * gs);
                 }
                 acc[s] += t;
-                reinterpret_cast<T*>(p.grad[s])[row + u] = gr;
+                store_unit<V, WIDE>(p.grad[s], row + u, gr);
             }
         }
     }
@@ -271,15 +291,16 @@ extern "C" int mpnhip_mask_loss(const float* const* preds, int n_steps, const fl
     }
     MPN_CHECK_ARG(preds && grads && labels && valid && loss_out, "mask_loss: null tensor");
     MaskPtrs p = {};
-    bool vec = (row_floats & 3) == 0 && aligned16(labels);
+    const bool quad = (row_floats & 3) == 0;   // units of 4 floats; with every base on a 16-byte boundary one access each
+    bool wide = quad && aligned16(labels);
     for (int i = 0; i < n_steps; ++i) {
         MPN_CHECK_ARG(preds[i] && grads[i], "mask_loss: null tensor of step %d", i);
         p.pred[i] = preds[i];
         p.grad[i] = grads[i];
-        vec = vec && aligned16(preds[i]) && aligned16(grads[i]);
+        wide = wide && aligned16(preds[i]) && aligned16(grads[i]);
     }
     int cpr, chunk;
-    mask_plan(vec ? row_floats / 4 : row_floats, &cpr, &chunk);
+    mask_plan(quad ? row_floats / 4 : row_floats, &cpr, &chunk);
     MPN_CHECK_ARG(n_nodes <= (int64_t)INT_MAX / cpr, "mask_loss: %lld rows of %lld floats exceed one launch", (long long)n_nodes,
                   (long long)row_floats);
     const MaskLossView v = mask_loss_view(workspace, n_steps, n_nodes, row_floats, n_graphs);
@@ -289,12 +310,9 @@ extern "C" int mpnhip_mask_loss(const float* const* preds, int n_steps, const fl
     hipLaunchKernelGGL(k_mask_counts, dim3(blocks_for(n_nodes)), dim3(256), (size_t)n_graphs * sizeof(int), s, valid,
                        node_graph, n_nodes, n_graphs, v.counts);
     MPN_LAUNCH_CHECK();
-    if (vec)
-        hipLaunchKernelGGL(k_mask_bce<4>, dim3((unsigned)nblk), dim3(256), 0, s, p, n_steps, labels, valid, node_graph, n_graphs, v.counts,
-                           row_floats, cpr, chunk, weight, v.partial);
-    else
-        hipLaunchKernelGGL(k_mask_bce<1>, dim3((unsigned)nblk), dim3(256), 0, s, p, n_steps, labels, valid, node_graph, n_graphs, v.counts,
-                           row_floats, cpr, chunk, weight, v.partial);
+    auto* kernel = wide ? k_mask_bce<4, true> : (quad ? k_mask_bce<4, false> : k_mask_bce<1, false>);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)nblk), dim3(256), 0, s, p, n_steps, labels, valid, node_graph, n_graphs, v.counts,
+                       row_floats, cpr, chunk, weight, v.partial);
     MPN_LAUNCH_CHECK();
     // (the block sums were divided by their graph's valid rows; the mean over a row's elements and over the graphs goes here)
     const double scale = (double)weight / ((double)row_floats * (double)n_graphs);

@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 import torch
 
+import loss_cases as LC
 from mpntrackseg_amd import synth
 from mpntrackseg_amd.loss import compute_perform_metrics, tracking_loss, tracking_loss_and_grad
 from oracle import loss_oracle as LO
@@ -22,6 +23,8 @@ def test_tracking_loss_and_grad(E, L, frac):
     loss, grad = tracking_loss_and_grad(logits.to(dev()), labels.to(dev()), 0, 1.0)
     assert abs(float(loss[0]) - float(ref)) <= 1e-5 * max(1.0, abs(float(ref)))
     assert float((grad.cpu() - lg.grad).abs().max()) <= 1e-6 * max(1.0, float(lg.grad.abs().max()))
+    # per element against float64 (tests/loss_ref.py) under the bounds of tests/test_gpu_loss_ops.py
+    LC.check_tracking("E=%d L=%d" % (E, L), loss.cpu().numpy(), grad.cpu().numpy(), logits.numpy(), labels.numpy(), 0, 1.0)
     # autograd wrapper over the reference's list-of-[E,1] output
     lgd = logits.to(dev()).requires_grad_(True)
     out = tracking_loss([lgd[s].view(E, 1) for s in range(L)], labels.to(dev()))
@@ -125,12 +128,14 @@ def test_tracking_loss_against_reference_compute_loss(golden, tag):
     ref = float(z[f"{tag}:loss"])
     assert abs(float(loss[0]) - ref) <= 1e-5 * max(1.0, abs(ref))
     assert float(np.abs(grad.cpu().numpy() - z[f"{tag}:grad"]).max()) <= 1e-6 * max(1.0, float(np.abs(z[f"{tag}:grad"]).max()))
+    LC.check_tracking("g9 " + tag, loss.cpu().numpy(), grad.cpu().numpy(), z[f"{tag}:logits"], z[f"{tag}:labels"], 0, w)
     lg = logits.clone().requires_grad_(True)
     k, E = lg.shape
     out = tracking_loss([lg[s].view(E, 1) for s in range(k)], labels, weight=w)
     out.backward()
     assert abs(float(out) - ref) <= 1e-5 * max(1.0, abs(ref))
     assert float(np.abs(lg.grad.cpu().numpy() - z[f"{tag}:grad"]).max()) <= 1e-6 * max(1.0, float(np.abs(z[f"{tag}:grad"]).max()))
+    LC.check_tracking("g9 autograd " + tag, None, lg.grad.cpu().numpy(), z[f"{tag}:logits"], z[f"{tag}:labels"], 0, w)
 
 
 @pytest.mark.parametrize("tag", ["m1", "m2", "m3"])
@@ -164,6 +169,8 @@ def test_graph_batched_loss_against_the_reference_per_graph_loss(golden, tag):
     ref = float(z[f"{tag}:loss"])
     assert abs(float(loss[0]) - ref) <= 1e-5 * max(1.0, abs(ref))
     assert float(np.abs(grad.cpu().numpy() - z[f"{tag}:grad"]).max()) <= 1e-6 * max(1.0, float(np.abs(z[f"{tag}:grad"]).max()))
+    LC.check_tracking("g16 " + tag, loss.cpu().numpy(), grad.cpu().numpy(), z[f"{tag}:logits"], z[f"{tag}:labels"], 0,
+                      float(z[f"{tag}:weight"]), eg.cpu().numpy(), K)
     # one graph: the plain loss
     l1, g1 = tracking_loss_and_grad(logits, labels, 0, 0.75)
     l2, g2 = tracking_loss_and_grad(logits, labels, 0, 0.75, edge_graph=torch.zeros_like(eg), n_graphs=1)

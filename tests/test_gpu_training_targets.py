@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 import torch
 
+import loss_cases as LC
 import training_targets_ref as R
 from mpntrackseg_amd import synth
 from mpntrackseg_amd.graph import assign_edge_labels
@@ -172,6 +173,12 @@ def test_compute_loss_under_autograd(z, tag):
         assert pr[s].grad is not None and pr[s].grad.shape == pr[s].shape
         want = z[f"{tag}:gmask_rows"][s]
         assert float(np.abs(pr[s].grad.cpu().numpy()[rows] / 2 - want).max()) <= 1e-6 * max(1.0, float(np.abs(want).max()))
+    # every element of both gradients against float64 (tests/loss_ref.py) under the bounds of tests/test_gpu_loss_ops.py (halving
+    # is exact)
+    graphs = (edge_graph, node_graph, 3) if tag == "graphs" else (None, None, 1)
+    LC.check_tracking("autograd " + tag, None, lg.grad.cpu().numpy() / 2, logits, labels, 0, W["tracking"], graphs[0], graphs[2])
+    LC.check_mask("autograd mask " + tag, None, [p.grad.cpu().numpy() / 2 for p in pr], preds, mlab, valid, W["segmentation"],
+                  graphs[1], graphs[2])
     if tag == "mid":   # the sum of the two native terms, bit for bit
         track = tracking_loss([on(logits[s]).view(-1, 1) for s in range(k)], on(labels), weight=W["tracking"])
         lv, _ = mask_loss_and_grad([on(preds[s]) for s in range(k)], on(mlab), on(valid), W["segmentation"])
