@@ -854,6 +854,24 @@ typedef struct mpnhip_conv_affine_args {
 } mpnhip_conv_affine_args;
 int mpnhip_conv2d_affine_forward(const mpnhip_conv_affine_args* args, void* stream);
 
+/* The lateral convolution of a feature pyramid's top-down path (torchvision's FeaturePyramidNetwork), inner = conv(x) + bias +
+ * F.interpolate(coarser_inner, size=inner.shape[-2:], mode='nearest'): mpnhip_conv2d_affine_forward -- the same kernel, the same
+ * chain, every field as above -- whose residual is a COARSER map, image i at residual + i * residual_stride, dense
+ * [cout][residual_H][residual_W].  Output pixel (oy, ox) adds residual[m][sy][sx] with aten's nearest-neighbour source index in
+ * float32: sy = min((int)floorf(oy * ((float)residual_H / Hout)), residual_H - 1), sx likewise from ox, residual_W and Wout; the
+ * index is computed once per output pixel, not per channel.  The convolution's bias goes in as shift with a NULL scale
+ * (fmaf(acc, 1, bias) is acc + bias rounded once).  With residual_H == Hout and residual_W == Wout the result equals
+ * mpnhip_conv2d_affine_forward's bit for bit.  Path counters: conv_affine_up, beside those of mpnhip_conv2d_affine_forward.
+ * MPNHIP_ERR_ARG before any launch: everything mpnhip_conv2d_affine_forward refuses, a null residual, residual_H or residual_W < 1
+ * and a residual image (cout * residual_H * residual_W) beyond INT32_MAX.  n_images == 0 is a successful no-op. */
+typedef struct mpnhip_conv_affine_up_args {
+    const float* x; int64_t x_stride; const float* weight; const float* scale; const float* shift;
+    const float* residual; int64_t residual_stride; int relu; float* out; int64_t out_stride;
+    int64_t n_images; int cin; int cout; int H; int W; int ksize; int stride;
+    int residual_H; int residual_W;
+} mpnhip_conv_affine_up_args;
+int mpnhip_conv2d_affine_up_forward(const mpnhip_conv_affine_up_args* args, void* stream);
+
 /* nn.MaxPool2d(3, stride 2, padding 1) (the ReID ResNet50's stem): image i at x + i * x_stride, dense [C][H][W], to out + i *
  * out_stride, dense [C][Hout][Wout] with Hout = (H - 1) / 2 + 1, Wout likewise.  Padded cells do not take part: a window of
  * negative values yields the largest of them, never 0.  One thread per output element.  MPNHIP_ERR_ARG before any launch:
@@ -1441,6 +1459,25 @@ size_t mpnhip_reid_crops_workspace_bytes(int64_t n, int max_ph, int max_pw, int 
 int mpnhip_reid_crops(const unsigned char* frames, int64_t n_frames, int H, int W, const int32_t* geom, const int32_t* box_frame,
                       int64_t n, int max_ph, int max_pw, int oh, int ow, const float* mean_std, float* out, unsigned char* out_u8,
                       void* workspace, size_t workspace_bytes, void* stream);
+
+/* GeneralizedRCNNTransform.forward of torchvision 0.6.0 under torch 1.5.0 (tracktor_masked/maskrcnn_fpn.py:81-92) for n_frames
+ * frames of one size, in one launch: ToTensor, Normalize, the bilinear resize to oh x ow and the zero padding of the batch to
+ * Hp x Wp.  The caller computes the sizes (embed_inputs.transform_sizes).
+ *   frames [n_frames, H, W, 3] (uint8, as imread returns them); mean_std (HOST, 6 floats): Normalize's mean and std per channel;
+ *   out [n_frames, 3, Hp, Wp] (float32).
+ * A tap of channel c is t(v) = (float(v) / 255f - mean[c]) / std[c] in float32, one rounded operation at a time: the image is
+ * normalised first and interpolated after, the reference's order.  Per axis in -> out, aten's upsample_bilinear2d with
+ * align_corners=False and no antialiasing in float32, unfused: scale = (float)in / out -- from the OUTPUT SIZE, as torch 1.5.0
+ * recomputes it for a float scale_factor, which is F.interpolate(size=(oh, ow)) in later releases --, src = max(scale * (dst +
+ * 0.5f) - 0.5f, 0), i0 = min((int)src, in - 1), i1 = i0 + (i0 < in - 1), l1 = src - i0, l0 = 1 - l1.  An output inside oh x ow is
+ *   ly0 * (lx0 * t(y0, x0) + lx1 * t(y0, x1)) + ly1 * (lx0 * t(y1, x0) + lx1 * t(y1, x1));
+ * every output outside it is 0.  One thread per output pixel: the indices and weights of both axes are computed once and serve
+ * the three channels; the 3 x 256 values of t sit in LDS.  No sums across threads: the same bits on every call, and a frame's
+ * bits do not depend on the batch.  MPNHIP_ERR_ARG before any launch: n_frames < 0 (0 is a successful no-op), a null pointer,
+ * a size below 1, oh > Hp or ow > Wp, a frame (3 * H * W) or an output image (3 * Hp * Wp) beyond INT32_MAX, more elements than a
+ * launch holds. */
+int mpnhip_rcnn_transform(const unsigned char* frames, int64_t n_frames, int H, int W, int oh, int ow, int Hp, int Wp,
+                          const float* mean_std, float* out, void* stream);
 
 #define MPNHIP_FPN_LEVELS 4
 /* largest output_size * sampling_ratio of mpnhip_fpn_roi_align: the samples of one axis, kept in LDS */

@@ -162,6 +162,12 @@ class ConvAffineArgs(C.Structure):
     ]
 
 
+class ConvAffineUpArgs(C.Structure):
+    """``mpnhip_conv_affine_up_args`` (include/mpnhip.h): ``ConvAffineArgs`` whose residual is a coarser map of
+    ``residual_H x residual_W``, read at the nearest-neighbour source cell (``mpnhip_conv2d_affine_up_forward``)."""
+    _fields_ = ConvAffineArgs._fields_ + [("residual_H", C.c_int), ("residual_W", C.c_int)]
+
+
 _P, _I, _L, _Z = C.c_void_p, C.c_int, C.c_int64, C.c_size_t
 SIGNATURES = {
     "mpnhip_version": (C.c_char_p, []),
@@ -251,6 +257,7 @@ SIGNATURES = {
     "mpnhip_layer_norm_backward": (_I, [C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int), _I, _L, _L, _P, C.c_float, _P,
                                         _L, _P, _P, _P, _P, _Z, _P]),
     "mpnhip_conv2d_affine_forward": (_I, [C.POINTER(ConvAffineArgs), _P]),
+    "mpnhip_conv2d_affine_up_forward": (_I, [C.POINTER(ConvAffineUpArgs), _P]),
     "mpnhip_maxpool2d_forward": (_I, [_P, _L, _L, _I, _I, _I, _P, _L, _P]),
     "mpnhip_adam_step": (_I, [_P, _P, _P, _P, _L, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _I, _P]),
     "mpnhip_adam_step_guarded": (_I, [_P, _P, _P, _P, _L, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _I, _P, _P]),
@@ -325,6 +332,7 @@ SIGNATURES = {
     "mpnhip_roi_align_labels": (_I, [_P, _L, _I, _I, _P, _P, _P, _L, _P, _P, _L, _P, _P, _L, _P, _I, _I, _I, _P, _P, _P]),
     "mpnhip_reid_crops_workspace_bytes": (_Z, [_L, _I, _I, _I, _I]),
     "mpnhip_reid_crops": (_I, [_P, _L, _I, _I, _P, _P, _L, _I, _I, _I, _I, C.POINTER(C.c_float), _P, _P, _P, _Z, _P]),
+    "mpnhip_rcnn_transform": (_I, [_P, _L, _I, _I, _I, _I, _I, _I, C.POINTER(C.c_float), _P, _P]),
     "mpnhip_fpn_roi_align": (_I, [C.POINTER(FpnLevels), _L, _I, _P, _P, _P, _L, _I, _I, _P, _P, _P]),
     "mpnhip_augment_boxes_workspace_bytes": (_Z, []),
     "mpnhip_augment_boxes": (_I, [_P, _P, _P, _L, _P, _P, _L, _P, _L, _P, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _P]),

@@ -1,5 +1,5 @@
-// Inference forward of the ReID ResNet50's convolution-type layers (include/mpnhip.h: mpnhip_conv2d_affine_forward,
-// mpnhip_maxpool2d_forward): implicit-GEMM convolution (1x1 / 3x3 / 7x7, stride 1 or 2, padding k / 2, no bias) on the fp32-input
+// Inference forward of the convolution-type layers of the two ResNet50s (the ReID network, the Mask R-CNN FPN backbone;
+// include/mpnhip.h: mpnhip_conv2d_affine_forward, mpnhip_conv2d_affine_up_forward, mpnhip_maxpool2d_forward): implicit-GEMM convolution (1x1 / 3x3 / 7x7, stride 1 or 2, padding k / 2, no bias) on the fp32-input
 // MFMA with the eval-mode BatchNorm (one fmaf per output), the residual add and the ReLU in its epilogue, and MaxPool2d(3, 2, 1).
 //
 // GEMM view of conv_affine_tile_kernel: M = output channels (rows of the weight), N = the output pixels of ALL images packed into
@@ -12,6 +12,8 @@
 // travels in registers (conv_tile_kernel's prefetch).  The summation order (channel, then tap; one chain per output) is a function
 // of the layer alone: no split of K across blocks, no atomics, so an output's bits depend on the layer and on its image only --
 // not on n_images, not on where the image sits in the batch.  (K > 2048: the chain is cut into groups, see GROUPED below.)
+// UP (mpnhip_conv2d_affine_up_forward, the FPN's top-down path): the residual is a coarser map [cout][res_H][res_W] read at the
+// nearest-neighbour source cell of every output pixel; nothing else of the kernel changes.
 #include "common.h"
 
 #include <math.h>
@@ -33,6 +35,8 @@ struct ConvAffine {
     int64_t x_stride, residual_stride, out_stride;
     int cin, cout, H, W, Hout, Wout, stride, relu;
     int ntotal;                                   // n_images * Hout * Wout
+    int res_H, res_W;                             // UP only: the residual's own size, and (float)res_H / Hout, (float)res_W / Wout
+    float up_sy, up_sx;
 };
 
 constexpr int CA_GROUP_CHUNKS = 4;               // GROUPED: chunks per partial sum
@@ -45,7 +49,9 @@ constexpr int CA_GROUP_MIN_K = 2048;             // K above this takes the group
 // from zero in a second accumulator, and the group's sum is added to the running total, groups in order.  Still (channel, then
 // tap) order, fixed by the layer alone; it keeps the rounding of a K = 4608 chain (measured 2.5e-6 of the largest output as ONE
 // chain, against 1.5e-6 at K = 2048) below what the project holds the short chains to.
-template <int KS, int WM, int TW, bool GROUPED>
+// UP: the epilogue adds residual[m][sy][sx] with aten's nearest-neighbour source index, sy = min((int)floorf(oy * up_sy), res_H - 1)
+// and sx likewise, computed once per column; with res_H == Hout and res_W == Wout that is the cell (oy, ox) itself.
+template <int KS, int WM, int TW, bool GROUPED, bool UP>
 __global__ __launch_bounds__(CA_THREADS) void conv_affine_tile_kernel(ConvAffine p) {
     constexpr int TAPS = KS * KS, PAD = KS / 2;
     constexpr int CK = KS == 1 ? 32 : (KS == 3 ? 4 : 1);   // input channels per chunk
@@ -156,7 +162,14 @@ __global__ __launch_bounds__(CA_THREADS) void conv_affine_tile_kernel(ConvAffine
         if (n >= p.ntotal) continue;
         const int img = n / hwo, pix = n % hwo;
         float* __restrict__ o = p.out + (int64_t)img * p.out_stride + pix;
-        const float* __restrict__ res = p.residual ? p.residual + (int64_t)img * p.residual_stride + pix : nullptr;
+        int rpix = pix;
+        if constexpr (UP) {
+            const int sy = min((int)floorf((float)(pix / p.Wout) * p.up_sy), p.res_H - 1);
+            const int sx = min((int)floorf((float)(pix % p.Wout) * p.up_sx), p.res_W - 1);
+            rpix = sy * p.res_W + sx;
+        }
+        const int rplane = UP ? p.res_H * p.res_W : hwo;
+        const float* __restrict__ res = p.residual ? p.residual + (int64_t)img * p.residual_stride + rpix : nullptr;
 #pragma unroll
         for (int i = 0; i < TW; ++i) {
 #pragma unroll
@@ -164,7 +177,7 @@ __global__ __launch_bounds__(CA_THREADS) void conv_affine_tile_kernel(ConvAffine
                 const int m = m0 + (wm * TW + i) * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
                 if (m >= p.cout) continue;
                 float v = fmaf(acc[i][j][r], p.scale ? p.scale[m] : 1.f, p.shift ? p.shift[m] : 0.f);
-                if (res) v += res[m * hwo];
+                if (res) v += res[m * rplane];
                 if (p.relu) v = fmaxf(v, 0.f);
                 o[m * hwo] = v;
             }
@@ -203,15 +216,15 @@ bool conv_affine_grouped(const ConvAffine& p, int ksize) { return (int64_t)p.cin
 
 constexpr int64_t CA_SMALL_GRID = 512;            // fewer blocks than this (two per CU of an MI355X): the 64 x 64 block
 
-template <int KS>
+template <int KS, bool UP>
 void launch_conv_affine(const ConvAffine& p, hipStream_t stream) {
     const bool grouped = conv_affine_grouped(p, KS);
     const int64_t n = p.ntotal;
 #define MPN_CA_LAUNCH(WM, TW, BM, BN)                                                                                   \
     do {                                                                                                                \
         const dim3 grid((unsigned)((n + BN - 1) / BN), (unsigned)((p.cout + BM - 1) / BM));                             \
-        if (grouped) conv_affine_tile_kernel<KS, WM, TW, true><<<grid, CA_THREADS, 0, stream>>>(p);                     \
-        else conv_affine_tile_kernel<KS, WM, TW, false><<<grid, CA_THREADS, 0, stream>>>(p);                            \
+        if (grouped) conv_affine_tile_kernel<KS, WM, TW, true, UP><<<grid, CA_THREADS, 0, stream>>>(p);                     \
+        else conv_affine_tile_kernel<KS, WM, TW, false, UP><<<grid, CA_THREADS, 0, stream>>>(p);                            \
     } while (0)
     if constexpr (KS != 7) {            // (the 7 x 7 chunk is no multiple of four rows, and with 256 columns it would not fit 64 KB of LDS)
         const int64_t blocks = p.cout <= 64 ? (n + 255) / 256 : ((n + 127) / 128) * ((p.cout + 127) / 128);
@@ -235,11 +248,8 @@ void launch_conv_affine(const ConvAffine& p, hipStream_t stream) {
 
 using namespace mpnhip;
 
-extern "C" int mpnhip_conv2d_affine_forward(const mpnhip_conv_affine_args* args, void* stream_) {
-    static const char* const name = "mpnhip_conv2d_affine_forward";
-    hipStream_t stream = (hipStream_t)stream_;
-    MPN_CHECK_ARG(args != nullptr, "%s: null args", name);
-    const mpnhip_conv_affine_args& a = *args;
+// The argument checks both convolution entry points share, then the launch.  up: the residual is [cout][res_H][res_W] per image.
+static int conv_affine_run(const char* name, const mpnhip_conv_affine_args& a, bool up, int res_H, int res_W, hipStream_t stream) {
     MPN_CHECK_ARG(a.n_images >= 0, "%s: negative n_images", name);
     if (a.n_images == 0) return MPNHIP_OK;
     MPN_CHECK_ARG(a.x != nullptr && a.weight != nullptr && a.out != nullptr, "%s: null x, weight or out", name);
@@ -262,19 +272,51 @@ extern "C" int mpnhip_conv2d_affine_forward(const mpnhip_conv_affine_args* args,
     MPN_CHECK_ARG(a.n_images <= (INT32_MAX - 256) / hwo, "%s: %lld images of %lld output pixels are beyond the 32-bit column index", name,
                   (long long)a.n_images, (long long)hwo);
     MPN_CHECK_ARG((a.cout + 63) / 64 <= 65535, "%s: cout %d is more than one launch holds", name, a.cout);
+    if (up) {
+        MPN_CHECK_ARG(a.residual != nullptr, "%s: null residual", name);
+        MPN_CHECK_ARG(res_H >= 1 && res_W >= 1, "%s: residual_H %d, residual_W %d must be positive", name, res_H, res_W);
+        MPN_CHECK_ARG((int64_t)a.cout * res_H * res_W <= INT32_MAX, "%s: a residual image of %d x %lld floats is beyond the 32-bit offsets",
+                      name, a.cout, (long long)res_H * res_W);
+    }
 
     ConvAffine p;
     p.x = a.x, p.weight = a.weight, p.scale = a.scale, p.shift = a.shift, p.residual = a.residual, p.out = a.out;
     p.x_stride = a.x_stride, p.residual_stride = a.residual_stride, p.out_stride = a.out_stride;
     p.cin = a.cin, p.cout = a.cout, p.H = a.H, p.W = a.W, p.Hout = (int)Hout, p.Wout = (int)Wout, p.stride = a.stride, p.relu = a.relu;
     p.ntotal = (int)(a.n_images * hwo);
-    if (a.ksize == 1) launch_conv_affine<1>(p, stream);
-    else if (a.ksize == 3) launch_conv_affine<3>(p, stream);
-    else launch_conv_affine<7>(p, stream);
+    p.res_H = up ? res_H : (int)Hout, p.res_W = up ? res_W : (int)Wout;
+    p.up_sy = (float)p.res_H / (float)Hout, p.up_sx = (float)p.res_W / (float)Wout;
+    if (up) {
+        if (a.ksize == 1) launch_conv_affine<1, true>(p, stream);
+        else if (a.ksize == 3) launch_conv_affine<3, true>(p, stream);
+        else launch_conv_affine<7, true>(p, stream);
+        count_path(PC_CONV_AFFINE_UP);
+    } else {
+        if (a.ksize == 1) launch_conv_affine<1, false>(p, stream);
+        else if (a.ksize == 3) launch_conv_affine<3, false>(p, stream);
+        else launch_conv_affine<7, false>(p, stream);
+    }
     count_path(PC_CONV_AFFINE_TILE);
     if (conv_affine_grouped(p, a.ksize)) count_path(PC_CONV_AFFINE_GROUPED);
     MPN_LAUNCH_CHECK();
     return MPNHIP_OK;
+}
+
+extern "C" int mpnhip_conv2d_affine_forward(const mpnhip_conv_affine_args* args, void* stream_) {
+    static const char* const name = "mpnhip_conv2d_affine_forward";
+    MPN_CHECK_ARG(args != nullptr, "%s: null args", name);
+    return conv_affine_run(name, *args, false, 0, 0, (hipStream_t)stream_);
+}
+
+extern "C" int mpnhip_conv2d_affine_up_forward(const mpnhip_conv_affine_up_args* args, void* stream_) {
+    static const char* const name = "mpnhip_conv2d_affine_up_forward";
+    MPN_CHECK_ARG(args != nullptr, "%s: null args", name);
+    const mpnhip_conv_affine_up_args& u = *args;
+    mpnhip_conv_affine_args a;
+    a.x = u.x, a.x_stride = u.x_stride, a.weight = u.weight, a.scale = u.scale, a.shift = u.shift;
+    a.residual = u.residual, a.residual_stride = u.residual_stride, a.relu = u.relu, a.out = u.out, a.out_stride = u.out_stride;
+    a.n_images = u.n_images, a.cin = u.cin, a.cout = u.cout, a.H = u.H, a.W = u.W, a.ksize = u.ksize, a.stride = u.stride;
+    return conv_affine_run(name, a, true, u.residual_H, u.residual_W, (hipStream_t)stream_);
 }
 
 extern "C" int mpnhip_maxpool2d_forward(const float* x, int64_t x_stride, int64_t n_images, int C, int H, int W, float* out,

@@ -1,7 +1,11 @@
 """The inputs of the two embedding CNNs of the reference's ``MOTSeqProcessor._store_embeddings``
 (``data/seq_processing/seq_processor.py:395-562``), on the device and without ``torchvision`` or ``PIL``.  The Mask R-CNN FPN
-backbone stays a stock module; the torchreid ResNet50 is ``reid_net.ResNet`` (stock modules by default, native kernels on
-request); what surrounds them is here:
+backbone is ``fpn_net.BackboneWithFPN`` and the torchreid ResNet50 is ``reid_net.ResNet`` (both: stock modules by default, native
+kernels on request); what surrounds them is here:
+
+``transform_sizes``, ``rcnn_transform``   ``GeneralizedRCNNTransform`` for a batch of frames: normalise, resize, pad;
+``fpn_features``              ``MaskRCNN_FPN.load_image``: the transform and the backbone (``convs='stock' | 'native'``);
+``node_ext_embeddings_from_frames``   frames and detections -> ``x_ext`` in its stored format;
 
 ``reid_embeddings``           crops -> the ReID CNN (``convs='stock' | 'native'``) -> node-core maps and ReID vectors;
 ``store_reid_embeddings``     their per-frame files (``seq_processor.py:443-475``);
@@ -290,6 +294,71 @@ def node_ext_embeddings(features, det, image_size, original_size=None, frames=No
         raise ValueError("a detection lies in a frame whose features are not given")
     return fpn_roi_align(features, det, order[pos] if frame.size else pos, image_size, original_size, output_size, sampling_ratio,
                          _col(det, "detection_id", np.int64))
+
+
+# ------------------------------------------------------------------------------------------------ the FPN backbone's input
+def transform_sizes(H, W, min_size=800, max_size=1333, size_divisible=32):
+    """``GeneralizedRCNNTransform``'s sizes for an ``H x W`` frame, in Python floats exactly as torchvision 0.6.0 computes them:
+    ``(oh, ow, Hp, Wp)`` -- the resized image (the floor of the scaled sides: 1080 x 1920 gives 749, not 750, rows) and the batch
+    padded to multiples of ``size_divisible``."""
+    H, W = int(H), int(W)
+    if H < 1 or W < 1 or min_size < 1 or max_size < 1 or size_divisible < 1:
+        raise ValueError("sizes must be positive")
+    s = float(min_size) / float(min(H, W))
+    if float(max(H, W)) * s > float(max_size):
+        s = float(max_size) / float(max(H, W))
+    oh, ow = int(math.floor(float(H) * s)), int(math.floor(float(W) * s))
+    if oh < 1 or ow < 1:
+        raise ValueError("a %d x %d frame resizes to nothing" % (H, W))
+    d = int(size_divisible)
+    return oh, ow, int(math.ceil(float(oh) / d) * d), int(math.ceil(float(ow) / d) * d)
+
+
+def rcnn_transform(frames, min_size=800, max_size=1333, mean=IMAGENET_MEAN, std=IMAGENET_STD, size_divisible=32):
+    """``GeneralizedRCNNTransform.forward`` (``maskrcnn_fpn.py:81-92``) for equally sized frames in one launch
+    (``mpnhip_rcnn_transform``, whose header comment states the arithmetic): ``(batch, image_size)`` -- float32
+    ``[B, 3, Hp, Wp]`` on the device of ``frames``, normalised, resized to ``image_size = (oh, ow)`` and zero-padded.
+    ``frames``: uint8 ``[B, H, W, 3]`` on the device, as for ``reid_crops``.  The resize takes its scale from the output size,
+    as torch 1.5.0 does for a float ``scale_factor`` (``F.interpolate(size=(oh, ow))`` in later releases)."""
+    if not isinstance(frames, torch.Tensor) or frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3:
+        raise MpnhipError("frames must be a uint8 tensor [B, H, W, 3]")
+    B, H, W = int(frames.shape[0]), int(frames.shape[1]), int(frames.shape[2])
+    oh, ow, hp, wp = transform_sizes(H, W, min_size, max_size, size_divisible)
+    capi.require_device(frames)
+    mean_std = (C.c_float * 6)(*[float(v) for v in tuple(mean) + tuple(std)])
+    with torch.cuda.device(frames.device):
+        frames = frames.contiguous()
+        out = torch.empty((B, 3, hp, wp), dtype=torch.float32, device=frames.device)
+        check(capi.load().mpnhip_rcnn_transform(ptr(frames), B, H, W, oh, ow, hp, wp, mean_std, ptr(out), stream_ptr()),
+              "mpnhip_rcnn_transform")
+    return out, (oh, ow)
+
+
+def fpn_features(backbone, frames, convs='stock', **transform_kw):
+    """``MaskRCNN_FPN.load_image`` for a batch of frames: ``rcnn_transform`` -> ``backbone`` (a ``fpn_net.BackboneWithFPN`` in
+    eval mode on the device of ``frames``) -> ``(features, image_size)``, the ordered dict ``'0' .. '3', 'pool'`` and the
+    resized image's ``(oh, ow)``.  ``convs='stock'`` (the default) runs ``backbone.forward`` -- the stock modules -- under
+    ``no_grad``; ``convs='native'`` runs ``backbone.forward_native`` (csrc/conv_strided.hip).  ``transform_kw``:
+    ``rcnn_transform``'s keywords."""
+    if convs not in ('stock', 'native'):
+        raise ValueError("convs must be 'stock' or 'native', not %r" % (convs,))
+    batch, image_size = rcnn_transform(frames, **transform_kw)
+    if convs == 'native':
+        return backbone.forward_native(batch), image_size
+    with torch.no_grad():
+        return backbone(batch), image_size
+
+
+def node_ext_embeddings_from_frames(backbone, frames, det, convs='stock', frames_index=None, output_size=14, sampling_ratio=2,
+                                    **transform_kw):
+    """``load_image`` + ``get_node_embeddings`` + the id channel (``seq_processor.py:498-548``) for a batch of frames:
+    ``fpn_features`` -> ``node_ext_embeddings`` with ``original_size=(H, W)``.  ``frames``: uint8 ``[B, H, W, 3]`` on the device;
+    ``det``: the detections table of ``node_ext_embeddings``; ``frames_index``: the frame number of every entry of ``B``
+    (default: the sorted frame numbers of ``det``).  Returns float32 ``[n, 1 + 256, S, S]``."""
+    features, image_size = fpn_features(backbone, frames, convs=convs, **transform_kw)
+    return node_ext_embeddings([features[k] for k in ('0', '1', '2', '3')], det, image_size,
+                               original_size=(int(frames.shape[1]), int(frames.shape[2])), frames=frames_index, output_size=output_size,
+                               sampling_ratio=sampling_ratio)
 
 
 def store_node_ext_embeddings(seq_path, det_file_name, embeddings_dir, frame, embeddings):

@@ -220,6 +220,30 @@ def make_reid_weights(net, seed):
     return out
 
 
+def make_fpn_weights(net, seed):
+    """Fills every ``state_dict`` entry of a ``fpn_net.BackboneWithFPN``, in ``state_dict`` order, from stream i = its index:
+    Conv2d weights He-scaled (std = sqrt(2 / (cin k k))), Conv2d biases (the pyramid's) std 0.05, frozen-BatchNorm ``weight`` and
+    ``running_var`` 0.75 + 0.5 uniform01, frozen-BatchNorm ``bias`` and ``running_mean`` N(0, 0.1^2).  Loads them into ``net`` and
+    returns {key: float32 ndarray}."""
+    import torch
+    sd = net.state_dict()
+    out = {}
+    for i, (k, t) in enumerate(sd.items()):
+        shp = tuple(t.shape)
+        prefix, leaf = k.rsplit(".", 1)
+        if leaf == "weight" and len(shp) == 4:
+            v = normal(seed, shp, stream=i, std=math.sqrt(2.0 / (shp[1] * shp[2] * shp[3])))
+        elif leaf in ("weight", "running_var"):
+            v = (0.75 + 0.5 * uniform01(seed, shp[0], stream=i)).astype(np.float32)
+        elif leaf == "bias" and sd[prefix + ".weight"].dim() == 4:
+            v = normal(seed, shp, stream=i, std=0.05)
+        else:                                   # frozen-BatchNorm bias, running_mean
+            v = normal(seed, shp, stream=i, std=0.1)
+        out[k] = v
+    net.load_state_dict({k: torch.from_numpy(v).to(sd[k].dtype) for k, v in out.items()})
+    return out
+
+
 def make_weights(p, seed=7, bias_std=0.1, gain=1.0):
     """He-normal weights (std = gain*sqrt(2/fan_in)), biases N(0, bias_std^2); one RNG stream per
     tensor in ``hot_path_param_shapes`` order. Returns {key: float32 ndarray}."""
