@@ -214,6 +214,7 @@ extern "C" int mpnhip_bn_relu_dropout_backward(const float* dy, const float* z, 
     a.z = z; a.dy = dy; a.out = dz; a.m = m; a.n = n; a.relu = relu; a.use_bn = use_bn ? 1 : 0;
     a.p = dropout_p; a.scale = 1.f / (1.f - dropout_p); a.seed = seed;
     if (use_bn) {
+        MPN_CHECK_ARG(m > 1, "bn_relu_dropout_backward: BatchNorm1d in training mode needs more than one row");   // (as the forward)
         MPN_CHECK_ARG(save_mean && save_invstd, "bn_relu_dropout_backward: save_mean / save_invstd required with BatchNorm");
         BnWorkspace v;
         MPN_CHECK_ARG(workspace && workspace_bytes >= bn_layout(m, n, workspace, &v), "bn_relu_dropout_backward: workspace too small");
