@@ -2,7 +2,7 @@
 HIPCC ?= /opt/rocm/bin/hipcc
 ARCH ?= gfx950
 CSRC := mpntrackseg_amd/csrc
-SRCS := $(CSRC)/gemm.hip $(CSRC)/gemm_bf16.hip $(CSRC)/gemm_tn.hip $(CSRC)/wgrad_panel.hip $(CSRC)/wgrad_rows16.hip $(CSRC)/wgrad.hip $(CSRC)/edge_chain.hip $(CSRC)/edge_chain_bf16.hip $(CSRC)/edge_chain_bf16_bwd.hip $(CSRC)/graph_prep.hip $(CSRC)/segment.hip $(CSRC)/node_chain.hip $(CSRC)/mpn.hip $(CSRC)/backward.hip $(CSRC)/loss.hip $(CSRC)/bn_dropout.hip $(CSRC)/attention.hip $(CSRC)/graph_build.hip $(CSRC)/tracker.hip $(CSRC)/tracker_tail.hip $(CSRC)/projection.hip $(CSRC)/exact_projection.hip $(CSRC)/full_masks.hip $(CSRC)/rle_codec.hip $(CSRC)/train_targets.hip $(CSRC)/mots_eval.hip $(CSRC)/hota.hip $(CSRC)/clear_identity.hip $(CSRC)/assignment.hip $(CSRC)/gt_assign.hip $(CSRC)/embed_inputs.hip $(CSRC)/train_batch.hip $(CSRC)/conv.hip $(CSRC)/conv_backward.hip $(CSRC)/conv_strided.hip $(CSRC)/rcnn_transform.hip
+SRCS := $(CSRC)/gemm.hip $(CSRC)/gemm_bf16.hip $(CSRC)/gemm_tn.hip $(CSRC)/wgrad_panel.hip $(CSRC)/wgrad_rows16.hip $(CSRC)/wgrad.hip $(CSRC)/edge_chain.hip $(CSRC)/edge_chain_bf16.hip $(CSRC)/edge_chain_bf16_bwd.hip $(CSRC)/graph_prep.hip $(CSRC)/segment.hip $(CSRC)/node_chain.hip $(CSRC)/mpn.hip $(CSRC)/backward.hip $(CSRC)/loss.hip $(CSRC)/bn_dropout.hip $(CSRC)/attention.hip $(CSRC)/graph_build.hip $(CSRC)/tracker.hip $(CSRC)/tracker_tail.hip $(CSRC)/projection.hip $(CSRC)/exact_projection.hip $(CSRC)/full_masks.hip $(CSRC)/rle_codec.hip $(CSRC)/train_targets.hip $(CSRC)/mots_eval.hip $(CSRC)/hota.hip $(CSRC)/clear_identity.hip $(CSRC)/assignment.hip $(CSRC)/gt_assign.hip $(CSRC)/embed_inputs.hip $(CSRC)/train_batch.hip $(CSRC)/conv.hip $(CSRC)/conv_backward.hip $(CSRC)/conv_strided.hip $(CSRC)/rcnn_transform.hip $(CSRC)/rcnn_heads.hip
 OBJS := $(SRCS:.hip=.o)
 LIB := $(CSRC)/libmpnhip.so
 # EXTRA=-DMPNHIP_CHAIN_TS builds the fused chain kernels with per-phase cycle stamps (tools/chain_stamps.py)

@@ -1508,6 +1508,82 @@ int mpnhip_fpn_roi_align(const mpnhip_fpn_levels* levels, int64_t n_frames, int 
                          float* out, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The Mask R-CNN RoI heads on given boxes (tracktor_masked/frcnn_fpn.py:29-64, maskrcnn_fpn.py:31-79, data/preprocessing.py:19-42),
+ * inference: what follows the dense and convolution-type layers (mpnhip_fpn_roi_align, mpnhip_linear,
+ * mpnhip_conv2d_affine_forward, mpnhip_conv2d_forward).  Everything is float32; every operation a decision or a coordinate
+ * depends on is rounded on its own, never contracted into an FMA.  No float atomics: the same bits on every call.
+ * ------------------------------------------------------------------------------------------- */
+#define MPNHIP_BOX_MAX_CLASSES 91
+/* FastRCNNPredictor + F.softmax(class_logits, -1)[:, label] + BoxCoder(weights).decode(...)[:, label] + resize_boxes back to the
+ * original image (torchvision 0.6.0), for one class, in one launch.
+ *   h [n, K] (row stride ldh) the box head's output; w_cls [C, K], b_cls [C]; w_box [4 C, K], b_box [4 C]; proposals [n, 4]
+ *   (x1, y1, x2, y2 in the network's image); weights (HOST, 4 floats): the coder's (wx, wy, ww, wh), (10, 10, 5, 5) in RoIHeads;
+ *   clip: float32(log(1000 / 16)); ratio_h, ratio_w: resize_boxes' Python-float ratios original / network size, rounded to
+ *   float32 (1 and 1: the boxes stay in the network's image).
+ *   boxes [n, 4], scores [n]; logits [n, C] and deltas [n, 4] (the four rows 4 label .. 4 label + 3 of the regression, before
+ *   the weights) may be NULL.
+ * One wavefront per box computes the C + 4 dot products it needs: a lane adds the products of the float4s lane, lane + 64, ... of
+ * a row in that order (fmaf), a butterfly adds the 64 partial sums, the bias is added last -- an order that is a function of K
+ * alone, so a box's bits depend neither on n nor on its position.  Softmax: e_c = expf(logit_c - max), the sum in class order,
+ * score = e_label / sum.  Decoding per axis (decode_single): w = v2 - v1, c = v1 + 0.5f * w, d = delta / weight, the size delta
+ * d > clip ? clip : d, pc = d * w + c, pw = expf(dsize) * w, lo = (pc - 0.5f * pw) * ratio, hi = (pc + 0.5f * pw) * ratio.
+ * No clip_boxes_to_image: predict_boxes and predict do not clip.
+ * MPNHIP_ERR_ARG before any launch, the message starting with the entry point's name: n < 0 (n == 0 is a successful no-op,
+ * nothing else is looked at); a null h, weight, bias, proposals, weights, boxes or scores; C outside 2 .. MPNHIP_BOX_MAX_CLASSES;
+ * K < 4 or K % 4 != 0; label outside [0, C); ldh < K or ldh % 4 != 0; h, w_cls or w_box not 16-byte aligned; a weight that is 0
+ * or not finite; n beyond INT32_MAX.  Path counter: box_predict. */
+int mpnhip_box_predict(const float* h, int64_t ldh, const float* w_cls, const float* b_cls, const float* w_box, const float* b_box,
+                       const float* proposals, int64_t n, int k, int num_classes, int label, const float* weights, float clip,
+                       float ratio_h, float ratio_w, float* boxes, float* scores, float* logits, float* deltas, void* stream);
+
+/* the most boxes of one frame mpnhip_nms_batched takes: 64 lanes x 64 bits of one wavefront's "removed" set */
+#define MPNHIP_NMS_MAX_PER_FRAME 4096
+/* scores >= score_threshold followed by torchvision.ops.nms(boxes, scores, iou_threshold) (data/preprocessing.py:26-31) for
+ * every frame of a batch at once.
+ *   boxes [n, 4] (x1, y1, x2, y2), scores [n]; ptr [n_frames + 1] (int32, device): the boxes of frame f are the rows ptr[f] ..
+ *   ptr[f + 1]; it must start at 0 and never descend; max_per_frame (host): an upper bound of a frame's row count;
+ *   score_threshold: -INFINITY switches the filter off.
+ *   keep [n] (uint8) 1 for a kept row; order [n] (int32): from ptr[f] the kept rows of frame f in the order they were visited,
+ *   -1 behind them (and for rows of no frame); count [n_frames] (int32).
+ * Within a frame the candidates -- rows with score >= score_threshold, which a NaN score never is -- are visited by decreasing
+ * score, equal scores (-0 equals +0) by increasing row.  A candidate i is kept unless an earlier KEPT box j of the frame has
+ * iou(j, i) > iou_threshold (strict); a suppressed box suppresses nobody.  iou = inter / ((area_i + area_j) - inter), inter =
+ * max(min(x2) - max(x1), 0) * max(min(y2) - max(y1), 0), area = (x2 - x1) * (y2 - y1); 0 / 0 is NaN and suppresses nothing.
+ * A frame's result depends neither on n_frames nor on the frame's position.
+ * Three steps: a stable radix sort of (frame, descending score) keys over all rows (rocprim); one wavefront per 64 x 64 tile of
+ * every frame's upper triangle builds 64-bit suppression words with ballots, all frames in one launch of n_frames *
+ * ceil(max_per_frame / 64)^2 blocks; ONE wavefront per frame scans them, lane l holding word l of the removed set.
+ * A frame whose OWN range ptr does not describe (negative, descending, beyond n, more rows than max_per_frame; every frame
+ * when ptr[0] != 0) gets count -1 and keeps nothing.  Only a frame's own range is checked: where ptr descends, the results of the
+ * other frames whose rows overlap the bad range are unspecified.  Every access stays inside the buffers whatever ptr holds.
+ * Workspace (every region padded to 256 bytes), W = ceil(max_per_frame / 64):
+ *   keys [n] (8 bytes) | sorted keys [n] | row ids [n] (int32) | sorted row ids [n] | suppression words [n][W] (8 bytes) | rocprim
+ * MPNHIP_ERR_ARG before any launch, the message starting with the entry point's name: n or n_frames < 0 (n == 0 is a successful
+ * no-op: nothing else is looked at and nothing is written, count included); max_per_frame outside 1 .. MPNHIP_NMS_MAX_PER_FRAME;
+ * n above 2^30; n_frames < 1; a null boxes, scores, ptr, keep, order or count; boxes not 16-byte aligned; a NaN threshold; more
+ * tiles than a launch holds.  MPNHIP_ERR_WORKSPACE: a null workspace or one smaller than mpnhip_nms_batched_workspace_bytes (0 for
+ * sizes the operator refuses and for n == 0).  Path counter: nms_batched. */
+size_t mpnhip_nms_batched_workspace_bytes(int64_t n, int max_per_frame);
+int mpnhip_nms_batched(const float* boxes, const float* scores, const int32_t* ptr, int64_t n, int64_t n_frames, int max_per_frame,
+                       float score_threshold, float iou_threshold, unsigned char* keep, int32_t* order, int32_t* count,
+                       void* workspace, size_t workspace_bytes, void* stream);
+
+#define MPNHIP_ROI_MASK_MAX_SIZE 1024
+/* maskrcnn_inference for one label (maskrcnn_fpn.py:68-75), optionally followed by the tracker's nn.Upsample(scale_factor=2,
+ * mode='bilinear') (tracker/mpn_tracker.py:300-341): out [n, S * up, S * up] = bilinear_up(1 / (1 + expf(-logits[:, label]))).
+ *   logits: image i at logits + i * ld (floats), dense [num_channels][S][S] -- num_channels may be 1 when the caller computed
+ *   only the label's channel (label 0); S = size; up 1 or 2.
+ * The sigmoid comes first, one rounded operation at a time.  up == 2, per axis, aten's float32 arithmetic for
+ * align_corners=False: src = max((dst + 0.5f) * 0.5f - 0.5f, 0), i0 = (int)src, i1 = min(i0 + 1, S - 1), l1 = src - i0,
+ * l0 = 1 - l1; out = ly0 * (lx0 * t(y0, x0) + lx1 * t(y0, x1)) + ly1 * (lx0 * t(y1, x0) + lx1 * t(y1, x1)).  One thread per output.
+ * MPNHIP_ERR_ARG before any launch, the message starting with the entry point's name: n < 0 (n == 0 is a successful no-op,
+ * nothing else is looked at); null logits or out; size outside 1 .. MPNHIP_ROI_MASK_MAX_SIZE; up other than 1, 2; num_channels < 1
+ * or an image beyond INT32_MAX; label outside [0, num_channels); ld smaller than an image; more outputs than a launch holds.
+ * Path counter: roi_mask_finish. */
+int mpnhip_roi_mask_finish(const float* logits, int64_t ld, int64_t n, int num_channels, int label, int size, int up, float* out,
+                           void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Training batches: MOTGraphDataset.get_from_frame_and_seq (data/mot_graph_dataset.py:185-234) and the DataLoader's collation
  * for all graphs of a batch at once.  A batch is n_nodes nodes in graph order (graph g owns the nodes graph_ptr[g] ..
  * graph_ptr[g + 1]), every node a row of a sequence table that stays on the device.  Which rows, and the random shifts, come

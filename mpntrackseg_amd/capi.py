@@ -334,6 +334,11 @@ SIGNATURES = {
     "mpnhip_reid_crops": (_I, [_P, _L, _I, _I, _P, _P, _L, _I, _I, _I, _I, C.POINTER(C.c_float), _P, _P, _P, _Z, _P]),
     "mpnhip_rcnn_transform": (_I, [_P, _L, _I, _I, _I, _I, _I, _I, C.POINTER(C.c_float), _P, _P]),
     "mpnhip_fpn_roi_align": (_I, [C.POINTER(FpnLevels), _L, _I, _P, _P, _P, _L, _I, _I, _P, _P, _P]),
+    "mpnhip_box_predict": (_I, [_P, _L, _P, _P, _P, _P, _P, _L, _I, _I, _I, C.POINTER(C.c_float), C.c_float, C.c_float, C.c_float, _P, _P, _P,
+                                _P, _P]),
+    "mpnhip_nms_batched_workspace_bytes": (_Z, [_L, _I]),
+    "mpnhip_nms_batched": (_I, [_P, _P, _P, _L, _L, _I, C.c_float, C.c_float, _P, _P, _P, _P, _Z, _P]),
+    "mpnhip_roi_mask_finish": (_I, [_P, _L, _L, _I, _I, _I, _I, _P, _P]),
     "mpnhip_augment_boxes_workspace_bytes": (_Z, []),
     "mpnhip_augment_boxes": (_I, [_P, _P, _P, _L, _P, _P, _L, _P, _L, _P, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _P]),
     "mpnhip_batch_pairs_workspace_bytes": (_Z, [_L]),

@@ -464,6 +464,7 @@ enum PathCounter {
     PC_NODE_STEP32_BWD, PC_SEG_SHORT, PC_SEG_BLOCK, PC_SEG_BLOCK3, PC_EDGE_ENCODER, PC_EDGE_ENCODER_BWD, PC_TN_MFMA, PC_TN_SMALL,
     PC_TN_GENERIC, PC_GEMM_FP32, PC_GEMM_SPLIT, PC_GEMM_BF16, PC_WEIGHT_PACK, PC_SEG_SHORT3, PC_GEMM_SPLITK, PC_CHAIN_FWD_BF16, PC_TN_PANEL, PC_TN_PANEL_LAUNCH, PC_NODE_CHAIN, PC_TN_PANEL_FALLBACK, PC_CHAIN_BWD_BF16, PC_NODE_CHAIN_BWD, PC_GEMM_BF16_TILED, PC_GEMM_BF16_RING, PC_TN_ROWS16, PC_TN_ROWS16_LAUNCH, PC_TN_PANEL_NARROW, PC_LABEL_OVERLAP_LDS, PC_LABEL_OVERLAP_GLOBAL, PC_CONV_TILE, PC_CONV_SMALL_COUT,
     PC_CONV_TRANSPOSE, PC_LAYER_NORM, PC_CONV_BWD_GATE, PC_CONV_WGRAD, PC_CONV_WGRAD_PLAIN, PC_CONV_AFFINE_TILE, PC_CONV_AFFINE_GROUPED, PC_CONV_AFFINE_SMALL_GRID, PC_CONV_AFFINE_WIDE, PC_MAXPOOL, PC_CONV_AFFINE_UP,
+    PC_BOX_PREDICT, PC_NMS_BATCHED, PC_ROI_MASK_FINISH,
     PC_CONV_TRANSPOSE_BWD,
     PC_LAYER_NORM_BWD, PC_COUNT
 };

@@ -36,6 +36,7 @@ static const char* const g_path_names[PC_COUNT] = {
     "node_step32", "node_step32_bwd", "segment_reduce", "segment_reduce_block", "segment_reduce_block3", "edge_encoder",
     "edge_encoder_bwd", "gemm_tn_mfma", "gemm_tn_small", "gemm_tn_generic", "gemm_fp32", "gemm_split", "gemm_bf16", "weight_pack", "segment_reduce3", "gemm_splitk", "edge_chain_fwd_bf16", "gemm_tn_panel", "wgrad_panel_launches", "node_chain", "wgrad_panel_fallback", "edge_chain_bwd_bf16", "node_chain_bwd", "gemm_bf16_tiled", "gemm_bf16_ring", "wgrad_rows16", "wgrad_rows16_launches", "wgrad_panel_narrow_launches", "label_overlap_lds", "label_overlap_global", "conv_tile", "conv_small_cout",
     "conv_transpose", "layer_norm", "conv_bwd_gate", "conv_wgrad", "conv_wgrad_plain", "conv_affine_tile", "conv_affine_grouped", "conv_affine_small_grid", "conv_affine_wide", "maxpool", "conv_affine_up",
+    "box_predict", "nms_batched", "roi_mask_finish",
     "conv_transpose_bwd",
     "layer_norm_bwd"};
 void count_path(int id) {

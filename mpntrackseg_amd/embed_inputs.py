@@ -184,8 +184,8 @@ def store_reid_embeddings(seq_path, det_file_name, reid_dir, node_core_dir, fram
 
 # ------------------------------------------------------------------------------------------------ FPN RoIAlign
 def resize_boxes(boxes, original_size, image_size):
-    """torchvision's ``resize_boxes`` in torch float32 on the host: boxes [n, 4] of a frame of ``original_size`` (H, W) mapped into
-    the network's image of ``image_size``"""
+    """torchvision's ``resize_boxes`` in torch float32, on the device of ``boxes`` (the host for an array): boxes [n, 4] of a frame
+    of ``original_size`` (H, W) mapped into the network's image of ``image_size``"""
     b = torch.as_tensor(boxes, dtype=torch.float32).reshape(-1, 4)
     ratio_h, ratio_w = (torch.tensor(float(s), dtype=torch.float32) / torch.tensor(float(o), dtype=torch.float32)
                         for s, o in zip(image_size, original_size))
@@ -206,7 +206,8 @@ def level_scales(level_shapes, image_size):
 
 
 def box_levels(boxes, k_min=2, k_max=5):
-    """torchvision 0.6.0's ``LevelMapper`` in torch float32 on the host: ``floor(4 + log2(sqrt(area) / 224) + 1e-6)`` clamped to
+    """torchvision 0.6.0's ``LevelMapper`` in torch float32, on the device of ``boxes`` (the host for an array; ``rcnn_heads`` maps
+    refined boxes where they are): ``floor(4 + log2(sqrt(area) / 224) + 1e-6)`` clamped to
     ``[k_min, k_max]``, minus ``k_min`` (int64 [n])"""
     b = torch.as_tensor(boxes, dtype=torch.float32).reshape(-1, 4)
     s = torch.sqrt((b[:, 2] - b[:, 0]) * (b[:, 3] - b[:, 1]))

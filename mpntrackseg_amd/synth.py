@@ -244,6 +244,27 @@ def make_fpn_weights(net, seed):
     return out
 
 
+def make_roi_head_weights(heads, seed, bias_std=0.05):
+    """Fills every ``state_dict`` entry of a ``rcnn_heads.RoIHeads``, in ``state_dict`` order, from stream i = its index: Conv2d and
+    ConvTranspose2d weights std = sqrt(2 / (shape[1] k k)), Linear weights std = sqrt(2 / in_features) -- ``cls_score`` and
+    ``bbox_pred`` std = sqrt(1 / in_features), so that scores spread and deltas stay moderate --, biases std ``bias_std``.  Loads
+    them into ``heads`` and returns {key: float32 ndarray}."""
+    import torch
+    sd = heads.state_dict()
+    out = {}
+    for i, (k, t) in enumerate(sd.items()):
+        shp = tuple(t.shape)
+        if k.endswith("weight") and len(shp) == 4:
+            v = normal(seed, shp, stream=i, std=math.sqrt(2.0 / (shp[1] * shp[2] * shp[3])))
+        elif k.endswith("weight"):
+            v = normal(seed, shp, stream=i, std=math.sqrt((1.0 if k.startswith("box_predictor.") else 2.0) / shp[1]))
+        else:
+            v = normal(seed, shp, stream=i, std=bias_std)
+        out[k] = v
+    heads.load_state_dict({k: torch.from_numpy(v).to(sd[k].dtype) for k, v in out.items()})
+    return out
+
+
 def make_weights(p, seed=7, bias_std=0.1, gain=1.0):
     """He-normal weights (std = gain*sqrt(2/fan_in)), biases N(0, bias_std^2); one RNG stream per
     tensor in ``hot_path_param_shapes`` order. Returns {key: float32 ndarray}."""

@@ -26,8 +26,9 @@ detections in, track ids out.
 ``:398-417``): the RoI masks of the surviving detections are pasted into their frames, made disjoint and thresholded on the device
 (``masks.py``, ``csrc/full_masks.hip``: one label per pixel instead of one image per detection), leave it as run boundaries and
 become COCO run-length strings on the host (or, with ``strings='device'``, on the device: ``csrc/rle_codec.hip``); the text file
-has the MOTS challenge's rows.  ``mots_sequence`` is ``track_sequence`` followed by ``to_full_masks``: detections in, MOTS rows out.  What stays in the reference needs a second network or files of its
-detector (``_predict_nan_masks``, ``_add_tracktor_detects``), or is commented out there (the trajectory interpolation)."""
+has the MOTS challenge's rows.  ``mots_sequence`` is ``track_sequence`` followed by ``to_full_masks``: detections in, MOTS rows out.  What stays in the reference needs files of its
+detector (``_add_tracktor_detects``, and the data-frame work of ``_predict_nan_masks`` around its network call, which is
+``rcnn_heads.nan_roi_masks``), or is commented out there (the trajectory interpolation)."""
 import collections
 import types
 
