@@ -20,7 +20,6 @@ the last convolution of a block) and one ``mpnhip_maxpool2d_forward``; the pyram
 in the lateral's epilogue -- and four 3 x 3 output convolutions (K = 2304: the grouped summation).  The conv biases go in as
 ``shift`` with no ``scale``.  ``'pool'`` is a strided slice of ``'3'`` (``max_pool2d(kernel 1, stride 2)`` picks every other
 cell).  No MIOpen algorithm search, and the bits of a frame's features do not depend on the batch."""
-import ctypes as C
 from collections import OrderedDict
 
 import torch
@@ -29,8 +28,9 @@ from torch import nn
 
 from . import capi
 from .capi import MpnhipError
-from .cnn import _out_tensor
-from .reid_net import _conv_out, _dense_input, _vec, fold_batchnorm
+from .conv_affine import (Bottleneck, DropsNativeCache, Launch, Stage, _conv_out, _Held, bind_layer, fold_batchnorm, make_layer,
+                          resnet_body_steps, resnet_conv_layers, run_steps)
+from .conv_affine import conv2d_affine_up_native  # noqa: F401  (importable from here as before)
 
 OUT_CHANNELS = 256
 # forward_native's activations per frame in units of the padded input's pixels P = Hp * Wp (floats): the three buffers the
@@ -38,53 +38,6 @@ OUT_CHANNELS = 256
 # results 21.25 P, the input 3 P -- 102.25 P floats, 409 bytes per pixel: 0.42 GB per frame at 768 x 1344.
 NATIVE_FLOATS_PER_PIXEL = 102.25
 MAX_IMAGES = 8        # frames per slice of forward_native: 3.4 GB of activations at 768 x 1344
-
-
-def conv2d_affine_up_native(x, weight, scale, shift, residual, stride=1, relu=False, out=None):
-    """``mpnhip_conv2d_affine_up_forward``: ``reid_net.conv2d_affine_native`` whose ``residual`` ``[N, cout, rh, rw]`` is a map
-    of another size, added as ``F.interpolate(residual, size=(Hout, Wout), mode='nearest')``.  The pyramid's lateral: ``weight``
-    1 x 1, ``scale`` None, ``shift`` the convolution's bias.  No autograd."""
-    xx = _dense_input(x, "x")
-    w = capi.f32c(weight.detach())
-    capi.require_device(w)
-    n, cin, h, wd = xx.shape
-    if w.dim() != 4 or int(w.shape[1]) != cin or w.shape[2] != w.shape[3] or w.device != xx.device:
-        raise MpnhipError("weight %s does not fit %d input channels on %s" % (tuple(w.shape), cin, xx.device))
-    cout, k = int(w.shape[0]), int(w.shape[2])
-    ho, wo = _conv_out(h, stride), _conv_out(wd, stride)
-    sc, sh = _vec(scale, cout, xx, "scale"), _vec(shift, cout, xx, "shift")
-    res = _dense_input(residual, "residual")
-    if tuple(res.shape[:2]) != (n, cout) or res.device != xx.device:
-        raise MpnhipError("residual must be [%d, %d, rh, rw] on %s" % (n, cout, xx.device))
-    y = _out_tensor(out, (n, cout, ho, wo), xx)
-    a = capi.ConvAffineUpArgs()
-    a.x, a.x_stride, a.weight = xx.data_ptr(), xx.stride(0), w.data_ptr()
-    a.scale, a.shift = (sc.data_ptr() if sc is not None else None), (sh.data_ptr() if sh is not None else None)
-    a.residual, a.residual_stride, a.residual_H, a.residual_W = res.data_ptr(), res.stride(0), int(res.shape[2]), int(res.shape[3])
-    a.relu, a.out, a.out_stride, a.n_images = int(bool(relu)), y.data_ptr(), y.stride(0), int(n)
-    a.cin, a.cout, a.H, a.W, a.ksize, a.stride = int(cin), cout, int(h), int(wd), k, int(stride)
-    with torch.cuda.device(y.device):
-        capi.check(capi.load().mpnhip_conv2d_affine_up_forward(C.byref(a), capi.stream_ptr()), "mpnhip_conv2d_affine_up_forward")
-    return y
-
-
-class _Held:
-    """What one buffer of ``forward_native`` holds for the current slice: ``address`` of the slice's first image, ``stride``
-    (floats from one image to the next) and ``shape`` of an image.  ``fixed``: a caller-visible tensor (the input, a result)
-    whose stride and shape never change; the others take the stride and shape of whatever is written into them."""
-    __slots__ = ("address", "stride", "shape", "fixed", "tensor")
-
-    def __init__(self, address, stride=0, shape=None, fixed=False, tensor=None):
-        self.address, self.stride, self.shape, self.fixed, self.tensor = address, stride, shape, fixed, tensor
-
-    def take(self, shape):
-        """a dense ``[C, h, w]`` image per frame is about to be written here"""
-        if not self.fixed:
-            self.stride, self.shape = shape[0] * shape[1] * shape[2], tuple(shape)
-
-    def view(self, m):
-        """the ``m`` images held, as a tensor (diagnosis)"""
-        return self.tensor[:m * self.stride].view((m,) + self.shape)
 
 
 class FrozenBatchNorm2d(nn.Module):
@@ -109,59 +62,23 @@ class FrozenBatchNorm2d(nn.Module):
         return x * scale.reshape(1, -1, 1, 1) + bias.reshape(1, -1, 1, 1)
 
 
-class Bottleneck(nn.Module):
-    """torchvision's Bottleneck: 1 x 1 -> 3 x 3 (carries the stride) -> 1 x 1 (x 4 channels), each with its frozen BatchNorm,
-    around a shortcut"""
-    expansion = 4
-
-    def __init__(self, inplanes, planes, stride=1, downsample=None, norm_layer=FrozenBatchNorm2d):
-        super().__init__()
-        self.conv1 = nn.Conv2d(inplanes, planes, 1, bias=False)
-        self.bn1 = norm_layer(planes)
-        self.conv2 = nn.Conv2d(planes, planes, 3, stride=stride, padding=1, bias=False)
-        self.bn2 = norm_layer(planes)
-        self.conv3 = nn.Conv2d(planes, planes * self.expansion, 1, bias=False)
-        self.bn3 = norm_layer(planes * self.expansion)
-        self.relu = nn.ReLU(inplace=True)
-        self.downsample = downsample
-        self.stride = stride
-
-    def forward(self, x):
-        out = self.relu(self.bn1(self.conv1(x)))
-        out = self.relu(self.bn2(self.conv2(out)))
-        out = self.bn3(self.conv3(out))
-        out = out + (x if self.downsample is None else self.downsample(x))
-        return self.relu(out)
-
-
 class ResNetBody(nn.Module):
     """``IntermediateLayerGetter(resnet50(norm_layer=FrozenBatchNorm2d), {'layer1': '0', ..., 'layer4': '3'})``: the network
     without ``avgpool`` and ``fc``; ``forward`` returns the outputs of ``layer1 .. layer4`` as ``'0' .. '3'``."""
 
     def __init__(self, layers=(3, 4, 6, 3), norm_layer=FrozenBatchNorm2d):
         super().__init__()
-        self.inplanes = 64
         self.conv1 = nn.Conv2d(3, 64, 7, stride=2, padding=3, bias=False)
         self.bn1 = norm_layer(64)
         self.relu = nn.ReLU(inplace=True)
         self.maxpool = nn.MaxPool2d(3, stride=2, padding=1)
-        self.layer1 = self._make_layer(64, layers[0], 1, norm_layer)
-        self.layer2 = self._make_layer(128, layers[1], 2, norm_layer)
-        self.layer3 = self._make_layer(256, layers[2], 2, norm_layer)
-        self.layer4 = self._make_layer(512, layers[3], 2, norm_layer)
+        self.layer1 = make_layer(Bottleneck, 64, 64, layers[0], 1, norm_layer)
+        self.layer2 = make_layer(Bottleneck, 256, 128, layers[1], 2, norm_layer)
+        self.layer3 = make_layer(Bottleneck, 512, 256, layers[2], 2, norm_layer)
+        self.layer4 = make_layer(Bottleneck, 1024, 512, layers[3], 2, norm_layer)
         for m in self.modules():
             if isinstance(m, nn.Conv2d):
                 nn.init.kaiming_normal_(m.weight, mode='fan_out', nonlinearity='relu')
-
-    def _make_layer(self, planes, blocks, stride, norm_layer):
-        out = planes * Bottleneck.expansion
-        downsample = None
-        if stride != 1 or self.inplanes != out:
-            downsample = nn.Sequential(nn.Conv2d(self.inplanes, out, 1, stride=stride, bias=False), norm_layer(out))
-        stack = [Bottleneck(self.inplanes, planes, stride, downsample, norm_layer)]
-        self.inplanes = out
-        stack += [Bottleneck(out, planes, norm_layer=norm_layer) for _ in range(1, blocks)]
-        return nn.Sequential(*stack)
 
     def forward(self, x):
         x = self.maxpool(self.relu(self.bn1(self.conv1(x))))
@@ -201,7 +118,7 @@ class FeaturePyramidNetwork(nn.Module):
         return out
 
 
-class BackboneWithFPN(nn.Module):
+class BackboneWithFPN(DropsNativeCache, nn.Module):
     """``body`` + ``fpn``, see the module docstring.  State-dict names are torchvision's: ``body.conv1.weight``, ``body.bn1.*``,
     ``body.layerL.B.convK.weight``, ``body.layerL.B.bnK.*``, ``body.layerL.0.downsample.{0,1}.*``,
     ``fpn.inner_blocks.I.{weight,bias}``, ``fpn.layer_blocks.I.{weight,bias}``."""
@@ -216,43 +133,10 @@ class BackboneWithFPN(nn.Module):
     def forward(self, x):
         return self.fpn(self.body(x))
 
-    # ---- whatever changes the parameters or the mode drops the folded constants
-    def load_state_dict(self, *args, **kw):
-        self._native = None
-        return super().load_state_dict(*args, **kw)
-
-    def _apply(self, *args, **kw):
-        self._native = None
-        return super()._apply(*args, **kw)
-
-    def train(self, mode=True):
-        self._native = None
-        return super().train(mode)
-
     # ---- the native forward
     def conv_layers(self, H, W):
-        """Every convolution of the body in execution order for an ``H x W`` input, as dicts: ``name`` (the Conv2d's name in the
-        module tree), ``bn`` (its BatchNorm's), ``cin, cout, k, stride, H, W`` (input size), ``Hout, Wout``."""
-        out = []
-
-        def add(name, bn, conv, h, w):
-            s = int(conv.stride[0])
-            out.append(dict(name=name, bn=bn, cin=conv.in_channels, cout=conv.out_channels, k=int(conv.kernel_size[0]), stride=s, H=h, W=w,
-                            Hout=_conv_out(h, s), Wout=_conv_out(w, s)))
-            return out[-1]["Hout"], out[-1]["Wout"]
-
-        h, w = add("body.conv1", "body.bn1", self.body.conv1, H, W)
-        h, w = _conv_out(h, 2), _conv_out(w, 2)
-        for li in range(1, 5):
-            for bi, blk in enumerate(getattr(self.body, "layer%d" % li)):
-                p = "body.layer%d.%d." % (li, bi)
-                add(p + "conv1", p + "bn1", blk.conv1, h, w)
-                h2, w2 = add(p + "conv2", p + "bn2", blk.conv2, h, w)
-                if blk.downsample is not None:
-                    add(p + "downsample.0", p + "downsample.1", blk.downsample[0], h, w)
-                add(p + "conv3", p + "bn3", blk.conv3, h2, w2)
-                h, w = h2, w2
-        return out
+        """Every convolution of the body in execution order for an ``H x W`` input (``conv_affine.resnet_conv_layers``)"""
+        return resnet_conv_layers(self.body, "body.", H, W)
 
     def level_shapes(self, H, W):
         """``[(h, w)]`` of the levels ``'0' .. '3'`` and ``'pool'`` for an ``H x W`` input"""
@@ -277,66 +161,31 @@ class BackboneWithFPN(nn.Module):
         return self._native
 
     def _plan(self, native, H, W):
-        """The launch list of one slice for an ``H x W`` input, cached beside the folded constants.  Buffers: 'x' the input,
-        0 .. 2 the three activation buffers the blocks take turns in, 'c2' .. 'c5' the outputs of layer1 .. layer4 (they stay
-        alive until their lateral has run), '0' .. '3' the results.  Inside a bottleneck with its input in ``ci``: conv1 -> a,
-        conv2 -> b; without a downsample conv3 reads b, adds ci and writes a; with one the shortcut goes to a and conv3 reads b,
-        adds a and writes ci when that is one of the three (the input is dead), the third of them when ci is a kept 'c' buffer
-        -- an output never overlaps what its launch reads.  The last block of a layer writes the layer's 'c' buffer.  The inner
-        maps of the pyramid reuse the three buffers, which the body no longer needs."""
+        """The launch list of one slice for an ``H x W`` input, cached beside the folded constants.  The body's steps are
+        ``conv_affine.resnet_body_steps`` with every layer's output kept: 'c2' .. 'c5' stay alive until their lateral has run.
+        The pyramid follows, coarsest level first: the inner maps take turns in buffers 0 and 1, which the body no longer needs,
+        and the output convolutions write the results '0' .. '3'."""
         plan = native["plans"].get((H, W))
         if plan is not None:
             return plan
         mods = dict(self.named_modules())
-        layers = {c["name"]: c for c in self.conv_layers(H, W)}
-        for name, c in layers.items():
-            c["scale"], c["shift"] = native["affine"][name]
+        layers = {c["name"]: bind_layer(c, mods[c["name"]], *native["affine"][c["name"]]) for c in self.conv_layers(H, W)}
+        keep = {li: 'c%d' % (li + 1) for li in range(1, 5)}
+        steps = resnet_body_steps(self.body, "body.", layers, keep, ("C2", "C3", "C4", "C5"))
+        kept = {st.dst: st.layer["floats"] for st in steps if isinstance(st, Launch) and st.dst in keep.values()}
         shapes = self.level_shapes(H, W)
-        for i in range(4):
-            h, w = shapes[i]
-            layers["fpn.inner_blocks.%d" % i] = dict(name="fpn.inner_blocks.%d" % i, cin=self.fpn.inner_blocks[i].in_channels, cout=OUT_CHANNELS,
-                                                     k=1, stride=1, H=h, W=w, Hout=h, Wout=w)
-            layers["fpn.layer_blocks.%d" % i] = dict(name="fpn.layer_blocks.%d" % i, cin=OUT_CHANNELS, cout=OUT_CHANNELS, k=3, stride=1,
-                                                     H=h, W=w, Hout=h, Wout=w)
-        for name, c in layers.items():
-            c["weight"] = mods[name].weight                 # the parameter itself: a deepcopy of the module keeps the tie
-            if not c["weight"].is_contiguous():
-                raise MpnhipError("forward_native: %s.weight is not contiguous" % name)
-            if name.startswith("fpn."):
-                c["scale"], c["shift"] = None, mods[name].bias
-            c["floats"] = c["cout"] * c["Hout"] * c["Wout"]
-        stem = layers["body.conv1"]
-        steps = [("conv", stem, 'x', 0, None, True, None), ("pool", stem, 0, 1, None, False, None), ("stage", "stem", 1)]
-        ci = 1
-        for li in range(1, 5):
-            blocks = getattr(self.body, "layer%d" % li)
-            for bi, blk in enumerate(blocks):
-                p = "body.layer%d.%d." % (li, bi)
-                free = [i for i in range(3) if i != ci]
-                a, b = free[0], free[1]
-                last = 'c%d' % (li + 1) if bi == len(blocks) - 1 else None
-                steps.append(("conv", layers[p + "conv1"], ci, a, None, True, None))
-                steps.append(("conv", layers[p + "conv2"], a, b, None, True, None))
-                if blk.downsample is None:
-                    dst = last or a
-                    steps.append(("conv", layers[p + "conv3"], b, dst, ci, True, None))
-                else:
-                    dst = last or (ci if isinstance(ci, int) else free[2])
-                    steps.append(("conv", layers[p + "downsample.0"], ci, a, None, False, None))
-                    steps.append(("conv", layers[p + "conv3"], b, dst, a, True, None))
-                ci = dst
-            steps.append(("stage", "C%d" % (li + 1), ci))
-        # the pyramid, coarsest level first: the inner map, then the level's output convolution
         prev = None
         for i in range(3, -1, -1):
+            h, w = shapes[i]
+            for name, k in (("fpn.inner_blocks.%d" % i, 1), ("fpn.layer_blocks.%d" % i, 3)):     # the convolutions' biases go in as shift
+                layers[name] = bind_layer(dict(name=name, cin=mods[name].in_channels, cout=OUT_CHANNELS, k=k, stride=1, H=h, W=w, Hout=h,
+                                               Wout=w), mods[name], None, mods[name].bias)
             buf = 0 if prev != 0 else 1
             up = None if prev is None else shapes[i + 1]
-            steps.append(("conv", layers["fpn.inner_blocks.%d" % i], 'c%d' % (i + 2), buf, prev, False, up))
-            steps.append(("stage", "inner%d" % i, buf))
-            steps.append(("conv", layers["fpn.layer_blocks.%d" % i], buf, str(i), None, False, None))
+            steps.append(Launch("conv", layers["fpn.inner_blocks.%d" % i], 'c%d' % (i + 2), buf, prev, False, up))
+            steps.append(Stage("inner%d" % i, buf))
+            steps.append(Launch("conv", layers["fpn.layer_blocks.%d" % i], buf, str(i)))
             prev = buf
-        kept = {'c%d' % (li + 1): layers["body.layer%d.%d.conv3" % (li, len(getattr(self.body, "layer%d" % li)) - 1)]["floats"]
-                for li in range(1, 5)}
         plan = dict(steps=steps, per_image=max(c["floats"] for c in layers.values()), kept=kept, shapes=shapes)
         native["plans"][(H, W)] = plan
         return plan
@@ -364,7 +213,6 @@ class BackboneWithFPN(nn.Module):
         step = max(min(int(max_images), n), 1)
         shapes = plan["shapes"]
         lib = capi.load()
-        args, up = capi.ConvAffineArgs(), capi.ConvAffineUpArgs()
         with torch.cuda.device(x.device):
             stream = capi.stream_ptr()
             out = OrderedDict((str(i), torch.empty((n, OUT_CHANNELS) + shapes[i], dtype=torch.float32, device=x.device)) for i in range(4))
@@ -382,31 +230,7 @@ class BackboneWithFPN(nn.Module):
                     held[k] = _Held(t.data_ptr(), tensor=t)
                 for i in range(4):
                     held[str(i)] = _Held(out[str(i)][k0:k0 + m].data_ptr(), out[str(i)].stride(0), (OUT_CHANNELS,) + shapes[i], fixed=True)
-                for st in plan["steps"]:
-                    if st[0] == "stage":
-                        if stages is not None:
-                            stages.append((st[1], held[st[2]].view(m).clone()))
-                        continue
-                    kind, c, src, dst, res, relu, res_hw = st
-                    xs, ys, rs = held[src], held[dst], (held[res] if res is not None else None)
-                    if kind == "pool":
-                        ys.take((c["cout"], _conv_out(c["Hout"], 2), _conv_out(c["Wout"], 2)))
-                        capi.check(lib.mpnhip_maxpool2d_forward(xs.address, xs.stride, m, c["cout"], c["Hout"], c["Wout"], ys.address,
-                                                                ys.stride, stream), "mpnhip_maxpool2d_forward")
-                        continue
-                    ys.take((c["cout"], c["Hout"], c["Wout"]))
-                    a = up if res_hw is not None else args
-                    a.x, a.x_stride, a.weight = xs.address, xs.stride, c["weight"].data_ptr()
-                    a.scale = c["scale"].data_ptr() if c["scale"] is not None else None
-                    a.shift = c["shift"].data_ptr()
-                    a.residual, a.residual_stride = (rs.address, rs.stride) if rs is not None else (None, 0)
-                    a.relu, a.out, a.out_stride, a.n_images = int(relu), ys.address, ys.stride, m
-                    a.cin, a.cout, a.H, a.W, a.ksize, a.stride = c["cin"], c["cout"], c["H"], c["W"], c["k"], c["stride"]
-                    if res_hw is not None:
-                        a.residual_H, a.residual_W = res_hw
-                        capi.check(lib.mpnhip_conv2d_affine_up_forward(C.byref(a), stream), "mpnhip_conv2d_affine_up_forward")
-                    else:
-                        capi.check(lib.mpnhip_conv2d_affine_forward(C.byref(a), stream), "mpnhip_conv2d_affine_forward")
+                run_steps(plan["steps"], held, m, lib, stream, stages)
             out['pool'] = out['3'][:, :, ::2, ::2].contiguous()
         return out
 

@@ -29,8 +29,8 @@ from torch import nn
 
 from . import capi, embed_inputs
 from .capi import MpnhipError, check, ptr, stream_ptr
-from .cnn import conv2d_native
-from .reid_net import conv2d_affine_native
+from .cnn import _image_dense, conv2d_native
+from .conv_affine import conv2d_affine_native
 
 BBOX_REG_WEIGHTS = (10.0, 10.0, 5.0, 5.0)         # RoIHeads' default bbox_reg_weights
 BBOX_XFORM_CLIP = math.log(1000.0 / 16)           # BoxCoder's bbox_xform_clip
@@ -256,7 +256,6 @@ def box_predict_native(h, predictor, proposals, label=1, ratios=(1.0, 1.0), weig
 def roi_mask_finish_native(logits, label=0, upsample=1):
     """``mpnhip_roi_mask_finish``: ``[n, S * up, S * up]`` from mask logits float32 [n, C, S, S] on the device with dense images
     (a channel slice of a wider tensor is fine)."""
-    from .cnn import _image_dense
     capi.require_device(logits)
     if logits.dim() != 4 or logits.shape[2] != logits.shape[3]:
         raise MpnhipError("roi_mask_finish_native takes logits [n, C, S, S]")

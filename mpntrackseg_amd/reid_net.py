@@ -21,7 +21,6 @@ The folded constants ``scale = gamma / sqrt(var + eps)``, ``shift = beta - mean 
 computed in float64 and rounded once to the parameters' dtype (float32 for every module ``forward_native`` accepts); they are
 cached on the module by ``prepare_native()`` and dropped by ``load_state_dict``, ``.to()`` (anything that goes through
 ``_apply``) and ``.train()`` / ``.eval()``."""
-import ctypes as C
 from collections import OrderedDict
 
 import torch
@@ -29,127 +28,15 @@ from torch import nn
 
 from . import capi
 from .capi import MpnhipError
-from .cnn import _image_dense, _out_tensor
+from .conv_affine import (Bottleneck, DropsNativeCache, _Held, _dense_input, bind_layer, fold_batchnorm, fold_linear_batchnorm,
+                          make_layer, resnet_body_steps, resnet_conv_layers, run_steps)
+from .conv_affine import conv2d_affine_native, maxpool2d_native  # noqa: F401  (importable from here as before)
 
 
 MAX_SLICE = 8191      # crops per slice of forward_native: launch_gemm changes its kernel (hence v's summation) at 8192 rows
 
 
-# ------------------------------------------------------------------------------------------------ operators
-def _conv_out(size, stride):
-    return (int(size) - 1) // int(stride) + 1
-
-
-def _dense_input(x, what):
-    if not isinstance(x, torch.Tensor) or x.dim() != 4:
-        raise MpnhipError("%s must be a float32 [N, C, H, W] device tensor" % what)
-    capi.require_device(x)
-    return x if _image_dense(x) else capi.f32c(x)
-
-
-def _vec(t, n, like, what):
-    if t is None:
-        return None
-    t = capi.f32c(t.detach())
-    capi.require_device(t)
-    if t.numel() != n or t.device != like.device:
-        raise MpnhipError("%s must hold %d floats on %s" % (what, n, like.device))
-    return t
-
-
-def conv2d_affine_native(x, weight, scale, shift, stride=1, residual=None, relu=False, out=None):
-    """``mpnhip_conv2d_affine_forward``: Conv2d(k = 1 | 3 | 7, stride 1 | 2, padding k // 2, no bias) on ``x`` [N, cin, H, W]
-    with ``weight`` [cout, cin, k, k], then ``* scale + shift`` per output channel (either may be None), ``+ residual``
-    ([N, cout, Hout, Wout] or None) and the ReLU.  ``out`` (optional) may be a channel slice of a wider tensor; it must not
-    overlap ``x`` or ``residual``.  No autograd."""
-    xx = _dense_input(x, "x")
-    w = capi.f32c(weight.detach())
-    capi.require_device(w)
-    n, cin, h, wd = xx.shape
-    if w.dim() != 4 or int(w.shape[1]) != cin or w.shape[2] != w.shape[3] or w.device != xx.device:
-        raise MpnhipError("weight %s does not fit %d input channels on %s" % (tuple(w.shape), cin, xx.device))
-    cout, k = int(w.shape[0]), int(w.shape[2])
-    ho, wo = _conv_out(h, stride), _conv_out(wd, stride)
-    sc, sh = _vec(scale, cout, xx, "scale"), _vec(shift, cout, xx, "shift")
-    res = None
-    if residual is not None:
-        res = _dense_input(residual, "residual")
-        if tuple(res.shape) != (n, cout, ho, wo) or res.device != xx.device:
-            raise MpnhipError("residual must be [%d, %d, %d, %d] on %s" % (n, cout, ho, wo, xx.device))
-    y = _out_tensor(out, (n, cout, ho, wo), xx)
-    a = capi.ConvAffineArgs()
-    a.x, a.x_stride, a.weight = xx.data_ptr(), xx.stride(0), w.data_ptr()
-    a.scale, a.shift = (sc.data_ptr() if sc is not None else None), (sh.data_ptr() if sh is not None else None)
-    a.residual, a.residual_stride = (res.data_ptr(), res.stride(0)) if res is not None else (None, 0)
-    a.relu, a.out, a.out_stride, a.n_images = int(bool(relu)), y.data_ptr(), y.stride(0), int(n)
-    a.cin, a.cout, a.H, a.W, a.ksize, a.stride = int(cin), cout, int(h), int(wd), k, int(stride)
-    with torch.cuda.device(y.device):
-        capi.check(capi.load().mpnhip_conv2d_affine_forward(C.byref(a), capi.stream_ptr()), "mpnhip_conv2d_affine_forward")
-    return y
-
-
-def maxpool2d_native(x, out=None):
-    """``mpnhip_maxpool2d_forward``: MaxPool2d(3, stride 2, padding 1) on ``x`` [N, C, H, W].  No autograd."""
-    xx = _dense_input(x, "x")
-    n, c, h, wd = xx.shape
-    y = _out_tensor(out, (n, c, _conv_out(h, 2), _conv_out(wd, 2)), xx)
-    with torch.cuda.device(y.device):
-        capi.check(capi.load().mpnhip_maxpool2d_forward(capi.ptr(xx), xx.stride(0), int(n), int(c), int(h), int(wd), capi.ptr(y),
-                                                        y.stride(0), capi.stream_ptr()), "mpnhip_maxpool2d_forward")
-    return y
-
-
-def fold_batchnorm(bn):
-    """``(scale, shift)`` of an eval-mode BatchNorm, ``gamma / sqrt(var + eps)`` and ``beta - mean * scale``: float64 arithmetic,
-    one rounding to the module's dtype."""
-    var, mean = bn.running_var.detach().double(), bn.running_mean.detach().double()
-    gamma = bn.weight.detach().double() if bn.weight is not None else torch.ones_like(var)
-    beta = bn.bias.detach().double() if bn.bias is not None else torch.zeros_like(var)
-    scale = gamma / torch.sqrt(var + bn.eps)
-    shift = beta - mean * scale
-    dtype = bn.running_var.dtype
-    return scale.to(dtype).contiguous(), shift.to(dtype).contiguous()
-
-
-def fold_linear_batchnorm(linear, bn):
-    """``(weight, bias)`` of ``bn(linear(x))`` as one Linear, float64 arithmetic, one rounding to the module's dtype."""
-    var, mean = bn.running_var.detach().double(), bn.running_mean.detach().double()
-    gamma = bn.weight.detach().double() if bn.weight is not None else torch.ones_like(var)
-    beta = bn.bias.detach().double() if bn.bias is not None else torch.zeros_like(var)
-    scale = gamma / torch.sqrt(var + bn.eps)
-    w = linear.weight.detach().double() * scale[:, None]
-    b0 = linear.bias.detach().double() if linear.bias is not None else torch.zeros_like(var)
-    b = (b0 - mean) * scale + beta
-    dtype = linear.weight.dtype
-    return w.to(dtype).contiguous(), b.to(dtype).contiguous()
-
-
-# ------------------------------------------------------------------------------------------------ modules
-class Bottleneck(nn.Module):
-    """1 x 1 -> 3 x 3 (carries the stride) -> 1 x 1 (x 4 channels), each with its BatchNorm, around a shortcut."""
-    expansion = 4
-
-    def __init__(self, inplanes, planes, stride=1, downsample=None):
-        super().__init__()
-        self.conv1 = nn.Conv2d(inplanes, planes, 1, bias=False)
-        self.bn1 = nn.BatchNorm2d(planes)
-        self.conv2 = nn.Conv2d(planes, planes, 3, stride=stride, padding=1, bias=False)
-        self.bn2 = nn.BatchNorm2d(planes)
-        self.conv3 = nn.Conv2d(planes, planes * self.expansion, 1, bias=False)
-        self.bn3 = nn.BatchNorm2d(planes * self.expansion)
-        self.relu = nn.ReLU(inplace=True)
-        self.downsample = downsample
-        self.stride = stride
-
-    def forward(self, x):
-        out = self.relu(self.bn1(self.conv1(x)))
-        out = self.relu(self.bn2(self.conv2(out)))
-        out = self.bn3(self.conv3(out))
-        out = out + (x if self.downsample is None else self.downsample(x))
-        return self.relu(out)
-
-
-class ResNet(nn.Module):
+class ResNet(DropsNativeCache, nn.Module):
     """``models/resnet.py``'s ResNet for the block types this project runs (``Bottleneck``), see the module docstring."""
 
     def __init__(self, num_classes, loss, block, layers, last_stride=2, fc_dims=None, dropout_p=None):
@@ -157,31 +44,20 @@ class ResNet(nn.Module):
         self.loss = loss
         self.block = block
         self.dropout_p = dropout_p
-        self.inplanes = 64
         self.conv1 = nn.Conv2d(3, 64, 7, stride=2, padding=3, bias=False)
         self.bn1 = nn.BatchNorm2d(64)
         self.relu = nn.ReLU(inplace=True)
         self.maxpool = nn.MaxPool2d(3, stride=2, padding=1)
-        self.layer1 = self._make_layer(block, 64, layers[0], 1)
-        self.layer2 = self._make_layer(block, 128, layers[1], 2)
-        self.layer3 = self._make_layer(block, 256, layers[2], 2)
-        self.layer4 = self._make_layer(block, 512, layers[3], last_stride)
+        self.layer1 = make_layer(block, 64, 64, layers[0], 1)
+        self.layer2 = make_layer(block, 64 * block.expansion, 128, layers[1], 2)
+        self.layer3 = make_layer(block, 128 * block.expansion, 256, layers[2], 2)
+        self.layer4 = make_layer(block, 256 * block.expansion, 512, layers[3], last_stride)
         self.global_avgpool = nn.AdaptiveAvgPool2d((1, 1))
         self.feature_dim = 512 * block.expansion
         self.fc = self._construct_fc_layer(fc_dims, 512 * block.expansion, dropout_p)
         self.classifier = nn.Linear(self.feature_dim, num_classes)
         self._native = None
         self._init_params()
-
-    def _make_layer(self, block, planes, blocks, stride):
-        downsample = None
-        if stride != 1 or self.inplanes != planes * block.expansion:
-            downsample = nn.Sequential(nn.Conv2d(self.inplanes, planes * block.expansion, 1, stride=stride, bias=False),
-                                       nn.BatchNorm2d(planes * block.expansion))
-        stack = [block(self.inplanes, planes, stride, downsample)]
-        self.inplanes = planes * block.expansion
-        stack += [block(self.inplanes, planes) for _ in range(1, blocks)]
-        return nn.Sequential(*stack)
 
     def _construct_fc_layer(self, fc_dims, input_dim, dropout_p=None):
         if fc_dims is None:
@@ -219,43 +95,10 @@ class ResNet(nn.Module):
         v = v.view(v.size(0), -1)
         return (f, self.fc(v)) if self.fc is not None else (f, v)
 
-    # ---- whatever changes the parameters or the mode drops the folded constants
-    def load_state_dict(self, *args, **kw):
-        self._native = None
-        return super().load_state_dict(*args, **kw)
-
-    def _apply(self, *args, **kw):
-        self._native = None
-        return super()._apply(*args, **kw)
-
-    def train(self, mode=True):
-        self._native = None
-        return super().train(mode)
-
     # ---- the native forward
     def conv_layers(self, H, W):
-        """Every convolution of ``featuremaps`` in execution order for an ``H x W`` input, as dicts: ``name`` (the Conv2d's name
-        in the module tree), ``bn`` (its BatchNorm's), ``cin, cout, k, stride, H, W`` (input size), ``Hout, Wout``."""
-        out = []
-
-        def add(name, bn, conv, h, w):
-            s = int(conv.stride[0])
-            out.append(dict(name=name, bn=bn, cin=conv.in_channels, cout=conv.out_channels, k=int(conv.kernel_size[0]), stride=s, H=h, W=w,
-                            Hout=_conv_out(h, s), Wout=_conv_out(w, s)))
-            return out[-1]["Hout"], out[-1]["Wout"]
-
-        h, w = add("conv1", "bn1", self.conv1, H, W)
-        h, w = _conv_out(h, 2), _conv_out(w, 2)
-        for li in range(1, 5):
-            for bi, blk in enumerate(getattr(self, "layer%d" % li)):
-                p = "layer%d.%d." % (li, bi)
-                add(p + "conv1", p + "bn1", blk.conv1, h, w)
-                h2, w2 = add(p + "conv2", p + "bn2", blk.conv2, h, w)
-                if blk.downsample is not None:
-                    add(p + "downsample.0", p + "downsample.1", blk.downsample[0], h, w)
-                add(p + "conv3", p + "bn3", blk.conv3, h2, w2)
-                h, w = h2, w2
-        return out
+        """Every convolution of ``featuremaps`` in execution order for an ``H x W`` input (``conv_affine.resnet_conv_layers``)"""
+        return resnet_conv_layers(self, "", H, W)
 
     def output_shapes(self, H, W):
         """``((C, h, w) of an image of f, width of v)`` for an ``H x W`` input"""
@@ -294,41 +137,15 @@ class ResNet(nn.Module):
 
     def _plan(self, native, H, W):
         """The launch list of one slice for an ``H x W`` input, cached beside the folded constants: the convolutions in execution
-        order with their weights and constants and the buffers they read and write.  Buffers: 'x' the input, 0 .. 2 the three
-        activation buffers the blocks take turns in, 'f' the result.  Inside a bottleneck with its input in buffer ``ci`` and
-        ``a``, ``b`` the other two: conv1 -> a, conv2 -> b; without a downsample conv3 reads b, adds ci and writes a (conv1's
-        output is dead); with one the shortcut goes to a and conv3 reads b, adds a and writes ci (the input is dead) -- an output
-        never overlaps what its launch reads."""
+        order with their weights and constants and the buffers they read and write (``conv_affine.resnet_body_steps``): 'x' the
+        input, 0 .. 2 the three activation buffers the blocks take turns in, 'f' -- the result -- kept from layer4."""
         plan = native["plans"].get((H, W))
         if plan is not None:
             return plan
         mods = dict(self.named_modules())
-        layers = {c["name"]: c for c in self.conv_layers(H, W)}
-        for name, c in layers.items():
-            c["weight"] = mods[name].weight                 # the parameter itself: a deepcopy of the module keeps the tie
-            if not c["weight"].is_contiguous():
-                raise MpnhipError("forward_native: %s.weight is not contiguous" % name)
-            c["scale"], c["shift"] = native["affine"][name]
-            c["floats"] = c["cout"] * c["Hout"] * c["Wout"]
-        names = list(layers)
-        steps = [("conv", layers["conv1"], 'x', 0, None, True), ("pool", layers["conv1"], 0, 1, None, False), ("stage", "stem", 1)]
-        ci = 1
-        for li in range(1, 5):
-            for bi, blk in enumerate(getattr(self, "layer%d" % li)):
-                p = "layer%d.%d." % (li, bi)
-                a, b = [i for i in range(3) if i != ci]
-                last = p + "conv3" == names[-1]
-                steps.append(("conv", layers[p + "conv1"], ci, a, None, True))
-                steps.append(("conv", layers[p + "conv2"], a, b, None, True))
-                if blk.downsample is None:
-                    steps.append(("conv", layers[p + "conv3"], b, 'f' if last else a, ci, True))
-                    ci = a
-                else:
-                    steps.append(("conv", layers[p + "downsample.0"], ci, a, None, False))
-                    steps.append(("conv", layers[p + "conv3"], b, 'f' if last else ci, a, True))
-            steps.append(("stage", "layer%d" % li, 'f' if li == 4 else ci))
-        final = layers[names[-1]]
-        plan = dict(steps=steps, per_image=max(c["floats"] for c in layers.values()), final=final)
+        layers = {c["name"]: bind_layer(c, mods[c["name"]], *native["affine"][c["name"]]) for c in self.conv_layers(H, W)}
+        steps = resnet_body_steps(self, "", layers, {4: 'f'}, ("layer1", "layer2", "layer3", "layer4"))
+        plan = dict(steps=steps, per_image=max(c["floats"] for c in layers.values()), final=list(layers.values())[-1])
         native["plans"][(H, W)] = plan
         return plan
 
@@ -350,10 +167,8 @@ class ResNet(nn.Module):
         n, _, H, W = (int(s) for s in x.shape)
         plan = self._plan(native, H, W)
         step = max(min(int(max_images), n, MAX_SLICE), 1)
-        final = plan["final"]
-        hf, wf, cf = final["Hout"], final["Wout"], final["cout"]
+        cf, hf, wf = plan["final"]["out_shape"]
         lib = capi.load()
-        args = capi.ConvAffineArgs()
         with torch.cuda.device(x.device):
             stream = capi.stream_ptr()
             f = torch.empty((n, cf, hf, wf), dtype=torch.float32, device=x.device)
@@ -361,33 +176,14 @@ class ResNet(nn.Module):
             bufs = [torch.empty(step * plan["per_image"], dtype=torch.float32, device=x.device) for _ in range(3)]
             for k0 in range(0, n, step):
                 m = min(step, n - k0)
-                # buffer -> [address, floats per image, shape of an image] of what it holds now
-                held = {'x': [x[k0:k0 + m].data_ptr(), x.stride(0), None], 'f': [f[k0:k0 + m].data_ptr(), f.stride(0), (cf, hf, wf)]}
+                fs = f[k0:k0 + m]
+                held = {'x': _Held(x[k0:k0 + m].data_ptr(), x.stride(0), (3, H, W), fixed=True),
+                        'f': _Held(fs.data_ptr(), f.stride(0), (cf, hf, wf), fixed=True, tensor=fs.view(-1) if stages is not None else None)}
                 for i in range(3):
-                    held[i] = [bufs[i].data_ptr(), 0, None]
-                for st in plan["steps"]:
-                    if st[0] == "stage":
-                        if stages is not None:
-                            src = f[k0:k0 + m] if st[2] == 'f' else bufs[st[2]][:m * held[st[2]][1]].view((m,) + held[st[2]][2])
-                            stages.append((st[1], src.clone()))
-                        continue
-                    kind, c, src, dst, res, relu = st
-                    if kind == "pool":
-                        hp, wp = _conv_out(c["Hout"], 2), _conv_out(c["Wout"], 2)
-                        held[dst][1:] = [c["cout"] * hp * wp, (c["cout"], hp, wp)]
-                        capi.check(lib.mpnhip_maxpool2d_forward(held[src][0], held[src][1], m, c["cout"], c["Hout"], c["Wout"], held[dst][0],
-                                                                held[dst][1], stream), "mpnhip_maxpool2d_forward")
-                        continue
-                    if dst != 'f':
-                        held[dst][1:] = [c["floats"], (c["cout"], c["Hout"], c["Wout"])]
-                    args.x, args.x_stride, args.weight = held[src][0], held[src][1], c["weight"].data_ptr()
-                    args.scale, args.shift = c["scale"].data_ptr(), c["shift"].data_ptr()
-                    args.residual, args.residual_stride = (held[res][0], held[res][1]) if res is not None else (None, 0)
-                    args.relu, args.out, args.out_stride, args.n_images = int(relu), held[dst][0], held[dst][1], m
-                    args.cin, args.cout, args.H, args.W, args.ksize, args.stride = c["cin"], c["cout"], c["H"], c["W"], c["k"], c["stride"]
-                    capi.check(lib.mpnhip_conv2d_affine_forward(C.byref(args), stream), "mpnhip_conv2d_affine_forward")
+                    held[i] = _Held(bufs[i].data_ptr(), tensor=bufs[i])
+                run_steps(plan["steps"], held, m, lib, stream, stages)
                 pooled = torch.empty((m, cf), dtype=torch.float32, device=x.device)
-                capi.check(lib.mpnhip_avgpool(held['f'][0], m * cf, hf * wf, capi.ptr(pooled), stream), "mpnhip_avgpool")
+                capi.check(lib.mpnhip_avgpool(held['f'].address, m * cf, hf * wf, capi.ptr(pooled), stream), "mpnhip_avgpool")
                 h = pooled
                 for i, (wt, bias) in enumerate(native["fc"]):
                     y = v[k0:k0 + m] if i == len(native["fc"]) - 1 else torch.empty((m, wt.shape[0]), dtype=torch.float32, device=x.device)

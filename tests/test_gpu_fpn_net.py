@@ -122,6 +122,26 @@ def test_features_do_not_depend_on_the_batch(seeded):
     assert [tuple(none[k].shape) for k in NAMES] == [(0,) + tuple(s.native[k].shape[1:]) for k in NAMES]
 
 
+def test_one_frame_of_40_by_72(seeded):
+    """the upper left 40 x 72 of the first frame: levels of 10 x 18, 5 x 9, 3 x 5 and 2 x 3 -- odd strided sizes, and upsample
+    ratios that are no integers (3 -> 5, 5 -> 9).  The module docstring's rule, its comparators measured here."""
+    s = seeded
+    xd = s.xd[:1, :, :40, :72].contiguous()
+    x = xd.cpu()
+    with torch.no_grad():
+        stock = s.net(xd)
+        cpu32 = copy.deepcopy(s.net).cpu()(x)
+        ref = s.host64(x.double())
+    native = s.net.forward_native(xd)
+    shapes = [(10, 18), (5, 9), (3, 5), (2, 3), (1, 2)]
+    for k, hw in zip(NAMES, shapes):
+        e_native, e_stock, e_cpu = nerr(native[k].cpu(), ref[k]), nerr(stock[k].cpu(), ref[k]), nerr(cpu32[k], ref[k])
+        bound = max(TOL, 4 * max(e_cpu, e_stock))
+        print("%s: native %.3g, stock device %.3g, float32 CPU %.3g (bound %.3g)" % (k, e_native, e_stock, e_cpu, bound))
+        assert tuple(native[k].shape) == (1, 256) + hw
+        assert e_native < bound, k
+
+
 def test_refusals_and_the_dropped_cache(seeded):
     s = seeded
     net = copy.deepcopy(s.net)

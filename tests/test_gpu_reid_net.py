@@ -112,6 +112,30 @@ def test_f_does_not_depend_on_the_batch(seeded):
     assert torch.equal(v3, s.native[1])
 
 
+def test_one_block_per_layer_on_odd_crops():
+    """ResNet [1, 1, 1, 1] with last stride 2 and one fc layer on 2 crops of 37 x 21: every block has a downsample, the last one
+    writes f, and the strided launches meet odd sizes (37 x 21 -> 19 x 11 -> pool 10 x 6 -> 5 x 3 -> 3 x 2 -> 2 x 1).  The module
+    docstring's rule, its comparators measured here."""
+    host = reid_net.ResNet(10, 'xent', reid_net.Bottleneck, [1, 1, 1, 1], fc_dims=[16])
+    synth.make_reid_weights(host, SEED)
+    host.eval()
+    x = torch.from_numpy(synth.normal(SEED, (2, 3, 37, 21), stream=synth.REID_INPUT_STREAM))
+    with torch.no_grad():
+        cpu32 = host(x)
+        ref = copy.deepcopy(host).double()(x.double())
+        net = host.to(dev())
+        stock = net(x.to(dev()))
+    native = net.forward_native(x.to(dev()))
+    assert tuple(native[0].shape) == (2, 2048, 2, 1) and tuple(native[1].shape) == (2, 16)
+    for i, what in enumerate(("f", "v")):
+        e_native, e_stock, e_cpu = nerr(native[i].cpu(), ref[i]), nerr(stock[i].cpu(), ref[i]), nerr(cpu32[i], ref[i])
+        bound = max(TOL, 4 * max(e_cpu, e_stock))
+        print("%s: native %.3g, stock device %.3g, float32 CPU %.3g (bound %.3g)" % (what, e_native, e_stock, e_cpu, bound))
+        assert e_native < bound, what
+    sliced = net.forward_native(x.to(dev()), max_images=1)
+    assert torch.equal(sliced[0], native[0]) and torch.equal(sliced[1], native[1])
+
+
 def test_refusals_and_the_dropped_cache(seeded):
     s = seeded
     net = copy.deepcopy(s.net)

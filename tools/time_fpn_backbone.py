@@ -84,38 +84,33 @@ def one(size, runs, warmup):
 
 
 def group_times(net, x):
-    """Where the native forward's time goes: every convolution of the launch list alone, on an input of its shape and through the
-    entry point and epilogue the forward uses for it, as the median of five device-event-timed calls after one warm-up; summed
-    by group (the stem's convolution, layer1 .. layer4, the pyramid's laterals and its output convolutions) with the group's
-    multiply-adds.  A body convolution carries scale, shift and the ReLU, a block's last one also the residual; the top lateral
-    is the plain entry point with a bias; the three laterals below it are ``mpnhip_conv2d_affine_up_forward`` reading the coarser
-    level's map; the output convolutions carry a bias.  The max-pool and the host's work between launches are not in it."""
+    """Where the native forward's time goes: every convolution of the forward's own launch plan (its ``Launch`` records: layer,
+    residual or not, ReLU, the ``up`` size) alone, on an input of its shape and through the entry point and epilogue the record
+    names, as the median of five device-event-timed calls after one warm-up; summed by group (the stem's convolution, layer1 ..
+    layer4, the pyramid's laterals and its output convolutions) with the group's multiply-adds.  The max-pool and the host's work
+    between launches are not in it."""
     import torch
-    from mpntrackseg_amd.fpn_net import conv2d_affine_up_native
-    from mpntrackseg_amd.reid_net import conv2d_affine_native
+    from mpntrackseg_amd.conv_affine import Launch, conv2d_affine_native, conv2d_affine_up_native
     n, _, H, W = (int(s) for s in x.shape)
-    layers = [(c["name"].split(".")[1] if c["name"] != "body.conv1" else "stem", dict(c, affine=True, residual=c["name"].endswith("conv3"),
-                                                                                     relu=not c["name"].endswith("downsample.0")))
-              for c in net.conv_layers(H, W)]
-    shapes = net.level_shapes(H, W)
-    for i, (h, w) in enumerate(shapes[:4]):
-        layers.append(("fpn_lateral", dict(cin=net.fpn.inner_blocks[i].in_channels, cout=256, k=1, stride=1, H=h, W=w, Hout=h, Wout=w,
-                                           affine=False, residual=False, relu=False, up=shapes[i + 1] if i < 3 else None)))
-        layers.append(("fpn_output", dict(cin=256, cout=256, k=3, stride=1, H=h, W=w, Hout=h, Wout=w, affine=False, residual=False,
-                                          relu=False)))
+    steps = net._plan(net._native if net._native is not None else net.prepare_native(), H, W)["steps"]
     groups = {}
-    for group, c in layers:
+    for st in steps:
+        if not isinstance(st, Launch) or st.kind != "conv":
+            continue
+        c, name = st.layer, st.layer["name"]
+        group = ("stem" if name == "body.conv1" else "fpn_lateral" if name.startswith("fpn.inner_blocks.") else
+                 "fpn_output" if name.startswith("fpn.layer_blocks.") else name.split(".")[1])
         xin = torch.randn((n, c["cin"], c["H"], c["W"]), device=x.device)
         wt = torch.randn((c["cout"], c["cin"], c["k"], c["k"]), device=x.device)
         sh = torch.ones(c["cout"], device=x.device)
-        sc = sh if c["affine"] else None
-        out = torch.empty((n, c["cout"], c["Hout"], c["Wout"]), device=x.device)
-        if c.get("up") is not None:
-            coarse = torch.randn((n, c["cout"]) + tuple(c["up"]), device=x.device)
+        sc = sh if c["scale"] is not None else None
+        out = torch.empty((n,) + c["out_shape"], device=x.device)
+        if st.up is not None:
+            coarse = torch.randn((n, c["cout"]) + tuple(st.up), device=x.device)
             call = lambda: conv2d_affine_up_native(xin, wt, sc, sh, coarse, out=out)
         else:
-            res = torch.randn_like(out) if c["residual"] else None
-            call = lambda: conv2d_affine_native(xin, wt, sc, sh, stride=c["stride"], residual=res, relu=c["relu"], out=out)
+            res = torch.randn_like(out) if st.residual is not None else None
+            call = lambda: conv2d_affine_native(xin, wt, sc, sh, stride=c["stride"], residual=res, relu=st.relu, out=out)
         call()
         ms = statistics.median(timed(call)[0] for _ in range(5))
         g = groups.setdefault(group, {"launches": 0, "ms": 0.0, "gmac": 0.0})

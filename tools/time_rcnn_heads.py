@@ -92,7 +92,7 @@ def one(runs, warmup):
     import numpy as np
     import torch
     from mpntrackseg_amd import rcnn_heads as RH, synth
-    from mpntrackseg_amd.reid_net import conv2d_affine_native
+    from mpntrackseg_amd.conv_affine import conv2d_affine_native
     dev = torch.device("cuda:0")
     heads = RH.RoIHeads().eval()
     synth.make_roi_head_weights(heads, SEED)
